@@ -7,7 +7,10 @@ rank lists) and the merge.  Gallery and queries are resident in HBM before the t
 to the host inside it.  Default workload = BASELINE.json configs[2]: batch 100 latents vs a 100k synthetic gallery.
 The gallery is FIXED at G as N grows (gallery shards across ranks): "scaling": "strong".
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line (--dump-outputs DIR: the last timed
+step's merged rank lists as .npy first).  What else the line can carry and that takes work of its own outside the timed steps (the CPU baseline,
+the back-to-back steps of roofline.alone_on_the_chip, board power, the -ldir exchange of a multi-rank run, the structured workload's score
+statistics) runs with --full only.
 """
 import argparse
 import importlib
@@ -256,9 +259,12 @@ def main():
     ap.add_argument("--tile-share", type=int, default=0)
     ap.add_argument("--bound-cus", type=int, default=-1, help="CUs the bound pass is confined to, the minutiae stage running beside it on the others (-1 = the library's default, 128; 0 = one stream, kernels back to back)")
     ap.add_argument("--s3-tie-order", type=int, default=0, choices=[0, 1, 2], help="option s3_tie_order: 1 = candidate norms that tie in libstdc++'s std::sort order, as the reference binary (lists short of 120 positive similarities go through the any-shape kernel); NOT the headline setting")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--score-stats", action="store_true", help="after the timed region: the share of non-mate pairs with a positive score (always reported for --workload structured)")
-    ap.add_argument("--no-alone", action="store_true", help="skip the extra back-to-back steps after the timed region (roofline.alone_on_the_chip): for profiler runs, whose per-kernel averages they would mix into")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need, outside the timed steps: the CPU baseline, the back-to-back steps "
+                    "(roofline.alone_on_the_chip), board power, the -ldir exchange (more than one rank) and the score statistics of --workload structured")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the merged rank lists of the last timed step to DIR/topk_idx.npy (float64) and DIR/topk_score.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--score-stats", action="store_true", help="after the timed region: the share of non-mate pairs with a positive score (with --full always reported for --workload structured)")
+    ap.add_argument("--no-alone", action="store_true", help="--full without the extra back-to-back steps after the timed region (roofline.alone_on_the_chip): for profiler runs, whose per-kernel averages they would mix into")
     ap.add_argument("--refine-stats", action="store_true", help="adc_variant 9: report what the selection / exact-recomputation kernel did (one extra step after the timed region, in a second context on the test library)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for the rank-list exchange (nccl = RCCL; gloo for tests)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "torch", "cpp"], help="the rank-list exchange step: cpp = the `match` host's own exchange (csrc/rank_exchange.cpp: ONE ncclAllGather of the "
@@ -388,7 +394,7 @@ def main():
         step()
     sync()
     wall["search"] = wall["exchange"] = 0.0
-    power = PowerSampler(m.device_info(gpu).get("pci_bus_id")).start() if rank == 0 else None
+    power = PowerSampler(m.device_info(gpu).get("pci_bus_id")).start() if (rank == 0 and a.full) else None
     t0 = time.perf_counter()
     tm_acc = None
     for _ in range(a.steps):
@@ -398,6 +404,10 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     power_timed = power.stop(elapsed, Q * a.steps) if power is not None else None
+    if rank == 0 and a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "topk_idx.npy"), np.asarray(idx).astype(np.float64))      # gallery indices < 2**53: exact in float64
+        np.save(os.path.join(a.dump_outputs, "topk_score.npy"), np.asarray(sc, np.float32))
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -446,7 +456,7 @@ def main():
     # ---- outside the timed region: the same step with the kernels back to back on one stream, so that the line also carries the bound pass's duration when it
     # has the whole chip (the roofline of the kernel by itself) and the per-stage times without overlap.  Two steps after one warm-up step; rank lists must not change.
     alone = None; power_alone = None
-    if bound_cus > 0 and world == 1 and not a.no_alone:
+    if a.full and bound_cus > 0 and world == 1 and not a.no_alone:
         m.set_option("bound_cus", 0)
         m.search_resident(qh, k=a.k)
         acc = None
@@ -462,7 +472,7 @@ def main():
     # ---- outside the timed region: the OTHER exchange of the path — `match -ldir` writes every score (matcher.cpp:201-204), so each rank contributes its shard's score
     # columns [Q][shard] (padded to the largest shard: 100 x 12 500 x 4 B = 5 MB per rank at 8 ranks) to one all-gather.  Three exchanges after one warm-up. ----
     exchange_ldir = None
-    if use_dist:
+    if use_dist and a.full:
         r_ = m.search_resident(qh, k=a.k, want_scores=True)
         widest = max(hi_ - lo_ for lo_, hi_ in bounds)
         blk = np.full((Q, widest), -1.0, np.float32); blk[:, :hi - lo] = r_["scores"]
@@ -481,7 +491,7 @@ def main():
         sync()
     # ---- outside the timed region: what share of the (latent, non-mate) pairs scores above zero (i.i.d. random templates: none; extracted prints: most) ----
     score_stats = None
-    if world == 1 and (a.workload == "structured" or a.score_stats):
+    if world == 1 and ((a.full and a.workload == "structured") or a.score_stats):
         r_ = m.search_resident(qh, k=a.k, want_scores=True, want_parts=True)
         sc_ = r_["scores"].copy(); pt_ = r_["parts"]
         mate = np.zeros_like(sc_, bool)
@@ -597,8 +607,8 @@ def main():
                                      "exchange_and_merge": {"min": round(float(pr_min[1]), 3), "max": round(float(pr_max[1]), 3)},
                                      "note": "host wall time per rank; a rank that finishes its shard early waits in the exchange for the slowest: min(exchange) is the step's own cost"},
             "exchange_ms_per_step": round(float(pr_min[1]), 3), "exchange_ldir": exchange_ldir,
-            "power": {"timed_schedule": power_timed, "kernels_back_to_back": power_alone,
-                      "what": "board power of rank 0's GPU sampled by a host thread during the timed steps, and during the two back-to-back steps after them (bound_cus 0); joules_per_query = mean watts x wall seconds / queries; null = the box exposes no power reading"},
+            "power": None if not a.full else {"timed_schedule": power_timed, "kernels_back_to_back": power_alone,
+                                              "what": "board power of rank 0's GPU sampled by a host thread during the timed steps, and during the two back-to-back steps after them (bound_cus 0); joules_per_query = mean watts x wall seconds / queries; null = the box exposes no power reading"},
             "ranks": ranks_info,
             "distinct_devices": len({(r_["uuid"] or r_["pci_bus_id"]) for r_ in ranks_info}),
             "shared_gpu": bool(a.share_gpu) or len({(r_["uuid"] or r_["pci_bus_id"]) for r_ in ranks_info}) < world,
@@ -610,7 +620,7 @@ def main():
             "latency_ms_per_query": round(ms_per_step / max(1, Q), 3), "launch_groups_per_step": tm_acc["launch_groups"] // max(1, a.steps),
             "rank1_hits": f"{hits}/{Q}", "setup_s": {"generate": round(t_gen, 1), "upload": round(t_up, 1)},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             cpu = cpu_baseline(cb_bytes, lats, gal, lo)
             try:
                 cpu_model = next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))

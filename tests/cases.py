@@ -47,3 +47,34 @@ def to_orc(orc, ocb, lats, gal):
     hl = [orc.latent(ocb, T.write_latent(L))[0] for L in lats]
     hr = [orc.rolled(T.write_rolled(R))[0] for R in gal]
     return hl, hr
+
+
+# ---- inputs of the checks against the reference's own header, argparser and JSON library (tests/test_oracle.py); their outputs on these
+# inputs are recorded in tests/golden/golden_ref.json by tests/golden/make_golden_ref.py ----
+REF_ARG_LINES = [["-l", "a.dat", "-g", "gal/", "-s", "out/", "-c", "cb.dat"], ["-g", "gal", "-l"], ["-l", "-g", "x"], ["-s", "1", "-s", "2"],
+                 [], ["-ldir", "d", "-l", "f"], ["-c"], ["--c", "x", "-c", "y"]]
+REF_ARG_OPTS = ["-l", "-ldir", "-g", "-s", "-c", "-d"]
+REF_CONFIG_KEYS = ["CodebookPath", "ScorePath", "GalleryTemplateDirectory", "LatentTemplateDirectory", "MinuPath", "Absent"]
+REF_CONFIG_TEXTS = [
+    '{\n\t"CodebookPath": "/home/x/codebook.dat",\n\t"ScorePath": "/home/x/scores",\n\n\t"GalleryTemplateDirectory": "/g",\n'
+    '\t"LatentTemplateDirectory": "/l",\n\t"MinuPath": "None"\n\n}\n',
+    '{"ScorePath":"a b/c",   "CodebookPath" :\n "q\\\\r\\"s" , "Depth": 3, "Flag": true, "GalleryTemplateDirectory": "/g/"}',
+    '{ "LatentTemplateDirectory": "", "ScorePath": "/s/", "Nested": {"CodebookPath": "inner"}, "List": ["x", "y"] }',
+]
+
+
+def ref_lut_descriptors(cb):
+    """37 latent texture descriptors for the S4 look-up table; row 3 is made of exact codewords (zero distances)."""
+    rng = np.random.default_rng(5)
+    des = (rng.standard_normal((37, 96)) * 0.2).astype(np.float32)
+    des[3] = np.concatenate([cb.words[m, (7 * m) % 256] for m in range(16)])
+    return des
+
+
+def ref_rolled_template():
+    """A rolled template of 23 texture points with random PQ codes (and 5 minutiae, so that the writer emits the texture block)."""
+    rng = np.random.default_rng(6)
+    n = 23
+    return T.FPTemplate(minu=[T.MinutiaeTemplate(np.arange(5, dtype=np.int16), np.arange(5, dtype=np.int16), np.zeros(5, np.float32), np.ones((5, 96), np.float32))],
+                        tex=[T.TextureTemplate(rng.integers(0, 45, n).astype(np.int16), rng.integers(0, 47, n).astype(np.int16),
+                                               rng.uniform(-1, 1, n).astype(np.float32), codes=rng.integers(0, 256, (n, 16)).astype(np.uint8))])

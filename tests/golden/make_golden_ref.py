@@ -1,0 +1,53 @@
+#!/usr/bin/env python
+"""Generates tests/golden/golden_ref.json — what the reference's own code returns on the inputs of tests/cases.py (REF_*, ref_*), recorded
+through oracle/_ref/libafis_ref.so (oracle/ref_harness.cpp, built by `make -C oracle ref` where the reference tree is present):
+  * lut_sha256   LatentTextureTemplate::compute_dist_to_codewords (include.h) on ref_lut_descriptors(): sha256 of the [37][16][256] f32 table
+  * pi           the PI constant of include.h
+  * rolled       RolledTextureTemplatePQ on ref_rolled_template()'s texture block: the PQ codes it keeps and the converted points (ori as f32 bits)
+  * args         matching/argparser.h: [exists, value] for every line of REF_ARG_LINES x option of REF_ARG_OPTS
+  * config       main.cpp's config read with the vendored JSON library: [rc, value] for every text of REF_CONFIG_TEXTS x key of REF_CONFIG_KEYS
+tests/test_oracle.py checks the oracle and the `match` CLI against these records, so that it needs no reference tree.
+
+Run from the repo root:  python tests/golden/make_golden_ref.py
+"""
+import hashlib
+import importlib
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cases  # noqa: E402
+from oracle_lib import RefHarness  # noqa: E402
+
+T = importlib.import_module("msu-latentafis_amd.host.templates")
+
+
+def main():
+    ref = RefHarness()
+    with open(os.path.join(ROOT, "tests", "golden", "codebook_EmbeddingSize_96_stride_16_subdim_6.dat"), "rb") as f:
+        cb = T.Codebook.from_bytes(f.read())
+    lut = ref.build_lut(cases.ref_lut_descriptors(cb), cb.words)
+    x = cases.ref_rolled_template().tex[0]
+    codes, xo, yo, oo = ref.rolled_texture(x.x, x.y, x.ori, 16, x.codes.tobytes())
+    args = [[[int(e), v] for e, v in (ref.arg(["match"] + toks, opt) for opt in cases.REF_ARG_OPTS)] for toks in cases.REF_ARG_LINES]
+    config = []
+    with tempfile.TemporaryDirectory() as d:
+        for n, text in enumerate(cases.REF_CONFIG_TEXTS):
+            p = os.path.join(d, f"c{n}.config")
+            with open(p, "w") as f: f.write(text)
+            config.append([list(ref.config_get(p, key)) for key in cases.REF_CONFIG_KEYS])
+    out = {"lut_shape": list(lut.shape), "lut_sha256": hashlib.sha256(lut.tobytes()).hexdigest(), "pi": ref.lib.ref_pi(),
+           "rolled": {"codes": codes.tolist(), "x": xo.tolist(), "y": yo.tolist(), "ori_bits": oo.view(np.uint32).tolist()},
+           "args": args, "config": config}
+    path = os.path.join(ROOT, "tests", "golden", "golden_ref.json")
+    with open(path, "w") as f: f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in out.items()) + "\n}\n")     # one line per record
+    print("wrote", path)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,8 @@
-"""CPU tests of the parity checker itself: oracle vs committed golden vectors, oracle vs the reference's own header
-(oracle/_ref, built from /root/reference/matching/include.h), and the reference's documented edge-case rules."""
+"""CPU tests of the parity checker itself: oracle vs committed golden vectors, oracle vs what the reference's own header, argparser and
+JSON library return (recorded in tests/golden/golden_ref.json by tests/golden/make_golden_ref.py), and the reference's documented edge-case rules."""
 import hashlib
 import importlib
+import json
 import os
 
 import numpy as np
@@ -12,6 +13,13 @@ import cases
 T = importlib.import_module("msu-latentafis_amd.host.templates")
 S = importlib.import_module("msu-latentafis_amd.host.synth")
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_pairs.npz")
+REF_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_ref.json")
+
+
+@pytest.fixture(scope="module")
+def ref_gold():
+    with open(REF_GOLD) as f:
+        return json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -56,45 +64,33 @@ def test_golden_lut_and_rowmax_hashes(gold, oracle, handles):
             k += 1
 
 
-def test_lut_pinned_by_reference_header(oracle, codebook_bytes):
-    """S4: the oracle's LUT equals LatentTextureTemplate::compute_dist_to_codewords compiled from the reference's include.h."""
-    from oracle_lib import RefHarness
-    try:
-        ref = RefHarness()
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref/libafis_ref.so not built (needs /root/reference)")
+def test_lut_pinned_by_reference_header(oracle, codebook_bytes, ref_gold):
+    """S4: the oracle's LUT equals LatentTextureTemplate::compute_dist_to_codewords compiled from the reference's include.h (bit for bit: the sha256 of its table)."""
     cb = T.Codebook.from_bytes(codebook_bytes)
     ocb = oracle.codebook(codebook_bytes)
-    rng = np.random.default_rng(5)
-    des = (rng.standard_normal((37, 96)) * 0.2).astype(np.float32)
-    des[3] = np.concatenate([cb.words[m, (7 * m) % 256] for m in range(16)])     # exact codewords: zero distances
-    a = oracle.build_lut(ocb, des); b = ref.build_lut(des, cb.words)
-    assert a.shape == b.shape == (37, 16, 256)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    des = cases.ref_lut_descriptors(cb)                                             # row 3: exact codewords, zero distances
+    a = oracle.build_lut(ocb, des)
+    assert list(a.shape) == ref_gold["lut_shape"] == [37, 16, 256]
+    assert hashlib.sha256(a.tobytes()).hexdigest() == ref_gold["lut_sha256"]
     assert a[3, 5, 35] == 0.0
-    assert abs(ref.lib.ref_pi() - 3.1415926) == 0.0                               # include.h:22
+    assert ref_gold["pi"] == 3.1415926                                             # include.h:22
 
 
-def test_rolled_code_extraction_pinned_by_reference_header(oracle):
+def test_rolled_code_extraction_pinned_by_reference_header(oracle, ref_gold):
     """T1: the PQ codes the reference keeps are the first n*des_len BYTES of the buffer it read as floats (include.h:401-406)."""
-    from oracle_lib import RefHarness
-    try:
-        ref = RefHarness()
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref/libafis_ref.so not built (needs /root/reference)")
-    rng = np.random.default_rng(6)
-    n = 23
-    t = T.FPTemplate(minu=[T.MinutiaeTemplate(np.arange(5, dtype=np.int16), np.arange(5, dtype=np.int16), np.zeros(5, np.float32), np.ones((5, 96), np.float32))],
-                     tex=[T.TextureTemplate(rng.integers(0, 45, n).astype(np.int16), rng.integers(0, 47, n).astype(np.int16),
-                                            rng.uniform(-1, 1, n).astype(np.float32), codes=rng.integers(0, 256, (n, 16)).astype(np.uint8))])
+    t = cases.ref_rolled_template()
+    n = t.tex[0].n
     buf = T.write_rolled(t)
     h, rc = oracle.rolled(buf)
     assert rc == 0
     x = t.tex[0]
-    codes, xo, yo, oo = ref.rolled_texture(x.x, x.y, x.ori, 16, x.codes.tobytes())
+    r = ref_gold["rolled"]
+    codes, xo, yo = np.array(r["codes"], np.uint8), np.array(r["x"], np.int32), np.array(r["y"], np.int32)
+    oo = np.array(r["ori_bits"], np.uint32).view(np.float32)
+    assert codes.shape == (n, 16) and len(xo) == len(yo) == len(oo) == n
     got = np.ctypeslib.as_array(oracle.lib.orc_rolled_codes(h, 0), shape=(n, 16))
     assert np.array_equal(got, codes) and np.array_equal(codes, x.codes)
-    assert np.array_equal(xo, x.x.astype(np.int32)) and np.array_equal(oo, x.ori)
+    assert np.array_equal(xo, x.x.astype(np.int32)) and np.array_equal(yo, x.y.astype(np.int32)) and np.array_equal(oo, x.ori)
 
 
 def test_table_dist_is_a_correctly_rounded_sqrt(oracle, codebook_bytes):
@@ -167,54 +163,35 @@ def test_pq_encoder_pinned_to_scipy_golden(oracle, codebook_bytes, templates_mod
     assert np.array_equal(cb.encode(g["des"]), g["codes"])
 
 
-def test_cli_token_rules_pinned_by_reference_argparser():
-    """`match`'s flag parsing against the reference's own matching/argparser.h (compiled into oracle/_ref): first occurrence wins,
+def test_cli_token_rules_pinned_by_reference_argparser(ref_gold):
+    """`match`'s flag parsing against the reference's own matching/argparser.h (its answers recorded in golden_ref.json): first occurrence wins,
     a flag at the end of the line exists but has an empty value, a value may look like a flag."""
     import os, subprocess
-    from oracle_lib import RefHarness
-    try:
-        ref = RefHarness()
-        ref.lib.ref_arg
-    except (FileNotFoundError, OSError, AttributeError):
-        pytest.skip("oracle/_ref/libafis_ref.so not built with argparser.h (needs /root/reference)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "msu-latentafis_amd", "csrc", "match_selftest")
     if not os.path.exists(exe):
         subprocess.run(["make", "-s", "-C", os.path.dirname(exe), "match_selftest"], check=True)
-    lines = [["-l", "a.dat", "-g", "gal/", "-s", "out/", "-c", "cb.dat"], ["-g", "gal", "-l"], ["-l", "-g", "x"], ["-s", "1", "-s", "2"],
-             [], ["-ldir", "d", "-l", "f"], ["-c"], ["--c", "x", "-c", "y"]]
-    for toks in lines:
-        for opt in ("-l", "-ldir", "-g", "-s", "-c", "-d"):
-            want = ref.arg(["match"] + toks, opt)
+    assert len(ref_gold["args"]) == len(cases.REF_ARG_LINES)
+    for toks, wants in zip(cases.REF_ARG_LINES, ref_gold["args"]):
+        assert len(wants) == len(cases.REF_ARG_OPTS)
+        for opt, want in zip(cases.REF_ARG_OPTS, wants):
             out = subprocess.run([exe, "-selftest-args", opt] + toks, capture_output=True, text=True, check=True).stdout.rstrip("\n")
             assert out == f"exists={int(want[0])} value={want[1]}", (toks, opt, out, want)
 
 
-def test_config_fallback_pinned_by_reference_json_library(tmp_path):
-    """`../afis.config` as main.cpp:41-44 reads it — with the JSON library vendored in the reference tree — against the flat reader
-    of the `match` CLI: the reference's own key set, escapes in values, extra whitespace, non-string values next to the keys."""
+def test_config_fallback_pinned_by_reference_json_library(tmp_path, ref_gold):
+    """`../afis.config` as main.cpp:41-44 reads it — with the JSON library vendored in the reference tree, its answers recorded in golden_ref.json —
+    against the flat reader of the `match` CLI: the reference's own key set, escapes in values, extra whitespace, non-string values next to the keys."""
     import os, subprocess
-    from oracle_lib import RefHarness
-    try:
-        ref = RefHarness()
-        ref.lib.ref_config_get
-    except (FileNotFoundError, OSError, AttributeError):
-        pytest.skip("oracle/_ref/libafis_ref.so not built with json.hpp (needs /root/reference)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "msu-latentafis_amd", "csrc", "match_selftest")
     if not os.path.exists(exe):
         subprocess.run(["make", "-s", "-C", os.path.dirname(exe), "match_selftest"], check=True)
-    keys = ["CodebookPath", "ScorePath", "GalleryTemplateDirectory", "LatentTemplateDirectory", "MinuPath", "Absent"]
-    texts = [
-        '{\n\t"CodebookPath": "/home/x/codebook.dat",\n\t"ScorePath": "/home/x/scores",\n\n\t"GalleryTemplateDirectory": "/g",\n'
-        '\t"LatentTemplateDirectory": "/l",\n\t"MinuPath": "None"\n\n}\n',
-        '{"ScorePath":"a b/c",   "CodebookPath" :\n "q\\\\r\\"s" , "Depth": 3, "Flag": true, "GalleryTemplateDirectory": "/g/"}',
-        '{ "LatentTemplateDirectory": "", "ScorePath": "/s/", "Nested": {"CodebookPath": "inner"}, "List": ["x", "y"] }',
-    ]
-    for n, text in enumerate(texts):
+    assert len(ref_gold["config"]) == len(cases.REF_CONFIG_TEXTS)
+    for n, (text, wants) in enumerate(zip(cases.REF_CONFIG_TEXTS, ref_gold["config"])):
         f = tmp_path / f"c{n}.config"; f.write_text(text)
-        for key in keys:
-            rc, want = ref.config_get(str(f), key)
+        assert len(wants) == len(cases.REF_CONFIG_KEYS)
+        for key, (rc, want) in zip(cases.REF_CONFIG_KEYS, wants):
             out = subprocess.run([exe, "-selftest-config", str(f), "-key", key], capture_output=True, text=True, check=True).stdout.rstrip("\n")
             if rc == 1:
                 assert out == f"found=1 value={want}", (n, key, out, want)

@@ -16,7 +16,7 @@ d = json.load(open(sys.argv[1])); print(d["value"], d["ms_per_step"], d["stage_m
 PY
 }
 case $MODE in
-  bench)  python bench.py --no-cpu-baseline "$@" > $OUT/$TAG.json 2> $OUT/$TAG.err; line $OUT/$TAG.json ;;
+  bench)  python bench.py --full --no-cpu-baseline "$@" > $OUT/$TAG.json 2> $OUT/$TAG.err; line $OUT/$TAG.json ;;
   sweep)  OPT=$1; VALS=$2; shift 2
           for v in $VALS; do python bench.py --no-cpu-baseline --no-alone $OPT $v "$@" > $OUT/${TAG}_$v.json 2> $OUT/${TAG}_$v.err; echo -n "$OPT $v: "; line $OUT/${TAG}_$v.json; done ;;
   kstats) mkdir -p $OUT/$TAG; cd /tmp; export TMPDIR=/tmp

@@ -8,7 +8,7 @@ TAG=${1:-r05}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 REPO=$PWD
-python bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --bound-cus 0 > $OUT/bench_back_to_back.json 2> $OUT/bench_back_to_back.err
 python bench.py --steps 1 --warmup 0 --no-cpu-baseline --refine-stats > $OUT/bench_refine_stats.json 2> $OUT/bench_refine_stats.err
 # the named off-envelope workload (rolled minutiae clip(N(130, 40), 20, 400), latent U{20..150}): NOT the headline

@@ -6,10 +6,10 @@ TAG=${1:-r06}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 REPO=$PWD
-python bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --bound-cus 0 > $OUT/bench_back_to_back.json 2> $OUT/bench_back_to_back.err
 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --refine-stats > $OUT/bench_refine_stats.json 2> $OUT/bench_refine_stats.err
-for d in 10 0 30; do python bench.py --workload structured --dup $d --steps 3 --warmup 1 --no-cpu-baseline --refine-stats > $OUT/bench_structured_dup$d.json 2> $OUT/bench_structured_dup$d.err; done
+for d in 10 0 30; do python bench.py --workload structured --dup $d --steps 3 --warmup 1 --full --no-cpu-baseline --refine-stats > $OUT/bench_structured_dup$d.json 2> $OUT/bench_structured_dup$d.err; done
 python bench.py --workload wide --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_wide.json 2> $OUT/bench_wide.err
 for g in 12500 25000 50000; do python bench.py --steps 3 --warmup 1 --gallery $g --no-cpu-baseline > $OUT/bench_shard_$g.json 2> $OUT/bench_shard_$g.err; done
 python bench.py --queries 1 --gallery 10000 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/latency_1x10k.json 2> $OUT/latency_1x10k.err
