@@ -231,7 +231,7 @@ int afis_get_timing2(const afis_ctx* ctx, afis_timing* out, size_t struct_size);
  * (adc_mfma.hip, adc_refine.hip); 8 = a 16-bit fixed-point LDS-table pass bounds the candidates, which are then evaluated exactly from an fp32 table in HBM/L2
  * (the north_star's LDS-LUT design; 1.6 x the time of 9).  libafis_hip.so (the product) accepts 9 and 8 only; the direct exact kernels of rounds 1-2 — 7 = conflict-free lane classes, 1024-thread
  * workgroups (2.9 x); 6 = the same with 512; 0 = plain LDS gather, 1 = chain/row-quad rotated lanes, 2/3 = 0/1 with 1024-thread workgroups — are reference kernels built into libafis_hip_test.so only.
- * "mf_blocks" (form of variant 9's bound pass, bit-identical: 2 = two row blocks per wave, the only value of the product library; libafis_hip_test.so also takes 3), "bound_cus" (below), "query_batch" (latents per launch group),
+ * "mf_blocks" (form of variant 9's bound pass: 2 = two row blocks per wave, the only value; the three-row-block form was removed), "bound_cus" (below), "query_batch" (latents per launch group),
  * "chunk" (gallery templates per workgroup), "minu_generic" (force the generic minutiae candidate kernel), "s3_tie_order" (0 [default]: candidate norms that tie — in practice the zero norms that fill a list with fewer
  * than 120 positive similarities — are taken in ascending element order; 1: in the order libstdc++'s std::sort leaves them, i.e. what the reference binary's matcher.cpp:473-476 delivers:
  * such lists — and the rare list in which two positive norms tie — then go through the any-shape candidate kernel, one wave of which runs the sort; about +2 % of a search on structured templates), "ref_tie_order" (0 [default], 1 = "s3_tie_order" 1, 2 = in addition the greedy selections of S8 and S9 — matcher.cpp:1301 / :1423 / :1590 — walk
@@ -253,7 +253,7 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in
- * include/afis_matcher_taps.h and exported only by libafis_hip_test.so (the same objects with afis_api.cpp built -DAFIS_PARITY_TAPS),
+ * include/afis_matcher_taps.h and exported only by libafis_hip_test.so (the product objects plus afis_taps.cpp and adc_direct.hip),
  * which tests/ load.  libafis_hip.so exports exactly the functions declared above. */
 
 #ifdef __cplusplus

@@ -1,5 +1,5 @@
 /* afis_matcher_taps.h — parity-test taps of the MI355X matcher: stage intermediates the tests compare with oracle/ bit for bit.
- * TEST INFRASTRUCTURE: exported by libafis_hip_test.so only (csrc/Makefile: afis_api.cpp with -DAFIS_PARITY_TAPS); the product
+ * TEST INFRASTRUCTURE: exported by libafis_hip_test.so only (csrc/Makefile: the product objects plus afis_taps.cpp and adc_direct.hip); the product
  * library libafis_hip.so (include/afis_matcher.h) does not contain them. */
 #ifndef AFIS_MATCHER_TAPS_H
 #define AFIS_MATCHER_TAPS_H

@@ -1,4 +1,4 @@
-// adc_common.h — small device helpers shared by the ADC translation units (adc.hip: adc_variant 8; adc_direct.hip: the direct kernels, test library only).
+// adc_common.h — small device helpers shared by the ADC translation units (adc.hip: adc_variant 8; adc_direct.hip: the direct kernels, linked into libafis_hip_test.so only).
 #pragma once
 #include "afis_device.h"
 

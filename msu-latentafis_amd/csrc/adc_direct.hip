@@ -1,8 +1,8 @@
 // adc_direct.hip — the DIRECT exact ADC kernels (adc_variant 0-3, 6, 7) and their tile LUT: S4 (per-query PQ look-up table) and S5+S6 (ADC similarity + per-row
 // max / first arg-max) evaluated entry by entry, with no bound pass.  EXPERIMENTAL / reference kernels: rounds 1-2 shipped them; since round 3 the product path is
-// adc_variant 9 (adc_mfma.hip + adc_refine.hip) with adc_variant 8 (adc.hip, the LDS-table design of north_star) as the selectable alternative.  These kernels are built
-// only into libafis_hip_test.so (-DAFIS_EXPERIMENTAL_KERNELS), where the parity tests use them as a second, independent witness of the row maxima.
-//
+// adc_variant 9 (adc_mfma.hip + adc_refine.hip) with adc_variant 8 (adc.hip, the LDS-table design of north_star) as the selectable alternative.  These kernels are linked
+// only into libafis_hip_test.so, whose afis_taps.cpp launches them (the search reaches them through g_direct_adc_stage, afis_ctx.h); the parity tests use them as a second,
+// independent witness of the row maxima.
 //
 // Reference: LatentTextureTemplate::compute_dist_to_codewords (matching/include.h:327-359) and
 // Matcher::One2One_texture_matching method 1 + row arg-max (matching/matcher.cpp:563-595, :723-735).

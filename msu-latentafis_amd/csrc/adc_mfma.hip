@@ -20,12 +20,6 @@
 // the fp16 codebook in LDS (64 KB) straight into MFMA operand layout (another 48 KB of LDS, double buffered); HBM carries 20 bytes per point.
 #include "afis_device.h"
 #include <algorithm>
-#ifndef AFIS_MF_ABLATE
-#define AFIS_MF_ABLATE 0
-#endif
-#ifndef AFIS_MF_PREFETCH
-#define AFIS_MF_PREFETCH 1
-#endif
 
 namespace afis {
 
@@ -71,8 +65,7 @@ __device__ __forceinline__ float med3f(float a, float b, float c) { return __bui
 //   NB = 2: 12 waves, three per SIMD (<= 168 registers), stages of 6 tiles.  Every wave reads every operand tile from LDS itself: 10 KB per tile and wave (6 KB of
 //           A fragments + 4 KB of point terms) for 12 MFMAs — 12 waves x 10 KB = 960 LDS-cycles per tile round against 1152 matrix-pipe cycles per SIMD: the LDS return path
 //           is all but co-critical (with the tracking stubbed out AND the decode skipped the kernel still takes 0.83 of its time: profiles/r04_bound_pass_ablation.json).
-//   NB = 3:  8 waves, two per SIMD (<= 256 registers), stages of 4 tiles: the same 10 KB feed 18 MFMAs (the point terms are shared by the three row blocks), a third less
-//           LDS traffic per MFMA.
+//   NB = 3 (8 waves, two per SIMD, stages of 4 tiles: a third less LDS traffic per MFMA) measured 1 % faster alone on the chip and 2 % slower in the default schedule; removed.
 constexpr int kM12RowBlocks = 24;
 template <int TILES> struct __align__(16) M12Stage {
     uint4 a[TILES][12][32];
@@ -80,29 +73,13 @@ template <int TILES> struct __align__(16) M12Stage {
     int2 meta[TILES];
 };
 
-// The records are written once and read ~100 ms later by the recomputation kernel: 9 GB per launch that no cache can hold.  AFIS_MF_NT_STORE (experiment) marks the stores
-// non-temporal so that they do not displace what the kernels running beside the pass keep in the L2 (the candidate kernel's latent fragments).
-// Measured (tools/lib_ab.py, 20 latents x 100 000, default schedule): 426.6 against 427.3 ms per group, candidates 173.8 against 174.1 — nothing; the candidate kernel beside
-// the pass takes 2.05 x its time alone on the chip, i.e. what half the CUs cost.  Not shipped.
-#ifndef AFIS_MF_NT_STORE
-#define AFIS_MF_NT_STORE 0
-#endif
-__device__ __forceinline__ void store_rec(uint2* p, uint32_t a, uint32_t b)
-{
-#if AFIS_MF_NT_STORE
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    u32x2 v; v.x = a; v.y = b;
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(p));
-#else
-    *p = make_uint2(a, b);
-#endif
-}
-
+// The records are written once and read ~100 ms later by the recomputation kernel: 9 GB per launch that no cache can hold.  Non-temporal stores (so that they do not
+// displace what the kernels beside the pass keep in the L2) measured no different (tools/lib_ab.py, 20 latents x 100 000, default schedule: 426.6 against 427.3 ms per group).
 template <int NB>
 __global__ __launch_bounds__(64 * (kM12RowBlocks / NB)) void k_adc_mfma(GalleryDev g, const uint4* __restrict__ codes_p, const float* __restrict__ nrm_p,
                                                             const int2* __restrict__ tile_meta, const int32_t* __restrict__ tile0, const uint4* __restrict__ cw16,
                                                             const uint4* __restrict__ bfrag, const float4* __restrict__ rowk, int n_rows, int n_rb, int R_pad,
-                                                            int n_rg, int chunk, uint2* __restrict__ rec, unsigned long long* __restrict__ diag, int xcd_map)
+                                                            int n_rg, int chunk, uint2* __restrict__ rec, unsigned long long* __restrict__ diag)
 {
     constexpr int kWaves = kM12RowBlocks / NB, kThreads = 64 * kWaves, kStageTiles = kThreads / 128;
     static_assert(kWaves * NB == kM12RowBlocks && kStageTiles * 128 == kThreads, "row blocks per wave must divide 24, and the threads must decode whole tiles");
@@ -112,8 +89,8 @@ __global__ __launch_bounds__(64 * (kM12RowBlocks / NB)) void k_adc_mfma(GalleryD
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with its own L2: the row groups of ONE gallery chunk go to ONE XCD, one after the other, so that a chunk's codes
     // cross the fabric once per round of row groups instead of once per XCD (the launcher rounds the chunk count up to a multiple of 8; chunks beyond the shard return at once).
-    const int slot = xcd_map ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int rg = slot % n_rg, chunk_id = xcd_map ? (slot / n_rg) * 8 + (int)(blockIdx.x & 7) : slot / n_rg;
+    const int slot = (int)(blockIdx.x >> 3);
+    const int rg = slot % n_rg, chunk_id = (slot / n_rg) * 8 + (int)(blockIdx.x & 7);
     const int t_lo = chunk_id * chunk, t_hi = min(g.G, t_lo + chunk);
     if (t_lo >= t_hi) return;
     const int tile_lo = tile0[t_lo], tile_hi = tile0[t_hi];                // tiles of 32 rolled points; a template owns ceil(n/32) of them
@@ -239,7 +216,7 @@ __global__ __launch_bounds__(64 * (kM12RowBlocks / NB)) void k_adc_mfma(GalleryD
             const uint32_t D = (dp & 0x1fffffu) | ((sw ? 1u : 0u) << 21) | ((in_o ? 1u : 0u) << 22) | (cell << 23) | (((in_o & o_more) ? 1u : 0u) << 20);
             // padding rows of a partial row block store too (their records are never read: R_pad covers them); only a row block beyond the last is skipped
             const int rbm = rb0 + p0 + (paired ? h : 0);
-            if (rbm < n_rb && (paired || h == 0)) store_rec(&rec[(size_t)tmpl * R_pad + (size_t)rbm * 32 + col], f2u(V), D);
+            if (rbm < n_rb && (paired || h == 0)) rec[(size_t)tmpl * R_pad + (size_t)rbm * 32 + col] = make_uint2(f2u(V), D);
         }
         reset();
     };
@@ -254,33 +231,17 @@ __global__ __launch_bounds__(64 * (kM12RowBlocks / NB)) void k_adc_mfma(GalleryD
             // prefetch costs no register; only a stage's first tile still waits for its operands.  (The two forms of rounds 3-4 that broke the chain kept two operand AND two accumulator
             // sets: 236 registers, two waves per SIMD, slower.)
             half8 af[6];
-#if AFIS_MF_PREFETCH
 #pragma unroll
             for (int kk = 0; kk < 6; ++kk) af[kk] = __builtin_bit_cast(half8, st.a[0][2 * kk + h][col]);
-#endif
 #pragma unroll
             for (int j = 0; j < kStageTiles; ++j) {
-#if AFIS_MF_ABLATE == 5 || AFIS_MF_ABLATE == 7          // timing experiments only: the operands are read from LDS once per stage, not per tile
-                const int jr = 0;
-#else
-                const int jr = j;
-#endif
                 floatx16 nrm;
-#if AFIS_MF_ABLATE == 10                                 // timing experiment only (wrong results): the point terms are not read — what delivering the C operand for free could save at most
-#pragma unroll
-                for (int r = 0; r < 16; ++r) nrm[r] = 0.0f;
-#else
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
-                    const float4 v = *reinterpret_cast<const float4*>(&st.nrm[jr][8 * q4 + 4 * h]);
+                    const float4 v = *reinterpret_cast<const float4*>(&st.nrm[j][8 * q4 + 4 * h]);
                     nrm[4 * q4] = v.x; nrm[4 * q4 + 1] = v.y; nrm[4 * q4 + 2] = v.z; nrm[4 * q4 + 3] = v.w;
                 }
-#endif
                 const int2 mv = st.meta[j];
-#if !AFIS_MF_PREFETCH
-#pragma unroll
-                for (int kk = 0; kk < 6; ++kk) af[kk] = __builtin_bit_cast(half8, st.a[jr][2 * kk + h][col]);
-#endif
                 floatx16 X[NB];
 #pragma unroll
                 for (int blk = 0; blk < NB; ++blk) X[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[blk][0], nrm, 0, 0, 0);
@@ -289,72 +250,37 @@ __global__ __launch_bounds__(64 * (kM12RowBlocks / NB)) void k_adc_mfma(GalleryD
 #pragma unroll
                     for (int blk = 0; blk < NB; ++blk) X[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk], bf[blk][kk], X[blk], 0, 0, 0);
                 }
-#if AFIS_MF_PREFETCH
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + 1 < kStageTiles) {
 #pragma unroll
                     for (int kk = 0; kk < 6; ++kk) af[kk] = __builtin_bit_cast(half8, st.a[j + 1][2 * kk + h][col]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 const int my = __builtin_amdgcn_readfirstlane(mv.y);
                 const uint32_t gid = (uint32_t)(2 * (my & 255));
-#if AFIS_MF_ABLATE == 1 || (AFIS_MF_ABLATE >= 4 && AFIS_MF_ABLATE <= 7)          // timing experiments only (wrong results): no tracking
-#pragma unroll
-                for (int blk = 0; blk < NB; ++blk) m[blk][0] = max3f(m[blk][0], X[blk][0], X[blk][15]);
-                (void)gid;
-#elif AFIS_MF_ABLATE == 11                               // timing experiment only (wrong results): the cheapest conceivable packed tracking — 8 conversions to fp16 pairs + 8 v_pk_max_f16 per 16 values, no group tracking
-#pragma unroll
-                for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-                        const half2v pk = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(X[blk][k], X[blk][k + 8]));
-                        const half2v cur = __builtin_bit_cast(half2v, m[blk][k]);
-                        m[blk][k] = __builtin_bit_cast(float, __builtin_elementwise_max(cur, pk));
-                    }
-                (void)gid;
-#else
 #pragma unroll
                 for (int blk = 0; blk < NB; ++blk) track(blk, X[blk], gid);
-#endif
                 if (my & 256) finish_template(__builtin_amdgcn_readfirstlane(mv.x));
             }
         }
-#if AFIS_MF_ABLATE == 3 || (AFIS_MF_ABLATE >= 4 && AFIS_MF_ABLATE <= 7)           // timing experiments only: the stages after the first two are not decoded (stale operands)
-        if (s + 1 < n_stages && s < 1) decode((s + 1) & 1, pf_cur);
-#else
         if (s + 1 < n_stages) decode((s + 1) & 1, pf_cur);
-#endif
         pf_cur = pf_nxt;
-#if AFIS_MF_ABLATE == 6 || AFIS_MF_ABLATE == 7           // timing experiments only: no stage barrier
-        if (s < 1) __syncthreads();
-#else
         __syncthreads();
-#endif
     }
     if (sampler && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) { atomicAdd(&diag[kDiagBoundClk], (unsigned long long)__builtin_readcyclecounter() - clk0); atomicAdd(&diag[kDiagBoundWall], (unsigned long long)wall_clock64() - wall0); }
 }
 
 // ---- launcher ----------------------------------------------------------------------------------------------------------------
 hipError_t launch_adc_mfma(const GalleryDev& g, const void* codes_p, const float* nrm_p, const void* tile_meta, const int32_t* tile0, const void* cw16,
-                           const void* bfrag, const void* rowk, int n_rows, int n_rb, int R_pad, int chunk, int blocks_per_wave, void* rec, unsigned long long* diag, hipStream_t stream)
+                           const void* bfrag, const void* rowk, int n_rows, int n_rb, int R_pad, int chunk, void* rec, unsigned long long* diag, hipStream_t stream)
 {
     if (n_rb <= 0 || g.G <= 0) return hipSuccess;
     const int n_chunks = (g.G + chunk - 1) / chunk;
     const int n_rg = (n_rb + kM12RowBlocks - 1) / kM12RowBlocks;
-    static const bool xcd_map = AFIS_EXPERIMENT_ENV("AFIS_MF_NO_XCD_MAP") == nullptr;       // experiment knob: round-robin chunks as in rounds 3-4
-    const long long blocks = (long long)n_rg * (xcd_map ? (n_chunks + 7) / 8 * 8 : n_chunks);
+    const long long blocks = (long long)n_rg * ((n_chunks + 7) / 8 * 8);         // every XCD gets its own chunks (see the kernel)
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#ifdef AFIS_EXPERIMENTAL_KERNELS                                          // three row blocks per wave (8 waves, 224 registers): -1 % alone on the chip, +2 % in the default schedule; test library only
-    if (blocks_per_wave == 3) {
-        hipLaunchKernelGGL(k_adc_mfma<3>, dim3((unsigned)blocks), dim3(64 * (kM12RowBlocks / 3)), 0, stream, g, (const uint4*)codes_p, nrm_p, (const int2*)tile_meta, tile0,
-                           (const uint4*)cw16, (const uint4*)bfrag, (const float4*)rowk, n_rows, n_rb, R_pad, n_rg, chunk, (uint2*)rec, diag, xcd_map ? 1 : 0);
-        return hipGetLastError();
-    }
-#endif
     hipLaunchKernelGGL(k_adc_mfma<2>, dim3((unsigned)blocks), dim3(64 * (kM12RowBlocks / 2)), 0, stream, g, (const uint4*)codes_p, nrm_p, (const int2*)tile_meta, tile0,
-                           (const uint4*)cw16, (const uint4*)bfrag, (const float4*)rowk, n_rows, n_rb, R_pad, n_rg, chunk, (uint2*)rec, diag, xcd_map ? 1 : 0);
+                           (const uint4*)cw16, (const uint4*)bfrag, (const float4*)rowk, n_rows, n_rb, R_pad, n_rg, chunk, (uint2*)rec, diag);
     return hipGetLastError();
 }
 

@@ -93,7 +93,7 @@ void afis_destroy(afis_ctx* c)
     static const bool trace = getenv("AFIS_DESTROY_TRACE") != nullptr;       // development aid: where a destroy spends its time, on stderr
     auto lap = [&](const char* what) { if (trace) { fprintf(stderr, "afis_destroy: %s\n", what); fflush(stderr); } };
     // the side streams first, the context's stream last: work on the context's stream may wait for events of the side streams, and a blocking wait on it alone has been seen
-    // not to return while they had not been waited for themselves (tools/repro/README.md)
+    // not to return while they had not been waited for themselves (profiles/r05_side_stream_waits.json)
     lap("waiting for the side streams");
     for (hipStream_t* ps : {&c->stream_lo, &c->stream_hi}) if (*ps) (void)hipStreamSynchronize(*ps);
     lap("waiting for the context's stream");
@@ -158,7 +158,7 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "bound_cus") *value = (ctx->stream_lo && !ctx->overlap_failed) ? ctx->bound_cus : 0;
     else if (n == "search_timeout_s") *value = ctx->search_timeout_s <= 0 ? 0 : (int64_t)std::ceil(ctx->search_timeout_s);     // rounded up: a bound set in milliseconds must not read back as 0 = "unbounded"
     else if (n == "search_timeout_ms") *value = ctx->search_timeout_s <= 0 ? 0 : (int64_t)std::llround(ctx->search_timeout_s * 1e3);
-    else if (n == "mf_blocks") *value = ctx->mf_blocks;
+    else if (n == "mf_blocks") *value = 2;
     else if (n == "query_batch") *value = ctx->query_batch;
     else if (n == "chunk") *value = ctx->chunk;
     else if (n == "tile_share") *value = ctx->tile_share;
@@ -180,12 +180,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value)
     if (!ctx || !name) return AFIS_EINVAL;
     const std::string n(name);
     if (n == "adc_variant") {
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-        if (value < 0 || value > 9 || value == 4 || value == 5) return fail(ctx, AFIS_EINVAL, "adc_variant must be 0..3, 6, 7, 8 or 9");
-#else
-        if (value != 8 && value != 9) return fail(ctx, AFIS_EINVAL, "adc_variant must be 9 (matrix-core bound pass + exact values) or 8 (16-bit LDS-table bound pass + exact values); the direct kernels 0..3, 6, 7 "
-                                                                     "are reference kernels built into libafis_hip_test.so only");
-#endif
+        if (value < 0 || value > 9 || value == 4 || value == 5 || (value < 8 && !g_direct_adc_stage))
+            return fail(ctx, AFIS_EINVAL, "adc_variant must be 9 (matrix-core bound pass + exact values) or 8 (16-bit LDS-table bound pass + exact values); the direct kernels 0..3, 6, 7 "
+                                          "are reference kernels built into libafis_hip_test.so only");
         ctx->adc_variant = (int)value;
     }
     else if (n == "lut_dtype") { if (value != 32) return fail(ctx, AFIS_EINVAL, "lut_dtype: only 32 (exact) exists; the 16-bit tolerance path of rounds 1-2 missed its stated tolerance and was removed (the reduced-precision pass of BASELINE.json configs[4] is adc_variant 9 / 8: a bound, followed by exact values)"); }
@@ -208,8 +205,8 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value)
         ctx->overlap_failed = false;
         if (value > 0) {
             uint32_t lo[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hi[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the runtime deals the mask's bits round-robin over the XCDs: the low N bits are N / 8 CUs of each
-            const bool whole_xcds = AFIS_EXPERIMENT_ENV("AFIS_BOUND_WHOLE_XCDS") != nullptr;   // experiment: value / 32 WHOLE XCDs for the bound pass instead of value / 8 CUs of each — measured: the pass takes 287 ms per group on 4 whole XCDs against 235 on 16 CUs of each of the 8 (the power limit acts per XCD); the step falls back to the back-to-back time
-            for (int b = 0; b < std::min(256, ctx->n_cus); ++b) ((whole_xcds ? (b & 7) < (int)value / 32 : b < (int)value) ? lo : hi)[b >> 5] |= 1u << (b & 31);
+            // (value / 32 WHOLE XCDs instead measured slower: the pass takes 287 ms per group on 4 whole XCDs against 235 on 16 CUs of each of the 8 — the power limit acts per XCD; profiles/r04_whole_xcd_mask.txt)
+            for (int b = 0; b < std::min(256, ctx->n_cus); ++b) (b < (int)value ? lo : hi)[b >> 5] |= 1u << (b & 31);
             hipError_t e = hipExtStreamCreateWithCUMask(&ctx->stream_lo, 8, lo);
             if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&ctx->stream_hi, 8, hi);
             if (e != hipSuccess) {
@@ -219,14 +216,7 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value)
             }
         }
     }
-    else if (n == "mf_blocks") {
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-        if (value != 2 && value != 3) return fail(ctx, AFIS_EINVAL, "mf_blocks must be 2 or 3 (row blocks per wave of the bound pass)");
-#else
-        if (value != 2) return fail(ctx, AFIS_EINVAL, "mf_blocks must be 2 (the three-row-block form of the bound pass is built into libafis_hip_test.so only; it measured 1 % faster alone and 2 % slower in the default schedule)");
-#endif
-        ctx->mf_blocks = (int)value;
-    }
+    else if (n == "mf_blocks") { if (value != 2) return fail(ctx, AFIS_EINVAL, "mf_blocks must be 2 (row blocks per wave of the bound pass; the three-row-block form measured 2 % slower in the default schedule and was removed)"); }
     else if (n == "rowmax_budget_mb") { if (value < 1) return fail(ctx, AFIS_EINVAL, "rowmax_budget_mb must be positive"); ctx->rowmax_budget_bytes = value << 20; }
     else return fail(ctx, AFIS_EINVAL, "unknown option: " + n);
     return AFIS_OK;

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode) and afis_taps.cpp (parity taps, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -89,8 +89,7 @@ struct afis_ctx {
     int64_t index_base = 0;
     GalleryDev gal;
     DevBuf g_minu_off, g_minu_xy, g_minu_ori, g_minu_des, g_minu_frag, g_minu_tile_off, g_tex_off, g_tex_xy, g_tex_ori, g_tex_codes, g_tex_codes_cf, g_tex_cf_blk, g_tex_codes_q, g_tex_q_blk, g_tex_t32_blk, g_empty, g_task_ctr;
-    bool codes_cf_built = false;         // variants 6 / 7: their lane-ordered code stream, laid out on first use
-    int64_t cf_blocks = 0;
+    bool codes_cf_built = false;         // variants 6 / 7 (test library): their lane-ordered code stream and its block offsets, laid out on first use
     bool codes_q_built = false;          // adc_variant 8's lane-ordered code stream is laid out on first use
     int64_t q_blocks = 0;
     int64_t t32_tiles = 0;               // tiles of 32 rolled texture points (ceil(n/32) per template): the matrix-core bound pass's stream
@@ -102,14 +101,13 @@ struct afis_ctx {
     DevBuf mf_cw16, mf_cwn, g_codes_p, g_nrm_p, g_tile_meta, mf_bfrag, mf_rowk, mf_rec, mf_stats;
     bool mf_cb_built = false, mf_gal_built = false;
     int mf_collect_stats = 0;
-    int mf_blocks = 2;                   // row blocks per wave of the bound pass: 2 (12 waves per workgroup) or 3 (8 waves, a third less LDS traffic per MFMA)
     DevBuf lutq, lutq_min, lutq_rng, lutq_rowc, lut32;      // adc_variant 8: 16-row fixed-point tiles, per-(row, m) min / range, per-row (offset, step, margin), fp32 table
     DevBuf lut, rm_val, rm_arg, rm_cv, rm_n, parts, scores, scratch, cands, cand_n, minu_fb, topk_idx, topk_score;
     DevBuf diag;                         // kDiagWords unsigned 64-bit counters per launch group of a search (afis_device.h): zeroed when the search starts, read back with its results
     std::vector<unsigned long long> h_diag;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;   // pinned host buffer for what a search reads back inside its wait (rank lists, diagnostics)
     std::vector<float> h_scores, h_parts;
-    int adc_variant = 9;                 // 9: fp16 matrix-core bound pass + exact recomputation (default); 8: 16-bit LDS-table bound pass + exact refine; 7: direct exact kernel; 0-3, 6: earlier direct kernels
+    int adc_variant = 9;                 // 9: fp16 matrix-core bound pass + exact recomputation (default); 8: 16-bit LDS-table bound pass + exact refine; 7: direct exact kernel; 0-3, 6: earlier direct kernels (0-3, 6, 7: test library only)
     int tile_share = 0;                  // adc_variant 8: consecutive chunks per tile on an XCD; 0 = 4 (the refine's fp32 table stays in L2)
     int query_batch = 0;                 // latents per launch group at most; 0 = by shard size (afis_queries_upload); adc_variant 9 places the cuts by latent texture rows
     int chunk = 0;                       // gallery templates per ADC workgroup; 0 = by gallery size
@@ -202,9 +200,11 @@ int adc_stage_q(afis_ctx* ctx, QueryGroup& grp, int chunk, bool exact, hipEvent_
 int adc_refine_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, bool compact);
 int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t after_lut = nullptr, hipEvent_t after_bound = nullptr, bool compact = false, hipStream_t sb = nullptr,
                    bool refine_now = true, unsigned long long* diag = nullptr);
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-int ensure_codes_cf(afis_ctx* ctx, int variant);       // the direct kernels' lane-ordered code stream (adc_variant 6 / 7), laid out at first use
-#endif
+// S4-S6 of the direct exact ADC kernels (adc_direct.hip, adc_variant 0-3, 6, 7) for one query group against the resident shard, on the context's stream, into
+// rm_val / rm_arg (sized by the caller); after_lut is recorded between the table and the row maxima.  Set by afis_taps.cpp, so only libafis_hip_test.so has it:
+// null in libafis_hip.so, which rejects those variants.  Hidden: with both libraries in one process, neither may bind to the other's copy.
+typedef int (*DirectAdcStage)(afis_ctx* ctx, const QueryDev& d, int chunk, hipEvent_t after_lut);
+extern DirectAdcStage g_direct_adc_stage __attribute__((visibility("hidden")));
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what);
 void register_context(afis_ctx* ctx); void unregister_context(afis_ctx* ctx);   // the process-wide list group_budget_bytes consults
 int drain_abandoned(afis_ctx* ctx);                     // waits (bounded) for a search that returned at its deadline

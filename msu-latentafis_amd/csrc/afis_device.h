@@ -4,15 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Experiment knobs (environment variables that re-create an earlier round's schedule, or skip work for a timing-only run) exist in libafis_hip_test.so only
-// (-DAFIS_EXPERIMENTAL_KERNELS): the product library does not read them, and their names do not occur in it (tests/test_host.py compares `strings libafis_hip.so`
-// with the table of operational variables in INTEGRATION.md section E).
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-#define AFIS_EXPERIMENT_ENV(name) (getenv(name))
-#else
-#define AFIS_EXPERIMENT_ENV(name) (static_cast<const char*>(nullptr))
-#endif
-
 namespace afis {
 
 constexpr int kM = 16;            // PQ sub-quantizers         (codebook header, matcher.cpp:74)
@@ -42,8 +33,8 @@ struct GalleryDev {
     const float*   tex_ori = nullptr;    // [NT]
     const uint4*   tex_codes = nullptr;  // [NT]   16 PQ code bytes per point, byte m = sub-quantizer m
     const uint4*   tex_codes_cf = nullptr;  // the same bytes as a per-template stream of (blocks + 1) x 64 lane entries, permuted per
-                                            // lane class and half-period shifted for the conflict-free ADC kernel (adc.hip)
-    const int32_t* tex_cf_blk = nullptr;    // [G+1] offset of each template's stream in tex_codes_cf, in 64-entry blocks
+                                            // lane class and half-period shifted for the conflict-free direct ADC kernel (adc_direct.hip)
+    const int32_t* tex_cf_blk = nullptr;    // [G+1] offset of each template's stream in tex_codes_cf, in 64-entry blocks (both laid out at the first use of that kernel)
     const uint8_t* empty = nullptr;      // [G] 1 = rolled template has neither minutiae nor texture (score -1)
     int32_t* task_ctr = nullptr;         // [4] next-task counters of the graph kernels (texture, minutiae), the refine kernel and the candidate kernel: zeroed by their launchers
 };
@@ -106,16 +97,17 @@ __device__ __forceinline__ float lut_entry(const float* __restrict__ des6, const
 }
 #endif
 
+// The direct exact ADC kernels (adc_direct.hip, adc_variant 0-3, 6, 7; linked into libafis_hip_test.so only).  S4: the tile LUT of kTileRows rows.
 hipError_t launch_lut_build(const QueryDev& q, const float* codewords, float* lut_tiles, int variant, hipStream_t stream);
 // S5+S6: ADC similarity + per-row (max, first argmax) for queries [q0, q0+nq) against gallery templates.
 hipError_t launch_adc_rowmax(const QueryDev& q, const GalleryDev& g, const float* lut_tiles, int chunk, int variant,
                              float* rm_val, int32_t* rm_arg, hipStream_t stream);
+// the conflict-free kernel's lane-ordered code stream (variants 6 / 7): g.tex_cf_blk = its block offsets
+hipError_t launch_codes_cf(const GalleryDev& g, void* out, hipStream_t stream);
 // adc_variant 8 (adc.hip): 16-bit fixed-point LUT tiles of 16 rows + per-row (offset, step, margin); the lane-ordered code stream it reads
 // (ceil(n/64) blocks per template, first block q_blk[t]); S5+S6 with integer sums as a bound pass.
 hipError_t launch_lutq_build(const QueryDev& q, int n_rows_total, const float* codewords, float* row_min, float* row_rng, void* tiles, void* rowc, hipStream_t stream);
 hipError_t launch_codes_q(const GalleryDev& g, const int32_t* q_blk, void* out, hipStream_t stream);
-// the direct conflict-free kernel's lane-ordered code stream (variants 6 / 7), laid out on the device at first use (g.tex_cf_blk = its block offsets)
-hipError_t launch_codes_cf(const GalleryDev& g, void* out, hipStream_t stream);
 // lut32 != NULL (adc_variant 8): the quantised pass only bounds the candidates, which are then evaluated exactly from the fp32 table in the
 // reference layout [row][16][256] (launch_lut_reference_layout over all latent texture rows of the group): exact results, bit for bit.
 hipError_t launch_adc_rowmax_q(const QueryDev& q, const GalleryDev& g, const void* codes_q, const int32_t* q_blk, const void* lutq_tiles, const void* rowc,
@@ -130,7 +122,7 @@ hipError_t launch_mf_codebook(const float* codewords, void* cw16, float* cwn, hi
 hipError_t launch_mf_tiles(const GalleryDev& g, const int32_t* t32_blk, const float* cwn, void* codes_p, float* nrm_p, void* tile_meta, hipStream_t stream);
 hipError_t launch_mf_rows(const float* lt_des, int n_rows, int n_rb, const float* codewords, const float* cwn, void* bfrag, void* rowk, hipStream_t stream);
 hipError_t launch_adc_mfma(const GalleryDev& g, const void* codes_p, const float* nrm_p, const void* tile_meta, const int32_t* tile0, const void* cw16,
-                           const void* bfrag, const void* rowk, int n_rows, int n_rb, int R_pad, int chunk, int blocks_per_wave, void* rec,
+                           const void* bfrag, const void* rowk, int n_rows, int n_rb, int R_pad, int chunk, void* rec,
                            unsigned long long* diag /* NULL or a diagnostics row: clock samples */, hipStream_t stream);
 hipError_t launch_tex_refine(const QueryDev& q, const GalleryDev& g, const float* codewords, const void* rec, const void* rowk, int R_pad, int all_rows,
                              float* rm_val, int32_t* rm_arg, unsigned long long* stats, float* rm_cv, int32_t* rm_n, hipStream_t stream);

@@ -462,18 +462,6 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     HIPCHK(ctx, upload_bulk(pp, ctx->g_tex_codes, s_tcodes, NT * kM, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     lap("texture codes");
-    {   // block offsets of the direct conflict-free kernel's code stream (variants 6 / 7): (blocks + 1) x 64 entries per template.  The stream
-        // itself — a full copy of the PQ codes — is laid out on the device at the first use of those variants (k_codes_cf); the default path
-        // never builds it.
-        std::vector<int32_t> cfb(G + 1);
-        int64_t nblk = 0;
-        for (int64_t t = 0; t < G; ++t) { cfb[t] = (int32_t)nblk; const int64_t n = (int64_t)(to[t + 1] - to[t]); nblk += n > 0 ? (n + 63) / 64 + 1 : 0; }
-        cfb[G] = (int32_t)nblk;
-        if (nblk > 0x7fffffff / 64) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: shard too large for the ADC code stream; split the gallery into more shards");
-        ctx->cf_blocks = nblk; ctx->codes_cf_built = false;
-        HIPCHK(ctx, upload(ctx->g_tex_cf_blk, cfb, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
     {   // block offsets of the quantised path's code stream (ceil(n/64) blocks per template); the stream itself is made on first use
         std::vector<int32_t> qb(G + 1);
         int64_t nb = 0;
@@ -498,7 +486,7 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     g.G = (int32_t)G;
     g.minu_off = ctx->g_minu_off.as<int32_t>(); g.minu_xy = ctx->g_minu_xy.as<short2>(); g.minu_ori = ctx->g_minu_ori.as<float>();
     g.minu_des = ctx->g_minu_des.as<float>(); g.minu_frag = ctx->g_minu_frag.as<float4>(); g.minu_tile_off = ctx->g_minu_tile_off.as<int32_t>(); g.tex_off = ctx->g_tex_off.as<int32_t>(); g.tex_xy = ctx->g_tex_xy.as<short2>();
-    g.tex_ori = ctx->g_tex_ori.as<float>(); g.tex_codes = ctx->g_tex_codes.as<uint4>(); g.tex_codes_cf = nullptr; g.tex_cf_blk = ctx->g_tex_cf_blk.as<int32_t>(); g.empty = ctx->g_empty.as<uint8_t>();
+    g.tex_ori = ctx->g_tex_ori.as<float>(); g.tex_codes = ctx->g_tex_codes.as<uint4>(); g.tex_codes_cf = nullptr; g.tex_cf_blk = nullptr; g.empty = ctx->g_empty.as<uint8_t>();
     g.task_ctr = ctx->g_task_ctr.as<int32_t>();
     ctx->max_nR = max_nR;
     ctx->total_tex_points = (int64_t)NT; ctx->total_minutiae = (int64_t)NM;

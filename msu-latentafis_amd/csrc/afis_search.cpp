@@ -52,15 +52,13 @@ int64_t group_budget_bytes(const afis_ctx* ctx)
 
 // Host wait for streams with a deadline: hipStreamQuery on each of them in turn (which also keeps every one of them submitting: with ROCm 7.2 a blocking hipStreamSynchronize
 // of the context's stream ALONE was seen not to return while work it depended on sat on the CU-masked side streams — round 4; round 5 saw it once more, in afis_destroy after an
-// early return; tools/repro/README.md), a yield between rounds
+// early return, and could not reproduce it otherwise: profiles/r05_side_stream_waits.json, r05_side_stream_repro_first_form.txt), a yield between rounds
 // and a short sleep once the wait is long.  A device that does not come back within search_timeout_s is reported as AFIS_EDEVICE instead of holding the caller's
 // thread for ever; when that happens with side streams in use, the context stops using them (bound_cus off: one stream, the kernels back to back).
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what)
 {
     if (ctx->search_timeout_s <= 0) {                                      // unbounded: every stream of the list in turn (the side streams come first)
-        static const bool last_only = AFIS_EXPERIMENT_ENV("AFIS_WAIT_CTX_SYNC_ONLY") != nullptr;     // experiment (tools/repro/README.md): round 4's hanging form, a blocking wait on the context's stream alone
-        hipStream_t last = nullptr; for (hipStream_t st : streams) last = st;
-        for (hipStream_t st : streams) if (st && (!last_only || st == last)) HIPCHK(ctx, hipStreamSynchronize(st));
+        for (hipStream_t st : streams) if (st) HIPCHK(ctx, hipStreamSynchronize(st));
         return AFIS_OK;
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -73,7 +71,7 @@ int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, cons
             else if (e != hipSuccess) return fail(ctx, AFIS_EDEVICE, std::string(what) + ": hipStreamQuery: " + hipGetErrorString(e));
         }
         if (all) return AFIS_OK;
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > ctx->search_timeout_s) {     // (looked at every round: hipStreamQuery itself returns in microseconds — tools/repro/side_stream_hang.hip, mode 5)
+        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > ctx->search_timeout_s) {     // (looked at every round: hipStreamQuery itself returns in microseconds)
             if (streams.size() > 1) ctx->overlap_failed = true;
             ctx->search_abandoned = true;
             char msg[256];
@@ -265,22 +263,11 @@ void afis_queries_free(afis_ctx* ctx, afis_queries* q)
     delete q;
 }
 
-// variants 6 / 7 read the gallery's codes from their own lane-ordered stream: lay it out now if this is their first use
 }  // extern "C"
 
 namespace afis {
 
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-int ensure_codes_cf(afis_ctx* ctx, int variant)
-{
-    if ((variant != 6 && variant != 7) || ctx->codes_cf_built) return AFIS_OK;
-    HIPCHK(ctx, ctx->g_tex_codes_cf.ensure(std::max<size_t>((size_t)ctx->cf_blocks * 64 * 16, 16)));
-    ctx->gal.tex_codes_cf = ctx->g_tex_codes_cf.as<uint4>();
-    HIPCHK(ctx, launch_codes_cf(ctx->gal, ctx->g_tex_codes_cf.p, ctx->stream));
-    ctx->codes_cf_built = true;
-    return AFIS_OK;
-}
-#endif
+DirectAdcStage g_direct_adc_stage = nullptr;
 
 static int tile_share_of(const afis_ctx* ctx) { return ctx->tile_share > 0 ? ctx->tile_share : 4; }
 
@@ -360,7 +347,7 @@ int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t aft
     const long long want_chunks = (std::max<long long>(1, (256 * 24) / n_rg) + 7) / 8 * 8;   // a multiple of 8: the kernel gives every XCD its own chunks (adc_mfma.hip), an uneven count would leave XCDs idle at the end
     const int chunk = ctx->chunk > 0 ? ctx->chunk : (int)std::max<long long>(8, ((long long)g.G + want_chunks - 1) / want_chunks);
     HIPCHK(ctx, launch_adc_mfma(g, ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, ctx->g_tex_t32_blk.as<int32_t>(), ctx->mf_cw16.p,
-                                ctx->mf_bfrag.p, ctx->mf_rowk.p, n_rows, n_rb, R_pad, chunk, ctx->mf_blocks, ctx->mf_rec.p, diag, s));
+                                ctx->mf_bfrag.p, ctx->mf_rowk.p, n_rows, n_rb, R_pad, chunk, ctx->mf_rec.p, diag, s));
     if (after_bound) HIPCHK(ctx, hipEventRecord(after_bound, s));
     return refine_now ? adc_refine_mfma(ctx, grp, all_rows, compact) : AFIS_OK;
 }
@@ -368,8 +355,6 @@ int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t aft
 int adc_refine_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, bool compact)
 {
     if (grp.n_lt_rows <= 0 || ctx->gal.G <= 0) return AFIS_OK;
-    static const bool skip = AFIS_EXPERIMENT_ENV("AFIS_ABLATE_SKIP_TEXTURE_TAIL") != nullptr;    // timing experiments with ablated bound-pass builds (tools/r05_run10.sh): their records are garbage, the kernels behind the pass must not read them
-    if (skip) return AFIS_OK;
     const int R_pad = (grp.n_lt_rows + 31) / 32 * 32;
     HIPCHK(ctx, launch_tex_refine(grp.dev, ctx->gal, ctx->codewords.as<float>(), ctx->mf_rec.p, ctx->mf_rowk.p, R_pad, all_rows ? 1 : 0, ctx->rm_val.as<float>(),
                                   ctx->rm_arg.as<int32_t>(), ctx->mf_collect_stats ? ctx->mf_stats.as<unsigned long long>() : nullptr,
@@ -500,7 +485,6 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     size_t gi = 0;
     SideStreamGuard side_guard(ctx);
     bool any_overlap = false;
-    static const bool skip_tex_tail = AFIS_EXPERIMENT_ENV("AFIS_ABLATE_SKIP_TEXTURE_TAIL") != nullptr;   // timing experiments only (see adc_refine_mfma)
     for (QueryGroup& grp : q->groups) {
         const QueryDev& d = grp.dev;
         const int nq = grp.nq;
@@ -508,9 +492,6 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
         unsigned long long* const diag_row = ctx->diag.as<unsigned long long>() + gi * kDiagWords;
         if (G > 0) {
             const size_t n_pairs = (size_t)nq * G;
-#ifdef AFIS_EXPERIMENTAL_KERNELS
-            if (ctx->adc_variant < 8) HIPCHK(ctx, ctx->lut.ensure(std::max<size_t>((size_t)d.n_tiles * kTileFloats * 4, 16)));   // tile LUT of the direct kernels only
-#endif
             const size_t lt_cap = (size_t)d.lt_pad;                          // (already large enough: the top of the search sized them for its largest group)
             if (ctx->adc_variant != 9) HIPCHK(ctx, ctx->rm_val.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
             HIPCHK(ctx, ctx->rm_arg.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
@@ -575,7 +556,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 rc9 = adc_refine_mfma(ctx, grp, false, true);
                 if (rc9 != AFIS_OK) return rc9;
                 HIPCHK(ctx, hipEventRecord(ev[2], s));
-                if (!skip_tex_tail) HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
+                HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
                 HIPCHK(ctx, hipEventRecord(ev[3], s));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[7], 0));                              // every candidate list exists: help with whatever lists are left
                 HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s, true));
@@ -583,9 +564,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 // No host wait here: the groups of a search follow one another on the three streams through events alone, and the search's final wait polls ALL THREE streams
                 // (wait_streams).  Round 4 blocked on the two side streams after every group because hipStreamSynchronize of the context's stream alone never returned with
                 // ROCm 7.2 while work it depends on sat on the CU-masked side streams; a hipStreamQuery loop does return (profiles/r05_side_stream_waits.json: 46.11 / 46.09 / 46.03
-                // queries/s without the group wait polling one stream / all three / with the group wait), and it is bounded.  AFIS_GROUP_WAIT=1 restores the per-group wait.
-                static const bool group_wait = AFIS_EXPERIMENT_ENV("AFIS_GROUP_WAIT") != nullptr;
-                if (group_wait) { const int rcw = wait_streams(ctx, {sl, sh}, "afis_search: side streams of a launch group"); side_guard.disarm(); if (rcw != AFIS_OK) return rcw; }
+                // queries/s without the group wait polling one stream / all three / with the group wait), and it is bounded.
                 any_overlap = true;
             } else {
             if (ctx->adc_variant == 9) {                                    // fp16 matrix-core bound pass + exact recomputation
@@ -594,18 +573,12 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             } else if (ctx->adc_variant == 8) {                             // 16-bit fixed-point LDS-table bound pass + exact refine
                 int rc16 = adc_stage_q(ctx, grp, chunk, true, ev[1]);
                 if (rc16 != AFIS_OK) return rc16;
-            } else {
-#ifdef AFIS_EXPERIMENTAL_KERNELS                                              // the direct exact kernels (adc_direct.hip): test library only
-                { int rcf = ensure_codes_cf(ctx, ctx->adc_variant); if (rcf != AFIS_OK) return rcf; }
-                HIPCHK(ctx, launch_lut_build(d, ctx->codewords.as<float>(), ctx->lut.as<float>(), ctx->adc_variant, s));
-                HIPCHK(ctx, hipEventRecord(ev[1], s));
-                HIPCHK(ctx, launch_adc_rowmax(d, g, ctx->lut.as<float>(), chunk, ctx->adc_variant, ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), s));
-#else
-                return fail(ctx, AFIS_EINVAL, "adc_variant: the direct kernels are not part of this library");
-#endif
+            } else {                                                        // the direct exact kernels (afis_set_option admits them only where the hook is set)
+                int rcd = g_direct_adc_stage(ctx, d, chunk, ev[1]);
+                if (rcd != AFIS_OK) return rcd;
             }
             HIPCHK(ctx, hipEventRecord(ev[2], s));
-            if (!skip_tex_tail) HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), compact9 ? ctx->rm_cv.as<float>() : nullptr,
+            HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), compact9 ? ctx->rm_cv.as<float>() : nullptr,
                                              compact9 ? ctx->rm_n.as<int32_t>() : nullptr, grp_parts, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
             HIPCHK(ctx, hipEventRecord(ev[3], s));
             { int rcm = minutiae_stage(); if (rcm != AFIS_OK) return rcm; }
@@ -636,7 +609,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     }
     // What comes back inside the wait goes through a PINNED buffer of the context (rank lists, diagnostics: a few KB): an "asynchronous" copy into pageable host memory — the caller's
     // arrays, a std::vector — makes the runtime wait for the stream inside the call, which is where a search used to spend its two seconds before the deadline below was ever looked at
-    // (tools/repro/timeout_recovery.py).  The caller's arrays are filled from it after the wait; the score matrix (-ldir: 40 MB at 100 x 100k) is copied after the wait as well.
+    // (profiles/r05_deadline_recovery.log).  The caller's arrays are filled from it after the wait; the score matrix (-ldir: 40 MB at 100 x 100k) is copied after the wait as well.
     const size_t pin_topk = dev_topk ? (size_t)nq_all * k * 12 : 0, pin_diag = std::max<size_t>(n_groups, 1) * kDiagWords * 8;
     if (ctx->h_pin_bytes < pin_topk + pin_diag) {
         if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
@@ -721,7 +694,7 @@ int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const i
         for (int i = 0; i < n && err == AFIS_OK; ++i) {
             const int64_t gi = gallery_idx[i] - ctx->index_base;
             GalleryDev one = g;                                            // a one-template view: offsets are absolute, so only the CSR bases move
-            one.G = 1; one.minu_off += gi; one.minu_tile_off += gi; one.tex_off += gi; one.tex_cf_blk += gi; one.empty += gi;
+            one.G = 1; one.minu_off += gi; one.minu_tile_off += gi; one.tex_off += gi; one.empty += gi;
             MinuCand* cands = ctx->cands.as<MinuCand>() + (size_t)i * 3 * kTopMinu;
             int32_t* cand_n = ctx->cand_n.as<int32_t>() + (size_t)i * 3;
             if (launch_minu_cands(grp.dev, one, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), cands, cand_n, ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, nullptr, s) != hipSuccess ||

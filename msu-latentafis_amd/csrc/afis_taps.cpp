@@ -1,9 +1,51 @@
-// afis_taps.cpp — the parity taps (include/afis_matcher_taps.h: afis_debug_*): stage intermediates for tests/.  Built ONLY into libafis_hip_test.so; the product
-// library exports none of them.
+// afis_taps.cpp — the parity taps (include/afis_matcher_taps.h: afis_debug_*): stage intermediates for tests/, and the host side of the direct exact ADC kernels
+// (adc_direct.hip, adc_variant 0-3, 6, 7).  Built ONLY into libafis_hip_test.so, with adc_direct.o; the product library exports none of the taps and has none of the kernels.
 #include "afis_ctx.h"
 #include "../../include/afis_matcher_taps.h"
 
 using namespace afis;
+
+// The conflict-free kernel's lane-ordered code stream (variants 6 / 7) — a full copy of the PQ codes that nothing else reads — and its block offsets
+// ((blocks + 1) x 64 entries per template), laid out at the first use of those variants.
+static int ensure_codes_cf(afis_ctx* ctx, int variant)
+{
+    if ((variant != 6 && variant != 7) || ctx->codes_cf_built) return AFIS_OK;
+    const int64_t G = ctx->gal.G;
+    std::vector<int32_t> to((size_t)G + 1), cfb((size_t)G + 1);
+    HIPCHK(ctx, hipMemcpyAsync(to.data(), ctx->gal.tex_off, to.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t nblk = 0;
+    for (int64_t t = 0; t < G; ++t) { cfb[(size_t)t] = (int32_t)nblk; const int64_t n = to[(size_t)t + 1] - to[(size_t)t]; nblk += n > 0 ? (n + 63) / 64 + 1 : 0; }
+    cfb[(size_t)G] = (int32_t)nblk;
+    if (nblk > 0x7fffffff / 64) return fail(ctx, AFIS_EINVAL, "adc_variant 6 / 7: shard too large for the direct kernel's code stream; split the gallery into more shards");
+    HIPCHK(ctx, upload(ctx->g_tex_cf_blk, cfb, ctx->stream));
+    HIPCHK(ctx, ctx->g_tex_codes_cf.ensure(std::max<size_t>((size_t)nblk * 64 * 16, 16)));
+    ctx->gal.tex_cf_blk = ctx->g_tex_cf_blk.as<int32_t>();
+    ctx->gal.tex_codes_cf = ctx->g_tex_codes_cf.as<uint4>();
+    HIPCHK(ctx, launch_codes_cf(ctx->gal, ctx->g_tex_codes_cf.p, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->codes_cf_built = true;
+    return AFIS_OK;
+}
+
+// S4-S6 of a direct kernel for the query group d against the gallery view g (rm_val / rm_arg sized by the caller)
+static int direct_rowmax(afis_ctx* ctx, const QueryDev& d, const GalleryDev& g, int variant, int chunk, hipEvent_t after_lut)
+{
+    HIPCHK(ctx, ctx->lut.ensure(std::max<size_t>((size_t)d.n_tiles * kTileFloats * 4, 16)));
+    HIPCHK(ctx, launch_lut_build(d, ctx->codewords.as<float>(), ctx->lut.as<float>(), variant, ctx->stream));
+    if (after_lut) HIPCHK(ctx, hipEventRecord(after_lut, ctx->stream));
+    HIPCHK(ctx, launch_adc_rowmax(d, g, ctx->lut.as<float>(), chunk, variant, ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->stream));
+    return AFIS_OK;
+}
+
+// g_direct_adc_stage (afis_ctx.h): the selected direct kernel against the resident shard
+static int direct_adc_stage(afis_ctx* ctx, const QueryDev& d, int chunk, hipEvent_t after_lut)
+{
+    const int rcf = ensure_codes_cf(ctx, ctx->adc_variant);
+    if (rcf != AFIS_OK) return rcf;
+    return direct_rowmax(ctx, d, ctx->gal, ctx->adc_variant, chunk, after_lut);
+}
+__attribute__((constructor)) static void set_direct_adc_stage() { g_direct_adc_stage = direct_adc_stage; }
 
 extern "C" {
 
@@ -96,18 +138,13 @@ int afis_debug_texture_rowmax(afis_ctx* ctx, const afis_template_view* query, in
     if (n_rows) *n_rows = n_lt;
     if (n_lt > 0) {
         const size_t n_pairs = (size_t)ctx->gal.G;
-        HIPCHK(ctx, ctx->lut.ensure((size_t)d.n_tiles * kTileFloats * 4));
         HIPCHK(ctx, ctx->rm_val.ensure(n_pairs * d.lt_pad * 4));
         HIPCHK(ctx, ctx->rm_arg.ensure(n_pairs * d.lt_pad * 4));
         HIPCHK(ctx, hipMemsetAsync(ctx->rm_val.p, 0, n_pairs * d.lt_pad * 4, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->rm_arg.p, 0, n_pairs * d.lt_pad * 4, ctx->stream));
         if (ctx->adc_variant == 9) { int rc9 = adc_stage_mfma(ctx, grp, true); if (rc9 != AFIS_OK) { grp.release(); return rc9; } }
         else if (ctx->adc_variant == 8) { int rc16 = adc_stage_q(ctx, grp, ctx->chunk > 0 ? ctx->chunk : 32, true); if (rc16 != AFIS_OK) { grp.release(); return rc16; } }
-        else {
-        { int rcf = ensure_codes_cf(ctx, ctx->adc_variant); if (rcf != AFIS_OK) { grp.release(); return rcf; } }
-        HIPCHK(ctx, launch_lut_build(d, ctx->codewords.as<float>(), ctx->lut.as<float>(), ctx->adc_variant, ctx->stream));
-        HIPCHK(ctx, launch_adc_rowmax(d, ctx->gal, ctx->lut.as<float>(), ctx->chunk > 0 ? ctx->chunk : 32, ctx->adc_variant, ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->stream));
-        }
+        else { int rcd = direct_adc_stage(ctx, d, ctx->chunk > 0 ? ctx->chunk : 32, nullptr); if (rcd != AFIS_OK) { grp.release(); return rcd; } }
         HIPCHK(ctx, hipMemcpyAsync(val, ctx->rm_val.as<float>() + (size_t)gidx * d.lt_pad, (size_t)n_lt * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(arg, ctx->rm_arg.as<int32_t>() + (size_t)gidx * d.lt_pad, (size_t)n_lt * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -135,7 +172,7 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
         if (st[0] != AFIS_QUERY_OK) return AFIS_OK;
         const QueryDev& d = grp.dev;
         GalleryDev one = ctx->gal;
-        one.G = 1; one.minu_off += gidx; one.minu_tile_off += gidx; one.tex_off += gidx; one.tex_cf_blk += gidx; one.empty += gidx;
+        one.G = 1; one.minu_off += gidx; one.minu_tile_off += gidx; one.tex_off += gidx; one.empty += gidx;
         hipStream_t s = ctx->stream;
         HIPCHK(ctx, d_out.ensure(3 * (size_t)kTopTex * sizeof(MinuCand)));
         HIPCHK(ctx, d_n.ensure(3 * 4));
@@ -144,13 +181,11 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
         int slot = 0, cap = kTopTex;
         if (which == 0) {
             if (d.n_tiles <= 0) return AFIS_OK;
-            HIPCHK(ctx, ctx->lut.ensure((size_t)d.n_tiles * kTileFloats * 4));
             HIPCHK(ctx, ctx->rm_val.ensure((size_t)d.lt_pad * 4)); HIPCHK(ctx, ctx->rm_arg.ensure((size_t)d.lt_pad * 4));
             const int av = ctx->adc_variant >= 8 ? 0 : ctx->adc_variant;     // the tap always uses a direct exact kernel (same bits); for the
             { int rcf = ensure_codes_cf(ctx, av); if (rcf != AFIS_OK) return rcf; }  // bound + refine variants the plain one, which needs no extra code stream
-            one.tex_codes_cf = ctx->gal.tex_codes_cf;
-            HIPCHK(ctx, launch_lut_build(d, ctx->codewords.as<float>(), ctx->lut.as<float>(), av, s));
-            HIPCHK(ctx, launch_adc_rowmax(d, one, ctx->lut.as<float>(), 32, av, ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), s));
+            if (av == 6 || av == 7) { one.tex_codes_cf = ctx->gal.tex_codes_cf; one.tex_cf_blk = ctx->gal.tex_cf_blk + gidx; }
+            { int rcd = direct_rowmax(ctx, d, one, av, 32, nullptr); if (rcd != AFIS_OK) return rcd; }
             HIPCHK(ctx, launch_graph_texture(d, one, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), nullptr, nullptr, ctx->parts.as<float>(),
                                              d_out.as<MinuCand>(), d_n.as<int32_t>(), stage | (ctx->s89_tie_order << 8), s));
         } else {

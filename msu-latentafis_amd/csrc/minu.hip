@@ -504,14 +504,6 @@ __global__ __launch_bounds__(256) void k_minu_classify(QueryDev q, GalleryDev g,
 }
 
 // fb[0] = number of fallback tasks, fb[1 ...] = their task indices
-#ifndef AFIS_MC_ABLATE
-#define AFIS_MC_ABLATE 0
-#endif
-#if AFIS_MC_ABLATE == 1                                                  // timing experiment only (wrong results): no workgroup barriers inside a task
-#define RT_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define RT_SYNC() __syncthreads()
-#endif
 template <int S, int ref_tie_order /* option s3_tie_order: lists short of 120 positive norms, and lists in which positive norms tie, go to the any-shape kernel, which orders equal norms as std::sort does; an instantiation of its own: the default kernel carries none of it */>
 __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, GalleryDev g, const float4* __restrict__ lat_frag,
                                                                 const float4* __restrict__ rol_frag,  // descriptors as operand fragments
@@ -655,7 +647,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
             }
             if (S == 1 || tid < kSelBins) sm.hist[tid] = 0u;
             if (tid == 0) sm.thr_bin = -1;
-            RT_SYNC();
+            __syncthreads();
             pf_qs = -1;
             if (qs_next < qs_hi) {                                                   // uniform
                 const int nLn = q.lm_off[qs_next + 1] - q.lm_off[qs_next];
@@ -672,11 +664,6 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                 }
             }
             PHASE(16);
-#if AFIS_MC_ABLATE == 2                                                  // timing experiment only: the GEMM and its stores, no selection
-            if (tid == 0) cand_n[task] = 0;
-            __syncthreads();
-            continue;
-#endif
             // ---- S2 (:455-456): index-ascending sums; odd row stride: both walks are conflict free.  The adds are one dependent chain per lane (that IS the reference's order); the
             // LDS reads are not: eight are issued before the eight adds that use them, and the NEXT eight are already in flight while those adds run.
             auto seq_sum = [&](const float* __restrict__ p, const int stride, const int n) {
@@ -705,7 +692,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
             };
             if (tid < nR) sm.colsum[tid] = seq_sum(&sm.simi[tid], ld, nL);
             else if (tid >= Cfg::kMaxR && tid - Cfg::kMaxR < nL) sm.rowsum[tid - Cfg::kMaxR] = seq_sum(&sm.simi[(tid - Cfg::kMaxR) * ld], 1, nR);
-            RT_SYNC();
+            __syncthreads();
             PHASE(17);
             // ---- S3 (:461-488): the 120 largest norm values.  The kernel is bound by VALU issue (about 2000 wave-instructions per wave
             // and task before this layout), so the selection is organised for few instructions per element: thread = (column cj, row
@@ -752,7 +739,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                     }
                 }
             }
-            RT_SYNC();
+            __syncthreads();
             PHASE(29);
             if (wave == 0) {   // one wave scans the 256 bins (lane = four consecutive bins): suffix sums over the higher bins find the bin holding the 120th largest approximate key
                 const uint4 h = reinterpret_cast<const uint4*>(sm.hist)[lane];
@@ -771,7 +758,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                 if (a0 < kTopMinu && a0 + (int)h.x >= kTopMinu) sm.thr_bin = 4 * lane;
                 reinterpret_cast<uint4*>(sm.hist)[lane] = make_uint4((uint32_t)a0, (uint32_t)a1, (uint32_t)a2, (uint32_t)a3);   // from here on: where the next candidate of each bin goes
             }
-            RT_SYNC();
+            __syncthreads();
             PHASE(30);
             const int Braw = __builtin_amdgcn_readfirstlane(sm.thr_bin);            // (uniform: one LDS word)
             // Fewer than 120 positive norms, every one of them at least 2^-15 (a latent and a rolled print whose descriptors point away from each other: nearly every similarity is
@@ -780,7 +767,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
             bool fill = false;
             if (__builtin_expect(Braw < 0 && !ref_tie_order, 0)) {                                        // uniform, rare: are there positive norms below 2^-15 (uncounted, bin <= 0)?  Looked for only here — the histogram pass pays nothing for it
                 if (tid == 0) sm.pad_[0] = 0;
-                RT_SYNC();
+                __syncthreads();
                 bool tiny = false;
                 {   // (the keys are recomputed from the matrix, not read from the 32 registers that hold them: a rare path that walks the register array costs the common one 1 % — measured)
                     const float cs2 = my_rows > 0 ? sm.colsum[cj] : 0.0f;
@@ -791,10 +778,10 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                     }
                 }
                 if (tiny) sm.pad_[0] = 1;
-                RT_SYNC();
+                __syncthreads();
                 fill = __builtin_amdgcn_readfirstlane(sm.pad_[0]) == 0;
             }
-            if (__builtin_expect(Braw < 2 && !fill, 0)) { if (tid == 0) to_fallback(task); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); RT_SYNC(); continue; }   // a threshold in or next to bin 0, or tiny positive norms among fewer than 120
+            if (__builtin_expect(Braw < 2 && !fill, 0)) { if (tid == 0) to_fallback(task); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); continue; }   // a threshold in or next to bin 0, or tiny positive norms among fewer than 120
             const int B = fill ? 0 : Braw;
             // ---- a crowded threshold bin: a second histogram inside it ----
             // Descriptors of extracted prints lie near a common manifold: a pair's norm keys then crowd into an octave or less, and the threshold bin alone (1/16 octave) can hold
@@ -807,7 +794,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                 if (__builtin_expect(above + inbin > kCandCap - 32 && B < kSelBins - 1, 0)) {                 // (the top bin also holds everything above it: its keys' lower bits say nothing)
                     uint32_t* const h2 = reinterpret_cast<uint32_t*>(sm.cand);             // the composites' array is free until the candidates are keyed
                     if (tid < 256) h2[tid] = 0u;
-                    RT_SYNC();
+                    __syncthreads();
                     const uint32_t bin_bits = edge >> 19;
                     {   // (keys recomputed from the matrix: see the fill path above)
                         const float cs2 = my_rows > 0 ? sm.colsum[cj] : 0.0f;
@@ -817,7 +804,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                             if ((key >> 19) == bin_bits) atomicAdd(&h2[(key >> 11) & 255u], 1u);
                         }
                     }
-                    RT_SYNC();
+                    __syncthreads();
                     if (wave == 0) {                                                     // the scan of the first histogram, over the sub-bins: the (120 - above)-th largest key of the bin
                         const int need = kTopMinu - above;                               // 1 <= need <= inbin: exactly one sub-bin qualifies
                         if (lane == 0) sm.thr_bin = 0;                                   // (were none to qualify, the edge stays the bin's own)
@@ -836,7 +823,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                         if (a1 < need && a1 + (int)h.y >= need) sm.thr_bin = 4 * lane + 1;
                         if (a0 < need && a0 + (int)h.x >= need) sm.thr_bin = 4 * lane;
                     }
-                    RT_SYNC();
+                    __syncthreads();
                     edge |= (uint32_t)__builtin_amdgcn_readfirstlane(sm.thr_bin) << 11;
                 }
             }
@@ -872,10 +859,10 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
                     }
                 }
             }
-            RT_SYNC();
+            __syncthreads();
             PHASE(31);
             const int n_c = (int)sm.hist[B];                                         // >= 120: group B ends the list
-            if (n_c > kCandCap) { if (tid == 0) to_fallback(task); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); RT_SYNC(); continue; }
+            if (n_c > kCandCap) { if (tid == 0) to_fallback(task); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); continue; }
             int ci = 0, cj2 = 0, cbin = 0;
             uint32_t ke = 0u;
             if (tid < n_c) {                                                         // one exact (double-precision) key per candidate
@@ -886,7 +873,7 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
             }
             if (tid < 8) sm.cand[n_c + tid] = 0ull;                                  // padding: the ranking below reads the list eight composites at a time
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        // this wave's share of the next task's tiles has landed in LDS (waited for here, before the list's stores join the counter)
-            RT_SYNC();
+            __syncthreads();
             PHASE(18);
             // ---- rank the candidates by counting (composites are unique); ranks < 120 are the list, in the reference's order.
             // The list is grouped by the bin of the APPROXIMATE key, highest bin first; sm.hist[b] now holds the END of group b (= the start of group b - 1).  Approximate and
@@ -930,14 +917,12 @@ __global__ __launch_bounds__(256 * S, 4) void k_minu_cands_rt(QueryDev q, Galler
             }
             if (tid == 0) cand_n[task] = kTopMinu;
             ++n_done;
-#if AFIS_MC_ABLATE != 3                                                  // (3: timing experiment only — no barrier at the end of a task: what dropping it could give at most)
-            RT_SYNC();
+            __syncthreads();
             if (ref_tie_order) {                                                     // one list in 10^5: two equal positive norms among the first 121 -> the any-shape kernel redoes the list in the reference's
                 if (tid + 1 < min(n_c, kTopMinu + 1) && sm.cand_e[tid] == sm.cand_e[tid + 1]) sm.pad_[1] = 1;   // sort order (it runs after this kernel, on the same stream)
-                RT_SYNC();
+                __syncthreads();
                 if (tid == 0 && sm.pad_[1] != 0) { sm.pad_[1] = 0; to_fallback(task); }
             }
-#endif
             PHASE(20);
         }
     }

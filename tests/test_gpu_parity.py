@@ -317,7 +317,7 @@ def test_stage_lists_match_oracle_traces(codebook_bytes, cb, oracle, small):
     m.close()
 
 
-def test_c_abi_error_behaviour(codebook_bytes, cb, small):
+def test_c_abi_errors_leave_the_context_usable(codebook_bytes, cb, small):
     """The boundary fails loudly and leaves the context usable: state errors, bad views, bad options, bad files."""
     import ctypes as C
     lats, gal = small
@@ -341,8 +341,8 @@ def test_c_abi_error_behaviour(codebook_bytes, cb, small):
         m.set_option("adc_variant", 4)                               # removed variants
     with pytest.raises(M.AfisError, match="libafis_hip_test"):
         m.set_option("adc_variant", 7)                               # the direct kernels are reference kernels of the test library, not product surface
-    with pytest.raises(M.AfisError, match="libafis_hip_test"):
-        m.set_option("mf_blocks", 3)
+    with pytest.raises(M.AfisError, match="mf_blocks must be 2"):
+        m.set_option("mf_blocks", 3)                                 # the three-row-block form is gone from both libraries
     with pytest.raises(M.AfisError):
         m.set_option("no_such_option", 1)
     with pytest.raises(M.AfisError, match="96"):
@@ -1161,28 +1161,29 @@ def test_results_do_not_depend_on_the_launch_groups(codebook_bytes, cb, oracle, 
     assert float(np.asarray(want["scores"])[qi][planted[qi][0][0]]) > 50
 
 
-def test_bound_pass_kernel_forms_are_bit_identical(codebook_bytes, cb, oracle, small):
-    """The matrix-core bound pass exists in two forms — two row blocks per wave (default) and three (mf_blocks 3: a third less LDS operand traffic per MFMA; test
-    library only) — which differ only in when a wave does what (round 4's third form, a two-stage software pipeline, measured 6 % slower and was deleted in round 5).
-    Row maxima / first arg-maxima against the oracle, and the searches' per-part scores and rank lists against the default form's, bit for bit; workgroup chunks of 1
-    and 3 templates exercise the stage / template edges of the 4-tile stages the alternative form uses."""
+def test_bound_pass_chunk_edges_are_bit_identical(codebook_bytes, cb, oracle, small):
+    """The matrix-core bound pass has one form, two row blocks per wave (mf_blocks 2: the three-row-block form measured 2 % slower in the default schedule and was
+    removed; round 4's two-stage software pipeline, 6 % slower, went in round 5).  Workgroup chunks of 1 and 3 templates exercise the stage / template edges of
+    its 6-tile stages: the searches' per-part scores and rank lists equal those at the automatic chunk (0) bit for bit, and at every chunk the row maxima / first
+    arg-maxima equal the oracle's.  Other mf_blocks values are rejected."""
     lats, gal = small
     m = _matcher(codebook_bytes, gal, taps=True)
     ocb = oracle.codebook(codebook_bytes)
     hl, hr = cases.to_orc(oracle, ocb, lats, gal)
+    picks = [(qi, g) for qi in range(len(lats)) for g in (0, 4, 17, len(gal) - 1)]
+    orc = {p: oracle.texture_rowmax(ocb, hl[p[0]], hr[p[1]]) for p in picks}
     want = m.search(lats, k=10, want_parts=True)
-    for mb in (3,):
-        m.set_option("mf_blocks", mb)
-        for chunk in (0, 1, 3):
-            m.set_option("chunk", chunk)
-            got = m.search(lats, k=10, want_parts=True)
-            assert np.array_equal(got["parts"].view(np.uint32), want["parts"].view(np.uint32)) and np.array_equal(got["topk_idx"], want["topk_idx"]), (mb, chunk)
-        for qi in range(len(lats)):
-            for g in (0, 4, 17, len(gal) - 1):
-                val, arg = m.debug_texture_rowmax(lats[qi], g)
-                oval, oarg = oracle.texture_rowmax(ocb, hl[qi], hr[g])
-                assert np.array_equal(val.view(np.uint32), oval.view(np.uint32)) and np.array_equal(arg, oarg), (mb, qi, g)
-    for bad in (4, 102):
+    for chunk in (0, 1, 3):
+        m.set_option("chunk", chunk)
+        got = m.search(lats, k=10, want_parts=True)
+        assert np.array_equal(got["parts"].view(np.uint32), want["parts"].view(np.uint32)) and np.array_equal(got["topk_idx"], want["topk_idx"]), chunk
+        for qi, g in picks:
+            val, arg = m.debug_texture_rowmax(lats[qi], g)
+            oval, oarg = orc[(qi, g)]
+            assert np.array_equal(val.view(np.uint32), oval.view(np.uint32)) and np.array_equal(arg, oarg), (chunk, qi, g)
+    m.set_option("mf_blocks", 2)
+    assert m.get_option("mf_blocks") == 2
+    for bad in (3, 4, 102):
         with pytest.raises(M.AfisError):
             m.set_option("mf_blocks", bad)
     m.close()
