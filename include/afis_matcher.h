@@ -199,7 +199,8 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
 int afis_rank_list(const float* scores, int64_t n, int ref_order, int k, int64_t* idx, float* sc);
 
 /* PQ encoder — replaces TrainedPQEncoder.encode_multi (extraction/descriptor_PQ.py:19-27, scipy.cluster.vq.vq per
- * sub-space): codes[i][m] = index of the codeword of sub-quantizer m nearest (squared L2, fp32, first minimum) to
+ * sub-space): codes[i][m] = index of the codeword of sub-quantizer m nearest (squared L2 in fp32 as vq evaluates it,
+ * |x|^2 + |c|^2 - 2 x.c; first minimum) to
  * des[i][6m .. 6m+5].  des: [n][96] fp32, codes: [n][16] u8, host pointers.  afis_gallery_add calls it for rolled texture
  * views that carry fp32 descriptors (codes == NULL, des_len == 96). */
 int afis_pq_encode(afis_ctx* ctx, const float* des, int64_t n, uint8_t* codes);

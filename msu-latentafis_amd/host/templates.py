@@ -60,8 +60,10 @@ class Codebook:
         return struct.pack("<3h", self.M, self.K, self.dsub) + self.words.astype("<f4").tobytes()
 
     def encode(self, des: np.ndarray) -> np.ndarray:
-        """Nearest codeword per sub-space (squared L2, first minimum), as TrainedPQEncoder.encode_multi
-        (descriptor_PQ.py:19-27, scipy.cluster.vq.vq)."""
+        """Nearest codeword per sub-space (squared L2 term by term in float64, first minimum): the codes of TrainedPQEncoder.encode_multi
+        (descriptor_PQ.py:19-27, scipy.cluster.vq.vq) wherever the nearest codeword is clear.  vq itself evaluates |x|^2 + |c|^2 - 2 x.c in
+        float32 and can pick the other codeword of an exact or near tie (midpoints, codewords equal to the last bits); the library's encoder
+        (afis_pq_encode) and the oracle's follow vq's arithmetic.  This one serves the generators of synthetic templates."""
         des = np.asarray(des, dtype=np.float32)
         n = des.shape[0]
         codes = np.empty((n, self.M), dtype=np.uint8)

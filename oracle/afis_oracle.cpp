@@ -720,21 +720,41 @@ void orc_build_lut(void* cb, const float* des, int n, int des_len, float* out)
 }
 
 // PQ encoder: TrainedPQEncoder.encode_multi, extraction/descriptor_PQ.py:19-27 — per sub-space the index of the
-// nearest codeword, computed by scipy.cluster.vq.vq (third-party, version unpinned by the reference).  Restated as: squared L2
-// in fp32 with the SAME arithmetic as the matcher's own table (include.h:327-359, build_lut above), first minimum on ties — so
-// a point's code is the codeword its own ADC table ranks nearest.  Pinned against scipy 1.15.3's vq (float32 path) run in the
-// build container: tests/golden/golden_pq.npz, 0 differences on 8192 (point, sub-space) cases (tests/test_oracle.py).
+// nearest codeword, computed by scipy.cluster.vq.vq (third-party, version unpinned by the reference).  For 5 or more features its
+// float32 path does not evaluate |x - c|^2 term by term: it expands it as |x|^2 + |c|^2 - 2 x.c with the products x.c from BLAS sgemm
+// (alpha = -2), i.e.  dist = fl(fl(-2 fma_chain(x, c) + |x|^2) + |c|^2)  with the dot product an fma chain over d ascending and the two
+// squared norms plain sums of rounded squares, d ascending; the first strict minimum from +inf wins (codes start at 0).  Restated here
+// with exactly those roundings.  On exact and near ties (midpoints of two codewords, codewords equal to the last few bits) this
+// arithmetic and the matcher's table (include.h:327-359) rank codewords differently, and the reference's encoder is vq.  Pinned against
+// scipy 1.15.3's vq (float32 path, OpenBLAS sgemm) run in the build container: tests/golden/golden_pq.npz and, for every codebook of
+// tests/cases.py's family, tests/golden/golden_pq_codebooks.npz (exact codewords, exact midpoints, ordinary rows; tests/test_oracle.py).
 void orc_pq_encode(void* cbp, const float* des, int n, int des_len, unsigned char* codes)
 {
     const Codebook& cb = *(Codebook*)cbp;
-    std::vector<float> lut;
+    std::vector<float> csq((size_t)cb.M * cb.K);
+    for (size_t e = 0; e < csq.size(); ++e) {
+        const float* w = cb.cw.data() + e * cb.dsub;
+        float s = 0.0f;
+        for (int k = 0; k < cb.dsub; ++k) { const float t = w[k] * w[k]; s += t; }
+        csq[e] = s;
+    }
     for (int i = 0; i < n; ++i) {
-        build_lut(des + (size_t)i * des_len, 1, des_len, cb, lut);
         for (int j = 0; j < cb.M; ++j) {
-            const float* row = lut.data() + (size_t)j * cb.K;
-            int best = 0;
-            for (int q = 1; q < cb.K; ++q) if (row[q] < row[best]) best = q;
-            codes[(size_t)i * cb.M + j] = (unsigned char)best;
+            const float* x = des + (size_t)i * des_len + j * cb.dsub;
+            float xsq = 0.0f;
+            for (int k = 0; k < cb.dsub; ++k) { const float t = x[k] * x[k]; xsq += t; }
+            float best = INFINITY;
+            int arg = 0;
+            for (int q = 0; q < cb.K; ++q) {
+                const float* w = cb.cw.data() + ((size_t)j * cb.K + q) * cb.dsub;
+                float dot = 0.0f;
+                for (int k = 0; k < cb.dsub; ++k) dot = std::fma(w[k], x[k], dot);
+                const float mm = -2.0f * dot;
+                const float t = mm + xsq;
+                const float dist = t + csq[(size_t)j * cb.K + q];
+                if (dist < best) { best = dist; arg = q; }
+            }
+            codes[(size_t)i * cb.M + j] = (unsigned char)arg;
         }
     }
 }

@@ -78,3 +78,144 @@ def ref_rolled_template():
     return T.FPTemplate(minu=[T.MinutiaeTemplate(np.arange(5, dtype=np.int16), np.arange(5, dtype=np.int16), np.zeros(5, np.float32), np.ones((5, 96), np.float32))],
                         tex=[T.TextureTemplate(rng.integers(0, 45, n).astype(np.int16), rng.integers(0, 47, n).astype(np.int16),
                                                rng.uniform(-1, 1, n).astype(np.float32), codes=rng.integers(0, 256, (n, 16)).astype(np.uint8))])
+
+
+# ---- a family of codebooks (tests/test_gpu_codebooks.py, the codebook checks of tests/test_oracle.py and tests/test_host.py): every member is made from the
+# shipped file by scaling, copying and editing entries, so no further codebook is committed; tests/golden/golden_ref.json records each member's sha256 ----
+SHIPPED_CODEBOOK = "codebook_EmbeddingSize_96_stride_16_subdim_6.dat"
+CODEBOOK_SCALE = {"shipped": 1.0, "tiny": 3e-4, "large": 37.5, "huge": 1500.0, "overflow": 1.0, "duplicates": 1.0, "fp16_twins": 1.0, "flat": 1.0, "halfulp": 1.0}
+CODEBOOK_FAMILY = list(CODEBOOK_SCALE)
+DUPLICATE_SLOTS = [(s, 128 + s) for s in range(32)] + [(3, 255), (100, 254)]    # (earlier slot, later exact copy) in every sub-quantizer
+TWIN_SLOTS = [(40 + s, 168 + s) for s in range(32)]                                         # (earlier slot, its fp16 twin): equal in fp16, 1 ulp apart in fp32
+OVERFLOW_ENTRIES = [(2, 17, 3, 7e4), (2, 200, 0, -7e4), (2, 201, 5, 7e4), (9, 5, 5, 7e4), (9, 5, 1, -7e4)]   # (sub-quantizer, slot, component, value beyond fp16)
+FLAT_SUBQ = 11
+
+
+def shipped_codebook():
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", SHIPPED_CODEBOOK), "rb") as f:
+        return T.Codebook.from_bytes(f.read())
+
+
+def family_codebook(name, base=None):
+    """Member `name` of the family (a T.Codebook).  tiny (x 3e-4) puts 77 % of the entries among fp16's subnormals; large and huge scale the similarities
+    into the thousands and millions; overflow has components beyond fp16's range; duplicates / fp16_twins / flat plant exact and fp16-level ties; halfulp
+    maximises the codewords' fp16 rounding error, all of one sign."""
+    w = (base or shipped_codebook()).words.copy()
+    s = CODEBOOK_SCALE[name]
+    if s != 1.0:
+        w = (w * np.float32(s)).astype(np.float32)
+    if name == "overflow":
+        for m, k, d, v in OVERFLOW_ENTRIES:
+            w[m, k, d] = np.float32(v)
+    elif name == "duplicates":
+        for a, b in DUPLICATE_SLOTS:
+            w[:, b] = w[:, a]
+    elif name == "fp16_twins":
+        for a, b in TWIN_SLOTS:
+            t = w[:, a].copy()
+            for m in range(w.shape[0]):
+                d = (a + m) % 6
+                for direction in (np.inf, -np.inf):                 # one fp32 ulp away, the fp16 rounding unchanged
+                    x = np.nextafter(t[m, d], np.float32(direction)).astype(np.float32)
+                    if np.float16(x) == np.float16(t[m, d]):
+                        t[m, d] = x
+                        break
+            w[:, b] = t
+    elif name == "flat":
+        w[FLAT_SUBQ] = 0.0
+    elif name == "halfulp":                                          # every component just under half an fp16 ulp ABOVE its fp16 rounding: with latent rows
+        h = w.astype(np.float16)                                     # that are positive and exact in fp16 (family_set), the bound pass's whole error is the
+        gap = np.nextafter(h, np.float16(np.inf)).astype(np.float32) - h.astype(np.float32)     # codewords' rounding, all of one sign (its Q term)
+        v = (h.astype(np.float32) + np.float32(0.499) * gap).astype(np.float32)
+        w = np.where(v.astype(np.float16) == h, v, w).astype(np.float32)
+    return T.Codebook(np.ascontiguousarray(w, np.float32))
+
+
+def family_lut_descriptors(name, base=None):
+    """ref_lut_descriptors for a member: the shipped rows scaled by the member's factor, row 3 the member's own exact codewords."""
+    base = base or shipped_codebook()
+    des = (ref_lut_descriptors(base) * np.float32(CODEBOOK_SCALE[name])).astype(np.float32)
+    cb = family_codebook(name, base)
+    des[3] = np.concatenate([cb.words[m, (7 * m) % 256] for m in range(16)])
+    return des
+
+
+def family_encoder_descriptors(name, base=None):
+    """128 descriptors for the encoder checks: 48 exact codewords (for duplicates / fp16_twins: of the LATER copy or twin, and of the earlier one),
+    40 exact fp32 midpoints of two codewords, 40 ordinary unit-norm rows (norm 1.73) scaled to the member."""
+    cb = family_codebook(name, base)
+    rng = np.random.default_rng(4000 + CODEBOOK_FAMILY.index(name))
+    pairs = DUPLICATE_SLOTS if name == "duplicates" else TWIN_SLOTS if name == "fp16_twins" else None
+    slots = rng.integers(0, 256, (48, 16))
+    if pairs is not None:
+        pick = np.array(pairs)[rng.integers(0, len(pairs), (48, 16))]
+        slots = np.where((np.arange(48) % 3 == 2)[:, None], pick[..., 0], pick[..., 1])        # two in three rows: the later copy / twin
+    exact = np.stack([np.concatenate([cb.words[m, slots[i, m]] for m in range(16)]) for i in range(48)])
+    i, j = rng.integers(0, 256, (2, 40, 16))
+    mid = np.stack([np.concatenate([(cb.words[m, i[r, m]] + cb.words[m, j[r, m]]) * np.float32(0.5) for m in range(16)]) for r in range(40)])
+    unit = rng.standard_normal((40, 96))
+    unit = unit / np.linalg.norm(unit, axis=1, keepdims=True) * T.DESCRIPTOR_NORM * CODEBOOK_SCALE[name]
+    return np.ascontiguousarray(np.concatenate([exact, mid, unit]).astype(np.float32))
+
+
+def family_set(name, base=None, seed=31):
+    """(member codebook, latents, gallery) for the texture and pair checks: 2 latents x 12 rolled templates, planted mates first.  For scaled members the
+    latents' texture descriptors are scaled by the member's factor (so the planted mates stay mates: scaling does not move a nearest codeword), and a third,
+    unscaled latent sits far from every codeword.  For halfulp the latents' texture descriptors are positive and exact in fp16.
+
+    For duplicates / fp16_twins the last two templates plant TIED row maxima: for rows of the first latent whose best code vector names a codeword with a
+    later copy / twin, two adjacent points carry that vector once through the earlier slots' bytes and once through the later ones' (the same codewords, or
+    codewords equal in fp16), in both orders; the rest of the template is a mate.  Such a template records its plan in `_pairs`: rows of
+    (latent row, first point, second point, 1 if the later bytes come first)."""
+    base = base or shipped_codebook()
+    cb = family_codebook(name, base)
+    s = CODEBOOK_SCALE[name]
+    rng = np.random.default_rng(seed)
+    lats = [S.make_latent(rng, n_tex_lo=300, n_tex_hi=360) for _ in range(2)]
+    if name == "halfulp":
+        for L in lats:
+            L.tex[0].des = np.abs(L.tex[0].des).astype(np.float16).astype(np.float32)
+    enc_cb = base if s != 1.0 else cb
+    gal = []
+    for L in lats:
+        for frac, n in ((0.8, 640), (0.5, 1000)):
+            gal.append(S.make_mate(rng, enc_cb, L, frac=frac, n_tex=n))
+    for n in (1, 33, 640, 1200, 700, 500):
+        gal.append(S.make_rolled(rng, cb, n_tex=n))
+    pairs = DUPLICATE_SLOTS if name == "duplicates" else TWIN_SLOTS if name == "fp16_twins" else None
+    if pairs is not None:
+        earlier = np.arange(256); later = np.arange(256)
+        for a, b in pairs:
+            earlier[b] = a; later[a] = b
+        early = earlier[cb.encode(lats[0].tex[0].des)]              # each row's best code vector through the earlier slots' bytes ...
+        late = later[early]                                          # ... and through the later copies' / twins'
+        rows = np.flatnonzero((late != early).any(axis=1))
+        for t, (n, sel) in enumerate(((640, rows[:len(rows) // 2]), (1000, rows[len(rows) // 2:][::-1]))):
+            r = S.make_mate(rng, cb, lats[0], frac=0.7, n_tex=n)
+            c = r.tex[0].codes
+            plan = []
+            for i, row in enumerate(sel[:n // 2]):
+                late_first = (i + t) % 2
+                c[2 * i], c[2 * i + 1] = (late[row], early[row]) if late_first else (early[row], late[row])
+                plan.append((int(row), 2 * i, 2 * i + 1, late_first))
+            r._pairs = np.array(plan, np.int64)
+            gal.append(r)
+    gal = gal[:12]
+    if s != 1.0:
+        for L in lats:
+            L.tex[0].des = (L.tex[0].des * np.float32(s)).astype(np.float32)
+        lats.append(S.make_latent(rng, n_tex_lo=300, n_tex_hi=360))
+    return cb, lats, gal
+
+
+def reference_similarities(lut_row, codes):
+    """matcher.cpp:571-592 on one latent row's table [16][256] and code vectors [n][16]: four chains from 6 / 0 / 0 / 0, chain c subtracting the entries of
+    sub-quantizers c, c + 4, c + 8, c + 12 in that order, met as (d0 + d1) + (d2 + d3); every operation rounded to fp32."""
+    codes = np.asarray(codes)
+    d = [np.full(len(codes), 6.0, np.float32)] + [np.zeros(len(codes), np.float32) for _ in range(3)]
+    for mg in range(4):
+        for c in range(4):
+            m = 4 * mg + c
+            d[c] = (d[c] - lut_row[m][codes[:, m]]).astype(np.float32)
+    return ((d[0] + d[1]).astype(np.float32) + (d[2] + d[3]).astype(np.float32)).astype(np.float32)

@@ -6,6 +6,8 @@ through oracle/_ref/libafis_ref.so (oracle/ref_harness.cpp, built by `make -C or
   * rolled       RolledTextureTemplatePQ on ref_rolled_template()'s texture block: the PQ codes it keeps and the converted points (ori as f32 bits)
   * args         matching/argparser.h: [exists, value] for every line of REF_ARG_LINES x option of REF_ARG_OPTS
   * config       main.cpp's config read with the vendored JSON library: [rc, value] for every text of REF_CONFIG_TEXTS x key of REF_CONFIG_KEYS
+  * codebooks    per member of cases.CODEBOOK_FAMILY: the sha256 of the member's codebook file (Codebook.to_bytes) and of
+                 compute_dist_to_codewords on family_lut_descriptors(member) with the member's codewords ([37][16][256] f32)
 tests/test_oracle.py checks the oracle and the `match` CLI against these records, so that it needs no reference tree.
 
 Run from the repo root:  python tests/golden/make_golden_ref.py
@@ -41,9 +43,14 @@ def main():
             p = os.path.join(d, f"c{n}.config")
             with open(p, "w") as f: f.write(text)
             config.append([list(ref.config_get(p, key)) for key in cases.REF_CONFIG_KEYS])
+    family = {}
+    for name in cases.CODEBOOK_FAMILY:
+        fcb = cases.family_codebook(name, cb)
+        flut = ref.build_lut(cases.family_lut_descriptors(name, cb), fcb.words)
+        family[name] = {"codebook_sha256": hashlib.sha256(fcb.to_bytes()).hexdigest(), "lut_sha256": hashlib.sha256(flut.tobytes()).hexdigest()}
     out = {"lut_shape": list(lut.shape), "lut_sha256": hashlib.sha256(lut.tobytes()).hexdigest(), "pi": ref.lib.ref_pi(),
            "rolled": {"codes": codes.tolist(), "x": xo.tolist(), "y": yo.tolist(), "ori_bits": oo.view(np.uint32).tolist()},
-           "args": args, "config": config}
+           "args": args, "config": config, "codebooks": family}
     path = os.path.join(ROOT, "tests", "golden", "golden_ref.json")
     with open(path, "w") as f: f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in out.items()) + "\n}\n")     # one line per record
     print("wrote", path)

@@ -495,3 +495,18 @@ def test_rank_list_entry_point_is_the_reference_sort(oracle):
             assert np.array_equal(idx[:m], want[:m]) and np.array_equal(sc[:m], s[want[:m]]) and (idx[m:] == -1).all() and (sc[m:] == 0).all(), (n, ref)
     assert lib.afis_rank_list(None, C.c_int64(5), C.c_int(0), C.c_int(3), None, None) != 0
 
+
+
+@pytest.mark.parametrize("name", cases.CODEBOOK_FAMILY)
+def test_codebook_family_reads_back_in_python_and_cpp(cb, tio, tmp_path, name):
+    """Every member of tests/cases.py's codebook family (values beyond fp16's range, fp16 subnormals, exact copies included) survives the Python reader and
+    template_io.cpp::parse_codebook (what afis_create_from_codebook, `match -c` and `pq_encode -c` use) bit for bit."""
+    fam = cases.family_codebook(name, cb)
+    buf = fam.to_bytes()
+    assert len(buf) == 98310
+    back = T.Codebook.from_bytes(buf)
+    assert np.array_equal(back.words.view(np.uint32), fam.words.view(np.uint32))
+    p = tmp_path / f"{name}.dat"; p.write_bytes(buf)
+    out = subprocess.run([tio, "codebook", str(p)], capture_output=True, text=True, check=True).stdout
+    assert "ok=1 M=16 K=256 dsub=6" in out
+    assert int(re.search(r"hash=([0-9a-f]+)", out).group(1), 16) == fnv([fam.words.astype("<f4").tobytes()])

@@ -276,3 +276,98 @@ def test_where_the_reference_sort_order_moves_scores(oracle, codebook_bytes):
     s1 = oracle.search(ocb, hl[3], hr, tie_mode=1)[1]; s4 = oracle.search(ocb, hl[3], hr, tie_mode=4)[1]; s0 = oracle.search(ocb, hl[3], hr, tie_mode=0)[1]
     assert not np.array_equal(bits(s1), bits(s4)) and int((bits(s4) != bits(s0)).sum()) <= int((bits(s1) != bits(s0)).sum())
 
+
+
+@pytest.fixture(scope="module")
+def family_pq():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_pq_codebooks.npz"))
+
+
+@pytest.mark.parametrize("name", cases.CODEBOOK_FAMILY)
+def test_codebook_family_pinned_by_reference_header_and_scipy(oracle, codebook_bytes, ref_gold, family_pq, name):
+    """Every codebook of the family (tests/cases.py: scaled, with values beyond fp16, with exact copies, fp16 twins, a constant sub-quantizer): its bytes are the
+    recorded ones; S4 equals LatentTextureTemplate::compute_dist_to_codewords (include.h) bit for bit; the encoder equals scipy.cluster.vq.vq — the reference's
+    encoder — on exact codewords (of the later copy / twin too), exact midpoints and ordinary rows, first minimum on exact ties."""
+    base = T.Codebook.from_bytes(codebook_bytes)
+    cb = cases.family_codebook(name, base)
+    rec = ref_gold["codebooks"][name]
+    assert hashlib.sha256(cb.to_bytes()).hexdigest() == rec["codebook_sha256"]
+    ocb = oracle.codebook(cb.to_bytes())
+    lut = oracle.build_lut(ocb, cases.family_lut_descriptors(name, base))
+    assert hashlib.sha256(lut.tobytes()).hexdigest() == rec["lut_sha256"], name
+    assert (lut[3][np.arange(16), (7 * np.arange(16)) % 256] == 0).all()             # row 3: the member's own codewords
+    des = cases.family_encoder_descriptors(name, base)
+    assert str(family_pq["scipy_version"]) == "1.15.3"
+    assert hashlib.sha256(des.tobytes()).hexdigest() == str(family_pq["des_sha256_" + name])
+    want = family_pq["codes_" + name]
+    got = oracle.pq_encode(ocb, des)
+    assert np.array_equal(got, want), (name, np.argwhere(got != want)[:8].tolist())
+    if name == "duplicates":                                                         # an exact copy never wins: the earliest slot holding that codeword does
+        copy = np.array([[(cb.words[m, :k] == cb.words[m, k]).all(axis=1).any() for k in range(256)] for m in range(16)])
+        assert copy.sum() == 16 * 34 and not copy[np.arange(16), got].any()
+        assert copy[np.arange(16), des_slots(des[:48], cb)].sum() > 300               # ... though most exact-codeword rows ARE a later copy
+    if name == "fp16_twins":                                                         # an exact LATER twin: vq's rounding cannot tell the pair apart either, and its
+        rows = np.arange(48) % 3 != 2                                                #   first minimum often falls on the earlier twin (what the encoders must reproduce)
+        pair = {b: a for a, b in cases.TWIN_SLOTS}
+        slots = des_slots(des[:48][rows], cb)
+        earlier = np.vectorize(pair.get)(slots)
+        assert ((got[:48][rows] == slots) | (got[:48][rows] == earlier)).all()
+        assert 0 < (got[:48][rows] == earlier).sum() < slots.size
+
+
+def des_slots(des, cb):
+    """The LAST slot of each sub-quantizer whose codeword equals the descriptor's sub-vector (-1 where none does)."""
+    out = np.full((des.shape[0], 16), -1)
+    for m in range(16):
+        eq = (des[:, None, 6 * m:6 * m + 6] == cb.words[m][None]).all(axis=2)
+        out[:, m] = np.where(eq.any(axis=1), 255 - eq[:, ::-1].argmax(axis=1), -1)
+    return out
+
+
+def test_encoder_arithmetic_is_vq_not_the_matcher_table(oracle, codebook_bytes, family_pq):
+    """Why the encoder does not rank codewords by the matcher's own table (|x - c|^2 term by term, include.h:327-359): vq expands |x|^2 + |c|^2 - 2 x.c, and on exact
+    midpoints and fp16 twins the two arithmetics pick different codewords of (all but) equidistant pairs.  The recorded vq codes differ from the table's first minimum
+    somewhere in the family, and the oracle's encoder follows vq everywhere."""
+    base = T.Codebook.from_bytes(codebook_bytes)
+    n_diff = 0
+    for name in cases.CODEBOOK_FAMILY:
+        cb = cases.family_codebook(name, base)
+        ocb = oracle.codebook(cb.to_bytes())
+        des = cases.family_encoder_descriptors(name, base)
+        table_first_min = oracle.build_lut(ocb, des).argmin(axis=2)
+        n_diff += int((table_first_min != family_pq["codes_" + name]).sum())
+    assert n_diff > 0
+
+
+@pytest.mark.parametrize("name", ["duplicates", "fp16_twins"])
+def test_family_sets_plant_tied_row_maxima(oracle, codebook_bytes, name):
+    """The tie templates of cases.family_set: rows whose maximum sits at two adjacent points that name the same codewords (duplicates) or codewords equal in fp16
+    (fp16_twins) through different code bytes, the later bytes first in half of them.  k_mf_tiles cannot see such repeats and the bound pass cannot separate them:
+    the exact evaluation must.  Here the oracle (std::max_element, matcher.cpp:730) is checked to put each such row's first arg-max where the reference's own
+    chains (matcher.cpp:571-592) say: on the first of the two points whenever they tie, on the larger otherwise."""
+    base = T.Codebook.from_bytes(codebook_bytes)
+    cb, lats, gal = cases.family_set(name, base)
+    ocb = oracle.codebook(cb.to_bytes())
+    hl, hr = cases.to_orc(oracle, ocb, lats, gal)
+    lut = oracle.build_lut(ocb, lats[0].tex[0].des)
+    n = {"rows": 0, "tie": 0, "separated": 0, "later_first_and_arg": 0, "later_nearer_first": 0}
+    for g in (10, 11):
+        plan = gal[g]._pairs
+        codes = gal[g].tex[0].codes
+        ov, oa = oracle.texture_rowmax(ocb, hl[0], hr[g])
+        for row, p1, p2, later_first in plan:
+            sims = cases.reference_similarities(lut[row], codes[[p1, p2]])
+            assert ov[row] == sims.max(), (g, row)                       # the row's maximum is at its pair
+            assert oa[row] == (p1 if sims[0] >= sims[1] else p2), (g, row, sims)
+            n["rows"] += 1
+            n["tie" if sims[0] == sims[1] else "separated"] += 1
+            n["later_first_and_arg"] += int(later_first and oa[row] == p1)
+            if name == "fp16_twins" and later_first:                     # the later twin EXACTLY nearer (float64) and first in the template
+                x = lats[0].tex[0].des[row].astype(np.float64).reshape(16, 6)
+                d = [((x - cb.words[np.arange(16), codes[p]].astype(np.float64)) ** 2).sum() for p in (p1, p2)]
+                n["later_nearer_first"] += int(d[0] < d[1])
+    assert n["rows"] >= 250 and n["later_first_and_arg"] >= 100, n
+    if name == "duplicates":
+        assert n["tie"] == n["rows"], n                                  # the same codewords: bit-identical similarities
+    else:
+        assert n["tie"] >= 200 and n["later_nearer_first"] >= 20, n      # fp16 twins: fp32 similarities that tie, or (rarely) differ in the last bit
