@@ -107,7 +107,7 @@ void afis_destroy(afis_ctx* c)
     free_gallery_dev(c);
     c->codewords.release(); c->table.release(); c->lut.release(); c->rm_val.release(); c->rm_arg.release(); c->rm_cv.release(); c->rm_n.release();
     c->parts.release(); c->scores.release(); c->scratch.release(); c->cands.release(); c->cand_n.release(); c->minu_fb.release(); c->diag.release(); c->topk_idx.release(); c->topk_score.release(); c->lutq.release(); c->lutq_min.release(); c->lutq_rng.release(); c->lutq_rowc.release(); c->lut32.release();
-    c->mf_cw16.release(); c->mf_cwn.release(); c->mf_bfrag.release(); c->mf_rowk.release(); c->mf_rec.release(); c->mf_stats.release();
+    c->mf_cw16.release(); c->mf_cwn.release(); c->mf_bfrag.release(); c->mf_rowk.release(); c->mf_rec.release(); c->mf_stats.release(); c->tex_slab.release(); c->minu_slab.release();
     lap("destroying events and the context's stream");
     for (auto& e : c->evpool) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -168,6 +168,8 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "minu_fast_max_latent") *value = rt_class_max_latent(4);            // read-only: what the fast candidate kernel's largest shape class takes (afis_device.h: rt_max_rows)
     else if (n == "minu_fast_max_rolled") *value = rt_class_max_rolled(4);
     else if (n == "minu_fast_max_cells") *value = rt_class_simi_floats(4);
+    else if (n == "graph_slab_steps_texture") *value = kTexSlabSteps;                 // read-only: neighbours per row whose values the list kernels keep in their slabs (afis_device.h); longer rows recompute the rest
+    else if (n == "graph_slab_steps_minutiae") *value = kMinuSlabSteps;
     else if (n == "mf_stats") *value = ctx->mf_collect_stats;
     else if (n == "rowmax_budget_mb") *value = ctx->rowmax_budget_bytes >> 20;
     else if (n == "lut_dtype") *value = 32;

@@ -103,6 +103,10 @@ struct afis_ctx {
     int mf_collect_stats = 0;
     DevBuf lutq, lutq_min, lutq_rng, lutq_rowc, lut32;      // adc_variant 8: 16-row fixed-point tiles, per-(row, m) min / range, per-row (offset, step, margin), fp32 table
     DevBuf lut, rm_val, rm_arg, rm_cv, rm_n, parts, scores, scratch, cands, cand_n, minu_fb, topk_idx, topk_score;
+    // The list kernels' slabs (afis_device.h: kTexSlabWgBytes / kMinuSlabWgBytes per one-wave workgroup of the launch): the neighbour values of S8's power iterations, written in
+    // iteration 0 and read back by the later ones.  minu_slab holds TWO instances' worth: the overlapped schedule runs the minutiae list kernel twice at once (side stream + context's stream).
+    // Sized with the launch groups' buffers (prepare_search_buffers) and counted in their budget (graph_slab_bytes); nothing in them outlives a kernel.
+    DevBuf tex_slab, minu_slab;
     DevBuf diag;                         // kDiagWords unsigned 64-bit counters per launch group of a search (afis_device.h): zeroed when the search starts, read back with its results
     std::vector<unsigned long long> h_diag;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;   // pinned host buffer for what a search reads back inside its wait (rank lists, diagnostics)
@@ -205,6 +209,7 @@ int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t aft
 // null in libafis_hip.so, which rejects those variants.  Hidden: with both libraries in one process, neither may bind to the other's copy.
 typedef int (*DirectAdcStage)(afis_ctx* ctx, const QueryDev& d, int chunk, hipEvent_t after_lut);
 extern DirectAdcStage g_direct_adc_stage __attribute__((visibility("hidden")));
+int64_t graph_slab_bytes(int64_t n_pairs);             // both slabs for a launch of n_pairs (latent, rolled) pairs (1.0 GB + 2 x 0.67 GB from 16 384 pairs on)
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what);
 void register_context(afis_ctx* ctx); void unregister_context(afis_ctx* ctx);   // the process-wide list group_budget_bytes consults
 int drain_abandoned(afis_ctx* ctx);                     // waits (bounded) for a search that returned at its deadline

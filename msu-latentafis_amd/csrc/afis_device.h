@@ -196,11 +196,25 @@ enum { kDiagFallback = 0,       // candidate tasks handed to the any-shape kerne
        kDiagCandsClk = 4, kDiagCandsWall = 5,      // sampled workgroups of the candidate kernel: shader cycles and 100 MHz ticks they lived
        kDiagBoundClk = 6, kDiagBoundWall = 7,      // the same for the bound pass
        kDiagWords = 16 };
+// The list kernels' slabs (graph.hip::dist_filter): the power iterations of S8 compute a row's neighbour values H(t, k) once, in iteration 0, and keep the first kTexSlabSteps /
+// kMinuSlabSteps of every row in a region of global memory that belongs to the WORKGROUP (blockIdx.x; one wave each): per pass of 64 rows and block of four steps the lanes'
+// four values (16 B per lane), then, behind all values, the four neighbour indices as the bytes of a dword — passes x steps x 64 lanes x 5 bytes.  Longer rows recompute what
+// lies beyond.  The capacities cover the longest row of nearly every pass of the headline lists (mean row 24.8 / 10.6 neighbours, mean longest row of a pass 36 / 15.6) and most
+// of the structured workload's (39 / 21 per row); afis_get_option reports them (graph_slab_steps_texture / _minutiae).  The launchers refuse a slab smaller than grid x bytes per
+// workgroup, and the kernels reach it through a buffer descriptor of exactly its size.
+constexpr int kTexSlabSteps = 48, kMinuSlabSteps = 32;
+constexpr size_t kTexSlabWgBytes = (size_t)((kTopTex + 63) / 64) * kTexSlabSteps * 64 * 5;       // 61 440
+constexpr size_t kMinuSlabWgBytes = (size_t)((kTopMinu + 63) / 64) * kMinuSlabSteps * 64 * 5;    // 20 480
+// one-wave workgroups the list kernels are launched with: lists are drawn from a counter, the grids only have to fill the chip and keep the tail short
+inline int graph_texture_grid(long long n_tasks) { return (int)(n_tasks < 16384 ? n_tasks : 16384); }
+inline int graph_minutiae_grid(long long n_tasks) { return (int)(n_tasks < 32768 ? n_tasks : 32768); }
+inline size_t graph_texture_slab_bytes(long long n_tasks) { return n_tasks > 0 ? (size_t)graph_texture_grid(n_tasks) * kTexSlabWgBytes : 0; }
+inline size_t graph_minutiae_slab_bytes(long long n_tasks) { return n_tasks > 0 ? (size_t)graph_minutiae_grid(n_tasks) * kMinuSlabWgBytes : 0; }   // per instance of the kernel
 // S7+S8b+S9: texture lists, one wave per (query, gallery template) -> parts[(q*G+g)*4+3]; rm_n != NULL: the compact form above (rm_val unused), otherwise the dense one (rm_cv unused).
 // tap_stage (this launcher and launch_graph_minutiae): bits 0-7 = the stage a parity tap stops after (2 = the whole scorer); bit 8 = option ref_tie_order 2 (the <1> instantiation of the
 // kernel: equal selectable scores of S8 / S9 in std::sort's order, graph.hip::sort_scores)
 hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const float* table_dist,
-                                const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream);
+                                const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream);
 // S1-S3 for the three selected latent minutiae templates: correspondence lists in rank order, cands[task][120], cand_n[task]
 // (task = (q*3+s)*G + g).  Pairs of up to 256 latent x 512 rolled minutiae and 38 912 similarities go through the rolled-template-stationary MFMA kernel in one of its
 // three shape classes (above); what it cannot take (other shapes, degenerate key distributions) it appends to `fallback` (count, task ids), which the
@@ -209,9 +223,9 @@ hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const fl
 hipError_t launch_minu_cands(const QueryDev& q, const GalleryDev& g, float* scratch, size_t scratch_floats_per_wg, int n_wg,
                              int force_generic, MinuCand* cands, int32_t* cand_n, int32_t* fallback /* minu_fb_ints() ints */, int max_nL, int max_nR,
                              unsigned long long* diag /* NULL or a diagnostics row */, hipStream_t stream);
-// S8a+S9 on those lists, one wave per list -> parts[(q*G+g)*4+{0,1,2}]
+// S8a+S9 on those lists, one wave per list -> parts[(q*G+g)*4+{0,1,2}].  join: a second instance beside one that is already running (same list counter, no reset): it needs a slab of its own
 hipError_t launch_graph_minutiae(const QueryDev& q, const GalleryDev& g, const MinuCand* cands, const int32_t* cand_n,
-                                 float* parts, short4* corr_out, int32_t* corr_n, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join = false);
+                                 float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join = false);
 // S10: fusion -> scores[q*G+g]
 hipError_t launch_fuse(const QueryDev& q, const GalleryDev& g, const float* parts, float* scores, hipStream_t stream);
 

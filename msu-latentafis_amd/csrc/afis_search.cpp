@@ -7,8 +7,15 @@ using namespace afis;
 
 namespace afis {
 
+// The list kernels' slabs for a launch of n_pairs pairs: one per workgroup of the texture kernel's grid, and per workgroup of the minutiae kernel's for each of its two instances.
+// Bounded (the grids are): 1.0 GB + 1.34 GB from 16 384 pairs on.
+int64_t graph_slab_bytes(int64_t n_pairs)
+{
+    return (int64_t)graph_texture_slab_bytes(n_pairs) + 2 * (int64_t)graph_minutiae_slab_bytes(3 * n_pairs);
+}
 // Device bytes one latent of a launch group costs at worst (1000 texture rows): row maxima (value + point: 8 B per (pair, row) — adc_variant 9 keeps them in the compact list only, the others in the dense arrays),
 // adc_variant 9's bound-pass records (kMfRecBytes per (template, row)), the minutiae candidate lists and the per-part scores.
+// The slabs (graph_slab_bytes: bounded, not per latent) are taken off the budget before it is divided by this.
 int64_t group_bytes_per_query(const afis_ctx* ctx, int64_t G)
 {
     const int64_t per_pair = (int64_t)kTexMax * 8 + (ctx->adc_variant == 9 ? (int64_t)kTexMax * kMfRecBytesPerRow : 0) + 3 * (int64_t)kTopMinu * (int64_t)sizeof(MinuCand) + 3 * 4 + 16 + 8;
@@ -20,7 +27,7 @@ int64_t group_bytes_actual(const afis_ctx* ctx, int64_t G, int64_t nq, int64_t r
 {
     const int64_t lt_pad = std::max<int64_t>(kTileRows, (lt_max + kTileRows - 1) / kTileRows * kTileRows), R_pad = (rows_total + 31) / 32 * 32;
     const int64_t per_pair = lt_pad * 8 + 3 * (int64_t)kTopMinu * (int64_t)sizeof(MinuCand) + 3 * 4 + 16 + 8;
-    return std::max<int64_t>(1, G) * (nq * per_pair + (ctx->adc_variant == 9 ? R_pad * kMfRecBytesPerRow : 0));
+    return std::max<int64_t>(1, G) * (nq * per_pair + (ctx->adc_variant == 9 ? R_pad * kMfRecBytesPerRow : 0)) + graph_slab_bytes(nq * std::max<int64_t>(1, G));
 }
 
 // Contexts of this process, per device: what each of them holds in per-group buffers and what it has PLANNED to hold (its largest uploaded launch group) — a context that
@@ -28,7 +35,7 @@ int64_t group_bytes_actual(const afis_ctx* ctx, int64_t G, int64_t nq, int64_t r
 namespace { std::mutex g_ctx_mutex; std::vector<afis_ctx*> g_ctx_live; }
 static size_t held_group_bytes(const afis_ctx* c)
 {
-    return c->rm_val.bytes + c->rm_arg.bytes + c->rm_cv.bytes + c->rm_n.bytes + c->mf_rec.bytes + c->cands.bytes + c->cand_n.bytes + c->parts.bytes + c->minu_fb.bytes;
+    return c->rm_val.bytes + c->rm_arg.bytes + c->rm_cv.bytes + c->rm_n.bytes + c->mf_rec.bytes + c->cands.bytes + c->cand_n.bytes + c->parts.bytes + c->minu_fb.bytes + c->tex_slab.bytes + c->minu_slab.bytes;
 }
 void register_context(afis_ctx* c) { std::lock_guard<std::mutex> lk(g_ctx_mutex); g_ctx_live.push_back(c); }
 void unregister_context(afis_ctx* c) { std::lock_guard<std::mutex> lk(g_ctx_mutex); g_ctx_live.erase(std::remove(g_ctx_live.begin(), g_ctx_live.end(), c), g_ctx_live.end()); }
@@ -203,7 +210,7 @@ int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
     // group size: bounded by the option and by the memory budget of a group's per-pair buffers
     const int64_t G = std::max<int64_t>(1, ctx->gal.G);
-    const int64_t by_mem = group_budget_bytes(ctx) / group_bytes_per_query(ctx, G);
+    const int64_t by_mem = std::max<int64_t>(0, group_budget_bytes(ctx) - graph_slab_bytes(INT64_C(1) << 40)) / group_bytes_per_query(ctx, G);
     // latents per launch group: the option, or (0 = auto) as many as keep about five million (latent, rolled) pairs in a launch (round 5; two million before) — 50 at a 100k-template
     // shard, 128 at <= 39k (round 3, a 12.5k-template shard: 100 latents in one launch 310.7 ms, in 64 + 36: 315.1): the persistent per-pair kernels lose their tails once per launch, which shows on small shards (12 launches of 100k pairs
     // each cost 1.2 x their share of a 100k-template step; 2 launches do not).  Measured at 100k templates, 100 latents: 7 per launch 2 495 ms, 10: 2 486,
@@ -391,6 +398,8 @@ static int prepare_search_buffers(afis_ctx* ctx, const afis_queries* q, bool wan
             HIPCHK(ctx, ctx->cands.ensure(n_pairs * 3 * kTopMinu * sizeof(MinuCand)));
             HIPCHK(ctx, ctx->cand_n.ensure(n_pairs * 3 * 4));
             HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(n_pairs * 3, (size_t)G) * 4));
+            HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs)));
+            HIPCHK(ctx, ctx->minu_slab.ensure(2 * graph_minutiae_slab_bytes(3 * (long long)n_pairs)));     // two instances at once in the overlapped schedule
             {   // the generic candidate kernel's scratch (sized as in the loop below, for the longest latent minutiae template of the search)
                 const size_t per_wg = minu_scratch_floats(nL_max, ctx->max_nR, ctx->s3_tie_order);
                 int n_wg = 1024;
@@ -527,11 +536,13 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             const bool minutiae_light = cells_m <= ctx->overlap_cell_ratio * cells_t;
             const bool overlap = ctx->adc_variant == 9 && ctx->stream_lo != nullptr && !ctx->overlap_failed && n_pairs >= 65536 && minutiae_light;
             grp.overlapped = overlap;
+            const size_t minu_slab_1 = graph_minutiae_slab_bytes(3 * (long long)n_pairs);      // one instance's slab of the minutiae list kernel (minu_slab holds two)
+            HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs))); HIPCHK(ctx, ctx->minu_slab.ensure(2 * minu_slab_1));   // (already large enough, as the buffers above)
             const bool compact9 = ctx->adc_variant == 9;                  // the recomputation kernel's compact list of the rows that matter (S7 reads a third of the rows)
             auto minutiae_stage = [&]() -> int {
                 HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, diag_row, s));
                 HIPCHK(ctx, hipEventRecord(ev[7], s));
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
+                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
                 return AFIS_OK;
             };
             if (overlap) {
@@ -549,17 +560,17 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, diag_row, sh));
                 HIPCHK(ctx, hipMemsetAsync(g.task_ctr + 1, 0, 4, sh));                     // the list counter both instances of the list kernel draw from: reset BEFORE either may start
                 HIPCHK(ctx, hipEventRecord(ev[7], sh));
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), sh, true));
+                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), sh, true));
                 HIPCHK(ctx, hipEventRecord(ev[4], sh));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[6], 0));
                 HIPCHK(ctx, hipEventRecord(ev[8], s));                                     // the bound pass is done
                 rc9 = adc_refine_mfma(ctx, grp, false, true);
                 if (rc9 != AFIS_OK) return rc9;
                 HIPCHK(ctx, hipEventRecord(ev[2], s));
-                HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
+                HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, ctx->tex_slab.p, ctx->tex_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
                 HIPCHK(ctx, hipEventRecord(ev[3], s));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[7], 0));                              // every candidate list exists: help with whatever lists are left
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s, true));
+                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.as<unsigned char>() + minu_slab_1, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s, true));   // beside the side stream's instance: the slab's second half
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[4], 0));
                 // No host wait here: the groups of a search follow one another on the three streams through events alone, and the search's final wait polls ALL THREE streams
                 // (wait_streams).  Round 4 blocked on the two side streams after every group because hipStreamSynchronize of the context's stream alone never returned with
@@ -579,7 +590,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             }
             HIPCHK(ctx, hipEventRecord(ev[2], s));
             HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), compact9 ? ctx->rm_cv.as<float>() : nullptr,
-                                             compact9 ? ctx->rm_n.as<int32_t>() : nullptr, grp_parts, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
+                                             compact9 ? ctx->rm_n.as<int32_t>() : nullptr, grp_parts, ctx->tex_slab.p, ctx->tex_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
             HIPCHK(ctx, hipEventRecord(ev[3], s));
             { int rcm = minutiae_stage(); if (rcm != AFIS_OK) return rcm; }
             HIPCHK(ctx, hipEventRecord(ev[4], s));
@@ -687,6 +698,7 @@ int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const i
         HIPCHK(ctx, ctx->cand_n.ensure((size_t)n * 3 * 4));
         HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(3, 1) * 4));
         HIPCHK(ctx, ctx->parts.ensure((size_t)n * 16));
+        HIPCHK(ctx, ctx->minu_slab.ensure(graph_minutiae_slab_bytes(3)));                  // three lists per launch, launches in stream order
         HIPCHK(ctx, d_xy.ensure((size_t)n * 3 * kTopMinu * sizeof(short4)));
         HIPCHK(ctx, d_n.ensure((size_t)n * 3 * 4));
         hipStream_t s = ctx->stream;
@@ -699,7 +711,7 @@ int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const i
             int32_t* cand_n = ctx->cand_n.as<int32_t>() + (size_t)i * 3;
             if (launch_minu_cands(grp.dev, one, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), cands, cand_n, ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, nullptr, s) != hipSuccess ||
                 launch_graph_minutiae(grp.dev, one, cands, cand_n, ctx->parts.as<float>() + (size_t)i * 4,
-                                      d_xy.as<short4>() + (size_t)i * 3 * kTopMinu, d_n.as<int32_t>() + (size_t)i * 3, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s) != hipSuccess)
+                                      d_xy.as<short4>() + (size_t)i * 3 * kTopMinu, d_n.as<int32_t>() + (size_t)i * 3, ctx->minu_slab.p, ctx->minu_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s) != hipSuccess)
                 err = fail(ctx, AFIS_EDEVICE, "afis_correspondences: kernel launch failed");
         }
         if (err == AFIS_OK) {
@@ -744,7 +756,7 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
     const int n_pq = std::max((n_minu + 2) / 3, n_tex);
-    const int64_t by_mem = std::max<int64_t>(1, group_budget_bytes(ctx) / group_bytes_per_query(ctx, G));
+    const int64_t by_mem = std::max<int64_t>(1, std::max<int64_t>(0, group_budget_bytes(ctx) - graph_slab_bytes(INT64_C(1) << 40)) / group_bytes_per_query(ctx, G));
     const int per = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->query_batch > 0 ? ctx->query_batch : 10, by_mem));
     std::vector<float> parts;
     for (int j0 = 0; j0 < n_pq; j0 += per) {

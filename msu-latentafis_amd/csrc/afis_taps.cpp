@@ -186,7 +186,8 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
             { int rcf = ensure_codes_cf(ctx, av); if (rcf != AFIS_OK) return rcf; }  // bound + refine variants the plain one, which needs no extra code stream
             if (av == 6 || av == 7) { one.tex_codes_cf = ctx->gal.tex_codes_cf; one.tex_cf_blk = ctx->gal.tex_cf_blk + gidx; }
             { int rcd = direct_rowmax(ctx, d, one, av, 32, nullptr); if (rcd != AFIS_OK) return rcd; }
-            HIPCHK(ctx, launch_graph_texture(d, one, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), nullptr, nullptr, ctx->parts.as<float>(),
+            HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes(d.nq)));
+            HIPCHK(ctx, launch_graph_texture(d, one, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), nullptr, nullptr, ctx->parts.as<float>(), ctx->tex_slab.p, ctx->tex_slab.bytes,
                                              d_out.as<MinuCand>(), d_n.as<int32_t>(), stage | (ctx->s89_tie_order << 8), s));
         } else {
             slot = which - 1; cap = kTopMinu;
@@ -194,7 +195,8 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
             HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * 64));
             HIPCHK(ctx, ctx->cands.ensure(3 * (size_t)kTopMinu * sizeof(MinuCand))); HIPCHK(ctx, ctx->cand_n.ensure(12)); HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(3, 1) * 4));
             HIPCHK(ctx, launch_minu_cands(d, one, ctx->scratch.as<float>(), per_wg, 64, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, nullptr, s));
-            HIPCHK(ctx, launch_graph_minutiae(d, one, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->parts.as<float>(), nullptr, nullptr,
+            HIPCHK(ctx, ctx->minu_slab.ensure(graph_minutiae_slab_bytes(3ll * d.nq)));
+            HIPCHK(ctx, launch_graph_minutiae(d, one, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->parts.as<float>(), nullptr, nullptr, ctx->minu_slab.p, ctx->minu_slab.bytes,
                                               d_out.as<MinuCand>(), d_n.as<int32_t>(), stage | (ctx->s89_tie_order << 8), s));
         }
         std::vector<MinuCand> h((size_t)3 * kTopTex); int32_t hn[3] = {-1, -1, -1};

@@ -20,8 +20,9 @@
 //   * greedy clique selection          -> rounds: the first still-alive candidate in rank order is accepted and every later
 //                                        candidate that conflicts with it is killed in parallel; identical to the sequential
 //                                        scan, but the trip count is the number of ACCEPTED candidates;
-//   * H (200x200 fp32 = 160 KB)        -> never stored: LDS keeps the bitmask of its non-zero entries, values are recomputed on
-//                                        demand and cached per row; a zero entry would only add +0.0f, so skipping it is exact.
+//   * H (200x200 fp32 = 160 KB)        -> never stored whole: LDS keeps the bitmask of its non-zero entries; the power iterations compute a row's
+//                                        non-zero values once and keep them in the workgroup's slab in global memory (dist_filter); a zero entry
+//                                        would only add +0.0f, so skipping it is exact.
 #include "afis_device.h"
 #include <type_traits>
 #include "atan2f_libm.h"
@@ -89,6 +90,13 @@ __device__ __forceinline__ int g_wave_sum(int x)
     return __builtin_amdgcn_readlane(x, 63);
 }
 
+// A workgroup's slab (the list kernels' power iterations, dist_filter) as a raw buffer: base and size sit in four scalar registers, an access adds a wave-uniform scalar
+// offset and the lane's 32-bit offset — no 64-bit address per lane and access in vector registers (which is what the loop optimisations make of pointer arithmetic
+// here) — and the hardware drops whatever would fall outside [0, bytes).  Plain cached accesses (aux 0).
+typedef __amdgpu_buffer_rsrc_t SlabBuf;
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ SlabBuf g_slab_buf(unsigned char* base, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000); }   // word 3: 32-bit raw buffer, gfx9 data format
+
 struct Pt { int lx, ly, rx, ry; };
 __device__ __forceinline__ int2 pack_xy(int lx, int ly, int rx, int ry) { return make_int2((lx & 0xffff) | (ly << 16), (rx & 0xffff) | (ry << 16)); }
 __device__ __forceinline__ Pt unpack_xy(int2 v) { Pt p; p.lx = (int)(short)v.x; p.ly = v.x >> 16; p.rx = (int)(short)v.y; p.ry = v.y >> 16; return p; }
@@ -101,9 +109,9 @@ template <int N> struct SimStore<N, false> {};
 #ifndef AFIS_MINU_ALIAS
 #define AFIS_MINU_ALIAS 1
 #endif
-template <int NMAX_, int CACHE_, bool OWN_SIM_>
+template <int NMAX_, bool OWN_SIM_>
 struct __attribute__((aligned(16))) WaveSmem : SimStore<NMAX_, OWN_SIM_> {
-    static constexpr int NMAX = NMAX_, CACHE = CACHE_;
+    static constexpr int NMAX = NMAX_;
     static constexpr bool OWN_SIM = OWN_SIM_;
     static constexpr bool ALIAS_ORI = NMAX_ > 128 || AFIS_MINU_ALIAS;   // LDS is what limits the lists per CU: the angle stage's orientations live in b[] / cc[] while its H is built
     static constexpr int W = (NMAX + 31) / 32;
@@ -119,7 +127,7 @@ struct __attribute__((aligned(16))) WaveSmem : SimStore<NMAX_, OWN_SIM_> {
     uint32_t hb[NMAX][W];                  // bit rows: non-zero pattern of H (distance stage), then the boolean H of the angle stage
     // LDS is what limits how many lists a CU works on at once, so buffers with disjoint lifetimes share storage:
     union {
-        float stash[CACHE * NMAX];                                                  // power iterations: CACHE * 4 bytes per row for the rows' first neighbour indices (bytes, [n][t]) and, optionally, values
+        uint32_t sortbuf[N4 + 128];                                                 // sort_scores: the keys in index order + 128 bin counters (the power iterations keep nothing here: their values and indices live in the slab)
         struct { u64 keys[N4]; float lo[ALIAS_ORI ? 1 : NMAX], ro[ALIAS_ORI ? 1 : NMAX]; } s;   // sorts (after the iterations); orientations (angle stage, unless they borrow b / cc)
         struct { uint32_t keys[N4]; short te[NMAX], targ[NMAX]; } pick;          // texture rows picked by S7, before they are ranked (32-bit keys)
     } x;
@@ -468,7 +476,7 @@ __device__ __forceinline__ float h_value(float dist)
 // S8a (LOOKUP = false, 5 iterations) / S8b (LOOKUP = true, 3 iterations).  Returns the number of survivors (compacted in place).
 // MODE 0: generic arithmetic; 1: packed 16-bit coordinates (texture: with the |d| < 50 test); 2: texture, every coordinate in [0, 49]
 template <class SM, bool LOOKUP, int ITERS, int MODE, int REF_TIE>
-__device__ int dist_filter(SM& sm, int num, const float* __restrict__ table, const float* __restrict__ ext)
+__device__ int dist_filter(SM& sm, int num, const float* __restrict__ table, const float* __restrict__ ext, SlabBuf slab)
 {
     constexpr bool fast = MODE > 0;
     constexpr bool range_test = MODE == 1;
@@ -640,29 +648,36 @@ __device__ int dist_filter(SM& sm, int num, const float* __restrict__ table, con
 #pragma unroll
     for (int u = 0; u < U; ++u) mine[u] = myrow[u] >= 0 ? sm.xy[myrow[u]] : make_int2(0, 0);
     // power iteration, :1284-1289 / :1406-1411 (canonical order: k ascending, unfused; see oracle).
-    // Iteration 0 walks each row's bit mask (every lane ITS row, a (word, remaining bits) cursor inside ONE loop whose trip count is the longest
-    // row of the pass), computes every value and notes, per row, the first kIdxN neighbour indices as bytes and the first kValN values
-    // (idx8[n][row], vst[n][row]: together they fill the stash space).  Iterations 1.. read the n-th neighbour from there — a byte load instead of
-    // the bit walk with its divergent "next non-empty word" loop — take the value from the stash (n < kValN) or recompute it (20 instructions
-    // in the fp16 form); only rows longer than kIdxN go on with the bit walk, from the cursor iteration 0 left at position kIdxN.
-    // Texture lists (200 rows, 17 neighbours on average): 8 indices per row, minutiae lists (120 rows, 10 on average): 12, and no values — values + indices
-    // were 2-4 % faster at equal occupancy, but LDS decides how many lists a SIMD holds, and two more texture lists per CU / two more minutiae lists per SIMD are worth more.
-    // (Before the index lists: 4 and 10 values per row; the walk cost as much as a value.)
+    // H(t, k) depends on the coordinates of entries t and k only: it is the same float in every iteration.  Iteration 0 walks each row's bit mask (every lane ITS row, a
+    // (word, remaining bits) cursor inside ONE loop whose trip count is the longest row of the pass), computes every value and writes the first kSlabN (value, neighbour index)
+    // of its row to the workgroup's SLAB in global memory, in blocks of four steps (layout below).  Iterations 1.. read the blocks back — the lane that wrote an element is the
+    // lane that reads it (myrow[u] is fixed for the list), so program order is all the ordering there is — multiply by b[k] and add: no bit walk, no value.  A block's loads are
+    // issued before the block in front of it is consumed.  Steps beyond kSlabN (rows longer than the capacity) go on with the bit walk from the cursor iteration 0 left there, and
+    // recompute the value.
+    // The slab costs neither LDS nor registers, which is what every earlier form of keeping the values paid with (an LDS stash: two texture lists per CU / two minutiae lists per
+    // SIMD fewer; registers: scratch).  What is read beyond a row's end — an ended row's stale steps, blocks a shorter list left — is dropped by the `n < rlen` select.
+    // Measured forms (one box, interleaved; texture / minutiae list kernel, 16 latents x 50k templates, ms): values recomputed 36.1 / 69.4; one float + one index BYTE per step
+    // ([step][lane]) 30.8 / 61.9; blocks of four through generic 64-bit addresses 28.4 / 57.0; through the buffer descriptor 27.8 / 55.6.  Masking the accesses of ended rows,
+    // blocks of 2 or 8 and a second block in flight were within 1 ms of the byte form or slower (profiles/r07_graph_phases.txt).
     constexpr bool kFlat = NMAX > 128;
-#ifndef AFIS_MINU_VALN
-#define AFIS_MINU_VALN 0
-#endif
-    constexpr int kValN = kFlat ? 0 : AFIS_MINU_VALN, kIdxN = 4 * SM::CACHE - 4 * kValN;   // 4 kValN + kIdxN bytes per row = the stash space (CACHE floats per row)
-    static_assert(kValN * NMAX * 4 + kIdxN * NMAX <= (int)sizeof(sm.x.stash), "index lists + value stash exceed the stash space");
-    float* const vst = sm.x.stash;
-    unsigned char* const idx8 = reinterpret_cast<unsigned char*>(sm.x.stash + kValN * NMAX);
-#ifndef AFIS_MINU_REGN
-#define AFIS_MINU_REGN 0
-#endif
-    // minutiae lists only: the values of a row's first kRegN neighbours stay in REGISTERS from iteration 0 on (statically indexed: the first kRegN steps of every loop are unrolled)
-    constexpr int kRegN = kFlat ? 0 : AFIS_MINU_REGN;
-    static_assert(kRegN <= kIdxN, "cached values need their neighbour indices");
-    float hreg[U][kRegN > 0 ? kRegN : 1];
+    constexpr int kSlabN = kFlat ? kTexSlabSteps : kMinuSlabSteps;
+    static_assert(kSlabN % 4 == 0, "the read loop takes blocks of four steps");
+    static_assert((size_t)U * kSlabN * 64 * 5 == (kFlat ? kTexSlabWgBytes : kMinuSlabWgBytes), "slab layout and the size the host allocates differ");
+    // A block = four consecutive steps of a pass: the lane's four values as one float4 ([pass u][block][lane], a 1 KB request per wave) and its four neighbour indices as the bytes of
+    // one dword (same order, behind the values; 256 B per wave) — two memory instructions per four steps.
+    // Addresses = the slab's descriptor + a wave-uniform offset (both in scalar registers) + the lane's 32-bit offset (g_slab_buf above).
+    constexpr int kSlabBlk = kSlabN / 4;
+    constexpr uint32_t kSlabIdx0 = (uint32_t)U * kSlabN * 64 * 4;
+    const uint32_t lane16 = (uint32_t)lane * 16u, lane4 = (uint32_t)lane * 4u;
+    // e = u * kSlabBlk + block (uniform)
+    auto put_block = [&](int e, const float (&h)[4], uint32_t k4) {
+        __builtin_amdgcn_raw_buffer_store_b128(v4u{__float_as_uint(h[0]), __float_as_uint(h[1]), __float_as_uint(h[2]), __float_as_uint(h[3])}, slab, lane16, e * 1024, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(k4, slab, lane4, (int)kSlabIdx0 + e * 256, 0);
+    };
+    auto get_block = [&](int e, v4u& h, uint32_t& k4) {
+        h = __builtin_amdgcn_raw_buffer_load_b128(slab, lane16, e * 1024, 0);
+        k4 = __builtin_amdgcn_raw_buffer_load_b32(slab, lane4, (int)kSlabIdx0 + e * 256, 0);
+    };
     int cur_w[U]; uint32_t cur_bits[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) { cur_w[u] = 0; cur_bits[u] = 0u; }
@@ -689,60 +704,46 @@ __device__ int dist_filter(SM& sm, int num, const float* __restrict__ table, con
                 if (t >= 0) {                                                // lanes beyond the list sit the pass out: ONE divergent region, not one per step
                     int w = 0;
                     uint32_t bits = hrow[0];
+                    for (int n0 = 0; n0 < trip[u]; n0 += 4) {                // uniform
+                        if (n0 == kSlabN) { cur_w[u] = w; cur_bits[u] = bits; }   // uniform condition
+                        float h4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                        uint32_t k4 = 0u;
 #pragma unroll
-                    for (int r = 0; r < kRegN; ++r) {                        // the first kRegN steps, unrolled: their values go to registers
-                        if (r < trip[u]) {                                   // uniform
-                            while (bits == 0u && w + 1 < Wn) { ++w; bits = hrow[w]; }
-                            const bool have = bits != 0u;
-                            const int k = (w * 32 + __ffs(bits) - 1) & 255;
-                            bits &= bits - 1;
-                            const float h = value(mine[u], k);
-                            idx8[r * NMAX + t] = (unsigned char)k;
-                            hreg[u][r] = h;
-                            const float p = h * sm.b[k];
-                            acc += have ? p : 0.0f;
+                        for (int j = 0; j < 4; ++j) {
+                            if (n0 + j < trip[u]) {                          // uniform
+                                while (bits == 0u && w + 1 < Wn) { ++w; bits = hrow[w]; }   // next non-empty word of this lane's row
+                                const bool have = bits != 0u;                // an ended row notes a stale index (never used: n >= its length) and adds +0.0f
+                                const int k = (w * 32 + __ffs(bits) - 1) & 255;
+                                bits &= bits - 1;
+                                const float h = value(mine[u], k);
+                                h4[j] = h; k4 |= (uint32_t)k << (8 * j);
+                                const float p = h * sm.b[k];
+                                acc += have ? p : 0.0f;
+                            }
                         }
-                    }
-                    for (int n = kRegN; n < trip[u]; ++n) {                  // uniform
-                        if (n == kIdxN) { cur_w[u] = w; cur_bits[u] = bits; }    // uniform condition
-                        while (bits == 0u && w + 1 < Wn) { ++w; bits = hrow[w]; }   // next non-empty word of this lane's row
-                        const bool have = bits != 0u;                        // an ended row notes a stale index (never read: n >= its length) and adds +0.0f
-                        const int k = (w * 32 + __ffs(bits) - 1) & 255;
-                        bits &= bits - 1;
-                        const float h = value(mine[u], k);
-                        if (n < kIdxN) idx8[n * NMAX + t] = (unsigned char)k;
-                        if (n < kValN) vst[n * NMAX + t] = h;
-                        const float p = h * sm.b[k];
-                        acc += have ? p : 0.0f;
+                        if (n0 < kSlabN) put_block(u * kSlabBlk + (n0 >> 2), h4, k4);   // uniform condition
                     }
                 }
             } else {
-                const int nV = min(trip[u], kValN), nA = min(trip[u], kIdxN);
-                const int tt = t >= 0 ? t : 0;
-                // no divergent region per step: a lane whose row has ended computes on a stale index byte (any byte addresses LDS of this list) and adds
+                // no divergent region per step: a lane whose row has ended computes on whatever the slab holds there (any index byte addresses LDS of this list) and adds
                 // +0.0f instead (acc >= +0: x + 0.0f == x) — the exec bookkeeping of a branch costs more than the masked lanes' work
-                for (int n = 0; n < nV; ++n) {                               // uniform
-                    const int k = idx8[n * NMAX + tt];
-                    const float p = vst[n * NMAX + tt] * sm.b[k];
-                    acc += n < rlen[u] ? p : 0.0f;
-                }
+                const int nS = min(trip[u], kSlabN);
+                v4u hc = {0u, 0u, 0u, 0u}; uint32_t kc = 0u;
+                if (nS > 0) get_block(u * kSlabBlk, hc, kc);                 // uniform
+                for (int n0 = 0; n0 < nS; n0 += 4) {                         // uniform; kSlabN is a multiple of 4: every step of a block lies inside the slab
+                    const float hn[4] = {__uint_as_float(hc.x), __uint_as_float(hc.y), __uint_as_float(hc.z), __uint_as_float(hc.w)};
+                    const uint32_t kn = kc;
+                    if (n0 + 4 < nS) get_block(u * kSlabBlk + (n0 >> 2) + 1, hc, kc);   // uniform: the next block's loads are in flight while this one is consumed
 #pragma unroll
-                for (int r = 0; r < kRegN; ++r) {
-                    if (r < nA) {                                            // uniform
-                        const int k = idx8[r * NMAX + tt];
-                        const float p = hreg[u][r] * sm.b[k];
-                        acc += r < rlen[u] ? p : 0.0f;
+                    for (int j = 0; j < 4; ++j) {
+                        const float p = hn[j] * sm.b[(kn >> (8 * j)) & 255u];
+                        acc += n0 + j < rlen[u] ? p : 0.0f;
                     }
                 }
-                for (int n = max(nV, kRegN); n < nA; ++n) {
-                    const int k = idx8[n * NMAX + tt];
-                    const float p = value(mine[u], k) * sm.b[k];
-                    acc += n < rlen[u] ? p : 0.0f;
-                }
-                if (trip[u] > kIdxN) {
+                if (trip[u] > kSlabN) {
                     int w = cur_w[u];
                     uint32_t bits = cur_bits[u];
-                    for (int n = kIdxN; n < trip[u]; ++n) {
+                    for (int n = kSlabN; n < trip[u]; ++n) {
                         while (bits == 0u && w + 1 < Wn) { ++w; bits = t >= 0 ? hrow[w] : 0u; }
                         const bool have = bits != 0u;                        // as above: no divergent region around the value, an ended row adds +0.0f
                         const int k = (w * 32 + __ffs(bits) - 1) & 255;
@@ -903,14 +904,14 @@ __device__ int angle_filter(SM& sm, int num, const float* __restrict__ lori, con
 // both graph stages + the final sum; a list of fewer than 2 correspondences cannot survive S9 (a single node ends with S = 0)
 template <class SM, bool LOOKUP, int ITERS, int REF_TIE>
 __device__ __forceinline__ float graph_score(SM& sm, int num, const float* __restrict__ table, const float* __restrict__ lori,
-                                             const float* __restrict__ rori, const float* __restrict__ ext, int& n_survivors, int stop_after = 2, int mode = 0)
+                                             const float* __restrict__ rori, const float* __restrict__ ext, SlabBuf slab, int& n_survivors, int stop_after = 2, int mode = 0)
 {
     n_survivors = num;                                                     // stop_after 0: the candidate list itself (S3 / S7)
     if (stop_after == 0) return 0.0f;
     // instantiations rather than flags inside the loops: the register budget is that of the path taken
-    if (mode == 2 && LOOKUP) num = dist_filter<SM, LOOKUP, ITERS, 2, REF_TIE>(sm, num, table, ext);
-    else if (mode >= 1) num = dist_filter<SM, LOOKUP, ITERS, 1, REF_TIE>(sm, num, table, ext);
-    else num = dist_filter<SM, LOOKUP, ITERS, 0, REF_TIE>(sm, num, table, ext);
+    if (mode == 2 && LOOKUP) num = dist_filter<SM, LOOKUP, ITERS, 2, REF_TIE>(sm, num, table, ext, slab);
+    else if (mode >= 1) num = dist_filter<SM, LOOKUP, ITERS, 1, REF_TIE>(sm, num, table, ext, slab);
+    else num = dist_filter<SM, LOOKUP, ITERS, 0, REF_TIE>(sm, num, table, ext, slab);
     n_survivors = num;                                                     // stop_after 1: corr2, the survivors of S8
     if (mode >= 1) {                                                       // the survivors' points back to 16-bit integers: what S9 and the correspondence export read
         for (int t = threadIdx.x; t < num; t += 64) {
@@ -947,24 +948,22 @@ __device__ __forceinline__ void tap_write(const GraphTap& tap, const SM& sm, con
 // =====================================================================================================================
 // texture lists: S7 (top-200 rows of the ADC row maxima) + S8b + S9
 // =====================================================================================================================
-// 14 lists per CU: 11 200 B of LDS (8 neighbour indices per row; sort keys, picked rows and the angle stage's orientations share what is left) and 128 registers
-// (26 spilled).  Measured (texture stage, 100k templates): 16 indices at 12 lists per CU 47.6 ms, 8 indices at 12 lists 51.6, 8 indices at 14 lists 46.2.
-#ifndef AFIS_TEX_CACHE
-#define AFIS_TEX_CACHE 2
-#endif
+// 14 lists per CU: 11 200 B of LDS (sort keys, picked rows and the angle stage's orientations share one union; the power iterations' values and neighbour indices live in
+// the workgroup's slab in global memory: kTexSlabWgBytes at slab + blockIdx.x * kTexSlabWgBytes) and 128 registers.
 #ifndef AFIS_TEX_WAVES
 #define AFIS_TEX_WAVES 4
 #endif
-typedef WaveSmem<kTopTex, AFIS_TEX_CACHE, false> TexSmem;
+typedef WaveSmem<kTopTex, false> TexSmem;
 constexpr int kTexRegs = (kTexMax + 63) / 64;     // 16 row maxima per lane: the wave holds all <= 1000 keys in registers
 
 template <int REF_TIE>   // 1: option ref_tie_order 2 (sort_scores); its own instantiation, so that the default kernel is the code it was
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAVES, AFIS_TEX_WAVES))) void k_graph_texture(QueryDev q, GalleryDev g, const float* __restrict__ table_dist,
                                                       const float* __restrict__ rm_val, const int32_t* __restrict__ rm_arg,
                                                       const float* __restrict__ rm_cv, const int32_t* __restrict__ rm_n,
-                                                      float* __restrict__ parts, GraphTap tap)
+                                                      float* __restrict__ parts, unsigned char* slab_all, GraphTap tap)
 {
     __shared__ TexSmem sm;
+    const SlabBuf slab = g_slab_buf(slab_all + (size_t)blockIdx.x * kTexSlabWgBytes, (uint32_t)kTexSlabWgBytes);
     const int lane = threadIdx.x;
     GPH_ZERO();
     const int n_tasks = q.nq * g.G;
@@ -1118,7 +1117,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
         GPH_K(15);                                                       // S7 + list build
         int n_surv;
         const float* const row_max = (rm_n ? rm_cv : rm_val) + o;           // the array the entries' slots index
-        const float score = graph_score<TexSmem, true, 3, REF_TIE>(sm, num, table_dist, q.lt_ori + l0, g.tex_ori + r0, row_max, n_surv, tap.out ? tap.stage : 2, mode);   // :759, :767
+        const float score = graph_score<TexSmem, true, 3, REF_TIE>(sm, num, table_dist, q.lt_ori + l0, g.tex_ori + r0, row_max, slab, n_surv, tap.out ? tap.stage : 2, mode);   // :759, :767
         if (lane == 0) *out = score;
         if (tap.out) tap_write(tap, sm, row_max, task, n_surv, kTopTex);
         WSYNC();
@@ -1127,41 +1126,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
 }
 
 hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const float* table_dist,
-                                const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream)
+                                const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream)
 {
     const long long n_tasks = (long long)q.nq * g.G;
     if (n_tasks <= 0) return hipSuccess;
     if (n_tasks > 0x7ffffff0LL || !g.task_ctr) return hipErrorInvalidValue;
-    const int grid = (int)(n_tasks < 16384 ? n_tasks : 16384);
+    const int grid = graph_texture_grid(n_tasks);
+    if (!slab || slab_bytes < (size_t)grid * kTexSlabWgBytes) return hipErrorInvalidValue;       // every workgroup writes its own kTexSlabWgBytes
     hipError_t e0 = hipMemsetAsync(g.task_ctr + 0, 0, 4, stream);
     if (e0 != hipSuccess) return e0;
     const GraphTap tap{tap_out, tap_n, tap_stage & 255};
-    if ((tap_stage >> 8) & 1) hipLaunchKernelGGL(k_graph_texture<1>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, tap);
-    else hipLaunchKernelGGL(k_graph_texture<0>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, tap);
+    if ((tap_stage >> 8) & 1) hipLaunchKernelGGL(k_graph_texture<1>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, (unsigned char*)slab, tap);
+    else hipLaunchKernelGGL(k_graph_texture<0>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, (unsigned char*)slab, tap);
     return hipGetLastError();
 }
 
 // =====================================================================================================================
 // minutiae lists (produced by k_minu_cands, already in rank order): S8a + S9
 // =====================================================================================================================
-#ifndef AFIS_MINU_CACHE
-#define AFIS_MINU_CACHE 3
-#endif
-typedef WaveSmem<kTopMinu, AFIS_MINU_CACHE, true> MinuGraphSmem;
+typedef WaveSmem<kTopMinu, true> MinuGraphSmem;
 
 // corr_out / corr_n (optional): the surviving correspondences of every task as (lx, ly, rx, ry), matcher.cpp:497-505
-// Six lists per SIMD: 6240 B of LDS (12 neighbour indices per row, no value stash: recomputing a value costs 20 instructions, the stash cost waves; the angle
-// stage's orientations borrow b[] / cc[]) and 80 registers.  Measured at 100k templates (minutiae stage, candidates included): 4 waves with 6 values + 16 indices per row
-// 93.7 ms, 5 waves with 24 indices 89.7-90.4, 6 waves with 12 indices 88.9 (12 indices at 5 waves: 92.3).
+// Six lists per SIMD: 80 registers; the power iterations' values and neighbour indices live in the workgroup's slab in global memory (kMinuSlabWgBytes at
+// slab + blockIdx.x * kMinuSlabWgBytes), the angle stage's orientations borrow b[] / cc[].  (An LDS stash of values cost waves: 4 waves with 6 values + 16 indices per row
+// 93.7 ms for the minutiae stage at 100k templates, 6 waves with 12 indices and no values 88.9.)
 #ifndef AFIS_MINU_WAVES
 #define AFIS_MINU_WAVES 6
 #endif
 template <int REF_TIE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WAVES, AFIS_MINU_WAVES))) void k_graph_minutiae(QueryDev q, GalleryDev g, const MinuCand* __restrict__ cands,
                                                        const int32_t* __restrict__ cand_n, float* __restrict__ parts,
-                                                       short4* __restrict__ corr_out, int32_t* __restrict__ corr_n, GraphTap tap)
+                                                       short4* __restrict__ corr_out, int32_t* __restrict__ corr_n, unsigned char* slab_all, GraphTap tap)
 {
     __shared__ MinuGraphSmem sm;
+    const SlabBuf slab = g_slab_buf(slab_all + (size_t)blockIdx.x * kMinuSlabWgBytes, (uint32_t)kMinuSlabWgBytes);
     const int lane = threadIdx.x;
     GPH_ZERO();
     const int n_tasks = q.nq * 3 * g.G;
@@ -1200,7 +1198,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WA
         WSYNC();
         GPH_K(7);                                                        // list load
         int n_surv;
-        const float score = graph_score<MinuGraphSmem, false, 5, REF_TIE>(sm, num, nullptr, q.lm_ori + l0, g.minu_ori + r0, nullptr, n_surv, tap.out ? tap.stage : 2, mode);   // :492, :495
+        const float score = graph_score<MinuGraphSmem, false, 5, REF_TIE>(sm, num, nullptr, q.lm_ori + l0, g.minu_ori + r0, nullptr, slab, n_surv, tap.out ? tap.stage : 2, mode);   // :492, :495
         if (lane == 0) *out = score;
         if (tap.out) tap_write(tap, sm, nullptr, task, n_surv, kTopMinu);
         if (corr_out) {
@@ -1216,18 +1214,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WA
 }
 
 hipError_t launch_graph_minutiae(const QueryDev& q, const GalleryDev& g, const MinuCand* cands, const int32_t* cand_n,
-                                 float* parts, short4* corr_out, int32_t* corr_n, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join)
+                                 float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join)
 {
     // join: a second instance of the kernel on another stream that draws from the SAME list counter as one already running (afis_search.cpp, option bound_cus): no reset
     const long long n_tasks = (long long)q.nq * 3 * g.G;
     if (n_tasks <= 0) return hipSuccess;
     if (n_tasks > 0x7ffffff0LL || !g.task_ctr) return hipErrorInvalidValue;
-    const int grid = (int)(n_tasks < 32768 ? n_tasks : 32768);
+    const int grid = graph_minutiae_grid(n_tasks);
+    if (!slab || slab_bytes < (size_t)grid * kMinuSlabWgBytes) return hipErrorInvalidValue;      // every workgroup writes its own kMinuSlabWgBytes; two instances that run at once get disjoint slabs from the caller
     hipError_t e0 = join ? hipSuccess : hipMemsetAsync(g.task_ctr + 1, 0, 4, stream);
     if (e0 != hipSuccess) return e0;
     const GraphTap tap{tap_out, tap_n, tap_stage & 255};
-    if ((tap_stage >> 8) & 1) hipLaunchKernelGGL(k_graph_minutiae<1>, dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, tap);
-    else hipLaunchKernelGGL(k_graph_minutiae<0>, dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, tap);
+    if ((tap_stage >> 8) & 1) hipLaunchKernelGGL(k_graph_minutiae<1>, dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, (unsigned char*)slab, tap);
+    else hipLaunchKernelGGL(k_graph_minutiae<0>, dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, (unsigned char*)slab, tap);
     return hipGetLastError();
 }
 
