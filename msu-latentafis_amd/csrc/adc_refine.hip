@@ -160,17 +160,21 @@ __global__ __launch_bounds__(256) void k_mf_rows(const float* __restrict__ lt_de
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Selection by bounds + exact evaluation.  Persistent workgroups of 8 waves (the fp32 codebook, 96 KB, in LDS); each wave draws
-// (latent, rolled) pairs from a counter and owns a 4 KB item list.
+// Selection by bounds + exact evaluation.  Persistent workgroups of 16 waves (the fp32 codebook, 96 KB, in LDS); each wave draws
+// (latent, rolled) pairs from a counter, kRfChunk at a time, and owns a 3.75 KB item list.
+// The counter is ONE address for the whole chip: an atomic per pair (10^7 a step) is served at about 13 ns each, which was the kernel's floor — whatever
+// else was taken out of a pair, 100 000 templates x 16 latents stayed at 21.4-22 ms (profiles/r08_refine_forms.txt).  Four pairs per draw lift it.
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int kRfWaves = 16, kRfItems = 384;        // 96 KB codebook + 16 x 3.75 KB item lists = 156 KB of LDS; <= 128 VGPRs
+constexpr int kRfBatches = 4;                       // code words of a flush: fetched 64 items per load instruction (lane = item), this many loads in flight
+constexpr int kRfChunk = 4;                         // pairs per draw from the task counter, in launches where every wave draws at least four times (otherwise one: a small search keeps every wave busy)
 struct __align__(16) RfWave { unsigned short row[kRfItems]; unsigned short pt[kRfItems]; unsigned short slot[kRfItems]; float val[kRfItems]; };
 
 __device__ __forceinline__ uint32_t ord_f32(float v) { const uint32_t b = f2u(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 // this wave's own LDS traffic in program order (the waves of the workgroup work on different pairs: no workgroup barrier may be used)
 #define RF_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 
-__device__ __forceinline__ int rf_next_task(int32_t* ctr)               // one atomic by lane 0 (see graph.hip::next_task for why it is asm)
+__device__ __forceinline__ int rf_next_task(int32_t* ctr, int chunk)    // one atomic by lane 0 (see graph.hip::next_task for why it is asm): the first of `chunk` pairs
 {
     int t;
     unsigned long long saved;
@@ -179,7 +183,7 @@ __device__ __forceinline__ int rf_next_task(int32_t* ctr)               // one a
                  "global_atomic_add %0, %2, %3, %4 sc0\n\t"
                  "s_waitcnt vmcnt(0)\n\t"
                  "s_mov_b64 exec, %1"
-                 : "=&v"(t), "=&s"(saved) : "v"(0), "v"(1), "s"(ctr) : "memory");
+                 : "=&v"(t), "=&s"(saved) : "v"(0), "v"(chunk), "s"(ctr) : "memory");
     return __builtin_amdgcn_readfirstlane(t);
 }
 
@@ -198,7 +202,7 @@ __device__ __forceinline__ void rf_argmax(float& v, int& i)             // value
 __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, GalleryDev g, const float* __restrict__ cw32, const uint2* __restrict__ rec,
                                                                const float4* __restrict__ rowk, int R_pad, int all_rows, float* __restrict__ rm_val,
                                                                int32_t* __restrict__ rm_arg, int32_t* __restrict__ task_ctr, unsigned long long* __restrict__ stats,
-                                                               float* __restrict__ rm_cv, int32_t* __restrict__ rm_n)
+                                                               float* __restrict__ rm_cv, int32_t* __restrict__ rm_n, int chunk)
 {
     __shared__ float s_cw[kM * kK * kDsub];                             // 96 KB
     __shared__ RfWave s_w[kRfWaves];                                    // 32 KB
@@ -207,9 +211,14 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
     const int lane = threadIdx.x & 63;
     RfWave& W = s_w[threadIdx.x >> 6];
     const int n_tasks = q.nq * g.G;
+    int t_next = 0, t_end = 0;
     for (;;) {
-        const int task = rf_next_task(task_ctr);
-        if (task >= n_tasks) break;
+        if (t_next >= t_end) {
+            t_next = rf_next_task(task_ctr, chunk);
+            if (t_next >= n_tasks) break;
+            t_end = min(t_next + chunk, n_tasks);
+        }
+        const int task = t_next++;
         const int qi = task / g.G, gi = task - qi * g.G;
         const int l0 = q.lt_off[qi], n_lt = q.lt_off[qi + 1] - l0;
         const int r0 = g.tex_off[gi], n_rt = g.tex_off[gi + 1] - r0;
@@ -294,9 +303,7 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
         // The same value with FOUR lanes per item, lane = one of the reference's four chains (matcher.cpp:571-592: chain c subtracts the entries of sub-quantizers c, c + 4, c + 8, c + 12
         // in that order from 6 / 0 / 0 / 0; the chains meet as (d0 + d1) + (d2 + d3)): the four lanes of an item read 96 contiguous bytes of the latent row per step instead of every
         // lane walking its own 384-byte row (64 cache lines per load instruction, 24 instructions per item: the address path of the CU, not the arithmetic, was what the wave waited for).
-        auto exact_sim4 = [&](int e, int p, int c) -> float {                // valid in the lanes with c == 0
-            const uint4 cd = g.tex_codes[r0 + p];
-            const uint32_t w4[4] = {cd.x, cd.y, cd.z, cd.w};
+        auto exact_sim4 = [&](const uint32_t (&w4)[4], int e, int c) -> float {   // valid in the lanes with c == 0
             const float2* a2 = reinterpret_cast<const float2*>(des + (size_t)e * kDes);
             float d = c == 0 ? 6.0f : 0.0f;
             float2 av[4][3];
@@ -318,13 +325,33 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
             const float u2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s2), 0xAA, 0xf, 0xf, false)); // quad_perm [2, 2, 2, 2]
             return s2 + u2;                                                                                            // lane 0: (d0 + d1) + (d2 + d3)
         };
+        // The items of a flush are known before it starts, so their code words (a 16-byte gather at a random point of the template: first touch, HBM) are fetched with lane = item,
+        // 64 items per load instruction and up to kRfBatches such batches in flight before the first is used: one exposed round trip per 256 items instead of one per trip of
+        // sixteen.  A trip takes its items' words out of the owning lanes' registers (four ds_bpermute_b32).
         auto flush = [&]() {
             RF_WSYNC();
-            for (int it0 = 0; it0 < n_items; it0 += 16) {                   // sixteen items per trip
-                const int it = it0 + (lane >> 2);
-                const bool ok = it < n_items;
-                const float v = exact_sim4(W.row[ok ? it : 0], W.pt[ok ? it : 0], lane & 3);
-                if (ok && (lane & 3) == 0) W.val[it] = v;
+            for (int sb = 0; sb < n_items; sb += kRfBatches * 64) {
+                uint4 cd[kRfBatches];
+#pragma unroll
+                for (int b = 0; b < kRfBatches; ++b) {
+                    cd[b] = make_uint4(0u, 0u, 0u, 0u);
+                    const int it = sb + b * 64 + lane;
+                    if (sb + b * 64 < n_items) cd[b] = g.tex_codes[r0 + (it < n_items ? (int)W.pt[it] : 0)];
+                }
+                const int sb_end = min(sb + kRfBatches * 64, n_items);
+                for (int it0 = sb; it0 < sb_end; it0 += 16) {               // sixteen items per trip
+                    const int it = it0 + (lane >> 2);
+                    const bool ok = it < n_items;
+                    const int b = (it0 - sb) >> 6;                          // wave-uniform: the batch this trip's items were fetched in
+                    uint4 cb = cd[0];
+#pragma unroll
+                    for (int k = 1; k < kRfBatches; ++k) if (b == k) cb = cd[k];
+                    const int src = ((it0 & 63) + (lane >> 2)) << 2;        // the lane that holds the item's words (sb is a multiple of 64)
+                    const uint32_t w4[4] = {(uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cb.x), (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cb.y),
+                                            (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cb.z), (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cb.w)};
+                    const float v = exact_sim4(w4, W.row[ok ? it : 0], lane & 3);
+                    if (ok && (lane & 3) == 0) W.val[it] = v;
+                }
             }
             RF_WSYNC();
             for (int it = lane; it < n_items; it += 64) {
@@ -348,88 +375,118 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
             n_items = 0;
             RF_WSYNC();
         };
-        // (the record and the row constants of round u + 1 are fetched before round u is worked on: one exposed memory round trip per pair instead of one per round)
+        // the record and the row constants of round u + 1 are fetched before round u is worked on (ra_n, rk_n): one exposed memory round trip per pair instead of one per round
         uint2 ra_n = make_uint2(0u, 0u); float4 rk_n = make_float4(0.f, 0.f, 0.f, 0.f);
         if (lane < n_lt) { ra_n = rec0[lane]; rk_n = rowk[l0 + lane]; }
-        for (int u = 0; u < n_regs; ++u) {
-            const int e = u * 64 + lane;
-            const bool in = e < n_lt;
-            const uint2 ra = ra_n; const float4 rkc = rk_n;
-            if (e + 64 < n_lt) { ra_n = rec0[e + 64]; rk_n = rowk[l0 + e + 64]; }
-            bool active = false;
-            if (in) {
-                float lo, hi; bounds_rk(rkc, ra, lo, hi);
-                active = ord_f32(hi) >= C;
+        // A third of the rows is active.  A round of 64 rows only QUEUES its active rows (descriptor, row) — in the wave's value buffer, idle outside flush() and the full-row scan —
+        // and the candidate cells are worked out 64 ACTIVE rows at a time: four such steps per pair instead of eleven.  What stays queued while a step runs (fewer than 64 entries)
+        // waits in two registers, because the step may flush or scan a full row through the buffer.
+        uint32_t* qd = reinterpret_cast<uint32_t*>(W.val);              // [0, 128): descriptors, [128, 256): rows
+        int n_pend = 0;
+        // One loop body for three kinds of round, so that flush() is expanded ONCE: rounds 0 .. n_regs - 1 queue (and run a step when 64 rows are queued), round n_regs runs the
+        // step that drains the queue, round n_regs + 1 is the last flush.  (A second expansion of flush() after the loop: 15 288 bytes of kernel code against 13 156, same registers;
+        // not timed.)  The step's results that the append below needs (cnt, pts, incl, total, my_slot, e_it) and what stays queued (rest, sv_d, sv_e) therefore live outside the `if`s.
+        for (int u = 0; ; ++u) {
+            const bool fin = u > n_regs;
+            uint32_t pts[4] = {0u, 0u, 0u, 0u}; int cnt = 0, incl = 0, total = 0, my_slot = 0, rest = 0;
+            uint32_t e_it = 0u, sv_d = 0u, sv_e = 0u;
+            if (u < n_regs) {
+                const int e = u * 64 + lane;
+                const bool in = e < n_lt;
+                const uint2 ra = ra_n; const float4 rkc = rk_n;
+                if (e + 64 < n_lt) { ra_n = rec0[e + 64]; rk_n = rowk[l0 + e + 64]; }
+                bool active = false;
+                if (in) {
+                    float lo, hi; bounds_rk(rkc, ra, lo, hi);
+                    active = ord_f32(hi) >= C;
+                }
+                if (in && !active && !compact) { rm_val[o + e] = -INFINITY; rm_arg[o + e] = 0; }
+                const unsigned long long am = __ballot(active);
+                const int pos = n_pend + __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0));   // < 64 + 63
+                if (active) { qd[pos] = ra.y; qd[128 + pos] = (uint32_t)e; }
+                n_pend += (int)__popcll(am);
+                st_active += (unsigned long long)__popcll(am);
             }
-            if (in && !active && !compact) { rm_val[o + e] = -INFINITY; rm_arg[o + e] = 0; }
-            // compact form: the active rows' (value, row | point << 16) side by side in row order (what S7 reads: a third of the rows), values also at their row (for the list's sums)
-            const unsigned long long am = __ballot(active);
-            const int my_slot = n_act + __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0));
-            n_act += (int)__popcll(am);
-            uint32_t pts[4]; int cnt = 0; bool full = false;
-            if (active) {
-                const uint32_t dsc = ra.y;
-                full = (dsc >> 20) & 1u;
-                const uint32_t hp = (dsc >> 21) & 1u;                   // the primary half: {its groups} x {its slots}
-                const uint32_t tt[2] = {dsc & 63u, (dsc >> 6) & 63u}, kk[2] = {(dsc >> 12) & 7u, (dsc >> 15) & 7u};
-                const int nt = 1 + (int)((dsc >> 18) & 1u), nk = 1 + (int)((dsc >> 19) & 1u);
-                auto add = [&](uint32_t grp, uint32_t slot, uint32_t hh, bool take) {
-                    const uint32_t rr = slot + 8u * (grp & 1u);
-                    const uint32_t p = 32u * (grp >> 1) + (rr & 3u) + 8u * (rr >> 2) + 4u * hh;
-                    if (take && p < (uint32_t)n_rt) {
-#pragma unroll
-                        for (int z = 0; z < 4; ++z) if (z == cnt) pts[z] = p;
-                        ++cnt;
-                    }
-                };
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) add(tt[a], kk[b], hp, a < nt && b < nk);
-                add((dsc >> 23) & 63u, dsc >> 29, hp ^ 1u, (dsc >> 22) & 1u);   // the other half's best cell, when within reach
-                full = full || cnt > 4;                                 // five candidate cells (a full primary half and the other half): every point instead
-                if (full) cnt = 0;
-            }
-            st_active += (unsigned long long)__popcll(__ballot(active));
-            // rows whose candidates the bound pass could not pin down (or forced rows): every point, exactly — the whole wave per row
-            unsigned long long fm = __ballot(active && full);
-            while (fm) {
-                const int src = (int)__ffsll((long long)fm) - 1;
-                fm &= fm - 1;
-                const int row = u * 64 + src;
-                // std::max_element (matcher.cpp:730): the first point's value stands until a STRICTLY greater one comes.  A NaN similarity never compares
-                // greater, and a NaN at point 0 (a NaN in the latent row: every similarity of the row is NaN) is never beaten; a row of -inf
-                // (an infinite or overflowing descriptor) keeps point 0 as well.
-                // The row's descriptor goes through the wave's (idle: values only live inside flush()) value buffer: every trip of the loop used to fetch its 96 floats again — 24 vector loads of
-                // ONE address per lane and trip (13 trips per row): the texture path, not the arithmetic, was what a full row cost.  From LDS they are 24 broadcast reads.
-                if (lane < 24) reinterpret_cast<float4*>(W.val)[lane] = reinterpret_cast<const float4*>(des + (size_t)row * kDes)[lane];
+            const int take = fin ? 0 : n_pend >= 64 ? 64 : u == n_regs ? n_pend : 0;
+            if (take > 0) {
                 RF_WSYNC();
-                float bv = -INFINITY, v_first = 0.0f; int bp = 0x7fffffff;
-                for (int p = lane; p < n_rt; p += 64) { const float v = exact_sim_lds(p); if (p == lane) v_first = v; if (v > bv) { bv = v; bp = p; } }
-                RF_WSYNC();
-                rf_argmax(bv, bp);
-                const float s0 = __shfl(v_first, 0);                    // n_rt >= 1: lane 0 evaluated point 0
-                if (s0 != s0 || bp == 0x7fffffff) { bv = s0; bp = 0; }
-                const int sl = __shfl(my_slot, src);
-                if (lane == 0) { if (compact) { rm_cv[o + sl] = bv; rm_arg[o + sl] = row | (bp << 16); } else { rm_val[o + row] = bv; rm_arg[o + row] = bp; } }
-                ++st_full;
-            }
-            // append this round's items, rows in ascending order (a row's items stay adjacent)
-            int incl = cnt;                                             // inclusive prefix sum over the lanes: four row_shr steps inside the rows of 16 lanes, then the totals of the rows below (no LDS permutes)
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, true);
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, true);
-            const int t0 = __builtin_amdgcn_readlane(incl, 15), t1 = __builtin_amdgcn_readlane(incl, 31), t2 = __builtin_amdgcn_readlane(incl, 47), t3 = __builtin_amdgcn_readlane(incl, 63);
-            incl += lane < 16 ? 0 : lane < 32 ? t0 : lane < 48 ? t0 + t1 : t0 + t1 + t2;
-            const int total = t0 + t1 + t2 + t3;
-            if (n_items + total > kRfItems) flush();
-            const int base = n_items + incl - cnt;
+                const bool have = lane < take;
+                const uint32_t dsc = qd[lane];
+                e_it = qd[128 + lane];
+                rest = n_pend - take;                                   // < 64
+                sv_d = qd[64 + lane]; sv_e = qd[192 + lane];
+                // compact form: the active rows' (value, row | point << 16) side by side in row order (what S7 reads: a third of the rows), values also at their row (for the list's sums)
+                my_slot = n_act + lane;
+                n_act += take;
+                bool full = false;
+                if (have) {
+                    full = (dsc >> 20) & 1u;
+                    const uint32_t hp = (dsc >> 21) & 1u;                   // the primary half: {its groups} x {its slots}
+                    const uint32_t tt[2] = {dsc & 63u, (dsc >> 6) & 63u}, kk[2] = {(dsc >> 12) & 7u, (dsc >> 15) & 7u};
+                    const int nt = 1 + (int)((dsc >> 18) & 1u), nk = 1 + (int)((dsc >> 19) & 1u);
+                    auto add = [&](uint32_t grp, uint32_t slot, uint32_t hh, bool take_it) {
+                        const uint32_t rr = slot + 8u * (grp & 1u);
+                        const uint32_t p = 32u * (grp >> 1) + (rr & 3u) + 8u * (rr >> 2) + 4u * hh;
+                        if (take_it && p < (uint32_t)n_rt) {
 #pragma unroll
-            for (int z = 0; z < 4; ++z) if (z < cnt) { W.row[base + z] = (unsigned short)e; W.pt[base + z] = (unsigned short)pts[z]; W.slot[base + z] = (unsigned short)my_slot; }
-            n_items += total;
+                            for (int z = 0; z < 4; ++z) if (z == cnt) pts[z] = p;
+                            ++cnt;
+                        }
+                    };
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int b = 0; b < 2; ++b) add(tt[a], kk[b], hp, a < nt && b < nk);
+                    add((dsc >> 23) & 63u, dsc >> 29, hp ^ 1u, (dsc >> 22) & 1u);   // the other half's best cell, when within reach
+                    full = full || cnt > 4;                                 // five candidate cells (a full primary half and the other half): every point instead
+                    if (full) cnt = 0;
+                }
+                // rows whose candidates the bound pass could not pin down (or forced rows): every point, exactly — the whole wave per row
+                unsigned long long fm = __ballot(have && full);
+                while (fm) {
+                    const int src = (int)__ffsll((long long)fm) - 1;
+                    fm &= fm - 1;
+                    const int row = (int)__shfl(e_it, src);
+                    // std::max_element (matcher.cpp:730): the first point's value stands until a STRICTLY greater one comes.  A NaN similarity never compares
+                    // greater, and a NaN at point 0 (a NaN in the latent row: every similarity of the row is NaN) is never beaten; a row of -inf
+                    // (an infinite or overflowing descriptor) keeps point 0 as well.
+                    // The row's descriptor goes through the wave's value buffer (what it queued is in registers by now): every trip of the loop used to fetch its 96 floats again — 24 vector loads of
+                    // ONE address per lane and trip (13 trips per row): the texture path, not the arithmetic, was what a full row cost.  From LDS they are 24 broadcast reads.
+                    RF_WSYNC();
+                    if (lane < 24) reinterpret_cast<float4*>(W.val)[lane] = reinterpret_cast<const float4*>(des + (size_t)row * kDes)[lane];
+                    RF_WSYNC();
+                    float bv = -INFINITY, v_first = 0.0f; int bp = 0x7fffffff;
+                    for (int p = lane; p < n_rt; p += 64) { const float v = exact_sim_lds(p); if (p == lane) v_first = v; if (v > bv) { bv = v; bp = p; } }
+                    RF_WSYNC();
+                    rf_argmax(bv, bp);
+                    const float s0 = __shfl(v_first, 0);                    // n_rt >= 1: lane 0 evaluated point 0
+                    if (s0 != s0 || bp == 0x7fffffff) { bv = s0; bp = 0; }
+                    const int sl = __shfl(my_slot, src);
+                    if (lane == 0) { if (compact) { rm_cv[o + sl] = bv; rm_arg[o + sl] = row | (bp << 16); } else { rm_val[o + row] = bv; rm_arg[o + row] = bp; } }
+                    ++st_full;
+                }
+                // this step's items, rows in ascending order (a row's items stay adjacent)
+                incl = cnt;                                                 // inclusive prefix sum over the lanes: four row_shr steps inside the rows of 16 lanes, then the totals of the rows below (no LDS permutes)
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, true);
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, true);
+                const int t0 = __builtin_amdgcn_readlane(incl, 15), t1 = __builtin_amdgcn_readlane(incl, 31), t2 = __builtin_amdgcn_readlane(incl, 47), t3 = __builtin_amdgcn_readlane(incl, 63);
+                incl += lane < 16 ? 0 : lane < 32 ? t0 : lane < 48 ? t0 + t1 : t0 + t1 + t2;
+                total = t0 + t1 + t2 + t3;
+            }
+            if (fin || n_items + total > kRfItems) flush();
+            if (fin) break;
+            if (take > 0) {
+                const int base = n_items + incl - cnt;
+#pragma unroll
+                for (int z = 0; z < 4; ++z) if (z < cnt) { W.row[base + z] = (unsigned short)e_it; W.pt[base + z] = (unsigned short)pts[z]; W.slot[base + z] = (unsigned short)my_slot; }
+                n_items += total;
+                RF_WSYNC();                                             // the step's reads of the queue (and a full row's descriptor) before what stays queued goes back to its head
+                if (lane < rest) { qd[lane] = sv_d; qd[128 + lane] = sv_e; }
+                n_pend = rest;
+            }
         }
-        flush();
         if (compact && lane == 0) rm_n[task] = n_act;
         if (stats && lane == 0) {
             atomicAdd(stats + 0, 1ull); atomicAdd(stats + 1, (unsigned long long)n_lt); atomicAdd(stats + 2, st_active);
@@ -464,12 +521,13 @@ hipError_t launch_tex_refine(const QueryDev& q, const GalleryDev& g, const float
 {
     const long long n_tasks = (long long)q.nq * g.G;
     if (n_tasks <= 0) return hipSuccess;
-    if (n_tasks > 0x7ffffff0LL || !g.task_ctr) return hipErrorInvalidValue;
+    if (n_tasks > 0x7fff0000LL || !g.task_ctr) return hipErrorInvalidValue;   // (every wave's last draw adds kRfChunk beyond n_tasks: 16 384 in all)
     hipError_t e0 = hipMemsetAsync(g.task_ctr + 2, 0, 4, stream);
     if (e0 != hipSuccess) return e0;
     const int grid = (int)std::min<long long>(256, (n_tasks + kRfWaves - 1) / kRfWaves);
+    const int chunk = n_tasks >= 4LL * kRfChunk * grid * kRfWaves ? kRfChunk : 1;
     hipLaunchKernelGGL(k_tex_refine, dim3(grid), dim3(kRfWaves * 64), 0, stream, q, g, codewords, (const uint2*)rec, (const float4*)rowk, R_pad, all_rows,
-                       rm_val, rm_arg, g.task_ctr + 2, stats, rm_cv, rm_n);
+                       rm_val, rm_arg, g.task_ctr + 2, stats, rm_cv, rm_n, chunk);
     return hipGetLastError();
 }
 
