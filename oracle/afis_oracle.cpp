@@ -11,13 +11,16 @@
 //     third-party dependency).
 //   * The PQ encoder (orc_pq_encode; SURVEY §8f-1, extraction/descriptor_PQ.py:19-27) is PINNED to scipy.cluster.vq.vq — the
 //     routine the reference calls — through tests/golden/golden_pq.npz (made by tests/golden/make_golden_pq.py).
-//   * Everything that lives in /root/reference/matching/matcher.cpp (S1-S3, S5-S11, F1, F2) is
-//     "PARITY UNPINNED": matcher.cpp needs Eigen and Boost.Filesystem, which are neither in the
-//     reference tree nor in this image, the reference ships no tests or golden vectors for this
-//     path, and the three scores in sample_data/sample_scores.txt need the Python-2/TF-1.3
-//     extraction stack to reproduce.  Those stages are restated line by line below with the
-//     reference's evaluation order, float/double promotions and thresholds, each citing the
-//     file:line it follows.
+//   * Everything that lives in the reference's matching/matcher.cpp (S1-S3, S5-S11, F1, F2: similarity, normalisation, top-120,
+//     the texture scorer, both graph filters, fusion, status rules, both loaders, the codebook constructor) is PINNED to a RECORD
+//     of the reference's own translation unit: tests/golden/golden_matcher_ref.npz, made by tests/golden/make_golden_matcher_ref.py
+//     from matcher.cpp compiled unmodified against the stand-in headers of oracle/standin/ (oracle/ref_matcher_harness.cpp).
+//     tests/test_reference_record.py holds this file's tie mode 0 to the record bit for bit: whole score vectors in every recorded
+//     accumulation order, status, loaders' codes, stage lists, correspondence files, List2List digits.  Pinned thereby: the
+//     reference's control flow, comparisons, promotions, thresholds, loaders and sort calls.  NOT pinned: Eigen's own summation
+//     order, which in that build is the stand-in's (the order family below) — the one residual assumption.  Inputs on which the
+//     reference has no defined answer (DESIGN.md section 2 lists them with line numbers) are not in the record; what this file
+//     does there is the project's reading.
 //
 // Where the reference's arithmetic order is not its own (Eigen GEMM / mat-vec / reductions,
 // matcher.cpp:443,455-456,1286-1288,1408-1410 — Eigen version unpinned) this file fixes a

@@ -3,9 +3,8 @@
 //
 // TEST INFRASTRUCTURE ONLY (see oracle/afis_oracle.cpp header).  Output: oracle/_ref/libafis_ref.so.
 //
-// Only matching/include.h is buildable in this image: it is self-contained.  matching/matcher.cpp needs
-// Eigen and Boost.Filesystem, which are absent from the reference tree and from the image, so it is
-// treated as unbuildable (no stand-in headers are written for it).  What this pins:
+// matching/include.h is self-contained.  (matching/matcher.cpp needs Eigen and Boost.Filesystem, absent from the reference tree:
+// it is built against stand-in headers by its own harness, ref_matcher_harness.cpp.)  What this one pins:
 //   * LatentTextureTemplate::compute_dist_to_codewords (include.h:327-359)  -> S4, the per-query PQ LUT
 //   * RolledTextureTemplatePQ(n,x,y,ori,des_len,des)  (include.h:401-406)   -> PQ code extraction from the
 //     float-typed read buffer, and the short->int point conversion (include.h:171-193)

@@ -219,3 +219,440 @@ def reference_similarities(lut_row, codes):
             m = 4 * mg + c
             d[c] = (d[c] - lut_row[m][codes[:, m]]).astype(np.float32)
     return ((d[0] + d[1]).astype(np.float32) + (d[2] + d[3]).astype(np.float32)).astype(np.float32)
+
+
+# ---- inputs that several tests share and that tests/golden/make_golden_matcher_ref.py runs through the reference's own matcher.cpp ----
+# Each function takes its seed as a parameter; the defaults are the seeds the GPU parity tests have always used.
+def _SS():
+    return importlib.import_module("msu-latentafis_amd.host.synth_structured")
+
+
+STRUCTURED_CONFIGS = ((10, 4, 30, 0.3, None), (30, 2, 40, 1.0, 0.0057))      # (share of repeated code vectors in %, latents, gallery, identity weight, sigma or None = DUP_SIGMA)
+
+
+def structured_set(cb, dup, n_lat, n_gal, identity_weight, sigma=None, seed=None):
+    """One configuration of the structured sweep (host/synth_structured.py): latents, gallery (mates of latent q at 2q and 2q + 1, then non-mates)."""
+    SS = _SS()
+    sg = SS.DUP_SIGMA[dup] if sigma is None else sigma
+    keep = SS.IDENTITY_WEIGHT
+    SS.IDENTITY_WEIGHT = identity_weight
+    try:
+        rng = np.random.default_rng(600 + dup if seed is None else seed)
+        lats = [SS.make_structured_latent(rng, sigma=sg) for _ in range(n_lat)]
+        gal = [SS.make_structured_mate(rng, cb, L, frac=f, sigma=sg) for L in lats for f in (0.8, 0.3)]
+        while len(gal) < n_gal: gal.append(SS.make_structured_rolled(rng, cb, sigma=sg))
+    finally:
+        SS.IDENTITY_WEIGHT = keep
+    return lats, gal
+
+
+def edge_shapes_set(cb, seed=42):
+    """Shapes off the fast paths: > 64 latent / > 128 rolled minutiae, texture templates above the 1000-point clamp, tiny templates, duplicated points."""
+    rng = np.random.default_rng(seed)
+    big = S.make_latent(rng, n_tex_lo=1100, n_tex_hi=1200, n_minu_lo=90, n_minu_hi=110)        # texture > 1000 rows, minutiae > 64
+    tiny = S.make_latent(rng, n_tex_lo=40, n_tex_hi=60, n_minu_lo=3, n_minu_hi=6)
+    dup = S.make_latent(rng, n_tex_lo=230, n_tex_hi=260)
+    t0 = dup.tex[0]
+    t0.x[50:100] = t0.x[0:50]; t0.y[50:100] = t0.y[0:50]; t0.des[50:100] = t0.des[0:50]; t0.ori[50:100] = t0.ori[0:50]   # exact duplicates
+    lats = [big, tiny, dup]
+    gal = []
+    for L in lats:
+        gal.append(S.make_mate(rng, cb, L, frac=0.8, n_minu=min(300, max(8, len(L._pool[0]) * 3)), n_tex=1300 if L is big else 500))
+        gal.append(S.make_mate(rng, cb, L, frac=0.4, n_minu=150, n_tex=700))
+    gal.append(S.make_rolled(rng, cb, n_minu=5, n_tex=30))
+    gal.append(S.make_rolled(rng, cb, n_minu=260, n_tex=1900))
+    return lats, gal
+
+
+def degenerate_key_pairs(cb, seed=5):
+    """(latent, rolled) pairs whose S3 keys are degenerate for latent template 26: (a) fewer than 120 non-zero similarities, (b) every similarity identical,
+    (c) a few levels with large blocks of exact ties straddling the 120th place."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng)
+    d = rng.standard_normal(96).astype(np.float32); d *= np.float32(1.73) / np.linalg.norm(d)
+    e = rng.standard_normal(96).astype(np.float32); e -= d * (e @ d) / (d @ d); e *= np.float32(1.73) / np.linalg.norm(e)     # orthogonal to d
+
+    def latent_with(des_rows):
+        L = T.FPTemplate(minu=list(base.minu), tex=list(base.tex))
+        n = len(des_rows)
+        L.minu[26] = T.MinutiaeTemplate(rng.integers(50, 700, n).astype(np.int16), rng.integers(50, 700, n).astype(np.int16),
+                                        rng.uniform(-3, 3, n).astype(np.float32), np.stack(des_rows).astype(np.float32))
+        return L
+
+    def rolled_with(des_rows):
+        n = len(des_rows)
+        R = S.make_rolled(rng, cb, n_minu=n, n_tex=300)
+        R.minu[0] = T.MinutiaeTemplate(R.minu[0].x, R.minu[0].y, R.minu[0].ori, np.stack(des_rows).astype(np.float32))
+        return R
+
+    return [
+        (latent_with([d] * 30), rolled_with([-d] * 37 + [d] * 3)),                      # (a) 90 non-zero of 1200
+        (latent_with([d] * 32), rolled_with([d] * 40)),                                  # (b) 1280 identical keys
+        (latent_with([d] * 10 + [e] * 22), rolled_with([d] * 10 + [0.5 * d + 0.5 * e] * 30)),   # (c) a few levels, large tie blocks
+    ]
+
+
+PACKED_PATH_OFFSETS = ((0, 0, 1), (2040, 1500, 1), (5000, 4000, 3), (30000, 250, 1))      # (latent offset, rolled offset, scale)
+
+
+def packed_path_pairs(cb, seed=33):
+    """(latent, rolled) pairs with minutiae pixel coordinates inside [0, 2047], straddling it, and far beyond (S8a's generic float arithmetic)."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng, n_tex_lo=210, n_tex_hi=240)
+    R0 = S.make_mate(rng, cb, base, frac=0.8, n_tex=300)
+    out = []
+    for off_l, off_r, scale in PACKED_PATH_OFFSETS:
+        def shift(m, off):
+            x = (m.x.astype(np.int64) * scale + off).astype(np.uint16).view(np.int16)
+            y = (m.y.astype(np.int64) * scale + off).astype(np.uint16).view(np.int16)
+            return T.MinutiaeTemplate(x, y, m.ori, m.des)
+        L = T.FPTemplate(minu=[shift(m_, off_l) for m_ in base.minu], tex=list(base.tex))
+        R = T.FPTemplate(minu=[shift(R0.minu[0], off_r)], tex=list(R0.tex))
+        out.append((L, R))
+    return out
+
+
+TIED_ROW_GROUPS = ([], [(10, 40)], [(5, 330)], [(50, 90), (120, 300)])
+
+
+def tied_row_maxima_set(cb, seed=33):
+    """(latents, rolled): latent texture rows that share a descriptor have bit-identical similarity rows, hence equal maxima — none, inside the top 200,
+    straddling the 200th place, two groups."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng, n_tex_lo=330, n_tex_hi=360)
+    R = S.make_mate(rng, cb, base, frac=0.7, n_tex=600)
+    t0 = base.tex[0]
+    lats = []
+    for groups in TIED_ROW_GROUPS:
+        des = t0.des.copy()
+        for lo, hi in groups:
+            des[lo:hi] = des[lo]
+        lats.append(T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(t0.x, t0.y, t0.ori, des=des)]))
+    return lats, R
+
+
+def both_signs_set(cb, seed=905, n_gal=40):
+    """Structured latents of 201 .. 256 texture rows against prints whose descriptors point away from theirs: the 200 best row maxima have both signs."""
+    SS = _SS()
+    rng = np.random.default_rng(seed)
+    keep = SS.IDENTITY_WEIGHT
+    SS.IDENTITY_WEIGHT = 1.0
+    try:
+        lats = [SS.make_structured_latent(rng, sigma=0.0095, n_tex_lo=200, n_tex_hi=260) for _ in range(2)]
+        gal = [SS.make_structured_rolled(rng, cb, sigma=0.0095, n_minu=int(rng.integers(20, 128)), n_tex=300) for _ in range(n_gal)]
+    finally:
+        SS.IDENTITY_WEIGHT = keep
+    return lats, gal
+
+
+def nan_inf_set(cb, seed=404):
+    """(latent with NaN / +-inf / huge / denormal texture descriptor rows, the same latent without them, gallery of 3 random prints and a mate)."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng, n_tex_lo=300, n_tex_hi=320)
+    lt = base.tex[0]
+    des = lt.des.copy()
+    des[3, 5] = np.nan; des[4, :] = np.nan; des[9, 0] = np.inf; des[10, 95] = -np.inf; des[11, 40] = np.inf; des[11, 41] = -np.inf
+    des[20, 7] = 7e4; des[21, 8] = -3e38; des[22, :] = 1e-42; des[23, 17] = 1001.0; des[24, 17] = 999.0; des[25, :] = 0.0
+    lat = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(lt.x, lt.y, lt.ori, des=des)])
+    gal = [S.make_rolled(rng, cb, n_tex=n) for n in (640, 33, 1)] + [S.make_mate(rng, cb, base, frac=0.6, n_tex=500)]
+    clean = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(lt.x, lt.y, lt.ori, des=lt.des)])
+    return lat, clean, gal
+
+
+def wide_slice(cb, seed=88, n_lat=2, n_gal=12):
+    """A slice of the "wide" workload (host/synth.py WORKLOADS): rolled prints of 130 +- 40 minutiae, latent templates of 20 .. 150, mates planted."""
+    w = S.WORKLOADS["wide"]
+    lats = S.make_latents(seed, n_lat, **w["latent"])
+    packed = S.make_packed_gallery(seed, n_gal, cb, **w["gallery"])
+    S.plant_mates(seed, packed, cb, lats)
+    return lats, [packed.template(g) for g in range(n_gal)]
+
+
+TEXTURE_SPREAD = ((25, 0, 0), (25, 9000, 9000), (10, 40000, 40000), (25, 0, 8180))      # (scale in tenths, latent offset, rolled offset)
+
+
+def texture_spread_pairs(cb, seed=21):
+    """(latent, rolled) pairs whose texture block coordinates are spread over 0..120 (many point pairs with |dx| or |dy| of 50 and more, the range rule of
+    matcher.cpp:1257, some of exactly 50), moved beyond 8191 and beyond 32767 (negative as the reference reads them)."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng, n_tex_lo=260, n_tex_hi=300)
+
+    def spread(t, scale, offset=0):
+        x = ((t.x.astype(np.int64) * scale) // 10 + offset).astype(np.int64)
+        y = ((t.y.astype(np.int64) * scale) // 10 + offset).astype(np.int64)
+        return x.astype(np.uint16).view(np.int16), y.astype(np.uint16).view(np.int16)
+
+    out = []
+    for scale, off_l, off_r in TEXTURE_SPREAD:
+        L = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(*spread(base.tex[0], scale, off_l), base.tex[0].ori, des=base.tex[0].des)])
+        R0 = S.make_mate(rng, cb, base, frac=0.7, n_tex=500)
+        rx, ry = spread(R0.tex[0], scale, off_r)
+        out.append((L, T.FPTemplate(minu=list(R0.minu), tex=[T.TextureTemplate(rx, ry, R0.tex[0].ori, codes=R0.tex[0].codes)])))
+    return out
+
+
+def s9_limit_pairs(cb, seed=17):
+    """(latent, rolled) pairs planted ON the limits of the angle tests of matcher.cpp:1503-1540.  Latent template 26 and the rolled minutiae template hold two
+    minutiae each, at the same coordinates on a horizontal line (the line's angle is exactly 0), with orthogonal descriptors, so that the candidate list starts with
+    the two true correspondences.  The rolled orientations are 0; the latent ones make one test's angle difference exactly a chosen float (eight pairs: each of
+    the four values below with the offset on either minutia):
+      the second test (limit PI / 6 in double, 0.5235987666...) at float(PI / 6) = 0.52359879, which is ABOVE the double limit — the two are incompatible, but
+      a comparison in float would call them compatible — and at the float just below it;
+      the first test (limit PI / 4 = 0.78539815) at float(PI / 4) = 0.78539813, just below the limit, and at the float just above (a1 - b1 = +x / 2, a2 - b2 = -x / 2,
+      so that the second and third test see x / 2 and pass)."""
+    rng = np.random.default_rng(seed)
+    base = S.make_latent(rng, n_tex_lo=210, n_tex_hi=240)
+    R0 = S.make_rolled(rng, cb, n_minu=30, n_tex=300)
+    e = np.zeros((2, 96), np.float32); e[0, 0] = 1.8; e[1, 1] = 1.7
+    x = np.array([100, 200], np.int16); y = np.array([100, 100], np.int16)      # the distance stage hands the two over in the order (second, first): the line runs from x = 200 to x = 100, atan2f(0, 100) = 0
+    PI = 3.1415926
+    x6, x4 = np.float32(PI / 6.), np.float32(PI / 4.)
+    lim = [(x6, 0.0), (np.nextafter(x6, np.float32(0)), 0.0), (x4 / np.float32(2), -x4 / np.float32(2)),
+           (np.nextafter(x4, np.float32(1)) / np.float32(2), -np.nextafter(x4, np.float32(1)) / np.float32(2))]
+    out = []
+    for a1, a2 in lim + [(b, a) for a, b in lim]:                              # the offset on the first minutia (the third test sees it) and on the second (the second test does)
+        L = T.FPTemplate(minu=list(base.minu), tex=list(base.tex))
+        L.minu[26] = T.MinutiaeTemplate(x.copy(), y.copy(), np.array([a1, a2], np.float32), e.copy())
+        R = T.FPTemplate(minu=[T.MinutiaeTemplate(x.copy(), y.copy(), np.zeros(2, np.float32), e.copy())], tex=list(R0.tex))
+        out.append((L, R))
+    return out
+
+
+def s2_rounding_pairs(cb, seed=0, n=15, noise=1e-5, count=3):
+    """(latent, rolled) pairs in which ROUNDING inside S2's row and column sums (matcher.cpp:455-456) decides the candidate list: latent template 26 and the rolled
+    minutiae template hold n minutiae each whose descriptors are one direction plus noise of relative size 1e-5, so the n * n similarities — and their
+    normalised values, about 1 / (2n - 1) each — agree to five digits and the 120th place is contested by values a few ulps apart.  Minutia i has the same
+    coordinates and orientation on both sides, so the candidates (i, i) that make the list survive the graph stages and the score tells which ones did."""
+    rng = np.random.default_rng([seed, 0x52])
+    base = S.make_latent(rng, n_tex_lo=210, n_tex_hi=240)
+    R0 = S.make_rolled(rng, cb, n_minu=30, n_tex=300)
+    out = []
+    for _ in range(count):
+        d = rng.standard_normal(96); d *= 1.73 / np.linalg.norm(d)
+        x = rng.integers(50, 700, n).astype(np.int16); y = rng.integers(50, 700, n).astype(np.int16); ori = rng.uniform(-3, 3, n).astype(np.float32)
+        dl = (d[None, :] * (1 + noise * rng.standard_normal((n, 96)))).astype(np.float32)
+        dr = (d[None, :] * (1 + noise * rng.standard_normal((n, 96)))).astype(np.float32)
+        L = T.FPTemplate(minu=list(base.minu), tex=list(base.tex))
+        L.minu[26] = T.MinutiaeTemplate(x, y, ori, dl)
+        out.append((L, T.FPTemplate(minu=[T.MinutiaeTemplate(x.copy(), y.copy(), ori.copy(), dr)], tex=list(R0.tex))))
+    return out
+
+
+def rules_gallery(cb, base, seed=11):
+    """Rolled templates for the selection / fusion rules: mates and a non-mate of `base` at the default sizes and at 200 / 400 / 600 minutiae, and the first
+    one without its texture template.  (A rolled template without minutiae cannot be written as a file: the writer stops after the header.)"""
+    gal = []
+    for nm in ((None, None, None), (200, 400, 600)):
+        rng = np.random.default_rng(seed)
+        kw = [dict(n_minu=n) if n else {} for n in nm]
+        gal += [S.make_mate(rng, cb, base, frac=0.8, n_tex=400, **kw[0]), S.make_mate(rng, cb, base, frac=0.4, n_tex=350, **kw[1]), S.make_rolled(rng, cb, n_tex=300, **kw[2])]
+    rng = np.random.default_rng([seed, 1])
+    gal += [S.make_mate(rng, cb, base, frac=0.6, n_tex=250), S.make_rolled(rng, cb, n_tex=1200)]
+    gal.append(T.FPTemplate(minu=list(gal[0].minu), tex=[]))
+    return gal
+
+
+def rolled_dat_with_texture_count(R, count):
+    """T.write_rolled(R) with the point count of its first texture template overwritten (2001: the loaders refuse the file with -1, matcher.cpp:966-970)."""
+    import struct
+    buf = bytearray(T.write_rolled(R))
+    pos = 32 + 1
+    for m in R.minu:
+        pos += 2 + (m.n * 8 + 2 + m.n * m.des.shape[1] * 4 if m.n > 0 else 0)
+    pos += 1
+    assert struct.unpack_from("<H", buf, pos)[0] == R.tex[0].n
+    struct.pack_into("<H", buf, pos, count)
+    return bytes(buf)
+
+
+def _patch_first_count(buf, pos, count):
+    import struct
+    b = bytearray(buf); struct.pack_into("<H", b, pos, count)
+    return bytes(b)
+
+
+def loader_edge_files(cb, seed=3):
+    """{name: (kind, bytes)} — files at the edges of the reference's two loaders (matcher.cpp:785-884 latent, :886-983 rolled) on which their result is DEFINED:
+    empty files, a rolled file of 10 bytes (the rolled loader's own limit), a point count of 2001 in the first minutiae template (code 2) and in the texture
+    template (code -1, the minutiae templates stay loaded), templates with a point count of 0 (skipped: later templates move up), a missing texture template."""
+    rng = np.random.default_rng(seed)
+    L = S.make_latent(rng, n_tex_lo=210, n_tex_hi=230)
+    R = S.make_rolled(rng, cb, n_minu=25, n_tex=260)
+    none = T.MinutiaeTemplate(np.zeros(0, np.int16), np.zeros(0, np.int16), np.zeros(0, np.float32), np.zeros((0, 96), np.float32))
+    lat_tex_pos = 32 + 1 + sum(2 + m.n * 8 + 2 + m.n * m.des.shape[1] * 4 for m in L.minu) + 1
+    out = {
+        "rolled_empty": ("rolled", b""), "rolled_10_bytes": ("rolled", T.write_rolled(R)[:10]),
+        "rolled_minutiae_2001": ("rolled", _patch_first_count(T.write_rolled(R), 33, 2001)), "rolled_texture_2001": ("rolled", rolled_dat_with_texture_count(R, 2001)),
+        "rolled_no_texture": ("rolled", T.write_rolled(T.FPTemplate(minu=list(R.minu), tex=[]))),
+        "rolled_first_template_without_points": ("rolled", T.write_rolled(T.FPTemplate(minu=[none] + list(R.minu), tex=list(R.tex)))),
+        "latent_empty": ("latent", b""),
+        "latent_minutiae_2001": ("latent", _patch_first_count(T.write_latent(L), 33, 2001)), "latent_texture_2001": ("latent", _patch_first_count(T.write_latent(L), lat_tex_pos, 2001)),
+        "latent_no_texture": ("latent", T.write_latent(T.FPTemplate(minu=list(L.minu), tex=[]))),
+        "latent_template_5_without_points": ("latent", T.write_latent(T.FPTemplate(minu=list(L.minu[:5]) + [none] + list(L.minu[6:]), tex=list(L.tex)))),
+    }
+    return out, T.write_latent(L), T.write_rolled(R)
+
+
+class RecordSet:
+    """One input set of the reference record: .dat bytes, the pairs taken from them, and what is recorded for them."""
+
+    def __init__(self, name, cbb, lat, rol, pairs=None, orders=(0,), mode="selected", stage_pairs=(), corr=False, list2list=None, gpu=True, lat_names=None):
+        self.name, self.cbb, self.lat, self.rol = name, cbb, lat, rol
+        self.pairs = [(i, j) for i in range(len(lat)) for j in range(len(rol))] if pairs is None else list(pairs)
+        self.orders, self.mode, self.stage_pairs, self.corr, self.list2list, self.gpu = tuple(orders), mode, list(stage_pairs), corr, list2list, gpu
+        self.lat_names = lat_names
+
+
+def _dats(lats, gal):
+    return [T.write_latent(L) for L in lats], [T.write_rolled(R) for R in gal]
+
+
+def _golden_npz():
+    import os
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_pairs.npz"))
+
+
+def _shipped_bytes():
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", SHIPPED_CODEBOOK), "rb") as f:
+        return f.read()
+
+
+def _rs_golden(cbb, cb):
+    g = _golden_npz()
+    lat = [g[f"latent_{i}"].tobytes() for i in range(2)]; rol = [g[f"rolled_{j}"].tobytes() for j in range(12)]
+    allp = [(i, j) for i in range(2) for j in range(12)]
+    return RecordSet("golden", cbb, lat, rol, orders=(0, 1, 2, 3, 4, 5), stage_pairs=allp, corr=True, list2list={"latents": [0, 1], "extra": {}})
+
+
+def _rs_small(cbb, cb):
+    lats, gal = small_set(cb, seed=1)
+    lat, rol = _dats(lats, gal)
+    extra = {"R_empty.dat": b"", "R_tex2001.dat": rolled_dat_with_texture_count(gal[3], 2001)}
+    return RecordSet("small", cbb, lat, rol, orders=(0, 1), list2list={"latents": [0, 1, 2], "extra": extra})
+
+
+def _rs_structured(k):
+    def make(cbb, cb):
+        dup, n_lat, n_gal, idw, sg = STRUCTURED_CONFIGS[k]
+        lats, gal = structured_set(cb, dup, n_lat, n_gal, idw, sg)
+        lat, rol = _dats(lats, gal)
+        return RecordSet(f"structured{dup}", cbb, lat, rol, orders=(0, 1), stage_pairs=[(0, 0), (0, n_gal - 1), (1, n_gal - 2)])
+    return make
+
+
+def _rs_rules(cbb, cb):
+    base, variants = edge_latents(cb)
+    names = [n for n in variants if n != "minu0_tex"]          # a latent without minutiae is a header-only file: undefined in the reference (matcher.cpp:827)
+    lat = [T.write_latent(variants[n]) for n in names]
+    rol = [T.write_rolled(R) for R in rules_gallery(cb, base)]
+    return RecordSet("rules", cbb, lat, rol, lat_names=names)
+
+
+def _rs_pairs(name, fn, which_stage=False):
+    def make(cbb, cb):
+        prs = fn(cb)
+        lat = [T.write_latent(L) for L, _ in prs]; rol = [T.write_rolled(R) for _, R in prs]
+        diag = [(i, i) for i in range(len(prs))]
+        return RecordSet(name, cbb, lat, rol, pairs=diag, stage_pairs=diag if which_stage else ())
+    return make
+
+
+def _rs_edge_shapes(cbb, cb):
+    return RecordSet("shapes_edge", cbb, *_dats(*edge_shapes_set(cb)))
+
+
+# The device does not reproduce std::sort's order of equal keys at S7 (matcher.cpp:741; option ref_tie_order 2 covers S3, S8 and S9: the oracle's tie mode 9), so the sets
+# the GPU tests compare with the record are built from seeds at which that order does not decide a score (tests/test_reference_record.py asserts that no pair of them
+# depends on it).  The same inputs at the seeds of the GPU parity tests, where it does decide some, are recorded as well and held against the oracle on the CPU.
+def _rs_tied(seed, name, gpu):
+    def make(cbb, cb):
+        lats, R = tied_row_maxima_set(cb, seed)
+        lat, rol = _dats(lats, [R])
+        return RecordSet(name, cbb, lat, rol, stage_pairs=[(i, 0) for i in range(len(lats))], gpu=gpu)
+    return make
+
+
+def _rs_both_signs(cbb, cb):
+    lats, gal = both_signs_set(cb)
+    return RecordSet("shapes_both_signs", cbb, *_dats(lats, gal[:12]))
+
+
+def _rs_nan(seed, name, gpu):
+    def make(cbb, cb):
+        lat, clean, gal = nan_inf_set(cb, seed)
+        return RecordSet(name, cbb, *_dats([lat, clean], gal), gpu=gpu)
+    return make
+
+
+def _rs_offenv(cbb, cb):
+    lats, rolled, _ = S.make_offenvelope_set(5, 3, 12, cb)
+    return RecordSet("shapes_offenvelope", cbb, *_dats(lats, rolled))
+
+
+def _rs_wide(cbb, cb):
+    return RecordSet("shapes_wide", cbb, *_dats(*wide_slice(cb)))
+
+
+def _rs_all(cbb, cb):
+    lats, gal = small_set(cb, seed=5, n_lat=2, n_gal=10)
+    return RecordSet("all", cbb, *_dats(lats, gal), mode="all")
+
+
+def _rs_family(name, seed=31, set_name=None, gpu=True):
+    def make(cbb, cb):
+        fcb, lats, gal = family_set(name, cb, seed)
+        return RecordSet(set_name or "family_" + name, fcb.to_bytes(), *_dats(lats, gal), gpu=gpu)
+    return make
+
+
+RECORD_SETS = {"golden": _rs_golden, "small": _rs_small, "structured10": _rs_structured(0), "structured30": _rs_structured(1), "rules": _rs_rules,
+               "shapes_edge": _rs_edge_shapes, "shapes_degenerate_keys": _rs_pairs("shapes_degenerate_keys", degenerate_key_pairs, True),
+               "shapes_packed_path": _rs_pairs("shapes_packed_path", packed_path_pairs),
+               "shapes_texture_spread": _rs_pairs("shapes_texture_spread", texture_spread_pairs, True), "shapes_s9_limits": _rs_pairs("shapes_s9_limits", s9_limit_pairs, True),
+               "shapes_s2_rounding": _rs_pairs("shapes_s2_rounding", lambda cb: s2_rounding_pairs(cb, seed=1), True),      # at this seed the third pair's score changes when the row sums run backwards
+               "shapes_tied_maxima": _rs_tied(52, "shapes_tied_maxima", True), "shapes_tied_maxima_s7": _rs_tied(33, "shapes_tied_maxima_s7", False),
+               "shapes_both_signs": _rs_both_signs, "shapes_nan_inf": _rs_nan(410, "shapes_nan_inf", True), "shapes_nan_inf_s7": _rs_nan(404, "shapes_nan_inf_s7", False), "shapes_offenvelope": _rs_offenv, "shapes_wide": _rs_wide, "all": _rs_all}
+RECORD_SETS.update({"family_" + n: _rs_family(n) for n in CODEBOOK_FAMILY})
+# tiny codebook: nearly every similarity is 6 minus very little, row maxima tie in every pair and S7's order of them decides one pair in ten (see the note above _rs_tied)
+RECORD_SETS.update({"family_tiny": _rs_family("tiny", 55), "family_tiny_s7": _rs_family("tiny", 31, "family_tiny_s7", False)})
+_record_cache = {}
+
+
+def record_set(name):
+    """The input set `name` of tests/golden/golden_matcher_ref.npz (built once per process)."""
+    if name not in _record_cache:
+        cbb = _shipped_bytes()
+        _record_cache[name] = RECORD_SETS[name](cbb, T.Codebook.from_bytes(cbb))
+    return _record_cache[name]
+
+
+def record_latent_name(i): return f"L{i}.dat"
+def record_rolled_name(j): return f"R{j:03d}.dat"
+
+
+def load_reference_record():
+    import os
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_matcher_ref.npz"))
+
+
+def record_parts(vec_bits, info, status):
+    """(s0, s1, s2, texture, fused) as uint32 bit patterns from a recorded score vector of One2One_matching_selected_templates: the minutiae scores of latent
+    templates 26 / 2 / 11 sit in slots 0..2 (0 where the latent lacks the template), the texture score in slot n_minu_templates, and the fused score is
+    matcher.cpp:188's `score[0] + score[1] + score[2] + score[28]*0.3` (float sums, then double).  With fewer than 29 slots the reference reads beyond the
+    vector there (undefined); the project's reading — an absent slot is 0 — is what this returns then.  Status 1 / 2: zeros and a fused score of -1."""
+    n_lm, n_lt = int(info[2]), int(info[3])
+    vec = np.asarray(vec_bits, np.uint32).view(np.float32)
+    out = np.zeros(5, np.float32)
+    if status != 0:
+        out[4] = -1.0
+        return out.view(np.uint32)
+    sel = (26, 2, 11)
+    for i in range(3):
+        if n_lm > sel[i]: out[i] = vec[i]
+    if n_lt > 0: out[3] = vec[n_lm]
+    at = lambda k: vec[k] if k < n_lm + n_lt else np.float32(0)
+    with np.errstate(all="ignore"):
+        f = np.float32(np.float32(at(0) + at(1)) + at(2))
+        out[4] = np.float32(np.float64(f) + np.float64(at(28)) * 0.3)
+    return out.view(np.uint32)

@@ -3,8 +3,10 @@
 (oracle/afis_oracle.cpp) gives for them, in both tie modes, plus hashes of the S4 look-up tables and S5/S6 row maxima.
 
 What these vectors pin: the oracle against itself over time (regressions) and the HIP path against the oracle on fixed inputs.
-They are NOT outputs of the reference: matching/matcher.cpp is unbuildable in this image (Eigen / Boost absent).
-The only stage checked against reference code is S4 / the template data model, through oracle/_ref (tests/test_oracle.py).
+They are the oracle's output.  That parts[0] (tie mode 0) is also what the REFERENCE's own matcher.cpp computes on these bytes is held by
+tests/test_reference_record.py::test_committed_golden_vectors_are_reference_outputs against the record of golden_matcher_ref.npz
+(make_golden_matcher_ref.py: the reference's unmodified translation unit on stand-in Eigen / Boost headers; Eigen's own summation order
+is the one thing that build does not have).  S4 / the template data model are checked against oracle/_ref as well (tests/test_oracle.py).
 
 Run from the repo root:  python tests/golden/make_golden.py
 """

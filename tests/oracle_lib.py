@@ -187,3 +187,84 @@ class RefHarness:
         self.lib.ref_rolled_texture(n, p(x, C.c_short), p(y, C.c_short), p(ori, C.c_float), des_len, p(buf, C.c_float),
                                     p(codes, C.c_uint8), p(xo, C.c_int), p(yo, C.c_int), p(oo, C.c_float))
         return codes, xo, yo, oo
+
+
+class RefMatcher:
+    """oracle/_ref/libafis_refmatcher.so — the reference's own matcher.cpp, compiled unmodified against the stand-in headers of
+    oracle/standin/ (only a machine that has the reference tree builds it).  Every call takes file paths: the reference's loaders are
+    part of what runs.  Used by tests/golden/make_golden_matcher_ref.py to record golden_matcher_ref.npz; the tests read the record."""
+
+    STAGE_FN = {"dist_eigen": 0, "dist_lookup": 1, "angle": 2}
+
+    def __init__(self, codebook_path):
+        so = os.path.join(ORACLE_DIR, "_ref", "libafis_refmatcher.so")
+        if not os.path.exists(so):
+            build()
+        if not os.path.exists(so):
+            raise FileNotFoundError(so)
+        L = self.lib = _load(so)
+        vp, cp, ip, up = C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+        L.refm_new.restype = vp; L.refm_new.argtypes = [cp]
+        L.refm_free.argtypes = [vp]
+        L.refm_set_order.argtypes = [C.c_int]
+        L.refm_dims.argtypes = [vp, ip]
+        L.refm_pair_load.restype = vp; L.refm_pair_load.argtypes = [vp, cp, cp, C.c_int, ip]
+        L.refm_pair_free.argtypes = [vp]
+        L.refm_points.restype = C.c_int; L.refm_points.argtypes = [vp, C.c_int, C.c_int]
+        L.refm_selected.restype = C.c_int; L.refm_selected.argtypes = [vp, vp, C.c_int, cp, up, C.c_int, ip]
+        L.refm_all.restype = C.c_int; L.refm_all.argtypes = [vp, vp, up, C.c_int, ip]
+        L.refm_stage.restype = C.c_int; L.refm_stage.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, up, ip, ip, up, ip, ip, C.c_int]
+        L.refm_list2list.restype = C.c_int; L.refm_list2list.argtypes = [vp, cp, cp, cp]
+        self.h = L.refm_new(codebook_path.encode())
+
+    def close(self):
+        if self.h:
+            self.lib.refm_free(self.h); self.h = None
+
+    def set_order(self, order):
+        self.lib.refm_set_order(int(order))
+
+    def dims(self):
+        d = (C.c_int * 3)(); self.lib.refm_dims(self.h, d)
+        return tuple(d)
+
+    def load_pair(self, latent_path, rolled_path, zero_failed_rolled=True):
+        """(handle, info): info = latent rc, rolled rc, latent minutiae / texture template counts, rolled minutiae / texture template counts."""
+        info = (C.c_int * 6)()
+        h = self.lib.refm_pair_load(self.h, latent_path.encode(), rolled_path.encode(), int(zero_failed_rolled), info)
+        return h, np.array(info[:], np.int32)
+
+    def free_pair(self, h):
+        self.lib.refm_pair_free(h)
+
+    def points(self, pair, kind, t=0):
+        return self.lib.refm_points(pair, kind, t)
+
+    def selected(self, pair, corr_prefix=None):
+        """(status, score vector as uint32 bit patterns) of One2One_matching_selected_templates."""
+        bits = np.zeros(64, np.uint32); n = C.c_int(0)
+        rc = self.lib.refm_selected(self.h, pair, int(corr_prefix is not None), (corr_prefix or "").encode(), bits.ctypes.data_as(C.POINTER(C.c_uint32)), 64, C.byref(n))
+        assert n.value <= 64
+        return rc, bits[:n.value].copy()
+
+    def all_templates(self, pair):
+        bits = np.zeros(64, np.uint32); n = C.c_int(0)
+        rc = self.lib.refm_all(self.h, pair, bits.ctypes.data_as(C.POINTER(C.c_uint32)), 64, C.byref(n))
+        assert n.value <= 64
+        return rc, bits[:n.value].copy()
+
+    def stage(self, pair, fn, texture, latent_t, sim_bits, li, ri):
+        """The reference's stage function `fn` (dist_eigen / dist_lookup / angle) on the list (sim_bits, li, ri); returns the list it gives back, or None."""
+        sim_bits = np.ascontiguousarray(sim_bits, np.uint32); li = np.ascontiguousarray(li, np.int32); ri = np.ascontiguousarray(ri, np.int32)
+        cap = max(1, len(li))
+        so = np.zeros(cap, np.uint32); lo = np.zeros(cap, np.int32); ro = np.zeros(cap, np.int32)
+        p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        n = self.lib.refm_stage(self.h, pair, self.STAGE_FN[fn], int(bool(texture)), int(latent_t), len(li), p(sim_bits, C.c_uint32), p(li, C.c_int), p(ri, C.c_int),
+                                p(so, C.c_uint32), p(lo, C.c_int), p(ro, C.c_int), cap)
+        if n < 0:
+            return None
+        assert n <= cap
+        return so[:n], lo[:n], ro[:n]
+
+    def list2list(self, latent_dir, rolled_dir, score_prefix):
+        return self.lib.refm_list2list(self.h, latent_dir.encode(), rolled_dir.encode(), score_prefix.encode())

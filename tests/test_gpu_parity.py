@@ -366,30 +366,7 @@ def test_candidate_selection_degenerate_keys(codebook_bytes, cb, oracle):
     the 120th candidate is a zero decided by element index; (b) every similarity identical, so all keys share one bin and the
     whole top-120 is decided by index; (c) a block of exact ties straddling the 120th place.  Candidate lists (members, order,
     similarity bits) and scores against the oracle."""
-    rng = np.random.default_rng(5)
-    base = S.make_latent(rng)
-    d = rng.standard_normal(96).astype(np.float32); d *= np.float32(1.73) / np.linalg.norm(d)
-    e = rng.standard_normal(96).astype(np.float32); e -= d * (e @ d) / (d @ d); e *= np.float32(1.73) / np.linalg.norm(e)     # orthogonal to d
-
-    def latent_with(des_rows):
-        L = T.FPTemplate(minu=list(base.minu), tex=list(base.tex))
-        m0 = base.minu[26]
-        n = len(des_rows)
-        L.minu[26] = T.MinutiaeTemplate(rng.integers(50, 700, n).astype(np.int16), rng.integers(50, 700, n).astype(np.int16),
-                                        rng.uniform(-3, 3, n).astype(np.float32), np.stack(des_rows).astype(np.float32))
-        return L
-
-    def rolled_with(des_rows):
-        n = len(des_rows)
-        R = S.make_rolled(rng, cb, n_minu=n, n_tex=300)
-        R.minu[0] = T.MinutiaeTemplate(R.minu[0].x, R.minu[0].y, R.minu[0].ori, np.stack(des_rows).astype(np.float32))
-        return R
-
-    cases_ = [
-        (latent_with([d] * 30), rolled_with([-d] * 37 + [d] * 3)),                      # (a) 90 non-zero of 1200
-        (latent_with([d] * 32), rolled_with([d] * 40)),                                  # (b) 1280 identical keys
-        (latent_with([d] * 10 + [e] * 22), rolled_with([d] * 10 + [0.5 * d + 0.5 * e] * 30)),   # (c) a few levels, large tie blocks
-    ]
+    cases_ = cases.degenerate_key_pairs(cb)
     ocb = oracle.codebook(codebook_bytes)
     for ci, (L, R) in enumerate(cases_):
         m = M.Matcher(codebook_bytes, taps=True); m.gallery_add([R]); m.gallery_commit(0)
@@ -441,20 +418,8 @@ def test_texture_coordinates_off_the_beaten_path(codebook_bytes, cb, oracle):
     """S8b range rule and arithmetic paths: block coordinates spread over 0..120 (many pairs with |dx| or |dy| >= 50, which the
     table look-up treats as incompatible, matcher.cpp:1257), beyond 8191 (the kernel's packed 16-bit fast path must step aside) and
     >= 32768 (negative as the reference reads them into int16-backed storage).  Stage lists and scores against the oracle."""
-    rng = np.random.default_rng(21)
-    base = S.make_latent(rng, n_tex_lo=260, n_tex_hi=300)
     ocb = oracle.codebook(codebook_bytes)
-
-    def spread(t, scale, offset=0):
-        x = ((t.x.astype(np.int64) * scale) // 10 + offset).astype(np.int64)
-        y = ((t.y.astype(np.int64) * scale) // 10 + offset).astype(np.int64)
-        return x.astype(np.uint16).view(np.int16), y.astype(np.uint16).view(np.int16)
-
-    for ci, (scale, off_l, off_r) in enumerate(((25, 0, 0), (25, 9000, 9000), (10, 40000, 40000), (25, 0, 8180))):
-        L = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(*spread(base.tex[0], scale, off_l), base.tex[0].ori, des=base.tex[0].des)])
-        R0 = S.make_mate(rng, cb, base, frac=0.7, n_tex=500)
-        rx, ry = spread(R0.tex[0], scale, off_r)
-        R = T.FPTemplate(minu=list(R0.minu), tex=[T.TextureTemplate(rx, ry, R0.tex[0].ori, codes=R0.tex[0].codes)])
+    for ci, (L, R) in enumerate(cases.texture_spread_pairs(cb)):
         m = M.Matcher(codebook_bytes, taps=True); m.gallery_add_dat(T.write_rolled(R)); m.gallery_commit(0)
         hl, _ = oracle.latent(ocb, T.write_latent(L)); hr, _ = oracle.rolled(T.write_rolled(R))
         for stage in (0, 1, 2):
@@ -472,19 +437,11 @@ def test_texture_top200_with_tied_row_maxima(codebook_bytes, cb, oracle):
     """S7 (matcher.cpp:736-749) when row maxima tie: latent texture rows that share a descriptor have bit-identical ADC rows, hence equal
     maxima and arg-maxima.  Ties (a) inside the top 200, (b) straddling the 200th place (lowest indices kept) and (c) none at all exercise
     the kernel's 32-bit rank with its collision check and the 64-bit (key, ~index) fallback.  Stage lists and scores against the oracle."""
-    rng = np.random.default_rng(33)
-    base = S.make_latent(rng, n_tex_lo=330, n_tex_hi=360)
-    R = S.make_mate(rng, cb, base, frac=0.7, n_tex=600)
+    lats, R = cases.tied_row_maxima_set(cb)
     ocb = oracle.codebook(codebook_bytes)
     m = M.Matcher(codebook_bytes, taps=True); m.gallery_add_dat(T.write_rolled(R)); m.gallery_commit(0)
     hr, _ = oracle.rolled(T.write_rolled(R))
-    t0 = base.tex[0]
-    n = len(t0.x)
-    for ci, groups in enumerate(([], [(10, 40)], [(5, 330)], [(50, 90), (120, 300)])):
-        des = t0.des.copy()
-        for lo, hi in groups:
-            des[lo:hi] = des[lo]
-        L = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(t0.x, t0.y, t0.ori, des=des)])
+    for ci, (groups, L) in enumerate(zip(cases.TIED_ROW_GROUPS, lats)):
         hl, _ = oracle.latent(ocb, T.write_latent(L))
         for stage in (0, 1, 2):
             want = oracle.trace(ocb, hl, hr, which=0, stage=stage, tie_mode=1)
@@ -791,19 +748,7 @@ def test_cli_matches_oracle(codebook_bytes, cb, oracle, small, tmp_path):
 def test_edge_shapes_against_oracle(codebook_bytes, cb, oracle):
     """Shapes off the fast paths: > 64 latent / > 128 rolled minutiae (generic candidate kernel), texture templates above the
     1000-point clamp (matcher.cpp:544-547), tiny templates (fewer than 120 / 200 candidates), duplicated points (ties)."""
-    rng = np.random.default_rng(42)
-    big = S.make_latent(rng, n_tex_lo=1100, n_tex_hi=1200, n_minu_lo=90, n_minu_hi=110)        # texture > 1000 rows, minutiae > 64
-    tiny = S.make_latent(rng, n_tex_lo=40, n_tex_hi=60, n_minu_lo=3, n_minu_hi=6)
-    dup = S.make_latent(rng, n_tex_lo=230, n_tex_hi=260)
-    t0 = dup.tex[0]
-    t0.x[50:100] = t0.x[0:50]; t0.y[50:100] = t0.y[0:50]; t0.des[50:100] = t0.des[0:50]; t0.ori[50:100] = t0.ori[0:50]   # exact duplicates
-    lats = [big, tiny, dup]
-    gal = []
-    for L in lats:
-        gal.append(S.make_mate(rng, cb, L, frac=0.8, n_minu=min(300, max(8, len(L._pool[0]) * 3)), n_tex=1300 if L is big else 500))
-        gal.append(S.make_mate(rng, cb, L, frac=0.4, n_minu=150, n_tex=700))
-    gal.append(S.make_rolled(rng, cb, n_minu=5, n_tex=30))
-    gal.append(S.make_rolled(rng, cb, n_minu=260, n_tex=1900))
+    lats, gal = cases.edge_shapes_set(cb)
     m = M.Matcher(codebook_bytes)
     m.gallery_add(gal); m.gallery_commit(0)
     res = m.search(lats, k=0, want_parts=True)
@@ -1014,14 +959,7 @@ def test_bound_pass_with_nan_and_inf_latent_descriptors(codebook_bytes, cb, orac
     an infinite one makes them all -inf, again the first point.  Row maxima / first arg-maxima of variants 7, 8 and 9 equal the oracle's (NaN == NaN),
     the finite rows around them are untouched, and a search over such a latent neither hangs nor crashes and gives the same scores in variants 7 and 9
     (the reference's own S7 sort of NaN keys is undefined behaviour: there is no oracle value for the pair score)."""
-    rng = np.random.default_rng(404)
-    base = S.make_latent(rng, n_tex_lo=300, n_tex_hi=320)
-    lt = base.tex[0]
-    des = lt.des.copy()
-    des[3, 5] = np.nan; des[4, :] = np.nan; des[9, 0] = np.inf; des[10, 95] = -np.inf; des[11, 40] = np.inf; des[11, 41] = -np.inf
-    des[20, 7] = 7e4; des[21, 8] = -3e38; des[22, :] = 1e-42; des[23, 17] = 1001.0; des[24, 17] = 999.0; des[25, :] = 0.0
-    lat = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(lt.x, lt.y, lt.ori, des=des)])
-    gal = [S.make_rolled(rng, cb, n_tex=n) for n in (640, 33, 1)] + [S.make_mate(rng, cb, base, frac=0.6, n_tex=500)]
+    lat, clean, gal = cases.nan_inf_set(cb)
     m = _matcher(codebook_bytes, gal, taps=True)
     ocb = oracle.codebook(codebook_bytes)
     for g in range(len(gal)):
@@ -1046,7 +984,6 @@ def test_bound_pass_with_nan_and_inf_latent_descriptors(codebook_bytes, cb, orac
     m.set_option("adc_variant", 9); m.set_option("mf_stats", 1)
     r9 = m.search([lat], k=0, want_parts=True); r9b = m.search([lat], k=0, want_parts=True)
     assert _same_bits(r9["parts"], r9b["parts"]) and m.refine_stats()["bound_violations"] == 0
-    clean = T.FPTemplate(minu=list(base.minu), tex=[T.TextureTemplate(lt.x, lt.y, lt.ori, des=lt.des)])
     rc = m.search([clean], k=0, want_parts=True)
     assert np.array_equal(rc["parts"][..., :3].view(np.uint32), r9["parts"][..., :3].view(np.uint32))
     m.set_option("adc_variant", 7); r7 = m.search([lat], k=0, want_parts=True)
@@ -1261,17 +1198,8 @@ def test_minutiae_coordinates_beyond_the_packed_path(codebook_bytes, cb, oracle)
     """S8a arithmetic paths: pixel coordinates within [0, 2047] take the packed 16-bit predicate (v_pk_sub_i16 + v_dot2), anything larger
     — here offsets of 2040 (straddling the limit), 5000 and 30000 — the generic float arithmetic, where dx*dx + dy*dy is no longer exact.
     Stage lists of the three minutiae scorers and the scores against the oracle, bit for bit."""
-    rng = np.random.default_rng(33)
-    base = S.make_latent(rng, n_tex_lo=210, n_tex_hi=240)
     ocb = oracle.codebook(codebook_bytes)
-    R0 = S.make_mate(rng, cb, base, frac=0.8, n_tex=300)
-    for ci, (off_l, off_r, scale) in enumerate(((0, 0, 1), (2040, 1500, 1), (5000, 4000, 3), (30000, 250, 1))):
-        def shift(m, off):
-            x = (m.x.astype(np.int64) * scale + off).astype(np.uint16).view(np.int16)
-            y = (m.y.astype(np.int64) * scale + off).astype(np.uint16).view(np.int16)
-            return T.MinutiaeTemplate(x, y, m.ori, m.des)
-        L = T.FPTemplate(minu=[shift(m_, off_l) for m_ in base.minu], tex=list(base.tex))
-        R = T.FPTemplate(minu=[shift(R0.minu[0], off_r)], tex=list(R0.tex))
+    for ci, (L, R) in enumerate(cases.packed_path_pairs(cb)):
         m = M.Matcher(codebook_bytes, taps=True); m.gallery_add_dat(T.write_rolled(R)); m.gallery_commit(0)
         hl, _ = oracle.latent(ocb, T.write_latent(L)); hr, _ = oracle.rolled(T.write_rolled(R))
         for which in (1, 2, 3):
@@ -1420,11 +1348,7 @@ def test_structured_templates_against_oracle(codebook_bytes, cb, oracle):
     SS = importlib.import_module("msu-latentafis_amd.host.synth_structured")
     n_pos = n_pairs = n_fill = 0
     for dup, n_lat, n_gal, idw, sg in ((10, 4, 30, 0.3, SS.DUP_SIGMA[10]), (30, 2, 40, 1.0, 0.0057)):      # identity weight 1.0 (0.0057 = its noise level for 30 % repeats): a tenth of the minutiae lists has fewer than 120 positive similarities (the zero-fill route of the candidate kernel)
-        SS.IDENTITY_WEIGHT = idw
-        rng = np.random.default_rng(600 + dup)
-        lats = [SS.make_structured_latent(rng, sigma=sg) for _ in range(n_lat)]
-        gal = [SS.make_structured_mate(rng, cb, L, frac=f, sigma=sg) for L in lats for f in (0.8, 0.3)]
-        while len(gal) < n_gal: gal.append(SS.make_structured_rolled(rng, cb, sigma=sg))
+        lats, gal = cases.structured_set(cb, dup, n_lat, n_gal, idw, sg)
         off = np.concatenate([[0], np.cumsum([g.tex[0].n for g in gal])])
         share = SS.dup_share(np.concatenate([g.tex[0].codes for g in gal]), off)
         assert 0.4 * dup / 100 <= share <= 2.0 * dup / 100, share
@@ -1454,7 +1378,6 @@ def test_structured_templates_against_oracle(codebook_bytes, cb, oracle):
             for s_ in (26, 2, 11):
                 for R in gal: n_fill += int(((L.minu[s_].des @ R.minu[0].des.T) > 0).sum() < 120 and L.minu[s_].n * R.minu[0].n >= 512)
         m.close()
-    SS.IDENTITY_WEIGHT = 0.3
     assert n_fill >= 5, n_fill
     assert n_pairs == 200 and n_pos >= 100, (n_pairs, n_pos)                   # most non-mates score above zero
 
@@ -1628,14 +1551,7 @@ def test_texture_top200_with_row_maxima_of_both_signs(codebook_bytes, cb, oracle
     difference as an int when they binned the 200 keys for ranking — a negative number, a zero shift, bins far out of range, counters scattered over the list's LDS, ranking loops of 2^31
     trips: 72 s for one search (the results stayed right: the tie fallback re-ranked).  Scores against the oracle, the texture stage's time, and a host emulation of the search that
     shows such lists are in the set."""
-    SS = importlib.import_module("msu-latentafis_amd.host.synth_structured")
-    rng = np.random.default_rng(905)
-    SS.IDENTITY_WEIGHT = 1.0
-    try:
-        lats = [SS.make_structured_latent(rng, sigma=0.0095, n_tex_lo=200, n_tex_hi=260) for _ in range(2)]
-        gal = [SS.make_structured_rolled(rng, cb, sigma=0.0095, n_minu=int(rng.integers(20, 128)), n_tex=300) for _ in range(40)]
-    finally:
-        SS.IDENTITY_WEIGHT = 0.3
+    lats, gal = cases.both_signs_set(cb)
     assert all(200 < L.tex[0].n <= 256 for L in lats)
     m = M.Matcher(codebook_bytes, taps=True)
     m.gallery_add(gal); m.gallery_commit(0)
