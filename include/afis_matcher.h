@@ -134,6 +134,30 @@ int afis_gallery_add_packed(afis_ctx* ctx, int64_t n,
 int afis_gallery_commit(afis_ctx* ctx, int64_t index_base);
 int64_t afis_gallery_size(const afis_ctx* ctx);
 
+/* Live gallery (no reference counterpart: the reference's gallery is whatever the directory holds at the moment of a search): enrol and remove rolled prints
+ * after the commit, without staging and uploading the resident shard again.  Every edit first waits for all device work of the context.
+ * afis_gallery_reopen  valid on a committed gallery only (AFIS_ESTATE otherwise): opens a new staging area beside the resident shard.  Until the next commit every
+ *                     staging call above and afis_gallery_load append to it exactly as before the first commit; searches, afis_correspondences and
+ *                     afis_match_all_templates stay allowed and see the resident shard only; afis_gallery_size reports resident + staged; afis_gallery_save
+ *                     stays AFIS_ESTATE (afis_gallery_export writes a resident shard).
+ * afis_gallery_commit  on a reopened gallery appends the staged templates: they take the indices index_base + G_old ... in staging order.  index_base must be the
+ *                     shard's (AFIS_EINVAL otherwise, nothing changes).  Only the new points and the offset tables cross PCIe: the device arrays grow by
+ *                     capacity with a device-to-device copy, and the derived layouts are made for the new templates only.  The shard size limits apply to the
+ *                     sum.  A failed append leaves the resident shard searchable and the staged templates in place.
+ * afis_gallery_remove  idx[0 .. n): global indices as afis_search reports them.  The listed entries become EMPTY entries — their points leave every device array
+ *                     (one compaction pass per call, whatever n is), every other template keeps its index — exactly as if the gallery had been committed with
+ *                     empty templates at those positions: score -1, rolled_status 2.  An entry that is empty already, or listed twice, is a no-op; an index
+ *                     outside the shard is AFIS_EINVAL with nothing changed; templates staged but not yet committed are AFIS_ESTATE.  Should the device run
+ *                     out of memory half-way (AFIS_EDEVICE), the resident shard is dropped and the context is back to "not committed".
+ * afis_gallery_export  writes the resident shard as a packed container (below): byte for byte the file afis_gallery_save writes from a context staged with the
+ *                     same entries.  names as for afis_gallery_save, one per resident template.
+ * Query handles (afis_queries_upload) are cut into launch groups for the shard size of the moment: after an appending commit or a removal that changed the shard,
+ * afis_search_resident refuses an older handle with AFIS_ESTATE; free it and upload the latents again.  afis_search uploads per call and is not affected.
+ * After every edit the results are, bit for bit, those of a context freshly committed with the final gallery. */
+int afis_gallery_reopen(afis_ctx* ctx);
+int afis_gallery_remove(afis_ctx* ctx, const int64_t* idx, int64_t n);
+int afis_gallery_export(afis_ctx* ctx, const char* path, const char* const* names);
+
 /* The hot path.  Replaces the body of the OpenMP loop of One2List_matching / List2List_matching
  * (matcher.cpp:168-190, :273-295) for n_q latents at once.
  *   scores      [n_q][G] or NULL : final fused score per gallery template, -1 where the rolled template is empty
@@ -250,7 +274,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * (38 912, counted with the odd row stride's padding column): the largest minutiae counts / latent x rolled similarities a candidate task may have to run in the matrix-core kernel's shape classes; larger tasks (the
  * reference's reader allows 2000 minutiae per template, matcher.cpp:788-790) go to the any-shape kernel — same results, slower (afis_timing.minu_fallback_tasks counts them).  "bound_cus": 128 by default — the bound pass runs on a stream confined to half of the chip's CUs
  * (hipExtStreamCreateWithCUMask) with the minutiae stage beside it on the other half: the pass is power-limited, half the CUs deliver 0.64 of its throughput;
- * 0 = one stream, kernels back to back; 32 ... 224 in steps of 32; the environment variable AFIS_BOUND_CUS sets the initial value. */
+ * 0 = one stream, kernels back to back; 32 ... 224 in steps of 32; the environment variable AFIS_BOUND_CUS sets the initial value.  "gallery_h2d_bytes" (read-only): the bytes handed to every host-to-device copy
+ * of the context's gallery commits and removals so far, counted where the copies are issued: an appending commit adds its own points and the offset tables, not the resident shard.
+ * "gallery_resident" (read-only): the templates of the committed shard, the G of afis_search's outputs (afis_gallery_size also counts what is staged beside it after afis_gallery_reopen). */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

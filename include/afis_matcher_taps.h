@@ -38,6 +38,10 @@ int afis_debug_graph_arith(afis_ctx* ctx, unsigned long long* out8);
  * [5] rows whose exact maximum lay outside the bounds the selection used (a self-check: must be 0). */
 int afis_debug_refine_stats(afis_ctx* ctx, unsigned long long* out8, int reset);
 
+/* The compaction kernels of the last afis_gallery_remove (gallery_edit.hip): out2[0] = their device time in microseconds (HIP events around each of the six
+ * launches, summed), out2[1] = the bytes they copied.  tools/bench_live_gallery.py sets them beside a device-to-device copy of the same bytes. */
+int afis_debug_compact_stats(afis_ctx* ctx, long long* out2);
+
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */
 int afis_debug_phase_cycles(afis_ctx* ctx, unsigned long long* out32, int reset);

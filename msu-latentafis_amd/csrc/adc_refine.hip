@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void k_mf_codebook(const float* __restrict__ c
 
 // Tile-aligned copy of the gallery's texture codes: template t owns ceil(n/32) tiles (32 entries of 16 code bytes, zero beyond the template's
 // points) starting at tile t_blk[t]; per entry also G's point term -|b_j|^2 / 2 (kMfNeg beyond the points), and per tile
-// (template, tile index in the template | 256 on the template's last tile).  grid = G, block = 64.
+// (template, tile index in the template | 256 on the template's last tile).  grid = the templates to lay out (all of them, or the ones a commit appended: t_first), block = 64.
 //
 // Repeated code vectors.  Texture descriptors of neighbouring grid points come from overlapping patches (extraction_rolled.py:112-141) and are PQ-encoded
 // afterwards: in smooth regions several points of a template carry the SAME 16 code bytes.  Such points have the same similarity to every latent row, bit for bit
@@ -51,11 +51,11 @@ __global__ __launch_bounds__(256) void k_mf_codebook(const float* __restrict__ c
 // pass gives up on it ("many") and the recomputation evaluates every point of the template for it: at 30 % repeated points that was 4 % of the evaluated rows and
 // most of the recomputation's time (profiles/r06_bench_structured.json).  (A row evaluated in full still walks all points, repeated ones included: same result.)
 __global__ __launch_bounds__(64) void k_mf_tiles(GalleryDev g, const int32_t* __restrict__ t_blk, const float* __restrict__ cwn,
-                                                 uint4* __restrict__ codes_p, float* __restrict__ nrm_p, int2* __restrict__ tile_meta)
+                                                 uint4* __restrict__ codes_p, float* __restrict__ nrm_p, int2* __restrict__ tile_meta, int t_first)
 {
     __shared__ uint4 s_c[kTexMax];
     __shared__ uint32_t s_hash[kTexMax];
-    const int t = blockIdx.x, lane = threadIdx.x;
+    const int t = t_first + blockIdx.x, lane = threadIdx.x;
     const int p0 = g.tex_off[t], n = min(g.tex_off[t + 1] - p0, kTexMax);
     const int nt = (n + 31) >> 5;
     for (int p = lane; p < n; p += 64) {
@@ -502,10 +502,11 @@ hipError_t launch_mf_codebook(const float* codewords, void* cw16, float* cwn, hi
     return hipGetLastError();
 }
 
-hipError_t launch_mf_tiles(const GalleryDev& g, const int32_t* q_blk, const float* cwn, void* codes_p, float* nrm_p, void* tile_meta, hipStream_t stream)
+hipError_t launch_mf_tiles(const GalleryDev& g, const int32_t* q_blk, const float* cwn, void* codes_p, float* nrm_p, void* tile_meta, hipStream_t stream, int t_first, int n_templates)
 {
-    if (g.G <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mf_tiles, dim3(g.G), dim3(64), 0, stream, g, q_blk, cwn, (uint4*)codes_p, nrm_p, (int2*)tile_meta);
+    if (n_templates < 0) n_templates = g.G - t_first;
+    if (n_templates <= 0 || t_first < 0 || t_first + n_templates > g.G) return n_templates <= 0 ? hipSuccess : hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mf_tiles, dim3(n_templates), dim3(64), 0, stream, g, q_blk, cwn, (uint4*)codes_p, nrm_p, (int2*)tile_meta, t_first);
     return hipGetLastError();
 }
 

@@ -67,6 +67,7 @@ struct afis_queries {
     std::vector<QueryGroup> groups;
     std::vector<int32_t> status;     // per query
     int n_q = 0;
+    uint64_t gallery_epoch = 0;      // afis_ctx::gallery_epoch when the handle was uploaded: its launch groups were cut for that shard's size (afis_search_resident refuses it after an edit)
 };
 
 struct afis_ctx {
@@ -86,6 +87,14 @@ struct afis_ctx {
     int64_t pend_first = 0, pend_count = 0;
     std::thread staging_reaper;          // returns the staged arrays to the system after the commit (0.5 s per 5 GB), off the caller's path; joined in afis_destroy
     bool committed = false;
+    // The live gallery (afis_gallery_reopen / afis_gallery_remove / afis_gallery_export).  `hg` / `pend` hold STAGED templates only; what the host keeps of the resident shard is below.
+    bool reopened = false;               // afis_gallery_reopen: the staging calls append to hg / pend again, beside the resident shard, until the next commit
+    std::vector<uint8_t> res_empty;      // [G] 1 = resident entry is empty (score -1, rolled_status 2)
+    std::vector<int32_t> res_mo, res_to; // [G + 1] the resident shard's CSR offsets (what g_minu_off / g_tex_off hold): the offset tables are rewritten whole from these
+    int64_t minu_tiles = 0;              // 16-descriptor tiles in g_minu_frag
+    uint64_t gallery_epoch = 0;          // counts the edits of the resident shard (appending commits, removals)
+    int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
+    int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
     int64_t index_base = 0;
     GalleryDev gal;
     DevBuf g_minu_off, g_minu_xy, g_minu_ori, g_minu_des, g_minu_frag, g_minu_tile_off, g_tex_off, g_tex_xy, g_tex_ori, g_tex_codes, g_tex_codes_cf, g_tex_cf_blk, g_tex_codes_q, g_tex_q_blk, g_tex_t32_blk, g_empty, g_task_ctr;

@@ -119,7 +119,8 @@ hipError_t launch_adc_rowmax_q(const QueryDev& q, const GalleryDev& g, const voi
 // search uses) — per pair the evaluated rows side by side in row order, value in rm_cv[pair * lt_pad + slot], (row | point << 16) in rm_arg[pair * lt_pad + slot], their count in rm_n[pair];
 // rm_val is not touched — or dense (rm_n == NULL): value and point at rm_val / rm_arg[pair * lt_pad + row], -inf for the other rows (all_rows != 0: every row exactly; the parity taps use it).
 hipError_t launch_mf_codebook(const float* codewords, void* cw16, float* cwn, hipStream_t stream);
-hipError_t launch_mf_tiles(const GalleryDev& g, const int32_t* t32_blk, const float* cwn, void* codes_p, float* nrm_p, void* tile_meta, hipStream_t stream);
+// t_first / n_templates (afis_gallery_commit on a reopened gallery): only templates [t_first, t_first + n_templates) are laid out (n_templates < 0: to the end)
+hipError_t launch_mf_tiles(const GalleryDev& g, const int32_t* t32_blk, const float* cwn, void* codes_p, float* nrm_p, void* tile_meta, hipStream_t stream, int t_first = 0, int n_templates = -1);
 hipError_t launch_mf_rows(const float* lt_des, int n_rows, int n_rb, const float* codewords, const float* cwn, void* bfrag, void* rowk, hipStream_t stream);
 hipError_t launch_adc_mfma(const GalleryDev& g, const void* codes_p, const float* nrm_p, const void* tile_meta, const int32_t* tile0, const void* cw16,
                            const void* bfrag, const void* rowk, int n_rows, int n_rb, int R_pad, int chunk, void* rec,
@@ -237,6 +238,9 @@ hipError_t launch_topk(const float* scores, int n_q, int G, int k, long long ind
 hipError_t launch_pq_encode(const float* des, long long n, const float* codewords, uint8_t* codes, hipStream_t stream);
 // descriptors -> MFMA operand fragment tiles on the device (pq_encode.hip); off / tile_off: [n_templates + 1] device arrays
 hipError_t launch_fragment_tiles(const float* des, const int32_t* off, const int32_t* tile_off, int n_templates, void* frag, hipStream_t stream);
+// afis_gallery_remove (gallery_edit.hip): one SoA array of the shard copied into a new buffer with every surviving template's range moved from old_off[t] to new_off[t]
+// (device offset tables [G + 1]); elem_bytes 384 (descriptors), 16 (PQ codes) or 4 ((x, y), orientations); n_new = new_off[G]
+hipError_t launch_compact_ranges(const void* src, void* dst, int elem_bytes, const int32_t* old_off, const int32_t* new_off, int G, long long n_new, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

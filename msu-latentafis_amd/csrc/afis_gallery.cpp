@@ -79,7 +79,7 @@ extern "C" {
 int afis_gallery_add(afis_ctx* ctx, const afis_template_view* t, int n)
 {
     if (!ctx || (n > 0 && !t)) return fail(ctx, AFIS_EINVAL, "afis_gallery_add: null argument");
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_add: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_add: gallery already committed (afis_gallery_reopen opens it for more)");
     if (int rc_ = materialise(ctx)) return rc_;
     for (int i = 0; i < n; ++i) { int rc = check_rolled(ctx, t[i]); if (rc) return rc; }
     std::vector<uint8_t> enc;
@@ -144,7 +144,7 @@ int afis_encode_rolled_dat(afis_ctx* ctx, const void* bytes, size_t len, void* o
 int afis_gallery_add_dat(afis_ctx* ctx, const void* bytes, size_t len, int* load_rc)
 {
     if (!ctx) return AFIS_EINVAL;
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_dat: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_dat: gallery already committed (afis_gallery_reopen opens it for more)");
     if (int rc_ = materialise(ctx)) return rc_;
     HostTemplate t;
     int rc = parse_rolled_dat(bytes, len, t);
@@ -164,7 +164,7 @@ int afis_gallery_add_dat(afis_ctx* ctx, const void* bytes, size_t len, int* load
 int afis_gallery_add_dat_batch(afis_ctx* ctx, const void* const* bytes, const size_t* lens, int64_t n, int* load_rc)
 {
     if (!ctx || n < 0 || (n > 0 && (!bytes || !lens))) return fail(ctx, AFIS_EINVAL, "afis_gallery_add_dat_batch: bad argument");
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_dat_batch: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_dat_batch: gallery already committed (afis_gallery_reopen opens it for more)");
     if (int rc_ = materialise(ctx)) return rc_;
     std::vector<HostTemplate> ts((size_t)n);
     std::vector<int> rcs((size_t)n, 0);
@@ -223,7 +223,7 @@ int afis_gallery_add_dat_batch(afis_ctx* ctx, const void* const* bytes, const si
 int afis_gallery_reserve(afis_ctx* ctx, int64_t n_templates)
 {
     if (!ctx || n_templates < 0) return fail(ctx, AFIS_EINVAL, "afis_gallery_reserve: bad argument");
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_reserve: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_reserve: gallery already committed (afis_gallery_reopen opens it for more)");
     if (ctx->pend) return AFIS_OK;                                          // a mapped container is not staged in host arrays at all
     HostGallery& hg = ctx->hg;
     const double have = (double)hg.size();
@@ -244,7 +244,7 @@ int afis_gallery_add_packed(afis_ctx* ctx, int64_t n, const int64_t* minu_off, c
                             const int16_t* tex_y, const float* tex_ori, const uint8_t* tex_codes)
 {
     if (!ctx || n < 0 || !minu_off || !tex_off) return fail(ctx, AFIS_EINVAL, "afis_gallery_add_packed: null argument");
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_packed: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_add_packed: gallery already committed (afis_gallery_reopen opens it for more)");
     if (int rc_ = materialise(ctx)) return rc_;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t nm = minu_off[i + 1] - minu_off[i], nt = tex_off[i + 1] - tex_off[i];
@@ -285,7 +285,7 @@ int afis_gallery_save(afis_ctx* ctx, const char* path, const char* const* names)
 int afis_gallery_load(afis_ctx* ctx, const char* path, int64_t first, int64_t count)
 {
     if (!ctx || !path) return fail(ctx, AFIS_EINVAL, "afis_gallery_load: null argument");
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_load: gallery already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_load: gallery already committed (afis_gallery_reopen opens it for more)");
     std::string err;
     if (ctx->hg.size() == 0 && !ctx->pend) {                               // the usual case (one container, or one shard of it): map it, validate it, read it at the commit
         std::unique_ptr<GalleryMapping> gm = map_gallery_container(path, err);
@@ -357,6 +357,8 @@ int afis_gallery_file_names(const char* path, int64_t first, int64_t count, char
 struct PinnedPipe {
     static constexpr size_t kCap = (size_t)64 << 20;
     void* buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool used[2] = {false, false}; int k = 0;
+    size_t direct_below = (size_t)4 << 20;                                 // smaller copies go straight from the caller's memory
+    int64_t* h2d = nullptr;                                                // option gallery_h2d_bytes: every host-to-device copy issued through the pipe adds its bytes here
     hipError_t init()
     {
         for (int i = 0; i < 2; ++i) {
@@ -368,32 +370,62 @@ struct PinnedPipe {
     ~PinnedPipe() { for (int i = 0; i < 2; ++i) { if (ev[i]) (void)hipEventDestroy(ev[i]); if (buf[i]) (void)hipHostFree(buf[i]); } }
 };
 
-static hipError_t upload_bulk(PinnedPipe& pp, DevBuf& b, const void* src, size_t bytes, hipStream_t s)
+// ... to device memory that is already there (dst): the whole array of a first commit, or the tail an appending commit adds behind the resident part
+static hipError_t upload_bulk_at(PinnedPipe& pp, void* dst, const void* src, size_t bytes, hipStream_t s)
 {
-    hipError_t e = b.ensure(std::max<size_t>(bytes, 16));
-    if (e != hipSuccess || bytes == 0) return e;
-    if (bytes < ((size_t)4 << 20)) return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s);
+    hipError_t e = hipSuccess;
+    if (bytes == 0) return e;
+    if (bytes < pp.direct_below) { if (pp.h2d) *pp.h2d += (int64_t)bytes; return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); }
+    if (!pp.buf[1]) { e = pp.init(); if (e != hipSuccess) return e; }       // (an appending commit pins the buffers only when an array is large enough to need them)
     for (size_t off = 0; off < bytes; off += PinnedPipe::kCap) {
         const size_t n = std::min(PinnedPipe::kCap, bytes - off);
         const int slot = pp.k & 1;
         if (pp.used[slot]) { e = hipEventSynchronize(pp.ev[slot]); if (e != hipSuccess) return e; }
         const uint8_t* from = (const uint8_t*)src + off; uint8_t* to = (uint8_t*)pp.buf[slot];
         parallel_for((int64_t)((n + 4095) / 4096), [&](int64_t lo, int64_t hi) { const size_t a = (size_t)lo * 4096, z = std::min(n, (size_t)hi * 4096); memcpy(to + a, from + a, z - a); });
-        e = hipMemcpyAsync((uint8_t*)b.p + off, pp.buf[slot], n, hipMemcpyHostToDevice, s); if (e != hipSuccess) return e;
+        if (pp.h2d) *pp.h2d += (int64_t)n;
+        e = hipMemcpyAsync((uint8_t*)dst + off, pp.buf[slot], n, hipMemcpyHostToDevice, s); if (e != hipSuccess) return e;
         e = hipEventRecord(pp.ev[slot], s); if (e != hipSuccess) return e;
         pp.used[slot] = true; ++pp.k;
     }
     return hipSuccess;
 }
 
+static hipError_t upload_bulk(PinnedPipe& pp, DevBuf& b, const void* src, size_t bytes, hipStream_t s)
+{
+    const hipError_t e = b.ensure(std::max<size_t>(bytes, 16));
+    return e != hipSuccess ? e : upload_bulk_at(pp, b.p, src, bytes, s);
+}
+
+// The gallery's own host-to-device copies outside the pipe — offset tables, empty flags — counted the same way: by the bytes handed to the copy.
+static hipError_t h2d_copy(afis_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s)
+{
+    if (bytes == 0) return hipSuccess;
+    ctx->gallery_h2d_bytes += (int64_t)bytes;
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+}
+static hipError_t upload_table(afis_ctx* ctx, DevBuf& b, const std::vector<int32_t>& v, hipStream_t s)
+{
+    const hipError_t e = b.ensure(std::max<size_t>(v.size() * sizeof(int32_t), 16));
+    return e != hipSuccess ? e : h2d_copy(ctx, b.p, v.data(), v.size() * sizeof(int32_t), s);
+}
+static void derived_offsets(const std::vector<int32_t>& mo, const std::vector<int32_t>& to, std::vector<int32_t>& toff, std::vector<int32_t>& qb, std::vector<int32_t>& tb,
+                            int64_t& n_q_blocks, int64_t& n_t32, int& max_nR);
+
 static int commit_shard(afis_ctx* ctx, int64_t index_base);
+static int append_shard(afis_ctx* ctx);
+static void release_staging(afis_ctx* ctx);
 
 // A failed commit leaves the context as it was before the call: not committed, no half-uploaded shard on the device, the staged templates (host arrays or the mapped
 // container) still in place, so that the caller may retry or destroy.
 int afis_gallery_commit(afis_ctx* ctx, int64_t index_base)
 {
     if (!ctx) return AFIS_EINVAL;
-    if (ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_commit: already committed");
+    if (ctx->committed && !ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_commit: already committed (afis_gallery_reopen opens the gallery for more)");
+    if (ctx->committed) {                                                   // reopened: the staged templates go behind the resident shard, which is not uploaded again
+        if (index_base != ctx->index_base) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: index_base differs from the resident shard's");
+        return append_shard(ctx);                                           // a failure leaves the resident shard searchable and the staged templates in place
+    }
     const int rc = commit_shard(ctx, index_base);
     if (rc != AFIS_OK) {
         ctx->committed = false;
@@ -432,19 +464,22 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     double t_prev = now();
     auto lap = [&](const char* what) { if (clock_it) { (void)hipStreamSynchronize(ctx->stream); const double t = now(); fprintf(stderr, "commit: %-28s %8.1f ms\n", what, t - t_prev); t_prev = t; } };
     PinnedPipe pp;
+    pp.h2d = &ctx->gallery_h2d_bytes;
     HIPCHK(ctx, pp.init());
     lap("pinned buffers");
-    std::vector<int32_t> mo(G + 1), to(G + 1);
+    std::vector<int32_t> mo(G + 1), to(G + 1), toff, qb, tb;
     int max_nR = 0;
     for (int64_t i = 0; i <= G; ++i) { mo[i] = (int32_t)(src_mo[i] - m0); to[i] = (int32_t)(src_to[i] - t0); }
-    for (int64_t i = 0; i < G; ++i) max_nR = std::max(max_nR, mo[i + 1] - mo[i]);
+    // tile offsets of the descriptor fragments (16 descriptors), block offsets of the quantised path's code stream (64 points; made on first use), tile offsets of the
+    // matrix-core bound pass's stream (32 points): one routine for the commit and the edits, so that an edited shard's tables are a fresh commit's
+    int64_t n_q_blocks = 0, n_t32 = 0;
+    derived_offsets(mo, to, toff, qb, tb, n_q_blocks, n_t32, max_nR);
+    if (n_t32 > 0x7fffffff / 32) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: shard too large for the bound pass's code stream; split the gallery into more shards");
     HIPCHK(ctx, upload_bulk(pp, ctx->g_minu_des, s_mdes, NM * kDes * sizeof(float), ctx->stream));     // the big one first: the fragment kernel below runs while the rest is uploaded
     lap("minutiae descriptors");
-    HIPCHK(ctx, upload(ctx->g_minu_off, mo, ctx->stream));
-    std::vector<int32_t> toff((size_t)G + 1, 0);
+    HIPCHK(ctx, upload_table(ctx, ctx->g_minu_off, mo, ctx->stream));
     {   // the descriptors as MFMA operand fragments: laid out on the device from the descriptors just uploaded (round 3 transposed them on the host and uploaded another 34 KB per template)
-        for (int64_t t = 0; t < G; ++t) toff[(size_t)t + 1] = toff[(size_t)t] + (mo[t + 1] - mo[t] + 15) / 16;
-        HIPCHK(ctx, upload(ctx->g_minu_tile_off, toff, ctx->stream));
+        HIPCHK(ctx, upload_table(ctx, ctx->g_minu_tile_off, toff, ctx->stream));
         HIPCHK(ctx, ctx->g_minu_frag.ensure(std::max<size_t>((size_t)toff[(size_t)G] * 6 * 64 * 16, 16)));
         HIPCHK(ctx, launch_fragment_tiles(ctx->g_minu_des.as<float>(), ctx->g_minu_off.as<int32_t>(), ctx->g_minu_tile_off.as<int32_t>(), (int)G, ctx->g_minu_frag.p, ctx->stream));
     }
@@ -455,31 +490,16 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     lap("xy packing");
     HIPCHK(ctx, upload_bulk(pp, ctx->g_minu_xy, mxy.data(), NM * sizeof(short2), ctx->stream));
     HIPCHK(ctx, upload_bulk(pp, ctx->g_minu_ori, s_mori, NM * sizeof(float), ctx->stream));
-    HIPCHK(ctx, upload(ctx->g_tex_off, to, ctx->stream));
+    HIPCHK(ctx, upload_table(ctx, ctx->g_tex_off, to, ctx->stream));
     HIPCHK(ctx, upload_bulk(pp, ctx->g_tex_xy, txy.data(), NT * sizeof(short2), ctx->stream));
     HIPCHK(ctx, upload_bulk(pp, ctx->g_tex_ori, s_tori, NT * sizeof(float), ctx->stream));
     lap("small arrays");
     HIPCHK(ctx, upload_bulk(pp, ctx->g_tex_codes, s_tcodes, NT * kM, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     lap("texture codes");
-    {   // block offsets of the quantised path's code stream (ceil(n/64) blocks per template); the stream itself is made on first use
-        std::vector<int32_t> qb(G + 1);
-        int64_t nb = 0;
-        for (int64_t t = 0; t < G; ++t) { qb[t] = (int32_t)nb; nb += ((int64_t)(to[t + 1] - to[t]) + 63) / 64; }
-        qb[G] = (int32_t)nb;
-        ctx->q_blocks = nb;
-        HIPCHK(ctx, upload(ctx->g_tex_q_blk, qb, ctx->stream));
-    }
-    {   // tile offsets of the matrix-core bound pass's stream (ceil(n/32) tiles of 32 points per template); the stream itself is made on first use
-        std::vector<int32_t> tb(G + 1);
-        int64_t nt = 0;
-        for (int64_t t = 0; t < G; ++t) { tb[t] = (int32_t)nt; nt += ((int64_t)(to[t + 1] - to[t]) + 31) / 32; }
-        tb[G] = (int32_t)nt;
-        if (nt > 0x7fffffff / 32) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: shard too large for the bound pass's code stream; split the gallery into more shards");
-        ctx->t32_tiles = nt;
-        HIPCHK(ctx, upload(ctx->g_tex_t32_blk, tb, ctx->stream));
-    }
-    { DevBuf& eb = ctx->g_empty; HIPCHK(ctx, eb.ensure(std::max<size_t>((size_t)G, 16))); if (G) HIPCHK(ctx, hipMemcpyAsync(eb.p, s_empty, (size_t)G, hipMemcpyHostToDevice, ctx->stream)); }
+    ctx->q_blocks = n_q_blocks; ctx->t32_tiles = n_t32;
+    HIPCHK(ctx, upload_table(ctx, ctx->g_tex_q_blk, qb, ctx->stream)); HIPCHK(ctx, upload_table(ctx, ctx->g_tex_t32_blk, tb, ctx->stream));
+    { DevBuf& eb = ctx->g_empty; HIPCHK(ctx, eb.ensure(std::max<size_t>((size_t)G, 16))); HIPCHK(ctx, h2d_copy(ctx, eb.p, s_empty, (size_t)G, ctx->stream)); }
     HIPCHK(ctx, ctx->g_task_ctr.ensure(64));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     GalleryDev& g = ctx->gal;
@@ -492,19 +512,35 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     ctx->total_tex_points = (int64_t)NT; ctx->total_minutiae = (int64_t)NM;
     ctx->index_base = index_base;
     ctx->committed = true;
+    ++ctx->gallery_epoch;                                                   // (no handle can exist before a first commit; one may after a removal that failed and dropped the shard)
     if (ctx->adc_variant == 9 && G > 0) {                                    // the default path's derived streams belong to the resident gallery: built here, not by the first search
         int rcg = ensure_mf_gallery(ctx, ctx->stream);
         if (rcg != AFIS_OK) return rcg;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         lap("bound pass's code stream");
     }
-    // the host staging copy is no longer needed
-    std::vector<uint8_t> e(s_empty, s_empty + G);
+    // what the host keeps of the resident shard: the empty flags and the offsets (a later edit rewrites the offset tables from them)
+    ctx->res_empty.assign(s_empty, s_empty + G);
+    ctx->minu_tiles = toff[(size_t)G];
+    ctx->res_mo = std::move(mo); ctx->res_to = std::move(to);
+    lap("offset tables");
+    release_staging(ctx);
+    lap("staging released");
+    return AFIS_OK;
+}
+
+// the host staging copy (arrays or mapping) is no longer needed
+static void release_staging(afis_ctx* ctx)
+{
+    HostGallery& hg = ctx->hg;
     if (hg.mdes.capacity() > ((size_t)16 << 20)) {                           // a large staging copy is released by a thread of its own
         // The pages go back in 32 MB pieces (madvise takes the address-space lock shared and briefly); one munmap of 3 GB holds it exclusively for
         // a third of a second, and every allocation the caller makes next — the commit's own clean-up, the first search — would wait for it.
         HostGallery* old = new HostGallery(std::move(ctx->hg));
-        ctx->staging_reaper = std::thread([old]() {
+        // (an earlier commit's thread may still be at work — an append right behind a 5 GB commit — and is waited for by the new one, not by the caller)
+        std::thread earlier = std::move(ctx->staging_reaper);
+        ctx->staging_reaper = std::thread([old, prev = std::move(earlier)]() mutable {
+            if (prev.joinable()) prev.join();
             std::vector<std::pair<uintptr_t, size_t>> pieces;
             auto drop = [&](void* p, size_t bytes) {
                 const uintptr_t a = ((uintptr_t)p + 4095) & ~(uintptr_t)4095, z = ((uintptr_t)p + bytes) & ~(uintptr_t)4095;
@@ -521,13 +557,299 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
             delete old;
         });
     }
-    lap("offset tables");
-    ctx->hg = HostGallery(); ctx->hg.empty = std::move(e);
+    ctx->hg = HostGallery();
     ctx->pend.reset(); ctx->pend_first = ctx->pend_count = 0;
-    lap("staging released");
+}
+
+// ---- the live gallery: afis_gallery_reopen, the appending commit, afis_gallery_remove, afis_gallery_export ---------------------------------
+// An edit replaces device buffers that searches read: nothing of the context may be running.  The search that timed out (if any) first, then all three streams.
+static int quiesce(afis_ctx* ctx, const char* what)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
+    return wait_streams(ctx, {ctx->stream_lo, ctx->stream_hi, ctx->stream}, what);
+}
+
+// the SoA pointers of ctx->gal from the buffers that hold them now (a buffer that grew or was compacted has moved)
+static void refresh_gallery_view(afis_ctx* ctx)
+{
+    GalleryDev& g = ctx->gal;
+    g.minu_off = ctx->g_minu_off.as<int32_t>(); g.minu_xy = ctx->g_minu_xy.as<short2>(); g.minu_ori = ctx->g_minu_ori.as<float>();
+    g.minu_des = ctx->g_minu_des.as<float>(); g.minu_frag = ctx->g_minu_frag.as<float4>(); g.minu_tile_off = ctx->g_minu_tile_off.as<int32_t>(); g.tex_off = ctx->g_tex_off.as<int32_t>(); g.tex_xy = ctx->g_tex_xy.as<short2>();
+    g.tex_ori = ctx->g_tex_ori.as<float>(); g.tex_codes = ctx->g_tex_codes.as<uint4>(); g.empty = ctx->g_empty.as<uint8_t>();
+}
+
+// the streams laid out on first use belong to the shard they were made from
+static void invalidate_lazy_streams(afis_ctx* ctx)
+{
+    ctx->codes_q_built = false; ctx->codes_cf_built = false;
+    ctx->gal.tex_codes_cf = nullptr; ctx->gal.tex_cf_blk = nullptr;
+}
+
+// block offsets of variant 8's code stream (64 points) and tile offsets of the bound pass's (32 points) and of the descriptor fragments (16), from the CSR offsets
+static void derived_offsets(const std::vector<int32_t>& mo, const std::vector<int32_t>& to, std::vector<int32_t>& toff, std::vector<int32_t>& qb, std::vector<int32_t>& tb,
+                            int64_t& n_q_blocks, int64_t& n_t32, int& max_nR)
+{
+    const size_t G = mo.size() - 1;
+    toff.assign(G + 1, 0); qb.assign(G + 1, 0); tb.assign(G + 1, 0);
+    int64_t nq = 0, nt = 0; max_nR = 0;
+    for (size_t t = 0; t < G; ++t) {
+        toff[t + 1] = toff[t] + (mo[t + 1] - mo[t] + 15) / 16;
+        qb[t] = (int32_t)nq; nq += ((int64_t)(to[t + 1] - to[t]) + 63) / 64;
+        tb[t] = (int32_t)std::min<int64_t>(nt, 0x7fffffff); nt += ((int64_t)(to[t + 1] - to[t]) + 31) / 32;
+        max_nR = std::max(max_nR, mo[t + 1] - mo[t]);
+    }
+    qb[G] = (int32_t)nq; tb[G] = (int32_t)std::min<int64_t>(nt, 0x7fffffff);
+    n_q_blocks = nq; n_t32 = nt;
+}
+
+// DevBuf::ensure frees before it allocates; the resident part must survive: the new buffer first (with headroom: one capacity copy per eighth of growth), a device-to-device
+// copy of the `used` bytes, then the old buffer goes.  On failure the old buffer is untouched.
+static hipError_t grow_keep(DevBuf& b, size_t used, size_t need, hipStream_t s)
+{
+    if (need <= b.bytes) return hipSuccess;
+    const size_t cap = (need + need / 8 + 255) & ~(size_t)255;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, cap);
+    if (e != hipSuccess) return e;
+    if (used > 0) e = hipMemcpyAsync(p, b.p, used, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipFree(p); return e; }
+    if (b.p) (void)hipFree(b.p);
+    b.p = p; b.bytes = cap;
+    return hipSuccess;
+}
+
+struct TableSet {                                                           // offset tables written aside, swapped in when everything else has succeeded
+    DevBuf minu_off, tile_off, tex_off, q_blk, t32_blk;
+    ~TableSet() { minu_off.release(); tile_off.release(); tex_off.release(); q_blk.release(); t32_blk.release(); }
+};
+
+int afis_gallery_reopen(afis_ctx* ctx)
+{
+    if (!ctx) return AFIS_EINVAL;
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_reopen: commit the gallery first");
+    ctx->reopened = true;                                                   // (again on a reopened gallery: nothing changes, what is staged stays)
     return AFIS_OK;
 }
 
-int64_t afis_gallery_size(const afis_ctx* ctx) { return !ctx ? 0 : ctx->pend ? ctx->pend_count : (int64_t)ctx->hg.empty.size(); }
+// afis_gallery_commit on a reopened gallery.  Order: (1) every array grows to hold the sum — the resident bytes are copied on the device, never uploaded; (2) the staged
+// points go behind them; (3) the offset tables of the whole shard are written into buffers of their own; (4) fragment tiles and the bound pass's tiles are laid out
+// for the new templates only; (5) the tables and the counters are switched.  Up to (5) the resident shard is what it was: a failure returns with it searchable.
+static int append_shard(afis_ctx* ctx)
+{
+    HostGallery& hg = ctx->hg;
+    const GalleryMapping* gm = ctx->pend.get();
+    const int64_t Gn = gm ? ctx->pend_count : hg.size();
+    const int64_t G0 = ctx->gal.G, G1 = G0 + Gn;
+    const int64_t* src_mo = gm ? gm->minu_off + ctx->pend_first : hg.minu_off.data();
+    const int64_t* src_to = gm ? gm->tex_off + ctx->pend_first : hg.tex_off.data();
+    const int64_t m0 = src_mo[0], t0 = src_to[0];
+    const size_t NMn = (size_t)(src_mo[Gn] - m0), NTn = (size_t)(src_to[Gn] - t0);
+    const size_t NM0 = (size_t)ctx->total_minutiae, NT0 = (size_t)ctx->total_tex_points, NM1 = NM0 + NMn, NT1 = NT0 + NTn;
+    const int16_t* s_mx = gm ? gm->mx + m0 : hg.mx.data(); const int16_t* s_my = gm ? gm->my + m0 : hg.my.data();
+    const float* s_mori = gm ? gm->mori + m0 : hg.mori.data(); const float* s_mdes = gm ? gm->mdes + (size_t)m0 * kDes : hg.mdes.data();
+    const int16_t* s_tx = gm ? gm->tx + t0 : hg.tx.data(); const int16_t* s_ty = gm ? gm->ty + t0 : hg.ty.data();
+    const float* s_tori = gm ? gm->tori + t0 : hg.tori.data(); const uint8_t* s_tcodes = gm ? gm->tcodes + (size_t)t0 * kM : hg.tcodes.data();
+    const uint8_t* s_empty = gm ? gm->empty + ctx->pend_first : hg.empty.data();
+    if (G1 > 0x7fffffff / 8 || NM1 > 0x7fffffffull || NT1 > 0x7fffffffull)
+        return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: shard too large for 32-bit point offsets; split the gallery into more shards");
+    if (gm && gm->fd_ >= 0) {
+        struct stat st;
+        if (fstat(gm->fd_, &st) != 0 || (size_t)st.st_size < gm->len_) return fail(ctx, AFIS_EFORMAT, "gallery container: " + gm->path + " was truncated after it was loaded");
+    }
+    if (Gn == 0) { release_staging(ctx); ctx->reopened = false; return AFIS_OK; }      // nothing staged: the shard is what it was
+    std::vector<int32_t> mo((size_t)G1 + 1), to((size_t)G1 + 1), toff, qb, tb;
+    std::copy(ctx->res_mo.begin(), ctx->res_mo.end(), mo.begin()); std::copy(ctx->res_to.begin(), ctx->res_to.end(), to.begin());
+    for (int64_t i = 1; i <= Gn; ++i) { mo[(size_t)(G0 + i)] = (int32_t)((int64_t)NM0 + src_mo[i] - m0); to[(size_t)(G0 + i)] = (int32_t)((int64_t)NT0 + src_to[i] - t0); }
+    int64_t q_blocks = 0, t32 = 0; int max_nR = 0;
+    derived_offsets(mo, to, toff, qb, tb, q_blocks, t32, max_nR);
+    if (t32 > 0x7fffffff / 32) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit: shard too large for the bound pass's code stream; split the gallery into more shards");
+    { const int rcq = quiesce(ctx, "afis_gallery_commit"); if (rcq != AFIS_OK) return rcq; }
+    hipStream_t s = ctx->stream;
+    const bool clock_it = getenv("AFIS_COMMIT_TIMING") != nullptr;           // development aid, as in commit_shard
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t_prev = now();
+    auto lap = [&](const char* what) { if (clock_it) { (void)hipStreamSynchronize(s); const double t = now(); fprintf(stderr, "append: %-28s %8.1f ms\n", what, t - t_prev); t_prev = t; } };
+    const size_t tiles0 = (size_t)ctx->minu_tiles, tiles1 = (size_t)toff[(size_t)G1], t32_0 = (size_t)ctx->t32_tiles;
+    const size_t kFragTile = 6 * 64 * 16;
+    // (1) room for the sum
+    struct Grow { DevBuf* b; size_t used, need; bool bound_pass; };          // bound_pass: the matrix-core pass's stream, which may not exist yet (its first use then lays out the whole shard)
+    const Grow grows[] = {
+        {&ctx->g_minu_des, NM0 * kDes * 4, NM1 * kDes * 4, false}, {&ctx->g_minu_frag, tiles0 * kFragTile, tiles1 * kFragTile, false}, {&ctx->g_tex_codes, NT0 * kM, NT1 * kM, false},
+        {&ctx->g_minu_xy, NM0 * 4, NM1 * 4, false}, {&ctx->g_minu_ori, NM0 * 4, NM1 * 4, false}, {&ctx->g_tex_xy, NT0 * 4, NT1 * 4, false}, {&ctx->g_tex_ori, NT0 * 4, NT1 * 4, false},
+        {&ctx->g_empty, (size_t)G0, (size_t)G1, false},
+        {&ctx->g_codes_p, t32_0 * 32 * 16, (size_t)t32 * 32 * 16, true}, {&ctx->g_nrm_p, t32_0 * 32 * 4, (size_t)t32 * 32 * 4, true}, {&ctx->g_tile_meta, t32_0 * 8, (size_t)t32 * 8, true},
+    };
+    for (const Grow& gr : grows) {
+        if (gr.bound_pass && !ctx->mf_gal_built) continue;
+        const hipError_t e = grow_keep(*gr.b, gr.used, std::max<size_t>(gr.need, 16), s);
+        refresh_gallery_view(ctx);                                          // (the resident part has moved with its buffer)
+        HIPCHK(ctx, e);
+    }
+    lap("capacity");
+    // (2) the staged points behind the resident ones.  Pinning the pipe's 128 MB costs more than a pageable copy of a few thousand templates takes: arrays below 256 MB go directly.
+    PinnedPipe pp;
+    pp.h2d = &ctx->gallery_h2d_bytes;
+    pp.direct_below = (size_t)256 << 20;
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_minu_des.as<uint8_t>() + NM0 * kDes * 4, s_mdes, NMn * kDes * 4, s));
+    std::vector<short2> mxy(NMn), txy(NTn);
+    parallel_for((int64_t)NMn, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) mxy[(size_t)i] = make_short2(s_mx[i], s_my[i]); });
+    parallel_for((int64_t)NTn, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) txy[(size_t)i] = make_short2(s_tx[i], s_ty[i]); });
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_minu_xy.as<uint8_t>() + NM0 * 4, mxy.data(), NMn * 4, s));
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_minu_ori.as<uint8_t>() + NM0 * 4, s_mori, NMn * 4, s));
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_tex_xy.as<uint8_t>() + NT0 * 4, txy.data(), NTn * 4, s));
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_tex_ori.as<uint8_t>() + NT0 * 4, s_tori, NTn * 4, s));
+    HIPCHK(ctx, upload_bulk_at(pp, ctx->g_tex_codes.as<uint8_t>() + NT0 * kM, s_tcodes, NTn * kM, s));
+    HIPCHK(ctx, h2d_copy(ctx, ctx->g_empty.as<uint8_t>() + G0, s_empty, (size_t)Gn, s));
+    lap("new points");
+    // (3) the offset tables of the whole shard, aside
+    TableSet nt;
+    HIPCHK(ctx, upload_table(ctx, nt.minu_off, mo, s)); HIPCHK(ctx, upload_table(ctx, nt.tile_off, toff, s)); HIPCHK(ctx, upload_table(ctx, nt.tex_off, to, s));
+    HIPCHK(ctx, upload_table(ctx, nt.q_blk, qb, s)); HIPCHK(ctx, upload_table(ctx, nt.t32_blk, tb, s));
+    // (4) the derived layouts of the new templates: views whose CSR bases are shifted to the first of them (offsets are absolute)
+    HIPCHK(ctx, launch_fragment_tiles(ctx->g_minu_des.as<float>(), nt.minu_off.as<int32_t>() + G0, nt.tile_off.as<int32_t>() + G0, (int)Gn, ctx->g_minu_frag.p, s));
+    if (ctx->mf_gal_built) {
+        GalleryDev v = ctx->gal;
+        v.G = (int32_t)G1; v.tex_off = nt.tex_off.as<int32_t>();
+        HIPCHK(ctx, launch_mf_tiles(v, nt.t32_blk.as<int32_t>(), ctx->mf_cwn.as<float>(), ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, s, (int)G0, (int)Gn));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    lap("tables and derived layouts");
+    // (5) the switch
+    std::swap(ctx->g_minu_off, nt.minu_off); std::swap(ctx->g_minu_tile_off, nt.tile_off); std::swap(ctx->g_tex_off, nt.tex_off);
+    std::swap(ctx->g_tex_q_blk, nt.q_blk); std::swap(ctx->g_tex_t32_blk, nt.t32_blk);
+    refresh_gallery_view(ctx);
+    ctx->gal.G = (int32_t)G1;
+    ctx->max_nR = max_nR; ctx->q_blocks = q_blocks; ctx->t32_tiles = t32; ctx->minu_tiles = (int64_t)tiles1;
+    ctx->total_minutiae = (int64_t)NM1; ctx->total_tex_points = (int64_t)NT1;
+    ctx->res_empty.insert(ctx->res_empty.end(), s_empty, s_empty + Gn);
+    ctx->res_mo = std::move(mo); ctx->res_to = std::move(to);
+    invalidate_lazy_streams(ctx);
+    ++ctx->gallery_epoch;
+    release_staging(ctx);
+    ctx->reopened = false;
+    lap("switch, staging released");
+    return AFIS_OK;
+}
+
+int afis_gallery_remove(afis_ctx* ctx, const int64_t* idx, int64_t n)
+{
+    if (!ctx || n < 0 || (n > 0 && !idx)) return fail(ctx, AFIS_EINVAL, "afis_gallery_remove: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_remove: commit the gallery first");
+    if (ctx->reopened && (ctx->pend ? ctx->pend_count : ctx->hg.size()) > 0)
+        return fail(ctx, AFIS_ESTATE, "afis_gallery_remove: templates are staged; commit them first");
+    const int64_t G = ctx->gal.G;
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < ctx->index_base || idx[i] >= ctx->index_base + G) return fail(ctx, AFIS_EINVAL, "afis_gallery_remove: gallery index outside this shard");
+    std::vector<uint8_t> gone((size_t)G, 0);
+    bool any = false;
+    for (int64_t i = 0; i < n; ++i) { const size_t g = (size_t)(idx[i] - ctx->index_base); if (!ctx->res_empty[g]) { gone[g] = 1; any = true; } }
+    if (!any) return AFIS_OK;                                               // only empty entries listed: nothing to do
+    std::vector<int32_t> mo((size_t)G + 1, 0), to((size_t)G + 1, 0), toff, qb, tb;
+    for (size_t t = 0; t < (size_t)G; ++t) {
+        mo[t + 1] = mo[t] + (gone[t] ? 0 : ctx->res_mo[t + 1] - ctx->res_mo[t]);
+        to[t + 1] = to[t] + (gone[t] ? 0 : ctx->res_to[t + 1] - ctx->res_to[t]);
+    }
+    int64_t q_blocks = 0, t32 = 0; int max_nR = 0;
+    derived_offsets(mo, to, toff, qb, tb, q_blocks, t32, max_nR);
+    std::vector<uint8_t> empty = ctx->res_empty;
+    for (size_t t = 0; t < (size_t)G; ++t) if (gone[t]) empty[t] = 1;
+    { const int rcq = quiesce(ctx, "afis_gallery_remove"); if (rcq != AFIS_OK) return rcq; }
+    hipStream_t s = ctx->stream;
+    const int64_t NM1 = mo[(size_t)G], NT1 = to[(size_t)G];
+    // the parity tap afis_debug_compact_stats: device time of the compaction kernels of this call (HIP events around each launch) and the bytes they copied
+    double compact_us = 0; int64_t compact_bytes = 0;
+    hipEvent_t ev_c[2] = {nullptr, nullptr};
+    for (hipEvent_t& e : ev_c) HIPCHK(ctx, hipEventCreate(&e));
+    bool touched = false;                                                   // an array has been replaced: from here on a failure cannot leave the old shard behind
+    auto body = [&]() -> int {
+        TableSet nt;                                                        // the new CSR offsets beside the old ones: the compaction reads both
+        HIPCHK(ctx, upload_table(ctx, nt.minu_off, mo, s)); HIPCHK(ctx, upload_table(ctx, nt.tex_off, to, s));
+        // One array at a time into a buffer of its new size, the old one released before the next: the transient memory is the largest array's, and that one goes first —
+        // when its buffer can be had, the smaller ones that follow fit into what it has just given back.
+        struct Arr { DevBuf* b; int elem; bool minu; };
+        const Arr arrs[] = {{&ctx->g_minu_des, kDes * 4, true}, {&ctx->g_tex_codes, kM, false}, {&ctx->g_minu_xy, 4, true}, {&ctx->g_minu_ori, 4, true}, {&ctx->g_tex_xy, 4, false}, {&ctx->g_tex_ori, 4, false}};
+        for (const Arr& a : arrs) {
+            const int64_t n_new = a.minu ? NM1 : NT1;
+            DevBuf fresh;
+            HIPCHK(ctx, fresh.ensure(std::max<size_t>((size_t)n_new * (size_t)a.elem, 16)));
+            hipError_t e = hipEventRecord(ev_c[0], s);
+            if (e == hipSuccess) e = launch_compact_ranges(a.b->p, fresh.p, a.elem, a.minu ? ctx->g_minu_off.as<int32_t>() : ctx->g_tex_off.as<int32_t>(),
+                                                 a.minu ? nt.minu_off.as<int32_t>() : nt.tex_off.as<int32_t>(), (int)G, n_new, s);
+            if (e == hipSuccess) e = hipEventRecord(ev_c[1], s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            float ms = 0;
+            if (e == hipSuccess && n_new > 0) e = hipEventElapsedTime(&ms, ev_c[0], ev_c[1]);
+            if (e != hipSuccess) { fresh.release(); HIPCHK(ctx, e); }
+            compact_us += (double)ms * 1e3; compact_bytes += n_new * a.elem;
+            std::swap(*a.b, fresh); fresh.release();
+            touched = true;
+            refresh_gallery_view(ctx);
+        }
+        std::swap(ctx->g_minu_off, nt.minu_off); std::swap(ctx->g_tex_off, nt.tex_off);
+        HIPCHK(ctx, upload_table(ctx, ctx->g_minu_tile_off, toff, s)); HIPCHK(ctx, upload_table(ctx, ctx->g_tex_q_blk, qb, s)); HIPCHK(ctx, upload_table(ctx, ctx->g_tex_t32_blk, tb, s));      // ([G + 1] as before: written in place)
+        HIPCHK(ctx, h2d_copy(ctx, ctx->g_empty.p, empty.data(), (size_t)G, s));
+        refresh_gallery_view(ctx);
+        // the derived layouts, from the compacted arrays into the buffers they already have (they only shrink)
+        HIPCHK(ctx, launch_fragment_tiles(ctx->g_minu_des.as<float>(), ctx->g_minu_off.as<int32_t>(), ctx->g_minu_tile_off.as<int32_t>(), (int)G, ctx->g_minu_frag.p, s));
+        if (ctx->mf_gal_built)
+            HIPCHK(ctx, launch_mf_tiles(ctx->gal, ctx->g_tex_t32_blk.as<int32_t>(), ctx->mf_cwn.as<float>(), ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return AFIS_OK;
+    };
+    const int rc = body();
+    for (hipEvent_t e : ev_c) (void)hipEventDestroy(e);
+    if (rc != AFIS_OK) {
+        if (touched) {                                                      // half-compacted arrays are no gallery: the context is back to "not committed", nothing staged
+            (void)hipStreamSynchronize(s);
+            free_gallery_dev(ctx);
+            ctx->gal = GalleryDev(); ctx->committed = false; ctx->reopened = false;
+            ++ctx->gallery_epoch;                                           // handles uploaded against the dropped shard stay refused whatever is committed next
+            ctx->res_empty.clear(); ctx->res_mo.clear(); ctx->res_to.clear();
+            ctx->err += " [afis_gallery_remove failed half-way: the resident shard was dropped; stage and commit the gallery again]";
+        }
+        return rc;
+    }
+    ctx->max_nR = max_nR; ctx->q_blocks = q_blocks; ctx->t32_tiles = t32; ctx->minu_tiles = toff[(size_t)G];
+    ctx->total_minutiae = NM1; ctx->total_tex_points = NT1;
+    ctx->res_empty = std::move(empty); ctx->res_mo = std::move(mo); ctx->res_to = std::move(to);
+    ctx->compact_us = (int64_t)compact_us; ctx->compact_bytes = compact_bytes;
+    invalidate_lazy_streams(ctx);
+    ++ctx->gallery_epoch;
+    return AFIS_OK;
+}
+
+int afis_gallery_export(afis_ctx* ctx, const char* path, const char* const* names)
+{
+    if (!ctx || !path) return fail(ctx, AFIS_EINVAL, "afis_gallery_export: null argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_export: commit the gallery first (afis_gallery_save writes a staged one)");
+    { const int rcq = quiesce(ctx, "afis_gallery_export"); if (rcq != AFIS_OK) return rcq; }
+    const int64_t G = ctx->gal.G;
+    const size_t NM = (size_t)ctx->total_minutiae, NT = (size_t)ctx->total_tex_points;
+    HostGallery out;
+    out.minu_off.assign(ctx->res_mo.begin(), ctx->res_mo.end()); out.tex_off.assign(ctx->res_to.begin(), ctx->res_to.end());
+    out.empty = ctx->res_empty;
+    std::vector<short2> mxy(NM), txy(NT);
+    out.mx.resize(NM); out.my.resize(NM); out.mori.resize(NM); out.mdes.resize(NM * kDes);
+    out.tx.resize(NT); out.ty.resize(NT); out.tori.resize(NT); out.tcodes.resize(NT * kM);
+    if (NM) {
+        HIPCHK(ctx, hipMemcpy(mxy.data(), ctx->g_minu_xy.p, NM * 4, hipMemcpyDeviceToHost)); HIPCHK(ctx, hipMemcpy(out.mori.data(), ctx->g_minu_ori.p, NM * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(out.mdes.data(), ctx->g_minu_des.p, NM * kDes * 4, hipMemcpyDeviceToHost));
+    }
+    if (NT) {
+        HIPCHK(ctx, hipMemcpy(txy.data(), ctx->g_tex_xy.p, NT * 4, hipMemcpyDeviceToHost)); HIPCHK(ctx, hipMemcpy(out.tori.data(), ctx->g_tex_ori.p, NT * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(out.tcodes.data(), ctx->g_tex_codes.p, NT * kM, hipMemcpyDeviceToHost));
+    }
+    parallel_for((int64_t)NM, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) { out.mx[(size_t)i] = mxy[(size_t)i].x; out.my[(size_t)i] = mxy[(size_t)i].y; } });
+    parallel_for((int64_t)NT, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) { out.tx[(size_t)i] = txy[(size_t)i].x; out.ty[(size_t)i] = txy[(size_t)i].y; } });
+    std::vector<std::string> nm;
+    if (names) for (int64_t i = 0; i < G; ++i) nm.emplace_back(names[i] ? names[i] : "");
+    std::string err;
+    if (!write_gallery_container(path, out, nm, err)) return fail(ctx, AFIS_EFORMAT, "afis_gallery_export: " + err);
+    return AFIS_OK;
+}
+
+int64_t afis_gallery_size(const afis_ctx* ctx) { return !ctx ? 0 : (int64_t)ctx->res_empty.size() + (ctx->pend ? ctx->pend_count : ctx->hg.size()); }
 
 }  // extern "C"

@@ -220,7 +220,7 @@ int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_
     const int64_t want = ctx->query_batch > 0 ? ctx->query_batch : launch_group_latents(G);
     int per = (int)std::max<int64_t>(1, std::min<int64_t>(want, by_mem));
     afis_queries* q = new afis_queries();
-    q->n_q = n_q;
+    q->n_q = n_q; q->gallery_epoch = ctx->gallery_epoch;
     const int64_t budget = group_budget_bytes(ctx);
     // Launch groups are contiguous runs of at most `per` queries; with the matrix-core bound pass (adc_variant 9) the cuts are placed where its row groups of 768 latent
     // texture rows are fewest (launch_group_cuts, afis_device.h; tests/test_host.py checks the rule on the CPU).  Results do not depend on the cuts.
@@ -472,6 +472,10 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     if (!ctx || !q) return fail(ctx, AFIS_EINVAL, "afis_search_resident: null argument");
     if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_search: commit the gallery first");
     if (k < 0 || (k > 0 && (!topk_idx || !topk_score))) return fail(ctx, AFIS_EINVAL, "afis_search: k > 0 needs topk_idx and topk_score");
+    // A handle's launch groups were cut for the shard size (and the free memory) of the moment it was uploaded: against a shard that has grown since, a group's per-pair
+    // buffers could exceed the budget.  Such a handle is refused; uploading the latents again takes milliseconds.
+    if (q->gallery_epoch != ctx->gallery_epoch)
+        return fail(ctx, AFIS_ESTATE, "afis_search_resident: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these queries were uploaded; free the handle and upload them again");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
     const GalleryDev& g = ctx->gal;
@@ -726,7 +730,7 @@ int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const i
                 int32_t off[2] = {0, 0};
                 if (hipMemcpy(off, g.minu_off + gi, sizeof(off), hipMemcpyDeviceToHost) != hipSuccess) { err = fail(ctx, AFIS_EDEVICE, "afis_correspondences: copy back failed"); break; }
                 for (int sl = 0; sl < 3; ++sl)
-                    if (ctx->hg.empty[(size_t)gi] || off[1] - off[0] <= 0 || query->n_minu <= kSelected[sl]) counts[i * 3 + sl] = -1;
+                    if (ctx->res_empty[(size_t)gi] || off[1] - off[0] <= 0 || query->n_minu <= kSelected[sl]) counts[i * 3 + sl] = -1;
             }
         } else (void)hipStreamSynchronize(s);
         return err;
@@ -750,7 +754,7 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
     const int64_t G = ctx->gal.G;
     const int width = n_minu + n_tex;
     if (query_status) *query_status = (n_minu <= 0 && n_tex <= 0) ? AFIS_QUERY_LATENT_EMPTY : AFIS_QUERY_OK;     // :345-348
-    if (rolled_status) for (int64_t g = 0; g < G; ++g) rolled_status[g] = ctx->hg.empty[(size_t)g] ? 2 : 0;        // :350-353
+    if (rolled_status) for (int64_t g = 0; g < G; ++g) rolled_status[g] = ctx->res_empty[(size_t)g] ? 2 : 0;        // :350-353
     for (size_t i = 0; i < (size_t)G * width; ++i) scores[i] = 0.0f;                                             // :342-343
     if (width == 0 || G == 0) return AFIS_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -767,7 +771,7 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
             for (int s = 0; s < 3; ++s) spec[(size_t)j * 4 + s] = 3 * (j0 + j) + s < n_minu ? 3 * (j0 + j) + s : -1;
             spec[(size_t)j * 4 + 3] = j0 + j < n_tex ? j0 + j : -1;
         }
-        afis_queries q; q.n_q = nq;
+        afis_queries q; q.n_q = nq; q.gallery_epoch = ctx->gallery_epoch;
         q.groups.emplace_back();
         int rc = build_group(ctx, views.data(), nq, q.groups.back(), q.status, spec.data());
         if (rc == AFIS_OK) {
@@ -780,7 +784,7 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
         if (rc != AFIS_OK) return rc;
         for (int j = 0; j < nq; ++j)
             for (int64_t g = 0; g < G; ++g) {
-                if (ctx->hg.empty[(size_t)g]) continue;                      // rolled empty: the vector stays zero (return 2 before any scorer)
+                if (ctx->res_empty[(size_t)g]) continue;                      // rolled empty: the vector stays zero (return 2 before any scorer)
                 const float* p = &parts[((size_t)j * G + g) * 4];
                 float* o = scores + (size_t)g * width;
                 for (int s = 0; s < 3; ++s) if (3 * (j0 + j) + s < n_minu) o[3 * (j0 + j) + s] = p[s];

@@ -76,6 +76,13 @@ int afis_debug_refine_stats(afis_ctx* ctx, unsigned long long* out8, int reset)
     return AFIS_OK;
 }
 
+int afis_debug_compact_stats(afis_ctx* ctx, long long* out2)
+{
+    if (!ctx || !out2) return fail(ctx, AFIS_EINVAL, "afis_debug_compact_stats: bad argument");
+    out2[0] = ctx->compact_us; out2[1] = ctx->compact_bytes;
+    return AFIS_OK;
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");
@@ -203,7 +210,7 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
         HIPCHK(ctx, hipMemcpyAsync(h.data(), d_out.p, h.size() * sizeof(MinuCand), hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(hn, d_n.p, 12, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
-        if (ctx->hg.empty[(size_t)gidx]) return AFIS_OK;                   // rolled empty: no scorer runs
+        if (ctx->res_empty[(size_t)gidx]) return AFIS_OK;                   // rolled empty: no scorer runs
         *n = hn[slot];
         for (int t = 0; t < hn[slot]; ++t) { const MinuCand& c = h[(size_t)slot * cap + t]; sim[t] = c.sim; li[t] = c.li; ri[t] = c.ri; }
         return AFIS_OK;

@@ -47,11 +47,11 @@ class Timing(C.Structure):
 
 
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
-           "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_save", "afis_gallery_load",
+           "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
-TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats"]
+TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -77,6 +77,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.afis_gallery_file_info.argtypes = [C.c_char_p, i64p, i64p, i64p, i32p]
     lib.afis_gallery_file_names.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.afis_gallery_size.argtypes = [vp]; lib.afis_gallery_size.restype = C.c_int64
+    if hasattr(lib, "afis_gallery_reopen"):                             # the live gallery; absent from older builds compared by tools/lib_ab.py
+        lib.afis_gallery_reopen.argtypes = [vp]
+        lib.afis_gallery_remove.argtypes = [vp, i64p, C.c_int64]
+        lib.afis_gallery_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p)]
     lib.afis_search.argtypes = [vp, C.POINTER(TemplateView), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_search_dat.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_queries_upload.argtypes = [vp, C.POINTER(TemplateView), C.c_int, C.POINTER(vp)]
@@ -102,6 +106,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_atan2_grid.argtypes = [vp, C.c_int, fp]
     if hasattr(lib, "afis_debug_graph_arith"):
         lib.afis_debug_graph_arith.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    if hasattr(lib, "afis_debug_compact_stats"):
+        lib.afis_debug_compact_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(lib, "afis_debug_refine_stats"):
         lib.afis_debug_refine_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.c_int]
     return lib
@@ -248,9 +254,36 @@ class Matcher:
     def gallery_commit(self, index_base: int = 0):
         self._chk(self.lib.afis_gallery_commit(self.ctx, index_base))
 
+    def gallery_reopen(self):
+        """Open a staging area beside the committed shard: the gallery_add* / gallery_load calls work again, and the next gallery_commit appends what they staged
+        (indices index_base + G_old ...) without uploading the resident templates again."""
+        self._chk(self.lib.afis_gallery_reopen(self.ctx))
+
+    def gallery_remove(self, idx: Sequence[int]):
+        """Turn the listed entries (global indices, as search reports them) into empty entries (score -1); every other template keeps its index."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        self._chk(self.lib.afis_gallery_remove(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a)))
+
+    def gallery_export(self, path: str, names: Sequence[str] = None):
+        """Write the RESIDENT shard as a packed container: the file gallery_save writes from a context staged with the same entries."""
+        arr = None
+        if names is not None:
+            if len(names) != self.resident_size:                          # the library reads one name per resident template
+                raise AfisError(f"gallery_export: {len(names)} names for {self.resident_size} resident templates")
+            arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        self._chk(self.lib.afis_gallery_export(self.ctx, path.encode(), arr))
+
     @property
     def gallery_size(self) -> int:
         return int(self.lib.afis_gallery_size(self.ctx))
+
+    @property
+    def resident_size(self) -> int:
+        """Templates of the committed shard — what a search scores; gallery_size also counts what is staged beside it after gallery_reopen."""
+        v = C.c_int64(0)
+        if self.lib.afis_get_option(self.ctx, b"gallery_resident", C.byref(v)) == 0:
+            return int(v.value)
+        return self.gallery_size                                          # (a build without the live gallery: nothing can be staged beside a committed shard)
 
     def set_option(self, name: str, value: int):
         self._chk(self.lib.afis_set_option(self.ctx, name.encode(), value))
@@ -264,7 +297,7 @@ class Matcher:
 
     # ---- search -----------------------------------------------------------------------------------------------
     def _alloc(self, nq, k, want_scores, want_parts):
-        G = self.gallery_size
+        G = self.resident_size
         scores = np.empty((nq, G), np.float32) if want_scores else None
         parts = np.empty((nq, G, 4), np.float32) if want_parts else None
         status = np.zeros(nq, np.int32)
@@ -322,7 +355,7 @@ class Matcher:
     def One2One_matching_all_templates(self, latent: FPTemplate):
         """matcher.cpp:339-374 against every gallery template: (query status, rolled status [G], scores [G][n_minu + n_tex])."""
         v = _Views([latent])
-        G = self.gallery_size; width = len(latent.minu) + len(latent.tex)
+        G = self.resident_size; width = len(latent.minu) + len(latent.tex)
         scores = np.zeros((max(G, 1), max(width, 1)), np.float32); rs = np.zeros(max(G, 1), np.int32); qs = C.c_int32(0)
         self._chk(self.lib.afis_match_all_templates(self.ctx, v.arr, _ptr(scores, C.c_float), _ptr(rs, C.c_int32), C.byref(qs)))
         return qs.value, rs[:G], scores[:G, :width] if width else np.zeros((G, 0), np.float32)
@@ -379,6 +412,12 @@ class Matcher:
         out = (C.c_ulonglong * 8)()
         self._chk(self._tap("afis_debug_refine_stats")(self.ctx, out, 1 if reset else 0))
         return dict(zip(("pairs", "rows", "rows_evaluated", "cells_evaluated", "rows_evaluated_in_full", "bound_violations"), list(out)[:6]))
+
+    def compact_stats(self):
+        """(device microseconds, bytes copied) of the compaction kernels of the last gallery_remove."""
+        out = (C.c_longlong * 2)()
+        self._chk(self._tap("afis_debug_compact_stats")(self.ctx, out))
+        return int(out[0]), int(out[1])
 
     def debug_stage_list(self, latent: FPTemplate, g: int, which: int, stage: int):
         """(sim, li, ri) of the scorer's correspondence list after a stage (None when the scorer is not run)."""
