@@ -2,6 +2,7 @@
 // the PQ encoder entry points, and afis_gallery_commit: SoA packing, upload through pinned buffers, the device-side derived streams.
 // Replaces the per-pair load_FP_template(rolled) of matching/matcher.cpp:173 / :278: parse once, keep the shard resident in HBM.
 #include "afis_ctx.h"
+#include "afis_offsets.h"
 #include <sys/stat.h>
 
 using namespace afis;
@@ -409,9 +410,6 @@ static hipError_t upload_table(afis_ctx* ctx, DevBuf& b, const std::vector<int32
     const hipError_t e = b.ensure(std::max<size_t>(v.size() * sizeof(int32_t), 16));
     return e != hipSuccess ? e : h2d_copy(ctx, b.p, v.data(), v.size() * sizeof(int32_t), s);
 }
-static void derived_offsets(const std::vector<int32_t>& mo, const std::vector<int32_t>& to, std::vector<int32_t>& toff, std::vector<int32_t>& qb, std::vector<int32_t>& tb,
-                            int64_t& n_q_blocks, int64_t& n_t32, int& max_nR);
-
 static int commit_shard(afis_ctx* ctx, int64_t index_base);
 static int append_shard(afis_ctx* ctx);
 static void release_staging(afis_ctx* ctx);
@@ -584,23 +582,6 @@ static void invalidate_lazy_streams(afis_ctx* ctx)
 {
     ctx->codes_q_built = false; ctx->codes_cf_built = false;
     ctx->gal.tex_codes_cf = nullptr; ctx->gal.tex_cf_blk = nullptr;
-}
-
-// block offsets of variant 8's code stream (64 points) and tile offsets of the bound pass's (32 points) and of the descriptor fragments (16), from the CSR offsets
-static void derived_offsets(const std::vector<int32_t>& mo, const std::vector<int32_t>& to, std::vector<int32_t>& toff, std::vector<int32_t>& qb, std::vector<int32_t>& tb,
-                            int64_t& n_q_blocks, int64_t& n_t32, int& max_nR)
-{
-    const size_t G = mo.size() - 1;
-    toff.assign(G + 1, 0); qb.assign(G + 1, 0); tb.assign(G + 1, 0);
-    int64_t nq = 0, nt = 0; max_nR = 0;
-    for (size_t t = 0; t < G; ++t) {
-        toff[t + 1] = toff[t] + (mo[t + 1] - mo[t] + 15) / 16;
-        qb[t] = (int32_t)nq; nq += ((int64_t)(to[t + 1] - to[t]) + 63) / 64;
-        tb[t] = (int32_t)std::min<int64_t>(nt, 0x7fffffff); nt += ((int64_t)(to[t + 1] - to[t]) + 31) / 32;
-        max_nR = std::max(max_nR, mo[t + 1] - mo[t]);
-    }
-    qb[G] = (int32_t)nq; tb[G] = (int32_t)std::min<int64_t>(nt, 0x7fffffff);
-    n_q_blocks = nq; n_t32 = nt;
 }
 
 // DevBuf::ensure frees before it allocates; the resident part must survive: the new buffer first (with headroom: one capacity copy per eighth of growth), a device-to-device

@@ -6,6 +6,7 @@
 //   match_selftest -selftest-exchange                        rendezvous: rank 0's 128 bytes reach every rank (RANK/WORLD_SIZE/MASTER_* env)
 //   match_selftest -selftest-allgather                       AFIS_EXCHANGE=tcp all-gather + the agreement point, N local ranks
 //   match_selftest -selftest-groups <rows file> -per N [-plain]   the launch-group rule (afis_device.h: launch_group_cuts / launch_group_latents): cut positions for the listed latent texture row counts
+//   match_selftest -selftest-offsets <counts file>          the gallery's derived offset tables (afis_offsets.h: derived_offsets) for the listed (minutiae, texture point) counts per template
 //   match_selftest -selftest-classes                         the candidate kernel's shape-class rule (afis_device.h: rt_max_rows) as a table: nR  L1 L2 L4  stride1 stride2 stride4
 #include <cstring>
 #include <fstream>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "afis_device.h"
+#include "afis_offsets.h"
 #include "cli_util.h"
 #include "rank_exchange.h"
 
@@ -26,6 +28,21 @@ int main(int argc, char** argv)
                   << rt_class_keys_per_thread(4) << " " << rt_class_max_rolled(4) << " " << rt_class_max_latent(4) << std::endl;
         for (int nR = 0; nR <= 2000; ++nR)
             std::cout << nR << " " << rt_max_rows(1, nR) << " " << rt_max_rows(2, nR) << " " << rt_max_rows(4, nR) << " " << rt_row_stride(1, nR) << " " << rt_row_stride(2, nR) << " " << rt_row_stride(4, nR) << std::endl;
+        return 0;
+    }
+    if (args.cmdOptionExists("-selftest-offsets")) {                            // the shard's derived tables (no GPU): one "minutiae texture-points" pair per line
+        std::ifstream f(args.getCmdOption("-selftest-offsets"));
+        std::vector<int32_t> mo{0}, to{0}, toff, qb, tb; long long a, b;
+        while (f >> a >> b) { mo.push_back((int32_t)(mo.back() + a)); to.push_back((int32_t)(to.back() + b)); }
+        int64_t nq = 0, nt = 0; int max_nR = 0;
+        derived_offsets(mo, to, toff, qb, tb, nq, nt, max_nR);
+        const size_t G = mo.size() - 1;
+        std::cout << G << " " << mo[G] << " " << to[G] << " " << toff[G] << " " << nq << " " << nt << " " << max_nR << std::endl;
+        // every table in full would be 3 x 10^6 lines: weighted sums modulo 2^64 over all entries, then every 997th entry and the last
+        unsigned long long h[3] = {0, 0, 0};
+        for (size_t t = 0; t <= G; ++t) { const unsigned long long w = 2 * (unsigned long long)t + 1; h[0] += w * (unsigned long long)toff[t]; h[1] += w * (unsigned long long)qb[t]; h[2] += w * (unsigned long long)tb[t]; }
+        std::cout << h[0] << " " << h[1] << " " << h[2] << std::endl;
+        for (size_t t = 0;; t = std::min(t + 997, G)) { std::cout << t << " " << toff[t] << " " << qb[t] << " " << tb[t] << std::endl; if (t == G) break; }
         return 0;
     }
     if (args.cmdOptionExists("-selftest-groups")) {                             // the launch-group rule (no GPU): rows per latent (one int per line), latents per launch at most

@@ -656,3 +656,36 @@ def record_parts(vec_bits, info, status):
         f = np.float32(np.float32(at(0) + at(1)) + at(2))
         out[4] = np.float32(np.float64(f) + np.float64(at(28)) * 0.3)
     return out.view(np.uint32)
+
+
+# ---- one slice of a large synthetic gallery, committed the way a rank commits its shard (tests/test_gpu_fullsize.py, tests/test_gpu_large_shard.py) ----
+def committed_slice(codebook_bytes, cb, seed, G, lats, lo, hi, index_base=0, n_partial=3, taps=False):
+    """Templates [lo, hi) of the G-template synthetic gallery, generated, planted with the latents' mates and committed alone at index_base + lo, exactly as rank r of a sharded
+    job would: -> (PackedGallery of the slice after planting, planted {latent: [(global gallery index, frac)]}, the committed Matcher; the caller closes it)."""
+    M = importlib.import_module("msu-latentafis_amd.host.matcher")
+    gal = S.make_packed_gallery(seed, G, cb, lo, hi)
+    planted = S.plant_mates(seed, gal, cb, lats, G=G, lo=lo, n_partial=n_partial)
+    m = M.Matcher(codebook_bytes, taps=taps)
+    m.gallery_add_packed(gal); m.gallery_commit(index_base + lo)
+    return gal, planted, m
+
+
+# The sizes at which one shard's device arrays pass 4 GiB and its descriptor floats pass 2^31 (element sizes: csrc/afis_device.h — 96 fp32 per minutia, fragment tiles of
+# 16 descriptors = 6 x 64 float4 = 6144 bytes, 16 code bytes per texture point, the bound pass's stream padded to tiles of 32 points).
+LARGE_SHARD_LIMITS = {"minu_des_floats": 1 << 31, "minu_frag_bytes": 1 << 32, "tex_codes_bytes": 1 << 32, "codes_p_bytes": 1 << 32}
+
+
+def large_shard_quantities(nm, nt):
+    """The four quantities of LARGE_SHARD_LIMITS for per-template minutiae / texture point counts nm, nt."""
+    nm = np.asarray(nm, np.int64); nt = np.asarray(nt, np.int64)
+    return {"minu_des_floats": int(nm.sum()) * 96, "minu_frag_bytes": int(((nm + 15) // 16).sum()) * 6144,
+            "tex_codes_bytes": int(nt.sum()) * 16, "codes_p_bytes": int(((nt + 31) // 32).sum()) * 32 * 16}
+
+
+def large_shard_size(seed, slice_size=50000, limit=2000000):
+    """The smallest multiple of slice_size for which S.gallery_counts(seed, G) passes every limit of LARGE_SHARD_LIMITS (the counts of a synthetic gallery depend on G)."""
+    for G in range(slice_size, limit + 1, slice_size):
+        q = large_shard_quantities(*S.gallery_counts(seed, G))
+        if all(q[k] > LARGE_SHARD_LIMITS[k] for k in LARGE_SHARD_LIMITS):
+            return G
+    raise AssertionError("no gallery size up to %d passes the limits" % limit)

@@ -17,6 +17,8 @@ import os
 import numpy as np
 import pytest
 
+import cases
+
 pytestmark = pytest.mark.gpu
 T = importlib.import_module("msu-latentafis_amd.host.templates")
 S = importlib.import_module("msu-latentafis_amd.host.synth")
@@ -211,10 +213,7 @@ def _search_shards(codebook_bytes, cb, seed, G, lats, world, k, keep=None, n_par
     assert bounds[0][0] == 0 and bounds[-1][1] == G and all(bounds[r][1] == bounds[r + 1][0] for r in range(world - 1))
     per_idx, per_sc, kept, planted = [], [], {}, None
     for lo, hi in bounds:
-        gal = S.make_packed_gallery(seed, G, cb, lo, hi)
-        planted = S.plant_mates(seed, gal, cb, lats, G=G, lo=lo, n_partial=n_partial)
-        m = M.Matcher(codebook_bytes, taps=stats is not None)
-        m.gallery_add_packed(gal); m.gallery_commit(lo)
+        gal, planted, m = cases.committed_slice(codebook_bytes, cb, seed, G, lats, lo, hi, n_partial=n_partial, taps=stats is not None)
         if stats is not None: m.set_option("mf_stats", 1)                # the bound pass's self-check counters of this shard (stats: a dict that accumulates them)
         res = m.search(lats, k=k, want_parts=True)
         if stats is not None:

@@ -403,6 +403,47 @@ def test_launch_group_rule_places_the_cuts_where_the_row_groups_are_fewest(tmp_p
     assert auto == {1: 128, 12500: 128, 39000: 128, 40000: 125, 50000: 100, 100000: 50, 250000: 20, 500000: 10, 1000000: 10}
 
 
+def test_derived_offset_tables_of_a_million_templates_and_the_large_shard_size(tmp_path):
+    """The tile tables every kernel indexes a shard with are made on the host by one routine (afis_offsets.h: derived_offsets — fragment tiles of 16 descriptors, variant 8's
+    blocks of 64 texture points, the bound pass's tiles of 32), in int32.  Against a numpy restatement on the counts of the 1 M-template synthetic gallery: totals, a weighted
+    sum over every entry and every 997th entry of each table.  And the size tests/test_gpu_large_shard.py picks (cases.large_shard_size) does pass its four limits, while the
+    multiple of the slice size below it does not: a wrong size shows up here, without a GPU."""
+    import subprocess
+    import importlib
+    S = importlib.import_module("msu-latentafis_amd.host.synth")
+    csrc = os.path.join(ROOT, "msu-latentafis_amd", "csrc")
+    exe = os.path.join(csrc, "match_selftest")
+    subprocess.run(["make", "-s", "-C", csrc, "match_selftest"], check=True)
+
+    def check(nm, nt):
+        f = tmp_path / "counts.txt"
+        np.savetxt(f, np.stack([nm, nt], axis=1), fmt="%d")
+        out = subprocess.run([exe, "-selftest-offsets", str(f)], capture_output=True, text=True, check=True).stdout.splitlines()
+        G = len(nm)
+        toff = np.concatenate([[0], np.cumsum((nm + 15) // 16)]); qb = np.concatenate([[0], np.cumsum((nt + 63) // 64)]); tb = np.concatenate([[0], np.cumsum((nt + 31) // 32)])
+        assert [int(x) for x in out[0].split()] == [G, int(nm.sum()), int(nt.sum()), int(toff[G]), int(qb[G]), int(tb[G]), int(nm.max()) if G else 0]
+        w = (2 * np.arange(G + 1, dtype=np.uint64) + np.uint64(1))
+        with np.errstate(over="ignore"):
+            want = [int((w * t.astype(np.uint64)).sum(dtype=np.uint64)) for t in (toff, qb, tb)]
+        assert [int(x) for x in out[1].split()] == want
+        rows = np.array([[int(x) for x in line.split()] for line in out[2:]], np.int64)
+        at = np.unique(np.concatenate([np.arange(0, G + 1, 997), [G]]))
+        assert np.array_equal(rows[:, 0], at) and np.array_equal(rows[:, 1], toff[at]) and np.array_equal(rows[:, 2], qb[at]) and np.array_equal(rows[:, 3], tb[at])
+
+    nm, nt = S.gallery_counts(31337, 1000000)
+    check(nm, nt)
+    check(np.array([1, 15, 16, 17, 0, 2000, 32], np.int64), np.array([0, 1, 31, 32, 33, 63, 1000], np.int64))
+    G = cases.large_shard_size(31337, 50000)
+    q = cases.large_shard_quantities(*S.gallery_counts(31337, G))
+    assert all(q[k] > cases.LARGE_SHARD_LIMITS[k] for k in q), (G, q)
+    below = cases.large_shard_quantities(*S.gallery_counts(31337, G - 50000))
+    assert any(below[k] <= cases.LARGE_SHARD_LIMITS[k] for k in below) and 300000 <= G <= 450000, (G, below)
+    nm, nt = S.gallery_counts(31337, G)
+    assert int(nm.sum()) > 22369621 and int(((nm + 15) // 16).sum()) > 699050 and int(nt.sum()) > 268435456    # the thresholds as counts of minutiae, tiles and points
+    # ... and the slices it is built from are consistent with the whole: the prefix sums a slice-by-slice build accumulates are the gallery's own
+    assert int(nm[:50000].sum()) + int(nm[50000:].sum()) == int(nm.sum())
+
+
 def test_both_libraries_read_only_the_operational_variables():
     """INTEGRATION.md section E lists the environment variables the library reads ("Operational"), and there are no others: `strings | grep ^AFIS_` of libafis_hip.so
     and of libafis_hip_test.so (the same objects plus the taps) must each be exactly the library's part of that table."""
