@@ -189,6 +189,34 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q,
                          int k, int64_t* topk_idx, float* topk_score);
 void afis_queries_free(afis_ctx* ctx, afis_queries* q);
 
+/* Subset search (no reference counterpart: the reference scores whatever the directory holds): score a candidate list of the resident shard — a filter of the caller's
+ * database, the survivors of a cheaper first stage, re-enrolled templates — without searching the whole shard and without staging the candidates from the host again.
+ * afis_subset_create   idx[0 .. n): global indices as afis_search reports them (index_base included), in any order; n == 0 is a valid, empty subset.  The listed
+ *                     templates' points are gathered on the device into a sub-shard of the subset's own: every SoA array, the derived layouts of the default path
+ *                     and an empty flag per entry (the streams of adc_variant 8 are laid out on the subset's first use of it, as they are for the shard).  Nothing of
+ *                     the gallery crosses PCIe: only the index list and the offset tables do.  An index outside the resident shard or listed twice is AFIS_EINVAL, an
+ *                     index of a template that is staged but not committed AFIS_ESTATE (as afis_gallery_remove), a call before the first commit AFIS_ESTATE; a refused
+ *                     call leaves nothing allocated and nothing changed.  Create and free first wait for all device work of the context, as every gallery edit does.
+ *                     Several subsets may be live at once; afis_destroy releases those that are left.  Their device memory is what option "subset_device_bytes"
+ *                     reports: launch groups cut afterwards (afis_queries_upload) are cut to the memory the subsets leave free.
+ * afis_search_subset / afis_search_subset_resident   as afis_search / afis_search_resident over the listed templates only: scores [n_q][n] and parts [n_q][n][4] with
+ *                     column j belonging to idx[j] in the caller's order (a listed entry that is empty scores -1), status as afis_search gives it, topk_idx GLOBAL
+ *                     indices, score descending, equal scores by ascending global index whatever order the list had; k > n pads as afis_search pads k > G; k <= 64 on
+ *                     the device, larger k on the host.  afis_timing counts the subset's work (pairs == n_q * n).  Every value is bit for bit the value afis_search
+ *                     gives for that (query, template) pair, under every option.
+ * A subset belongs to the gallery as it was when the subset was made: after an appending commit or a removal that changed the shard both search calls refuse it with
+ * AFIS_ESTATE (afis_subset_free still works).  A query handle stays valid for any subset of the shard it was uploaded for.  Full searches, afis_correspondences and
+ * afis_match_all_templates neither see a subset nor change when one exists. */
+typedef struct afis_subset afis_subset;
+int afis_subset_create(afis_ctx* ctx, const int64_t* idx, int64_t n, afis_subset** out);
+void afis_subset_free(afis_ctx* ctx, afis_subset* s);
+int afis_search_subset(afis_ctx* ctx, afis_subset* s, const afis_template_view* queries, int n_q,
+                       float* scores, float* parts, int32_t* status,
+                       int k, int64_t* topk_idx, float* topk_score);
+int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
+                                float* scores, float* parts, int32_t* status,
+                                int k, int64_t* topk_idx, float* topk_score);
+
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
  * 100k-1M template gallery is loaded — whole, or one contiguous shard per GPU — without touching 100k-1M small files.
@@ -276,7 +304,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * (hipExtStreamCreateWithCUMask) with the minutiae stage beside it on the other half: the pass is power-limited, half the CUs deliver 0.64 of its throughput;
  * 0 = one stream, kernels back to back; 32 ... 224 in steps of 32; the environment variable AFIS_BOUND_CUS sets the initial value.  "gallery_h2d_bytes" (read-only): the bytes handed to every host-to-device copy
  * of the context's gallery commits and removals so far, counted where the copies are issued: an appending commit adds its own points and the offset tables, not the resident shard.
- * "gallery_resident" (read-only): the templates of the committed shard, the G of afis_search's outputs (afis_gallery_size also counts what is staged beside it after afis_gallery_reopen). */
+ * "gallery_resident" (read-only): the templates of the committed shard, the G of afis_search's outputs (afis_gallery_size also counts what is staged beside it after afis_gallery_reopen).
+ * "subset_device_bytes" (read-only): the device bytes held by the context's live subsets (0 when there is none); "subset_gather_us" (read-only): the device time of the last
+ * afis_subset_create's gather launches, from HIP events around them. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -70,7 +70,48 @@ struct afis_queries {
     uint64_t gallery_epoch = 0;      // afis_ctx::gallery_epoch when the handle was uploaded: its launch groups were cut for that shard's size (afis_search_resident refuses it after an edit)
 };
 
-struct afis_ctx {
+// What describes "the shard being searched": the SoA arrays of a set of rolled templates in HBM with their offset tables, the derived layouts, the streams laid out on first
+// use and the counts the launch sequence of a search sizes its work by.  The context's resident shard is one instance (afis_ctx derives from it, so that ctx->gal and the
+// g_* buffers read as they always did); every live afis_subset holds another, gathered from the resident one on the device (afis_subset.cpp).  The launch sequence
+// (afis_search.cpp::search_shard) takes the instance.
+struct Shard {
+    GalleryDev gal;
+    DevBuf g_minu_off, g_minu_xy, g_minu_ori, g_minu_des, g_minu_frag, g_minu_tile_off, g_tex_off, g_tex_xy, g_tex_ori, g_tex_codes, g_tex_codes_cf, g_tex_cf_blk, g_tex_codes_q, g_tex_q_blk, g_tex_t32_blk, g_empty, g_task_ctr;
+    DevBuf g_codes_p, g_nrm_p, g_tile_meta;   // adc_variant 9: pair-aligned gallery codes / point terms / pair directory (commit, or first use)
+    bool codes_cf_built = false;         // variants 6 / 7 (test library): their lane-ordered code stream and its block offsets, laid out on first use
+    bool codes_q_built = false;          // adc_variant 8's lane-ordered code stream is laid out on first use
+    bool mf_gal_built = false;           // adc_variant 9's streams above exist
+    int64_t q_blocks = 0;
+    int64_t t32_tiles = 0;               // tiles of 32 rolled texture points (ceil(n/32) per template): the matrix-core bound pass's stream
+    int64_t minu_tiles = 0;              // 16-descriptor tiles in g_minu_frag
+    int max_nR = 0;
+    int64_t total_tex_points = 0;
+    int64_t total_minutiae = 0;          // rolled minutiae of the shard
+    int64_t index_base = 0;
+    std::vector<uint8_t> res_empty;      // [G] 1 = entry is empty (score -1, rolled_status 2)
+    std::vector<int32_t> res_mo, res_to; // [G + 1] the shard's CSR offsets (what g_minu_off / g_tex_off hold): the offset tables are rewritten whole from these
+    size_t device_bytes() const
+    {
+        size_t n = 0;
+        for (const DevBuf* b : {&g_minu_off, &g_minu_xy, &g_minu_ori, &g_minu_des, &g_minu_frag, &g_minu_tile_off, &g_tex_off, &g_tex_xy, &g_tex_ori, &g_tex_codes, &g_tex_codes_cf, &g_tex_cf_blk,
+                                &g_tex_codes_q, &g_tex_q_blk, &g_tex_t32_blk, &g_empty, &g_task_ctr, &g_codes_p, &g_nrm_p, &g_tile_meta}) n += b->bytes;
+        return n;
+    }
+};
+
+// A candidate list of the resident shard as a sub-shard of its own (afis_subset_create): the listed templates in ASCENDING global index order, so that the rank-list kernel's
+// tie rule (ascending position) is the rule on global indices; d_global maps a position back, d_pos is where the caller's column j sits.
+struct afis_subset {
+    Shard sh;
+    int64_t n = 0;
+    uint64_t gallery_epoch = 0;          // afis_ctx::gallery_epoch at creation: both search calls refuse the handle after an edit
+    bool identity = true;                // the caller listed the indices in ascending order: no column permutation on the way out
+    std::vector<int64_t> idx;            // [n] the caller's list (global indices, the caller's order): column j of the outputs
+    DevBuf d_global, d_pos;              // [n] int64 global index of position t; [n] int32 position of the caller's column j
+    size_t device_bytes() const { return sh.device_bytes() + d_global.bytes + d_pos.bytes; }
+};
+
+struct afis_ctx : Shard {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream_hi = nullptr;     // option bound_cus: the complement of stream_lo's CUs, for the minutiae stage while the bound pass runs
@@ -89,26 +130,15 @@ struct afis_ctx {
     bool committed = false;
     // The live gallery (afis_gallery_reopen / afis_gallery_remove / afis_gallery_export).  `hg` / `pend` hold STAGED templates only; what the host keeps of the resident shard is below.
     bool reopened = false;               // afis_gallery_reopen: the staging calls append to hg / pend again, beside the resident shard, until the next commit
-    std::vector<uint8_t> res_empty;      // [G] 1 = resident entry is empty (score -1, rolled_status 2)
-    std::vector<int32_t> res_mo, res_to; // [G + 1] the resident shard's CSR offsets (what g_minu_off / g_tex_off hold): the offset tables are rewritten whole from these
-    int64_t minu_tiles = 0;              // 16-descriptor tiles in g_minu_frag
     uint64_t gallery_epoch = 0;          // counts the edits of the resident shard (appending commits, removals)
+    std::vector<afis_subset*> subsets;   // live subsets (afis_subset_create .. afis_subset_free; afis_destroy releases what is left)
+    int64_t subset_gather_us = 0;        // option subset_gather_us (read-only): device time of the last afis_subset_create's gather launches (HIP events around them)
+    DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
-    int64_t index_base = 0;
-    GalleryDev gal;
-    DevBuf g_minu_off, g_minu_xy, g_minu_ori, g_minu_des, g_minu_frag, g_minu_tile_off, g_tex_off, g_tex_xy, g_tex_ori, g_tex_codes, g_tex_codes_cf, g_tex_cf_blk, g_tex_codes_q, g_tex_q_blk, g_tex_t32_blk, g_empty, g_task_ctr;
-    bool codes_cf_built = false;         // variants 6 / 7 (test library): their lane-ordered code stream and its block offsets, laid out on first use
-    bool codes_q_built = false;          // adc_variant 8's lane-ordered code stream is laid out on first use
-    int64_t q_blocks = 0;
-    int64_t t32_tiles = 0;               // tiles of 32 rolled texture points (ceil(n/32) per template): the matrix-core bound pass's stream
-    int max_nR = 0;
-    int64_t total_tex_points = 0;
-    int64_t total_minutiae = 0;          // rolled minutiae of the shard
-    // adc_variant 9: fp16 codebook + |cw|^2 (once), pair-aligned gallery codes / point terms / pair directory (first use), per group B fragments,
-    // row constants and the bound pass's records
-    DevBuf mf_cw16, mf_cwn, g_codes_p, g_nrm_p, g_tile_meta, mf_bfrag, mf_rowk, mf_rec, mf_stats;
-    bool mf_cb_built = false, mf_gal_built = false;
+    // adc_variant 9: fp16 codebook + |cw|^2 (once), per group B fragments, row constants and the bound pass's records (the gallery's own streams: Shard)
+    DevBuf mf_cw16, mf_cwn, mf_bfrag, mf_rowk, mf_rec, mf_stats;
+    bool mf_cb_built = false;
     int mf_collect_stats = 0;
     DevBuf lutq, lutq_min, lutq_rng, lutq_rowc, lut32;      // adc_variant 8: 16-row fixed-point tiles, per-(row, m) min / range, per-row (offset, step, margin), fp32 table
     DevBuf lut, rm_val, rm_arg, rm_cv, rm_n, parts, scores, scratch, cands, cand_n, minu_fb, topk_idx, topk_score;
@@ -201,26 +231,33 @@ std::vector<float> fragment_tiles(const std::vector<float>& des, const std::vect
 constexpr int64_t kMfRecBytesPerRow = 8;               // adc_variant 9: one 8-byte record per (rolled template, latent texture row)
 // afis_gallery.cpp
 int materialise(afis_ctx* ctx);                        // the staged gallery as host arrays: a container that afis_gallery_load only mapped is copied into ctx->hg now
-void free_gallery_dev(afis_ctx* c);
-int ensure_mf_gallery(afis_ctx* ctx, hipStream_t s);   // adc_variant 9's tile-aligned copy of the gallery codes (built at commit, or by the first search after the variant was selected)
+void free_gallery_dev(Shard* c);                       // every device buffer of a shard (the context's resident one, or a subset's)
+int quiesce(afis_ctx* ctx, const char* what);          // an edit replaces or releases device buffers that searches read: waits (bounded) for all device work of the context
+int ensure_mf_gallery(afis_ctx* ctx, Shard& sh, hipStream_t s);   // adc_variant 9's tile-aligned copy of the gallery codes (built at commit, or by the first search after the variant was selected)
 void views_of(const HostTemplate& t, std::vector<afis_minutiae_view>& mv, std::vector<afis_texture_view>& tv, afis_template_view& out);
 // afis_search.cpp
 // spec == NULL: the reference's selection for every query (templates 27, 3, 12 and texture template 0, matcher.cpp:380-415).
 // spec != NULL (afis_match_all_templates): query i uses latent minutiae templates spec[i*4 + 0..2] (-1 = none) and latent texture
 // template spec[i*4 + 3] (-1 = none), and is never "latent empty".
 int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup& grp, std::vector<int32_t>& status_out, const int* spec = nullptr);
-int adc_stage_q(afis_ctx* ctx, QueryGroup& grp, int chunk, bool exact, hipEvent_t after_lut = nullptr);
-int adc_refine_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, bool compact);
-int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t after_lut = nullptr, hipEvent_t after_bound = nullptr, bool compact = false, hipStream_t sb = nullptr,
+// (the ADC stages work on the shard `sh`: the context's own — *ctx — or a subset's)
+int adc_stage_q(afis_ctx* ctx, Shard& sh, QueryGroup& grp, int chunk, bool exact, hipEvent_t after_lut = nullptr);
+int adc_refine_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, bool compact);
+int adc_stage_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, hipEvent_t after_lut = nullptr, hipEvent_t after_bound = nullptr, bool compact = false, hipStream_t sb = nullptr,
                    bool refine_now = true, unsigned long long* diag = nullptr);
-// S4-S6 of the direct exact ADC kernels (adc_direct.hip, adc_variant 0-3, 6, 7) for one query group against the resident shard, on the context's stream, into
+// S4-S6 of the direct exact ADC kernels (adc_direct.hip, adc_variant 0-3, 6, 7) for one query group against a shard, on the context's stream, into
 // rm_val / rm_arg (sized by the caller); after_lut is recorded between the table and the row maxima.  Set by afis_taps.cpp, so only libafis_hip_test.so has it:
 // null in libafis_hip.so, which rejects those variants.  Hidden: with both libraries in one process, neither may bind to the other's copy.
-typedef int (*DirectAdcStage)(afis_ctx* ctx, const QueryDev& d, int chunk, hipEvent_t after_lut);
+typedef int (*DirectAdcStage)(afis_ctx* ctx, Shard& sh, const QueryDev& d, int chunk, hipEvent_t after_lut);
 extern DirectAdcStage g_direct_adc_stage __attribute__((visibility("hidden")));
 int64_t graph_slab_bytes(int64_t n_pairs);             // both slabs for a launch of n_pairs (latent, rolled) pairs (1.0 GB + 2 x 0.67 GB from 16 384 pairs on)
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what);
 void register_context(afis_ctx* ctx); void unregister_context(afis_ctx* ctx);   // the process-wide list group_budget_bytes consults
 int drain_abandoned(afis_ctx* ctx);                     // waits (bounded) for a search that returned at its deadline
+// The launch sequence of a search over one shard: the context's resident one (sub == NULL, sh == *ctx) or a subset's (sh == sub->sh).  afis_search_resident and
+// afis_search_subset_resident check their handles and call it.
+int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score);
+size_t subset_device_bytes(const afis_ctx* ctx);       // option subset_device_bytes: what the live subsets hold on the device
+void release_subset(afis_subset* s);                   // its device buffers and the handle itself (afis_subset.cpp)
 
 }  // namespace afis

@@ -241,6 +241,13 @@ hipError_t launch_fragment_tiles(const float* des, const int32_t* off, const int
 // afis_gallery_remove (gallery_edit.hip): one SoA array of the shard copied into a new buffer with every surviving template's range moved from old_off[t] to new_off[t]
 // (device offset tables [G + 1]); elem_bytes 384 (descriptors), 16 (PQ codes) or 4 ((x, y), orientations); n_new = new_off[G]
 hipError_t launch_compact_ranges(const void* src, void* dst, int elem_bytes, const int32_t* old_off, const int32_t* new_off, int G, long long n_new, hipStream_t stream);
+// afis_subset_create (gallery_subset.hip): one SoA array of the resident shard gathered by a template list — template t of the output takes the src_off[sel[t]] .. range of
+// src and lands at dst_off[t] (device tables: src_off [G + 1], sel [n], dst_off [n + 1]; ranges in any order, possibly empty); elem_bytes 384, 16 or 4; n_out = dst_off[n]
+hipError_t launch_gather_ranges(const void* src, void* dst, int elem_bytes, const int32_t* src_off, const int32_t* sel, const int32_t* dst_off, int n, long long n_out, hipStream_t stream);
+// a subset search's epilogues: positions of the rank lists -> global indices (idx[i] = map[idx[i]] where 0 <= idx[i] < n_map; the -1 padding stays), and the score (4-byte)
+// or part (16-byte) columns into the caller's order: dst[q][j] = src[q][pos[j]], j < n
+hipError_t launch_subset_topk_map(long long* idx, long long n_idx, const long long* map, int n_map, hipStream_t stream);
+hipError_t launch_permute_columns(const void* src, void* dst, int elem_bytes, int n_q, int n, const int32_t* pos, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

@@ -66,7 +66,7 @@ void views_of(const HostTemplate& t, std::vector<afis_minutiae_view>& mv, std::v
     out.n_minu = (int)mv.size(); out.minu = mv.data(); out.n_tex = (int)tv.size(); out.tex = tv.data();
 }
 
-void free_gallery_dev(afis_ctx* c)
+void free_gallery_dev(Shard* c)
 {
     c->g_minu_off.release(); c->g_minu_xy.release(); c->g_minu_ori.release(); c->g_minu_des.release(); c->g_minu_frag.release(); c->g_minu_tile_off.release();
     c->g_tex_off.release(); c->g_tex_xy.release(); c->g_tex_ori.release(); c->g_tex_codes.release(); c->g_tex_codes_cf.release(); c->g_tex_cf_blk.release(); c->g_tex_codes_q.release(); c->g_tex_q_blk.release(); c->g_tex_t32_blk.release(); c->g_empty.release(); c->g_task_ctr.release();
@@ -512,7 +512,7 @@ static int commit_shard(afis_ctx* ctx, int64_t index_base)
     ctx->committed = true;
     ++ctx->gallery_epoch;                                                   // (no handle can exist before a first commit; one may after a removal that failed and dropped the shard)
     if (ctx->adc_variant == 9 && G > 0) {                                    // the default path's derived streams belong to the resident gallery: built here, not by the first search
-        int rcg = ensure_mf_gallery(ctx, ctx->stream);
+        int rcg = ensure_mf_gallery(ctx, *ctx, ctx->stream);
         if (rcg != AFIS_OK) return rcg;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         lap("bound pass's code stream");
@@ -561,12 +561,17 @@ static void release_staging(afis_ctx* ctx)
 
 // ---- the live gallery: afis_gallery_reopen, the appending commit, afis_gallery_remove, afis_gallery_export ---------------------------------
 // An edit replaces device buffers that searches read: nothing of the context may be running.  The search that timed out (if any) first, then all three streams.
-static int quiesce(afis_ctx* ctx, const char* what)
+// (afis_subset_create / afis_subset_free wait the same way: afis_subset.cpp)
+}  // extern "C"
+namespace afis {
+int quiesce(afis_ctx* ctx, const char* what)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
     return wait_streams(ctx, {ctx->stream_lo, ctx->stream_hi, ctx->stream}, what);
 }
+}  // namespace afis
+extern "C" {
 
 // the SoA pointers of ctx->gal from the buffers that hold them now (a buffer that grew or was compacted has moved)
 static void refresh_gallery_view(afis_ctx* ctx)

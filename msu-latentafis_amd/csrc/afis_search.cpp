@@ -37,6 +37,14 @@ static size_t held_group_bytes(const afis_ctx* c)
 {
     return c->rm_val.bytes + c->rm_arg.bytes + c->rm_cv.bytes + c->rm_n.bytes + c->mf_rec.bytes + c->cands.bytes + c->cand_n.bytes + c->parts.bytes + c->minu_fb.bytes + c->tex_slab.bytes + c->minu_slab.bytes;
 }
+// What the live subsets of a context hold (option subset_device_bytes).  They are plain allocations that no launch group reuses, so they are NOT added back to the free
+// figure below as the held group buffers are: hipMemGetInfo has taken them off already, and a launch group cut after a subset was made is cut to what the subset leaves.
+size_t subset_device_bytes(const afis_ctx* c)
+{
+    size_t n = 0;
+    for (const afis_subset* s : c->subsets) n += s->device_bytes();
+    return n;
+}
 void register_context(afis_ctx* c) { std::lock_guard<std::mutex> lk(g_ctx_mutex); g_ctx_live.push_back(c); }
 void unregister_context(afis_ctx* c) { std::lock_guard<std::mutex> lk(g_ctx_mutex); g_ctx_live.erase(std::remove(g_ctx_live.begin(), g_ctx_live.end(), c), g_ctx_live.end()); }
 
@@ -280,15 +288,15 @@ static int tile_share_of(const afis_ctx* ctx) { return ctx->tile_share > 0 ? ctx
 
 // S4 + S5 + S6 of adc_variant 8 for one query group (rm_val / rm_arg sized by the caller): the quantised pass bounds the candidates, the fp32
 // table (reference layout, all rows of the group) settles them
-int adc_stage_q(afis_ctx* ctx, QueryGroup& grp, int chunk, bool exact, hipEvent_t after_lut)
+int adc_stage_q(afis_ctx* ctx, Shard& sh, QueryGroup& grp, int chunk, bool exact, hipEvent_t after_lut)
 {
     const QueryDev& d = grp.dev;
     hipStream_t s = ctx->stream;
-    if (d.n_tiles16 <= 0 || ctx->gal.G <= 0) { if (after_lut) HIPCHK(ctx, hipEventRecord(after_lut, s)); return AFIS_OK; }
-    if (!ctx->codes_q_built) {
-        HIPCHK(ctx, ctx->g_tex_codes_q.ensure(std::max<size_t>((size_t)ctx->q_blocks * 64 * 16, 16)));
-        HIPCHK(ctx, launch_codes_q(ctx->gal, ctx->g_tex_q_blk.as<int32_t>(), ctx->g_tex_codes_q.p, s));
-        ctx->codes_q_built = true;
+    if (d.n_tiles16 <= 0 || sh.gal.G <= 0) { if (after_lut) HIPCHK(ctx, hipEventRecord(after_lut, s)); return AFIS_OK; }
+    if (!sh.codes_q_built) {
+        HIPCHK(ctx, sh.g_tex_codes_q.ensure(std::max<size_t>((size_t)sh.q_blocks * 64 * 16, 16)));
+        HIPCHK(ctx, launch_codes_q(sh.gal, sh.g_tex_q_blk.as<int32_t>(), sh.g_tex_codes_q.p, s));
+        sh.codes_q_built = true;
     }
     HIPCHK(ctx, ctx->lutq.ensure((size_t)d.n_tiles16 * 131072));
     HIPCHK(ctx, ctx->lutq_min.ensure(std::max<size_t>((size_t)grp.n_lt_rows * kM * 4, 16)));
@@ -300,29 +308,29 @@ int adc_stage_q(afis_ctx* ctx, QueryGroup& grp, int chunk, bool exact, hipEvent_
         HIPCHK(ctx, launch_lut_reference_layout(d.lt_des, grp.n_lt_rows, ctx->codewords.as<float>(), ctx->lut32.as<float>(), s));
     }
     if (after_lut) HIPCHK(ctx, hipEventRecord(after_lut, s));
-    HIPCHK(ctx, launch_adc_rowmax_q(d, ctx->gal, ctx->g_tex_codes_q.p, ctx->g_tex_q_blk.as<int32_t>(), ctx->lutq.p, ctx->lutq_rowc.p,
+    HIPCHK(ctx, launch_adc_rowmax_q(d, sh.gal, sh.g_tex_codes_q.p, sh.g_tex_q_blk.as<int32_t>(), ctx->lutq.p, ctx->lutq_rowc.p,
                                     exact ? ctx->lut32.as<float>() : nullptr, chunk, tile_share_of(ctx), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), s));
     return AFIS_OK;
 }
 
 // adc_variant 9's derived data: the codebook in fp16 with its squared norms (once per context) and the gallery's PQ codes as tiles of 32 points with their point terms
-// (once per committed gallery).  Built by afis_gallery_commit when variant 9 is selected then — a resident gallery includes them — and on first use otherwise.
-int ensure_mf_gallery(afis_ctx* ctx, hipStream_t s)
+// (once per committed gallery, and once per subset: afis_subset_create).  Built by afis_gallery_commit when variant 9 is selected then — a resident gallery includes them — and on first use otherwise.
+int ensure_mf_gallery(afis_ctx* ctx, Shard& sh, hipStream_t s)
 {
-    const GalleryDev& g = ctx->gal;
+    const GalleryDev& g = sh.gal;
     if (!ctx->mf_cb_built) {
         HIPCHK(ctx, ctx->mf_cw16.ensure((size_t)kM * kK * 16));
         HIPCHK(ctx, ctx->mf_cwn.ensure((size_t)kM * kK * 4));
         HIPCHK(ctx, launch_mf_codebook(ctx->codewords.as<float>(), ctx->mf_cw16.p, ctx->mf_cwn.as<float>(), s));
         ctx->mf_cb_built = true;
     }
-    if (!ctx->mf_gal_built && g.G > 0) {
-        const size_t n_ent = std::max<size_t>((size_t)ctx->t32_tiles * 32, 1);
-        HIPCHK(ctx, ctx->g_codes_p.ensure(n_ent * 16));
-        HIPCHK(ctx, ctx->g_nrm_p.ensure(n_ent * 4));
-        HIPCHK(ctx, ctx->g_tile_meta.ensure(std::max<size_t>((size_t)ctx->t32_tiles * 8, 16)));
-        HIPCHK(ctx, launch_mf_tiles(g, ctx->g_tex_t32_blk.as<int32_t>(), ctx->mf_cwn.as<float>(), ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, s));
-        ctx->mf_gal_built = true;
+    if (!sh.mf_gal_built && g.G > 0) {
+        const size_t n_ent = std::max<size_t>((size_t)sh.t32_tiles * 32, 1);
+        HIPCHK(ctx, sh.g_codes_p.ensure(n_ent * 16));
+        HIPCHK(ctx, sh.g_nrm_p.ensure(n_ent * 4));
+        HIPCHK(ctx, sh.g_tile_meta.ensure(std::max<size_t>((size_t)sh.t32_tiles * 8, 16)));
+        HIPCHK(ctx, launch_mf_tiles(g, sh.g_tex_t32_blk.as<int32_t>(), ctx->mf_cwn.as<float>(), sh.g_codes_p.p, sh.g_nrm_p.as<float>(), sh.g_tile_meta.p, s));
+        sh.mf_gal_built = true;
     }
     return AFIS_OK;
 }
@@ -330,13 +338,13 @@ int ensure_mf_gallery(afis_ctx* ctx, hipStream_t s)
 // S4-S6 (+ the row selection of S7) of adc_variant 9 for one query group: row constants, matrix-core bound pass, selection by bounds and exact
 // recomputation.  all_rows: every row is evaluated exactly (parity taps); otherwise rows that cannot reach the pair's top 200 get -inf.
 // sb: the stream of the row constants and the bound pass (the context's stream, or the CU-masked one); refine_now false: the caller launches the selection / recomputation kernel itself (adc_refine_mfma)
-int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t after_lut, hipEvent_t after_bound, bool compact, hipStream_t sb, bool refine_now, unsigned long long* diag)
+int adc_stage_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, hipEvent_t after_lut, hipEvent_t after_bound, bool compact, hipStream_t sb, bool refine_now, unsigned long long* diag)
 {
     const QueryDev& d = grp.dev;
     hipStream_t s = sb ? sb : ctx->stream;
-    const GalleryDev& g = ctx->gal;
+    const GalleryDev& g = sh.gal;
     if (grp.n_lt_rows <= 0 || g.G <= 0) { if (after_lut) HIPCHK(ctx, hipEventRecord(after_lut, s)); if (after_bound) HIPCHK(ctx, hipEventRecord(after_bound, s)); return AFIS_OK; }
-    { int rcg = ensure_mf_gallery(ctx, s); if (rcg != AFIS_OK) return rcg; }
+    { int rcg = ensure_mf_gallery(ctx, sh, s); if (rcg != AFIS_OK) return rcg; }
     const int n_rows = grp.n_lt_rows, n_rb = (n_rows + 31) / 32, R_pad = n_rb * 32;
     // The per-row buffers have been brought to the size of the search's LARGEST group by afis_search_resident before it queued anything: these calls find them large enough
     // (a hipMalloc behind queued work was seen to take 0.5-0.8 s; see there).  Callers outside a search (the parity taps) allocate here.
@@ -353,17 +361,17 @@ int adc_stage_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, hipEvent_t aft
     const int n_rg = (n_rb + wg_rb - 1) / wg_rb;
     const long long want_chunks = (std::max<long long>(1, (256 * 24) / n_rg) + 7) / 8 * 8;   // a multiple of 8: the kernel gives every XCD its own chunks (adc_mfma.hip), an uneven count would leave XCDs idle at the end
     const int chunk = ctx->chunk > 0 ? ctx->chunk : (int)std::max<long long>(8, ((long long)g.G + want_chunks - 1) / want_chunks);
-    HIPCHK(ctx, launch_adc_mfma(g, ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, ctx->g_tex_t32_blk.as<int32_t>(), ctx->mf_cw16.p,
+    HIPCHK(ctx, launch_adc_mfma(g, sh.g_codes_p.p, sh.g_nrm_p.as<float>(), sh.g_tile_meta.p, sh.g_tex_t32_blk.as<int32_t>(), ctx->mf_cw16.p,
                                 ctx->mf_bfrag.p, ctx->mf_rowk.p, n_rows, n_rb, R_pad, chunk, ctx->mf_rec.p, diag, s));
     if (after_bound) HIPCHK(ctx, hipEventRecord(after_bound, s));
-    return refine_now ? adc_refine_mfma(ctx, grp, all_rows, compact) : AFIS_OK;
+    return refine_now ? adc_refine_mfma(ctx, sh, grp, all_rows, compact) : AFIS_OK;
 }
 
-int adc_refine_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, bool compact)
+int adc_refine_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, bool compact)
 {
-    if (grp.n_lt_rows <= 0 || ctx->gal.G <= 0) return AFIS_OK;
+    if (grp.n_lt_rows <= 0 || sh.gal.G <= 0) return AFIS_OK;
     const int R_pad = (grp.n_lt_rows + 31) / 32 * 32;
-    HIPCHK(ctx, launch_tex_refine(grp.dev, ctx->gal, ctx->codewords.as<float>(), ctx->mf_rec.p, ctx->mf_rowk.p, R_pad, all_rows ? 1 : 0, ctx->rm_val.as<float>(),
+    HIPCHK(ctx, launch_tex_refine(grp.dev, sh.gal, ctx->codewords.as<float>(), ctx->mf_rec.p, ctx->mf_rowk.p, R_pad, all_rows ? 1 : 0, ctx->rm_val.as<float>(),
                                   ctx->rm_arg.as<int32_t>(), ctx->mf_collect_stats ? ctx->mf_stats.as<unsigned long long>() : nullptr,
                                   compact ? ctx->rm_cv.as<float>() : nullptr, compact ? ctx->rm_n.as<int32_t>() : nullptr, ctx->stream));
     return AFIS_OK;
@@ -373,9 +381,9 @@ int adc_refine_mfma(afis_ctx* ctx, QueryGroup& grp, bool all_rows, bool compact)
 static const int kDeviceTopK = 64;
 
 // (1 of 3) Every buffer of the launch groups, brought to its size while the device is idle and before anything of the search is queued.
-static int prepare_search_buffers(afis_ctx* ctx, const afis_queries* q, bool want_parts)
+static int prepare_search_buffers(afis_ctx* ctx, Shard& sh, const afis_queries* q, bool want_parts)
 {
-    const int64_t G = ctx->gal.G;
+    const int64_t G = sh.gal.G;
     const int nq_all = q->n_q;
     float* const parts = want_parts ? reinterpret_cast<float*>(1) : nullptr;     // (only its being asked for matters here)
     // Every buffer of the launch groups is brought to its size HERE, while the device is idle and before anything of this search is queued: for the largest group of
@@ -401,7 +409,7 @@ static int prepare_search_buffers(afis_ctx* ctx, const afis_queries* q, bool wan
             HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs)));
             HIPCHK(ctx, ctx->minu_slab.ensure(2 * graph_minutiae_slab_bytes(3 * (long long)n_pairs)));     // two instances at once in the overlapped schedule
             {   // the generic candidate kernel's scratch (sized as in the loop below, for the longest latent minutiae template of the search)
-                const size_t per_wg = minu_scratch_floats(nL_max, ctx->max_nR, ctx->s3_tie_order);
+                const size_t per_wg = minu_scratch_floats(nL_max, sh.max_nR, ctx->s3_tie_order);
                 int n_wg = 1024;
                 while (n_wg > 64 && per_wg * 4 * n_wg > (8ull << 30)) n_wg /= 2;
                 HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * n_wg));
@@ -412,11 +420,11 @@ static int prepare_search_buffers(afis_ctx* ctx, const afis_queries* q, bool wan
                 HIPCHK(ctx, ctx->mf_bfrag.ensure(R_cap / 32 * 6 * 64 * 16));
                 HIPCHK(ctx, ctx->mf_rowk.ensure(R_cap * 16));
                 HIPCHK(ctx, ctx->mf_rec.ensure((size_t)G * R_cap * kMfRecBytesPerRow));
-                if (!ctx->mf_gal_built) {                                  // first search: the bound pass's copy of the gallery codes (adc_stage_mfma fills it)
-                    const size_t n_ent = std::max<size_t>((size_t)ctx->t32_tiles * 32, 1);
-                    HIPCHK(ctx, ctx->g_codes_p.ensure(n_ent * 16));
-                    HIPCHK(ctx, ctx->g_nrm_p.ensure(n_ent * 4));
-                    HIPCHK(ctx, ctx->g_tile_meta.ensure(std::max<size_t>((size_t)ctx->t32_tiles * 8, 16)));
+                if (!sh.mf_gal_built) {                                    // first search: the bound pass's copy of the gallery codes (adc_stage_mfma fills it)
+                    const size_t n_ent = std::max<size_t>((size_t)sh.t32_tiles * 32, 1);
+                    HIPCHK(ctx, sh.g_codes_p.ensure(n_ent * 16));
+                    HIPCHK(ctx, sh.g_nrm_p.ensure(n_ent * 4));
+                    HIPCHK(ctx, sh.g_tile_meta.ensure(std::max<size_t>((size_t)sh.t32_tiles * 8, 16)));
                 }
             }
         }
@@ -425,9 +433,9 @@ static int prepare_search_buffers(afis_ctx* ctx, const afis_queries* q, bool wan
 }
 
 // (3 of 3) What the search's events and diagnostics rows say: where the candidate tasks went, the clocks the sampled workgroups saw, the stage times per launch group.
-static int collect_timing(afis_ctx* ctx, const afis_queries* q, afis_timing& tm, bool dev_topk, hipEvent_t* evk)
+static int collect_timing(afis_ctx* ctx, const Shard& sh, const afis_queries* q, afis_timing& tm, bool dev_topk, hipEvent_t* evk)
 {
-    const int64_t G = ctx->gal.G;
+    const int64_t G = sh.gal.G;
     const size_t n_groups = q->groups.size();
     {   // where the candidate tasks went, and the clocks the sampled workgroups saw (shader cycles per tick of the constant 100 MHz counter)
         unsigned long long acc[kDiagWords] = {};
@@ -462,23 +470,14 @@ static int collect_timing(afis_ctx* ctx, const afis_queries* q, afis_timing& tm,
     return AFIS_OK;
 }
 
-}  // namespace afis
-
-extern "C" {
-
-int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* parts, int32_t* status,
-                         int k, int64_t* topk_idx, float* topk_score)
+// The launch sequence of a search over the shard `sh`: the context's resident one (sub == NULL) or a subset's (sh == sub->sh, whose templates stand in ascending global
+// index order).  One body for both: group loop, overlapped schedule, buffer sizing before queuing, timing, deadlines.  What a subset adds lies at the two ends — the
+// rank-list kernel's positions are mapped to global indices, and the score / part columns go to the caller's order (on the device, so that they are copied once).
+int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score)
 {
-    if (!ctx || !q) return fail(ctx, AFIS_EINVAL, "afis_search_resident: null argument");
-    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_search: commit the gallery first");
-    if (k < 0 || (k > 0 && (!topk_idx || !topk_score))) return fail(ctx, AFIS_EINVAL, "afis_search: k > 0 needs topk_idx and topk_score");
-    // A handle's launch groups were cut for the shard size (and the free memory) of the moment it was uploaded: against a shard that has grown since, a group's per-pair
-    // buffers could exceed the budget.  Such a handle is refused; uploading the latents again takes milliseconds.
-    if (q->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_search_resident: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these queries were uploaded; free the handle and upload them again");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
-    const GalleryDev& g = ctx->gal;
+    const GalleryDev& g = sh.gal;
     const int64_t G = g.G;
     const int nq_all = q->n_q;
     afis_timing tm = {};
@@ -491,7 +490,15 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     if (G > 0 && nq_all > 0) HIPCHK(ctx, ctx->scores.ensure((size_t)nq_all * G * 4));
     HIPCHK(ctx, ctx->diag.ensure(std::max<size_t>(n_groups, 1) * kDiagWords * 8));
     HIPCHK(ctx, hipMemsetAsync(ctx->diag.p, 0, std::max<size_t>(n_groups, 1) * kDiagWords * 8, s));    // before the first group's ev[0]: ordered before everything the side streams do
-    { const int rcp = prepare_search_buffers(ctx, q, parts != nullptr); if (rcp != AFIS_OK) return rcp; }
+    { const int rcp = prepare_search_buffers(ctx, sh, q, parts != nullptr); if (rcp != AFIS_OK) return rcp; }
+    const bool dev_topk = k > 0 && k <= kDeviceTopK && G > 0 && nq_all > 0;
+    const bool host_topk = k > 0 && !dev_topk;
+    // a subset listed out of order: scores (asked for, or needed by the host's rank lists) and parts leave through out_perm in the caller's column order
+    const bool perm = sub && !sub->identity && G > 0 && nq_all > 0;
+    const bool perm_scores = perm && (scores || host_topk), perm_parts = perm && parts;
+    const size_t perm_parts_at = perm_scores ? ((size_t)nq_all * G * 4 + 255) / 256 * 256 : 0;
+    if (perm_scores || perm_parts) HIPCHK(ctx, ctx->out_perm.ensure(perm_parts_at + (perm_parts ? (size_t)nq_all * G * 16 : 0)));
+    if (dev_topk) { HIPCHK(ctx, ctx->topk_idx.ensure((size_t)nq_all * k * 8)); HIPCHK(ctx, ctx->topk_score.ensure((size_t)nq_all * k * 4)); }
     static const bool alloc_trace = getenv("AFIS_ALLOC_TRACE") != nullptr;   // (the trace of DevBuf::ensure, afis_ctx.h: from this line on a search must not allocate — tests/test_gpu_parity.py)
     if (alloc_trace) { fprintf(stderr, "queue: the search starts queuing\n"); fflush(stderr); }
     int q0 = 0;
@@ -511,7 +518,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             if (ctx->adc_variant == 9) { HIPCHK(ctx, ctx->rm_cv.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16))); HIPCHK(ctx, ctx->rm_n.ensure(std::max<size_t>(n_pairs * 4, 16))); }
             HIPCHK(ctx, ctx->parts.ensure(parts ? (size_t)nq_all * G * 16 : n_pairs * 16));
             // minutiae scratch per workgroup: simi[n] | keys[n] | rowsum[2048] | colsum[2048]  (only pairs the fast kernel cannot take use it)
-            size_t per_wg = minu_scratch_floats(grp.max_nL, ctx->max_nR, ctx->s3_tie_order);
+            size_t per_wg = minu_scratch_floats(grp.max_nL, sh.max_nR, ctx->s3_tie_order);
             int n_wg = 1024;
             while (n_wg > 64 && per_wg * 4 * n_wg > (8ull << 30)) n_wg /= 2;
             HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * n_wg));
@@ -536,7 +543,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             // the candidate kernels would stay confined to half of the chip long after the pass has ended (measured: 4 215 ms per step overlapped against 3 864 back to back).
             // The stage's work is priced by its similarity cells (latent x rolled minutiae) against the pass's (latent rows x rolled points): at the headline shapes the candidate
             // kernel alone takes 0.49 of the bound pass alone for 0.0179 of its cells; on half the CUs it takes twice that, so it still ends with the pass at about twice the headline's ratio.
-            const double cells_m = (double)grp.n_lm_points * (double)ctx->total_minutiae, cells_t = (double)grp.n_lt_rows * (double)ctx->total_tex_points;
+            const double cells_m = (double)grp.n_lm_points * (double)sh.total_minutiae, cells_t = (double)grp.n_lt_rows * (double)sh.total_tex_points;
             const bool minutiae_light = cells_m <= ctx->overlap_cell_ratio * cells_t;
             const bool overlap = ctx->adc_variant == 9 && ctx->stream_lo != nullptr && !ctx->overlap_failed && n_pairs >= 65536 && minutiae_light;
             grp.overlapped = overlap;
@@ -544,7 +551,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs))); HIPCHK(ctx, ctx->minu_slab.ensure(2 * minu_slab_1));   // (already large enough, as the buffers above)
             const bool compact9 = ctx->adc_variant == 9;                  // the recomputation kernel's compact list of the rows that matter (S7 reads a third of the rows)
             auto minutiae_stage = [&]() -> int {
-                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, diag_row, s));
+                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, sh.max_nR, diag_row, s));
                 HIPCHK(ctx, hipEventRecord(ev[7], s));
                 HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
                 return AFIS_OK;
@@ -555,20 +562,20 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 // confined to the OTHER CUs (an unconfined stream's persistent workgroups would take every CU and the bound pass, whose workgroup needs a whole CU's LDS,
                 // would wait for them to leave).  When the bound pass is done the context's stream joins the list kernel (a second instance drawing from the same counter),
                 // then runs recomputation and texture lists on the whole chip.
-                hipStream_t sl = ctx->stream_lo, sh = ctx->stream_hi;
-                side_guard.arm(sl, sh);
+                hipStream_t sl = ctx->stream_lo, s_hi = ctx->stream_hi;
+                side_guard.arm(sl, s_hi);
                 HIPCHK(ctx, hipStreamWaitEvent(sl, ev[0], 0));                             // everything of the previous group (this stream's order) is done
-                HIPCHK(ctx, hipStreamWaitEvent(sh, ev[0], 0));
-                int rc9 = adc_stage_mfma(ctx, grp, false, ev[1], ev[6], true, sl, false, diag_row);
+                HIPCHK(ctx, hipStreamWaitEvent(s_hi, ev[0], 0));
+                int rc9 = adc_stage_mfma(ctx, sh, grp, false, ev[1], ev[6], true, sl, false, diag_row);
                 if (rc9 != AFIS_OK) return rc9;
-                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, diag_row, sh));
-                HIPCHK(ctx, hipMemsetAsync(g.task_ctr + 1, 0, 4, sh));                     // the list counter both instances of the list kernel draw from: reset BEFORE either may start
-                HIPCHK(ctx, hipEventRecord(ev[7], sh));
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), sh, true));
-                HIPCHK(ctx, hipEventRecord(ev[4], sh));
+                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, sh.max_nR, diag_row, s_hi));
+                HIPCHK(ctx, hipMemsetAsync(g.task_ctr + 1, 0, 4, s_hi));                     // the list counter both instances of the list kernel draw from: reset BEFORE either may start
+                HIPCHK(ctx, hipEventRecord(ev[7], s_hi));
+                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s_hi, true));
+                HIPCHK(ctx, hipEventRecord(ev[4], s_hi));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[6], 0));
                 HIPCHK(ctx, hipEventRecord(ev[8], s));                                     // the bound pass is done
-                rc9 = adc_refine_mfma(ctx, grp, false, true);
+                rc9 = adc_refine_mfma(ctx, sh, grp, false, true);
                 if (rc9 != AFIS_OK) return rc9;
                 HIPCHK(ctx, hipEventRecord(ev[2], s));
                 HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, ctx->tex_slab.p, ctx->tex_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
@@ -583,13 +590,13 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 any_overlap = true;
             } else {
             if (ctx->adc_variant == 9) {                                    // fp16 matrix-core bound pass + exact recomputation
-                int rc9 = adc_stage_mfma(ctx, grp, false, ev[1], ev[6], true, nullptr, true, diag_row);
+                int rc9 = adc_stage_mfma(ctx, sh, grp, false, ev[1], ev[6], true, nullptr, true, diag_row);
                 if (rc9 != AFIS_OK) return rc9;
             } else if (ctx->adc_variant == 8) {                             // 16-bit fixed-point LDS-table bound pass + exact refine
-                int rc16 = adc_stage_q(ctx, grp, chunk, true, ev[1]);
+                int rc16 = adc_stage_q(ctx, sh, grp, chunk, true, ev[1]);
                 if (rc16 != AFIS_OK) return rc16;
             } else {                                                        // the direct exact kernels (afis_set_option admits them only where the hook is set)
-                int rcd = g_direct_adc_stage(ctx, d, chunk, ev[1]);
+                int rcd = g_direct_adc_stage(ctx, sh, d, chunk, ev[1]);
                 if (rcd != AFIS_OK) return rcd;
             }
             HIPCHK(ctx, hipEventRecord(ev[2], s));
@@ -606,21 +613,31 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
                 tm.adc_launches += 1;
                 const int tile_rows = ctx->adc_variant == 8 ? 16 : kTileRows;   // rows the launched kernel pads a latent to (variant 9 does no table look-ups: the count is nominal there)
                 int64_t rows = 0; for (int n : grp.h_lt_n) rows += (n + tile_rows - 1) / tile_rows * tile_rows;
-                tm.adc_lookups += rows * ctx->total_tex_points * kM;
+                tm.adc_lookups += rows * sh.total_tex_points * kM;
             }
             tm.pairs += (int64_t)n_pairs;
         }
         q0 += nq; ++gi;
     }
     // ---- rank lists (matcher.cpp:306-309; ties by ascending index) ----
-    const bool dev_topk = k > 0 && k <= kDeviceTopK && G > 0 && nq_all > 0;
     hipEvent_t* evk = &ctx->evpool[n_groups * 10];
-    if (dev_topk) {
-        HIPCHK(ctx, ctx->topk_idx.ensure((size_t)nq_all * k * 8));
-        HIPCHK(ctx, ctx->topk_score.ensure((size_t)nq_all * k * 4));
+    if (dev_topk) {                                                        // (topk_idx / topk_score were sized before the search queued)
         HIPCHK(ctx, hipEventRecord(evk[0], s));
-        HIPCHK(ctx, launch_topk(ctx->scores.as<float>(), nq_all, (int)G, k, (long long)ctx->index_base, ctx->topk_idx.as<long long>(), ctx->topk_score.as<float>(), s));
+        // a subset's positions are not index_base + position: the kernel ranks positions (base 0: ascending position IS ascending global index there), the epilogue maps them
+        HIPCHK(ctx, launch_topk(ctx->scores.as<float>(), nq_all, (int)G, k, sub ? 0ll : (long long)sh.index_base, ctx->topk_idx.as<long long>(), ctx->topk_score.as<float>(), s));
+        if (sub) HIPCHK(ctx, launch_subset_topk_map(ctx->topk_idx.as<long long>(), (long long)nq_all * k, sub->d_global.as<long long>(), (int)G, s));
         HIPCHK(ctx, hipEventRecord(evk[1], s));
+    }
+    // the caller's column order (a subset listed out of order): one pass over the outputs on the device, so that they cross PCIe once
+    const float* out_scores = ctx->scores.as<float>();
+    const float* out_parts = ctx->parts.as<float>();
+    if (perm_scores) {
+        HIPCHK(ctx, launch_permute_columns(ctx->scores.p, ctx->out_perm.p, 4, nq_all, (int)G, sub->d_pos.as<int32_t>(), s));
+        out_scores = ctx->out_perm.as<float>();
+    }
+    if (perm_parts) {
+        HIPCHK(ctx, launch_permute_columns(ctx->parts.p, ctx->out_perm.as<unsigned char>() + perm_parts_at, 16, nq_all, (int)G, sub->d_pos.as<int32_t>(), s));
+        out_parts = reinterpret_cast<const float*>(ctx->out_perm.as<unsigned char>() + perm_parts_at);
     }
     // What comes back inside the wait goes through a PINNED buffer of the context (rank lists, diagnostics: a few KB): an "asynchronous" copy into pageable host memory — the caller's
     // arrays, a std::vector — makes the runtime wait for the stream inside the call, which is where a search used to spend its two seconds before the deadline below was ever looked at
@@ -646,24 +663,25 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     if (dev_topk) { memcpy(topk_idx, pin, (size_t)nq_all * k * 8); memcpy(topk_score, pin + (size_t)nq_all * k * 8, (size_t)nq_all * k * 4); }
     ctx->h_diag.assign(std::max<size_t>(n_groups, 1) * kDiagWords, 0ull);
     memcpy(ctx->h_diag.data(), pin + pin_topk, pin_diag);
-    if (parts && G > 0 && nq_all > 0) HIPCHK(ctx, hipMemcpy(parts, ctx->parts.p, (size_t)nq_all * G * 16, hipMemcpyDeviceToHost));   // per-part scores on request (tests, the all-templates mode)
-    const bool host_topk = k > 0 && !dev_topk;
+    if (parts && G > 0 && nq_all > 0) HIPCHK(ctx, hipMemcpy(parts, out_parts, (size_t)nq_all * G * 16, hipMemcpyDeviceToHost));   // per-part scores on request (tests, the all-templates mode)
     float* h_sc = scores;
     if (G > 0 && nq_all > 0 && (scores || host_topk)) {                    // the device is idle now: a plain copy
         if (!h_sc) { ctx->h_scores.resize((size_t)nq_all * G); h_sc = ctx->h_scores.data(); }
-        HIPCHK(ctx, hipMemcpy(h_sc, ctx->scores.p, (size_t)nq_all * G * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(h_sc, out_scores, (size_t)nq_all * G * 4, hipMemcpyDeviceToHost));
     }
-    { const int rct = collect_timing(ctx, q, tm, dev_topk, evk); if (rct != AFIS_OK) return rct; }
+    { const int rct = collect_timing(ctx, sh, q, tm, dev_topk, evk); if (rct != AFIS_OK) return rct; }
     if (host_topk) {                                                       // k > kDeviceTopK (or an empty gallery)
         std::vector<int32_t> ind((size_t)G);
+        const int64_t* col = sub ? sub->idx.data() : nullptr;               // a subset's columns stand in the caller's order: equal scores by the column's GLOBAL index
         for (int i = 0; i < nq_all; ++i) {
             const float* sc = G > 0 ? h_sc + (size_t)i * G : nullptr;
             std::iota(ind.begin(), ind.end(), 0);
             const int kk = (int)std::min<int64_t>(k, G);
-            std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [sc](int a, int b) { return sc[a] > sc[b] || (sc[a] == sc[b] && a < b); });
+            if (col) std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [sc, col](int a, int b) { return sc[a] > sc[b] || (sc[a] == sc[b] && col[a] < col[b]); });
+            else std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [sc](int a, int b) { return sc[a] > sc[b] || (sc[a] == sc[b] && a < b); });
             for (int r = 0; r < k; ++r) {
                 const size_t o = (size_t)i * k + r;
-                if (r < kk) { topk_idx[o] = ctx->index_base + ind[r]; topk_score[o] = sc[ind[r]]; }
+                if (r < kk) { topk_idx[o] = col ? col[ind[r]] : sh.index_base + ind[r]; topk_score[o] = sc[ind[r]]; }
                 else { topk_idx[o] = -1; topk_score[o] = -INFINITY; }
             }
         }
@@ -672,6 +690,23 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     for (const QueryGroup& grp : q->groups) tm.overlapped_groups += grp.overlapped ? 1 : 0;
     ctx->timing = tm;
     return AFIS_OK;
+}
+
+}  // namespace afis
+
+extern "C" {
+
+int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* parts, int32_t* status,
+                         int k, int64_t* topk_idx, float* topk_score)
+{
+    if (!ctx || !q) return fail(ctx, AFIS_EINVAL, "afis_search_resident: null argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_search: commit the gallery first");
+    if (k < 0 || (k > 0 && (!topk_idx || !topk_score))) return fail(ctx, AFIS_EINVAL, "afis_search: k > 0 needs topk_idx and topk_score");
+    // A handle's launch groups were cut for the shard size (and the free memory) of the moment it was uploaded: against a shard that has grown since, a group's per-pair
+    // buffers could exceed the budget.  Such a handle is refused; uploading the latents again takes milliseconds.
+    if (q->gallery_epoch != ctx->gallery_epoch)
+        return fail(ctx, AFIS_ESTATE, "afis_search_resident: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these queries were uploaded; free the handle and upload them again");
+    return search_shard(ctx, *ctx, nullptr, q, scores, parts, status, k, topk_idx, topk_score);
 }
 
 // Correspondence export (matcher.cpp:321-327 calling :376-417 with save_corr = true, :497-505): the minutiae scorers of the

@@ -7,24 +7,24 @@ using namespace afis;
 
 // The conflict-free kernel's lane-ordered code stream (variants 6 / 7) — a full copy of the PQ codes that nothing else reads — and its block offsets
 // ((blocks + 1) x 64 entries per template), laid out at the first use of those variants.
-static int ensure_codes_cf(afis_ctx* ctx, int variant)
+static int ensure_codes_cf(afis_ctx* ctx, Shard& sh, int variant)
 {
-    if ((variant != 6 && variant != 7) || ctx->codes_cf_built) return AFIS_OK;
-    const int64_t G = ctx->gal.G;
+    if ((variant != 6 && variant != 7) || sh.codes_cf_built) return AFIS_OK;
+    const int64_t G = sh.gal.G;
     std::vector<int32_t> to((size_t)G + 1), cfb((size_t)G + 1);
-    HIPCHK(ctx, hipMemcpyAsync(to.data(), ctx->gal.tex_off, to.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(to.data(), sh.gal.tex_off, to.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     int64_t nblk = 0;
     for (int64_t t = 0; t < G; ++t) { cfb[(size_t)t] = (int32_t)nblk; const int64_t n = to[(size_t)t + 1] - to[(size_t)t]; nblk += n > 0 ? (n + 63) / 64 + 1 : 0; }
     cfb[(size_t)G] = (int32_t)nblk;
     if (nblk > 0x7fffffff / 64) return fail(ctx, AFIS_EINVAL, "adc_variant 6 / 7: shard too large for the direct kernel's code stream; split the gallery into more shards");
-    HIPCHK(ctx, upload(ctx->g_tex_cf_blk, cfb, ctx->stream));
-    HIPCHK(ctx, ctx->g_tex_codes_cf.ensure(std::max<size_t>((size_t)nblk * 64 * 16, 16)));
-    ctx->gal.tex_cf_blk = ctx->g_tex_cf_blk.as<int32_t>();
-    ctx->gal.tex_codes_cf = ctx->g_tex_codes_cf.as<uint4>();
-    HIPCHK(ctx, launch_codes_cf(ctx->gal, ctx->g_tex_codes_cf.p, ctx->stream));
+    HIPCHK(ctx, upload(sh.g_tex_cf_blk, cfb, ctx->stream));
+    HIPCHK(ctx, sh.g_tex_codes_cf.ensure(std::max<size_t>((size_t)nblk * 64 * 16, 16)));
+    sh.gal.tex_cf_blk = sh.g_tex_cf_blk.as<int32_t>();
+    sh.gal.tex_codes_cf = sh.g_tex_codes_cf.as<uint4>();
+    HIPCHK(ctx, launch_codes_cf(sh.gal, sh.g_tex_codes_cf.p, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->codes_cf_built = true;
+    sh.codes_cf_built = true;
     return AFIS_OK;
 }
 
@@ -38,12 +38,12 @@ static int direct_rowmax(afis_ctx* ctx, const QueryDev& d, const GalleryDev& g, 
     return AFIS_OK;
 }
 
-// g_direct_adc_stage (afis_ctx.h): the selected direct kernel against the resident shard
-static int direct_adc_stage(afis_ctx* ctx, const QueryDev& d, int chunk, hipEvent_t after_lut)
+// g_direct_adc_stage (afis_ctx.h): the selected direct kernel against a shard (the resident one, or a subset's)
+static int direct_adc_stage(afis_ctx* ctx, Shard& sh, const QueryDev& d, int chunk, hipEvent_t after_lut)
 {
-    const int rcf = ensure_codes_cf(ctx, ctx->adc_variant);
+    const int rcf = ensure_codes_cf(ctx, sh, ctx->adc_variant);
     if (rcf != AFIS_OK) return rcf;
-    return direct_rowmax(ctx, d, ctx->gal, ctx->adc_variant, chunk, after_lut);
+    return direct_rowmax(ctx, d, sh.gal, ctx->adc_variant, chunk, after_lut);
 }
 __attribute__((constructor)) static void set_direct_adc_stage() { g_direct_adc_stage = direct_adc_stage; }
 
@@ -149,9 +149,9 @@ int afis_debug_texture_rowmax(afis_ctx* ctx, const afis_template_view* query, in
         HIPCHK(ctx, ctx->rm_arg.ensure(n_pairs * d.lt_pad * 4));
         HIPCHK(ctx, hipMemsetAsync(ctx->rm_val.p, 0, n_pairs * d.lt_pad * 4, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->rm_arg.p, 0, n_pairs * d.lt_pad * 4, ctx->stream));
-        if (ctx->adc_variant == 9) { int rc9 = adc_stage_mfma(ctx, grp, true); if (rc9 != AFIS_OK) { grp.release(); return rc9; } }
-        else if (ctx->adc_variant == 8) { int rc16 = adc_stage_q(ctx, grp, ctx->chunk > 0 ? ctx->chunk : 32, true); if (rc16 != AFIS_OK) { grp.release(); return rc16; } }
-        else { int rcd = direct_adc_stage(ctx, d, ctx->chunk > 0 ? ctx->chunk : 32, nullptr); if (rcd != AFIS_OK) { grp.release(); return rcd; } }
+        if (ctx->adc_variant == 9) { int rc9 = adc_stage_mfma(ctx, *ctx, grp, true); if (rc9 != AFIS_OK) { grp.release(); return rc9; } }
+        else if (ctx->adc_variant == 8) { int rc16 = adc_stage_q(ctx, *ctx, grp, ctx->chunk > 0 ? ctx->chunk : 32, true); if (rc16 != AFIS_OK) { grp.release(); return rc16; } }
+        else { int rcd = direct_adc_stage(ctx, *ctx, d, ctx->chunk > 0 ? ctx->chunk : 32, nullptr); if (rcd != AFIS_OK) { grp.release(); return rcd; } }
         HIPCHK(ctx, hipMemcpyAsync(val, ctx->rm_val.as<float>() + (size_t)gidx * d.lt_pad, (size_t)n_lt * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(arg, ctx->rm_arg.as<int32_t>() + (size_t)gidx * d.lt_pad, (size_t)n_lt * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -190,7 +190,7 @@ int afis_debug_stage_list(afis_ctx* ctx, const afis_template_view* query, int64_
             if (d.n_tiles <= 0) return AFIS_OK;
             HIPCHK(ctx, ctx->rm_val.ensure((size_t)d.lt_pad * 4)); HIPCHK(ctx, ctx->rm_arg.ensure((size_t)d.lt_pad * 4));
             const int av = ctx->adc_variant >= 8 ? 0 : ctx->adc_variant;     // the tap always uses a direct exact kernel (same bits); for the
-            { int rcf = ensure_codes_cf(ctx, av); if (rcf != AFIS_OK) return rcf; }  // bound + refine variants the plain one, which needs no extra code stream
+            { int rcf = ensure_codes_cf(ctx, *ctx, av); if (rcf != AFIS_OK) return rcf; }  // bound + refine variants the plain one, which needs no extra code stream
             if (av == 6 || av == 7) { one.tex_codes_cf = ctx->gal.tex_codes_cf; one.tex_cf_blk = ctx->gal.tex_cf_blk + gidx; }
             { int rcd = direct_rowmax(ctx, d, one, av, 32, nullptr); if (rcd != AFIS_OK) return rcd; }
             HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes(d.nq)));

@@ -49,6 +49,7 @@ class Timing(C.Structure):
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
+           "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats"]
@@ -85,6 +86,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.afis_search_dat.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_queries_upload.argtypes = [vp, C.POINTER(TemplateView), C.c_int, C.POINTER(vp)]
     lib.afis_search_resident.argtypes = [vp, vp, fp, fp, i32p, C.c_int, i64p, fp]
+    if hasattr(lib, "afis_subset_create"):                              # subset search; absent from older builds compared by tools/lib_ab.py
+        lib.afis_subset_create.argtypes = [vp, i64p, C.c_int64, C.POINTER(vp)]
+        lib.afis_subset_free.argtypes = [vp, vp]; lib.afis_subset_free.restype = None
+        lib.afis_search_subset.argtypes = [vp, vp, C.POINTER(TemplateView), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
+        lib.afis_search_subset_resident.argtypes = [vp, vp, vp, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -296,8 +302,8 @@ class Matcher:
         return int(v.value)
 
     # ---- search -----------------------------------------------------------------------------------------------
-    def _alloc(self, nq, k, want_scores, want_parts):
-        G = self.resident_size
+    def _alloc(self, nq, k, want_scores, want_parts, G=None):
+        G = self.resident_size if G is None else G
         scores = np.empty((nq, G), np.float32) if want_scores else None
         parts = np.empty((nq, G, 4), np.float32) if want_parts else None
         status = np.zeros(nq, np.int32)
@@ -339,6 +345,33 @@ class Matcher:
         h, n = handle
         scores, parts, status, ti, ts, args = self._alloc(n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search_resident(self.ctx, h, *args))
+        return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
+
+    # ---- subset search: a candidate list of the resident shard ---------------------------------------------------
+    def subset_create(self, idx: Sequence[int]):
+        """Gather the listed templates (global indices as search reports them, any order, no repeats) into a device-resident sub-shard; -> handle for search_subset*.
+        Nothing of the gallery is uploaded.  The handle is refused (AFIS_ESTATE) once the gallery has been edited; subset_free releases it."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        h = C.c_void_p()
+        self._chk(self.lib.afis_subset_create(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a), C.byref(h)))
+        return (h, len(a))
+
+    def subset_free(self, handle):
+        self.lib.afis_subset_free(self.ctx, handle[0])
+
+    def search_subset(self, handle, latents: Sequence[FPTemplate], k: int = 24, want_scores: bool = True, want_parts: bool = False):
+        """search() over the subset's templates only: column j of scores / parts belongs to the j-th listed index, topk_idx holds global indices."""
+        h, n = handle
+        v = _Views(latents)
+        scores, parts, status, ti, ts, args = self._alloc(v.n, k, want_scores, want_parts, G=n)
+        self._chk(self.lib.afis_search_subset(self.ctx, h, v.arr, v.n, *args))
+        return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
+
+    def search_subset_resident(self, handle, qhandle, k: int = 24, want_scores: bool = False, want_parts: bool = False):
+        h, n = handle
+        qh, nq = qhandle
+        scores, parts, status, ti, ts, args = self._alloc(nq, k, want_scores, want_parts, G=n)
+        self._chk(self.lib.afis_search_subset_resident(self.ctx, h, qh, *args))
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def correspondences(self, latent: FPTemplate, gallery_idx: Sequence[int]):

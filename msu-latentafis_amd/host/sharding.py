@@ -29,6 +29,21 @@ def shard_bounds(cost: np.ndarray, world: int) -> List[Tuple[int, int]]:
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
 
 
+def split_candidates(idx, bounds: List[Tuple[int, int]]) -> List[np.ndarray]:
+    """A global candidate list over a shard plan (shard_bounds): per rank the indices that fall inside its [lo, hi) — its index_base and
+    index_base + size — in the order the caller listed them, possibly none.  Each part is what that rank hands to Matcher.subset_create;
+    the per-rank rank lists of the subset searches then merge with merge_topk / gather_topk as those of full searches do.
+    An index outside every shard is an error (the ranges of a plan tile [0, G))."""
+    a = np.asarray(idx, np.int64).reshape(-1)
+    parts = [a[(a >= lo) & (a < hi)] for lo, hi in bounds]
+    if sum(len(p) for p in parts) != len(a):
+        covered = np.zeros(len(a), bool)
+        for lo, hi in bounds:
+            covered |= (a >= lo) & (a < hi)
+        raise ValueError(f"split_candidates: indices outside the shard plan (or a plan whose ranges overlap): {a[~covered][:8].tolist()}")
+    return parts
+
+
 def merge_topk(idx: np.ndarray, score: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
     """idx, score: [R, Q, kk] per-shard rank lists (idx -1 = padding).  Returns the merged [Q, k] list."""
     R, Q, kk = idx.shape
