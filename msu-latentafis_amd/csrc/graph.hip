@@ -17,6 +17,7 @@
 // How the reference's serial steps are mapped without changing their results:
 //   * std::sort of <= 200 keys        -> rank by counting (each key counts the keys larger than itself);
 //   * "top 200 of n <= 1000"          -> bit-by-bit search for the 200th largest key with ballot/popcount (all keys in registers);
+//                                        a compact list of <= 256 rows (a search's common case) is ranked whole instead: rank < 200 = the list (k_graph_texture);
 //   * greedy clique selection          -> rounds: the first still-alive candidate in rank order is accepted and every later
 //                                        candidate that conflicts with it is killed in parallel; identical to the sequential
 //                                        scan, but the trip count is the number of ACCEPTED candidates;
@@ -77,6 +78,10 @@ __device__ __forceinline__ int g_wave_max(int x)
     x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xc, 0xf, false));         // row_bcast:31
     return __builtin_amdgcn_readlane(x, 63);
 }
+
+// the same for unsigned values (the bias maps their order onto the signed one)
+__device__ __forceinline__ uint32_t g_wave_max_u32(uint32_t x) { return (uint32_t)g_wave_max((int)(x ^ 0x80000000u)) ^ 0x80000000u; }
+__device__ __forceinline__ uint32_t g_wave_min_u32(uint32_t x) { return ~g_wave_max_u32(~x); }
 
 // sum of x over the wave (wave-uniform result), same DPP ladder as g_wave_max
 __device__ __forceinline__ int g_wave_sum(int x)
@@ -955,6 +960,8 @@ __device__ __forceinline__ void tap_write(const GraphTap& tap, const SM& sm, con
 #endif
 typedef WaveSmem<kTopTex, false> TexSmem;
 constexpr int kTexRegs = (kTexMax + 63) / 64;     // 16 row maxima per lane: the wave holds all <= 1000 keys in registers
+constexpr int kTexFast = 256;                     // a compact list of at most this many rows is ranked whole, four keys per lane (k_graph_texture)
+constexpr int kTexFastRegs = kTexFast / 64;
 
 template <int REF_TIE>   // 1: option ref_tie_order 2 (sort_scores); its own instantiation, so that the default kernel is the code it was
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAVES, AFIS_TEX_WAVES))) void k_graph_texture(QueryDev q, GalleryDev g, const float* __restrict__ table_dist,
@@ -983,112 +990,186 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
             // otherwise every row's value and point at its row, -inf for rows that cannot
             const bool compact = rm_n != nullptr;
             const int n_in = compact ? rm_n[task] : n_lt;                // >= 200: the selection keeps at least the 200 rows with the largest lower bounds
-            const int n_regs = (n_in + 63) >> 6;                         // registers per lane that hold a row (uniform)
-            uint32_t key[kTexRegs]; int arg[kTexRegs];
+            if (compact && n_in >= kTopTex && n_in <= kTexFast) {
+                // A search's common case: the recomputation passes on little more than the 200 rows (213 of 671 on the headline workload), so the wave RANKS all n_in of them by counting — four
+                // keys per lane — and the entries of rank < 200 under (key descending, slot ascending) are the list, in its order: the order in which the ranking below breaks ties is the order in
+                // which "of the keys equal to the 200th keep the lowest indices" resolves the boundary (slots ascend with the rows).  No search for the 200th key, no count, no compaction.
+                uint32_t key[kTexFastRegs]; int arg[kTexFastRegs];
+                uint32_t kmin = 0xffffffffu, kmax = 0u;
 #pragma unroll
-            for (int u = 0; u < kTexRegs; ++u) {
-                const int e = u * 64 + lane;
-                const bool in = e < n_in;
-                key[u] = 0u; arg[u] = 0;                                 // real keys are never 0
-                if (u < n_regs) {                                        // uniform
-                    key[u] = in ? g_ord_f32(compact ? rm_cv[o + e] : rm_val[o + e]) : 0u;
-                    arg[u] = in ? rm_arg[o + e] : 0;                     // fetched with the values: one round trip, not one per picked row
-                }
-            }
-            uint32_t T = 0;                                              // 200th largest key, built bit by bit ...
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t cand = T | (1u << bit);
-                int c = 0;
-#pragma unroll
-                for (int u = 0; u < kTexRegs; ++u) if (u < n_regs) c += g_wave_popc(key[u] >= cand);
-                if (c >= kTopTex) { T = cand; if (c == kTopTex) break; } // ... or until exactly 200 keys are >= the prefix: they are the set
-            }
-            int n_gt = 0;
-#pragma unroll
-            for (int u = 0; u < kTexRegs; ++u) if (u < n_regs) n_gt += g_wave_popc(key[u] > T);
-            const int need = kTopTex - n_gt;                             // of the keys equal to T keep the lowest indices
-            int base_gt = 0, base_eq = 0;
-            uint32_t* const key32 = sm.x.pick.keys;   // 200 ordered-float keys, read four at a time below
-#pragma unroll
-            for (int u = 0; u < kTexRegs; ++u) {                         // u ascending, lane ascending = index ascending
-                if (u < n_regs) {
+                for (int u = 0; u < kTexFastRegs; ++u) {
                     const int e = u * 64 + lane;
-                    const bool gt = key[u] > T, eq = key[u] == T;
-                    const u64 mg = __ballot(gt), me = __ballot(eq);
-                    int pos = -1;
-                    if (gt) pos = base_gt + g_lane_prefix(mg);
-                    else if (eq) { const int r = base_eq + g_lane_prefix(me); if (r < need) pos = n_gt + r; }
-                    if (pos >= 0) { key32[pos] = key[u]; sm.x.pick.te[pos] = tex_pack_l(compact ? arg[u] & 0xffff : e, e); sm.x.pick.targ[pos] = tex_pack_r(compact ? arg[u] >> 16 : arg[u], e); }   // e = the row's slot in the array the values came from
-                    base_gt += __popcll(mg); base_eq += __popcll(me);
+                    const bool in = e < n_in;
+                    key[u] = in ? g_ord_f32(rm_cv[o + e]) : 0u;              // real keys are never 0
+                    arg[u] = in ? rm_arg[o + e] : 0;                         // fetched with the values: one round trip
+                    kmax = max(kmax, key[u]);
+                    if (in) kmin = min(kmin, key[u]);
                 }
-            }
-            WSYNC();
-            num = kTopTex;
-            // rank by counting on the 32-bit keys.  Picked rows sit in index order, so equal keys would need the index as a tie-break:
-            // ties make the ranks collide, which their sum shows (a permutation of 0..199 sums to 19900, anything else to less); the
-            // 64-bit (key, ~index) composites are ranked only then.
-            // The 200 keys are first dealt into 64 bins of equal width between the smallest and the largest (counting sort through LDS counters; b[] and
-            // cc[] are free until the distance stage), highest bin first; a key then counts the larger keys of ITS bin only and adds the bins above it:
-            // 200 x 200 comparisons become 200 x (a bin's population).
-            uint32_t m32[TexSmem::U]; int r[TexSmem::U];
-            uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(sm.b);          // [64] fill pointers, [64..128) bin starts
-            uint32_t* const s_gkey = reinterpret_cast<uint32_t*>(sm.y.cc);      // [200] the keys grouped by bin
-            int dmax = 0;
+                kmin = g_wave_min_u32(kmin); kmax = g_wave_max_u32(kmax);
+                // 64 bins of equal width between the smallest and the largest key, highest bin first, as below; HALF the span is what fits an int (maxima of both signs: see the shift below)
+                const int shift = max(0, 27 - __clz((int)((kmax - kmin) >> 1) | 1));   // bin = (key - kmin) >> shift in [0, 63]
+                uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(sm.b);   // [64] fill pointers, [64..128) bin starts (b[] is free until the distance stage)
+                uint32_t* const s_gkey = sm.x.sortbuf;                       // [256] the keys grouped by bin (nothing is picked into x: keys and rows stay in registers)
+                static_assert(TexSmem::N4 >= 128 && sizeof(sm.x.sortbuf) >= (size_t)kTexFast * 4, "the counting arrays of the compact S7 exceed their buffers");
+                int bin[kTexFastRegs], r[kTexFastRegs];
 #pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) {
-                const int t = lane + 64 * u;
-                m32[u] = t < num ? key32[t] : T;
-                dmax = max(dmax, (int)((m32[u] - T) >> 1));                       // keys are >= T (the 200th largest): the difference is non-negative — but NOT small when the 200 row maxima have both signs
-            }                                                                     // (ordered keys of +3 and -3 are 2^31 + 2^23 apart): HALF of it is what fits an int.  Rounds 3-5 took the difference itself: negative
-            dmax = g_wave_max(dmax);                                              // for such lists, a zero shift, bins far beyond 63, counters scattered over the list's LDS and ranking loops of 2^31 trips (72 s per
-            const int shift = max(0, 27 - __clz(dmax | 1));                       // search of a 224-row latent against structured prints; results still right: the tie fallback re-ranks).  bin = (key - T) >> shift in [0, 63]
-            int bin[TexSmem::U];
-#pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) bin[u] = min((int)((m32[u] - T) >> shift), 63);
-            s_cnt[lane] = 0u;
-            WSYNC();
-#pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) if (lane + 64 * u < num) atomicAdd(&s_cnt[bin[u]], 1u);
-            WSYNC();
-            {   // lane l owns bin l: start = number of keys in the bins above it
-                const int own = (int)s_cnt[lane];
-                int suf = own;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_down(suf, off); if (lane + off < 64) suf += v; }
+                for (int u = 0; u < kTexFastRegs; ++u) bin[u] = min((int)((key[u] - kmin) >> shift), 63);
+                s_cnt[lane] = 0u;
                 WSYNC();
-                s_cnt[lane] = (uint32_t)(suf - own); s_cnt[64 + lane] = (uint32_t)(suf - own);
-            }
-            WSYNC();
 #pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) if (lane + 64 * u < num) s_gkey[atomicAdd(&s_cnt[bin[u]], 1u)] = m32[u];
-            WSYNC();
+                for (int u = 0; u < kTexFastRegs; ++u) if (u * 64 + lane < n_in) atomicAdd(&s_cnt[bin[u]], 1u);
+                WSYNC();
+                {   // lane l owns bin l: start = number of keys in the bins above it
+                    const int own = (int)s_cnt[lane];
+                    int suf = own;
 #pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) {
-                r[u] = 0;
-                if (lane + 64 * u < num) {
-                    const int lo = (int)s_cnt[64 + bin[u]], hi = (int)s_cnt[bin[u]];   // the fill pointer ended at the bin's end
-                    int c = lo;
-                    for (int k = lo; k < hi; ++k) c += s_gkey[k] > m32[u];
-                    r[u] = c;
+                    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_down(suf, off); if (lane + off < 64) suf += v; }
+                    WSYNC();
+                    s_cnt[lane] = (uint32_t)(suf - own); s_cnt[64 + lane] = (uint32_t)(suf - own);
                 }
-            }
-            int rsum = 0;
+                WSYNC();
 #pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) rsum += r[u];            // lanes beyond the list hold the maximum key: rank 0
-            if (g_wave_sum(rsum) != kTopTex * (kTopTex - 1) / 2) {
-                u64 mine[TexSmem::U];
+                for (int u = 0; u < kTexFastRegs; ++u) if (u * 64 + lane < n_in) s_gkey[atomicAdd(&s_cnt[bin[u]], 1u)] = key[u];
+                WSYNC();
+                int rsum = 0;
 #pragma unroll
-                for (int u = 0; u < TexSmem::U; ++u) { const int t = lane + 64 * u; mine[u] = t < num ? ((u64)key32[t] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[t] & 1023)) : 0ull; r[u] = 0; }
-                for (int k = 0; k < num; ++k) {
-                    const u64 kk = ((u64)key32[k] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[k] & 1023));
-#pragma unroll
-                    for (int u = 0; u < TexSmem::U; ++u) r[u] += kk > mine[u];
+                for (int u = 0; u < kTexFastRegs; ++u) {
+                    r[u] = 0;
+                    if (u * 64 + lane < n_in) {
+                        const int lo = (int)s_cnt[64 + bin[u]], hi = (int)s_cnt[bin[u]];   // the fill pointer ended at the bin's end
+                        int c = lo;
+                        for (int k = lo; k < hi; ++k) c += s_gkey[k] > key[u];
+                        r[u] = c; rsum += c;
+                    }
                 }
-            }
+                if (g_wave_sum(rsum) != n_in * (n_in - 1) / 2) {             // equal keys (ranks collide: the sum falls short of a permutation's): the (key, ~slot) composites of all n_in
+                    WSYNC();                                                 // every lane has read the grouped keys: the keys in slot order take their place
 #pragma unroll
-            for (int u = 0; u < TexSmem::U; ++u) {
-                const int t = lane + 64 * u;
-                if (t < num) { sm.li[r[u]] = sm.x.pick.te[t]; sm.ri[r[u]] = sm.x.pick.targ[t]; }
+                    for (int u = 0; u < kTexFastRegs; ++u) if (u * 64 + lane < n_in) s_gkey[u * 64 + lane] = key[u];
+                    WSYNC();
+                    u64 mine[kTexFastRegs];
+#pragma unroll
+                    for (int u = 0; u < kTexFastRegs; ++u) { mine[u] = ((u64)key[u] << 32) | (uint32_t)(~(uint32_t)(u * 64 + lane)); r[u] = 0; }
+                    for (int k = 0; k < n_in; ++k) {
+                        const u64 kk = ((u64)s_gkey[k] << 32) | (uint32_t)(~(uint32_t)k);
+#pragma unroll
+                        for (int u = 0; u < kTexFastRegs; ++u) r[u] += kk > mine[u];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kTexFastRegs; ++u) {
+                    const int e = u * 64 + lane;                             // the row's slot in the compact array: what list_sim fetches its similarity by
+                    if (e < n_in && r[u] < kTopTex) { sm.li[r[u]] = tex_pack_l(arg[u] & 0xffff, e); sm.ri[r[u]] = tex_pack_r(arg[u] >> 16, e); }
+                }
+                num = kTopTex;
+            } else {                                                     // more than 256 rows passed on, or the dense form (the parity taps, adc_variant other than 9)
+                const int n_regs = (n_in + 63) >> 6;                         // registers per lane that hold a row (uniform)
+                uint32_t key[kTexRegs]; int arg[kTexRegs];
+#pragma unroll
+                for (int u = 0; u < kTexRegs; ++u) {
+                    const int e = u * 64 + lane;
+                    const bool in = e < n_in;
+                    key[u] = 0u; arg[u] = 0;                                 // real keys are never 0
+                    if (u < n_regs) {                                        // uniform
+                        key[u] = in ? g_ord_f32(compact ? rm_cv[o + e] : rm_val[o + e]) : 0u;
+                        arg[u] = in ? rm_arg[o + e] : 0;                     // fetched with the values: one round trip, not one per picked row
+                    }
+                }
+                uint32_t T = 0;                                              // 200th largest key, built bit by bit ...
+                for (int bit = 31; bit >= 0; --bit) {
+                    const uint32_t cand = T | (1u << bit);
+                    int c = 0;
+#pragma unroll
+                    for (int u = 0; u < kTexRegs; ++u) if (u < n_regs) c += g_wave_popc(key[u] >= cand);
+                    if (c >= kTopTex) { T = cand; if (c == kTopTex) break; } // ... or until exactly 200 keys are >= the prefix: they are the set
+                }
+                int n_gt = 0;
+#pragma unroll
+                for (int u = 0; u < kTexRegs; ++u) if (u < n_regs) n_gt += g_wave_popc(key[u] > T);
+                const int need = kTopTex - n_gt;                             // of the keys equal to T keep the lowest indices
+                int base_gt = 0, base_eq = 0;
+                uint32_t* const key32 = sm.x.pick.keys;   // 200 ordered-float keys, read four at a time below
+#pragma unroll
+                for (int u = 0; u < kTexRegs; ++u) {                         // u ascending, lane ascending = index ascending
+                    if (u < n_regs) {
+                        const int e = u * 64 + lane;
+                        const bool gt = key[u] > T, eq = key[u] == T;
+                        const u64 mg = __ballot(gt), me = __ballot(eq);
+                        int pos = -1;
+                        if (gt) pos = base_gt + g_lane_prefix(mg);
+                        else if (eq) { const int r = base_eq + g_lane_prefix(me); if (r < need) pos = n_gt + r; }
+                        if (pos >= 0) { key32[pos] = key[u]; sm.x.pick.te[pos] = tex_pack_l(compact ? arg[u] & 0xffff : e, e); sm.x.pick.targ[pos] = tex_pack_r(compact ? arg[u] >> 16 : arg[u], e); }   // e = the row's slot in the array the values came from
+                        base_gt += __popcll(mg); base_eq += __popcll(me);
+                    }
+                }
+                WSYNC();
+                num = kTopTex;
+                // rank by counting on the 32-bit keys.  Picked rows sit in index order, so equal keys would need the index as a tie-break:
+                // ties make the ranks collide, which their sum shows (a permutation of 0..199 sums to 19900, anything else to less); the
+                // 64-bit (key, ~index) composites are ranked only then.
+                // The 200 keys are first dealt into 64 bins of equal width between the smallest and the largest (counting sort through LDS counters; b[] and
+                // cc[] are free until the distance stage), highest bin first; a key then counts the larger keys of ITS bin only and adds the bins above it:
+                // 200 x 200 comparisons become 200 x (a bin's population).
+                uint32_t m32[TexSmem::U]; int r[TexSmem::U];
+                uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(sm.b);          // [64] fill pointers, [64..128) bin starts
+                uint32_t* const s_gkey = reinterpret_cast<uint32_t*>(sm.y.cc);      // [200] the keys grouped by bin
+                int dmax = 0;
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) {
+                    const int t = lane + 64 * u;
+                    m32[u] = t < num ? key32[t] : T;
+                    dmax = max(dmax, (int)((m32[u] - T) >> 1));                       // keys are >= T (the 200th largest): the difference is non-negative — but NOT small when the 200 row maxima have both signs
+                }                                                                     // (ordered keys of +3 and -3 are 2^31 + 2^23 apart): HALF of it is what fits an int.  Rounds 3-5 took the difference itself: negative
+                dmax = g_wave_max(dmax);                                              // for such lists, a zero shift, bins far beyond 63, counters scattered over the list's LDS and ranking loops of 2^31 trips (72 s per
+                const int shift = max(0, 27 - __clz(dmax | 1));                       // search of a 224-row latent against structured prints; results still right: the tie fallback re-ranks).  bin = (key - T) >> shift in [0, 63]
+                int bin[TexSmem::U];
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) bin[u] = min((int)((m32[u] - T) >> shift), 63);
+                s_cnt[lane] = 0u;
+                WSYNC();
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) if (lane + 64 * u < num) atomicAdd(&s_cnt[bin[u]], 1u);
+                WSYNC();
+                {   // lane l owns bin l: start = number of keys in the bins above it
+                    const int own = (int)s_cnt[lane];
+                    int suf = own;
+#pragma unroll
+                    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_down(suf, off); if (lane + off < 64) suf += v; }
+                    WSYNC();
+                    s_cnt[lane] = (uint32_t)(suf - own); s_cnt[64 + lane] = (uint32_t)(suf - own);
+                }
+                WSYNC();
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) if (lane + 64 * u < num) s_gkey[atomicAdd(&s_cnt[bin[u]], 1u)] = m32[u];
+                WSYNC();
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) {
+                    r[u] = 0;
+                    if (lane + 64 * u < num) {
+                        const int lo = (int)s_cnt[64 + bin[u]], hi = (int)s_cnt[bin[u]];   // the fill pointer ended at the bin's end
+                        int c = lo;
+                        for (int k = lo; k < hi; ++k) c += s_gkey[k] > m32[u];
+                        r[u] = c;
+                    }
+                }
+                int rsum = 0;
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) rsum += r[u];            // lanes beyond the list hold the maximum key: rank 0
+                if (g_wave_sum(rsum) != kTopTex * (kTopTex - 1) / 2) {
+                    u64 mine[TexSmem::U];
+#pragma unroll
+                    for (int u = 0; u < TexSmem::U; ++u) { const int t = lane + 64 * u; mine[u] = t < num ? ((u64)key32[t] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[t] & 1023)) : 0ull; r[u] = 0; }
+                    for (int k = 0; k < num; ++k) {
+                        const u64 kk = ((u64)key32[k] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[k] & 1023));
+#pragma unroll
+                        for (int u = 0; u < TexSmem::U; ++u) r[u] += kk > mine[u];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < TexSmem::U; ++u) {
+                    const int t = lane + 64 * u;
+                    if (t < num) { sm.li[r[u]] = sm.x.pick.te[t]; sm.ri[r[u]] = sm.x.pick.targ[t]; }
+                }
             }
         } else {                                                         // :748-749 rows stay in index order
             num = n_lt;
