@@ -217,6 +217,40 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
                                 float* scores, float* parts, int32_t* status,
                                 int k, int64_t* topk_idx, float* topk_score);
 
+/* Subject rank lists (no reference counterpart: the reference ranks the files of a directory): a resident gallery holds prints, an examiner is handed persons — a ten-print
+ * card is ten templates, a re-enrolment adds more.  The score matrix a search leaves on the device is grouped by enrolled person there, and only n_q x k x 20 bytes return.
+ * afis_subjects_create  subject[0 .. n): the caller's id of the person resident template index_base + i belongs to — any int64 >= 0, in any order, not necessarily dense.  n must
+ *                     be the resident shard's size (option "gallery_resident"; AFIS_EINVAL otherwise, as for a negative id); a call before the first commit is AFIS_ESTATE; a
+ *                     refused call leaves nothing allocated.  The distinct ids in ascending order become the slots of the rank lists; the slot of every template (int32) and
+ *                     the id table are uploaded, and counted in option "gallery_h2d_bytes" as a subset's tables are.  Create and free first wait for all device work of the
+ *                     context.  Several handles may be live at once; afis_destroy releases those that are left.  A handle belongs to the gallery as it was: after an
+ *                     appending commit or a removal that changed the shard afis_rank_subjects refuses it with AFIS_ESTATE (afis_subjects_free still works).
+ * afis_rank_subjects   ranks the score matrix of the context's LAST search — any of afis_search, afis_search_dat, afis_search_resident, afis_search_subset,
+ *                     afis_search_subset_resident, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
+ *                     search's (AFIS_EINVAL otherwise, as for k <= 0 or a null output).  Per query the k best subjects:
+ *                       subject_score  the greatest fused score among the subject's templates that the search covered: all of them for a full search, the listed ones for a
+ *                                      subset search (a subject without a listed template does not appear).  An empty or removed entry contributes its -1: a subject all of
+ *                                      whose templates are empty scores -1, and a latent-empty query lists the subjects by ascending id, all at -1.
+ *                       subject_id     score descending, equal scores by ascending subject id whatever order the templates or a subset's list had
+ *                       best_idx       the global index (index_base included) of the subject's best template, the lowest such index among equal scores
+ *                     padded with id -1, score -inf, best_idx -1 where k exceeds the subjects present.  "Greatest" and "descending" are taken on the score's bits in their
+ *                     total order (sign-magnitude: -0.0 below +0.0, a NaN where its bits put it); on the scores a search produces that is the order of the template rank
+ *                     lists, so that with subject[i] = c + i the result is entry for entry the rank list of afis_search: ids c + position, the same scores, the same
+ *                     indices.  k <= 64 is made on the device; larger k copies the [n_q][subjects] maxima to the host and sorts there, on the same keys.  The device
+ *                     keeps n_q x subjects x 8 bytes for the maxima (80 MB at 100 x 100 000), allocated on first use: AFIS_EDEVICE, with nothing changed, when that fails.
+ *                     The matrix stays rankable from the successful return of the search until the next call on the context that queues device work or edits the gallery —
+ *                     a search (a failed or timed-out one included), afis_queries_upload, afis_correspondences, afis_match_all_templates, every gallery
+ *                     edit and export, afis_subset_create, afis_subset_free, a change of option "bound_cus" — after which afis_rank_subjects is AFIS_ESTATE.  It may itself
+ *                     be repeated, with another k or another handle; afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
+ *                     afis_last_error and afis_gallery_size leave the matrix alone.  No result of a search changes because subjects exist.
+ * Shards: every rank labels its own shard and ranks its own subjects; the per-rank lists merge exactly although a person's prints may lie in several shards
+ * (host/sharding.py::merge_subject_topk). */
+typedef struct afis_subjects afis_subjects;
+int afis_subjects_create(afis_ctx* ctx, const int64_t* subject /*[n]*/, int64_t n, afis_subjects** out);
+void afis_subjects_free(afis_ctx* ctx, afis_subjects* s);
+int afis_rank_subjects(afis_ctx* ctx, afis_subjects* s, int n_q, int k,
+                       int64_t* subject_id /*[n_q][k]*/, float* subject_score /*[n_q][k]*/, int64_t* best_idx /*[n_q][k]*/);
+
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
  * 100k-1M template gallery is loaded — whole, or one contiguous shard per GPU — without touching 100k-1M small files.
@@ -306,7 +340,8 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * of the context's gallery commits and removals so far, counted where the copies are issued: an appending commit adds its own points and the offset tables, not the resident shard.
  * "gallery_resident" (read-only): the templates of the committed shard, the G of afis_search's outputs (afis_gallery_size also counts what is staged beside it after afis_gallery_reopen).
  * "subset_device_bytes" (read-only): the device bytes held by the context's live subsets (0 when there is none); "subset_gather_us" (read-only): the device time of the last
- * afis_subset_create's gather launches, from HIP events around them. */
+ * afis_subset_create's gather launches, from HIP events around them.  "subject_rank_us" (read-only): the device time of the last afis_rank_subjects' launches (the maxima's
+ * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

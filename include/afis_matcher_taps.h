@@ -42,6 +42,12 @@ int afis_debug_refine_stats(afis_ctx* ctx, unsigned long long* out8, int reset);
  * launches, summed), out2[1] = the bytes they copied.  tools/bench_live_gallery.py sets them beside a device-to-device copy of the same bytes. */
 int afis_debug_compact_stats(afis_ctx* ctx, long long* out2);
 
+/* Subject rank lists (afis_rank_subjects) over a caller-made score matrix: scores [n_q][G] for the resident shard is uploaded in place of the matrix a search leaves,
+ * marked valid as a full search of n_q queries marks it, and ranked by the code afis_rank_subjects runs — score patterns (ties, zeros of both signs, infinities, NaN) that
+ * no search produces on demand.  Outputs as afis_rank_subjects'. */
+int afis_debug_rank_subjects(afis_ctx* ctx, afis_subjects* subjects, const float* scores /*[n_q][G]*/, int n_q, int k,
+                             int64_t* subject_id, float* subject_score, int64_t* best_idx);
+
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */
 int afis_debug_phase_cycles(afis_ctx* ctx, unsigned long long* out32, int reset);

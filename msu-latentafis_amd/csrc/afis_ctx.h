@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -111,6 +111,19 @@ struct afis_subset {
     size_t device_bytes() const { return sh.device_bytes() + d_global.bytes + d_pos.bytes; }
 };
 
+// The enrolled person of every template of the resident shard (afis_subjects_create): the distinct ids in ascending order are the slots 0 .. S-1 of the subject rank
+// lists, slot_of maps a template (shard-local index) to its slot.
+struct afis_subjects {
+    int64_t n = 0, S = 0;                // templates labelled (the resident shard's size at creation), distinct subjects
+    uint64_t gallery_epoch = 0;          // afis_ctx::gallery_epoch at creation: afis_rank_subjects refuses the handle after an edit
+    std::vector<int64_t> ids;            // [S] ascending (the host's copy: rank lists of k > 64)
+    DevBuf d_slot_of, d_ids;             // [n] int32, [S] int64
+};
+
+// The score matrix the last search left in afis_ctx::scores ([n_q][G] in the order of the shard searched: the resident one, or sub's sub-shard), while nothing has
+// touched it or what it refers to: afis_rank_subjects ranks it.  Set by a search that succeeded, cleared by drain_abandoned at the top of every entry point that queues work.
+struct LastSearch { bool valid = false; int n_q = 0; int64_t G = 0; const afis_subset* sub = nullptr; uint64_t gallery_epoch = 0; };   // (gallery_epoch: the shard the matrix was scored against)
+
 struct afis_ctx : Shard {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -133,6 +146,10 @@ struct afis_ctx : Shard {
     uint64_t gallery_epoch = 0;          // counts the edits of the resident shard (appending commits, removals)
     std::vector<afis_subset*> subsets;   // live subsets (afis_subset_create .. afis_subset_free; afis_destroy releases what is left)
     int64_t subset_gather_us = 0;        // option subset_gather_us (read-only): device time of the last afis_subset_create's gather launches (HIP events around them)
+    std::vector<afis_subjects*> subject_sets;   // live subject handles (afis_subjects_create .. afis_subjects_free; afis_destroy releases what is left)
+    LastSearch last_search;
+    DevBuf subj_best, subj_out;          // afis_rank_subjects: best[n_q][S] composites (grown on demand), and the three [n_q][k] output arrays behind one another
+    int64_t subject_rank_us = 0;         // option subject_rank_us (read-only): device time of the last afis_rank_subjects' launches (HIP events around them)
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -228,11 +245,13 @@ std::vector<float> fragment_tiles(const std::vector<float>& des, const std::vect
     return out;
 }
 
+// Rank lists (of templates: afis_search*; of subjects: afis_rank_subjects) are made on the device for k <= kDeviceTopK (k passes of a workgroup-wide maximum per query); larger k sorts on the host.
+constexpr int kDeviceTopK = 64;
 constexpr int64_t kMfRecBytesPerRow = 8;               // adc_variant 9: one 8-byte record per (rolled template, latent texture row)
 // afis_gallery.cpp
 int materialise(afis_ctx* ctx);                        // the staged gallery as host arrays: a container that afis_gallery_load only mapped is copied into ctx->hg now
 void free_gallery_dev(Shard* c);                       // every device buffer of a shard (the context's resident one, or a subset's)
-int quiesce(afis_ctx* ctx, const char* what);          // an edit replaces or releases device buffers that searches read: waits (bounded) for all device work of the context
+int quiesce(afis_ctx* ctx, const char* what, bool keep_last_search = false);   // an edit replaces or releases device buffers that searches read: waits (bounded) for all device work of the context
 int ensure_mf_gallery(afis_ctx* ctx, Shard& sh, hipStream_t s);   // adc_variant 9's tile-aligned copy of the gallery codes (built at commit, or by the first search after the variant was selected)
 void views_of(const HostTemplate& t, std::vector<afis_minutiae_view>& mv, std::vector<afis_texture_view>& tv, afis_template_view& out);
 // afis_search.cpp
@@ -253,11 +272,15 @@ extern DirectAdcStage g_direct_adc_stage __attribute__((visibility("hidden")));
 int64_t graph_slab_bytes(int64_t n_pairs);             // both slabs for a launch of n_pairs (latent, rolled) pairs (1.0 GB + 2 x 0.67 GB from 16 384 pairs on)
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what);
 void register_context(afis_ctx* ctx); void unregister_context(afis_ctx* ctx);   // the process-wide list group_budget_bytes consults
-int drain_abandoned(afis_ctx* ctx);                     // waits (bounded) for a search that returned at its deadline
+int drain_abandoned(afis_ctx* ctx, bool keep_last_search = false);   // waits (bounded) for a search that returned at its deadline; the caller is about to queue work: the last search's score matrix is no longer afis_rank_subjects' to rank (unless kept)
 // The launch sequence of a search over one shard: the context's resident one (sub == NULL, sh == *ctx) or a subset's (sh == sub->sh).  afis_search_resident and
 // afis_search_subset_resident check their handles and call it.
 int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score);
 size_t subset_device_bytes(const afis_ctx* ctx);       // option subset_device_bytes: what the live subsets hold on the device
 void release_subset(afis_subset* s);                   // its device buffers and the handle itself (afis_subset.cpp)
+// afis_subjects.cpp
+void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
+// afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.
+int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* subject_id, float* subject_score, int64_t* best_idx) __attribute__((visibility("hidden")));
 
 }  // namespace afis

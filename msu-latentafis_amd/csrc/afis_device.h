@@ -248,6 +248,15 @@ hipError_t launch_gather_ranges(const void* src, void* dst, int elem_bytes, cons
 // or part (16-byte) columns into the caller's order: dst[q][j] = src[q][pos[j]], j < n
 hipError_t launch_subset_topk_map(long long* idx, long long n_idx, const long long* map, int n_map, hipStream_t stream);
 hipError_t launch_permute_columns(const void* src, void* dst, int elem_bytes, int n_q, int n, const int32_t* pos, hipStream_t stream);
+// afis_rank_subjects (subject_rank.hip): per (query, subject slot) the greatest composite (ordered score bits << 32 | ~position) over the positions whose template belongs
+// to the slot -> best[n_q][S] (zeroed first; 0 stays where no position of the row belongs to the slot).  slot_of: [templates of the resident shard] int32 in [0, S);
+// d_global NULL: position p of scores[n_q][G] is template p (a full search) — or a subset's [G] global indices: template d_global[p] - index_base
+hipError_t launch_subject_best(const float* scores, int n_q, int G, const int32_t* slot_of, const long long* d_global, long long index_base, int S,
+                               unsigned long long* best, hipStream_t stream);
+// ... and the k best slots of every query, score descending / slot ascending: out_id = ids[slot], out_score = the score at the slot's best position (read from scores),
+// out_best = index_base + position, or d_global[position]; (-1, -inf, -1) where k exceeds the slots that hold a composite
+hipError_t launch_topk_subjects(const unsigned long long* best, int n_q, int S, const long long* ids, const float* scores, int G, const long long* d_global, long long index_base,
+                                int k, long long* out_id, float* out_score, long long* out_best, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

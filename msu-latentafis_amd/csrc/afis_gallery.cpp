@@ -564,10 +564,10 @@ static void release_staging(afis_ctx* ctx)
 // (afis_subset_create / afis_subset_free wait the same way: afis_subset.cpp)
 }  // extern "C"
 namespace afis {
-int quiesce(afis_ctx* ctx, const char* what)
+int quiesce(afis_ctx* ctx, const char* what, bool keep_last_search)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
+    { const int rcd = drain_abandoned(ctx, keep_last_search); if (rcd != AFIS_OK) return rcd; }
     return wait_streams(ctx, {ctx->stream_lo, ctx->stream_hi, ctx->stream}, what);
 }
 }  // namespace afis

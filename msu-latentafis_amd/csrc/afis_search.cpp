@@ -100,8 +100,9 @@ int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, cons
 
 // A search that left at its deadline may still be running on the device: what it queued must be done before its buffers (device, pinned) are touched again and before anything
 // blocks on the context's stream alone.  Called at the top of the entry points that queue work.
-int drain_abandoned(afis_ctx* ctx)
+int drain_abandoned(afis_ctx* ctx, bool keep_last_search)
 {
+    if (!keep_last_search) ctx->last_search.valid = false;
     if (!ctx->search_abandoned) return AFIS_OK;
     ctx->search_abandoned = false;
     const int rc = wait_streams(ctx, {ctx->stream_lo, ctx->stream_hi, ctx->stream}, "waiting for the search that timed out");   // (a second timeout sets the flag again)
@@ -377,8 +378,6 @@ int adc_refine_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, bo
     return AFIS_OK;
 }
 
-// Rank lists are made on the device for k <= kDeviceTopK (k passes of a workgroup-wide maximum per query); larger k sorts on the host.
-static const int kDeviceTopK = 64;
 
 // (1 of 3) Every buffer of the launch groups, brought to its size while the device is idle and before anything of the search is queued.
 static int prepare_search_buffers(afis_ctx* ctx, Shard& sh, const afis_queries* q, bool want_parts)
@@ -689,6 +688,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
     tm.launch_groups = (int32_t)n_groups;
     for (const QueryGroup& grp : q->groups) tm.overlapped_groups += grp.overlapped ? 1 : 0;
     ctx->timing = tm;
+    ctx->last_search = LastSearch{true, nq_all, G, sub, ctx->gallery_epoch};                   // ctx->scores holds this search's matrix until the next entry point that queues work (afis_rank_subjects)
     return AFIS_OK;
 }
 
@@ -813,6 +813,7 @@ int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, flo
             parts.resize((size_t)nq * G * 4);
             rc = afis_search_resident(ctx, &q, nullptr, parts.data(), nullptr, 0, nullptr, nullptr);
         }
+        ctx->last_search.valid = false;                                     // (a pseudo-query search of this mode's own: not a matrix afis_rank_subjects may rank)
         if (ctx->search_abandoned) {                                        // timed out: the kernels may still read the group — park it (see afis_queries_free)
             afis_queries* keep = new afis_queries; keep->groups.swap(q.groups); ctx->parked_queries.push_back(keep);
         } else q.groups.back().release();

@@ -83,6 +83,22 @@ int afis_debug_compact_stats(afis_ctx* ctx, long long* out2)
     return AFIS_OK;
 }
 
+// A caller-made score matrix [n_q][G] for the resident shard in place of a search's: uploaded into ctx->scores, marked as a full search of n_q queries leaves it,
+// then ranked by the code afis_rank_subjects runs.
+int afis_debug_rank_subjects(afis_ctx* ctx, afis_subjects* subjects, const float* scores, int n_q, int k, int64_t* subject_id, float* subject_score, int64_t* best_idx)
+{
+    if (!ctx || !subjects || !scores || n_q <= 0) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_subjects: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_subjects: commit the gallery first");
+    { const int rcq = quiesce(ctx, "afis_debug_rank_subjects"); if (rcq != AFIS_OK) return rcq; }
+    const int64_t G = ctx->gal.G;
+    if (G > 0) {
+        HIPCHK(ctx, ctx->scores.ensure((size_t)n_q * (size_t)G * 4));
+        HIPCHK(ctx, hipMemcpy(ctx->scores.p, scores, (size_t)n_q * (size_t)G * 4, hipMemcpyHostToDevice));
+    }
+    ctx->last_search = LastSearch{true, n_q, G, nullptr, ctx->gallery_epoch};
+    return afis_rank_subjects(ctx, subjects, n_q, k, subject_id, subject_score, best_idx);
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

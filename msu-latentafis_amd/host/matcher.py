@@ -50,9 +50,10 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
+           "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
-TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats"]
+TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -91,6 +92,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_subset_free.argtypes = [vp, vp]; lib.afis_subset_free.restype = None
         lib.afis_search_subset.argtypes = [vp, vp, C.POINTER(TemplateView), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
         lib.afis_search_subset_resident.argtypes = [vp, vp, vp, fp, fp, i32p, C.c_int, i64p, fp]
+    if hasattr(lib, "afis_subjects_create"):                            # subject rank lists; absent from older builds compared by tools/lib_ab.py
+        lib.afis_subjects_create.argtypes = [vp, i64p, C.c_int64, C.POINTER(vp)]
+        lib.afis_subjects_free.argtypes = [vp, vp]; lib.afis_subjects_free.restype = None
+        lib.afis_rank_subjects.argtypes = [vp, vp, C.c_int, C.c_int, i64p, fp, i64p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -116,6 +121,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_compact_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(lib, "afis_debug_refine_stats"):
         lib.afis_debug_refine_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(lib, "afis_debug_rank_subjects"):
+        lib.afis_debug_rank_subjects.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp, i64p]
     return lib
 
 
@@ -373,6 +380,33 @@ class Matcher:
         scores, parts, status, ti, ts, args = self._alloc(nq, k, want_scores, want_parts, G=n)
         self._chk(self.lib.afis_search_subset_resident(self.ctx, h, qh, *args))
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
+
+    # ---- subject rank lists: the last search's scores grouped by enrolled person ---------------------------------
+    def subjects_create(self, ids: Sequence[int]):
+        """One subject id (any int64 >= 0) per template of the resident shard, in shard order; -> handle for rank_subjects.  The handle is refused (AFIS_ESTATE) once
+        the gallery has been edited; subjects_free releases it."""
+        a = np.ascontiguousarray(np.asarray(ids, np.int64).reshape(-1))
+        h = C.c_void_p()
+        self._chk(self.lib.afis_subjects_create(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a), C.byref(h)))
+        return (h, len(a))
+
+    def subjects_free(self, handle):
+        self.lib.afis_subjects_free(self.ctx, handle[0])
+
+    def _subject_lists(self, fn, n_q: int, k: int):
+        sid = np.empty((n_q, max(k, 0)), np.int64); sc = np.empty((n_q, max(k, 0)), np.float32); bi = np.empty((n_q, max(k, 0)), np.int64)
+        self._chk(fn(n_q, k, _ptr(sid, C.c_int64), _ptr(sc, C.c_float), _ptr(bi, C.c_int64)))
+        return {"subject": sid, "score": sc, "best_idx": bi}
+
+    def rank_subjects(self, handle, n_q: int, k: int = 24):
+        """The k best subjects of every query of the LAST search (any of the search calls; n_q is that search's): subject [n_q][k] ids, score descending / id ascending,
+        score [n_q][k] the best fused score among the subject's templates the search covered, best_idx [n_q][k] the global index of that template; (-1, -inf, -1) pads."""
+        return self._subject_lists(lambda nq, kk, a, b, c: self.lib.afis_rank_subjects(self.ctx, handle[0], nq, kk, a, b, c), n_q, k)
+
+    def debug_rank_subjects(self, handle, scores: np.ndarray, k: int = 24):
+        """rank_subjects over a caller-made [n_q][G] score matrix for the resident shard (parity tap)."""
+        s = np.ascontiguousarray(scores, np.float32)
+        return self._subject_lists(lambda nq, kk, a, b, c: self._tap("afis_debug_rank_subjects")(self.ctx, handle[0], _ptr(s, C.c_float), nq, kk, a, b, c), s.shape[0], k)
 
     def correspondences(self, latent: FPTemplate, gallery_idx: Sequence[int]):
         """Surviving minutiae correspondences (matcher.cpp:497-505) of one latent against each listed gallery template:

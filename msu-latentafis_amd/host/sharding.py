@@ -58,6 +58,34 @@ def merge_topk(idx: np.ndarray, score: np.ndarray, k: int) -> Tuple[np.ndarray, 
     return out_i, out_s
 
 
+def merge_subject_topk(ids: np.ndarray, score: np.ndarray, best_idx: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """ids, score, best_idx: [R, Q, kk] per-rank subject rank lists (Matcher.rank_subjects on every rank's shard; id -1 = padding).  Returns the merged [Q, k] lists:
+    entries with the same id keep the greater score — on equal scores the lower best_idx — then score descending, id ascending; padded with (-1, -inf, -1).
+
+    Exact although a person's prints may lie in several shards, for kk >= k: a subject's global score is the maximum of its per-shard scores, reached in some shard A.
+    If the subject is among the global k best, fewer than k subjects rank before it globally (greater score, or equal score and lower id); every subject that ranks
+    before it INSIDE A does so with a per-shard score no greater than its own global one, hence ranks before it globally too — so it is among A's k best and arrives
+    with its true score and best template (the lowest index at that score within A; the same score from another shard competes here on best_idx).  An entry that
+    arrives only with a lower score — from shards where the subject did not reach its maximum, while A's list was full — belongs to a subject that k others outrank
+    in A, all of them globally ahead of it: whatever place its understated score earns, it cannot be among the k best, and it cannot displace one of them, because
+    each of those arrives with its true score."""
+    R, Q, kk = ids.shape
+    fi = np.transpose(ids, (1, 0, 2)).reshape(Q, R * kk)
+    fs = np.transpose(score, (1, 0, 2)).reshape(Q, R * kk).astype(np.float32)
+    fb = np.transpose(best_idx, (1, 0, 2)).reshape(Q, R * kk)
+    out_i = np.full((Q, k), -1, np.int64); out_s = np.full((Q, k), -np.inf, np.float32); out_b = np.full((Q, k), -1, np.int64)
+    for q in range(Q):
+        valid = fi[q] >= 0
+        vi, vs, vb = fi[q][valid], fs[q][valid], fb[q][valid]
+        order = np.lexsort((vb, -vs.astype(np.float64), vi))                # by id; inside an id the greater score, then the lower best_idx, comes first
+        first = np.ones(len(order), bool); first[1:] = vi[order][1:] != vi[order][:-1]
+        keep = order[first]
+        vi, vs, vb = vi[keep], vs[keep], vb[keep]
+        order = np.lexsort((vi, -vs.astype(np.float64)))[:k]                # score descending, then subject id ascending
+        out_i[q, :len(order)] = vi[order]; out_s[q, :len(order)] = vs[order]; out_b[q, :len(order)] = vb[order]
+    return out_i, out_s, out_b
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""
