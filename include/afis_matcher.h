@@ -251,6 +251,34 @@ void afis_subjects_free(afis_ctx* ctx, afis_subjects* s);
 int afis_rank_subjects(afis_ctx* ctx, afis_subjects* s, int n_q, int k,
                        int64_t* subject_id /*[n_q][k]*/, float* subject_score /*[n_q][k]*/, int64_t* best_idx /*[n_q][k]*/);
 
+/* Hit lists (no reference counterpart): "who is above the decision score?" — lights-out identification, watch-list alarms and deduplication want every template, or every
+ * person, whose score reaches a threshold, and how many there are; an ELFT-style candidate list wants 100 entries, more than the rank lists make on the device.  Both are
+ * answered on the device from the score matrix of the context's LAST search, in one workgroup per query that passes over its row five times at most (rank_hits.hip): only
+ * n_q x (8 + cap x 12) bytes (templates) or n_q x (8 + cap x 20) bytes (subjects) return, through the context's pinned buffer.
+ * afis_rank_hits          the templates: idx / score as afis_search's topk_idx / topk_score (global indices; for a subset search the listed templates only).
+ * afis_rank_subject_hits  the enrolled persons of a subject handle: subject_id / subject_score / best_idx as afis_rank_subjects'.
+ * A hit list is the longest prefix of the corresponding rank list — afis_search's for templates, afis_rank_subjects' for subjects — whose entries reach min_score:
+ *   n_hits[q]     how many entries qualify; it may exceed cap, which is how a caller sees that the list was cut
+ *   the lists     the first min(n_hits[q], cap) entries of the rank list; the rest is padded as the rank lists are: idx / subject_id / best_idx -1, score -inf
+ * "Reach" is decided on the ordered key the rank list itself is sorted by, so that the qualifying entries are a prefix of it whatever bit patterns the matrix holds:
+ * for templates the bits of score + 0.0f in their total order (min_score gets the same + 0.0f, so the two zeros are one value; equal scores by ascending global index,
+ * also for a subset listed out of order), for subjects the raw bits of the subject's best score in their total order (-0.0 below +0.0; equal scores by ascending subject
+ * id; a subject none of whose templates the search covered is no entry and is not counted).  A NaN orders where its bits put it: above +inf with the sign clear, below
+ * -inf — and so below every min_score — with it set.  On the scores a search produces, -1 or a finite value >= +0.0, both rules are plainly score >= min_score.
+ * min_score = -INFINITY turns the call into a rank list of length cap: entry for entry afis_search's top-k, or afis_rank_subjects' list.
+ * Which searches count, what invalidates the matrix and what leaves it alone are exactly as for afis_rank_subjects: AFIS_ESTATE when there is no matrix to rank or the
+ * subject handle belongs to an older gallery; AFIS_EINVAL when n_q is not the last search's, the handle is not live, an output is null, cap is outside
+ * 1 .. AFIS_HITS_MAX (the list is sorted in the workgroup's local memory) or min_score is a NaN.  Both calls leave the matrix rankable: they may be repeated with other
+ * arguments, and afis_rank_subjects may follow; a wait that times out invalidates it.  With an empty shard, or a handle without subjects, every n_hits is 0 and every
+ * entry padding; n_q == 0 returns AFIS_OK.  Device and pinned room (n_q x subjects x 8 bytes for the subjects' maxima, as afis_rank_subjects) is ensured before anything
+ * is queued: AFIS_EDEVICE, with nothing changed, when that fails.  No result of a search changes because these functions exist.
+ * Shards: host/sharding.py::merge_hits and merge_subject_hits merge the per-rank lists and counts. */
+#define AFIS_HITS_MAX 4096
+int afis_rank_hits(afis_ctx* ctx, int n_q, float min_score, int cap,
+                   int64_t* n_hits /*[n_q]*/, int64_t* idx /*[n_q][cap]*/, float* score /*[n_q][cap]*/);
+int afis_rank_subject_hits(afis_ctx* ctx, afis_subjects* s, int n_q, float min_score, int cap,
+                           int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/, int64_t* best_idx /*[n_q][cap]*/);
+
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
  * 100k-1M template gallery is loaded — whole, or one contiguous shard per GPU — without touching 100k-1M small files.
@@ -341,7 +369,8 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "gallery_resident" (read-only): the templates of the committed shard, the G of afis_search's outputs (afis_gallery_size also counts what is staged beside it after afis_gallery_reopen).
  * "subset_device_bytes" (read-only): the device bytes held by the context's live subsets (0 when there is none); "subset_gather_us" (read-only): the device time of the last
  * afis_subset_create's gather launches, from HIP events around them.  "subject_rank_us" (read-only): the device time of the last afis_rank_subjects' launches (the maxima's
- * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them. */
+ * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them.  "rank_hits_us" (read-only): the device time of the last afis_rank_hits' or
+ * afis_rank_subject_hits' launches (k_rank_hits; for subjects the maxima's memset and k_subject_best before it), from HIP events around them; 0 when that call queued nothing. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -48,6 +48,12 @@ int afis_debug_compact_stats(afis_ctx* ctx, long long* out2);
 int afis_debug_rank_subjects(afis_ctx* ctx, afis_subjects* subjects, const float* scores /*[n_q][G]*/, int n_q, int k,
                              int64_t* subject_id, float* subject_score, int64_t* best_idx);
 
+/* Hit lists (afis_rank_hits, afis_rank_subject_hits) over a caller-made score matrix, uploaded and marked valid as afis_debug_rank_subjects does, then ranked by the code
+ * of the two entry points: subjects == NULL gives template hits (out_a = idx; out_b is ignored), a handle gives subject hits (out_a = subject_id, out_b = best_idx).
+ * The matrix stays rankable afterwards, so that the entry points themselves can be called on it. */
+int afis_debug_rank_hits(afis_ctx* ctx, afis_subjects* subjects, const float* scores /*[n_q][G]*/, int n_q, float min_score, int cap,
+                         int64_t* n_hits /*[n_q]*/, int64_t* out_a /*[n_q][cap]*/, float* out_score /*[n_q][cap]*/, int64_t* out_b /*[n_q][cap] or NULL*/);
+
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */
 int afis_debug_phase_cycles(afis_ctx* ctx, unsigned long long* out32, int reset);

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -150,6 +150,8 @@ struct afis_ctx : Shard {
     LastSearch last_search;
     DevBuf subj_best, subj_out;          // afis_rank_subjects: best[n_q][S] composites (grown on demand), and the three [n_q][k] output arrays behind one another
     int64_t subject_rank_us = 0;         // option subject_rank_us (read-only): device time of the last afis_rank_subjects' launches (HIP events around them)
+    DevBuf hits_out;                     // afis_rank_hits / afis_rank_subject_hits: n_hits [n_q] and the two or three [n_q][cap] output arrays behind one another
+    int64_t rank_hits_us = 0;            // option rank_hits_us (read-only): device time of the last hit-list call's launches (HIP events around them)
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -198,6 +200,17 @@ inline int fail(afis_ctx* ctx, int code, const std::string& msg)
         return fail(ctx, AFIS_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_) + (e_ == hipErrorOutOfMemory ?                                      \
             " (device memory: a launch group's buffers are sized from the memory that was free when the queries were uploaded - with several contexts or processes on one "  \
             "device lower option rowmax_budget_mb or query_batch)" : "")); } while (0)
+
+// the context's pinned read-back buffer, grown to at least `bytes` (nothing may be in flight into it)
+inline hipError_t ensure_pin(afis_ctx* ctx, size_t bytes)
+{
+    if (ctx->h_pin_bytes >= bytes) return hipSuccess;
+    if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
+    ctx->h_pin = nullptr; ctx->h_pin_bytes = 0;
+    const hipError_t e = hipHostMalloc(&ctx->h_pin, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) ctx->h_pin_bytes = bytes;
+    return e;
+}
 
 template <class T, class A>
 inline hipError_t upload(DevBuf& b, const std::vector<T, A>& v, hipStream_t s)
@@ -282,5 +295,8 @@ void release_subset(afis_subset* s);                   // its device buffers and
 void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
 // afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.
 int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* subject_id, float* subject_score, int64_t* best_idx) __attribute__((visibility("hidden")));
+// afis_hits.cpp
+// afis_rank_hits (subj == NULL: out_a = idx, out_b unused) and afis_rank_subject_hits (out_a = subject_id, out_b = best_idx) behind their argument checks.  Hidden, as rank_subjects.
+int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int cap, int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b) __attribute__((visibility("hidden")));
 
 }  // namespace afis

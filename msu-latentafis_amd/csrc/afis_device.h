@@ -257,6 +257,13 @@ hipError_t launch_subject_best(const float* scores, int n_q, int G, const int32_
 // out_best = index_base + position, or d_global[position]; (-1, -inf, -1) where k exceeds the slots that hold a composite
 hipError_t launch_topk_subjects(const unsigned long long* best, int n_q, int S, const long long* ids, const float* scores, int G, const long long* d_global, long long index_base,
                                 int k, long long* out_id, float* out_score, long long* out_best, hipStream_t stream);
+// afis_rank_hits / afis_rank_subject_hits (rank_hits.hip): per query the entries whose ordered score word is >= thr — out_n[q] how many, and the min(out_n[q], cap) best in
+// rank-list order, padded with (-1, -inf, -1) to cap.  best == NULL: the entries are the G scores of the row, ordered as k_topk orders them, out_a = the global index
+// (index_base + position, or d_global[position]), out_b unused.  best != NULL: the entries are the S slots of best[n_q][S] as launch_subject_best left it, ordered as
+// launch_topk_subjects orders them, out_a = ids[slot], out_b = the global index of the slot's best template.  thr >= 1 (the ordered word of -inf is 0x007fffff).
+constexpr int kRankHitsMax = 4096;                      // AFIS_HITS_MAX: the composites of a list are sorted in LDS (32 KB)
+hipError_t launch_rank_hits(const float* scores, int n_q, int G, const unsigned long long* best, int S, const long long* ids, const long long* d_global, long long index_base,
+                            uint32_t thr, int cap, long long* out_n, long long* out_a, float* out_score, long long* out_b, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

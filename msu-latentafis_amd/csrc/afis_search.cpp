@@ -642,12 +642,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
     // arrays, a std::vector — makes the runtime wait for the stream inside the call, which is where a search used to spend its two seconds before the deadline below was ever looked at
     // (profiles/r05_deadline_recovery.log).  The caller's arrays are filled from it after the wait; the score matrix (-ldir: 40 MB at 100 x 100k) is copied after the wait as well.
     const size_t pin_topk = dev_topk ? (size_t)nq_all * k * 12 : 0, pin_diag = std::max<size_t>(n_groups, 1) * kDiagWords * 8;
-    if (ctx->h_pin_bytes < pin_topk + pin_diag) {
-        if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-        ctx->h_pin = nullptr; ctx->h_pin_bytes = 0;
-        HIPCHK(ctx, hipHostMalloc(&ctx->h_pin, pin_topk + pin_diag, hipHostMallocDefault));
-        ctx->h_pin_bytes = pin_topk + pin_diag;
-    }
+    HIPCHK(ctx, ensure_pin(ctx, pin_topk + pin_diag));
     uint8_t* const pin = (uint8_t*)ctx->h_pin;
     if (dev_topk) {
         HIPCHK(ctx, hipMemcpyAsync(pin, ctx->topk_idx.p, (size_t)nq_all * k * 8, hipMemcpyDeviceToHost, s));

@@ -37,12 +37,7 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
     const size_t score_at = n_out * 8, best_at = (score_at + n_out * 4 + 7) / 8 * 8, out_bytes = best_at + n_out * 8;
     if (dev_topk) {
         HIPCHK(ctx, ctx->subj_out.ensure(out_bytes));
-        if (ctx->h_pin_bytes < out_bytes) {
-            if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-            ctx->h_pin = nullptr; ctx->h_pin_bytes = 0;
-            HIPCHK(ctx, hipHostMalloc(&ctx->h_pin, out_bytes, hipHostMallocDefault));
-            ctx->h_pin_bytes = out_bytes;
-        }
+        HIPCHK(ctx, ensure_pin(ctx, out_bytes));
     }
     hipStream_t s = ctx->stream;
     hipEvent_t ev[2] = {nullptr, nullptr};

@@ -99,6 +99,21 @@ int afis_debug_rank_subjects(afis_ctx* ctx, afis_subjects* subjects, const float
     return afis_rank_subjects(ctx, subjects, n_q, k, subject_id, subject_score, best_idx);
 }
 
+// The same for the hit lists: the matrix is uploaded and marked valid, then afis_rank_hits (subjects == NULL; out_b is not touched) or afis_rank_subject_hits runs.
+int afis_debug_rank_hits(afis_ctx* ctx, afis_subjects* subjects, const float* scores, int n_q, float min_score, int cap, int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b)
+{
+    if (!ctx || !scores || n_q <= 0) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_hits: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_hits: commit the gallery first");
+    { const int rcq = quiesce(ctx, "afis_debug_rank_hits"); if (rcq != AFIS_OK) return rcq; }
+    const int64_t G = ctx->gal.G;
+    if (G > 0) {
+        HIPCHK(ctx, ctx->scores.ensure((size_t)n_q * (size_t)G * 4));
+        HIPCHK(ctx, hipMemcpy(ctx->scores.p, scores, (size_t)n_q * (size_t)G * 4, hipMemcpyHostToDevice));
+    }
+    ctx->last_search = LastSearch{true, n_q, G, nullptr, ctx->gallery_epoch};
+    return subjects ? afis_rank_subject_hits(ctx, subjects, n_q, min_score, cap, n_hits, out_a, out_score, out_b) : afis_rank_hits(ctx, n_q, min_score, cap, n_hits, out_a, out_score);
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

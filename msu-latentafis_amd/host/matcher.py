@@ -50,10 +50,10 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
-           "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects",
+           "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
-TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects"]
+TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -96,6 +96,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_subjects_create.argtypes = [vp, i64p, C.c_int64, C.POINTER(vp)]
         lib.afis_subjects_free.argtypes = [vp, vp]; lib.afis_subjects_free.restype = None
         lib.afis_rank_subjects.argtypes = [vp, vp, C.c_int, C.c_int, i64p, fp, i64p]
+    if hasattr(lib, "afis_rank_hits"):                                  # hit lists; absent from older builds compared by tools/lib_ab.py
+        lib.afis_rank_hits.argtypes = [vp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp]
+        lib.afis_rank_subject_hits.argtypes = [vp, vp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -123,6 +126,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_refine_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.c_int]
     if hasattr(lib, "afis_debug_rank_subjects"):
         lib.afis_debug_rank_subjects.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp, i64p]
+    if hasattr(lib, "afis_debug_rank_hits"):
+        lib.afis_debug_rank_hits.argtypes = [vp, vp, fp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
     return lib
 
 
@@ -178,6 +183,7 @@ class Matcher:
             self.ctx = None
             raise AfisError(f"afis_create failed ({rc}): {self.lib.afis_last_error(None).decode()}")
         self.gallery_files: List[str] = []
+        self.last_n_q = 0                                                  # queries of the last search call made through this object (rank_hits / rank_subject_hits default to it)
 
     def device_info(self, device: int) -> dict:
         """What the HIP runtime says about a device (afis_device_info): name, PCI bus id, UUID, compute units."""
@@ -324,6 +330,7 @@ class Matcher:
         v = _Views(latents)
         scores, parts, status, ti, ts, args = self._alloc(v.n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search(self.ctx, v.arr, v.n, *args))
+        self.last_n_q = v.n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def search_dat(self, bufs: Sequence[bytes], k: int = 24, want_scores: bool = True, want_parts: bool = False):
@@ -332,6 +339,7 @@ class Matcher:
         lens = (C.c_size_t * max(1, n))(*[len(b) for b in bufs])
         scores, parts, status, ti, ts, args = self._alloc(n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search_dat(self.ctx, arr, lens, n, *args))
+        self.last_n_q = n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def rank_list(self, scores, k: int = 24, ref_order: bool = False):
@@ -352,6 +360,7 @@ class Matcher:
         h, n = handle
         scores, parts, status, ti, ts, args = self._alloc(n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search_resident(self.ctx, h, *args))
+        self.last_n_q = n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     # ---- subset search: a candidate list of the resident shard ---------------------------------------------------
@@ -372,6 +381,7 @@ class Matcher:
         v = _Views(latents)
         scores, parts, status, ti, ts, args = self._alloc(v.n, k, want_scores, want_parts, G=n)
         self._chk(self.lib.afis_search_subset(self.ctx, h, v.arr, v.n, *args))
+        self.last_n_q = v.n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def search_subset_resident(self, handle, qhandle, k: int = 24, want_scores: bool = False, want_parts: bool = False):
@@ -379,6 +389,7 @@ class Matcher:
         qh, nq = qhandle
         scores, parts, status, ti, ts, args = self._alloc(nq, k, want_scores, want_parts, G=n)
         self._chk(self.lib.afis_search_subset_resident(self.ctx, h, qh, *args))
+        self.last_n_q = nq
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     # ---- subject rank lists: the last search's scores grouped by enrolled person ---------------------------------
@@ -407,6 +418,33 @@ class Matcher:
         """rank_subjects over a caller-made [n_q][G] score matrix for the resident shard (parity tap)."""
         s = np.ascontiguousarray(scores, np.float32)
         return self._subject_lists(lambda nq, kk, a, b, c: self._tap("afis_debug_rank_subjects")(self.ctx, handle[0], _ptr(s, C.c_float), nq, kk, a, b, c), s.shape[0], k)
+
+    # ---- hit lists: everything of the last search that reaches a decision score -----------------------------------
+    def _hit_lists(self, fn, n_q: int, cap: int, subjects: bool):
+        c = max(cap, 0)
+        nh = np.empty(n_q, np.int64); a = np.empty((n_q, c), np.int64); sc = np.empty((n_q, c), np.float32); b = np.empty((n_q, c), np.int64) if subjects else None
+        self._chk(fn(n_q, _ptr(nh, C.c_int64), _ptr(a, C.c_int64), _ptr(sc, C.c_float), _ptr(b, C.c_int64) if subjects else None))
+        return {"n_hits": nh, "subject": a, "score": sc, "best_idx": b} if subjects else {"n_hits": nh, "idx": a, "score": sc}
+
+    def rank_hits(self, min_score: float, cap: int, n_q: Optional[int] = None):
+        """Of the LAST search (n_q: its queries; default: those of the last search call made through this object), per query every template whose score reaches min_score:
+        n_hits [n_q] how many (it may exceed cap), idx / score [n_q][cap] the best min(n_hits, cap) of them in the search's rank-list order, padded with (-1, -inf).
+        min_score = -inf gives the search's own top-cap, for cap up to 4096 (AFIS_HITS_MAX).  The default n_q is kept by this object's search* methods and by
+        debug_rank_hits only: after debug_rank_subjects, or a search made on the context by other means, pass n_q."""
+        n_q = self.last_n_q if n_q is None else n_q
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_hits(self.ctx, nq, min_score, cap, nh, a, sc), n_q, cap, False)
+
+    def rank_subject_hits(self, handle, min_score: float, cap: int, n_q: Optional[int] = None):
+        """rank_hits over the enrolled persons of a subjects_create handle: n_hits, and subject / score / best_idx [n_q][cap] as rank_subjects gives them."""
+        n_q = self.last_n_q if n_q is None else n_q
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits(self.ctx, handle[0], nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
+
+    def debug_rank_hits(self, handle, scores: np.ndarray, min_score: float, cap: int):
+        """rank_hits (handle None) or rank_subject_hits over a caller-made [n_q][G] score matrix for the resident shard (parity tap); the matrix stays rankable."""
+        s = np.ascontiguousarray(scores, np.float32)
+        self.last_n_q = s.shape[0]
+        return self._hit_lists(lambda nq, nh, a, sc, b: self._tap("afis_debug_rank_hits")(self.ctx, handle[0] if handle is not None else None, _ptr(s, C.c_float), nq, min_score, cap, nh, a, sc, b),
+                               s.shape[0], cap, handle is not None)
 
     def correspondences(self, latent: FPTemplate, gallery_idx: Sequence[int]):
         """Surviving minutiae correspondences (matcher.cpp:497-505) of one latent against each listed gallery template:

@@ -86,6 +86,28 @@ def merge_subject_topk(ids: np.ndarray, score: np.ndarray, best_idx: np.ndarray,
     return out_i, out_s, out_b
 
 
+def merge_hits(n_hits: np.ndarray, idx: np.ndarray, score: np.ndarray, cap: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """n_hits: [R, Q], idx, score: [R, Q, kk] per-rank hit lists (Matcher.rank_hits with one min_score on every rank's shard; kk >= cap).  Returns (n_hits [Q], idx [Q, cap],
+    score [Q, cap]): the counts add — a template lies in one shard — and the list is the merge on score descending, then global index ascending, cut at cap.  Exact: every
+    rank's list is the best-kk prefix of what qualifies in its shard, so an entry among the cap best of the union is among the kk best of its own shard."""
+    out_i, out_s = merge_topk(idx, score, cap)
+    return np.asarray(n_hits, np.int64).sum(axis=0), out_i, out_s
+
+
+def merge_subject_hits(n_hits: np.ndarray, subject: np.ndarray, score: np.ndarray, best_idx: np.ndarray, cap: int):
+    """n_hits: [R, Q], subject, score, best_idx: [R, Q, kk] per-rank subject hit lists (Matcher.rank_subject_hits with one min_score on every rank; kk >= cap).  Returns
+    (n_hits [Q], truncated [Q], subject, score, best_idx [Q, cap]).  The lists merge by merge_subject_topk's rule — a person's prints may lie in several shards: the best
+    score wins, then the lowest index — which is exact for the same reason (a subject's global score is its best per-shard score, and it qualifies where it reaches that).
+    The per-rank counts do NOT add, for the same person may qualify in several shards: n_hits[q] is the number of distinct subjects in the merged input.  That is the exact
+    count while every rank handed over all its hits; truncated[q] is true when a rank reported n_hits > kk, and only then is the count a lower bound."""
+    ids = np.asarray(subject)
+    R, Q, kk = ids.shape
+    out = merge_subject_topk(ids, score, best_idx, cap)
+    flat = np.transpose(ids, (1, 0, 2)).reshape(Q, R * kk)
+    n = np.array([len(np.unique(row[row >= 0])) for row in flat], np.int64)
+    return n, (np.asarray(n_hits, np.int64) > kk).any(axis=0), out[0], out[1], out[2]
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""
