@@ -689,3 +689,139 @@ def large_shard_size(seed, slice_size=50000, limit=2000000):
         if all(q[k] > LARGE_SHARD_LIMITS[k] for k in LARGE_SHARD_LIMITS):
             return G
     raise AssertionError("no gallery size up to %d passes the limits" % limit)
+
+
+# ---- correspondence lists of every length (tests/test_gpu_list_lengths.py) ----
+# The list kernels (csrc/graph.hip: dist_filter, angle_filter, sort_scores, greedy) choose nearly every branch by the LENGTH of the list they are handed: blocks of 64 rows,
+# a last block of 1..8 / 9..16 / 17..32 rows that is dealt to lane groups, the parity of the length (the antipodal offset), 48 and 16 entries in the sorts.  These inputs make
+# a list of exactly the wanted length and leave survivors whose number is known: a texture list has one entry per latent row (up to the 200-row cut), a minutiae list has
+# min(120, latent minutiae x rolled minutiae) entries.
+LIST_TEX_N = (1, 2, 3, 8, 9, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 72, 73, 80, 81, 95, 96, 97,
+              127, 128, 129, 136, 137, 144, 145, 160, 161, 191, 192, 193, 199, 200, 230)
+LIST_GEOMETRIES = ("rigid", "dense", "sparse", "range")
+LIST_RANGE_N = tuple(n for n in LIST_TEX_N if n >= 8)                   # the |d| < 50 rule needs pairs on both of its sides
+LIST_TEX_ROLLED = 300                                                   # texture points of every rolled template
+LIST_TEX_MOVE = (2, -1)                                                 # the rolled copy of the latent rows, in blocks
+LIST_TEX_JITTER = {"rigid": 0, "dense": 1, "sparse": 2, "range": 1}
+# (rolled minutiae, minutiae of the latent templates 26 / 2 / 11): one pair gives three list lengths.  The products cover 4, 9, 16, 18, 32, 33, 36, 48, 49, 63, 64, 65, 66,
+# 72, 80, 81, 96, 98, 99, 108, 119, 120 and beyond 120 (121, 144, 3200); 17 and 97 against ONE rolled minutia; the last five hand S9 about 64, 65, 96, 100 and 120 entries.
+LIST_MINU_SPECS = ((2, (2, 3, 4)), (3, (3, 6, 11)), (4, (4, 8, 2)), (6, (6, 8, 11)), (7, (7, 9, 14)), (7, (17, 5, 3)), (8, (8, 9, 10)), (8, (12, 3, 5)), (9, (9, 11, 12)),
+                   (13, (5, 8, 7)), (12, (10, 12, 4)), (11, (11, 6, 9)), (80, (40, 20, 10)), (1, (17, 97, 5)),
+                   (64, (64, 30, 10)), (70, (65, 16, 33)), (100, (96, 48, 24)), (110, (100, 50, 72)), (120, (120, 60, 90)))
+LIST_MINU_JITTER = (3, 20)                                              # pixels: every true correspondence agrees with every other / only some do
+LIST_SELECTED = (26, 2, 11)
+SHAPE_SWEEP_ARGS = ("5", "8", "30")                                       # tools/shape_sweep.py as tests/test_gpu_parity.py runs it ...
+SHAPE_SWEEP_NONZERO = 368                                               # ... and the oracle's non-zero part scores on those 240 pairs (960 part scores)
+LIST_RESEED = {}                                                        # {("texture", geometry, N) or ("minutiae", pair): n}: the n-th draw, where the first left fewer than two survivors
+
+
+def list_pair_matrices(lx, ly, rx, ry, texture):
+    """(in range, neighbours) of every pair of list entries as graph.hip decides them: texture pairs are in range when every |d| < 50 (matcher.cpp:1257), minutiae pairs always;
+    neighbours (H != 0) are in range with |d1 - d2| < 30 px in the reference's float arithmetic (a block is 16 px).  The neighbour matrix's row sums are row_degrees of
+    tests/test_gpu_graph_slab.py."""
+    lx, ly, rx, ry = (np.asarray(v, np.int64) for v in (lx, ly, rx, ry))
+    dx1 = lx[:, None] - lx[None, :]; dy1 = ly[:, None] - ly[None, :]; dx2 = rx[:, None] - rx[None, :]; dy2 = ry[:, None] - ry[None, :]
+    d1 = np.sqrt((dx1 * dx1 + dy1 * dy1).astype(np.float32)); d2 = np.sqrt((dx2 * dx2 + dy2 * dy2).astype(np.float32))
+    if texture:
+        ok = (np.abs(dx1) < 50) & (np.abs(dy1) < 50) & (np.abs(dx2) < 50) & (np.abs(dy2) < 50)
+        near = np.float32(16.0) * np.abs(d1 - d2) < np.float32(30.0)
+    else:
+        ok = np.ones(d1.shape, bool)
+        near = np.abs(d1 - d2) < np.float32(30.0)
+    np.fill_diagonal(ok, False)
+    return ok, ok & near
+
+
+def list_walk_classes(num):
+    """(antipodal, wrapped): boolean [num, num] masks over i < j of the pairs the kernels' pair walk (row t visits t + d mod num, d = 1 .. num / 2) reaches at the offset
+    d == num / 2 of an even list, and through the wrap past the list's end (from row j: i + num - j <= num / 2)."""
+    i, j = np.triu_indices(num, 1)
+    anti = np.zeros((num, num), bool); wrap = np.zeros((num, num), bool)
+    anti[i, j] = (num % 2 == 0) & (2 * (j - i) == num)
+    wrap[i, j] = 2 * (j - i) > num
+    return anti, wrap
+
+
+def _list_unit(rng, n):
+    d = rng.standard_normal((n, 96)).astype(np.float32)
+    return (d * (np.float32(T.DESCRIPTOR_NORM) / np.linalg.norm(d, axis=1, keepdims=True))).astype(np.float32)
+
+
+def _list_texture(rng, cb, geometry, N):
+    """Latent texture template of N rows on distinct cells and a rolled one of LIST_TEX_ROLLED points, N of which (at random places) are the rows moved by LIST_TEX_MOVE + jitter.
+    Default window: every coordinate of both sides in [0, 49]; "range": a window of 66 blocks, so that some pairs fail |d| < 50."""
+    J = LIST_TEX_JITTER[geometry]
+    side = 66 if geometry == "range" else 46
+    lori = rng.uniform(-np.pi / 2, np.pi / 2, N).astype(np.float32)
+    des = _list_unit(rng, N)
+    for _ in range(200):                                                     # dense and range: drawn until the planted pairs have the property the case is there for
+        cells = rng.permutation(side * side)[:N]
+        lx = cells % side; ly = cells // side + 3                           # rolled: x + 2 + j in [0, side + 3], y - 1 + j in [0, side + 3]
+        if J == 1:                                                           # two points in three stay put: nearly all pairs are neighbours, with H values that differ
+            jit = rng.choice([-1, 0, 0, 0, 0, 1], (N, 2))
+        else:
+            jit = rng.integers(-J, J + 1, (N, 2))
+        px = lx + LIST_TEX_MOVE[0] + jit[:, 0]; py = ly + LIST_TEX_MOVE[1] + jit[:, 1]
+        ok, near = list_pair_matrices(lx, ly, px, py, True)
+        if geometry == "dense" and N >= 2 and near.sum(axis=1).min() < 0.85 * (N - 1):
+            continue                                                         # (the test asks for 0.8 of the LIST's rows: of 230 rows S7 keeps 200)
+        if geometry == "range" and (ok.sum() == N * (N - 1) or not near.any()):
+            continue
+        break
+    else:
+        raise AssertionError(("no draw with the wanted pairs", geometry, N))
+    n_r = LIST_TEX_ROLLED
+    at = rng.permutation(n_r)[:N]
+    rx = rng.integers(0, side + 4, n_r); ry = rng.integers(0, side + 4, n_r)
+    rori = rng.uniform(-np.pi / 2, np.pi / 2, n_r).astype(np.float32)
+    codes = rng.integers(0, cb.K, (n_r, cb.M)).astype(np.uint8)
+    rx[at] = px; ry[at] = py
+    rori[at] = lori + (rng.standard_normal(N) * 0.05).astype(np.float32)
+    codes[at] = cb.encode_fast(des + np.float32(0.04) * rng.standard_normal((N, 96)).astype(np.float32))
+    return (T.TextureTemplate(lx.astype(np.int16), ly.astype(np.int16), lori, des=des),
+            T.TextureTemplate(rx.astype(np.int16), ry.astype(np.int16), rori, codes=codes))
+
+
+def _list_minutiae(rng, n_r, n_l3, jitter):
+    """28 latent minutiae templates (the selected ones hold the first n_l3[i] points of a pool, the others two) and a rolled one of the pool's first n_r points, moved and
+    jittered: min(n_l, n_r) true correspondences per list.  Pool points sit on a 110-px grid (+-8): far enough apart for the jitter not to turn the line between two of them, and spread widely enough
+    for two FALSE correspondences to agree in distance (within 30 px) only rarely — the true ones have to win the power iteration even where there are only two or three."""
+    P = max(n_r, *n_l3)
+    cells = rng.permutation(16 * 17)[:P]
+    px = 60 + 110 * (cells % 16) + rng.integers(-8, 9, P); py = 60 + 110 * (cells // 16) + rng.integers(-8, 9, P)   # <= 1828: with the move and the jitter inside [0, 2047]
+    po = rng.uniform(-np.pi, np.pi, P).astype(np.float32)
+    pd = _list_unit(rng, P)
+
+    def view(n, sigma, move=(0, 0), jit=0, ori_sigma=0.0):
+        o = rng.permutation(n)
+        d = pd[o] + np.float32(sigma) * rng.standard_normal((n, 96)).astype(np.float32)
+        d = (d * (np.float32(T.DESCRIPTOR_NORM) / np.linalg.norm(d, axis=1, keepdims=True))).astype(np.float32)
+        x = px[o] + move[0] + rng.integers(-jit, jit + 1, n); y = py[o] + move[1] + rng.integers(-jit, jit + 1, n)
+        return T.MinutiaeTemplate(x.astype(np.int16), y.astype(np.int16), (po[o] + (rng.standard_normal(n) * ori_sigma).astype(np.float32)).astype(np.float32), d)
+
+    sizes = dict(zip(LIST_SELECTED, n_l3))
+    lat = [view(sizes.get(i, min(2, P)), 0.02) for i in range(28)]
+    rol = view(n_r, 0.08, (int(rng.integers(-20, 21)), int(rng.integers(-20, 21))), jitter, 0.05)
+    return lat, rol
+
+
+def list_length_set(cb, seed=70):
+    """One (latent, rolled) pair per texture length and geometry; pair c carries the minutiae shapes LIST_MINU_SPECS[c % 19] with jitter LIST_MINU_JITTER[c // 19 % 2].
+    -> list of dicts: geometry, N, spec (rolled minutiae, latent minutiae of 26 / 2 / 11), minu_jitter, L, R."""
+    out = []
+    for gi, geometry in enumerate(LIST_GEOMETRIES):
+        for N in (LIST_RANGE_N if geometry == "range" else LIST_TEX_N):
+            c = len(out)
+            n_r, n_l3 = LIST_MINU_SPECS[c % len(LIST_MINU_SPECS)]
+            jitter = LIST_MINU_JITTER[c // len(LIST_MINU_SPECS) % 2]
+            lt, rt = _list_texture(np.random.default_rng([seed, 0, gi, N, LIST_RESEED.get(("texture", geometry, N), 0)]), cb, geometry, N)
+            lm, rm = _list_minutiae(np.random.default_rng([seed, 1, c, LIST_RESEED.get(("minutiae", c), 0)]), n_r, n_l3, jitter)
+            out.append(dict(geometry=geometry, N=N, spec=(n_r, n_l3), minu_jitter=jitter, L=T.FPTemplate(minu=lm, tex=[lt]), R=T.FPTemplate(minu=[rm], tex=[rt])))
+    return out
+
+
+def list_length_shifted(t, tex_shift=0, minu_shift=0):
+    """The template with every texture block coordinate moved by tex_shift and every minutiae pixel coordinate by minu_shift (into another arithmetic class of the list kernels)."""
+    mv = lambda v, s: (v.astype(np.int64) + s).astype(np.int16)
+    return T.FPTemplate(minu=[T.MinutiaeTemplate(mv(m.x, minu_shift), mv(m.y, minu_shift), m.ori, m.des) for m in t.minu],
+                        tex=[T.TextureTemplate(mv(x.x, tex_shift), mv(x.y, tex_shift), x.ori, des=x.des, codes=x.codes) for x in t.tex])

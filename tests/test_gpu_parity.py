@@ -459,12 +459,15 @@ def test_texture_top200_with_tied_row_maxima(codebook_bytes, cb, oracle):
 
 
 def test_template_shapes_sweep():
-    """Correspondence lists of every length (2-120 minutiae, 20-1000 texture points per template: short lists, nearly empty last row
-    blocks, lists below and above the top-120 / top-200 cuts): tools/shape_sweep.py compares every part score of 8 x 30 pairs with the
-    oracle, bit for bit (the wide run behind DESIGN section 2 is the same script with more seeds)."""
-    import subprocess, sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "shape_sweep.py"), "5", "8", "30"], capture_output=True, text=True, timeout=600)
+    """Templates of unusual sizes (2-120 minutiae, 20-1000 texture points per template) through the whole search: tools/shape_sweep.py compares every part score of
+    8 x 30 pairs with the oracle, bit for bit (the wide run behind DESIGN section 2 is the same script with more seeds), and 368 of those 960 part scores are non-zero
+    (the oracle's own count: tests/test_gpu_list_lengths.py, test_what_the_shape_sweep_covers).  At this seed every texture list is 200 long and the minutiae lists
+    take 33 lengths; the systematic sweep over list lengths is tests/test_gpu_list_lengths.py."""
+    import re, subprocess, sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "shape_sweep.py"), *cases.SHAPE_SWEEP_ARGS], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "differing bit: 0" in out.stdout, (out.stdout[-600:], out.stderr[-600:])
+    nz = re.search(r"240 pairs over 8 latent shapes, (\d+) non-zero part scores", out.stdout)
+    assert nz and int(nz.group(1)) == cases.SHAPE_SWEEP_NONZERO, out.stdout[-600:]
 
 
 def test_python_drivers_equal_cli(codebook_bytes, cb, small, tmp_path):
