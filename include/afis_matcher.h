@@ -152,7 +152,8 @@ int64_t afis_gallery_size(const afis_ctx* ctx);
  * afis_gallery_export  writes the resident shard as a packed container (below): byte for byte the file afis_gallery_save writes from a context staged with the
  *                     same entries.  names as for afis_gallery_save, one per resident template.
  * Query handles (afis_queries_upload) are cut into launch groups for the shard size of the moment: after an appending commit or a removal that changed the shard,
- * afis_search_resident refuses an older handle with AFIS_ESTATE; free it and upload the latents again.  afis_search uploads per call and is not affected.
+ * afis_search_resident refuses an older handle with AFIS_ESTATE; free it and upload the latents again.  afis_search uploads per call and is not affected; a handle of
+ * afis_queries_upload_reserved (below) is cut for a stated shard size instead and survives the edits.
  * After every edit the results are, bit for bit, those of a context freshly committed with the final gallery. */
 int afis_gallery_reopen(afis_ctx* ctx);
 int afis_gallery_remove(afis_ctx* ctx, const int64_t* idx, int64_t n);
@@ -184,6 +185,14 @@ int afis_search_dat(afis_ctx* ctx, const void* const* latent_bytes, const size_t
  * (-ldir mode) and the per-part scores only when `parts` is.  k > 64 sorts on the host. */
 typedef struct afis_queries afis_queries;
 int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_q, afis_queries** out);
+/* A query handle that survives gallery edits (reverse search, below): as afis_queries_upload, except that the launch groups are cut as that function would cut them at a
+ * shard of max_templates templates — the memory budget, the latents per launch (option "query_batch", or the automatic figure for that size) and the row-group cuts —
+ * whatever the resident shard holds at the time, which may be more.  The handle records max_templates and is accepted whatever edits have happened since it was
+ * uploaded: by afis_search_resident while the resident shard holds at most max_templates templates, by afis_search_subset_resident for a live, current subset of at most
+ * max_templates templates; a larger shard or subset is AFIS_EINVAL with both numbers in the message.  max_templates < 1 is AFIS_EINVAL, a call before the first commit
+ * AFIS_ESTATE.  Device memory behaves as with subsets: later enrolments take memory the cuts did not know of, and a search that cannot get its buffers returns
+ * AFIS_EDEVICE before it has queued anything.  A handle is not edited in place: a latent file that grows is kept as several handles (afis_rank_latent_hits' latent_base). */
+int afis_queries_upload_reserved(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out);
 int afis_search_resident(afis_ctx* ctx, afis_queries* q,
                          float* scores, float* parts, int32_t* status,
                          int k, int64_t* topk_idx, float* topk_score);
@@ -279,6 +288,33 @@ int afis_rank_hits(afis_ctx* ctx, int n_q, float min_score, int cap,
 int afis_rank_subject_hits(afis_ctx* ctx, afis_subjects* s, int n_q, float min_score, int cap,
                            int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/, int64_t* best_idx /*[n_q][cap]*/);
 
+/* Reverse search (no reference counterpart): every newly enrolled ten-print card is searched against the file of unsolved latents — the transaction that solves old cases.
+ * The pair score is the forward search's; what differs is who stays on the device and which way the matrix is read.  The latents (about 260 KB each, against 50 KB per
+ * print) are uploaded once with afis_queries_upload_reserved; per card the caller appends the prints (afis_gallery_reopen, afis_gallery_add*, afis_gallery_commit), lists
+ * their indices in afis_subset_create, runs afis_search_subset_resident with k = 0 and no outputs, and reads the answer with
+ * afis_rank_latent_hits  the hit lists of the context's LAST search taken along the COLUMNS of its matrix: per template the search covered, the search's queries whose
+ *                     score reaches min_score.  n_templates must be the number of columns that search covered — the resident shard's size for a full search, the
+ *                     subset's n for a subset search (AFIS_EINVAL otherwise).  Row j of the outputs belongs to idx[j] of the subset's list in the caller's order, or to
+ *                     template index_base + j of a full search:
+ *                       n_hits[j]      how many queries qualify; it may exceed cap
+ *                       latent_idx     latent_base + the query's position in the search, for the first min(n_hits[j], cap) entries of the order below; then -1
+ *                       score          the scores of those entries, their own bits; then -inf
+ *                     The key is afis_rank_hits': the bits of score + 0.0f in their total order, min_score treated the same way, descending; equal keys by ascending
+ *                     query position.  On the scores a search produces that is plainly score >= min_score.  min_score = -INFINITY gives the cap best latents of
+ *                     every print.  Latent-empty queries and empty or removed templates take part with the -1 the matrix holds.  With n_templates == 0, or a last
+ *                     search of no queries, the call returns AFIS_OK with zero counts and padding.  latent_base (>= 0) is where this handle's first latent stands
+ *                     in the caller's file: a file kept as several handles, or spread over ranks, is searched handle by handle and the per-column lists merge
+ *                     exactly (host/sharding.py::merge_hits — the columns are common, the latents disjoint).
+ *                     Which searches count, what invalidates the matrix and what leaves it alone are exactly as for afis_rank_hits; the call may be repeated and mixed
+ *                     with afis_rank_hits, afis_rank_subject_hits and afis_rank_subjects.  AFIS_EINVAL: cap outside 1 .. AFIS_HITS_MAX, a NaN min_score, a negative
+ *                     latent_base, a null output, a wrong n_templates; AFIS_ESTATE: no matrix to rank.  On the device the matrix is transposed through local memory
+ *                     in 64 x 64 tiles (latent_rank.hip) and the transposed rows are ranked by the kernel of afis_rank_hits, unchanged.  The device keeps
+ *                     n_templates x n_q x 4 bytes for the transposed matrix beside the outputs; that room and the pinned return buffer are ensured before anything is
+ *                     queued: AFIS_EDEVICE, with nothing changed, when that fails.  Only n_templates x (8 + cap x 12) bytes return.
+ * The P prints of one card fuse into one list per card with host/sharding.py::merge_prints_to_card.  No result of a search changes because these functions exist. */
+int afis_rank_latent_hits(afis_ctx* ctx, int64_t n_templates, float min_score, int cap, int64_t latent_base,
+                          int64_t* n_hits /*[n_templates]*/, int64_t* latent_idx /*[n_templates][cap]*/, float* score /*[n_templates][cap]*/);
+
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
  * 100k-1M template gallery is loaded — whole, or one contiguous shard per GPU — without touching 100k-1M small files.
@@ -370,7 +406,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "subset_device_bytes" (read-only): the device bytes held by the context's live subsets (0 when there is none); "subset_gather_us" (read-only): the device time of the last
  * afis_subset_create's gather launches, from HIP events around them.  "subject_rank_us" (read-only): the device time of the last afis_rank_subjects' launches (the maxima's
  * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them.  "rank_hits_us" (read-only): the device time of the last afis_rank_hits' or
- * afis_rank_subject_hits' launches (k_rank_hits; for subjects the maxima's memset and k_subject_best before it), from HIP events around them; 0 when that call queued nothing. */
+ * afis_rank_subject_hits' launches (k_rank_hits; for subjects the maxima's memset and k_subject_best before it), from HIP events around them; 0 when that call queued nothing.
+ * "rank_latents_us" (read-only): the device time of the last afis_rank_latent_hits' launches (k_transpose_scores, then k_rank_hits on the transposed matrix), from HIP
+ * events around them; 0 when that call queued nothing. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -54,6 +54,14 @@ int afis_debug_rank_subjects(afis_ctx* ctx, afis_subjects* subjects, const float
 int afis_debug_rank_hits(afis_ctx* ctx, afis_subjects* subjects, const float* scores /*[n_q][G]*/, int n_q, float min_score, int cap,
                          int64_t* n_hits /*[n_q]*/, int64_t* out_a /*[n_q][cap]*/, float* out_score /*[n_q][cap]*/, int64_t* out_b /*[n_q][cap] or NULL*/);
 
+/* Column hit lists (afis_rank_latent_hits) over a caller-made score matrix, uploaded and marked valid as afis_debug_rank_hits does (a full search of n_q queries over the
+ * resident shard), then ranked by the entry point itself with n_templates = the resident shard's size.  The matrix stays rankable afterwards. */
+int afis_debug_rank_latent_hits(afis_ctx* ctx, const float* scores /*[n_q][G]*/, int n_q, float min_score, int cap, int64_t latent_base,
+                                int64_t* n_hits /*[G]*/, int64_t* latent_idx /*[G][cap]*/, float* score /*[G][cap]*/);
+/* The transpose of the last afis_rank_latent_hits (latent_rank.hip: k_transpose_scores): out2[0] = its device time in microseconds (a pair of HIP events of its own),
+ * out2[1] = the bytes it read and wrote; both 0 when that call queued nothing.  tools/reverse_search_timing.py turns them into bytes per second. */
+int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2);
+
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */
 int afis_debug_phase_cycles(afis_ctx* ctx, unsigned long long* out32, int reset);

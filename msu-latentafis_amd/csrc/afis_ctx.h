@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -68,6 +68,7 @@ struct afis_queries {
     std::vector<int32_t> status;     // per query
     int n_q = 0;
     uint64_t gallery_epoch = 0;      // afis_ctx::gallery_epoch when the handle was uploaded: its launch groups were cut for that shard's size (afis_search_resident refuses it after an edit)
+    int64_t max_templates = 0;       // > 0 (afis_queries_upload_reserved): the launch groups were cut for a shard of this many templates; the handle is taken by any shard or subset up to that size, whatever edits happened since
 };
 
 // What describes "the shard being searched": the SoA arrays of a set of rolled templates in HBM with their offset tables, the derived layouts, the streams laid out on first
@@ -152,6 +153,9 @@ struct afis_ctx : Shard {
     int64_t subject_rank_us = 0;         // option subject_rank_us (read-only): device time of the last afis_rank_subjects' launches (HIP events around them)
     DevBuf hits_out;                     // afis_rank_hits / afis_rank_subject_hits: n_hits [n_q] and the two or three [n_q][cap] output arrays behind one another
     int64_t rank_hits_us = 0;            // option rank_hits_us (read-only): device time of the last hit-list call's launches (HIP events around them)
+    DevBuf scores_t;                     // afis_rank_latent_hits: the last search's matrix transposed, [n_templates][n_q] (its lists leave through hits_out)
+    int64_t rank_latents_us = 0;         // option rank_latents_us (read-only): device time of the last afis_rank_latent_hits' launches (k_transpose_scores, k_rank_hits)
+    int64_t transpose_us = 0, transpose_bytes = 0;   // k_transpose_scores alone in that call (its own pair of events) and the bytes it read and wrote (parity tap afis_debug_transpose_stats)
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -291,6 +295,9 @@ int drain_abandoned(afis_ctx* ctx, bool keep_last_search = false);   // waits (b
 int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score);
 size_t subset_device_bytes(const afis_ctx* ctx);       // option subset_device_bytes: what the live subsets hold on the device
 void release_subset(afis_subset* s);                   // its device buffers and the handle itself (afis_subset.cpp)
+// afis_queries_upload (max_templates == 0: the launch groups are cut for the resident shard's size) and afis_queries_upload_reserved (afis_reverse.cpp: for a shard of
+// max_templates templates) behind their argument checks.  Hidden, as rank_subjects below.
+int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out) __attribute__((visibility("hidden")));
 // afis_subjects.cpp
 void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
 // afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.
@@ -298,5 +305,9 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
 // afis_hits.cpp
 // afis_rank_hits (subj == NULL: out_a = idx, out_b unused) and afis_rank_subject_hits (out_a = subject_id, out_b = best_idx) behind their argument checks.  Hidden, as rank_subjects.
 int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int cap, int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b) __attribute__((visibility("hidden")));
+// what the hit-list entry points ask of the context and of their plain arguments (the order of afis_rank_subjects' checks); afis_rank_latent_hits (afis_reverse.cpp) asks the same
+int check_hits(afis_ctx* ctx, const char* who, int n_q, float min_score, int cap, bool outputs, const afis_subjects* s) __attribute__((visibility("hidden")));
+// the ordered form of a score word (minu.hip: ord_f32 without its + 0.0f; subject_rank.hip: sr_ord_f32)
+inline uint32_t ordered_word(float v) { uint32_t b; memcpy(&b, &v, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 
 }  // namespace afis

@@ -264,6 +264,9 @@ hipError_t launch_topk_subjects(const unsigned long long* best, int n_q, int S, 
 constexpr int kRankHitsMax = 4096;                      // AFIS_HITS_MAX: the composites of a list are sorted in LDS (32 KB)
 hipError_t launch_rank_hits(const float* scores, int n_q, int G, const unsigned long long* best, int S, const long long* ids, const long long* d_global, long long index_base,
                             uint32_t thr, int cap, long long* out_n, long long* out_a, float* out_score, long long* out_b, hipStream_t stream);
+// afis_rank_latent_hits (latent_rank.hip): the score matrix in [n_q][n] -> out [n][n_q], 64 x 64 tiles through LDS, both sides coalesced; launch_rank_hits then ranks
+// out's rows — per print the queries — as it ranks a search's
+hipError_t launch_transpose_scores(const float* in, float* out, int n_q, int n, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

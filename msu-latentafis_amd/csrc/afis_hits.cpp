@@ -9,9 +9,6 @@ static_assert(kRankHitsMax == AFIS_HITS_MAX, "rank_hits.hip sorts a list of AFIS
 
 namespace afis {
 
-// the ordered form of a score word (minu.hip: ord_f32 without its + 0.0f; subject_rank.hip: sr_ord_f32)
-static inline uint32_t ordered_word(float v) { uint32_t b; memcpy(&b, &v, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-
 int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int cap, int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b)
 {
     const LastSearch ls = ctx->last_search;
@@ -57,8 +54,8 @@ int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int 
     return AFIS_OK;
 }
 
-// what both entry points ask of the context and of their plain arguments (the order of afis_rank_subjects' checks)
-static int check_hits(afis_ctx* ctx, const char* who, int n_q, float min_score, int cap, bool outputs, const afis_subjects* s)
+// what the hit-list entry points ask of the context and of their plain arguments (the order of afis_rank_subjects' checks)
+int check_hits(afis_ctx* ctx, const char* who, int n_q, float min_score, int cap, bool outputs, const afis_subjects* s)
 {
     const std::string w(who);
     if (cap < 1 || cap > AFIS_HITS_MAX || !outputs || std::isnan(min_score)) return fail(ctx, AFIS_EINVAL, w + ": cap must be 1 .. AFIS_HITS_MAX, min_score a number and every output array given");

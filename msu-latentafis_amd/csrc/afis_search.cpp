@@ -207,18 +207,14 @@ int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup&
     return AFIS_OK;
 }
 
-}  // namespace afis
-
-extern "C" {
-
-int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_q, afis_queries** out)
+// The body of afis_queries_upload (max_templates == 0) and of afis_queries_upload_reserved (afis_reverse.cpp): the launch groups are cut for a shard of G templates — the
+// resident shard's size, or the size the handle is reserved for.
+int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out)
 {
-    if (!ctx || !out || n_q < 0 || (n_q > 0 && !queries)) return fail(ctx, AFIS_EINVAL, "afis_queries_upload: bad argument");
-    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_queries_upload: commit the gallery first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
     // group size: bounded by the option and by the memory budget of a group's per-pair buffers
-    const int64_t G = std::max<int64_t>(1, ctx->gal.G);
+    const int64_t G = max_templates > 0 ? max_templates : std::max<int64_t>(1, ctx->gal.G);
     const int64_t by_mem = std::max<int64_t>(0, group_budget_bytes(ctx) - graph_slab_bytes(INT64_C(1) << 40)) / group_bytes_per_query(ctx, G);
     // latents per launch group: the option, or (0 = auto) as many as keep about five million (latent, rolled) pairs in a launch (round 5; two million before) — 50 at a 100k-template
     // shard, 128 at <= 39k (round 3, a 12.5k-template shard: 100 latents in one launch 310.7 ms, in 64 + 36: 315.1): the persistent per-pair kernels lose their tails once per launch, which shows on small shards (12 launches of 100k pairs
@@ -229,7 +225,7 @@ int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_
     const int64_t want = ctx->query_batch > 0 ? ctx->query_batch : launch_group_latents(G);
     int per = (int)std::max<int64_t>(1, std::min<int64_t>(want, by_mem));
     afis_queries* q = new afis_queries();
-    q->n_q = n_q; q->gallery_epoch = ctx->gallery_epoch;
+    q->n_q = n_q; q->gallery_epoch = ctx->gallery_epoch; q->max_templates = max_templates;
     const int64_t budget = group_budget_bytes(ctx);
     // Launch groups are contiguous runs of at most `per` queries; with the matrix-core bound pass (adc_variant 9) the cuts are placed where its row groups of 768 latent
     // texture rows are fewest (launch_group_cuts, afis_device.h; tests/test_host.py checks the rule on the CPU).  Results do not depend on the cuts.
@@ -268,6 +264,17 @@ int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_
     }
     *out = q;
     return AFIS_OK;
+}
+
+}  // namespace afis
+
+extern "C" {
+
+int afis_queries_upload(afis_ctx* ctx, const afis_template_view* queries, int n_q, afis_queries** out)
+{
+    if (!ctx || !out || n_q < 0 || (n_q > 0 && !queries)) return fail(ctx, AFIS_EINVAL, "afis_queries_upload: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_queries_upload: commit the gallery first");
+    return upload_queries(ctx, queries, n_q, 0, out);
 }
 
 void afis_queries_free(afis_ctx* ctx, afis_queries* q)
@@ -699,7 +706,12 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     if (k < 0 || (k > 0 && (!topk_idx || !topk_score))) return fail(ctx, AFIS_EINVAL, "afis_search: k > 0 needs topk_idx and topk_score");
     // A handle's launch groups were cut for the shard size (and the free memory) of the moment it was uploaded: against a shard that has grown since, a group's per-pair
     // buffers could exceed the budget.  Such a handle is refused; uploading the latents again takes milliseconds.
-    if (q->gallery_epoch != ctx->gallery_epoch)
+    // (a handle of afis_queries_upload_reserved was cut for a shard of max_templates templates: any shard up to that size, whatever edits led to it)
+    if (q->max_templates > 0) {
+        if ((int64_t)ctx->gal.G > q->max_templates)
+            return fail(ctx, AFIS_EINVAL, "afis_search_resident: the resident shard holds " + std::to_string((long long)ctx->gal.G) + " templates, these queries were uploaded for at most " +
+                                              std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
+    } else if (q->gallery_epoch != ctx->gallery_epoch)
         return fail(ctx, AFIS_ESTATE, "afis_search_resident: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these queries were uploaded; free the handle and upload them again");
     return search_shard(ctx, *ctx, nullptr, q, scores, parts, status, k, topk_idx, topk_score);
 }

@@ -114,6 +114,28 @@ int afis_debug_rank_hits(afis_ctx* ctx, afis_subjects* subjects, const float* sc
     return subjects ? afis_rank_subject_hits(ctx, subjects, n_q, min_score, cap, n_hits, out_a, out_score, out_b) : afis_rank_hits(ctx, n_q, min_score, cap, n_hits, out_a, out_score);
 }
 
+// ... and for the column hit lists: afis_rank_latent_hits runs on the uploaded matrix, n_templates = the resident shard's size.
+int afis_debug_rank_latent_hits(afis_ctx* ctx, const float* scores, int n_q, float min_score, int cap, int64_t latent_base, int64_t* n_hits, int64_t* latent_idx, float* score)
+{
+    if (!ctx || !scores || n_q <= 0) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_latent_hits: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_latent_hits: commit the gallery first");
+    { const int rcq = quiesce(ctx, "afis_debug_rank_latent_hits"); if (rcq != AFIS_OK) return rcq; }
+    const int64_t G = ctx->gal.G;
+    if (G > 0) {
+        HIPCHK(ctx, ctx->scores.ensure((size_t)n_q * (size_t)G * 4));
+        HIPCHK(ctx, hipMemcpy(ctx->scores.p, scores, (size_t)n_q * (size_t)G * 4, hipMemcpyHostToDevice));
+    }
+    ctx->last_search = LastSearch{true, n_q, G, nullptr, ctx->gallery_epoch};
+    return afis_rank_latent_hits(ctx, G, min_score, cap, latent_base, n_hits, latent_idx, score);
+}
+
+int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2)
+{
+    if (!ctx || !out2) return fail(ctx, AFIS_EINVAL, "afis_debug_transpose_stats: bad argument");
+    out2[0] = ctx->transpose_us; out2[1] = ctx->transpose_bytes;
+    return AFIS_OK;
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

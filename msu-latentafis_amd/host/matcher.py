@@ -50,10 +50,11 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
-           "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits",
+           "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
-TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits"]
+TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
+               "afis_debug_transpose_stats"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -99,6 +100,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "afis_rank_hits"):                                  # hit lists; absent from older builds compared by tools/lib_ab.py
         lib.afis_rank_hits.argtypes = [vp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp]
         lib.afis_rank_subject_hits.argtypes = [vp, vp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
+    if hasattr(lib, "afis_rank_latent_hits"):                           # reverse search; absent from older builds compared by tools/lib_ab.py
+        lib.afis_queries_upload_reserved.argtypes = [vp, C.POINTER(TemplateView), C.c_int, C.c_int64, C.POINTER(vp)]
+        lib.afis_rank_latent_hits.argtypes = [vp, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -128,6 +132,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_rank_subjects.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp, i64p]
     if hasattr(lib, "afis_debug_rank_hits"):
         lib.afis_debug_rank_hits.argtypes = [vp, vp, fp, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
+    if hasattr(lib, "afis_debug_rank_latent_hits"):
+        lib.afis_debug_rank_latent_hits.argtypes = [vp, fp, C.c_int, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
+        lib.afis_debug_transpose_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     return lib
 
 
@@ -184,6 +191,8 @@ class Matcher:
             raise AfisError(f"afis_create failed ({rc}): {self.lib.afis_last_error(None).decode()}")
         self.gallery_files: List[str] = []
         self.last_n_q = 0                                                  # queries of the last search call made through this object (rank_hits / rank_subject_hits default to it)
+        self.last_n_templates = 0                                          # ... and the templates (columns) it covered (rank_latent_hits' rows)
+        self.index_base = 0
 
     def device_info(self, device: int) -> dict:
         """What the HIP runtime says about a device (afis_device_info): name, PCI bus id, UUID, compute units."""
@@ -272,6 +281,7 @@ class Matcher:
 
     def gallery_commit(self, index_base: int = 0):
         self._chk(self.lib.afis_gallery_commit(self.ctx, index_base))
+        self.index_base = index_base                                       # the shard's: an appending commit must name it again (reverse_search does)
 
     def gallery_reopen(self):
         """Open a staging area beside the committed shard: the gallery_add* / gallery_load calls work again, and the next gallery_commit appends what they staged
@@ -330,7 +340,7 @@ class Matcher:
         v = _Views(latents)
         scores, parts, status, ti, ts, args = self._alloc(v.n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search(self.ctx, v.arr, v.n, *args))
-        self.last_n_q = v.n
+        self.last_n_q = v.n; self.last_n_templates = self.resident_size
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def search_dat(self, bufs: Sequence[bytes], k: int = 24, want_scores: bool = True, want_parts: bool = False):
@@ -339,7 +349,7 @@ class Matcher:
         lens = (C.c_size_t * max(1, n))(*[len(b) for b in bufs])
         scores, parts, status, ti, ts, args = self._alloc(n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search_dat(self.ctx, arr, lens, n, *args))
-        self.last_n_q = n
+        self.last_n_q = n; self.last_n_templates = self.resident_size
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def rank_list(self, scores, k: int = 24, ref_order: bool = False):
@@ -350,17 +360,22 @@ class Matcher:
         self._chk(self.lib.afis_rank_list(_ptr(s, C.c_float) if len(s) else None, C.c_int64(len(s)), C.c_int(int(ref_order)), C.c_int(k), _ptr(idx, C.c_int64), _ptr(sc, C.c_float)))
         return idx[:k], sc[:k]
 
-    def upload_queries(self, latents: Sequence[FPTemplate]):
+    def upload_queries(self, latents: Sequence[FPTemplate], reserve: Optional[int] = None):
+        """Latents resident on the device -> handle for search_resident / search_subset_resident.  reserve=N (afis_queries_upload_reserved): the launch groups are cut for
+        a shard of N templates, and the handle stays valid through gallery edits for every shard or subset of at most N templates (reverse_search)."""
         v = _Views(latents)
         h = C.c_void_p()
-        self._chk(self.lib.afis_queries_upload(self.ctx, v.arr, v.n, C.byref(h)))
+        if reserve is None:
+            self._chk(self.lib.afis_queries_upload(self.ctx, v.arr, v.n, C.byref(h)))
+        else:
+            self._chk(self.lib.afis_queries_upload_reserved(self.ctx, v.arr, v.n, int(reserve), C.byref(h)))
         return (h, v.n)
 
     def search_resident(self, handle, k: int = 24, want_scores: bool = False, want_parts: bool = False):
         h, n = handle
         scores, parts, status, ti, ts, args = self._alloc(n, k, want_scores, want_parts)
         self._chk(self.lib.afis_search_resident(self.ctx, h, *args))
-        self.last_n_q = n
+        self.last_n_q = n; self.last_n_templates = self.resident_size
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     # ---- subset search: a candidate list of the resident shard ---------------------------------------------------
@@ -381,7 +396,7 @@ class Matcher:
         v = _Views(latents)
         scores, parts, status, ti, ts, args = self._alloc(v.n, k, want_scores, want_parts, G=n)
         self._chk(self.lib.afis_search_subset(self.ctx, h, v.arr, v.n, *args))
-        self.last_n_q = v.n
+        self.last_n_q = v.n; self.last_n_templates = n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     def search_subset_resident(self, handle, qhandle, k: int = 24, want_scores: bool = False, want_parts: bool = False):
@@ -389,7 +404,7 @@ class Matcher:
         qh, nq = qhandle
         scores, parts, status, ti, ts, args = self._alloc(nq, k, want_scores, want_parts, G=n)
         self._chk(self.lib.afis_search_subset_resident(self.ctx, h, qh, *args))
-        self.last_n_q = nq
+        self.last_n_q = nq; self.last_n_templates = n
         return {"scores": scores, "parts": parts, "status": status, "topk_idx": ti, "topk_score": ts}
 
     # ---- subject rank lists: the last search's scores grouped by enrolled person ---------------------------------
@@ -442,9 +457,58 @@ class Matcher:
     def debug_rank_hits(self, handle, scores: np.ndarray, min_score: float, cap: int):
         """rank_hits (handle None) or rank_subject_hits over a caller-made [n_q][G] score matrix for the resident shard (parity tap); the matrix stays rankable."""
         s = np.ascontiguousarray(scores, np.float32)
-        self.last_n_q = s.shape[0]
+        self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
         return self._hit_lists(lambda nq, nh, a, sc, b: self._tap("afis_debug_rank_hits")(self.ctx, handle[0] if handle is not None else None, _ptr(s, C.c_float), nq, min_score, cap, nh, a, sc, b),
                                s.shape[0], cap, handle is not None)
+
+    # ---- reverse search: the last search's matrix ranked along its columns -----------------------------------------
+    def _latent_lists(self, fn, n_templates: int, cap: int):
+        c = max(cap, 0)
+        nh = np.empty(n_templates, np.int64); li = np.empty((n_templates, c), np.int64); sc = np.empty((n_templates, c), np.float32)
+        self._chk(fn(n_templates, _ptr(nh, C.c_int64), _ptr(li, C.c_int64), _ptr(sc, C.c_float)))
+        return {"n_hits": nh, "latent": li, "score": sc}
+
+    def rank_latent_hits(self, min_score: float, cap: int, latent_base: int = 0, n_templates: Optional[int] = None):
+        """Of the LAST search, per template it covered (a subset's listed templates in the caller's order, or the resident shard's) every query whose score reaches
+        min_score: n_hits [n] how many (it may exceed cap), latent / score [n][cap] the best min(n_hits, cap) of them — latent_base + the query's position, score
+        descending, equal scores by ascending position — padded with (-1, -inf).  n_templates defaults to the columns of the last search call made through this object."""
+        n = self.last_n_templates if n_templates is None else n_templates
+        return self._latent_lists(lambda nt, nh, li, sc: self.lib.afis_rank_latent_hits(self.ctx, nt, min_score, cap, latent_base, nh, li, sc), n, cap)
+
+    def rank_latents(self, k: int, latent_base: int = 0, n_templates: Optional[int] = None):
+        """The k best latents of every template the last search covered: rank_latent_hits with min_score = -inf, without the counts."""
+        r = self.rank_latent_hits(-np.inf, k, latent_base, n_templates)
+        return {"latent": r["latent"], "score": r["score"]}
+
+    def debug_rank_latent_hits(self, scores: np.ndarray, min_score: float, cap: int, latent_base: int = 0):
+        """rank_latent_hits over a caller-made [n_q][G] score matrix for the resident shard (parity tap); the matrix stays rankable."""
+        s = np.ascontiguousarray(scores, np.float32)
+        self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
+        return self._latent_lists(lambda nt, nh, li, sc: self._tap("afis_debug_rank_latent_hits")(self.ctx, _ptr(s, C.c_float), s.shape[0], min_score, cap, latent_base, nh, li, sc),
+                                  s.shape[1], cap)
+
+    def transpose_stats(self):
+        """(device microseconds, bytes read and written) of the transpose of the last rank_latent_hits (parity tap)."""
+        out = (C.c_longlong * 2)()
+        self._chk(self._tap("afis_debug_transpose_stats")(self.ctx, out))
+        return int(out[0]), int(out[1])
+
+    def reverse_search(self, qhandle, templates: Sequence[FPTemplate], min_score: float, cap: int, latent_base: int = 0):
+        """One card of the reverse search: the rolled `templates` are appended to the resident shard (reopen, add, commit with the shard's index_base), and the latents
+        of `qhandle` — upload_queries(..., reserve=N) with N >= len(templates) — are searched against them alone.  -> (the new templates' global indices, the
+        rank_latent_hits lists with one row per new template)."""
+        first = self.index_base + self.resident_size
+        self.gallery_reopen()
+        self.gallery_add(templates)
+        self.gallery_commit(self.index_base)
+        idx = np.arange(first, first + len(templates), dtype=np.int64)
+        sub = self.subset_create(idx)
+        try:
+            self.search_subset_resident(sub, qhandle, k=0)
+            lists = self.rank_latent_hits(min_score, cap, latent_base)
+        finally:
+            self.subset_free(sub)
+        return idx, lists
 
     def correspondences(self, latent: FPTemplate, gallery_idx: Sequence[int]):
         """Surviving minutiae correspondences (matcher.cpp:497-505) of one latent against each listed gallery template:

@@ -89,9 +89,44 @@ def merge_subject_topk(ids: np.ndarray, score: np.ndarray, best_idx: np.ndarray,
 def merge_hits(n_hits: np.ndarray, idx: np.ndarray, score: np.ndarray, cap: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """n_hits: [R, Q], idx, score: [R, Q, kk] per-rank hit lists (Matcher.rank_hits with one min_score on every rank's shard; kk >= cap).  Returns (n_hits [Q], idx [Q, cap],
     score [Q, cap]): the counts add — a template lies in one shard — and the list is the merge on score descending, then global index ascending, cut at cap.  Exact: every
-    rank's list is the best-kk prefix of what qualifies in its shard, so an entry among the cap best of the union is among the kk best of its own shard."""
+    rank's list is the best-kk prefix of what qualifies in its shard, so an entry among the cap best of the union is among the kk best of its own shard.
+
+    The column lists of a reverse search (Matcher.rank_latent_hits: Q = the prints searched, the entries are latents) merge by this same function when the LATENTS are
+    split — over ranks, or over several query handles of one rank searched one after the other, each with its latent_base: the columns are common to every part, a
+    latent lies in one part, so the counts add, and the list is the merge on score descending, then latent index ascending; exact for the reason above."""
     out_i, out_s = merge_topk(idx, score, cap)
     return np.asarray(n_hits, np.int64).sum(axis=0), out_i, out_s
+
+
+def merge_prints_to_card(n_hits: np.ndarray, latent: np.ndarray, score: np.ndarray, cap: int):
+    """n_hits: [P], latent, score: [P, kk] — the column lists of the P prints of ONE card (Matcher.rank_latent_hits with one min_score; row p = print position p;
+    latent -1 = padding; kk >= cap).  Returns (latent [cap], score [cap], print_pos [cap], n_latents, truncated): per latent its greatest score over the card's prints — on
+    equal scores the lowest print position — then score descending, latent index ascending, cut at cap and padded with (-1, -inf, -1).  print_pos says which print of
+    the card the entry's score belongs to.
+
+    Exact for kk >= cap: a latent's card score is the maximum of its per-print scores, reached at some print p.  If the latent is among the card's cap best, fewer than
+    cap latents rank before it on the card (greater score, or equal score and lower index); every latent that ranks before it INSIDE p's list does so with a per-print
+    score no greater than its own card score, hence ranks before it on the card too — so the latent is among the cap best of the print where it reaches its maximum and
+    arrives with its true score.  An entry that arrives only with a lower score, from prints where the latent stays below its maximum while p's list was full, belongs
+    to a latent that cap others outrank in p, all of them ahead of it on the card: it cannot be among the cap best and cannot displace one of them.
+    The per-print counts do not add, for one latent may qualify against several prints of the card: n_latents is the number of distinct latents in the input.  That is
+    the exact count while every print handed over all its hits; truncated is true when a print reported n_hits > kk, and only then is the count a lower bound
+    (merge_subject_hits' rule)."""
+    li = np.asarray(latent, np.int64)
+    P, kk = li.shape
+    fs = np.asarray(score, np.float32).reshape(P * kk)
+    fp = np.repeat(np.arange(P, dtype=np.int64), kk)
+    fl = li.reshape(P * kk)
+    valid = fl >= 0
+    vl, vs, vp = fl[valid], fs[valid], fp[valid]
+    order = np.lexsort((vp, -vs.astype(np.float64), vl))                    # by latent; inside a latent the greater score, then the lower print position, comes first
+    first = np.ones(len(order), bool); first[1:] = vl[order][1:] != vl[order][:-1]
+    keep = order[first]
+    vl, vs, vp = vl[keep], vs[keep], vp[keep]
+    order = np.lexsort((vl, -vs.astype(np.float64)))[:cap]                  # score descending, then latent index ascending
+    out_l = np.full(cap, -1, np.int64); out_s = np.full(cap, -np.inf, np.float32); out_p = np.full(cap, -1, np.int64)
+    out_l[:len(order)] = vl[order]; out_s[:len(order)] = vs[order]; out_p[:len(order)] = vp[order]
+    return out_l, out_s, out_p, int(len(vl)), bool((np.asarray(n_hits, np.int64) > kk).any())
 
 
 def merge_subject_hits(n_hits: np.ndarray, subject: np.ndarray, score: np.ndarray, best_idx: np.ndarray, cap: int):

@@ -1,6 +1,7 @@
 """A/B of several builds of libafis_hip.so inside ONE process on ONE box (box-to-box clock differences are several per cent, larger than
 most kernel changes): python tools/lib_ab.py [G] [Q] <other .so> ...   — every library scores the same workload `reps` times,
-interleaved; prints the minimum stage times and whether the scores are bit-identical to the first library's."""
+interleaved; prints the minimum stage times and whether the scores are bit-identical to the first library's, then per library every kept step's total_ms with
+its median and spread (max - min), and whether the first library's median lies inside each other library's [min, max]."""
 import sys, importlib, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,7 +21,7 @@ for path in paths:
         m.set_option(kv.split("=")[0], int(kv.split("=")[1]))
     m.gallery_add_packed(gal); m.gallery_commit(0)
     ms.append((m, m.upload_queries(lats)))
-ref = None; best = [None] * len(paths)
+ref = None; best = [None] * len(paths); totals = [[] for _ in paths]
 for rep in range(4):
     for i, (m, qh) in enumerate(ms):
         r = m.search_resident(qh, want_scores=True); tm = m.timing()
@@ -29,5 +30,10 @@ for rep in range(4):
         if rep:                                                             # first round = warm-up
             best[i] = tm if best[i] is None else {k: min(best[i][k], v) if k.endswith("_ms") else v for k, v in tm.items()}
             best[i]["identical"] = same
+            totals[i].append(round(tm["total_ms"], 2))
 for p, b in zip(paths, best):
     print(os.path.basename(p), {k: round(v, 2) for k, v in b.items() if k.endswith("_ms")}, {k: v for k, v in b.items() if k.startswith("minu_") and k.endswith("tasks") or k.endswith("_ghz")}, "identical", b["identical"])
+import statistics
+for p, t in zip(paths, totals):
+    print(os.path.basename(p), "total_ms per step", t, "median", statistics.median(t), "spread", round(max(t) - min(t), 2),
+          "" if p == paths[0] else "first library's median inside this spread: %s" % (min(t) <= statistics.median(totals[0]) <= max(t)))
