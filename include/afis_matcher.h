@@ -165,7 +165,10 @@ int afis_gallery_export(afis_ctx* ctx, const char* path, const char* const* name
  *                                  (or for every entry of a latent-empty query)
  *   parts       [n_q][G][4] or NULL : s0, s1, s2 (latent minutiae templates 26, 2, 11) and the texture score
  *   status      [n_q] or NULL    : AFIS_QUERY_*
- *   k, topk_idx [n_q][k], topk_score [n_q][k] : rank list, score descending, ties by ascending index
+ *   k, topk_idx [n_q][k], topk_score [n_q][k] : rank list, sorted on the key rank_key(score) = the bits of score + 0.0f in their total order (csrc/rank_order.h; the
+ *                                  device's list for k <= 64 and the host's beyond sort on it alike), descending, equal keys by ascending global index: on the scores
+ *                                  a search produces plainly score descending, ties by ascending index; a NaN stands where its bits put it, above +inf with the
+ *                                  sign clear and below -inf with it set, and moves no other entry
  *                                  (the reference's tie order is unspecified, matcher.cpp:306-309 — a caller that wants the
  *                                  binary's order of EQUAL scores passes the score column to afis_rank_list(..., ref_order 1), as match -l -tie does); padded with
  *                                  idx -1 when k > G.  k = 0 skips it. */
@@ -273,8 +276,9 @@ int afis_rank_subjects(afis_ctx* ctx, afis_subjects* s, int n_q, int k,
  * for templates the bits of score + 0.0f in their total order (min_score gets the same + 0.0f, so the two zeros are one value; equal scores by ascending global index,
  * also for a subset listed out of order), for subjects the raw bits of the subject's best score in their total order (-0.0 below +0.0; equal scores by ascending subject
  * id; a subject none of whose templates the search covered is no entry and is not counted).  A NaN orders where its bits put it: above +inf with the sign clear, below
- * -inf — and so below every min_score — with it set.  On the scores a search produces, -1 or a finite value >= +0.0, both rules are plainly score >= min_score.
- * min_score = -INFINITY turns the call into a rank list of length cap: entry for entry afis_search's top-k, or afis_rank_subjects' list.
+ * -inf — and so below every min_score — with it set; afis_search's lists of every k, afis_rank_list and the merges of the per-rank lists sort on the same key.  On the scores a search produces, -1 or a finite value >= +0.0, both rules are plainly score >= min_score.
+ * min_score = -INFINITY turns the call into a rank list of length cap: entry for entry afis_search's top-k, or afis_rank_subjects' list (short of NaNs with the sign
+ * set, which stand at the tail of those lists and, lying below -inf, are padding here).
  * Which searches count, what invalidates the matrix and what leaves it alone are exactly as for afis_rank_subjects: AFIS_ESTATE when there is no matrix to rank or the
  * subject handle belongs to an older gallery; AFIS_EINVAL when n_q is not the last search's, the handle is not live, an output is null, cap is outside
  * 1 .. AFIS_HITS_MAX (the list is sorted in the workgroup's local memory) or min_score is a NaN.  Both calls leave the matrix rankable: they may be repeated with other
@@ -342,10 +346,13 @@ int afis_gallery_file_names(const char* path, int64_t first, int64_t count, char
  *   query_status  NULL or out : AFIS_QUERY_LATENT_EMPTY when the latent has no template at all (:345-348) */
 int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, float* scores, int32_t* rolled_status, int32_t* query_status);
 
-/* The rank list of One2List_matching, matcher.cpp:306-309, from a score column (host memory, no device work): idx[0 .. k) / sc[0 .. k) = the k best of scores[0 .. n), score descending.
- * ref_order 0: equal scores by ascending index (what afis_search's own top-k delivers); 1: the reference's statement itself — std::sort of the indices 0 .. n-1 on the non-strict
- * comparator scores[a] > scores[b], with this library's libstdc++ — so that equal scores (the zero scores at the tail of a small gallery's list) come out in the order the reference
- * binary leaves them.  k > n: the rest is padded with idx -1, sc 0.  sc may be NULL. */
+/* The rank list of One2List_matching, matcher.cpp:306-309, from a score column (host memory, no device work): idx[0 .. k) / sc[0 .. k) = the k best of scores[0 .. n), descending
+ * in afis_search's key rank_key(score) (csrc/rank_order.h: the bits of score + 0.0f in their total order; on a NaN-free column that is score descending).
+ * ref_order 0: equal keys by ascending index (what afis_search's own top-k delivers); 1: the reference's statement itself — std::sort of the indices 0 .. n-1 on a non-strict
+ * "greater" comparator, with this library's libstdc++ — so that equal scores (the zero scores at the tail of a small gallery's list) come out in the order the reference
+ * binary leaves them.  The comparison is rank_key(scores[a]) > rank_key(scores[b]): for every pair of a NaN-free column the outcome of the reference's scores[a] > scores[b],
+ * hence the same permutation, and a strict weak order on every column — a NaN score (the reference's own sort is undefined behaviour there) takes the place its key gives
+ * it and leaves the other entries in order.  k > n: the rest is padded with idx -1, sc 0.  sc may be NULL. */
 int afis_rank_list(const float* scores, int64_t n, int ref_order, int k, int64_t* idx, float* sc);
 
 /* PQ encoder — replaces TrainedPQEncoder.encode_multi (extraction/descriptor_PQ.py:19-27, scipy.cluster.vq.vq per

@@ -58,6 +58,14 @@ int afis_debug_rank_hits(afis_ctx* ctx, afis_subjects* subjects, const float* sc
  * resident shard), then ranked by the entry point itself with n_templates = the resident shard's size.  The matrix stays rankable afterwards. */
 int afis_debug_rank_latent_hits(afis_ctx* ctx, const float* scores /*[n_q][G]*/, int n_q, float min_score, int cap, int64_t latent_base,
                                 int64_t* n_hits /*[G]*/, int64_t* latent_idx /*[G][cap]*/, float* score /*[G][cap]*/);
+/* The rank list of afis_search* (topk_idx / topk_score) over a caller-made score matrix: scores [n_q][n] is uploaded in place of the matrix a search leaves, marked valid as
+ * a full search (subset == NULL: n = the resident shard's size, column j = template index_base + j) or a subset search of n_q queries marks it, and listed by the code
+ * the search itself runs: for k <= 64 the rank-list kernel with the base the search passes, then the subset's index map; for k > 64 the host's list over the columns in the
+ * order the search hands it (the caller's order of the subset's list, restored on the device when the subset was listed out of order).
+ * For a subset the caller supplies the columns in the order the device holds them: column t belongs to the t-th SMALLEST listed index (n = the subset's size).
+ * k >= 1.  Outputs as afis_search's, padding (-1, -inf) included.  The matrix stays rankable afterwards (afis_rank_hits, afis_rank_subjects, afis_rank_latent_hits). */
+int afis_debug_rank_rows(afis_ctx* ctx, afis_subset* subset, const float* scores /*[n_q][n]*/, int n_q, int k,
+                         int64_t* topk_idx /*[n_q][k]*/, float* topk_score /*[n_q][k]*/);
 /* The transpose of the last afis_rank_latent_hits (latent_rank.hip: k_transpose_scores): out2[0] = its device time in microseconds (a pair of HIP events of its own),
  * out2[1] = the bytes it read and wrote; both 0 when that call queued nothing.  tools/reverse_search_timing.py turns them into bytes per second. */
 int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2);

@@ -293,6 +293,9 @@ int drain_abandoned(afis_ctx* ctx, bool keep_last_search = false);   // waits (b
 // The launch sequence of a search over one shard: the context's resident one (sub == NULL, sh == *ctx) or a subset's (sh == sub->sh).  afis_search_resident and
 // afis_search_subset_resident check their handles and call it.
 int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score);
+// The host's rank lists (k > kDeviceTopK) of a score matrix [n_q][G] whose column j is template col[j] (a subset in the caller's order) or index_base + j (col == NULL);
+// the parity tap afis_debug_rank_rows runs it too.  Hidden, as rank_subjects below.
+void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* col, int64_t index_base, int64_t* topk_idx, float* topk_score) __attribute__((visibility("hidden")));
 size_t subset_device_bytes(const afis_ctx* ctx);       // option subset_device_bytes: what the live subsets hold on the device
 void release_subset(afis_subset* s);                   // its device buffers and the handle itself (afis_subset.cpp)
 // afis_queries_upload (max_templates == 0: the launch groups are cut for the resident shard's size) and afis_queries_upload_reserved (afis_reverse.cpp: for a shard of

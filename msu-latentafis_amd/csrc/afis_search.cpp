@@ -2,6 +2,7 @@
 // shard (the body of the reference's OpenMP gallery loop, matching/matcher.cpp:168-190 == :273-295, for a batch of latents), rank lists, correspondence export
 // (matcher.cpp:321-327) and the all-templates mode (matcher.cpp:339-374).  Kernels: adc*.hip, minu.hip, graph.hip.
 #include "afis_ctx.h"
+#include "rank_order.h"
 
 using namespace afis;
 
@@ -476,6 +477,14 @@ static int collect_timing(afis_ctx* ctx, const Shard& sh, const afis_queries* q,
     return AFIS_OK;
 }
 
+// The rank lists of k > kDeviceTopK (or of an empty gallery), on the host: per row of sc [n_q][G] the k best on k_topk's key (rank_order.h), padded with (-1, -inf).
+// col != NULL: a subset's columns stand in the caller's order, col[j] the global index of column j — equal keys go by the column's GLOBAL index.
+void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* col, int64_t index_base, int64_t* topk_idx, float* topk_score)
+{
+    for (int i = 0; i < n_q; ++i)
+        rank_topk(G > 0 ? sc + (size_t)i * G : nullptr, G, k, col, index_base, topk_idx + (size_t)i * k, topk_score + (size_t)i * k);
+}
+
 // The launch sequence of a search over the shard `sh`: the context's resident one (sub == NULL) or a subset's (sh == sub->sh, whose templates stand in ascending global
 // index order).  One body for both: group loop, overlapped schedule, buffer sizing before queuing, timing, deadlines.  What a subset adds lies at the two ends — the
 // rank-list kernel's positions are mapped to global indices, and the score / part columns go to the caller's order (on the device, so that they are copied once).
@@ -671,22 +680,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
         HIPCHK(ctx, hipMemcpy(h_sc, out_scores, (size_t)nq_all * G * 4, hipMemcpyDeviceToHost));
     }
     { const int rct = collect_timing(ctx, sh, q, tm, dev_topk, evk); if (rct != AFIS_OK) return rct; }
-    if (host_topk) {                                                       // k > kDeviceTopK (or an empty gallery)
-        std::vector<int32_t> ind((size_t)G);
-        const int64_t* col = sub ? sub->idx.data() : nullptr;               // a subset's columns stand in the caller's order: equal scores by the column's GLOBAL index
-        for (int i = 0; i < nq_all; ++i) {
-            const float* sc = G > 0 ? h_sc + (size_t)i * G : nullptr;
-            std::iota(ind.begin(), ind.end(), 0);
-            const int kk = (int)std::min<int64_t>(k, G);
-            if (col) std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [sc, col](int a, int b) { return sc[a] > sc[b] || (sc[a] == sc[b] && col[a] < col[b]); });
-            else std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [sc](int a, int b) { return sc[a] > sc[b] || (sc[a] == sc[b] && a < b); });
-            for (int r = 0; r < k; ++r) {
-                const size_t o = (size_t)i * k + r;
-                if (r < kk) { topk_idx[o] = col ? col[ind[r]] : sh.index_base + ind[r]; topk_score[o] = sc[ind[r]]; }
-                else { topk_idx[o] = -1; topk_score[o] = -INFINITY; }
-            }
-        }
-    }
+    if (host_topk) host_rank_rows(h_sc, nq_all, G, k, sub ? sub->idx.data() : nullptr, sh.index_base, topk_idx, topk_score);   // k > kDeviceTopK (or an empty gallery)
     tm.launch_groups = (int32_t)n_groups;
     for (const QueryGroup& grp : q->groups) tm.overlapped_groups += grp.overlapped ? 1 : 0;
     ctx->timing = tm;

@@ -129,6 +129,52 @@ int afis_debug_rank_latent_hits(afis_ctx* ctx, const float* scores, int n_q, flo
     return afis_rank_latent_hits(ctx, G, min_score, cap, latent_base, n_hits, latent_idx, score);
 }
 
+// ... and for the rank list of afis_search* itself: the matrix [n_q][n] over the resident shard (sub == NULL) or over a subset's sub-shard — its columns in the order the
+// sub-shard holds them, ascending global index — is uploaded and marked valid as that search marks it, then listed by the code at the end of search_shard: k_topk with the
+// base the search passes (and the subset's index map) for k <= kDeviceTopK, host_rank_rows on the caller's column order (launch_permute_columns for a subset listed out
+// of order) beyond.
+int afis_debug_rank_rows(afis_ctx* ctx, afis_subset* sub, const float* scores, int n_q, int k, int64_t* topk_idx, float* topk_score)
+{
+    if (!ctx || !scores || n_q <= 0 || k <= 0 || !topk_idx || !topk_score) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_rows: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_rows: commit the gallery first");
+    if (sub && std::find(ctx->subsets.begin(), ctx->subsets.end(), sub) == ctx->subsets.end()) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_rows: not a live subset of this context");
+    if (sub && sub->gallery_epoch != ctx->gallery_epoch) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_rows: the gallery was edited after this subset was created");
+    { const int rcq = quiesce(ctx, "afis_debug_rank_rows"); if (rcq != AFIS_OK) return rcq; }
+    const Shard& sh = sub ? sub->sh : *ctx;
+    const int64_t G = sh.gal.G;
+    const size_t n_out = (size_t)n_q * (size_t)k, bytes = (size_t)n_q * (size_t)G * 4;
+    hipStream_t s = ctx->stream;
+    if (G > 0) {
+        HIPCHK(ctx, ctx->scores.ensure(bytes));
+        HIPCHK(ctx, hipMemcpy(ctx->scores.p, scores, bytes, hipMemcpyHostToDevice));
+    }
+    ctx->last_search = LastSearch{true, n_q, G, sub, ctx->gallery_epoch};
+    if (k <= kDeviceTopK && G > 0) {
+        HIPCHK(ctx, ctx->topk_idx.ensure(n_out * 8)); HIPCHK(ctx, ctx->topk_score.ensure(n_out * 4));
+        HIPCHK(ctx, launch_topk(ctx->scores.as<float>(), n_q, (int)G, k, sub ? 0ll : (long long)sh.index_base, ctx->topk_idx.as<long long>(), ctx->topk_score.as<float>(), s));
+        if (sub) HIPCHK(ctx, launch_subset_topk_map(ctx->topk_idx.as<long long>(), (long long)n_out, sub->d_global.as<long long>(), (int)G, s));
+        HIPCHK(ctx, hipMemcpyAsync(topk_idx, ctx->topk_idx.p, n_out * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(topk_score, ctx->topk_score.p, n_out * 4, hipMemcpyDeviceToHost, s));
+        const int rcw = wait_streams(ctx, {s}, "afis_debug_rank_rows");
+        if (rcw != AFIS_OK) ctx->last_search.valid = false;
+        return rcw;
+    }
+    std::vector<float> h((size_t)n_q * (size_t)G);
+    if (G > 0) {
+        const void* src = ctx->scores.p;
+        if (sub && !sub->identity) {
+            HIPCHK(ctx, ctx->out_perm.ensure(bytes));
+            HIPCHK(ctx, launch_permute_columns(ctx->scores.p, ctx->out_perm.p, 4, n_q, (int)G, sub->d_pos.as<int32_t>(), s));
+            src = ctx->out_perm.p;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(h.data(), src, bytes, hipMemcpyDeviceToHost, s));
+        const int rcw = wait_streams(ctx, {s}, "afis_debug_rank_rows");
+        if (rcw != AFIS_OK) { ctx->last_search.valid = false; return rcw; }
+    }
+    host_rank_rows(h.data(), n_q, G, k, sub ? sub->idx.data() : nullptr, sh.index_base, topk_idx, topk_score);
+    return AFIS_OK;
+}
+
 int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2)
 {
     if (!ctx || !out2) return fail(ctx, AFIS_EINVAL, "afis_debug_transpose_stats: bad argument");

@@ -7,7 +7,8 @@
 //   match_selftest -selftest-allgather                       AFIS_EXCHANGE=tcp all-gather + the agreement point, N local ranks
 //   match_selftest -selftest-groups <rows file> -per N [-plain]   the launch-group rule (afis_device.h: launch_group_cuts / launch_group_latents): cut positions for the listed latent texture row counts
 //   match_selftest -selftest-offsets <counts file>          the gallery's derived offset tables (afis_offsets.h: derived_offsets) for the listed (minutiae, texture point) counts per template
-//   match_selftest -selftest-classes                         the candidate kernel's shape-class rule (afis_device.h: rt_max_rows) as a table: nR  L1 L2 L4  stride1 stride2 stride4
+//   match_selftest -selftest-merge <file>                    the exchange's merge of per-rank rank lists (rank_exchange.cpp: merge_topk) on gathered idx / score words
+//   match_selftest -selftest-classes                        the candidate kernel's shape-class rule (afis_device.h: rt_max_rows) as a table: nR  L1 L2 L4  stride1 stride2 stride4
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -89,7 +90,22 @@ int main(int argc, char** argv)
         for (const auto& b : shard_bounds((int64_t)wts.size(), none, world)) std::cout << b.first << " " << b.second << std::endl;
         return 0;
     }
-    if (args.cmdOptionExists("-selftest-allgather")) {                          // tcp all-gather of rank-dependent blocks, then world_agree
+    if (args.cmdOptionExists("-selftest-merge")) {                              // the exchange's merge (no GPU): "world k k_out", then world * k lines "idx score-word-in-hex"; prints k_out such lines
+        std::ifstream f(args.getCmdOption("-selftest-merge"));
+        int world = 0, k = 0, k_out = 0;
+        if (!(f >> world >> k >> k_out) || world < 1 || k < 0 || k_out < 0) { std::cerr << "match_selftest: bad merge file" << std::endl; return 2; }
+        std::vector<int64_t> idx((size_t)world * k), out_i; std::vector<float> sc((size_t)world * k), out_s;
+        for (size_t i = 0; i < idx.size(); ++i) {
+            long long v; std::string w;
+            if (!(f >> v >> w)) { std::cerr << "match_selftest: short merge file" << std::endl; return 2; }
+            const uint32_t bits = (uint32_t)strtoul(w.c_str(), nullptr, 16);
+            idx[i] = v; memcpy(&sc[i], &bits, 4);
+        }
+        merge_topk(idx, sc, world, k, k_out, out_i, out_s);
+        for (size_t r = 0; r < out_i.size(); ++r) { uint32_t bits; memcpy(&bits, &out_s[r], 4); std::cout << out_i[r] << " " << std::hex << bits << std::dec << std::endl; }
+        return 0;
+    }
+    if (args.cmdOptionExists("-selftest-allgather")) {                         // tcp all-gather of rank-dependent blocks, then world_agree
         RankWorld w; world_from_env(w);
         std::string err;
         setenv("AFIS_EXCHANGE", "tcp", 1);

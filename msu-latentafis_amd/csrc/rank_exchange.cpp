@@ -1,5 +1,6 @@
 // rank_exchange.cpp — see rank_exchange.h.  Host code: HIP runtime for the staging buffers, RCCL for the one collective.
 #include "rank_exchange.h"
+#include "rank_order.h"
 
 #include <arpa/inet.h>
 #include <hip/hip_runtime.h>
@@ -250,7 +251,7 @@ void merge_topk(const std::vector<int64_t>& idx, const std::vector<float>& score
 {
     std::vector<size_t> ord;
     for (size_t i = 0; i < (size_t)world * k; ++i) if (idx[i] >= 0) ord.push_back(i);
-    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return score[a] > score[b] || (score[a] == score[b] && idx[a] < idx[b]); });
+    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rank_before(score[a], idx[a], score[b], idx[b]); });    // the per-rank lists' own order (rank_order.h): a strict weak order whatever bits the scores hold
     out_idx.assign((size_t)k_out, -1); out_score.assign((size_t)k_out, -INFINITY);
     for (size_t r = 0; r < ord.size() && r < (size_t)k_out; ++r) { out_idx[r] = idx[ord[r]]; out_score[r] = score[ord[r]]; }
 }

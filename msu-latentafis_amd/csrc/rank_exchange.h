@@ -45,7 +45,7 @@ void world_finalize(RankWorld& w);
 // empty, by template count — the same cut rule as msu-latentafis_amd/host/sharding.py::shard_bounds
 std::vector<std::pair<int64_t, int64_t>> shard_bounds(int64_t G, const std::vector<int32_t>& weights, int world);
 
-// merge of per-rank top-k lists (rank-major [world][k]; idx < 0 = padding): score descending, index ascending
+// merge of per-rank top-k lists (rank-major [world][k]; idx < 0 = padding) in the lists' own order (rank_order.h): rank_key(score) descending, index ascending
 void merge_topk(const std::vector<int64_t>& idx, const std::vector<float>& score, int world, int k, int k_out,
                 std::vector<int64_t>& out_idx, std::vector<float>& out_score);
 

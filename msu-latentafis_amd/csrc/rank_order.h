@@ -1,0 +1,68 @@
+// rank_order.h — the order of a rank list, stated once for every host path that makes or merges one.  Standard library only: usable from g++ alone.
+//
+// A template rank list is sorted on rank_key(score), descending; equal keys go by ascending GLOBAL index.  rank_key is minu.hip::ord_f32 — the key k_topk
+// (afis_search*, k <= 64) and rank_hits.hip (afis_rank_hits, afis_rank_latent_hits) sort on — so every path lists the same entries whatever bits the scores
+// hold: the two zeros are one value, and a NaN stands where its bits put it (above +inf with the sign clear, below -inf with it set) instead of breaking the
+// strict weak order a float comparison needs.  On NaN-free scores key order IS float order (a > b  <=>  rank_key(a) > rank_key(b), a == b  <=>  equal keys),
+// so nothing changes there.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+namespace afis {
+
+// the ordered bits of s + 0.0f (-0.0 -> +0.0, so that equal floats get equal keys)
+inline uint32_t rank_key(float s)
+{
+    s = s + 0.0f;
+    uint32_t w;
+    memcpy(&w, &s, 4);
+    return (w & 0x80000000u) ? ~w : (w | 0x80000000u);
+}
+
+// "entry a stands before entry b" of a rank list: a strict total order while no global index repeats
+inline bool rank_before(float score_a, int64_t idx_a, float score_b, int64_t idx_b)
+{
+    const uint32_t ka = rank_key(score_a), kb = rank_key(score_b);
+    return ka > kb || (ka == kb && idx_a < idx_b);
+}
+
+// The k best of sc[0 .. n) in rank-list order: out_idx[r] = the global index of entry r — col[position] with a column-to-global-index table (a subset's
+// columns in the caller's order), index_base + position without one — and out_score[r] its score, own bits; (-1, -inf) pads where k > n.
+inline void rank_topk(const float* sc, int64_t n, int k, const int64_t* col, int64_t index_base, int64_t* out_idx, float* out_score)
+{
+    std::vector<uint32_t> key((size_t)n);
+    for (int64_t i = 0; i < n; ++i) key[(size_t)i] = rank_key(sc[i]);
+    std::vector<int32_t> ind((size_t)n);
+    std::iota(ind.begin(), ind.end(), 0);
+    const int kk = (int)std::min<int64_t>(k, n);
+    const uint32_t* const ky = key.data();
+    if (col) std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [ky, col](int32_t a, int32_t b) { return ky[a] > ky[b] || (ky[a] == ky[b] && col[a] < col[b]); });
+    else std::partial_sort(ind.begin(), ind.begin() + kk, ind.end(), [ky](int32_t a, int32_t b) { return ky[a] > ky[b] || (ky[a] == ky[b] && a < b); });
+    for (int r = 0; r < k; ++r) {
+        if (r < kk) { out_idx[r] = col ? col[ind[(size_t)r]] : index_base + ind[(size_t)r]; out_score[r] = sc[ind[(size_t)r]]; }
+        else { out_idx[r] = -1; out_score[r] = -INFINITY; }
+    }
+}
+
+// All of 0 .. n-1 in the order of afis_rank_list (include/afis_matcher.h).  ref_order 0: key descending, equal keys by ascending index.  ref_order 1:
+// std::sort of the indices on rank_key(a) > rank_key(b) — the reference's statement (matcher.cpp:306-308: std::sort on scores[a] > scores[b]) with the
+// comparison made on the key: the same outcome for every pair of a NaN-free column, hence the same permutation from the same libstdc++, and a strict weak
+// order (defined behaviour) for every column.
+inline void rank_list_order(const float* scores, int64_t n, bool ref_order, std::vector<int>& ind)
+{
+    std::vector<uint32_t> key((size_t)n);
+    for (int64_t i = 0; i < n; ++i) key[(size_t)i] = rank_key(scores[i]);
+    ind.resize((size_t)n);
+    std::iota(ind.begin(), ind.end(), 0);
+    const uint32_t* const ky = key.data();
+    auto by_key = [ky](const int& a, const int& b) { return ky[a] > ky[b]; };
+    if (ref_order) std::sort(ind.begin(), ind.end(), by_key);
+    else std::stable_sort(ind.begin(), ind.end(), by_key);
+}
+
+}  // namespace afis

@@ -54,7 +54,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
-               "afis_debug_transpose_stats"]
+               "afis_debug_transpose_stats", "afis_debug_rank_rows"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -135,6 +135,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "afis_debug_rank_latent_hits"):
         lib.afis_debug_rank_latent_hits.argtypes = [vp, fp, C.c_int, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
         lib.afis_debug_transpose_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if hasattr(lib, "afis_debug_rank_rows"):
+        lib.afis_debug_rank_rows.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp]
     return lib
 
 
@@ -460,6 +462,16 @@ class Matcher:
         self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
         return self._hit_lists(lambda nq, nh, a, sc, b: self._tap("afis_debug_rank_hits")(self.ctx, handle[0] if handle is not None else None, _ptr(s, C.c_float), nq, min_score, cap, nh, a, sc, b),
                                s.shape[0], cap, handle is not None)
+
+    def debug_rank_rows(self, scores: np.ndarray, k: int, subset=None):
+        """The rank list of search() / search_subset() over a caller-made [n_q][n] score matrix (parity tap): topk_idx / topk_score [n_q][k] by the code the search runs
+        (k <= 64 the device's rank-list kernel, k > 64 the host's).  subset: a subset_create handle; the columns then stand in ascending order of the listed global
+        indices, as the device holds them.  The matrix stays rankable (rank_hits, rank_subjects, rank_latent_hits)."""
+        s = np.ascontiguousarray(scores, np.float32)
+        ti = np.empty((s.shape[0], k), np.int64); ts = np.empty((s.shape[0], k), np.float32)
+        self._chk(self._tap("afis_debug_rank_rows")(self.ctx, subset[0] if subset is not None else None, _ptr(s, C.c_float), s.shape[0], k, _ptr(ti, C.c_int64), _ptr(ts, C.c_float)))
+        self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
+        return {"topk_idx": ti, "topk_score": ts}
 
     # ---- reverse search: the last search's matrix ranked along its columns -----------------------------------------
     def _latent_lists(self, fn, n_templates: int, cap: int):

@@ -3,13 +3,36 @@ the one exchange step (all_gather of the per-shard top-k; backend "nccl" = RCCL 
 
 Gallery templates are independent units: partition them into one contiguous shard per rank, balanced by the cost driver
 (number of rolled texture points); every rank scores all queries against its shard and reports its local top-k with GLOBAL
-gallery indices; the merged list is the top-k of the union, score descending, ties by ascending global index.
+gallery indices; the merged list is the top-k of the union in the lists' own order: rank_key(score) descending, ties by ascending global index.
+
+The order is the one every path of the library lists by (csrc/rank_order.h, minu.hip::k_topk): rank_key is the ordered bits of score + 0.0f, so that the two
+zeros are one value and a NaN stands where its bits put it (above +inf with the sign clear, below -inf with it set).  On NaN-free scores that is plainly score
+descending.  The subject lists merge on subject_key, the ordered bits of the raw word (-0.0 below +0.0), the key include/afis_matcher.h documents for subjects.
 """
 from __future__ import annotations
 
 from typing import List, Tuple
 
 import numpy as np
+
+
+def _ordered(words: np.ndarray) -> np.ndarray:
+    w = np.asarray(words, np.uint32)
+    return np.where(w & np.uint32(0x80000000), ~w, w | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def rank_key(score) -> np.ndarray:
+    """csrc/rank_order.h::rank_key (minu.hip::ord_f32): the uint32 key a template rank list is sorted on, descending."""
+    return _ordered((np.asarray(score, np.float32) + np.float32(0.0)).view(np.uint32))
+
+
+def subject_key(score) -> np.ndarray:
+    """The key of the subject rank lists (subject_rank.hip): the ordered bits of the raw score word."""
+    return _ordered(np.ascontiguousarray(score, np.float32).view(np.uint32))
+
+
+def _desc(key: np.ndarray) -> np.ndarray:
+    return -key.astype(np.int64)                                           # a lexsort column: key descending
 
 
 def shard_bounds(cost: np.ndarray, world: int) -> List[Tuple[int, int]]:
@@ -45,7 +68,8 @@ def split_candidates(idx, bounds: List[Tuple[int, int]]) -> List[np.ndarray]:
 
 
 def merge_topk(idx: np.ndarray, score: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-    """idx, score: [R, Q, kk] per-shard rank lists (idx -1 = padding).  Returns the merged [Q, k] list."""
+    """idx, score: [R, Q, kk] per-shard rank lists (idx -1 = padding).  Returns the merged [Q, k] list: rank_key(score) descending, then global index ascending —
+    whatever bits the scores hold, the first k of what one search over the union lists."""
     R, Q, kk = idx.shape
     fi = np.transpose(idx, (1, 0, 2)).reshape(Q, R * kk)
     fs = np.transpose(score, (1, 0, 2)).reshape(Q, R * kk).astype(np.float32)
@@ -53,7 +77,7 @@ def merge_topk(idx: np.ndarray, score: np.ndarray, k: int) -> Tuple[np.ndarray, 
     for q in range(Q):
         valid = fi[q] >= 0
         vi, vs = fi[q][valid], fs[q][valid]
-        order = np.lexsort((vi, -vs.astype(np.float64)))[:k]      # score descending, then global index ascending
+        order = np.lexsort((vi, _desc(rank_key(vs))))[:k]         # key descending, then global index ascending
         out_i[q, :len(order)] = vi[order]; out_s[q, :len(order)] = vs[order]
     return out_i, out_s
 
@@ -61,6 +85,7 @@ def merge_topk(idx: np.ndarray, score: np.ndarray, k: int) -> Tuple[np.ndarray, 
 def merge_subject_topk(ids: np.ndarray, score: np.ndarray, best_idx: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """ids, score, best_idx: [R, Q, kk] per-rank subject rank lists (Matcher.rank_subjects on every rank's shard; id -1 = padding).  Returns the merged [Q, k] lists:
     entries with the same id keep the greater score — on equal scores the lower best_idx — then score descending, id ascending; padded with (-1, -inf, -1).
+    "Greater", "equal" and "descending" are those of subject_key, the key the per-rank lists were made on: the raw bits in their total order, -0.0 below +0.0.
 
     Exact although a person's prints may lie in several shards, for kk >= k: a subject's global score is the maximum of its per-shard scores, reached in some shard A.
     If the subject is among the global k best, fewer than k subjects rank before it globally (greater score, or equal score and lower id); every subject that ranks
@@ -77,18 +102,18 @@ def merge_subject_topk(ids: np.ndarray, score: np.ndarray, best_idx: np.ndarray,
     for q in range(Q):
         valid = fi[q] >= 0
         vi, vs, vb = fi[q][valid], fs[q][valid], fb[q][valid]
-        order = np.lexsort((vb, -vs.astype(np.float64), vi))                # by id; inside an id the greater score, then the lower best_idx, comes first
+        order = np.lexsort((vb, _desc(subject_key(vs)), vi))                # by id; inside an id the greater key, then the lower best_idx, comes first
         first = np.ones(len(order), bool); first[1:] = vi[order][1:] != vi[order][:-1]
         keep = order[first]
         vi, vs, vb = vi[keep], vs[keep], vb[keep]
-        order = np.lexsort((vi, -vs.astype(np.float64)))[:k]                # score descending, then subject id ascending
+        order = np.lexsort((vi, _desc(subject_key(vs))))[:k]                # key descending, then subject id ascending
         out_i[q, :len(order)] = vi[order]; out_s[q, :len(order)] = vs[order]; out_b[q, :len(order)] = vb[order]
     return out_i, out_s, out_b
 
 
 def merge_hits(n_hits: np.ndarray, idx: np.ndarray, score: np.ndarray, cap: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """n_hits: [R, Q], idx, score: [R, Q, kk] per-rank hit lists (Matcher.rank_hits with one min_score on every rank's shard; kk >= cap).  Returns (n_hits [Q], idx [Q, cap],
-    score [Q, cap]): the counts add — a template lies in one shard — and the list is the merge on score descending, then global index ascending, cut at cap.  Exact: every
+    score [Q, cap]): the counts add — a template lies in one shard — and the list is merge_topk's (rank_key descending, then global index ascending), cut at cap.  Exact: every
     rank's list is the best-kk prefix of what qualifies in its shard, so an entry among the cap best of the union is among the kk best of its own shard.
 
     The column lists of a reverse search (Matcher.rank_latent_hits: Q = the prints searched, the entries are latents) merge by this same function when the LATENTS are
@@ -102,7 +127,7 @@ def merge_prints_to_card(n_hits: np.ndarray, latent: np.ndarray, score: np.ndarr
     """n_hits: [P], latent, score: [P, kk] — the column lists of the P prints of ONE card (Matcher.rank_latent_hits with one min_score; row p = print position p;
     latent -1 = padding; kk >= cap).  Returns (latent [cap], score [cap], print_pos [cap], n_latents, truncated): per latent its greatest score over the card's prints — on
     equal scores the lowest print position — then score descending, latent index ascending, cut at cap and padded with (-1, -inf, -1).  print_pos says which print of
-    the card the entry's score belongs to.
+    the card the entry's score belongs to.  Scores compare on rank_key, the key of the column lists.
 
     Exact for kk >= cap: a latent's card score is the maximum of its per-print scores, reached at some print p.  If the latent is among the card's cap best, fewer than
     cap latents rank before it on the card (greater score, or equal score and lower index); every latent that ranks before it INSIDE p's list does so with a per-print
@@ -119,11 +144,11 @@ def merge_prints_to_card(n_hits: np.ndarray, latent: np.ndarray, score: np.ndarr
     fl = li.reshape(P * kk)
     valid = fl >= 0
     vl, vs, vp = fl[valid], fs[valid], fp[valid]
-    order = np.lexsort((vp, -vs.astype(np.float64), vl))                    # by latent; inside a latent the greater score, then the lower print position, comes first
+    order = np.lexsort((vp, _desc(rank_key(vs)), vl))                       # by latent; inside a latent the greater key, then the lower print position, comes first
     first = np.ones(len(order), bool); first[1:] = vl[order][1:] != vl[order][:-1]
     keep = order[first]
     vl, vs, vp = vl[keep], vs[keep], vp[keep]
-    order = np.lexsort((vl, -vs.astype(np.float64)))[:cap]                  # score descending, then latent index ascending
+    order = np.lexsort((vl, _desc(rank_key(vs))))[:cap]                     # key descending, then latent index ascending
     out_l = np.full(cap, -1, np.int64); out_s = np.full(cap, -np.inf, np.float32); out_p = np.full(cap, -1, np.int64)
     out_l[:len(order)] = vl[order]; out_s[:len(order)] = vs[order]; out_p[:len(order)] = vp[order]
     return out_l, out_s, out_p, int(len(vl)), bool((np.asarray(n_hits, np.int64) > kk).any())
