@@ -292,6 +292,42 @@ int afis_rank_hits(afis_ctx* ctx, int n_q, float min_score, int cap,
 int afis_rank_subject_hits(afis_ctx* ctx, afis_subjects* s, int n_q, float min_score, int cap,
                            int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/, int64_t* best_idx /*[n_q][cap]*/);
 
+/* Case lists (no reference counterpart): an examiner's unit of work is a CASE — the same impression encoded twice, several lifts of one finger, several fingers of one
+ * hand — and fusing the queries of a case is one list per case instead of one per query.  Both calls rank the matrix of the context's LAST search; a case cannot span
+ * searches: all its latents must be queries of the one search that is ranked.  On the device the member rows of every case are folded into one fused row
+ * (case_fuse.hip) and the fused rows are ranked by the kernel of afis_rank_hits, unchanged; only n_cases x (8 + cap x 12) bytes return, through the pinned buffer.
+ * afis_rank_case_hits          the templates: idx / score as afis_rank_hits' (global indices; for a subset search the listed templates only, whatever order the list had).
+ * afis_rank_case_subject_hits  the enrolled persons of a subject handle: subject_id / score.  No best_idx: per-latent detail is afis_rank_subject_hits' job, and that call
+ *                              stays available on the same matrix.
+ * Rows: case_of[i] is the caller's id (any int64 >= 0, any order, not dense) of the case query position i belongs to.  The distinct ids in ascending order are the rows
+ * of the outputs, case_id[c] returns the id of row c, and n_cases must be the number of distinct ids (AFIS_EINVAL otherwise; the message carries both numbers).
+ * The fused value of (case, column j) — a column is a template, or a subject slot — over the case's MEMBERS, its queries in ascending query position, v_m a member's value
+ * in that column: the score the matrix holds, or the subject's best score for that query exactly as afis_rank_subject_hits makes it (a subject none of whose templates the
+ * search covered is no entry, for every case alike, and is neither counted nor listed).  A member TAKES PART when rank_key(v_m) >= rank_key(+0.0f) (csrc/rank_order.h):
+ * the -1 of an empty entry or of a latent-empty query, every negative value and a NaN with the sign set stay out.
+ *   AFIS_CASE_SUM  acc = +0.0f; for the members in ascending position, if the member takes part, acc = acc + v_m — one fp32 add each, never reassociated, never
+ *                  contracted; -1.0f when no member takes part
+ *   AFIS_CASE_MAX  the v_m of greatest rank_key, with the bits of the first such member (-1 loses by itself)
+ * The lists are afis_rank_hits' lists over the fused rows in every respect: the key is the bits of fused + 0.0f in their total order, min_score treated the same way,
+ * descending; equal keys by ascending global template index, or ascending subject id; n_hits[c] may exceed cap; the rest is padded with -1 / -inf; min_score = -INFINITY
+ * gives a rank list of length cap.  (On the device an uncovered subject's fused word is 0xffffffff: a NaN with the sign set, whose key lies below -inf's and so below
+ * every min_score — the property of the key stated for afis_rank_hits above.)
+ * Which searches count, what invalidates the matrix and what leaves it alone are exactly as for afis_rank_hits.  Both calls leave the matrix rankable: they may be
+ * repeated and mixed with afis_rank_hits, afis_rank_subject_hits, afis_rank_subjects and afis_rank_latent_hits; a wait that times out invalidates it.  AFIS_ESTATE: no
+ * matrix to rank, or a subject handle of an older gallery.  AFIS_EINVAL: a mode other than AFIS_CASE_SUM / AFIS_CASE_MAX, a negative case id, a null array, an n_q that
+ * is not the last search's, a wrong n_cases, cap outside 1 .. AFIS_HITS_MAX, a NaN min_score, a subject handle that is not live.  n_q == 0 returns AFIS_OK when
+ * n_cases == 0.  With an empty shard, or a handle without subjects, every n_hits is 0 and every entry padding.  Device and pinned room — the fused matrix,
+ * n_cases x columns x 4 bytes in a buffer of its own, the cases' member tables, n_q x subjects x 8 bytes for the subjects' maxima, the outputs — is ensured before
+ * anything is queued: AFIS_EDEVICE, with nothing changed, when that fails.  No result of a search changes because these functions exist.
+ * Shards: the columns of different shards are disjoint and a case's row is common, so the per-rank template lists merge with host/sharding.py::merge_hits as they are;
+ * the subject lists merge with merge_case_subject_hits — exactly for AFIS_CASE_MAX, for AFIS_CASE_SUM only while no subject's prints lie in two shards. */
+#define AFIS_CASE_SUM 0
+#define AFIS_CASE_MAX 1
+int afis_rank_case_hits(afis_ctx* ctx, const int64_t* case_of /*[n_q]*/, int n_q, int mode, int64_t n_cases, float min_score, int cap,
+                        int64_t* case_id /*[n_cases]*/, int64_t* n_hits /*[n_cases]*/, int64_t* idx /*[n_cases][cap]*/, float* score /*[n_cases][cap]*/);
+int afis_rank_case_subject_hits(afis_ctx* ctx, afis_subjects* s, const int64_t* case_of /*[n_q]*/, int n_q, int mode, int64_t n_cases, float min_score, int cap,
+                                int64_t* case_id /*[n_cases]*/, int64_t* n_hits /*[n_cases]*/, int64_t* subject_id /*[n_cases][cap]*/, float* score /*[n_cases][cap]*/);
+
 /* Reverse search (no reference counterpart): every newly enrolled ten-print card is searched against the file of unsolved latents — the transaction that solves old cases.
  * The pair score is the forward search's; what differs is who stays on the device and which way the matrix is read.  The latents (about 260 KB each, against 50 KB per
  * print) are uploaded once with afis_queries_upload_reserved; per card the caller appends the prints (afis_gallery_reopen, afis_gallery_add*, afis_gallery_commit), lists
@@ -415,7 +451,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them.  "rank_hits_us" (read-only): the device time of the last afis_rank_hits' or
  * afis_rank_subject_hits' launches (k_rank_hits; for subjects the maxima's memset and k_subject_best before it), from HIP events around them; 0 when that call queued nothing.
  * "rank_latents_us" (read-only): the device time of the last afis_rank_latent_hits' launches (k_transpose_scores, then k_rank_hits on the transposed matrix), from HIP
- * events around them; 0 when that call queued nothing. */
+ * events around them; 0 when that call queued nothing.  "rank_cases_us" (read-only): the device time of the last afis_rank_case_hits' or afis_rank_case_subject_hits'
+ * launches (the fold of case_fuse.hip — for subjects behind the maxima's memset and k_subject_best — then k_rank_hits on the fused rows), from HIP events around them;
+ * 0 when that call queued nothing.  "case_fuse_us" / "case_rank_us" (read-only): that call's two parts, each from its own pair of events — everything before k_rank_hits,
+ * and k_rank_hits. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

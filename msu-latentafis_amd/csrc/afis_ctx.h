@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_cases.cpp (case lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -156,6 +156,9 @@ struct afis_ctx : Shard {
     DevBuf scores_t;                     // afis_rank_latent_hits: the last search's matrix transposed, [n_templates][n_q] (its lists leave through hits_out)
     int64_t rank_latents_us = 0;         // option rank_latents_us (read-only): device time of the last afis_rank_latent_hits' launches (k_transpose_scores, k_rank_hits)
     int64_t transpose_us = 0, transpose_bytes = 0;   // k_transpose_scores alone in that call (its own pair of events) and the bytes it read and wrote (parity tap afis_debug_transpose_stats)
+    DevBuf case_fused, case_tab;         // afis_rank_case_hits / afis_rank_case_subject_hits: the fused matrix [n_cases][columns] floats, and the cases' CSR (case_off [n_cases + 1] | member [n_q], int32); the lists leave through hits_out
+    int64_t rank_cases_us = 0;           // option rank_cases_us (read-only): device time of the last case-list call's launches (the fold, for subjects behind the maxima's memset and k_subject_best; then k_rank_hits)
+    int64_t case_fuse_us = 0, case_rank_us = 0;   // options case_fuse_us / case_rank_us (read-only): that time's two parts, each from its own pair of events: everything before k_rank_hits, and k_rank_hits
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)

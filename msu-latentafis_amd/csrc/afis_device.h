@@ -267,6 +267,14 @@ hipError_t launch_rank_hits(const float* scores, int n_q, int G, const unsigned 
 // afis_rank_latent_hits (latent_rank.hip): the score matrix in [n_q][n] -> out [n][n_q], 64 x 64 tiles through LDS, both sides coalesced; launch_rank_hits then ranks
 // out's rows — per print the queries — as it ranks a search's
 hipError_t launch_transpose_scores(const float* in, float* out, int n_q, int n, hipStream_t stream);
+// afis_rank_case_hits / afis_rank_case_subject_hits (case_fuse.hip): the member rows of every case — the CSR case_off [n_cases + 1] into member [n_q], query positions in
+// ascending order inside a case — folded into one row: fused [n_cases][G] from scores [n_q][G], or fused [n_cases][S] from best [n_q][S] as launch_subject_best left it
+// (a slot no template of the search covered gets the word 0xffffffff, whose key lies below every thr).  mode: kCaseSum — +0.0f plus the members whose key reaches +0.0's,
+// in member order, one fp32 add each, -1.0f when there is none — or kCaseMax — the member value of greatest key, first member's bits.  launch_rank_hits then ranks
+// fused's rows in its template form
+constexpr int kCaseSum = 0, kCaseMax = 1;                // AFIS_CASE_SUM, AFIS_CASE_MAX
+hipError_t launch_case_fuse(const float* scores, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
+hipError_t launch_case_fuse_subjects(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

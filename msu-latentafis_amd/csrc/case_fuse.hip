@@ -1,0 +1,132 @@
+// case_fuse.hip — device code of the case lists (afis_cases.cpp: afis_rank_case_hits, afis_rank_case_subject_hits): the queries of one search that belong to one
+// CASE — two encodings of an impression, several lifts of a finger, several fingers of a hand — are fused into one row, and k_rank_hits (rank_hits.hip) ranks the fused
+// rows as it ranks a search's.  The host hands the cases over as a CSR: case_off[n_cases + 1] into member[n_q], the query positions of a case in ascending order.
+//
+// The fused value of (case, column) over the case's members m, v_m the member's value in that column:
+//   a member TAKES PART when rank_key(v_m) >= rank_key(+0.0f) (rank_order.h), i.e. when the sign bit of v_m + 0.0f is clear: the -1 of an empty entry or of a
+//   latent-empty query, every negative value and a NaN with the sign set stay out; -0.0 is the zero it equals
+//   kCaseSum  acc = +0.0f; for the members in ascending position: if the member takes part, acc = acc + v_m — one fp32 add each, in that order (the translation units
+//             are built with -ffp-contract=off, and nothing here lets the compiler reassociate); -1.0f when no member takes part
+//   kCaseMax  the v_m of greatest rank_key, with the bits of the first member that holds it; -1 loses by itself
+//
+// k_case_fuse: scores[n_q][G] -> fused[n_cases][G].  Grid = (column chunks, cases); a thread owns one column — or, where every row starts on a 16-byte boundary
+// (G % 4 == 0), four adjacent ones that travel as one float4 — and walks the member rows of its case in CSR order: every load of a wave is one contiguous run of a
+// row, the order of the adds is the order of the loop, and there is no atomic and no sum across lanes.  The member loop carries no dependence between its loads, so
+// the unrolled loop has four rows in flight.  An odd G leaves rows unaligned: those matrices take the one-column form.
+// k_case_fuse_subjects: the same over best[n_q][S], the composites k_subject_best (subject_rank.hip) made (ordered score word << 32 | ~position; 0 = none of the
+// subject's templates was covered): the ordered word is turned back into the score's own bits and folded as above into a float row [n_cases][S].  A subject that was
+// not covered — the same slots for every query of a search — gets the word 0xffffffff: a NaN with the sign set, whose key lies below -inf's and so below every
+// min_score, which makes k_rank_hits neither count nor list it (include/afis_matcher.h states that property of the key).
+// Every index into the matrices is a size_t: n_q x G may pass 2^31.  A grid's second dimension holds 65 535 blocks; more cases than that are walked in a loop.
+#include "afis_device.h"
+
+namespace afis {
+
+typedef unsigned long long u64;
+
+constexpr int kCfThreads = 256;
+constexpr unsigned kCfMaxY = 65535;
+constexpr uint32_t kCfNoEntry = 0xffffffffu;                                // a sign-set NaN: ordered word 0, below every threshold k_rank_hits takes (thr >= 1)
+
+struct CfAcc { float v; uint32_t key; bool any; };
+
+__device__ __forceinline__ void cf_start(CfAcc& a) { a.v = 0.0f; a.key = 0; a.any = false; }
+
+// one member's value into the accumulator of its column
+template <int kMode>
+__device__ __forceinline__ void cf_fold(CfAcc& a, float v)
+{
+    const uint32_t u = __float_as_uint(v + 0.0f);                           // rank_key's + 0.0f: -0.0 -> +0.0
+    if (kMode == kCaseSum) {
+        if (!(u & 0x80000000u)) { a.v = a.v + v; a.any = true; }            // rank_key(v) >= rank_key(+0.0f)
+    } else {
+        const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        if (!a.any || key > a.key) { a.v = v; a.key = key; a.any = true; }   // strictly greater: the first member of the greatest key keeps its bits
+    }
+}
+
+template <int kMode>
+__device__ __forceinline__ float cf_result(const CfAcc& a) { return (kMode == kCaseSum && !a.any) ? -1.0f : a.v; }
+
+// scores [n_q][G]; case_off [n_cases + 1], member [case_off[n_cases]] query positions < n_q; fused [n_cases][G].  kVec: G % 4 == 0 and both matrices 16-byte aligned
+template <int kMode, bool kVec>
+__global__ __launch_bounds__(kCfThreads) void k_case_fuse(const float* __restrict__ scores, int G, const int32_t* __restrict__ case_off, const int32_t* __restrict__ member,
+                                                          int n_cases, float* __restrict__ fused)
+{
+    constexpr int kCols = kVec ? 4 : 1;
+    const size_t col = ((size_t)blockIdx.x * kCfThreads + threadIdx.x) * kCols;
+    if (col >= (size_t)G) return;                                           // (kVec: G % 4 == 0, so col + 3 < G too)
+    for (int c = (int)blockIdx.y; c < n_cases; c += (int)gridDim.y) {
+        const int m0 = case_off[c], m1 = case_off[c + 1];
+        CfAcc acc[kCols];
+#pragma unroll
+        for (int j = 0; j < kCols; ++j) cf_start(acc[j]);
+#pragma unroll 4
+        for (int m = m0; m < m1; ++m) {
+            const float* const row = scores + (size_t)member[m] * (size_t)G + col;
+            if constexpr (kVec) {
+                const float4 v = *reinterpret_cast<const float4*>(row);
+                cf_fold<kMode>(acc[0], v.x); cf_fold<kMode>(acc[1], v.y); cf_fold<kMode>(acc[2], v.z); cf_fold<kMode>(acc[3], v.w);
+            } else cf_fold<kMode>(acc[0], row[0]);
+        }
+        float* const dst = fused + (size_t)c * (size_t)G + col;
+        if constexpr (kVec) *reinterpret_cast<float4*>(dst) = make_float4(cf_result<kMode>(acc[0]), cf_result<kMode>(acc[1]), cf_result<kMode>(acc[2]), cf_result<kMode>(acc[3]));
+        else dst[0] = cf_result<kMode>(acc[0]);
+    }
+}
+
+// best [n_q][S] as k_subject_best left it; fused [n_cases][S]
+template <int kMode>
+__global__ __launch_bounds__(kCfThreads) void k_case_fuse_subjects(const u64* __restrict__ best, int S, const int32_t* __restrict__ case_off, const int32_t* __restrict__ member,
+                                                                   int n_cases, float* __restrict__ fused)
+{
+    const size_t col = (size_t)blockIdx.x * kCfThreads + threadIdx.x;
+    if (col >= (size_t)S) return;
+    for (int c = (int)blockIdx.y; c < n_cases; c += (int)gridDim.y) {
+        const int m0 = case_off[c], m1 = case_off[c + 1];
+        CfAcc acc;
+        cf_start(acc);
+        bool covered = true;
+#pragma unroll 4
+        for (int m = m0; m < m1; ++m) {
+            const u64 b = best[(size_t)member[m] * (size_t)S + col];
+            const uint32_t o = (uint32_t)(b >> 32);
+            covered = covered && b != 0;
+            cf_fold<kMode>(acc, __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o));   // the score word whose ordered form is o
+        }
+        fused[(size_t)c * (size_t)S + col] = covered ? cf_result<kMode>(acc) : __uint_as_float(kCfNoEntry);
+    }
+}
+
+static inline dim3 cf_grid(size_t threads, int n_cases)
+{
+    return dim3((unsigned)((threads + kCfThreads - 1) / kCfThreads), (unsigned)n_cases < kCfMaxY ? (unsigned)n_cases : kCfMaxY);
+}
+
+hipError_t launch_case_fuse(const float* scores, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream)
+{
+    if (n_cases <= 0 || G <= 0) return hipSuccess;
+    if (!scores || !case_off || !member || !fused || (mode != kCaseSum && mode != kCaseMax)) return hipErrorInvalidValue;
+    const bool vec = G % 4 == 0 && (((uintptr_t)scores | (uintptr_t)fused) & 15) == 0;
+    const dim3 grid = cf_grid(vec ? (size_t)G / 4 : (size_t)G, n_cases);
+    if (mode == kCaseSum) {
+        if (vec) hipLaunchKernelGGL((k_case_fuse<kCaseSum, true>), grid, dim3(kCfThreads), 0, stream, scores, G, case_off, member, n_cases, fused);
+        else hipLaunchKernelGGL((k_case_fuse<kCaseSum, false>), grid, dim3(kCfThreads), 0, stream, scores, G, case_off, member, n_cases, fused);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_case_fuse<kCaseMax, true>), grid, dim3(kCfThreads), 0, stream, scores, G, case_off, member, n_cases, fused);
+        else hipLaunchKernelGGL((k_case_fuse<kCaseMax, false>), grid, dim3(kCfThreads), 0, stream, scores, G, case_off, member, n_cases, fused);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_case_fuse_subjects(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream)
+{
+    if (n_cases <= 0 || S <= 0) return hipSuccess;
+    if (!best || !case_off || !member || !fused || (mode != kCaseSum && mode != kCaseMax)) return hipErrorInvalidValue;
+    const dim3 grid = cf_grid((size_t)S, n_cases);
+    if (mode == kCaseSum) hipLaunchKernelGGL(k_case_fuse_subjects<kCaseSum>, grid, dim3(kCfThreads), 0, stream, best, S, case_off, member, n_cases, fused);
+    else hipLaunchKernelGGL(k_case_fuse_subjects<kCaseMax>, grid, dim3(kCfThreads), 0, stream, best, S, case_off, member, n_cases, fused);
+    return hipGetLastError();
+}
+
+}  // namespace afis

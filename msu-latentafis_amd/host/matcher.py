@@ -24,6 +24,9 @@ class AfisError(RuntimeError):
     pass
 
 
+CASE_SUM, CASE_MAX = 0, 1                                                   # AFIS_CASE_SUM, AFIS_CASE_MAX (include/afis_matcher.h)
+
+
 class MinutiaeView(C.Structure):
     _fields_ = [("n", C.c_int32), ("x", C.POINTER(C.c_int16)), ("y", C.POINTER(C.c_int16)), ("ori", C.POINTER(C.c_float)),
                 ("des_len", C.c_int32), ("des", C.POINTER(C.c_float))]
@@ -51,6 +54,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
+           "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -103,6 +107,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "afis_rank_latent_hits"):                           # reverse search; absent from older builds compared by tools/lib_ab.py
         lib.afis_queries_upload_reserved.argtypes = [vp, C.POINTER(TemplateView), C.c_int, C.c_int64, C.POINTER(vp)]
         lib.afis_rank_latent_hits.argtypes = [vp, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
+    if hasattr(lib, "afis_rank_case_hits"):                             # case lists; absent from older builds compared by tools/lib_ab.py
+        lib.afis_rank_case_hits.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
+        lib.afis_rank_case_subject_hits.argtypes = [vp, vp, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -472,6 +479,27 @@ class Matcher:
         self._chk(self._tap("afis_debug_rank_rows")(self.ctx, subset[0] if subset is not None else None, _ptr(s, C.c_float), s.shape[0], k, _ptr(ti, C.c_int64), _ptr(ts, C.c_float)))
         self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
         return {"topk_idx": ti, "topk_score": ts}
+
+    # ---- case lists: the queries of one case fused into one list ----------------------------------------------------
+    def _case_lists(self, fn, case_of, cap: int, subjects: bool):
+        co = np.ascontiguousarray(np.asarray(case_of, np.int64).reshape(-1))
+        n_cases = len(np.unique(co)); c = max(cap, 0)
+        cid = np.empty(n_cases, np.int64); nh = np.empty(n_cases, np.int64); a = np.empty((n_cases, c), np.int64); sc = np.empty((n_cases, c), np.float32)
+        self._chk(fn(_ptr(co, C.c_int64), len(co), n_cases, _ptr(cid, C.c_int64), _ptr(nh, C.c_int64), _ptr(a, C.c_int64), _ptr(sc, C.c_float)))
+        return {"case_id": cid, "n_hits": nh, "subject" if subjects else "idx": a, "score": sc}
+
+    def rank_case_hits(self, case_of: Sequence[int], mode: int, min_score: float, cap: int):
+        """Of the LAST search, per CASE every template whose fused score reaches min_score.  case_of[i] (any int64 >= 0) is the case of query position i — all of a
+        case's latents must be queries of that one search; the distinct ids in ascending order are the rows: case_id [n_cases], n_hits [n_cases] (it may exceed cap),
+        idx / score [n_cases][cap] in rank-list order, padded with (-1, -inf).  mode CASE_SUM: the fp32 sum, in query order, of the members' scores that are >= 0 (-1 when
+        there is none); CASE_MAX: the members' best score.  min_score = -inf gives a rank list of length cap."""
+        return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_hits(self.ctx, co, nq, mode, nc, min_score, cap, cid, nh, a, sc), case_of, cap, False)
+
+    def rank_case_subject_hits(self, handle, case_of: Sequence[int], mode: int, min_score: float, cap: int):
+        """rank_case_hits over the enrolled persons of a subjects_create handle: a member's value is the subject's best score for that query; subject / score
+        [n_cases][cap].  (Which template reached it is rank_subject_hits' to say, per latent, on the same matrix.)"""
+        return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_subject_hits(self.ctx, handle[0], co, nq, mode, nc, min_score, cap, cid, nh, a, sc),
+                                case_of, cap, True)
 
     # ---- reverse search: the last search's matrix ranked along its columns -----------------------------------------
     def _latent_lists(self, fn, n_templates: int, cap: int):

@@ -168,6 +168,44 @@ def merge_subject_hits(n_hits: np.ndarray, subject: np.ndarray, score: np.ndarra
     return n, (np.asarray(n_hits, np.int64) > kk).any(axis=0), out[0], out[1], out[2]
 
 
+def merge_case_subject_hits(n_hits: np.ndarray, subject: np.ndarray, score: np.ndarray, cap: int, mode: int):
+    """n_hits: [R, C], subject, score: [R, C, kk] per-rank case subject lists (Matcher.rank_case_subject_hits with one case_of, mode and min_score on every rank; kk >= cap;
+    subject -1 = padding).  Returns (n_hits [C], truncated [C], subject [C, cap], score [C, cap]), on rank_key, the key of the case lists.  (The TEMPLATE lists of the cases
+    need no function of their own: the columns of different shards are disjoint and a case's row is common to every rank, so they merge with merge_hits as they are.)
+
+    mode 1 (AFIS_CASE_MAX): exact although a person's prints may lie in several shards.  The fused value is a maximum over the members of a maximum over the subject's
+    templates, and maxima commute: it is the greatest of the per-rank fused values.  Entries with the same id keep the greater key, then the list is key descending,
+    id ascending — merge_subject_hits' argument: a subject among the cap best arrives from the rank where it reaches its value, with that value.  The per-rank counts do
+    not add; n_hits is the number of distinct subjects in the input, exact unless a rank was cut (truncated: a rank reported n_hits > kk).
+    mode 0 (AFIS_CASE_SUM): exact only while no subject's prints lie in two shards.  Rank r holds sum_m max_{t in r} s(m, t), and the sum over the members of the maxima
+    over ALL of a subject's templates is in general neither the greatest nor the sum of those.  With whole subjects per shard every id arrives from one rank, the counts
+    add and the lists merge as template lists do; an id that two ranks report raises ValueError."""
+    ids = np.asarray(subject, np.int64)
+    R, C, kk = ids.shape
+    if mode not in (0, 1):
+        raise ValueError(f"merge_case_subject_hits: mode {mode} is neither 0 (AFIS_CASE_SUM) nor 1 (AFIS_CASE_MAX)")
+    fi = np.transpose(ids, (1, 0, 2)).reshape(C, R * kk)
+    fs = np.transpose(np.asarray(score, np.float32), (1, 0, 2)).reshape(C, R * kk)
+    counts = np.asarray(n_hits, np.int64)
+    out_n = np.empty(C, np.int64); out_i = np.full((C, cap), -1, np.int64); out_s = np.full((C, cap), -np.inf, np.float32)
+    for c in range(C):
+        valid = fi[c] >= 0
+        vi, vs = fi[c][valid], fs[c][valid]
+        if mode == 0:
+            u, n = np.unique(vi, return_counts=True)
+            if (n > 1).any():
+                raise ValueError(f"merge_case_subject_hits: AFIS_CASE_SUM lists merge only while every subject's prints lie in one shard; ids {u[n > 1][:8].tolist()} arrive from two ranks")
+            out_n[c] = counts[:, c].sum()
+        else:
+            order = np.lexsort((_desc(rank_key(vs)), vi))                   # by id; inside an id the greater key comes first
+            first = np.ones(len(order), bool); first[1:] = vi[order][1:] != vi[order][:-1]
+            vi, vs = vi[order[first]], vs[order[first]]
+            out_n[c] = len(vi)
+        order = np.lexsort((vi, _desc(rank_key(vs))))[:cap]                 # key descending, then subject id ascending
+        out_i[c, :len(order)] = vi[order]; out_s[c, :len(order)] = vs[order]
+    return out_n, (counts > kk).any(axis=0), out_i, out_s
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""
