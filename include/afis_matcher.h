@@ -328,6 +328,54 @@ int afis_rank_case_hits(afis_ctx* ctx, const int64_t* case_of /*[n_q]*/, int n_q
 int afis_rank_case_subject_hits(afis_ctx* ctx, afis_subjects* s, const int64_t* case_of /*[n_q]*/, int n_q, int mode, int64_t n_cases, float min_score, int cap,
                                 int64_t* case_id /*[n_cases]*/, int64_t* n_hits /*[n_cases]*/, int64_t* subject_id /*[n_cases][cap]*/, float* score /*[n_cases][cap]*/);
 
+/* Filtered hit lists (no reference counterpart): an operational latent search is never unrestricted — a latent record carries the finger positions it may come from,
+ * often a hand, a sex or a region code, and the elimination prints (the victim's, the officers', persons already examined) leave the list before anyone looks at it.  A
+ * filter shared by a whole batch is best served by afis_subset_create, which saves the scoring; a filter that differs PER QUERY is applied here, at ranking time, on the
+ * device: the cells a query is not eligible for are taken out of a copy of the matrix (hit_filter.hip) and the copy is ranked by the kernels of afis_rank_hits and
+ * afis_rank_subject_hits, unchanged.  The matrix itself is never written.
+ * afis_labels_create   label[0 .. n): one 64-bit attribute word for resident template index_base + i; the bits are the caller's (say ten one-hot finger positions, two for
+ *                     sex, the rest a region code).  The life cycle is afis_subjects_create's, rule for rule: n must be the resident shard's size (option
+ *                     "gallery_resident"; AFIS_EINVAL otherwise); a call before the first commit is AFIS_ESTATE; a refused call leaves nothing allocated; create and free
+ *                     first wait for all device work of the context and leave the last search's matrix rankable; several handles may be live at once and afis_destroy
+ *                     releases those that are left; the n x 8 bytes uploaded count in option "gallery_h2d_bytes".  A handle belongs to the gallery as it was: after an
+ *                     appending commit or a removal that changed the shard both ranking calls refuse it with AFIS_ESTATE (afis_labels_free still works).
+ * afis_rank_hits_filtered          afis_rank_hits over the eligible cells; excl holds GLOBAL template indices.
+ * afis_rank_subject_hits_filtered  afis_rank_subject_hits over the eligible cells; excl_subject holds subject ids, and an excluded person is no entry for that query.
+ * Eligibility of cell (q, t), L the label of the template at that column (for a subset search: of the listed template the column belongs to):
+ *   the label test  masks[q] = (any_of, all_of, none_of); the cell passes when (any_of == 0 || (L & any_of) != 0) && (L & all_of) == all_of && (L & none_of) == 0.
+ *                   With one-hot fields "finger in {2, 7} and sex = F" is a single none_of: the complement of the allowed bits inside those fields.  masks == NULL
+ *                   means no label test, and labels may then be NULL; masks given with labels == NULL is AFIS_EINVAL.
+ *   the exclusions  a CSR per query: excl_off[n_q + 1] with excl_off[0] == 0, never decreasing, into excl[excl_off[n_q]], every entry >= 0 (any violation is AFIS_EINVAL
+ *                   with nothing queued).  An entry that names nothing the search covered — an index outside this shard, an index a subset does not list, an id the
+ *                   subject handle does not hold — is ignored silently, so that the same list can be handed to every rank of a sharded gallery; duplicates are
+ *                   no-ops.  excl_off == NULL means no exclusions.
+ * The result is exactly the lists afis_rank_hits or afis_rank_subject_hits would give if the ineligible cells did not exist: the keys, the tie rules, the treatment of
+ * min_score, n_hits exceeding cap and the padding (-1 / -inf / -1) are theirs; min_score = -INFINITY gives a rank list of length cap.  For subjects a person's score is
+ * the best among their ELIGIBLE covered templates and best_idx the lowest such index among equal scores; a person with no eligible covered template is neither counted
+ * nor listed.  With no masks and no exclusions the outputs are entry for entry those of the unfiltered call.  (On the device an ineligible cell is the word 0xffffffff,
+ * the "no entry" word of the case lists: a NaN with the sign set, whose key lies below -inf's and so below every min_score.  A matrix cell that already held that word
+ * could not be told from an ineligible one; a search never produces it.)
+ * Which searches count, what invalidates the matrix and what leaves it alone, the AFIS_ESTATE and AFIS_EINVAL cases and the answers for an empty shard and n_q == 0 are
+ * exactly afis_rank_hits' and afis_rank_subject_hits'; in addition a labels handle that is not live in this context is AFIS_EINVAL.  Both calls leave the matrix
+ * rankable and unchanged: they may be repeated with other filters and mixed with every other ranking call, which keep returning their unfiltered results.  Device and
+ * pinned room — the filtered copy, n_q x templates x 4 bytes in a buffer of its own, the masks and the resolved exclusions, n_q x subjects x 8 bytes for the subjects'
+ * maxima, the outputs — is ensured before anything is queued: AFIS_EDEVICE, with nothing changed, when that fails.  No result of a search changes because these
+ * functions exist.
+ * Not in this interface: filters on the case lists and on the reverse (column) lists.  A case whose members carry different filters needs a "no eligible member" state
+ * that AFIS_CASE_SUM's -1 does not have.
+ * Shards: every rank labels its own shard and takes the same masks and exclusion lists; the columns of different shards are disjoint and a filtered maximum is still a
+ * maximum, so the per-rank lists merge with host/sharding.py::merge_hits and merge_subject_hits as they are. */
+typedef struct afis_labels afis_labels;
+int afis_labels_create(afis_ctx* ctx, const uint64_t* label /*[n]*/, int64_t n, afis_labels** out);
+void afis_labels_free(afis_ctx* ctx, afis_labels* labels);
+int afis_rank_hits_filtered(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                            const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                            int n_q, float min_score, int cap, int64_t* n_hits /*[n_q]*/, int64_t* idx /*[n_q][cap]*/, float* score /*[n_q][cap]*/);
+int afis_rank_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                    const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/,
+                                    int n_q, float min_score, int cap, int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/,
+                                    int64_t* best_idx /*[n_q][cap]*/);
+
 /* Reverse search (no reference counterpart): every newly enrolled ten-print card is searched against the file of unsolved latents — the transaction that solves old cases.
  * The pair score is the forward search's; what differs is who stays on the device and which way the matrix is read.  The latents (about 260 KB each, against 50 KB per
  * print) are uploaded once with afis_queries_upload_reserved; per card the caller appends the prints (afis_gallery_reopen, afis_gallery_add*, afis_gallery_commit), lists
@@ -454,7 +502,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * events around them; 0 when that call queued nothing.  "rank_cases_us" (read-only): the device time of the last afis_rank_case_hits' or afis_rank_case_subject_hits'
  * launches (the fold of case_fuse.hip — for subjects behind the maxima's memset and k_subject_best — then k_rank_hits on the fused rows), from HIP events around them;
  * 0 when that call queued nothing.  "case_fuse_us" / "case_rank_us" (read-only): that call's two parts, each from its own pair of events — everything before k_rank_hits,
- * and k_rank_hits. */
+ * and k_rank_hits.  "rank_filtered_us" (read-only): the device time of the last afis_rank_hits_filtered's or afis_rank_subject_hits_filtered's launches (the filter pass
+ * of hit_filter.hip, for subjects the maxima's memset and k_subject_best, the exclusions' drops; then k_rank_hits), from HIP events around them; 0 when that call queued
+ * nothing.  "filter_us" (read-only): of that call everything before k_rank_hits, from its own pair of events; 0 when the call queued nothing. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

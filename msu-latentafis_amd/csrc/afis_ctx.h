@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_cases.cpp (case lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -121,6 +121,13 @@ struct afis_subjects {
     DevBuf d_slot_of, d_ids;             // [n] int32, [S] int64
 };
 
+// One attribute word per template of the resident shard (afis_labels_create): what the masks of the filtered hit lists are tested against (hit_filter.hip).
+struct afis_labels {
+    int64_t n = 0;                       // templates labelled (the resident shard's size at creation)
+    uint64_t gallery_epoch = 0;          // afis_ctx::gallery_epoch at creation: the filtered ranking calls refuse the handle after an edit
+    DevBuf d_label;                      // [n] uint64
+};
+
 // The score matrix the last search left in afis_ctx::scores ([n_q][G] in the order of the shard searched: the resident one, or sub's sub-shard), while nothing has
 // touched it or what it refers to: afis_rank_subjects ranks it.  Set by a search that succeeded, cleared by drain_abandoned at the top of every entry point that queues work.
 struct LastSearch { bool valid = false; int n_q = 0; int64_t G = 0; const afis_subset* sub = nullptr; uint64_t gallery_epoch = 0; };   // (gallery_epoch: the shard the matrix was scored against)
@@ -159,6 +166,10 @@ struct afis_ctx : Shard {
     DevBuf case_fused, case_tab;         // afis_rank_case_hits / afis_rank_case_subject_hits: the fused matrix [n_cases][columns] floats, and the cases' CSR (case_off [n_cases + 1] | member [n_q], int32); the lists leave through hits_out
     int64_t rank_cases_us = 0;           // option rank_cases_us (read-only): device time of the last case-list call's launches (the fold, for subjects behind the maxima's memset and k_subject_best; then k_rank_hits)
     int64_t case_fuse_us = 0, case_rank_us = 0;   // options case_fuse_us / case_rank_us (read-only): that time's two parts, each from its own pair of events: everything before k_rank_hits, and k_rank_hits
+    std::vector<afis_labels*> label_sets;   // live label handles (afis_labels_create .. afis_labels_free; afis_destroy releases what is left)
+    DevBuf filt_scores, filt_tab;        // afis_rank_hits_filtered / afis_rank_subject_hits_filtered: the filtered copy of the matrix [n_q][G] floats, and the call's tables (masks [n_q][3] uint64 | the exclusions' (row, column) pairs, int32 x 2); the lists leave through hits_out
+    int64_t rank_filtered_us = 0;        // option rank_filtered_us (read-only): device time of the last filtered call's launches (the filter pass, for subjects the maxima's memset and k_subject_best, the drops; then k_rank_hits)
+    int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -315,5 +326,7 @@ int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int 
 int check_hits(afis_ctx* ctx, const char* who, int n_q, float min_score, int cap, bool outputs, const afis_subjects* s) __attribute__((visibility("hidden")));
 // the ordered form of a score word (minu.hip: ord_f32 without its + 0.0f; subject_rank.hip: sr_ord_f32)
 inline uint32_t ordered_word(float v) { uint32_t b; memcpy(&b, &v, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+// afis_filter.cpp
+void release_labels(afis_labels* l);                   // its device buffer and the handle itself
 
 }  // namespace afis

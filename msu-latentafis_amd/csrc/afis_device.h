@@ -275,6 +275,16 @@ hipError_t launch_transpose_scores(const float* in, float* out, int n_q, int n, 
 constexpr int kCaseSum = 0, kCaseMax = 1;                // AFIS_CASE_SUM, AFIS_CASE_MAX
 hipError_t launch_case_fuse(const float* scores, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
 hipError_t launch_case_fuse_subjects(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
+// afis_rank_hits_filtered / afis_rank_subject_hits_filtered (hit_filter.hip): filtered [n_q][G] = scores [n_q][G] with every cell whose column's label fails the row's
+// masks [n_q][3] (any_of, all_of, none_of) replaced by the word 0xffffffff, which launch_rank_hits never counts and launch_subject_best turns into a composite that is
+// never counted; labels [templates of the resident shard], the label of position p is labels[p], or labels[d_global[p] - index_base] for a subset's matrix.  A thread
+// loads its columns' labels once and walks a strip of kFilterRows rows.  The drops write the same word at (row, column) pairs of filtered, or 0 ("no entry") at
+// (row, slot) pairs of best [n_q][S] after launch_subject_best; pairs [n_pairs][2] int32, resolved by the host
+constexpr int kFilterRows = 8;
+hipError_t launch_filter_rows(const float* scores, int n_q, int G, const unsigned long long* labels, const unsigned long long* masks, const long long* d_global, long long index_base,
+                              float* filtered, hipStream_t stream);
+hipError_t launch_filter_drop_cells(const int32_t* pairs, size_t n_pairs, float* filtered, int n_q, int G, hipStream_t stream);
+hipError_t launch_filter_drop_subjects(const int32_t* pairs, size_t n_pairs, unsigned long long* best, int n_q, int S, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

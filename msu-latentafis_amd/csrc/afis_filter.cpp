@@ -1,0 +1,185 @@
+// afis_filter.cpp — filtered hit lists of the C ABI (include/afis_matcher.h): afis_labels_create gives every template of the resident shard one 64-bit attribute word,
+// afis_rank_hits_filtered and afis_rank_subject_hits_filtered list, per query of the last search, the templates or the enrolled persons that reach a decision score
+// among the cells the query is ELIGIBLE for — the label passes the query's three masks, and the template or the person is not on the query's exclusion list.  The
+// ineligible cells are taken out of a copy of the matrix (hit_filter.hip) and the copy is ranked by k_subject_best and k_rank_hits, unchanged, the way afis_cases.cpp
+// ranks its fused rows.  Only n_q x (8 + cap x 12 or 20) bytes return; the [n_q][G] matrix stays where it is, and as it is.
+#include "afis_ctx.h"
+
+using namespace afis;
+
+namespace afis {
+
+void release_labels(afis_labels* l)
+{
+    if (!l) return;
+    l->d_label.release();
+    delete l;
+}
+
+// both entry points behind their checks (subj == NULL: the templates; out_a = idx, out_b unused).  masks NULL or [n_q][3]; pairs: the exclusions as (row, column) —
+// columns of the matrix for the templates, slots of the handle for the subjects — already inside the matrix
+static int rank_hits_filtered(afis_ctx* ctx, afis_subjects* subj, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, int n_q, float min_score, int cap,
+                              int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b)
+{
+    const LastSearch ls = ctx->last_search;
+    const int64_t G = ls.G, S = subj ? subj->S : 0;
+    const size_t n_out = (size_t)n_q * (size_t)cap, n_pairs = pairs.size() / 2;
+    const char* const who = subj ? "afis_rank_subject_hits_filtered" : "afis_rank_hits_filtered";
+    ctx->rank_filtered_us = 0; ctx->filter_us = 0;
+    if (n_q == 0) return AFIS_OK;
+    if (G == 0 || (subj && S == 0)) {                                       // nothing was scored: no hit, every entry is padding
+        for (int i = 0; i < n_q; ++i) n_hits[i] = 0;
+        for (size_t o = 0; o < n_out; ++o) { out_a[o] = -1; out_score[o] = -INFINITY; if (subj) out_b[o] = -1; }
+        return AFIS_OK;
+    }
+    const uint32_t thr = ordered_word(subj ? min_score : min_score + 0.0f);  // afis_rank_hits' thresholds, unchanged
+    // the copy is needed where cells change: by the masks, or by a template's exclusions (a subject's exclusions are dropped from the maxima)
+    const bool copy = masks || (!subj && n_pairs > 0);
+    const size_t mask_bytes = masks ? (size_t)n_q * 24 : 0, tab_bytes = mask_bytes + n_pairs * 8;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // room first: a failed allocation leaves everything as it was
+    if (copy) HIPCHK(ctx, ctx->filt_scores.ensure((size_t)n_q * (size_t)G * 4));
+    if (tab_bytes) HIPCHK(ctx, ctx->filt_tab.ensure(tab_bytes));
+    if (subj) HIPCHK(ctx, ctx->subj_best.ensure((size_t)n_q * (size_t)S * 8));
+    const size_t a_at = (size_t)n_q * 8, b_at = a_at + n_out * 8, score_at = b_at + (subj ? n_out * 8 : 0), out_bytes = score_at + n_out * 4;
+    HIPCHK(ctx, ctx->hits_out.ensure(out_bytes));
+    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
+    hipStream_t s = ctx->stream;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 3; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } drop_ev{ev};
+    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    const long long* const d_global = ls.sub ? ls.sub->d_global.as<long long>() : nullptr;
+    uint8_t* const d_tab = ctx->filt_tab.as<uint8_t>();
+    const int32_t* const d_pairs = (const int32_t*)(d_tab + mask_bytes);
+    const float* const ranked = copy ? ctx->filt_scores.as<float>() : ctx->scores.as<float>();   // neither masks nor exclusions: the search's matrix itself
+    uint8_t* const d_out = ctx->hits_out.as<uint8_t>();
+    uint8_t* const pin = (uint8_t*)ctx->h_pin;
+    if (masks) HIPCHK(ctx, hipMemcpyAsync(d_tab, masks, mask_bytes, hipMemcpyHostToDevice, s));            // (the caller's array and pairs live until the wait below)
+    if (n_pairs) HIPCHK(ctx, hipMemcpyAsync(d_tab + mask_bytes, pairs.data(), n_pairs * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipEventRecord(ev[0], s));
+    if (masks) HIPCHK(ctx, launch_filter_rows(ctx->scores.as<float>(), n_q, (int)G, labels->d_label.as<unsigned long long>(), (const unsigned long long*)d_tab, d_global,
+                                              (long long)ctx->index_base, ctx->filt_scores.as<float>(), s));
+    else if (copy) HIPCHK(ctx, hipMemcpyAsync(ctx->filt_scores.p, ctx->scores.p, (size_t)n_q * (size_t)G * 4, hipMemcpyDeviceToDevice, s));
+    if (subj) {                                                             // the maxima of the filtered rows, exactly as rank_hits makes them; then the excluded persons
+        HIPCHK(ctx, launch_subject_best(ranked, n_q, (int)G, subj->d_slot_of.as<int32_t>(), d_global, (long long)ctx->index_base, (int)S, ctx->subj_best.as<unsigned long long>(), s));
+        HIPCHK(ctx, launch_filter_drop_subjects(d_pairs, n_pairs, ctx->subj_best.as<unsigned long long>(), n_q, (int)S, s));
+    } else HIPCHK(ctx, launch_filter_drop_cells(d_pairs, n_pairs, ctx->filt_scores.as<float>(), n_q, (int)G, s));
+    HIPCHK(ctx, hipEventRecord(ev[1], s));
+    HIPCHK(ctx, launch_rank_hits(ranked, n_q, (int)G, subj ? ctx->subj_best.as<unsigned long long>() : nullptr, (int)S, subj ? subj->d_ids.as<long long>() : nullptr,
+                                 d_global, (long long)ctx->index_base, thr, cap, (long long*)d_out, (long long*)(d_out + a_at), (float*)(d_out + score_at),
+                                 subj ? (long long*)(d_out + b_at) : nullptr, s));
+    HIPCHK(ctx, hipEventRecord(ev[2], s));
+    HIPCHK(ctx, hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    { const int rcw = wait_streams(ctx, {s}, who); if (rcw != AFIS_OK) { ctx->last_search.valid = false; return rcw; } }
+    float ms = 0, ms_f = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&ms_f, ev[0], ev[1]));
+    ctx->rank_filtered_us = (int64_t)((double)ms * 1e3); ctx->filter_us = (int64_t)((double)ms_f * 1e3);
+    memcpy(n_hits, pin, (size_t)n_q * 8); memcpy(out_a, pin + a_at, n_out * 8); memcpy(out_score, pin + score_at, n_out * 4);
+    if (subj) memcpy(out_b, pin + b_at, n_out * 8);
+    return AFIS_OK;
+}
+
+// the checks both entry points share, in the order of afis_rank_hits'; on AFIS_OK pairs holds the exclusions that name something the search covered, as (row, column or slot)
+static int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s, const afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
+                          int n_q, float min_score, int cap, bool outputs, std::vector<int32_t>& pairs)
+{
+    const std::string w(who);
+    if (labels && std::find(ctx->label_sets.begin(), ctx->label_sets.end(), labels) == ctx->label_sets.end()) return fail(ctx, AFIS_EINVAL, w + ": not a live labels handle of this context");
+    if (masks && !labels) return fail(ctx, AFIS_EINVAL, w + ": masks need a labels handle");
+    const int rc = check_hits(ctx, who, n_q, min_score, cap, outputs, s);
+    if (rc != AFIS_OK) return rc;
+    // the labels are positions of the shard as it was: after an edit they may belong to other templates
+    if (labels && labels->gallery_epoch != ctx->gallery_epoch)
+        return fail(ctx, AFIS_ESTATE, w + ": the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these labels were given; free the handle and create it again");
+    pairs.clear();
+    if (!excl_off) return AFIS_OK;
+    if (excl_off[0] != 0) return fail(ctx, AFIS_EINVAL, w + ": excl_off[0] must be 0");
+    for (int i = 0; i < n_q; ++i) if (excl_off[i + 1] < excl_off[i]) return fail(ctx, AFIS_EINVAL, w + ": excl_off decreases");
+    const int64_t total = excl_off[n_q];
+    if (total > 0 && !excl) return fail(ctx, AFIS_EINVAL, w + ": excl_off lists entries, the entries are null");
+    for (int64_t e = 0; e < total; ++e) if (excl[e] < 0) return fail(ctx, AFIS_EINVAL, w + ": an exclusion is negative");
+    // an entry that names nothing the search covered is ignored: another shard's template, one the subset does not list, an id the handle does not hold
+    const LastSearch& ls = ctx->last_search;
+    std::vector<int64_t> held;                                              // a subset's device order: its listed indices ascending
+    if (!s && ls.sub) { held = ls.sub->idx; std::sort(held.begin(), held.end()); }
+    const std::vector<int64_t>& names = s ? s->ids : held;
+    for (int i = 0; i < n_q; ++i)
+        for (int64_t e = excl_off[i]; e < excl_off[i + 1]; ++e) {
+            int64_t c;
+            if (!s && !ls.sub) c = excl[e] - ctx->index_base;
+            else {
+                const auto it = std::lower_bound(names.begin(), names.end(), excl[e]);
+                c = (it != names.end() && *it == excl[e]) ? (int64_t)(it - names.begin()) : -1;
+            }
+            if (c >= 0 && c < (s ? s->S : ls.G)) { pairs.push_back((int32_t)i); pairs.push_back((int32_t)c); }
+        }
+    return AFIS_OK;
+}
+
+}  // namespace afis
+
+extern "C" {
+
+int afis_labels_create(afis_ctx* ctx, const uint64_t* label, int64_t n, afis_labels** out)
+{
+    if (!ctx || !out || n < 0 || (n > 0 && !label)) return fail(ctx, AFIS_EINVAL, "afis_labels_create: bad argument");
+    *out = nullptr;
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_labels_create: commit the gallery first");
+    if (n != (int64_t)ctx->res_empty.size()) return fail(ctx, AFIS_EINVAL, "afis_labels_create: one label per template of the resident shard (option gallery_resident)");
+    std::unique_ptr<afis_labels> lb(new afis_labels());
+    lb->n = n; lb->gallery_epoch = ctx->gallery_epoch;
+    { const int rcq = quiesce(ctx, "afis_labels_create", true); if (rcq != AFIS_OK) return rcq; }
+    if (n > 0) {
+        const int64_t h2d_before = ctx->gallery_h2d_bytes;
+        auto table = [&]() -> int {
+            HIPCHK(ctx, hipSetDevice(ctx->device));
+            HIPCHK(ctx, lb->d_label.ensure((size_t)n * 8));
+            HIPCHK(ctx, hipMemcpyAsync(lb->d_label.p, label, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+            ctx->gallery_h2d_bytes += n * 8;
+            return wait_streams(ctx, {ctx->stream}, "afis_labels_create");
+        };
+        const int rc = table();
+        if (rc != AFIS_OK) {                                                // nothing allocated, nothing changed
+            (void)hipStreamSynchronize(ctx->stream);
+            ctx->gallery_h2d_bytes = h2d_before;
+            release_labels(lb.release());
+            return rc;
+        }
+    }
+    ctx->label_sets.push_back(lb.get());
+    *out = lb.release();
+    return AFIS_OK;
+}
+
+void afis_labels_free(afis_ctx* ctx, afis_labels* labels)
+{
+    if (!labels) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)quiesce(ctx, "afis_labels_free", true);
+        ctx->label_sets.erase(std::remove(ctx->label_sets.begin(), ctx->label_sets.end(), labels), ctx->label_sets.end());
+    }
+    release_labels(labels);
+}
+
+int afis_rank_hits_filtered(afis_ctx* ctx, afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
+                            int n_q, float min_score, int cap, int64_t* n_hits, int64_t* idx, float* score)
+{
+    if (!ctx) return fail(ctx, AFIS_EINVAL, "afis_rank_hits_filtered: null argument");
+    std::vector<int32_t> pairs;
+    const int rc = check_filtered(ctx, "afis_rank_hits_filtered", nullptr, labels, masks, excl_off, excl, n_q, min_score, cap, n_hits && idx && score, pairs);
+    return rc != AFIS_OK ? rc : rank_hits_filtered(ctx, nullptr, labels, masks, pairs, n_q, min_score, cap, n_hits, idx, score, nullptr);
+}
+
+int afis_rank_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl_subject,
+                                    int n_q, float min_score, int cap, int64_t* n_hits, int64_t* subject_id, float* subject_score, int64_t* best_idx)
+{
+    if (!ctx || !s) return fail(ctx, AFIS_EINVAL, "afis_rank_subject_hits_filtered: null argument");
+    if (std::find(ctx->subject_sets.begin(), ctx->subject_sets.end(), s) == ctx->subject_sets.end()) return fail(ctx, AFIS_EINVAL, "afis_rank_subject_hits_filtered: not a live subject handle of this context");
+    std::vector<int32_t> pairs;
+    const int rc = check_filtered(ctx, "afis_rank_subject_hits_filtered", s, labels, masks, excl_off, excl_subject, n_q, min_score, cap, n_hits && subject_id && subject_score && best_idx, pairs);
+    return rc != AFIS_OK ? rc : rank_hits_filtered(ctx, s, labels, masks, pairs, n_q, min_score, cap, n_hits, subject_id, subject_score, best_idx);
+}
+
+}  // extern "C"

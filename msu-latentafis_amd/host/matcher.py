@@ -55,6 +55,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
+           "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -110,6 +111,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "afis_rank_case_hits"):                             # case lists; absent from older builds compared by tools/lib_ab.py
         lib.afis_rank_case_hits.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
         lib.afis_rank_case_subject_hits.argtypes = [vp, vp, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
+    if hasattr(lib, "afis_rank_hits_filtered"):                         # filtered hit lists; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64)
+        lib.afis_labels_create.argtypes = [vp, u64p, C.c_int64, C.POINTER(vp)]
+        lib.afis_labels_free.argtypes = [vp, vp]; lib.afis_labels_free.restype = None
+        lib.afis_rank_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_float, C.c_int, i64p, i64p, fp]
+        lib.afis_rank_subject_hits_filtered.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -479,6 +486,50 @@ class Matcher:
         self._chk(self._tap("afis_debug_rank_rows")(self.ctx, subset[0] if subset is not None else None, _ptr(s, C.c_float), s.shape[0], k, _ptr(ti, C.c_int64), _ptr(ts, C.c_float)))
         self.last_n_q = s.shape[0]; self.last_n_templates = s.shape[1]
         return {"topk_idx": ti, "topk_score": ts}
+
+    # ---- filtered hit lists: only the templates a query is eligible for ---------------------------------------------
+    def labels_create(self, labels: Sequence[int]):
+        """One 64-bit attribute word (the bits are the caller's) per template of the resident shard, in shard order; -> handle for rank_hits_filtered /
+        rank_subject_hits_filtered.  The handle is refused (AFIS_ESTATE) once the gallery has been edited; labels_free releases it."""
+        a = np.ascontiguousarray(np.asarray(labels, np.uint64).reshape(-1))
+        h = C.c_void_p()
+        self._chk(self.lib.afis_labels_create(self.ctx, _ptr(a, C.c_uint64) if len(a) else None, len(a), C.byref(h)))
+        return (h, len(a))
+
+    def labels_free(self, handle):
+        self.lib.afis_labels_free(self.ctx, handle[0])
+
+    @staticmethod
+    def _filter_args(n_q: int, masks, excl):
+        """masks: None or [n_q][3] uint64 (any_of, all_of, none_of); excl: None or one sequence of int64 per query -> the C arrays (kept alive by the caller)."""
+        mk = None if masks is None else np.ascontiguousarray(np.asarray(masks, np.uint64).reshape(n_q, 3))
+        off = ent = None
+        if excl is not None:
+            if len(excl) != n_q:
+                raise ValueError("one exclusion sequence per query")
+            rows = [np.asarray(e, np.int64).reshape(-1) for e in excl]
+            off = np.zeros(n_q + 1, np.int64); off[1:] = np.cumsum([len(r) for r in rows])
+            ent = np.ascontiguousarray(np.concatenate(rows)) if rows and off[-1] else np.zeros(1, np.int64)
+        return mk, off, ent
+
+    def rank_hits_filtered(self, min_score: float, cap: int, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """rank_hits over the cells each query is eligible for.  labels: a labels_create handle (needed with masks); masks: [n_q][3] uint64, per query (any_of, all_of,
+        none_of) tested against the label L of a column's template: (any_of == 0 or L & any_of) and L & all_of == all_of and not L & none_of; excl: per query a
+        sequence of GLOBAL template indices that are no entries for it (what the search did not cover is ignored).  None: no label test / no exclusions."""
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_hits_filtered(
+            self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+            _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc), n_q, cap, False)
+
+    def rank_subject_hits_filtered(self, handle, min_score: float, cap: int, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """rank_subject_hits over the eligible cells: a person's score is the best among their eligible covered templates; excl: per query a sequence of SUBJECT ids
+        that are no entries for it.  A person without an eligible covered template is neither counted nor listed."""
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits_filtered(
+            self.ctx, handle[0], labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+            _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
 
     # ---- case lists: the queries of one case fused into one list ----------------------------------------------------
     def _case_lists(self, fn, case_of, cap: int, subjects: bool):
