@@ -170,7 +170,6 @@ constexpr int kRfBatches = 4;                       // code words of a flush: fe
 constexpr int kRfChunk = 4;                         // pairs per draw from the task counter, in launches where every wave draws at least four times (otherwise one: a small search keeps every wave busy)
 struct __align__(16) RfWave { unsigned short row[kRfItems]; unsigned short pt[kRfItems]; unsigned short slot[kRfItems]; float val[kRfItems]; };
 
-__device__ __forceinline__ uint32_t ord_f32(float v) { const uint32_t b = f2u(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 // this wave's own LDS traffic in program order (the waves of the workgroup work on different pairs: no workgroup barrier may be used)
 #define RF_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 
@@ -276,7 +275,7 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
                 klo[u] = 0u;
                 if (u < n_regs && e < n_lt) {
                     float lo, hi; bounds(e, rec0[e], lo, hi);
-                    klo[u] = ord_f32(lo);
+                    klo[u] = ordered_word(lo);
                     kmax = max(kmax, klo[u]); kmin = min(kmin, klo[u]);
                 }
             }
@@ -398,7 +397,7 @@ __global__ __launch_bounds__(kRfWaves * 64) void k_tex_refine(QueryDev q, Galler
                 bool active = false;
                 if (in) {
                     float lo, hi; bounds_rk(rkc, ra, lo, hi);
-                    active = ord_f32(hi) >= C;
+                    active = ordered_word(hi) >= C;
                 }
                 if (in && !active && !compact) { rm_val[o + e] = -INFINITY; rm_arg[o + e] = 0; }
                 const unsigned long long am = __ballot(active);

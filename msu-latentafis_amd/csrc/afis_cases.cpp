@@ -18,15 +18,9 @@ static int rank_case_hits(afis_ctx* ctx, afis_subjects* subj, const int64_t* cas
     const LastSearch ls = ctx->last_search;
     const int n_q = ls.n_q;
     const int64_t n_cases = (int64_t)ids.size(), cols = subj ? subj->S : ls.G;
-    const size_t n_out = (size_t)n_cases * (size_t)cap;
-    const char* const who = subj ? "afis_rank_case_subject_hits" : "afis_rank_case_hits";
+    HitCall hc{ctx, subj ? "afis_rank_case_subject_hits" : "afis_rank_case_hits", n_cases, cap, n_hits, out_a, out_score, nullptr};
     ctx->rank_cases_us = 0; ctx->case_fuse_us = 0; ctx->case_rank_us = 0;
-    if (n_cases == 0) return AFIS_OK;
-    if (ls.G == 0 || cols == 0) {                                           // nothing was scored: no hit, every entry is padding
-        for (int64_t c = 0; c < n_cases; ++c) { case_id[c] = ids[(size_t)c]; n_hits[c] = 0; }
-        for (size_t o = 0; o < n_out; ++o) { out_a[o] = -1; out_score[o] = -INFINITY; }
-        return AFIS_OK;
-    }
+    if (hc.empty(ls.G == 0 || cols == 0)) { std::copy(ids.begin(), ids.end(), case_id); return AFIS_OK; }
     // the cases as a CSR: a counting sort of the query positions by the row of their case keeps the positions of a case in ascending order
     std::vector<int32_t> tab((size_t)n_cases + 1 + (size_t)n_q, 0);
     int32_t* const off = tab.data();
@@ -38,45 +32,22 @@ static int rank_case_hits(afis_ctx* ctx, afis_subjects* subj, const int64_t* cas
     }
     for (int64_t c = 0; c < n_cases; ++c) off[c + 1] += off[c];
     { std::vector<int32_t> next(off, off + n_cases); for (int i = 0; i < n_q; ++i) member[next[(size_t)row_of[(size_t)i]]++] = i; }
-    const uint32_t thr = ordered_word(min_score + 0.0f);                    // k_topk's key: -0.0 -> +0.0
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // room first: a failed allocation leaves everything as it was
     HIPCHK(ctx, ctx->case_fused.ensure((size_t)n_cases * (size_t)cols * 4));
     HIPCHK(ctx, ctx->case_tab.ensure(tab.size() * 4));
     if (subj) HIPCHK(ctx, ctx->subj_best.ensure((size_t)n_q * (size_t)cols * 8));
-    const size_t a_at = (size_t)n_cases * 8, score_at = a_at + n_out * 8, out_bytes = score_at + n_out * 4;
-    HIPCHK(ctx, ctx->hits_out.ensure(out_bytes));
-    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
+    AFISCHK(hc.begin({{ctx->case_tab.p, tab.data(), tab.size() * 4}}));
     hipStream_t s = ctx->stream;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 3; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } drop_ev{ev};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    const long long* const d_global = ls.sub ? ls.sub->d_global.as<long long>() : nullptr;
-    const int32_t* const d_off = ctx->case_tab.as<int32_t>();
-    const int32_t* const d_member = d_off + n_cases + 1;
-    uint8_t* const d_out = ctx->hits_out.as<uint8_t>();
-    uint8_t* const pin = (uint8_t*)ctx->h_pin;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->case_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));   // (tab lives until the wait below)
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
+    const int32_t* const d_off = ctx->case_tab.as<int32_t>(), * const d_member = d_off + n_cases + 1;
     if (subj) {                                                             // the maxima first, exactly as rank_hits makes them
-        HIPCHK(ctx, launch_subject_best(ctx->scores.as<float>(), n_q, (int)ls.G, subj->d_slot_of.as<int32_t>(), d_global, (long long)ctx->index_base, (int)cols,
-                                        ctx->subj_best.as<unsigned long long>(), s));
+        AFISCHK(queue_subject_best(ctx, subj, ctx->scores.as<float>()));
         HIPCHK(ctx, launch_case_fuse_subjects(ctx->subj_best.as<unsigned long long>(), (int)cols, d_off, d_member, (int)n_cases, mode, ctx->case_fused.as<float>(), s));
     } else HIPCHK(ctx, launch_case_fuse(ctx->scores.as<float>(), (int)cols, d_off, d_member, (int)n_cases, mode, ctx->case_fused.as<float>(), s));
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    // rows = the cases; entries = the columns: a template's global index (index_base + position, or the subset's d_global), or the id of a subject slot
-    HIPCHK(ctx, launch_rank_hits(ctx->case_fused.as<float>(), (int)n_cases, (int)cols, nullptr, 0, nullptr, subj ? subj->d_ids.as<long long>() : d_global, (long long)ctx->index_base,
-                                 thr, cap, (long long*)d_out, (long long*)(d_out + a_at), (float*)(d_out + score_at), nullptr, s));
-    HIPCHK(ctx, hipEventRecord(ev[2], s));
-    HIPCHK(ctx, hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    { const int rcw = wait_streams(ctx, {s}, who); if (rcw != AFIS_OK) { ctx->last_search.valid = false; return rcw; } }
-    float ms = 0, ms_f = 0, ms_r = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[2]));
-    HIPCHK(ctx, hipEventElapsedTime(&ms_f, ev[0], ev[1]));
-    HIPCHK(ctx, hipEventElapsedTime(&ms_r, ev[1], ev[2]));
-    ctx->rank_cases_us = (int64_t)((double)ms * 1e3); ctx->case_fuse_us = (int64_t)((double)ms_f * 1e3); ctx->case_rank_us = (int64_t)((double)ms_r * 1e3);
-    for (int64_t c = 0; c < n_cases; ++c) case_id[c] = ids[(size_t)c];
-    memcpy(n_hits, pin, (size_t)n_cases * 8); memcpy(out_a, pin + a_at, n_out * 8); memcpy(out_score, pin + score_at, n_out * 4);
+    // rows = the cases; entries = the columns: a template's global index (index_base + position, or the subset's table), or the id of a subject slot.  The template
+    // form either way: a fused subject row holds scores, and the folds compared rank_key
+    AFISCHK(hc.finish({ctx->case_fused.as<float>(), cols, nullptr, subj ? subj->d_ids.as<long long>() : global_map(ls), (long long)ctx->index_base}, min_score));
+    ctx->rank_cases_us = hc.total_us; ctx->case_fuse_us = hc.pre_us; ctx->case_rank_us = hc.rank_us;
+    std::copy(ids.begin(), ids.end(), case_id);
     return AFIS_OK;
 }
 
@@ -86,8 +57,7 @@ static int check_cases(afis_ctx* ctx, const char* who, const afis_subjects* s, c
 {
     const std::string w(who);
     if (mode != AFIS_CASE_SUM && mode != AFIS_CASE_MAX) return fail(ctx, AFIS_EINVAL, w + ": mode must be AFIS_CASE_SUM (0) or AFIS_CASE_MAX (1)");
-    const int rc = check_hits(ctx, who, n_q, min_score, cap, outputs && case_of, s);
-    if (rc != AFIS_OK) return rc;
+    AFISCHK(check_hits(ctx, who, n_q, min_score, cap, outputs && case_of, s));
     ids.assign(case_of, case_of + n_q);
     std::sort(ids.begin(), ids.end());
     if (!ids.empty() && ids.front() < 0) return fail(ctx, AFIS_EINVAL, w + ": a case id is negative");
@@ -114,7 +84,7 @@ int afis_rank_case_subject_hits(afis_ctx* ctx, afis_subjects* s, const int64_t* 
                                 int64_t* case_id, int64_t* n_hits, int64_t* subject_id, float* score)
 {
     if (!ctx || !s) return fail(ctx, AFIS_EINVAL, "afis_rank_case_subject_hits: null argument");
-    if (std::find(ctx->subject_sets.begin(), ctx->subject_sets.end(), s) == ctx->subject_sets.end()) return fail(ctx, AFIS_EINVAL, "afis_rank_case_subject_hits: not a live subject handle of this context");
+    AFISCHK(check_subject_handle(ctx, "afis_rank_case_subject_hits", s));
     std::vector<int64_t> ids;
     const int rc = check_cases(ctx, "afis_rank_case_subject_hits", s, case_of, n_q, mode, n_cases, min_score, cap, case_id && n_hits && subject_id && score, ids);
     return rc != AFIS_OK ? rc : rank_case_hits(ctx, s, case_of, mode, ids, min_score, cap, case_id, n_hits, subject_id, score);

@@ -1,5 +1,6 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
 #include "../../include/afis_matcher.h"
@@ -218,6 +219,21 @@ inline int fail(afis_ctx* ctx, int code, const std::string& msg)
         return fail(ctx, AFIS_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_) + (e_ == hipErrorOutOfMemory ?                                      \
             " (device memory: a launch group's buffers are sized from the memory that was free when the queries were uploaded - with several contexts or processes on one "  \
             "device lower option rowmax_budget_mb or query_batch)" : "")); } while (0)
+#define AFISCHK(call) do { const int rc_ = (call); if (rc_ != AFIS_OK) return rc_; } while (0)
+// a handle outlived an edit of the resident shard; `then`: what the handle was given for, and what to do now
+__attribute__((visibility("hidden"))) inline int fail_edited(afis_ctx* ctx, const char* who, const char* then, bool name_calls = true)
+{
+    return fail(ctx, AFIS_ESTATE, std::string(who) + ": the gallery was edited " + (name_calls ? "(afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) " : "") + "after " + then);
+}
+
+struct Events {                                     // the HIP events of one call (for (hipEvent_t& e : ev) creates them), destroyed when it returns
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    const int n;
+    explicit Events(int count) : n(count) {}  Events(const Events&) = delete;
+    __attribute__((visibility("hidden"))) ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t* begin() { return e; }  hipEvent_t* end() { return e + n; }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
 
 // the context's pinned read-back buffer, grown to at least `bytes` (nothing may be in flight into it)
 inline hipError_t ensure_pin(afis_ctx* ctx, size_t bytes)
@@ -322,10 +338,36 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
 // afis_hits.cpp
 // afis_rank_hits (subj == NULL: out_a = idx, out_b unused) and afis_rank_subject_hits (out_a = subject_id, out_b = best_idx) behind their argument checks.  Hidden, as rank_subjects.
 int rank_hits(afis_ctx* ctx, afis_subjects* subj, int n_q, float min_score, int cap, int64_t* n_hits, int64_t* out_a, float* out_score, int64_t* out_b) __attribute__((visibility("hidden")));
-// what the hit-list entry points ask of the context and of their plain arguments (the order of afis_rank_subjects' checks); afis_rank_latent_hits (afis_reverse.cpp) asks the same
+// The checks of the ranking calls, in the order every entry point makes them: a live subject handle of this context — the call's plain arguments (check_hits: the hit
+// lists'; afis_rank_subjects has its own) — then a committed gallery, a handle that labels the shard as it stands, the last search's matrix still there, and its n_q
+int check_subject_handle(afis_ctx* ctx, const char* who, const afis_subjects* s) __attribute__((visibility("hidden")));
+int check_last_search(afis_ctx* ctx, const char* who, int n_q, const afis_subjects* s) __attribute__((visibility("hidden")));
 int check_hits(afis_ctx* ctx, const char* who, int n_q, float min_score, int cap, bool outputs, const afis_subjects* s) __attribute__((visibility("hidden")));
-// the ordered form of a score word (minu.hip: ord_f32 without its + 0.0f; subject_rank.hip: sr_ord_f32)
-inline uint32_t ordered_word(float v) { uint32_t b; memcpy(&b, &v, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+inline const long long* global_map(const LastSearch& ls) { return ls.sub ? ls.sub->d_global.as<long long>() : nullptr; }   // a position of the last search's matrix -> global index: NULL (index_base + position) or the subset's table
+// k_subject_best over `matrix`, laid out as the last search's, into ctx->subj_best [n_q][S] (sized by the caller): the maxima every subject list is made of
+int queue_subject_best(afis_ctx* ctx, const afis_subjects* subj, const float* matrix) __attribute__((visibility("hidden")));
+// the end of a ranking call's device work: the bounded wait on the context's stream (a failed one clears last_search.valid), then the device time from the call's first event to its last and, where asked for, either side of ev[1]
+int wait_elapsed(afis_ctx* ctx, const char* who, const Events& ev, int64_t* total_us, int64_t* first_us = nullptr, int64_t* second_us = nullptr) __attribute__((visibility("hidden")));
+// What k_rank_hits ranks: scores [rows][cols], entry e of a row named map[e] or base + e — or, with a subject handle, the slots of ctx->subj_best [rows][S] as
+// queue_subject_best(subj, scores) left them (map / base then name a slot's best template).  The template form compares rank_key, the subject form the raw ordered word
+struct HitMatrix { const float* scores; int64_t cols; const afis_subjects* subj; const long long* map; long long base; };
+// One hit-list call, whatever it ranks: the entry points (afis_hits.cpp, afis_cases.cpp, afis_filter.cpp, afis_reverse.cpp) supply what differs, between its steps:
+//   empty(nothing was scored)   no list, or n_hits = 0 and padding: no device work
+//   begin(uploads)              after hipSetDevice and the caller's DevBuf::ensure()s: the rest of the room (every allocation precedes all device work: a failed one leaves
+//                               everything as it was), the caller's tables to the device — not timed; the host arrays live until finish() returns — then event 0
+//   finish(matrix, min_score)   after the caller's pre-passes: event 1, k_rank_hits, event 2, the lists to the pinned buffer, wait_elapsed, the lists into the caller's
+//                               arrays — list t as row out_row[t] (NULL: t).  total_us spans events 0 - 2, pre_us 0 - 1, rank_us 1 - 2; all 0 until finish() succeeds
+// rows: lists (queries, cases, prints); out_b NULL: the two-array form; hits_out and its pinned copy hold n_hits [rows] | a [rows][cap] | b [rows][cap] | score [rows][cap]
+struct __attribute__((visibility("hidden"))) HitCall {
+    afis_ctx* const ctx; const char* const who; const int64_t rows; const int cap;
+    int64_t* const n_hits; int64_t* const out_a; float* const out_score; int64_t* const out_b;
+    const size_t n_out = (size_t)rows * (size_t)cap, a_at = (size_t)rows * 8, b_at = a_at + n_out * 8, score_at = b_at + (out_b ? n_out * 8 : 0), out_bytes = score_at + n_out * 4;
+    Events ev{3}; int64_t total_us = 0, pre_us = 0, rank_us = 0;
+    struct H2D { void* dst; const void* src; size_t bytes; };                // (bytes 0: nothing to upload)
+    bool empty(bool nothing_scored);
+    int begin(std::initializer_list<H2D> uploads = {});
+    int finish(const HitMatrix& m, float min_score, const int32_t* out_row = nullptr);
+};
 // afis_filter.cpp
 void release_labels(afis_labels* l);                   // its device buffer and the handle itself
 

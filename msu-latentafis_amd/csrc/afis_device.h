@@ -4,8 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "score_order.h"
+
 namespace afis {
 
+typedef unsigned long long u64;
 constexpr int kM = 16;            // PQ sub-quantizers         (codebook header, matcher.cpp:74)
 constexpr int kK = 256;           // codewords per sub-quantizer
 constexpr int kDsub = 6;          // dims per sub-quantizer
@@ -285,6 +288,10 @@ hipError_t launch_filter_rows(const float* scores, int n_q, int G, const unsigne
                               float* filtered, hipStream_t stream);
 hipError_t launch_filter_drop_cells(const int32_t* pairs, size_t n_pairs, float* filtered, int n_q, int G, hipStream_t stream);
 hipError_t launch_filter_drop_subjects(const int32_t* pairs, size_t n_pairs, unsigned long long* best, int n_q, int S, hipStream_t stream);
+// what the row-walking launchers of case_fuse.hip and hit_filter.hip share: a thread takes four adjacent columns as one 16-byte word where every row of both matrices
+// starts on a 16-byte boundary, and a grid's second dimension holds 65 535 blocks (what lies beyond is walked in a loop; their one-dimensional grids stop there too)
+inline bool rows_take_16_bytes(int G, const void* a, const void* b) { return G % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+inline unsigned grid_clamp(size_t n) { return n < 65535 ? (unsigned)n : 65535u; }
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

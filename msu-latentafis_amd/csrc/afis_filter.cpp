@@ -23,60 +23,32 @@ static int rank_hits_filtered(afis_ctx* ctx, afis_subjects* subj, const afis_lab
 {
     const LastSearch ls = ctx->last_search;
     const int64_t G = ls.G, S = subj ? subj->S : 0;
-    const size_t n_out = (size_t)n_q * (size_t)cap, n_pairs = pairs.size() / 2;
-    const char* const who = subj ? "afis_rank_subject_hits_filtered" : "afis_rank_hits_filtered";
+    const size_t n_pairs = pairs.size() / 2;
+    HitCall hc{ctx, subj ? "afis_rank_subject_hits_filtered" : "afis_rank_hits_filtered", n_q, cap, n_hits, out_a, out_score, subj ? out_b : nullptr};
     ctx->rank_filtered_us = 0; ctx->filter_us = 0;
-    if (n_q == 0) return AFIS_OK;
-    if (G == 0 || (subj && S == 0)) {                                       // nothing was scored: no hit, every entry is padding
-        for (int i = 0; i < n_q; ++i) n_hits[i] = 0;
-        for (size_t o = 0; o < n_out; ++o) { out_a[o] = -1; out_score[o] = -INFINITY; if (subj) out_b[o] = -1; }
-        return AFIS_OK;
-    }
-    const uint32_t thr = ordered_word(subj ? min_score : min_score + 0.0f);  // afis_rank_hits' thresholds, unchanged
+    if (hc.empty(G == 0 || (subj && S == 0))) return AFIS_OK;
     // the copy is needed where cells change: by the masks, or by a template's exclusions (a subject's exclusions are dropped from the maxima)
     const bool copy = masks || (!subj && n_pairs > 0);
     const size_t mask_bytes = masks ? (size_t)n_q * 24 : 0, tab_bytes = mask_bytes + n_pairs * 8;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // room first: a failed allocation leaves everything as it was
     if (copy) HIPCHK(ctx, ctx->filt_scores.ensure((size_t)n_q * (size_t)G * 4));
     if (tab_bytes) HIPCHK(ctx, ctx->filt_tab.ensure(tab_bytes));
     if (subj) HIPCHK(ctx, ctx->subj_best.ensure((size_t)n_q * (size_t)S * 8));
-    const size_t a_at = (size_t)n_q * 8, b_at = a_at + n_out * 8, score_at = b_at + (subj ? n_out * 8 : 0), out_bytes = score_at + n_out * 4;
-    HIPCHK(ctx, ctx->hits_out.ensure(out_bytes));
-    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
-    hipStream_t s = ctx->stream;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 3; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } drop_ev{ev};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    const long long* const d_global = ls.sub ? ls.sub->d_global.as<long long>() : nullptr;
     uint8_t* const d_tab = ctx->filt_tab.as<uint8_t>();
+    AFISCHK(hc.begin({{d_tab, masks, mask_bytes}, {d_tab + mask_bytes, pairs.data(), n_pairs * 8}}));
+    hipStream_t s = ctx->stream;
+    const long long* const d_global = global_map(ls);
     const int32_t* const d_pairs = (const int32_t*)(d_tab + mask_bytes);
     const float* const ranked = copy ? ctx->filt_scores.as<float>() : ctx->scores.as<float>();   // neither masks nor exclusions: the search's matrix itself
-    uint8_t* const d_out = ctx->hits_out.as<uint8_t>();
-    uint8_t* const pin = (uint8_t*)ctx->h_pin;
-    if (masks) HIPCHK(ctx, hipMemcpyAsync(d_tab, masks, mask_bytes, hipMemcpyHostToDevice, s));            // (the caller's array and pairs live until the wait below)
-    if (n_pairs) HIPCHK(ctx, hipMemcpyAsync(d_tab + mask_bytes, pairs.data(), n_pairs * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
     if (masks) HIPCHK(ctx, launch_filter_rows(ctx->scores.as<float>(), n_q, (int)G, labels->d_label.as<unsigned long long>(), (const unsigned long long*)d_tab, d_global,
                                               (long long)ctx->index_base, ctx->filt_scores.as<float>(), s));
     else if (copy) HIPCHK(ctx, hipMemcpyAsync(ctx->filt_scores.p, ctx->scores.p, (size_t)n_q * (size_t)G * 4, hipMemcpyDeviceToDevice, s));
     if (subj) {                                                             // the maxima of the filtered rows, exactly as rank_hits makes them; then the excluded persons
-        HIPCHK(ctx, launch_subject_best(ranked, n_q, (int)G, subj->d_slot_of.as<int32_t>(), d_global, (long long)ctx->index_base, (int)S, ctx->subj_best.as<unsigned long long>(), s));
+        AFISCHK(queue_subject_best(ctx, subj, ranked));
         HIPCHK(ctx, launch_filter_drop_subjects(d_pairs, n_pairs, ctx->subj_best.as<unsigned long long>(), n_q, (int)S, s));
     } else HIPCHK(ctx, launch_filter_drop_cells(d_pairs, n_pairs, ctx->filt_scores.as<float>(), n_q, (int)G, s));
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    HIPCHK(ctx, launch_rank_hits(ranked, n_q, (int)G, subj ? ctx->subj_best.as<unsigned long long>() : nullptr, (int)S, subj ? subj->d_ids.as<long long>() : nullptr,
-                                 d_global, (long long)ctx->index_base, thr, cap, (long long*)d_out, (long long*)(d_out + a_at), (float*)(d_out + score_at),
-                                 subj ? (long long*)(d_out + b_at) : nullptr, s));
-    HIPCHK(ctx, hipEventRecord(ev[2], s));
-    HIPCHK(ctx, hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    { const int rcw = wait_streams(ctx, {s}, who); if (rcw != AFIS_OK) { ctx->last_search.valid = false; return rcw; } }
-    float ms = 0, ms_f = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[2]));
-    HIPCHK(ctx, hipEventElapsedTime(&ms_f, ev[0], ev[1]));
-    ctx->rank_filtered_us = (int64_t)((double)ms * 1e3); ctx->filter_us = (int64_t)((double)ms_f * 1e3);
-    memcpy(n_hits, pin, (size_t)n_q * 8); memcpy(out_a, pin + a_at, n_out * 8); memcpy(out_score, pin + score_at, n_out * 4);
-    if (subj) memcpy(out_b, pin + b_at, n_out * 8);
+    AFISCHK(hc.finish({ranked, G, subj, d_global, (long long)ctx->index_base}, min_score));   // afis_rank_hits' thresholds, unchanged
+    ctx->rank_filtered_us = hc.total_us; ctx->filter_us = hc.pre_us;
     return AFIS_OK;
 }
 
@@ -87,11 +59,10 @@ static int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s
     const std::string w(who);
     if (labels && std::find(ctx->label_sets.begin(), ctx->label_sets.end(), labels) == ctx->label_sets.end()) return fail(ctx, AFIS_EINVAL, w + ": not a live labels handle of this context");
     if (masks && !labels) return fail(ctx, AFIS_EINVAL, w + ": masks need a labels handle");
-    const int rc = check_hits(ctx, who, n_q, min_score, cap, outputs, s);
-    if (rc != AFIS_OK) return rc;
+    AFISCHK(check_hits(ctx, who, n_q, min_score, cap, outputs, s));
     // the labels are positions of the shard as it was: after an edit they may belong to other templates
     if (labels && labels->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, w + ": the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these labels were given; free the handle and create it again");
+        return fail_edited(ctx, who, "these labels were given; free the handle and create it again");
     pairs.clear();
     if (!excl_off) return AFIS_OK;
     if (excl_off[0] != 0) return fail(ctx, AFIS_EINVAL, w + ": excl_off[0] must be 0");
@@ -176,7 +147,7 @@ int afis_rank_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels
                                     int n_q, float min_score, int cap, int64_t* n_hits, int64_t* subject_id, float* subject_score, int64_t* best_idx)
 {
     if (!ctx || !s) return fail(ctx, AFIS_EINVAL, "afis_rank_subject_hits_filtered: null argument");
-    if (std::find(ctx->subject_sets.begin(), ctx->subject_sets.end(), s) == ctx->subject_sets.end()) return fail(ctx, AFIS_EINVAL, "afis_rank_subject_hits_filtered: not a live subject handle of this context");
+    AFISCHK(check_subject_handle(ctx, "afis_rank_subject_hits_filtered", s));
     std::vector<int32_t> pairs;
     const int rc = check_filtered(ctx, "afis_rank_subject_hits_filtered", s, labels, masks, excl_off, excl_subject, n_q, min_score, cap, n_hits && subject_id && subject_score && best_idx, pairs);
     return rc != AFIS_OK ? rc : rank_hits_filtered(ctx, s, labels, masks, pairs, n_q, min_score, cap, n_hits, subject_id, subject_score, best_idx);

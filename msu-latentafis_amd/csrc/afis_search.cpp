@@ -706,7 +706,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
             return fail(ctx, AFIS_EINVAL, "afis_search_resident: the resident shard holds " + std::to_string((long long)ctx->gal.G) + " templates, these queries were uploaded for at most " +
                                               std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
     } else if (q->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_search_resident: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these queries were uploaded; free the handle and upload them again");
+        return fail_edited(ctx, "afis_search_resident", "these queries were uploaded; free the handle and upload them again");
     return search_shard(ctx, *ctx, nullptr, q, scores, parts, status, k, topk_idx, topk_score);
 }
 

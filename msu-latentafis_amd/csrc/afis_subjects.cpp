@@ -14,9 +14,6 @@ void release_subjects(afis_subjects* s)
     delete s;
 }
 
-// the score word whose ordered form (subject_rank.hip: sr_ord_f32) is o
-static inline uint32_t score_bits_of(uint32_t o) { return (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o; }
-
 static void pad_entry(int64_t* id, float* score, int64_t* best) { *id = -1; *score = -INFINITY; *best = -1; }
 
 int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* subject_id, float* subject_score, int64_t* best_idx)
@@ -40,24 +37,18 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
         HIPCHK(ctx, ensure_pin(ctx, out_bytes));
     }
     hipStream_t s = ctx->stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } drop_ev{ev};
+    Events ev(2);
     for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    const long long* const d_global = ls.sub ? ls.sub->d_global.as<long long>() : nullptr;
     uint8_t* const d_out = ctx->subj_out.as<uint8_t>();
     uint8_t* const pin = (uint8_t*)ctx->h_pin;
     HIPCHK(ctx, hipEventRecord(ev[0], s));
-    HIPCHK(ctx, launch_subject_best(ctx->scores.as<float>(), n_q, (int)G, subj->d_slot_of.as<int32_t>(), d_global, (long long)ctx->index_base, (int)S,
-                                    ctx->subj_best.as<unsigned long long>(), s));
+    AFISCHK(queue_subject_best(ctx, subj, ctx->scores.as<float>()));
     if (dev_topk)
-        HIPCHK(ctx, launch_topk_subjects(ctx->subj_best.as<unsigned long long>(), n_q, (int)S, subj->d_ids.as<long long>(), ctx->scores.as<float>(), (int)G, d_global,
+        HIPCHK(ctx, launch_topk_subjects(ctx->subj_best.as<unsigned long long>(), n_q, (int)S, subj->d_ids.as<long long>(), ctx->scores.as<float>(), (int)G, global_map(ls),
                                          (long long)ctx->index_base, k, (long long*)d_out, (float*)(d_out + score_at), (long long*)(d_out + best_at), s));
     HIPCHK(ctx, hipEventRecord(ev[1], s));
     if (dev_topk) HIPCHK(ctx, hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    { const int rcw = wait_streams(ctx, {s}, "afis_rank_subjects"); if (rcw != AFIS_OK) { ctx->last_search.valid = false; return rcw; } }
-    float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->subject_rank_us = (int64_t)((double)ms * 1e3);
+    AFISCHK(wait_elapsed(ctx, "afis_rank_subjects", ev, &ctx->subject_rank_us));
     if (dev_topk) {
         memcpy(subject_id, pin, n_out * 8); memcpy(subject_score, pin + score_at, n_out * 4); memcpy(best_idx, pin + best_at, n_out * 8);
         return AFIS_OK;
@@ -72,13 +63,13 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
     for (int i = 0; i < n_q; ++i) {
         const unsigned long long* row = best.data() + (size_t)i * (size_t)S;
         keys.clear();
-        for (int64_t e = 0; e < S; ++e) if (row[e]) keys.push_back((row[e] & 0xffffffff00000000ull) | (uint32_t)(~(uint32_t)e));
+        for (int64_t e = 0; e < S; ++e) if (row[e]) keys.push_back(composite_at(row[e], (uint32_t)e));
         const size_t kk = std::min<size_t>((size_t)k, keys.size());
         std::partial_sort(keys.begin(), keys.begin() + kk, keys.end(), std::greater<unsigned long long>());
         for (int r = 0; r < k; ++r) {
             const size_t o = (size_t)i * k + r;
             if ((size_t)r >= kk) { pad_entry(subject_id + o, subject_score + o, best_idx + o); continue; }
-            const uint32_t slot = ~(uint32_t)keys[(size_t)r], pos = ~(uint32_t)row[slot], bits = score_bits_of((uint32_t)(keys[(size_t)r] >> 32));
+            const uint32_t slot = composite_position(keys[(size_t)r]), pos = composite_position(row[slot]), bits = score_bits_of(composite_word(keys[(size_t)r]));
             subject_id[o] = subj->ids[slot];
             memcpy(subject_score + o, &bits, 4);
             best_idx[o] = ls.sub ? global[pos] : ctx->index_base + (int64_t)pos;
@@ -143,15 +134,9 @@ void afis_subjects_free(afis_ctx* ctx, afis_subjects* s)
 int afis_rank_subjects(afis_ctx* ctx, afis_subjects* s, int n_q, int k, int64_t* subject_id, float* subject_score, int64_t* best_idx)
 {
     if (!ctx || !s) return fail(ctx, AFIS_EINVAL, "afis_rank_subjects: null argument");
-    if (std::find(ctx->subject_sets.begin(), ctx->subject_sets.end(), s) == ctx->subject_sets.end()) return fail(ctx, AFIS_EINVAL, "afis_rank_subjects: not a live subject handle of this context");
+    AFISCHK(check_subject_handle(ctx, "afis_rank_subjects", s));
     if (k <= 0 || !subject_id || !subject_score || !best_idx) return fail(ctx, AFIS_EINVAL, "afis_rank_subjects: k must be positive and the three output arrays given");
-    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_rank_subjects: commit the gallery first");
-    // the labels are positions of the shard as it was: after an edit they may name other templates
-    if (s->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_rank_subjects: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after these subjects were given; free the handle and create it again");
-    if (!ctx->last_search.valid || ctx->last_search.gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_rank_subjects: no score matrix to rank: call it after a search that succeeded, before any other call that queues device work or edits the gallery");
-    if (n_q != ctx->last_search.n_q) return fail(ctx, AFIS_EINVAL, "afis_rank_subjects: n_q is not the last search's");
+    AFISCHK(check_last_search(ctx, "afis_rank_subjects", n_q, s));
     return rank_subjects(ctx, s, n_q, k, subject_id, subject_score, best_idx);
 }
 

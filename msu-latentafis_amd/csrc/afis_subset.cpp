@@ -53,8 +53,7 @@ static int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32
     HIPCHK(ctx, upload_counted(ctx, sub->d_global, global, s));
     if (!sub->identity) HIPCHK(ctx, upload_counted(ctx, sub->d_pos, pos, s));
     // the gather: six launches, HIP events around them (option subset_gather_us)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } drop_ev{ev};
+    Events ev(2);
     for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
     HIPCHK(ctx, hipEventRecord(ev[0], s));
     for (const Arr& a : arrs)
@@ -73,11 +72,7 @@ static int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32
     sh.index_base = ctx->index_base;
     HIPCHK(ctx, launch_fragment_tiles(sh.g_minu_des.as<float>(), sh.g_minu_off.as<int32_t>(), sh.g_minu_tile_off.as<int32_t>(), (int)n, sh.g_minu_frag.p, s));
     if (ctx->adc_variant == 9) { const int rcg = ensure_mf_gallery(ctx, sh, s); if (rcg != AFIS_OK) return rcg; }     // (another variant: on the subset's first use, as for the shard)
-    { const int rcw = wait_streams(ctx, {s}, "afis_subset_create"); if (rcw != AFIS_OK) return rcw; }
-    float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->subset_gather_us = (int64_t)((double)ms * 1e3);
-    return AFIS_OK;
+    return wait_elapsed(ctx, "afis_subset_create", ev, &ctx->subset_gather_us);   // (afis_subset_create's quiesce() gave the last search's matrix up already)
 }
 
 }  // namespace afis
@@ -158,7 +153,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q, 
     if (std::find(ctx->subsets.begin(), ctx->subsets.end(), s) == ctx->subsets.end()) return fail(ctx, AFIS_EINVAL, "afis_search_subset: not a live subset of this context");
     // A subset is a copy of templates of the shard as it was: after an edit the copy may hold a template that has left, and the indices may mean other templates.
     if (s->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_search_subset: the gallery was edited (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) after this subset was created; free it and create it again");
+        return fail_edited(ctx, "afis_search_subset", "this subset was created; free it and create it again");
     // (the launch groups of a handle were cut for the whole shard, G >= n: they fit any subset of the same epoch)
     // (... and those of afis_queries_upload_reserved for a shard of max_templates templates: any subset up to that size, of any epoch)
     if (q->max_templates > 0) {
@@ -166,7 +161,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q, 
             return fail(ctx, AFIS_EINVAL, "afis_search_subset_resident: the subset lists " + std::to_string((long long)s->n) + " templates, these queries were uploaded for at most " +
                                               std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
     } else if (q->gallery_epoch != ctx->gallery_epoch)
-        return fail(ctx, AFIS_ESTATE, "afis_search_subset_resident: the gallery was edited after these queries were uploaded; free the handle and upload them again");
+        return fail_edited(ctx, "afis_search_subset_resident", "these queries were uploaded; free the handle and upload them again", false);
     return search_shard(ctx, s->sh, s, q, scores, parts, status, k, topk_idx, topk_score);
 }
 

@@ -138,7 +138,7 @@ int afis_debug_rank_rows(afis_ctx* ctx, afis_subset* sub, const float* scores, i
     if (!ctx || !scores || n_q <= 0 || k <= 0 || !topk_idx || !topk_score) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_rows: bad argument");
     if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_rows: commit the gallery first");
     if (sub && std::find(ctx->subsets.begin(), ctx->subsets.end(), sub) == ctx->subsets.end()) return fail(ctx, AFIS_EINVAL, "afis_debug_rank_rows: not a live subset of this context");
-    if (sub && sub->gallery_epoch != ctx->gallery_epoch) return fail(ctx, AFIS_ESTATE, "afis_debug_rank_rows: the gallery was edited after this subset was created");
+    if (sub && sub->gallery_epoch != ctx->gallery_epoch) return fail_edited(ctx, "afis_debug_rank_rows", "this subset was created", false);
     { const int rcq = quiesce(ctx, "afis_debug_rank_rows"); if (rcq != AFIS_OK) return rcq; }
     const Shard& sh = sub ? sub->sh : *ctx;
     const int64_t G = sh.gal.G;

@@ -3,7 +3,7 @@
 // rows as it ranks a search's.  The host hands the cases over as a CSR: case_off[n_cases + 1] into member[n_q], the query positions of a case in ascending order.
 //
 // The fused value of (case, column) over the case's members m, v_m the member's value in that column:
-//   a member TAKES PART when rank_key(v_m) >= rank_key(+0.0f) (rank_order.h), i.e. when the sign bit of v_m + 0.0f is clear: the -1 of an empty entry or of a
+//   a member TAKES PART when rank_key(v_m) >= rank_key(+0.0f) (score_order.h), i.e. when the sign bit of v_m + 0.0f is clear: the -1 of an empty entry or of a
 //   latent-empty query, every negative value and a NaN with the sign set stay out; -0.0 is the zero it equals
 //   kCaseSum  acc = +0.0f; for the members in ascending position: if the member takes part, acc = acc + v_m — one fp32 add each, in that order (the translation units
 //             are built with -ffp-contract=off, and nothing here lets the compiler reassociate); -1.0f when no member takes part
@@ -15,18 +15,14 @@
 // the unrolled loop has four rows in flight.  An odd G leaves rows unaligned: those matrices take the one-column form.
 // k_case_fuse_subjects: the same over best[n_q][S], the composites k_subject_best (subject_rank.hip) made (ordered score word << 32 | ~position; 0 = none of the
 // subject's templates was covered): the ordered word is turned back into the score's own bits and folded as above into a float row [n_cases][S].  A subject that was
-// not covered — the same slots for every query of a search — gets the word 0xffffffff: a NaN with the sign set, whose key lies below -inf's and so below every
-// min_score, which makes k_rank_hits neither count nor list it (include/afis_matcher.h states that property of the key).
+// not covered — the same slots for every query of a search — gets kNoEntryWord (score_order.h), which k_rank_hits neither counts nor lists (include/afis_matcher.h
+// states that property of the key).
 // Every index into the matrices is a size_t: n_q x G may pass 2^31.  A grid's second dimension holds 65 535 blocks; more cases than that are walked in a loop.
 #include "afis_device.h"
 
 namespace afis {
 
-typedef unsigned long long u64;
-
 constexpr int kCfThreads = 256;
-constexpr unsigned kCfMaxY = 65535;
-constexpr uint32_t kCfNoEntry = 0xffffffffu;                                // a sign-set NaN: ordered word 0, below every threshold k_rank_hits takes (thr >= 1)
 
 struct CfAcc { float v; uint32_t key; bool any; };
 
@@ -36,11 +32,10 @@ __device__ __forceinline__ void cf_start(CfAcc& a) { a.v = 0.0f; a.key = 0; a.an
 template <int kMode>
 __device__ __forceinline__ void cf_fold(CfAcc& a, float v)
 {
-    const uint32_t u = __float_as_uint(v + 0.0f);                           // rank_key's + 0.0f: -0.0 -> +0.0
     if (kMode == kCaseSum) {
-        if (!(u & 0x80000000u)) { a.v = a.v + v; a.any = true; }            // rank_key(v) >= rank_key(+0.0f)
+        if (reaches_zero(v)) { a.v = a.v + v; a.any = true; }               // the member takes part
     } else {
-        const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        const uint32_t key = rank_key(v);
         if (!a.any || key > a.key) { a.v = v; a.key = key; a.any = true; }   // strictly greater: the first member of the greatest key keeps its bits
     }
 }
@@ -90,24 +85,20 @@ __global__ __launch_bounds__(kCfThreads) void k_case_fuse_subjects(const u64* __
 #pragma unroll 4
         for (int m = m0; m < m1; ++m) {
             const u64 b = best[(size_t)member[m] * (size_t)S + col];
-            const uint32_t o = (uint32_t)(b >> 32);
             covered = covered && b != 0;
-            cf_fold<kMode>(acc, __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o));   // the score word whose ordered form is o
+            cf_fold<kMode>(acc, __uint_as_float(score_bits_of(composite_word(b))));
         }
-        fused[(size_t)c * (size_t)S + col] = covered ? cf_result<kMode>(acc) : __uint_as_float(kCfNoEntry);
+        fused[(size_t)c * (size_t)S + col] = covered ? cf_result<kMode>(acc) : __uint_as_float(kNoEntryWord);
     }
 }
 
-static inline dim3 cf_grid(size_t threads, int n_cases)
-{
-    return dim3((unsigned)((threads + kCfThreads - 1) / kCfThreads), (unsigned)n_cases < kCfMaxY ? (unsigned)n_cases : kCfMaxY);
-}
+static inline dim3 cf_grid(size_t threads, int n_cases) { return dim3((unsigned)((threads + kCfThreads - 1) / kCfThreads), grid_clamp((size_t)n_cases)); }
 
 hipError_t launch_case_fuse(const float* scores, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream)
 {
     if (n_cases <= 0 || G <= 0) return hipSuccess;
     if (!scores || !case_off || !member || !fused || (mode != kCaseSum && mode != kCaseMax)) return hipErrorInvalidValue;
-    const bool vec = G % 4 == 0 && (((uintptr_t)scores | (uintptr_t)fused) & 15) == 0;
+    const bool vec = rows_take_16_bytes(G, scores, fused);
     const dim3 grid = cf_grid(vec ? (size_t)G / 4 : (size_t)G, n_cases);
     if (mode == kCaseSum) {
         if (vec) hipLaunchKernelGGL((k_case_fuse<kCaseSum, true>), grid, dim3(kCfThreads), 0, stream, scores, G, case_off, member, n_cases, fused);

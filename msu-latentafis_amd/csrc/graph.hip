@@ -33,7 +33,6 @@
 namespace afis {
 
 #define AFIS_PI 3.1415926   /* matching/include.h:22 — a double literal; comparisons against it are in double */
-typedef unsigned long long u64;
 
 // optional per-phase cycle accounting (make PHASE_TIMING=1): slots 0..7 minutiae lists, 8..15 texture lists.  The stopwatch values are
 // accumulated in LDS (WaveSmem::ph) and flushed with one global atomic per slot at the end of the kernel: a global atomic inside
@@ -55,13 +54,7 @@ __device__ u64 g_graph_phase[16];
 #define GPH_FLUSH() do {} while (0)
 #endif
 
-__device__ __forceinline__ uint32_t g_ord_f32(float v)
-{
-    v = v + 0.0f;                                   // -0 -> +0 so that equal floats get equal keys
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ u64 g_make_key(float v, int idx) { return ((u64)g_ord_f32(v) << 32) | (uint32_t)(~(uint32_t)idx); }
+__device__ __forceinline__ u64 g_make_key(float v, int idx) { return rank_composite(rank_key(v), (uint32_t)idx); }
 __device__ __forceinline__ int g_wave_popc(bool p) { return __popcll(__ballot(p)); }
 __device__ __forceinline__ int g_lane_prefix(u64 mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0)); }
 // single-wave workgroup: orders this wave's LDS traffic (s_barrier is free for one wave)
@@ -223,7 +216,7 @@ __device__ __forceinline__ void sort_scores(SM& sm, int num, double thr)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int t = lane + 64 * u;
-        m32[u] = t < num ? g_ord_f32(sm.b[t]) : 0u;
+        m32[u] = t < num ? rank_key(sm.b[t]) : 0u;
         if (t < num) { s_key[t] = m32[u]; kmin = min(kmin, m32[u]); kmax = max(kmax, m32[u]); }
     }
 #pragma unroll
@@ -1000,7 +993,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                 for (int u = 0; u < kTexFastRegs; ++u) {
                     const int e = u * 64 + lane;
                     const bool in = e < n_in;
-                    key[u] = in ? g_ord_f32(rm_cv[o + e]) : 0u;              // real keys are never 0
+                    key[u] = in ? rank_key(rm_cv[o + e]) : 0u;              // real keys are never 0
                     arg[u] = in ? rm_arg[o + e] : 0;                         // fetched with the values: one round trip
                     kmax = max(kmax, key[u]);
                     if (in) kmin = min(kmin, key[u]);
@@ -1071,7 +1064,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                     const bool in = e < n_in;
                     key[u] = 0u; arg[u] = 0;                                 // real keys are never 0
                     if (u < n_regs) {                                        // uniform
-                        key[u] = in ? g_ord_f32(compact ? rm_cv[o + e] : rm_val[o + e]) : 0u;
+                        key[u] = in ? rank_key(compact ? rm_cv[o + e] : rm_val[o + e]) : 0u;
                         arg[u] = in ? rm_arg[o + e] : 0;                     // fetched with the values: one round trip, not one per picked row
                     }
                 }

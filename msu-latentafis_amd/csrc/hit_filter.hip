@@ -3,11 +3,11 @@
 // list — are taken out of a COPY of the matrix, and k_rank_hits (rank_hits.hip) and k_subject_best (subject_rank.hip) rank the copy as they rank a search's, unchanged.
 // The matrix itself is never written.
 //
-// An ineligible cell becomes the word 0xffffffff (kHfNoEntry; case_fuse.hip's kCfNoEntry): a NaN with the sign set whose ordered word is 0.
-//   templates  k_rank_hits takes thr >= 1 (the ordered word of -inf is 0x007fffff), so the cell is neither counted nor listed, whatever min_score is
+// An ineligible cell becomes kNoEntryWord (score_order.h), whose ordered word is 0.
+//   templates  k_rank_hits takes thr >= 1, so the cell is neither counted nor listed, whatever min_score is
 //   subjects   k_subject_best makes the composite (0 << 32 | ~position) of it: every eligible cell of the subject has an ordered word >= 1 and wins the maximum, and a
 //              subject left with ineligible cells only holds a composite whose high half is 0, which k_rank_hits<subjects> never counts (w >= thr fails)
-// A matrix cell that already holds 0xffffffff cannot be told from an ineligible one; a search never produces such a cell (its scores are -1 or finite values >= +0.0).
+// A matrix cell that already holds that word cannot be told from an ineligible one; a search never produces such a cell (its scores are -1 or finite values >= +0.0).
 //
 // The label test of cell (q, t), L the label of the template at column t, (any_of, all_of, none_of) = masks[q]:
 //   (any_of == 0 || (L & any_of) != 0) && (L & all_of) == all_of && (L & none_of) == 0
@@ -18,7 +18,7 @@
 // index depends on the block index and the loop counter only, so a query's three masks are uniform over the workgroup and are read as scalars.  A whole strip's
 // loads are issued before its first store, so kHfRows rows are in flight per thread; the last, shorter strip goes row by row.  No atomics, no cross-lane traffic.
 // k_filter_drop: the exclusions, as (row, column) pairs the host resolved (a full search's column is idx - index_base; a subset's device order is ascending global
-// index; a subject handle's ids are sorted): a 32-bit kHfNoEntry into the filtered matrix, or a 64-bit 0 ("no entry") into best[n_q][S] after k_subject_best ran.
+// index; a subject handle's ids are sorted): a 32-bit kNoEntryWord into the filtered matrix, or a 64-bit 0 ("no entry") into best[n_q][S] after k_subject_best ran.
 // Duplicated pairs write the same word twice.
 // Every index into the matrices is a size_t: n_q x G may pass 2^31.  A grid's second dimension holds 65 535 blocks; more strips than that are walked in a loop.
 #include "afis_device.h"
@@ -26,18 +26,13 @@
 
 namespace afis {
 
-typedef unsigned long long u64;
-
 constexpr int kHfThreads = 256;
-constexpr unsigned kHfMaxY = 65535;
-constexpr unsigned kHfMaxDropBlocks = 65535;
-constexpr uint32_t kHfNoEntry = 0xffffffffu;                                // a sign-set NaN: ordered word 0, below every threshold k_rank_hits takes (thr >= 1)
 constexpr int kHfRows = kFilterRows;                                        // query rows per strip (afis_device.h): the labels of a column are loaded once per strip
 
 __device__ __forceinline__ uint32_t hf_cell(uint32_t v, u64 L, u64 any_of, u64 all_of, u64 none_of)
 {
     const bool pass = (any_of == 0 || (L & any_of) != 0) && (L & all_of) == all_of && (L & none_of) == 0;
-    return pass ? v : kHfNoEntry;
+    return pass ? v : kNoEntryWord;
 }
 
 // scores, filtered [n_q][G]; labels [templates of the resident shard]; masks [n_q][3]; d_global NULL (full search: the template of position p is p) or [G] global indices
@@ -89,26 +84,21 @@ hipError_t launch_filter_rows(const float* scores, int n_q, int G, const unsigne
 {
     if (n_q <= 0 || G <= 0) return hipSuccess;
     if (!scores || !labels || !masks || !filtered || scores == filtered) return hipErrorInvalidValue;
-    const bool vec = G % 4 == 0 && (((uintptr_t)scores | (uintptr_t)filtered) & 15) == 0;
+    const bool vec = rows_take_16_bytes(G, scores, filtered);
     const size_t threads = vec ? (size_t)G / 4 : (size_t)G;
-    const unsigned strips = (unsigned)((n_q + kHfRows - 1) / kHfRows);
-    const dim3 grid((unsigned)((threads + kHfThreads - 1) / kHfThreads), strips < kHfMaxY ? strips : kHfMaxY);
+    const dim3 grid((unsigned)((threads + kHfThreads - 1) / kHfThreads), grid_clamp((size_t)((n_q + kHfRows - 1) / kHfRows)));
     if (vec) hipLaunchKernelGGL(k_filter_rows<true>, grid, dim3(kHfThreads), 0, stream, (const uint32_t*)scores, n_q, G, labels, masks, d_global, index_base, (uint32_t*)filtered);
     else hipLaunchKernelGGL(k_filter_rows<false>, grid, dim3(kHfThreads), 0, stream, (const uint32_t*)scores, n_q, G, labels, masks, d_global, index_base, (uint32_t*)filtered);
     return hipGetLastError();
 }
 
-static inline unsigned hf_drop_blocks(size_t n_pairs)
-{
-    const size_t b = (n_pairs + kHfThreads - 1) / kHfThreads;
-    return b < kHfMaxDropBlocks ? (unsigned)b : kHfMaxDropBlocks;
-}
+static inline unsigned hf_drop_blocks(size_t n_pairs) { return grid_clamp((n_pairs + kHfThreads - 1) / kHfThreads); }   // (a grid-stride loop walks the rest)
 
 hipError_t launch_filter_drop_cells(const int32_t* pairs, size_t n_pairs, float* filtered, int n_q, int G, hipStream_t stream)
 {
     if (n_pairs == 0) return hipSuccess;
     if (!pairs || !filtered || n_q <= 0 || G <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_filter_drop<uint32_t>, dim3(hf_drop_blocks(n_pairs)), dim3(kHfThreads), 0, stream, (const int2*)pairs, n_pairs, (uint32_t*)filtered, n_q, G, kHfNoEntry);
+    hipLaunchKernelGGL(k_filter_drop<uint32_t>, dim3(hf_drop_blocks(n_pairs)), dim3(kHfThreads), 0, stream, (const int2*)pairs, n_pairs, (uint32_t*)filtered, n_q, G, kNoEntryWord);
     return hipGetLastError();
 }
 

@@ -17,7 +17,6 @@ namespace afis {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-typedef unsigned long long u64;
 
 #ifdef AFIS_PHASE_TIMING
 // Development aid (make PHASE_TIMING=1): per-phase cycle shares as seen by thread 0 of every workgroup.  The stopwatch values are
@@ -34,13 +33,6 @@ __device__ u64 g_phase_cycles[32];
 #define PHASE_INIT() do {} while (0)
 #define PHASE(i) do {} while (0)
 #endif
-
-__device__ __forceinline__ uint32_t ord_f32(float v)
-{
-    v = v + 0.0f;                                   // -0 -> +0 so that equal floats get equal keys
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // Workgroup-wide sum of wave-uniform partial counts (each wave passes its own total).  One barrier per call.
 __device__ __forceinline__ int wg_sum(int wave_total, int* s_slots /*[2][kWaves]*/, int& parity)
@@ -277,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void k_minu_cands(QueryDev q, GalleryDev 
             const float sv = simi[e];
             float f = rowsum[i] + colsum[j];
             f = f - sv;
-            return ord_f32((float)((double)sv / ((double)f + 0.000001)));                        // :467
+            return rank_key((float)((double)sv / ((double)f + 0.000001)));                        // :467
         };
         if (ref_tie_order) {
             // The reference's own order of equal norms (matcher.cpp:473-476: std::sort of the indices 0 .. n-1 by norm, descending): every key of the task and the indices in
@@ -448,14 +440,14 @@ __device__ __forceinline__ uint32_t exact_norm_key(float sv, float rs, float cs)
 {
     float f = rs + cs;
     f = f - sv;
-    return ord_f32((float)((double)sv / ((double)f + 0.000001)));                               // matcher.cpp:467
+    return rank_key((float)((double)sv / ((double)f + 0.000001)));                               // matcher.cpp:467
 }
 __device__ __forceinline__ uint32_t approx_norm_key(float sv, float rs, float cs)
 {
     float f = rs + cs;
     f = f - sv;
     const float a = sv * __builtin_amdgcn_rcpf(f + 0.000001f);
-    return __float_as_uint(a) | 0x80000000u;                                                    // a >= 0: ord_f32's key
+    return __float_as_uint(a) | 0x80000000u;                                                    // a >= 0: rank_key's word
 }
 
 // Which rolled templates have work for which class in THIS launch (the class of a task follows from its two minutiae counts; the latent counts
@@ -1037,9 +1029,9 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk(const float* __restrict__
     const float* sc = scores + (size_t)qi * G;
     u64 prev = ~0ull;
     for (int r = 0; r < k; ++r) {
-        u64 best = 0;                                                     // every real composite is > 0 (ord_f32 >= 0x007fffff)
+        u64 best = 0;                                                     // every real composite is > 0 (rank_key >= 0x007fffff)
         for (int e = tid; e < G; e += kTopkThreads) {
-            const u64 c = ((u64)ord_f32(sc[e]) << 32) | (uint32_t)(~(uint32_t)e);
+            const u64 c = rank_composite(rank_key(sc[e]), (uint32_t)e);
             if (c < prev && c > best) best = c;
         }
 #pragma unroll

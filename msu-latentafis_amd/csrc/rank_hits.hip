@@ -1,8 +1,8 @@
 // rank_hits.hip — device code of the hit lists (afis_hits.cpp: afis_rank_hits, afis_rank_subject_hits): of the score matrix a search left on the device, per query
 // every entry whose score reaches a decision score — how many there are, and the `cap` best of them in rank-list order.  One kernel, k_rank_hits, in two
 // instantiations by what a row is:
-//   templates  the score row itself, [G] floats; the ordered word of an entry is k_topk's (minu.hip): ord(score + 0.0f), ties by ascending position
-//   subjects   best[query][0 .. S) as k_subject_best (subject_rank.hip) left it; the ordered word is the composite's high half (ord of the raw score word), ties by
+//   templates  the score row itself, [G] floats; the ordered word of an entry is k_topk's (minu.hip): rank_key(score) (score_order.h), ties by ascending position
+//   subjects   best[query][0 .. S) as k_subject_best (subject_rank.hip) left it; the ordered word is the composite's high half (ordered_word of the raw score word), ties by
 //              ascending slot = ascending subject id; a slot that is still 0 holds no template the search covered and is no entry
 // An entry QUALIFIES when its ordered word is >= thr, the ordered word of the decision score.  The lists are sorted by that same word, so the qualifying entries are a
 // prefix of k_topk's / k_topk_subjects' list whatever bits the matrix holds.
@@ -26,8 +26,6 @@
 
 namespace afis {
 
-typedef unsigned long long u64;
-
 constexpr int kRhThreads = 1024;
 constexpr int kRhWaves = kRhThreads / 64;
 constexpr int kRhPer = 4;                                                    // positions per thread and trip
@@ -40,10 +38,8 @@ struct RhSelect { uint32_t T, n_gt, n_eq, n_hits; };                         // 
 template <bool kSubjects>
 __device__ __forceinline__ bool rh_word(const float* __restrict__ sc, const u64* __restrict__ best, uint32_t e, uint32_t& w)
 {
-    if (kSubjects) { const u64 b = best[e]; w = (uint32_t)(b >> 32); return b != 0; }
-    const float v = sc[e] + 0.0f;                                            // -0 -> +0, as k_topk's key
-    const uint32_t u = __float_as_uint(v);
-    w = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    if (kSubjects) { const u64 b = best[e]; w = composite_word(b); return b != 0; }
+    w = rank_key(sc[e]);                                                     // k_topk's key
     return true;
 }
 
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(kRhThreads) void k_rank_hits(const float* __restric
             const uint32_t pre = before + mine;                             // (sums of at most 64 counts of at most 64: no carry between the halves)
             const uint32_t r_eq = carry_eq + (pre & 0xffffu) + (uint32_t)__popcll(b_eq[j] & below), r_gt = carry_gt + (pre >> 16) + (uint32_t)__popcll(b_gt[j] & below);
             const uint32_t slot = gt[j] ? r_gt : n_gt + r_eq;
-            if ((gt[j] || (eq[j] && r_eq < n_eq)) && slot < count) s_keys[slot] = ((u64)w[j] << 32) | (uint32_t)(~e[j]);   // (slot < count holds by the counts; it also keeps the store inside s_keys)
+            if ((gt[j] || (eq[j] && r_eq < n_eq)) && slot < count) s_keys[slot] = rank_composite(w[j], e[j]);   // (slot < count holds by the counts; it also keeps the store inside s_keys)
             before += row;
         }
         carry_eq += before & 0xffffu; carry_gt += before >> 16;
@@ -177,10 +173,10 @@ __global__ __launch_bounds__(kRhThreads) void k_rank_hits(const float* __restric
     if (tid == 0) out_n[qi] = (long long)sel.n_hits;
     for (uint32_t r = (uint32_t)tid; r < ucap; r += kRhThreads) {
         const size_t o = (size_t)qi * (size_t)cap + r;
-        const uint32_t e = r < count ? ~(uint32_t)s_keys[r] : n;             // < n: a composite is made from an entry of the row
+        const uint32_t e = r < count ? composite_position(s_keys[r]) : n;             // < n: a composite is made from an entry of the row
         if (e < n) {
             if (kSubjects) {
-                const uint32_t pos = ~(uint32_t)brow[e];                    // a position of the row: k_subject_best made the composite from one
+                const uint32_t pos = composite_position(brow[e]);                    // a position of the row: k_subject_best made the composite from one
                 if (pos < (uint32_t)G) { out_a[o] = ids[e]; out_score[o] = sc[pos]; out_b[o] = d_global ? d_global[pos] : index_base + (long long)pos; continue; }
             } else { out_a[o] = d_global ? d_global[e] : index_base + (long long)e; out_score[o] = sc[e]; continue; }
         }

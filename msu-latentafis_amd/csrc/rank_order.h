@@ -1,10 +1,8 @@
 // rank_order.h — the order of a rank list, stated once for every host path that makes or merges one.  Standard library only: usable from g++ alone.
 //
-// A template rank list is sorted on rank_key(score), descending; equal keys go by ascending GLOBAL index.  rank_key is minu.hip::ord_f32 — the key k_topk
-// (afis_search*, k <= 64) and rank_hits.hip (afis_rank_hits, afis_rank_latent_hits) sort on — so every path lists the same entries whatever bits the scores
-// hold: the two zeros are one value, and a NaN stands where its bits put it (above +inf with the sign clear, below -inf with it set) instead of breaking the
-// strict weak order a float comparison needs.  On NaN-free scores key order IS float order (a > b  <=>  rank_key(a) > rank_key(b), a == b  <=>  equal keys),
-// so nothing changes there.
+// A template rank list is sorted on rank_key(score) (score_order.h), descending; equal keys go by ascending GLOBAL index: the order of k_topk (afis_search*, k <= 64)
+// and rank_hits.hip (afis_rank_hits, afis_rank_latent_hits), so every path lists the same entries whatever bits the scores hold — a NaN stands where its bits put it
+// instead of breaking the strict weak order a float comparison needs.  On NaN-free scores key order IS float order (a > b  <=>  rank_key(a) > rank_key(b)).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -13,16 +11,9 @@
 #include <numeric>
 #include <vector>
 
-namespace afis {
+#include "score_order.h"
 
-// the ordered bits of s + 0.0f (-0.0 -> +0.0, so that equal floats get equal keys)
-inline uint32_t rank_key(float s)
-{
-    s = s + 0.0f;
-    uint32_t w;
-    memcpy(&w, &s, 4);
-    return (w & 0x80000000u) ? ~w : (w | 0x80000000u);
-}
+namespace afis {
 
 // "entry a stands before entry b" of a rank list: a strict total order while no global index repeats
 inline bool rank_before(float score_a, int64_t idx_a, float score_b, int64_t idx_b)

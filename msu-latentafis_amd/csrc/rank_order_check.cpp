@@ -1,4 +1,4 @@
-// rank_order_check — rank_order.h on score rows that hold NaNs, as a stand-alone program built with -fsanitize=address,undefined (csrc/Makefile): the sorts of
+// rank_order_check — rank_order.h on score rows that hold NaNs, and score_order.h on the words of every boundary of its order, as a stand-alone program built with -fsanitize=address,undefined (csrc/Makefile): the sorts of
 // afis_rank_list, of the search's host rank lists (k > 64) and of the exchange's merge must be defined behaviour and give ONE order whatever bits a row holds.
 //   rank_order_check                      every function on every row kind at n = 0, 1, 2, 15, 16, 17, 1000, 5000 (either side of libstdc++'s insertion-sort
 //                                         threshold, and well past it) against a model that sorts (key, index) pairs; exit 0 when all agree
@@ -140,6 +140,30 @@ static int check_all()
                         expect(ok, "merge of the shards' lists against the one-shard list", kind, n);
                     }
             }
+    // score_order.h itself: the words either side of every boundary of the order, and a stride through all of them
+    std::vector<uint32_t> words = {0x00000000u, 0x80000000u, 0x00000001u, 0x80000001u, 0x007fffffu, 0x807fffffu, 0x7f800000u, 0xff800000u, 0x7fc00000u, 0xffc00000u, 0x7fffffffu, 0xffffffffu, 0xbf800000u};
+    for (uint32_t i = 0; i < 65536u; ++i) words.push_back(i * 65537u);
+    bool inverse = true, increasing = true, key = true, takes_part = true, position = true;
+    for (uint32_t w : words) {
+        const float f = from_bits(w);
+        inverse = inverse && score_bits_of(ordered_word(w)) == w && ordered_word(f) == ordered_word(w);
+        key = key && rank_key(f) == ordered_word(bits_of(f + 0.0f));
+        takes_part = takes_part && reaches_zero(f) == (rank_key(f) >= rank_key(+0.0f));
+        for (uint32_t p : {0u, 1u, 0x7fffffffu}) {
+            const uint64_t c = rank_composite(ordered_word(w), p);
+            position = position && composite_position(c) == p && composite_word(c) == ordered_word(w) && composite_at(c, p ^ 1u) == rank_composite(ordered_word(w), p ^ 1u);
+        }
+        for (uint32_t v : {words[rnd() % words.size()], w + 1u, w ^ 0x80000000u}) {     // wherever the float order is strict, the words' is, the same way
+            const float g = from_bits(v);
+            if (f < g || f > g) increasing = increasing && (f < g) == (ordered_word(w) < ordered_word(v)) && ordered_word(w) != ordered_word(v);
+        }
+    }
+    expect(inverse, "score_bits_of inverts ordered_word", -1, (int64_t)words.size());
+    expect(increasing, "ordered_word increases with the float order", -1, (int64_t)words.size());
+    expect(key && takes_part, "rank_key is the ordered word of s + 0.0f, reaches_zero is rank_key(s) >= rank_key(+0.0f)", -1, (int64_t)words.size());
+    expect(position, "a composite gives its word and its position back", -1, (int64_t)words.size());
+    expect(rank_key(-0.0f) == rank_key(+0.0f) && ordered_word(-0.0f) < ordered_word(+0.0f), "the two zeros: one rank_key, two ordered words", -1, 2);
+    expect(ordered_word(kNoEntryWord) == 0u && ordered_word(from_bits(0xff800000u)) == 0x007fffffu, "the no-entry word lies below every threshold", -1, 1);
     printf("rank_order_check: %lld checks, %lld failures\n", cases, failures);
     return failures ? 1 : 0;
 }

@@ -17,18 +17,13 @@
 // the key is (ordered score bits << 32 | ~slot), and the slots are the distinct ids in ascending order, so equal scores go by ascending subject id.  A slot that is
 // still 0 belongs to a subject none of whose templates the search covered (a subset search) and is skipped.
 //
-// The ordered score bits are those of the raw word (the order adc_refine.hip's ord_f32 gives): -0.0 ranks below +0.0.  k_topk's own key adds +0.0f first and so
-// ranks the two zeros as equal; the two keys agree wherever no score is -0.0, and a fused score is (k_fuse: -1, or a sum of part scores, none of which is negative).
+// The ordered score bits are score_order.h's ordered_word, the raw word's, not k_topk's rank_key: the two agree on every fused score (k_fuse: -1, or a sum of part scores).
 #include "afis_device.h"
 
 namespace afis {
 
-typedef unsigned long long u64;
-
 constexpr int kSbThreads = 256;          // positions per workgroup of k_subject_best (four waves; the merge never leaves a wave)
 constexpr int kStThreads = 1024;         // k_topk_subjects: as k_topk
-
-__device__ __forceinline__ uint32_t sr_ord_f32(float v) { const uint32_t b = __float_as_uint(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 
 __device__ __forceinline__ u64 sr_shfl_up(u64 v, int d)
 {
@@ -49,7 +44,7 @@ __global__ __launch_bounds__(kSbThreads) void k_subject_best(const float* __rest
     int slot = -1;                                                          // lanes past the end of the row: a run of their own that issues nothing
     u64 c = 0;
     if (p < G) {
-        c = ((u64)sr_ord_f32(scores[qi * (size_t)G + p]) << 32) | (uint32_t)(~(uint32_t)p);
+        c = rank_composite(ordered_word(scores[qi * (size_t)G + p]), (uint32_t)p);
         slot = slot_of[d_global ? (int)(d_global[p] - index_base) : p];
     }
 #pragma unroll
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(kStThreads) void k_topk_subjects(const u64* __restr
         u64 top = 0;
         for (int e = tid; e < S; e += kStThreads) {
             const u64 b = row[e];
-            const u64 key = (b & 0xffffffff00000000ull) | (uint32_t)(~(uint32_t)e);
+            const u64 key = composite_at(b, (uint32_t)e);
             if (b != 0 && key < prev && key > top) top = key;
         }
 #pragma unroll
@@ -94,8 +89,8 @@ __global__ __launch_bounds__(kStThreads) void k_topk_subjects(const u64* __restr
             s_best = b;
             const size_t o = (size_t)qi * k + r;
             if (b) {
-                const uint32_t slot = ~(uint32_t)b;                          // < S: a key is made from a slot of the row
-                const uint32_t pos = ~(uint32_t)row[slot];                   // < G: a composite is made from a position of the row
+                const uint32_t slot = composite_position(b);                 // < S: a key is made from a slot of the row
+                const uint32_t pos = composite_position(row[slot]);          // < G: a composite is made from a position of the row
                 out_id[o] = ids[slot];
                 out_score[o] = scores[(size_t)qi * G + pos];
                 out_best[o] = d_global ? d_global[pos] : index_base + (long long)pos;

@@ -22,7 +22,7 @@ def _ordered(words: np.ndarray) -> np.ndarray:
 
 
 def rank_key(score) -> np.ndarray:
-    """csrc/rank_order.h::rank_key (minu.hip::ord_f32): the uint32 key a template rank list is sorted on, descending."""
+    """csrc/score_order.h::rank_key, stated in numpy: the uint32 key a template rank list is sorted on, descending."""
     return _ordered((np.asarray(score, np.float32) + np.float32(0.0)).view(np.uint32))
 
 
