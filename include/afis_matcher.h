@@ -361,10 +361,38 @@ int afis_rank_case_subject_hits(afis_ctx* ctx, afis_subjects* s, const int64_t* 
  * pinned room — the filtered copy, n_q x templates x 4 bytes in a buffer of its own, the masks and the resolved exclusions, n_q x subjects x 8 bytes for the subjects'
  * maxima, the outputs — is ensured before anything is queued: AFIS_EDEVICE, with nothing changed, when that fails.  No result of a search changes because these
  * functions exist.
- * Not in this interface: filters on the case lists and on the reverse (column) lists.  A case whose members carry different filters needs a "no eligible member" state
- * that AFIS_CASE_SUM's -1 does not have.
+ * The same eligibility filters the case lists and the reverse (column) lists:
+ * afis_rank_case_hits_filtered          afis_rank_case_hits, every column folded over the members that are eligible for it; excl holds GLOBAL template indices.
+ * afis_rank_case_subject_hits_filtered  afis_rank_case_subject_hits likewise; excl_subject holds subject ids.
+ * afis_rank_latent_hits_filtered        afis_rank_latent_hits over the eligible cells: per covered template, the queries that are eligible for it; excl holds GLOBAL
+ *                                       template indices.
+ * masks, excl_off and excl are per QUERY (n_q of the last search), as above, whatever the call lists: a case's members carry their own masks — "several fingers of one
+ * hand" is latent A an index or a middle finger, latent B a ring or a little finger — and a case-wide elimination list is that list repeated for each member.
+ * Filtered case lists: for case c and column j let E be the members of c that are eligible for j, in ascending query position.
+ *   templates  v_m is the matrix cell.
+ *   subjects   v_m is the person's best score among their covered templates that are eligible for member m, compared on the raw ordered word exactly as
+ *              afis_rank_subject_hits_filtered makes it; m is in E only if such a template exists and the person is not on m's exclusion list.
+ *   E empty    NO ENTRY: the column is neither counted nor listed for that case, whatever min_score is.  (An uncovered subject is uncovered for every member: the
+ *              unfiltered calls' "no entry, for every case alike" is this state.)
+ *   AFIS_CASE_SUM  acc = +0.0f; for m in E in ascending position, if m takes part, acc = acc + v_m — one fp32 add each, never reassociated, never contracted; -1.0f when
+ *                  E is not empty and no member of E takes part: that is an entry, listed when min_score <= -1
+ *   AFIS_CASE_MAX  the v_m of greatest rank_key over E, with the bits of the first such member
+ * Everything else — the rows and case_id, the key and the treatment of min_score, the tie rules, n_hits exceeding cap, the padding, min_score = -INFINITY — is
+ * afis_rank_case_hits' / afis_rank_case_subject_hits'.  With filters that pass every cell the outputs are entry for entry those of the unfiltered call.
+ * Filtered reverse lists: the key, the tie rule (ascending query position), latent_base, the padding and the row order for a subset listed out of order are
+ * afis_rank_latent_hits'; a template no query is eligible for has n_hits 0 and all padding.
+ * The caveat above carries over: a matrix cell that already held 0xffffffff could not be told from an ineligible one; a search never produces it.
+ * Every argument rule, AFIS_EINVAL / AFIS_ESTATE case, empty-shard and n_q == 0 answer of the two siblings a call combines applies unchanged, nothing is queued on a
+ * refusal, and which searches count, what invalidates the matrix and what leaves it alone are afis_rank_hits'.  All three calls leave the matrix rankable and unwritten
+ * and may be mixed with every other ranking call.  With neither masks nor exclusions they are their plain siblings, on the matrix itself.  Device and pinned room — the
+ * filtered copy, the fused or transposed matrix, the tables, the subjects' maxima, the outputs — is ensured before anything is queued: AFIS_EDEVICE, with nothing
+ * changed, when that fails.  On the device the filter pass above runs first, unchanged; the folds of case_fuse.hip then skip a member whose cell is no entry, and the
+ * transpose reads the copy.
+ * Not in this interface: a case spanning searches (a case cannot span searches, filtered or not), and filters on afis_search's own top-k and on afis_rank_subjects.
  * Shards: every rank labels its own shard and takes the same masks and exclusion lists; the columns of different shards are disjoint and a filtered maximum is still a
- * maximum, so the per-rank lists merge with host/sharding.py::merge_hits and merge_subject_hits as they are. */
+ * maximum, so the per-rank lists merge with host/sharding.py::merge_hits and merge_subject_hits as they are.  The filtered case template lists and the filtered column
+ * lists are merge_hits input as they are; the filtered case subject lists merge with merge_case_subject_hits under its conditions — exactly for AFIS_CASE_MAX, for
+ * AFIS_CASE_SUM only while no subject's prints lie in two shards. */
 typedef struct afis_labels afis_labels;
 int afis_labels_create(afis_ctx* ctx, const uint64_t* label /*[n]*/, int64_t n, afis_labels** out);
 void afis_labels_free(afis_ctx* ctx, afis_labels* labels);
@@ -375,6 +403,14 @@ int afis_rank_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels
                                     const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/,
                                     int n_q, float min_score, int cap, int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/,
                                     int64_t* best_idx /*[n_q][cap]*/);
+int afis_rank_case_hits_filtered(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                 const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                                 const int64_t* case_of /*[n_q]*/, int n_q, int mode, int64_t n_cases, float min_score, int cap,
+                                 int64_t* case_id /*[n_cases]*/, int64_t* n_hits /*[n_cases]*/, int64_t* idx /*[n_cases][cap]*/, float* score /*[n_cases][cap]*/);
+int afis_rank_case_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                         const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/,
+                                         const int64_t* case_of /*[n_q]*/, int n_q, int mode, int64_t n_cases, float min_score, int cap,
+                                         int64_t* case_id /*[n_cases]*/, int64_t* n_hits /*[n_cases]*/, int64_t* subject_id /*[n_cases][cap]*/, float* score /*[n_cases][cap]*/);
 
 /* Reverse search (no reference counterpart): every newly enrolled ten-print card is searched against the file of unsolved latents — the transaction that solves old cases.
  * The pair score is the forward search's; what differs is who stays on the device and which way the matrix is read.  The latents (about 260 KB each, against 50 KB per
@@ -402,6 +438,11 @@ int afis_rank_subject_hits_filtered(afis_ctx* ctx, afis_subjects* s, afis_labels
  * The P prints of one card fuse into one list per card with host/sharding.py::merge_prints_to_card.  No result of a search changes because these functions exist. */
 int afis_rank_latent_hits(afis_ctx* ctx, int64_t n_templates, float min_score, int cap, int64_t latent_base,
                           int64_t* n_hits /*[n_templates]*/, int64_t* latent_idx /*[n_templates][cap]*/, float* score /*[n_templates][cap]*/);
+/* afis_rank_latent_hits over the cells each query is eligible for (the contract stands with the filtered hit lists, above): n_q of masks and excl_off is the last search's */
+int afis_rank_latent_hits_filtered(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                   const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                                   int64_t n_templates, float min_score, int cap, int64_t latent_base,
+                                   int64_t* n_hits /*[n_templates]*/, int64_t* latent_idx /*[n_templates][cap]*/, float* score /*[n_templates][cap]*/);
 
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
@@ -498,11 +539,12 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * afis_subset_create's gather launches, from HIP events around them.  "subject_rank_us" (read-only): the device time of the last afis_rank_subjects' launches (the maxima's
  * memset, k_subject_best and, for k <= 64, k_topk_subjects), from HIP events around them.  "rank_hits_us" (read-only): the device time of the last afis_rank_hits' or
  * afis_rank_subject_hits' launches (k_rank_hits; for subjects the maxima's memset and k_subject_best before it), from HIP events around them; 0 when that call queued nothing.
- * "rank_latents_us" (read-only): the device time of the last afis_rank_latent_hits' launches (k_transpose_scores, then k_rank_hits on the transposed matrix), from HIP
- * events around them; 0 when that call queued nothing.  "rank_cases_us" (read-only): the device time of the last afis_rank_case_hits' or afis_rank_case_subject_hits'
- * launches (the fold of case_fuse.hip — for subjects behind the maxima's memset and k_subject_best — then k_rank_hits on the fused rows), from HIP events around them;
- * 0 when that call queued nothing.  "case_fuse_us" / "case_rank_us" (read-only): that call's two parts, each from its own pair of events — everything before k_rank_hits,
- * and k_rank_hits.  "rank_filtered_us" (read-only): the device time of the last afis_rank_hits_filtered's or afis_rank_subject_hits_filtered's launches (the filter pass
+ * "rank_latents_us" (read-only): the device time of the last afis_rank_latent_hits' or afis_rank_latent_hits_filtered's launches (for the filtered call the filter pass
+ * of hit_filter.hip first; k_transpose_scores, then k_rank_hits on the transposed matrix), from HIP events around them; 0 when that call queued nothing.
+ * "rank_cases_us" (read-only): the device time of the last call of the case family, plain or filtered — afis_rank_case_hits, afis_rank_case_subject_hits and their
+ * _filtered forms — (for a filtered call the filter pass first; the fold of case_fuse.hip — for subjects behind the maxima's memset, k_subject_best and the exclusions'
+ * drops — then k_rank_hits on the fused rows), from HIP events around them; 0 when that call queued nothing.  "case_fuse_us" / "case_rank_us" (read-only): that call's
+ * two parts, each from its own pair of events — everything before k_rank_hits (so a filtered call's filter pass too), and k_rank_hits.  "rank_filtered_us" (read-only): the device time of the last afis_rank_hits_filtered's or afis_rank_subject_hits_filtered's launches (the filter pass
  * of hit_filter.hip, for subjects the maxima's memset and k_subject_best, the exclusions' drops; then k_rank_hits), from HIP events around them; 0 when that call queued
  * nothing.  "filter_us" (read-only): of that call everything before k_rank_hits, from its own pair of events; 0 when the call queued nothing. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);

@@ -162,13 +162,13 @@ struct afis_ctx : Shard {
     DevBuf hits_out;                     // afis_rank_hits / afis_rank_subject_hits: n_hits [n_q] and the two or three [n_q][cap] output arrays behind one another
     int64_t rank_hits_us = 0;            // option rank_hits_us (read-only): device time of the last hit-list call's launches (HIP events around them)
     DevBuf scores_t;                     // afis_rank_latent_hits: the last search's matrix transposed, [n_templates][n_q] (its lists leave through hits_out)
-    int64_t rank_latents_us = 0;         // option rank_latents_us (read-only): device time of the last afis_rank_latent_hits' launches (k_transpose_scores, k_rank_hits)
-    int64_t transpose_us = 0, transpose_bytes = 0;   // k_transpose_scores alone in that call (its own pair of events) and the bytes it read and wrote (parity tap afis_debug_transpose_stats)
-    DevBuf case_fused, case_tab;         // afis_rank_case_hits / afis_rank_case_subject_hits: the fused matrix [n_cases][columns] floats, and the cases' CSR (case_off [n_cases + 1] | member [n_q], int32); the lists leave through hits_out
-    int64_t rank_cases_us = 0;           // option rank_cases_us (read-only): device time of the last case-list call's launches (the fold, for subjects behind the maxima's memset and k_subject_best; then k_rank_hits)
+    int64_t rank_latents_us = 0;         // option rank_latents_us (read-only): device time of the last afis_rank_latent_hits' or afis_rank_latent_hits_filtered's launches (the filtered call's filter pass; k_transpose_scores, k_rank_hits)
+    int64_t transpose_us = 0, transpose_bytes = 0;   // k_transpose_scores alone in that call — behind the filter pass in a filtered call — (its own pair of events) and the bytes it read and wrote (parity tap afis_debug_transpose_stats)
+    DevBuf case_fused, case_tab;         // afis_rank_case_hits / afis_rank_case_subject_hits and their _filtered forms: the fused matrix [n_cases][columns] floats, and the cases' CSR (case_off [n_cases + 1] | member [n_q], int32); the lists leave through hits_out
+    int64_t rank_cases_us = 0;           // option rank_cases_us (read-only): device time of the last case-list call's launches, plain or filtered (a filtered call's filter pass; the fold, for subjects behind the maxima's memset, k_subject_best and the drops; then k_rank_hits)
     int64_t case_fuse_us = 0, case_rank_us = 0;   // options case_fuse_us / case_rank_us (read-only): that time's two parts, each from its own pair of events: everything before k_rank_hits, and k_rank_hits
     std::vector<afis_labels*> label_sets;   // live label handles (afis_labels_create .. afis_labels_free; afis_destroy releases what is left)
-    DevBuf filt_scores, filt_tab;        // afis_rank_hits_filtered / afis_rank_subject_hits_filtered: the filtered copy of the matrix [n_q][G] floats, and the call's tables (masks [n_q][3] uint64 | the exclusions' (row, column) pairs, int32 x 2); the lists leave through hits_out
+    DevBuf filt_scores, filt_tab;        // every filtered ranking call (FilterPass): the filtered copy of the matrix [n_q][G] floats, and the call's tables (masks [n_q][3] uint64 | the exclusions' (row, column) pairs, int32 x 2); the lists leave through hits_out
     int64_t rank_filtered_us = 0;        // option rank_filtered_us (read-only): device time of the last filtered call's launches (the filter pass, for subjects the maxima's memset and k_subject_best, the drops; then k_rank_hits)
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
@@ -370,5 +370,30 @@ struct __attribute__((visibility("hidden"))) HitCall {
 };
 // afis_filter.cpp
 void release_labels(afis_labels* l);                   // its device buffer and the handle itself
+// The checks every filtered ranking call shares (afis_filter.cpp, afis_cases.cpp, afis_reverse.cpp), in the order of afis_rank_hits_filtered's: a live labels handle of this
+// context, masks with labels, check_hits, labels of the shard as it stands, a valid CSR.  On AFIS_OK pairs holds the exclusions that name something the last search
+// covered, as (row, column of the matrix — or slot of s)
+int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s, const afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
+                   int n_q, float min_score, int cap, bool outputs, std::vector<int32_t>& pairs) __attribute__((visibility("hidden")));
+// The filter pass of a filtered ranking call, whatever it ranks afterwards — the one definition of eligibility on the device (hit_filter.hip).  Between HitCall's steps:
+//   ensure()           with the caller's DevBuf::ensure()s: the filtered copy and the call's tables (masks | pairs)
+//   masks_up/pairs_up  the two uploads, for HitCall::begin
+//   queue_cells()      after begin(): the copy — launch_filter_rows, or a device-to-device copy where only cells are dropped — and the excluded templates' cells;
+//                      matrix() is then what the call ranks, folds or transposes: the copy, or the search's matrix itself where no cell changed
+//   queue_drop_subjects(S)  after queue_subject_best(matrix()): the excluded persons out of ctx->subj_best
+// subjects: pairs name (row, slot) and are dropped from the maxima, not from the cells.  filters() false: nothing is allocated, uploaded or queued
+struct __attribute__((visibility("hidden"))) FilterPass {
+    afis_ctx* const ctx; const afis_labels* const labels; const uint64_t* const masks; const std::vector<int32_t>& pairs; const bool subjects;
+    const int n_q = ctx->last_search.n_q; const int64_t G = ctx->last_search.G;
+    const size_t n_pairs = pairs.size() / 2, mask_bytes = masks ? (size_t)n_q * 24 : 0, tab_bytes = mask_bytes + n_pairs * 8;
+    const bool copy = masks || (!subjects && n_pairs > 0);              // the copy is needed where cells change: by the masks, or by a template's exclusions
+    bool filters() const { return masks || n_pairs > 0; }
+    hipError_t ensure();
+    HitCall::H2D masks_up() const { return {ctx->filt_tab.p, masks, mask_bytes}; }
+    HitCall::H2D pairs_up() const { return {ctx->filt_tab.as<uint8_t>() + mask_bytes, pairs.data(), n_pairs * 8}; }
+    const float* matrix() const { return copy ? ctx->filt_scores.as<float>() : ctx->scores.as<float>(); }
+    int queue_cells();
+    int queue_drop_subjects(int64_t S);
+};
 
 }  // namespace afis

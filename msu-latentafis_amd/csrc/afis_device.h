@@ -278,6 +278,11 @@ hipError_t launch_transpose_scores(const float* in, float* out, int n_q, int n, 
 constexpr int kCaseSum = 0, kCaseMax = 1;                // AFIS_CASE_SUM, AFIS_CASE_MAX
 hipError_t launch_case_fuse(const float* scores, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
 hipError_t launch_case_fuse_subjects(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
+// afis_rank_case_hits_filtered / afis_rank_case_subject_hits_filtered: the same folds over what the filter pass below left — filtered [n_q][G], or best [n_q][S] made of
+// it with the excluded persons dropped.  A member whose cell is the word 0xffffffff, or whose composite has a zero score word, is not folded; a column without a folded
+// member gets 0xffffffff (no entry), one whose folded members all hold -1 is kCaseSum's -1.0f
+hipError_t launch_case_fuse_eligible(const float* filtered, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
+hipError_t launch_case_fuse_subjects_eligible(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
 // afis_rank_hits_filtered / afis_rank_subject_hits_filtered (hit_filter.hip): filtered [n_q][G] = scores [n_q][G] with every cell whose column's label fails the row's
 // masks [n_q][3] (any_of, all_of, none_of) replaced by the word 0xffffffff, which launch_rank_hits never counts and launch_subject_best turns into a composite that is
 // never counted; labels [templates of the resident shard], the label of position p is labels[p], or labels[d_global[p] - index_base] for a subset's matrix.  A thread

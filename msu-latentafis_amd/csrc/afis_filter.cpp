@@ -16,6 +16,29 @@ void release_labels(afis_labels* l)
     delete l;
 }
 
+hipError_t FilterPass::ensure()
+{
+    if (copy) { const hipError_t e = ctx->filt_scores.ensure((size_t)n_q * (size_t)G * 4); if (e != hipSuccess) return e; }
+    return tab_bytes ? ctx->filt_tab.ensure(tab_bytes) : hipSuccess;
+}
+
+int FilterPass::queue_cells()
+{
+    hipStream_t s = ctx->stream;
+    const LastSearch& ls = ctx->last_search;
+    if (masks) HIPCHK(ctx, launch_filter_rows(ctx->scores.as<float>(), n_q, (int)G, labels->d_label.as<unsigned long long>(), ctx->filt_tab.as<unsigned long long>(), global_map(ls),
+                                              (long long)ctx->index_base, ctx->filt_scores.as<float>(), s));
+    else if (copy) HIPCHK(ctx, hipMemcpyAsync(ctx->filt_scores.p, ctx->scores.p, (size_t)n_q * (size_t)G * 4, hipMemcpyDeviceToDevice, s));
+    if (!subjects) HIPCHK(ctx, launch_filter_drop_cells((const int32_t*)(ctx->filt_tab.as<uint8_t>() + mask_bytes), n_pairs, ctx->filt_scores.as<float>(), n_q, (int)G, s));
+    return AFIS_OK;
+}
+
+int FilterPass::queue_drop_subjects(int64_t S)
+{
+    HIPCHK(ctx, launch_filter_drop_subjects((const int32_t*)(ctx->filt_tab.as<uint8_t>() + mask_bytes), n_pairs, ctx->subj_best.as<unsigned long long>(), n_q, (int)S, ctx->stream));
+    return AFIS_OK;
+}
+
 // both entry points behind their checks (subj == NULL: the templates; out_a = idx, out_b unused).  masks NULL or [n_q][3]; pairs: the exclusions as (row, column) —
 // columns of the matrix for the templates, slots of the handle for the subjects — already inside the matrix
 static int rank_hits_filtered(afis_ctx* ctx, afis_subjects* subj, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, int n_q, float min_score, int cap,
@@ -23,38 +46,27 @@ static int rank_hits_filtered(afis_ctx* ctx, afis_subjects* subj, const afis_lab
 {
     const LastSearch ls = ctx->last_search;
     const int64_t G = ls.G, S = subj ? subj->S : 0;
-    const size_t n_pairs = pairs.size() / 2;
     HitCall hc{ctx, subj ? "afis_rank_subject_hits_filtered" : "afis_rank_hits_filtered", n_q, cap, n_hits, out_a, out_score, subj ? out_b : nullptr};
     ctx->rank_filtered_us = 0; ctx->filter_us = 0;
     if (hc.empty(G == 0 || (subj && S == 0))) return AFIS_OK;
-    // the copy is needed where cells change: by the masks, or by a template's exclusions (a subject's exclusions are dropped from the maxima)
-    const bool copy = masks || (!subj && n_pairs > 0);
-    const size_t mask_bytes = masks ? (size_t)n_q * 24 : 0, tab_bytes = mask_bytes + n_pairs * 8;
+    FilterPass fp{ctx, labels, masks, pairs, subj != nullptr};
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (copy) HIPCHK(ctx, ctx->filt_scores.ensure((size_t)n_q * (size_t)G * 4));
-    if (tab_bytes) HIPCHK(ctx, ctx->filt_tab.ensure(tab_bytes));
+    HIPCHK(ctx, fp.ensure());
     if (subj) HIPCHK(ctx, ctx->subj_best.ensure((size_t)n_q * (size_t)S * 8));
-    uint8_t* const d_tab = ctx->filt_tab.as<uint8_t>();
-    AFISCHK(hc.begin({{d_tab, masks, mask_bytes}, {d_tab + mask_bytes, pairs.data(), n_pairs * 8}}));
-    hipStream_t s = ctx->stream;
-    const long long* const d_global = global_map(ls);
-    const int32_t* const d_pairs = (const int32_t*)(d_tab + mask_bytes);
-    const float* const ranked = copy ? ctx->filt_scores.as<float>() : ctx->scores.as<float>();   // neither masks nor exclusions: the search's matrix itself
-    if (masks) HIPCHK(ctx, launch_filter_rows(ctx->scores.as<float>(), n_q, (int)G, labels->d_label.as<unsigned long long>(), (const unsigned long long*)d_tab, d_global,
-                                              (long long)ctx->index_base, ctx->filt_scores.as<float>(), s));
-    else if (copy) HIPCHK(ctx, hipMemcpyAsync(ctx->filt_scores.p, ctx->scores.p, (size_t)n_q * (size_t)G * 4, hipMemcpyDeviceToDevice, s));
+    AFISCHK(hc.begin({fp.masks_up(), fp.pairs_up()}));
+    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is ranked
     if (subj) {                                                             // the maxima of the filtered rows, exactly as rank_hits makes them; then the excluded persons
-        AFISCHK(queue_subject_best(ctx, subj, ranked));
-        HIPCHK(ctx, launch_filter_drop_subjects(d_pairs, n_pairs, ctx->subj_best.as<unsigned long long>(), n_q, (int)S, s));
-    } else HIPCHK(ctx, launch_filter_drop_cells(d_pairs, n_pairs, ctx->filt_scores.as<float>(), n_q, (int)G, s));
-    AFISCHK(hc.finish({ranked, G, subj, d_global, (long long)ctx->index_base}, min_score));   // afis_rank_hits' thresholds, unchanged
+        AFISCHK(queue_subject_best(ctx, subj, fp.matrix()));
+        AFISCHK(fp.queue_drop_subjects(S));
+    }
+    AFISCHK(hc.finish({fp.matrix(), G, subj, global_map(ls), (long long)ctx->index_base}, min_score));   // afis_rank_hits' thresholds, unchanged
     ctx->rank_filtered_us = hc.total_us; ctx->filter_us = hc.pre_us;
     return AFIS_OK;
 }
 
-// the checks both entry points share, in the order of afis_rank_hits'; on AFIS_OK pairs holds the exclusions that name something the search covered, as (row, column or slot)
-static int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s, const afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
-                          int n_q, float min_score, int cap, bool outputs, std::vector<int32_t>& pairs)
+// the checks every filtered ranking call shares, in the order of afis_rank_hits'; on AFIS_OK pairs holds the exclusions that name something the search covered, as (row, column or slot)
+int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s, const afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
+                   int n_q, float min_score, int cap, bool outputs, std::vector<int32_t>& pairs)
 {
     const std::string w(who);
     if (labels && std::find(ctx->label_sets.begin(), ctx->label_sets.end(), labels) == ctx->label_sets.end()) return fail(ctx, AFIS_EINVAL, w + ": not a live labels handle of this context");

@@ -56,6 +56,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
+           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -117,6 +118,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_labels_free.argtypes = [vp, vp]; lib.afis_labels_free.restype = None
         lib.afis_rank_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_float, C.c_int, i64p, i64p, fp]
         lib.afis_rank_subject_hits_filtered.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, C.c_float, C.c_int, i64p, i64p, fp, i64p]
+    if hasattr(lib, "afis_rank_case_hits_filtered"):                    # filtered case and column lists; absent from older builds compared by tools/lib_ab.py
+        lib.afis_rank_case_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
+        lib.afis_rank_case_subject_hits_filtered.argtypes = [vp, vp, vp, u64p, i64p, i64p, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
+        lib.afis_rank_latent_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -552,6 +557,30 @@ class Matcher:
         return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_subject_hits(self.ctx, handle[0], co, nq, mode, nc, min_score, cap, cid, nh, a, sc),
                                 case_of, cap, True)
 
+    @staticmethod
+    def _filter_ptrs(labels, mk, off, ent):
+        """_filter_args' arrays and a labels_create handle as the four leading filter arguments of the C calls."""
+        return (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+                _ptr(ent, C.c_int64) if ent is not None else None)
+
+    def rank_case_hits_filtered(self, case_of: Sequence[int], mode: int, min_score: float, cap: int, labels=None, masks=None, excl=None):
+        """rank_case_hits, every column folded over the members that are ELIGIBLE for it.  labels / masks / excl are rank_hits_filtered's, per QUERY position (a case-wide
+        elimination list is that list repeated for each member).  A column no member of the case is eligible for is no entry: neither counted nor listed, whatever
+        min_score is; one whose eligible members all hold -1 is CASE_SUM's -1, listed when min_score <= -1."""
+        co = np.asarray(case_of, np.int64).reshape(-1)
+        mk, off, ent = self._filter_args(len(co), masks, excl)
+        f = self._filter_ptrs(labels, mk, off, ent)
+        return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_hits_filtered(self.ctx, *f, co, nq, mode, nc, min_score, cap, cid, nh, a, sc), co, cap, False)
+
+    def rank_case_subject_hits_filtered(self, handle, case_of: Sequence[int], mode: int, min_score: float, cap: int, labels=None, masks=None, excl=None):
+        """rank_case_subject_hits over the eligible members: a member's value is the person's best score among their covered templates that are eligible for that
+        member; excl: per query a sequence of SUBJECT ids.  A person no member is eligible for is neither counted nor listed."""
+        co = np.asarray(case_of, np.int64).reshape(-1)
+        mk, off, ent = self._filter_args(len(co), masks, excl)
+        f = self._filter_ptrs(labels, mk, off, ent)
+        return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_subject_hits_filtered(self.ctx, handle[0], *f, co, nq, mode, nc, min_score, cap, cid, nh, a, sc),
+                                co, cap, True)
+
     # ---- reverse search: the last search's matrix ranked along its columns -----------------------------------------
     def _latent_lists(self, fn, n_templates: int, cap: int):
         c = max(cap, 0)
@@ -565,6 +594,16 @@ class Matcher:
         descending, equal scores by ascending position — padded with (-1, -inf).  n_templates defaults to the columns of the last search call made through this object."""
         n = self.last_n_templates if n_templates is None else n_templates
         return self._latent_lists(lambda nt, nh, li, sc: self.lib.afis_rank_latent_hits(self.ctx, nt, min_score, cap, latent_base, nh, li, sc), n, cap)
+
+    def rank_latent_hits_filtered(self, min_score: float, cap: int, latent_base: int = 0, labels=None, masks=None, excl=None, n_templates: Optional[int] = None,
+                                  n_q: Optional[int] = None):
+        """rank_latent_hits over the cells each query is eligible for: per covered template only the queries whose masks its label passes and that do not exclude it.
+        labels / masks / excl are rank_hits_filtered's, per QUERY position of the last search (n_q defaults as there); a template no query is eligible for has
+        n_hits 0 and all padding."""
+        n = self.last_n_templates if n_templates is None else n_templates
+        mk, off, ent = self._filter_args(self.last_n_q if n_q is None else n_q, masks, excl)
+        f = self._filter_ptrs(labels, mk, off, ent)
+        return self._latent_lists(lambda nt, nh, li, sc: self.lib.afis_rank_latent_hits_filtered(self.ctx, *f, nt, min_score, cap, latent_base, nh, li, sc), n, cap)
 
     def rank_latents(self, k: int, latent_base: int = 0, n_templates: Optional[int] = None):
         """The k best latents of every template the last search covered: rank_latent_hits with min_score = -inf, without the counts."""
