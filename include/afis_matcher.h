@@ -444,6 +444,47 @@ int afis_rank_latent_hits_filtered(afis_ctx* ctx, afis_labels* labels /*or NULL*
                                    int64_t n_templates, float min_score, int cap, int64_t latent_base,
                                    int64_t* n_hits /*[n_templates]*/, int64_t* latent_idx /*[n_templates][cap]*/, float* score /*[n_templates][cap]*/);
 
+/* Eligible search (no reference counterpart): the filters above run at ranking time, after every pair has been scored; with masks that pass a tenth of the cells nine
+ * tenths of the search's work goes into cells the next call removes.  afis_search_eligible scores a (query, template) pair only where the query is ELIGIBLE for the
+ * template and leaves a matrix the whole ranking family reads unchanged.  labels and masks [n_q][3] are both required (AFIS_EINVAL when either is NULL).
+ * Eligibility of cell (q, t) is the label test of the filtered hit lists, word for word, L the label of resident template index_base + t:
+ *   (any_of == 0 || (L & any_of) != 0) && (L & all_of) == all_of && (L & none_of) == 0
+ * Values   an eligible cell holds, bit for bit, the value afis_search gives that pair under every option (an empty or removed entry and a latent-empty query give their
+ *          -1); an ineligible cell holds the word 0xffffffff, the "no entry" word of the filtered lists (csrc/score_order.h: kNoEntryWord) — in the matrix left on
+ *          the device and in scores [n_q][G] (NULL: not copied).  status [n_q] (or NULL) is afis_search's.
+ * The matrix afterwards   after AFIS_OK the context's last-search matrix is this [n_q][G] matrix: a full search's in every respect — no subset, the resident shard as
+ *          it stands — under afis_search's invalidation rules; the call is one of the searches that count.  Consequences:
+ *            - afis_rank_hits, afis_rank_subject_hits and afis_rank_latent_hits on it return exactly what their _filtered forms return after a full search with the
+ *              same labels and masks and no exclusions;
+ *            - the _filtered calls with the same labels and masks, with or without exclusion lists, return exactly what they return after a full search: the filter
+ *              pass re-marks cells that are marked already.  The CASE lists must be read this way: the plain case folds turn a no-entry member into "takes no part"
+ *              and so list -1 where the filtered folds list no entry;
+ *            - exclusion lists stay a ranking-time matter: they are a few cells and save no scoring;
+ *            - afis_rank_subjects, rank lists of afis_search's own kind (k, topk_idx) and parts are not in this interface: afis_rank_subjects on this matrix would
+ *              take the no-entry word for a score.
+ * How     the queries are grouped into CLASSES of identical mask triples, in order of first query position.  A class's eligible templates, in ascending index, are
+ *          gathered into a temporary sub-shard through afis_subset_create's path and searched with afis_search_subset's launch sequence — no scoring kernel knows
+ *          of it, and a score depends on nothing but its pair — then one pass (csrc/eligible_expand.hip) writes every word of the class's rows of the combined
+ *          matrix once.  One temporary sub-shard is live at a time, in buffers that only grow from class to class; it is never a subset of the caller's: option
+ *          "subset_device_bytes", "subset_gather_us" and "gallery_h2d_bytes" read as before, and it is released before the call returns.  A class that passes every
+ *          template — the triple (0, 0, 0), or any triple the whole shard passes — runs on the resident shard itself, with no copy; a class no template passes
+ *          scores nothing: its rows are all no entry, its status is still afis_search's.  The combined matrix lives in a buffer of its own ([n_q][G] floats beside
+ *          the search's) whose room, with the call's tables, is ensured before anything is queued.
+ *          It PAYS WHEN LATENTS SHARE MASKS: every class costs a sub-shard (tables, derived layouts, waits) and a launch sequence of its own, whatever its size
+ *          (DESIGN section 7, row 13 has the measurements; merging small classes into one search over the union of their templates is a follow-up).
+ * Arguments   AFIS_EINVAL: labels or masks NULL, n_q < 0, n_q > 0 with queries NULL, a labels handle not live in this context, a bad latent view (as afis_search);
+ *          AFIS_ESTATE: a call before the first commit, a labels handle from before a gallery edit (afis_rank_hits_filtered's rules).  n_q == 0 returns AFIS_OK as
+ *          afis_search with no queries does.  On any failure in the middle the call returns that code and holds nothing it allocated; the last-search matrix is
+ *          invalid; the caller's own live subsets and query handles are untouched.  A timeout follows afis_search_subset's rules (option "search_timeout_s").
+ * Timing   afis_get_timing*: every additive field is the sum over the searches the call ran — pairs is the number of pairs actually SCORED, the sum over the classes
+ *          of queries x eligible templates — and the two clock fields come from the search with the most pairs.  Options "eligible_classes" and
+ *          "eligible_expand_us" (read-only) describe the last call.
+ * Shards: every rank labels its own shard and takes the same masks; the columns of different shards are disjoint, so the per-rank lists read from this matrix are
+ * host/sharding.py::merge_hits / merge_subject_hits input as they are.  No result of afis_search changes because this function exists. */
+int afis_search_eligible(afis_ctx* ctx, afis_labels* labels, const uint64_t* masks /*[n_q][3]*/,
+                         const afis_template_view* queries, int n_q,
+                         float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/);
+
 /* Packed gallery container (no reference counterpart: the reference re-parses every rolled .dat for every pair,
  * matching/matcher.cpp:173,:278).  One mmap-able file holding the staged gallery's SoA arrays (layout: csrc/template_io.h), so a
  * 100k-1M template gallery is loaded — whole, or one contiguous shard per GPU — without touching 100k-1M small files.
@@ -546,7 +587,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * drops — then k_rank_hits on the fused rows), from HIP events around them; 0 when that call queued nothing.  "case_fuse_us" / "case_rank_us" (read-only): that call's
  * two parts, each from its own pair of events — everything before k_rank_hits (so a filtered call's filter pass too), and k_rank_hits.  "rank_filtered_us" (read-only): the device time of the last afis_rank_hits_filtered's or afis_rank_subject_hits_filtered's launches (the filter pass
  * of hit_filter.hip, for subjects the maxima's memset and k_subject_best, the exclusions' drops; then k_rank_hits), from HIP events around them; 0 when that call queued
- * nothing.  "filter_us" (read-only): of that call everything before k_rank_hits, from its own pair of events; 0 when the call queued nothing. */
+ * nothing.  "filter_us" (read-only): of that call everything before k_rank_hits, from its own pair of events; 0 when the call queued nothing.
+ * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
+ * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -69,6 +69,14 @@ int afis_debug_rank_rows(afis_ctx* ctx, afis_subset* subset, const float* scores
 /* The transpose of the last afis_rank_latent_hits (latent_rank.hip: k_transpose_scores): out2[0] = its device time in microseconds (a pair of HIP events of its own),
  * out2[1] = the bytes it read and wrote; both 0 when that call queued nothing.  tools/reverse_search_timing.py turns them into bytes per second. */
 int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2);
+/* The expand pass of afis_search_eligible (eligible_expand.hip: k_expand_rows) on planted data, so that its shapes are swept without a search: cls [n_c][m] stands for
+ * the rows of one class scored against m of G templates, sel [m] the columns those templates have in the combined matrix, strictly ascending in [0, G) — NULL with
+ * m == G is the identity (the class that passes every template), m == 0 the class no template is eligible for (cls and sel may be NULL) — and row_of [n_c] the
+ * distinct rows the class's queries have there, each in [0, n_q).  out [n_q][G] is uploaded as the caller filled it, the kernel runs once, out is copied back:
+ *   out[row_of[r]][t] = cls[r][i] where t == sel[i], 0xffffffff in every other column; rows row_of does not name come back as they went in.
+ * Words, not numbers: every bit pattern passes through unchanged.  AFIS_EINVAL for a list that breaks the rules above; no gallery is needed. */
+int afis_debug_expand_rows(afis_ctx* ctx, const float* cls /*[n_c][m]*/, int n_c, int64_t m, const int32_t* row_of /*[n_c]*/, const int32_t* sel /*[m] or NULL*/,
+                           int n_q, int64_t G, float* out /*[n_q][G]*/);
 
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -127,6 +127,7 @@ struct afis_labels {
     int64_t n = 0;                       // templates labelled (the resident shard's size at creation)
     uint64_t gallery_epoch = 0;          // afis_ctx::gallery_epoch at creation: the filtered ranking calls refuse the handle after an edit
     DevBuf d_label;                      // [n] uint64
+    std::vector<uint64_t> h_label;       // [n] the host's copy: afis_search_eligible lists a class's eligible templates from it
 };
 
 // The score matrix the last search left in afis_ctx::scores ([n_q][G] in the order of the shard searched: the resident one, or sub's sub-shard), while nothing has
@@ -171,6 +172,9 @@ struct afis_ctx : Shard {
     DevBuf filt_scores, filt_tab;        // every filtered ranking call (FilterPass): the filtered copy of the matrix [n_q][G] floats, and the call's tables (masks [n_q][3] uint64 | the exclusions' (row, column) pairs, int32 x 2); the lists leave through hits_out
     int64_t rank_filtered_us = 0;        // option rank_filtered_us (read-only): device time of the last filtered call's launches (the filter pass, for subjects the maxima's memset and k_subject_best, the drops; then k_rank_hits)
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
+    DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
+    int64_t eligible_classes = 0;        // option eligible_classes (read-only): classes (distinct mask triples) of the last afis_search_eligible
+    int64_t eligible_expand_us = 0;      // option eligible_expand_us (read-only): device time of that call's k_expand_rows launches, HIP events around each, summed over the classes
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -328,6 +332,11 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
 void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* col, int64_t index_base, int64_t* topk_idx, float* topk_score) __attribute__((visibility("hidden")));
 size_t subset_device_bytes(const afis_ctx* ctx);       // option subset_device_bytes: what the live subsets hold on the device
 void release_subset(afis_subset* s);                   // its device buffers and the handle itself (afis_subset.cpp)
+// Everything of afis_subset_create that touches the device (afis_subset.cpp): sub->n, the host tables of sub->sh (res_mo, res_to, res_empty) and the three lists are the
+// caller's — sel [n] shard-local indices ascending, global [n] their global indices, pos [n] the caller's column order (unused while sub->identity).  afis_search_eligible
+// builds its temporary sub-shard through it, class after class into the same afis_subset: its buffers only grow.  sel_buf: where the index list goes on the device
+// (NULL: a buffer of the call's own, released on return).  Ends in a bounded wait.  Hidden, as rank_subjects below.
+int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, const std::vector<int64_t>& global, const std::vector<int32_t>& pos, DevBuf* sel_buf = nullptr) __attribute__((visibility("hidden")));
 // afis_queries_upload (max_templates == 0: the launch groups are cut for the resident shard's size) and afis_queries_upload_reserved (afis_reverse.cpp: for a shard of
 // max_templates templates) behind their argument checks.  Hidden, as rank_subjects below.
 int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out) __attribute__((visibility("hidden")));

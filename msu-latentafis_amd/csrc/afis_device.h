@@ -293,10 +293,14 @@ hipError_t launch_filter_rows(const float* scores, int n_q, int G, const unsigne
                               float* filtered, hipStream_t stream);
 hipError_t launch_filter_drop_cells(const int32_t* pairs, size_t n_pairs, float* filtered, int n_q, int G, hipStream_t stream);
 hipError_t launch_filter_drop_subjects(const int32_t* pairs, size_t n_pairs, unsigned long long* best, int n_q, int S, hipStream_t stream);
-// what the row-walking launchers of case_fuse.hip and hit_filter.hip share: a thread takes four adjacent columns as one 16-byte word where every row of both matrices
+// what the row-walking launchers of case_fuse.hip, hit_filter.hip and eligible_expand.hip share: a thread takes four adjacent columns as one 16-byte word where every row of both matrices
 // starts on a 16-byte boundary, and a grid's second dimension holds 65 535 blocks (what lies beyond is walked in a loop; their one-dimensional grids stop there too)
 inline bool rows_take_16_bytes(int G, const void* a, const void* b) { return G % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 inline unsigned grid_clamp(size_t n) { return n < 65535 ? (unsigned)n : 65535u; }
+// afis_search_eligible (eligible_expand.hip): the rows cls [n_c][m] of one class of queries — scored against the m eligible templates of the shard only, in ascending
+// index — expanded into the class's rows of the combined matrix: out[row_of[r]][t] = inv[t] >= 0 ? cls[r][inv[t]] : 0xffffffff for every t < G, every word of those rows
+// written once; inv [G] int32 (position in the sub-shard or -1), NULL = identity (m == G); m == 0: cls and inv are not read.  Rows row_of does not name stay untouched
+hipError_t launch_expand_rows(const float* cls, int n_c, int m, const int32_t* inv, const int32_t* row_of, int n_q, int G, float* out, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

@@ -112,6 +112,7 @@ int afis_labels_create(afis_ctx* ctx, const uint64_t* label, int64_t n, afis_lab
     if (n != (int64_t)ctx->res_empty.size()) return fail(ctx, AFIS_EINVAL, "afis_labels_create: one label per template of the resident shard (option gallery_resident)");
     std::unique_ptr<afis_labels> lb(new afis_labels());
     lb->n = n; lb->gallery_epoch = ctx->gallery_epoch;
+    if (n > 0) lb->h_label.assign(label, label + n);
     { const int rcq = quiesce(ctx, "afis_labels_create", true); if (rcq != AFIS_OK) return rcq; }
     if (n > 0) {
         const int64_t h2d_before = ctx->gallery_h2d_bytes;

@@ -27,8 +27,9 @@ static hipError_t upload_counted(afis_ctx* ctx, DevBuf& b, const std::vector<T>&
     return hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
-// Everything of afis_subset_create that touches the device; on failure the caller releases the half-made subset.
-static int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, const std::vector<int64_t>& global, const std::vector<int32_t>& pos)
+// Everything of afis_subset_create that touches the device; on failure the caller releases the half-made subset.  (afis_search_eligible builds its temporary sub-shards
+// through it too, one after the other into the same afis_subset and the same sel_buf: every DevBuf::ensure below then finds room from the second class on.)
+int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, const std::vector<int64_t>& global, const std::vector<int32_t>& pos, DevBuf* sel_buf)
 {
     Shard& sh = sub->sh;
     const int64_t n = sub->n;
@@ -44,8 +45,9 @@ static int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32
     for (const Arr& a : arrs) HIPCHK(ctx, a.dst->ensure(std::max<size_t>((a.minu ? NM : NT) * (size_t)a.elem, 16)));
     HIPCHK(ctx, sh.g_minu_frag.ensure(std::max<size_t>((size_t)toff[(size_t)n] * 6 * 64 * 16, 16)));
     HIPCHK(ctx, sh.g_task_ctr.ensure(64));
-    DevBuf d_sel;
-    struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_sel{d_sel};
+    DevBuf own_sel;
+    struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_sel{own_sel};      // (nothing to release where the caller's buffer is used)
+    DevBuf& d_sel = sel_buf ? *sel_buf : own_sel;
     HIPCHK(ctx, upload_counted(ctx, d_sel, sel, s));
     HIPCHK(ctx, upload_counted(ctx, sh.g_minu_off, sh.res_mo, s)); HIPCHK(ctx, upload_counted(ctx, sh.g_tex_off, sh.res_to, s));
     HIPCHK(ctx, upload_counted(ctx, sh.g_minu_tile_off, toff, s)); HIPCHK(ctx, upload_counted(ctx, sh.g_tex_q_blk, qb, s)); HIPCHK(ctx, upload_counted(ctx, sh.g_tex_t32_blk, tb, s));

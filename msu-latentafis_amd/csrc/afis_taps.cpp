@@ -182,6 +182,42 @@ int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2)
     return AFIS_OK;
 }
 
+// k_expand_rows on planted data: the tables are made as afis_search_eligible makes them (inv from the ascending column list), in buffers of the call's own
+int afis_debug_expand_rows(afis_ctx* ctx, const float* cls, int n_c, int64_t m, const int32_t* row_of, const int32_t* sel, int n_q, int64_t G, float* out)
+{
+    if (!ctx || n_c <= 0 || n_q <= 0 || G <= 0 || G > 0x7fffffff || m < 0 || m > G || !row_of || !out || (m > 0 && !cls) || (!sel && m > 0 && m != G))
+        return fail(ctx, AFIS_EINVAL, "afis_debug_expand_rows: bad argument");
+    std::vector<uint8_t> seen((size_t)n_q, 0);
+    for (int r = 0; r < n_c; ++r) {
+        if (row_of[r] < 0 || row_of[r] >= n_q || seen[(size_t)row_of[r]]) return fail(ctx, AFIS_EINVAL, "afis_debug_expand_rows: row_of must hold distinct rows of out");
+        seen[(size_t)row_of[r]] = 1;
+    }
+    std::vector<int32_t> inv;
+    if (sel && m > 0) {
+        inv.assign((size_t)G, -1);
+        for (int64_t i = 0; i < m; ++i) {
+            if (sel[i] < 0 || sel[i] >= G || (i > 0 && sel[i] <= sel[i - 1])) return fail(ctx, AFIS_EINVAL, "afis_debug_expand_rows: sel must be strictly ascending columns of out");
+            inv[(size_t)sel[i]] = (int32_t)i;
+        }
+    }
+    { const int rcq = quiesce(ctx, "afis_debug_expand_rows"); if (rcq != AFIS_OK) return rcq; }
+    DevBuf d_cls, d_inv, d_rows, d_out;
+    struct Drop { DevBuf *a, *b, *c, *d; ~Drop() { a->release(); b->release(); c->release(); d->release(); } } drop{&d_cls, &d_inv, &d_rows, &d_out};
+    const size_t out_bytes = (size_t)n_q * (size_t)G * 4, cls_bytes = (size_t)n_c * (size_t)m * 4;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, d_out.ensure(out_bytes)); HIPCHK(ctx, d_rows.ensure((size_t)n_c * 4));
+    if (cls_bytes) HIPCHK(ctx, d_cls.ensure(cls_bytes));
+    if (!inv.empty()) HIPCHK(ctx, d_inv.ensure((size_t)G * 4));
+    HIPCHK(ctx, hipMemcpy(d_out.p, out, out_bytes, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(d_rows.p, row_of, (size_t)n_c * 4, hipMemcpyHostToDevice));
+    if (cls_bytes) HIPCHK(ctx, hipMemcpy(d_cls.p, cls, cls_bytes, hipMemcpyHostToDevice));
+    if (!inv.empty()) HIPCHK(ctx, hipMemcpy(d_inv.p, inv.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, launch_expand_rows(d_cls.as<float>(), n_c, (int)m, inv.empty() ? nullptr : d_inv.as<int32_t>(), d_rows.as<int32_t>(), n_q, (int)G, d_out.as<float>(), s));
+    { const int rcw = wait_streams(ctx, {s}, "afis_debug_expand_rows"); if (rcw != AFIS_OK) return rcw; }
+    HIPCHK(ctx, hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return AFIS_OK;
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

@@ -56,11 +56,11 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
-           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered",
+           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
-               "afis_debug_transpose_stats", "afis_debug_rank_rows"]
+               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -122,6 +122,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_rank_case_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
         lib.afis_rank_case_subject_hits_filtered.argtypes = [vp, vp, vp, u64p, i64p, i64p, i64p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, i64p, i64p, i64p, fp]
         lib.afis_rank_latent_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
+    if hasattr(lib, "afis_search_eligible"):                            # eligible search; absent from older builds compared by tools/lib_ab.py
+        lib.afis_search_eligible.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TemplateView), C.c_int, fp, i32p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -156,6 +158,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_transpose_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(lib, "afis_debug_rank_rows"):
         lib.afis_debug_rank_rows.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp]
+    if hasattr(lib, "afis_debug_expand_rows"):
+        lib.afis_debug_expand_rows.argtypes = [vp, fp, C.c_int, C.c_int64, i32p, i32p, C.c_int, C.c_int64, fp]
     return lib
 
 
@@ -535,6 +539,36 @@ class Matcher:
         return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits_filtered(
             self.ctx, handle[0], labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
             _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
+
+    # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
+    def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):
+        """search() that scores a (latent, template) pair only where the template's label passes the latent's masks (labels: a labels_create handle; masks [n_q][3]
+        uint64 as rank_hits_filtered takes them; both required).  scores [n_q][G]: an eligible cell is search()'s value bit for bit, every other cell the no-entry
+        word 0xffffffff (a NaN: compare scores.view(np.uint32)).  The matrix left on the device is read by rank_hits / rank_subject_hits / rank_latent_hits as their
+        _filtered forms read a full search's; the _filtered calls (case lists: always those) return what they return after a full search.  timing()["pairs"] counts
+        the pairs scored; get_option("eligible_classes") the distinct mask triples.  It pays when latents share masks."""
+        v = _Views(latents)
+        mk = None if masks is None else np.ascontiguousarray(np.asarray(masks, np.uint64).reshape(v.n, 3))
+        if mk is not None and v.n == 0:
+            mk = np.zeros((1, 3), np.uint64)                                 # (no query: the C call still wants a masks pointer)
+        G = self.resident_size
+        scores = np.empty((v.n, G), np.float32) if want_scores else None
+        status = np.zeros(v.n, np.int32)
+        self._chk(self.lib.afis_search_eligible(self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, v.arr, v.n,
+                                                _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32)))
+        self.last_n_q = v.n; self.last_n_templates = G
+        return {"scores": scores, "status": status}
+
+    def debug_expand_rows(self, cls: np.ndarray, row_of: Sequence[int], sel, out: np.ndarray) -> np.ndarray:
+        """k_expand_rows on planted data (parity tap): cls [n_c][m] words of one class, row_of [n_c] its rows of out [n_q][G], sel [m] ascending columns (None: the
+        identity, m == G; m == 0: no column).  -> out with the class's rows rewritten: cls[r][i] at column sel[i], 0xffffffff elsewhere.  uint32 or float32 arrays."""
+        c = np.ascontiguousarray(cls).view(np.float32); o = np.array(out, copy=True, order="C").view(np.float32)
+        ro = np.ascontiguousarray(np.asarray(row_of, np.int32).reshape(-1))
+        se = None if sel is None else np.ascontiguousarray(np.asarray(sel, np.int32).reshape(-1))
+        n_c, m = c.shape
+        self._chk(self._tap("afis_debug_expand_rows")(self.ctx, _ptr(c, C.c_float) if c.size else None, n_c, m, _ptr(ro, C.c_int32), _ptr(se, C.c_int32) if se is not None and len(se) else None,
+                                                      o.shape[0], o.shape[1], _ptr(o, C.c_float)))
+        return o.view(np.asarray(out).dtype)
 
     # ---- case lists: the queries of one case fused into one list ----------------------------------------------------
     def _case_lists(self, fn, case_of, cap: int, subjects: bool):
