@@ -292,6 +292,56 @@ int afis_rank_hits(afis_ctx* ctx, int n_q, float min_score, int cap,
 int afis_rank_subject_hits(afis_ctx* ctx, afis_subjects* s, int n_q, float min_score, int cap,
                            int64_t* n_hits /*[n_q]*/, int64_t* subject_id /*[n_q][cap]*/, float* subject_score /*[n_q][cap]*/, int64_t* best_idx /*[n_q][cap]*/);
 
+/* Rank positions (no reference counterpart): the lists above answer "who is at the top?"; these calls answer "where does THIS print, or this person, stand in that
+ * query's list?" — the rank of the true mate of every latent (a CMC curve), a named suspect's prints among 100 000 under the latent's filters, the per-shard term of a
+ * mate's global rank — for EVERY position, not only the first AFIS_HITS_MAX, without the [n_q][G] matrix leaving the device.  All three read the score matrix of the
+ * context's LAST search: one small pass reads the targets' cells, one counting pass reads each row that has
+ * targets once (rank_position.hip); about 24 bytes per target return, through the context's pinned buffer.  The matrix is neither written nor invalidated.
+ * Targets: n_targets pairs (query[i], idx[i] or subject_id[i]) — query[i] a query position of the last search, idx GLOBAL template indices — in any order, repeated or
+ * not; a query may have no target.  The outputs are per target, in the caller's order.
+ * afis_rank_positions          For target (q, t), n_before is the position of t in the list afis_rank_hits_filtered(labels, masks, excl, ..., min_score = -INFINITY, cap)
+ *                              gives query q — with no filters, the list afis_rank_hits gives: idx[q][n_before] == t for any cap > n_before, so that n_before is defined
+ *                              for every position.  score is the cell's own bits.  The order is csrc/rank_order.h::rank_before: rank_key descending, equal keys by
+ *                              ascending GLOBAL index, also for a subset listed out of order.  An ENTRY is a cell whose rank_key >= rank_key(-inf): a cell that holds
+ *                              0xffffffff (a filter or an exclusion took it out, or afis_search_eligible left it unscored) or any other NaN with the sign set is no
+ *                              entry, exactly as the hit lists treat it.
+ *                                AFIS_POS_LISTED       the target is an entry: n_before and score as above
+ *                                AFIS_POS_NO_ENTRY     the target is a column of the search but no entry: n_before -1, score -inf
+ *                                AFIS_POS_NOT_COVERED  idx lies outside this shard, or is not in the subset's list: the same outputs.  Silent, not an error, so that the
+ *                                                      same target list can go to every rank of a sharded gallery, as exclusion lists may
+ * afis_rank_subject_positions  the same sentence against afis_rank_subject_hits(_filtered) at -INFINITY: the key is the raw ordered word of the person's best eligible
+ *                              covered score, ties by ascending subject id, best_idx that call's best_idx.  A person on the query's excl_subject list, or with no
+ *                              eligible covered template, is AFIS_POS_NO_ENTRY (best_idx -1); an id the handle does not hold is AFIS_POS_NOT_COVERED.
+ * afis_count_before            the sharding primitive: n_before[i] is the number of ENTRIES of row query[i], under the same optional filters, that stand before a
+ *                              hypothetical entry (score[i], idx[i]) by rank_before.  A column whose global index equals idx is never counted — it is the target itself —
+ *                              and idx need not be covered.  On the owning rank afis_count_before(the cell's score, idx) equals afis_rank_positions' n_before; across
+ *                              ranks with disjoint columns the global n_before is the sum of the per-rank counts (host/sharding.py::merge_positions).  A NaN score is
+ *                              AFIS_EINVAL.
+ * Everything else is afis_rank_hits_filtered's: which searches count and what invalidates the matrix, the AFIS_ESTATE and AFIS_EINVAL cases, the handles' life cycles,
+ * the rules of masks and of the exclusions' CSR.  With neither masks nor exclusions the matrix itself is read; after afis_search_eligible the plain call gives what the
+ * filtered call gives after a full search.  In addition AFIS_EINVAL: a query[i] outside 0 .. n_q - 1, a negative idx or subject_id, n_targets < 0, a null array with
+ * n_targets > 0.  n_targets == 0 returns AFIS_OK; with an empty shard, or a handle without subjects, every target is AFIS_POS_NOT_COVERED and every count 0.  Device and
+ * pinned room — the filtered copy, the tables, n_q x subjects x 8 bytes for the subjects' maxima, 24 bytes per target — is ensured before anything is queued:
+ * AFIS_EDEVICE, with nothing changed, when that fails.  No result of a search changes because these functions exist.
+ * These calls do not give: positions in case lists and in column (reverse) lists; person positions summed across shards — a person's prints may lie in two shards, and the
+ * per-shard counts of persons do not add up (the caveat of host/sharding.py::merge_case_subject_hits). */
+#define AFIS_POS_LISTED      0   /* the target is an entry of the list                                             */
+#define AFIS_POS_NO_ENTRY    1   /* covered by the search, but no entry: ineligible, excluded, or a key below -inf's */
+#define AFIS_POS_NOT_COVERED 2   /* not a column of the last search / not a person the handle and the search hold   */
+typedef struct afis_labels afis_labels;
+int afis_rank_positions(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                        const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                        int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* idx /*[n_targets], GLOBAL*/,
+                        int32_t* status /*[n_targets]*/, int64_t* n_before /*[n_targets]*/, float* score /*[n_targets]*/);
+int afis_rank_subject_positions(afis_ctx* ctx, afis_subjects* s, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/,
+                                int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* subject_id /*[n_targets]*/,
+                                int32_t* status /*[n_targets]*/, int64_t* n_before /*[n_targets]*/, float* score /*[n_targets]*/, int64_t* best_idx /*[n_targets]*/);
+int afis_count_before(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                      const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                      int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const float* score /*[n_targets]*/, const int64_t* idx /*[n_targets], GLOBAL*/,
+                      int64_t* n_before /*[n_targets]*/);
+
 /* Case lists (no reference counterpart): an examiner's unit of work is a CASE — the same impression encoded twice, several lifts of one finger, several fingers of one
  * hand — and fusing the queries of a case is one list per case instead of one per query.  Both calls rank the matrix of the context's LAST search; a case cannot span
  * searches: all its latents must be queries of the one search that is ranked.  On the device the member rows of every case are folded into one fused row
@@ -393,7 +443,7 @@ int afis_rank_case_subject_hits(afis_ctx* ctx, afis_subjects* s, const int64_t* 
  * maximum, so the per-rank lists merge with host/sharding.py::merge_hits and merge_subject_hits as they are.  The filtered case template lists and the filtered column
  * lists are merge_hits input as they are; the filtered case subject lists merge with merge_case_subject_hits under its conditions — exactly for AFIS_CASE_MAX, for
  * AFIS_CASE_SUM only while no subject's prints lie in two shards. */
-typedef struct afis_labels afis_labels;
+/* (typedef afis_labels: with the rank positions above, which take the handle too) */
 int afis_labels_create(afis_ctx* ctx, const uint64_t* label /*[n]*/, int64_t n, afis_labels** out);
 void afis_labels_free(afis_ctx* ctx, afis_labels* labels);
 int afis_rank_hits_filtered(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
@@ -588,6 +638,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * two parts, each from its own pair of events — everything before k_rank_hits (so a filtered call's filter pass too), and k_rank_hits.  "rank_filtered_us" (read-only): the device time of the last afis_rank_hits_filtered's or afis_rank_subject_hits_filtered's launches (the filter pass
  * of hit_filter.hip, for subjects the maxima's memset and k_subject_best, the exclusions' drops; then k_rank_hits), from HIP events around them; 0 when that call queued
  * nothing.  "filter_us" (read-only): of that call everything before k_rank_hits, from its own pair of events; 0 when the call queued nothing.
+ * "rank_positions_us" (read-only): the device time of the last afis_rank_positions', afis_rank_subject_positions' or afis_count_before's launches (for a filtered call the
+ * filter pass of hit_filter.hip first, for persons the maxima's memset, k_subject_best and the exclusions' drops; then k_position_targets and k_count_before), from HIP
+ * events around them; 0 when that call queued nothing.
  * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
  * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -172,6 +172,8 @@ struct afis_ctx : Shard {
     DevBuf filt_scores, filt_tab;        // every filtered ranking call (FilterPass): the filtered copy of the matrix [n_q][G] floats, and the call's tables (masks [n_q][3] uint64 | the exclusions' (row, column) pairs, int32 x 2); the lists leave through hits_out
     int64_t rank_filtered_us = 0;        // option rank_filtered_us (read-only): device time of the last filtered call's launches (the filter pass, for subjects the maxima's memset and k_subject_best, the drops; then k_rank_hits)
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
+    DevBuf pos_tab, pos_out;             // afis_rank_positions / afis_rank_subject_positions / afis_count_before: the call's tables (the targets' composites [m] uint64 | rows | off | row [m] | position [m], int32) and its answers (count [m] uint64 | best_idx [m] int64 | status [m] int32 | score [m])
+    int64_t rank_positions_us = 0;       // option rank_positions_us (read-only): device time of the last such call's launches (a filtered call's filter pass, for persons the maxima and the drops; k_position_targets, k_count_before)
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
     int64_t eligible_classes = 0;        // option eligible_classes (read-only): classes (distinct mask triples) of the last afis_search_eligible
     int64_t eligible_expand_us = 0;      // option eligible_expand_us (read-only): device time of that call's k_expand_rows launches, HIP events around each, summed over the classes

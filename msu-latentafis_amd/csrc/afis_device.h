@@ -301,6 +301,26 @@ inline unsigned grid_clamp(size_t n) { return n < 65535 ? (unsigned)n : 65535u; 
 // index — expanded into the class's rows of the combined matrix: out[row_of[r]][t] = inv[t] >= 0 ? cls[r][inv[t]] : 0xffffffff for every t < G, every word of those rows
 // written once; inv [G] int32 (position in the sub-shard or -1), NULL = identity (m == G); m == 0: cls and inv are not read.  Rows row_of does not name stay untouched
 hipError_t launch_expand_rows(const float* cls, int n_c, int m, const int32_t* inv, const int32_t* row_of, int n_q, int G, float* out, hipStream_t stream);
+// afis_rank_positions / afis_rank_subject_positions / afis_count_before (rank_position.hip): where named targets stand in the list launch_rank_hits would make of a
+// row at thr = kPosFloor, the ordered word of -inf.  The host resolves a target to (row, position) and sorts the targets into a CSR by row: rows [n_rows] the rows that
+// have targets, off [n_rows + 1] their ranges in the target arrays [m].
+// launch_position_targets  mode 0: position = a column of scores [n_q][G] -> comp (the target's composite; ~0 for a target that is no entry), count = 0, status
+//                          (kPosListed / kPosNoEntry), score (the cell's own bits, -inf for no entry).  mode 1: position = a slot of best [n_q][S] as launch_subject_best
+//                          (and the drops) left it, scores the matrix it was made of -> the same and best_idx (global index of the slot's best template, -1).  mode 2
+//                          (afis_count_before): comp is the host's, position the column the hypothetical entry's index names or -1 -> count = -1 where that column's
+//                          own composite exceeds comp (the hot pass counts it, and it must not count), else 0.
+// launch_count_before      count[t] += the entries of the target's row whose composite exceeds comp[t]: the columns of scores [n_q][n] (best == NULL; composites of
+//                          rank_key and position, k_topk's order) or the slots of best [n_q][n] (composite_at(b, slot), 0 skipped).  Integer adds only.
+//                          max_row_targets: the longest range of off — how many workgroups share a row's targets.
+constexpr int kPosListed = 0, kPosNoEntry = 1;          // AFIS_POS_LISTED, AFIS_POS_NO_ENTRY
+constexpr uint32_t kPosFloor = 0x007fffffu;             // rank_key(-inf) == ordered_word(-inf): an entry's word reaches it
+constexpr int kPosLoads = 4, kPosTargetChunk = 64;      // k_count_before: loads in flight per thread; targets staged in LDS at a time
+constexpr int kPosChunkScalar = 256 * kPosLoads, kPosChunkVec = 4 * kPosChunkScalar;   // columns per workgroup: 1024, or 4096 where a thread takes 16 bytes per load
+hipError_t launch_position_targets(int mode, const float* scores, int G, const unsigned long long* best, int S, const int32_t* row, const int32_t* pos, size_t m,
+                                   const long long* d_global, long long index_base, unsigned long long* comp, unsigned long long* count, int32_t* status, float* score,
+                                   long long* best_idx, hipStream_t stream);
+hipError_t launch_count_before(const float* scores, const unsigned long long* best, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets,
+                               const unsigned long long* comp, unsigned long long* count, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

@@ -40,6 +40,21 @@ inline void rank_topk(const float* sc, int64_t n, int k, const int64_t* col, int
     }
 }
 
+// The host statement of afis_count_before (include/afis_matcher.h), and so of a rank position: how many ENTRIES of sc[0 .. n) stand before a hypothetical entry
+// (score, idx) by rank_before.  Column i is template col[i], or index_base + i without a table; an entry is a column whose rank_key reaches rank_key(-inf) — the
+// no-entry word of the filtered lists and every other NaN with the sign set are none — and a column whose global index is idx is the target itself, never counted.
+// The position of a listed template is count_before(sc, n, col, index_base, its own score, its own index).
+inline int64_t count_before(const float* sc, int64_t n, const int64_t* col, int64_t index_base, float score, int64_t idx)
+{
+    const uint32_t floor = rank_key(-INFINITY);
+    int64_t before = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t g = col ? col[i] : index_base + i;
+        if (g != idx && rank_key(sc[i]) >= floor && rank_before(sc[i], g, score, idx)) ++before;
+    }
+    return before;
+}
+
 // All of 0 .. n-1 in the order of afis_rank_list (include/afis_matcher.h).  ref_order 0: key descending, equal keys by ascending index.  ref_order 1:
 // std::sort of the indices on rank_key(a) > rank_key(b) — the reference's statement (matcher.cpp:306-308: std::sort on scores[a] > scores[b]) with the
 // comparison made on the key: the same outcome for every pair of a NaN-free column, hence the same permutation from the same libstdc++, and a strict weak

@@ -57,6 +57,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -124,6 +125,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_rank_latent_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
     if hasattr(lib, "afis_search_eligible"):                            # eligible search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_eligible.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TemplateView), C.c_int, fp, i32p]
+    if hasattr(lib, "afis_rank_positions"):                             # rank positions; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64)
+        lib.afis_rank_positions.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
+        lib.afis_rank_subject_positions.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp, i64p]
+        lib.afis_count_before.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, fp, i64p, i64p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
@@ -539,6 +545,50 @@ class Matcher:
         return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits_filtered(
             self.ctx, handle[0], labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
             _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
+
+    # ---- rank positions: where a named template or person stands in a query's list ----------------------------------
+    def _positions(self, fn, query, names, labels, masks, excl, n_q, subjects: bool, in_score=None):
+        n_q = self.last_n_q if n_q is None else n_q
+        q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); a = np.ascontiguousarray(np.asarray(names, np.int64).reshape(-1))
+        if len(q) != len(a):
+            raise ValueError("one query position per target")
+        n = len(q)
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        flt = (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+               _ptr(ent, C.c_int64) if ent is not None else None)
+        nb = np.empty(n, np.int64)
+        pq, pa, pn = (_ptr(q, C.c_int32), _ptr(a, C.c_int64), _ptr(nb, C.c_int64)) if n else (None, None, None)
+        if in_score is not None:
+            sc = np.ascontiguousarray(np.asarray(in_score, np.float32).reshape(-1))
+            if len(sc) != n:
+                raise ValueError("one score per target")
+            self._chk(fn(flt, n_q, n, pq, pa, _ptr(sc, C.c_float) if n else None, pn))
+            return nb
+        st = np.empty(n, np.int32); sc = np.empty(n, np.float32); bi = np.empty(n, np.int64) if subjects else None
+        self._chk(fn(flt, n_q, n, pq, pa, _ptr(st, C.c_int32) if n else None, pn, _ptr(sc, C.c_float) if n else None, _ptr(bi, C.c_int64) if subjects and n else None))
+        out = {"status": st, "n_before": nb, "score": sc}
+        if subjects:
+            out["best_idx"] = bi
+        return out
+
+    def rank_positions(self, query, idx, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """Where named templates stand in the lists of the LAST search: target i is (query[i], idx[i]), a query position of that search and a GLOBAL template index, in
+        any order, repeated or not.  -> status [n] (AFIS_POS_LISTED 0, AFIS_POS_NO_ENTRY 1, AFIS_POS_NOT_COVERED 2), n_before [n] — the target's position in the list
+        rank_hits_filtered(-inf, cap, labels, masks, excl) gives its query, for every position, not only the first 4096; -1 unless listed — and score [n], the cell's own
+        bits (-inf unless listed).  labels / masks / excl are rank_hits_filtered's; n_q defaults as there."""
+        return self._positions(lambda f, nq, n, q, a, st, nb, sc, bi: self.lib.afis_rank_positions(self.ctx, *f, nq, n, q, a, st, nb, sc), query, idx, labels, masks, excl, n_q, False)
+
+    def rank_subject_positions(self, handle, query, subject_id, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """rank_positions over the enrolled persons of a subjects_create handle, against rank_subject_hits_filtered(-inf, cap): also best_idx [n], the global index of the
+        person's best eligible template (-1 unless listed).  excl: per query a sequence of SUBJECT ids; an id the handle does not hold is AFIS_POS_NOT_COVERED."""
+        return self._positions(lambda f, nq, n, q, a, st, nb, sc, bi: self.lib.afis_rank_subject_positions(self.ctx, handle[0], *f, nq, n, q, a, st, nb, sc, bi),
+                               query, subject_id, labels, masks, excl, n_q, True)
+
+    def count_before(self, query, score, idx, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """The sharding primitive: n_before [n], per target the number of entries of row query[i] of the LAST search — under the same optional filters — that stand
+        before a hypothetical entry (score[i], idx[i]); a column whose global index is idx[i] is never counted, and idx[i] need not be covered.  Summed over the ranks
+        of a sharded gallery (host/sharding.py::merge_positions) that is the target's global position."""
+        return self._positions(lambda f, nq, n, q, a, sc, nb: self.lib.afis_count_before(self.ctx, *f, nq, n, q, sc, a, nb), query, idx, labels, masks, excl, n_q, False, in_score=score)
 
     # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
     def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):

@@ -206,6 +206,34 @@ def merge_case_subject_hits(n_hits: np.ndarray, subject: np.ndarray, score: np.n
     return out_n, (counts > kk).any(axis=0), out_i, out_s
 
 
+POS_LISTED, POS_NO_ENTRY, POS_NOT_COVERED = 0, 1, 2                         # AFIS_POS_* (include/afis_matcher.h)
+
+
+def merge_positions(status: np.ndarray, score: np.ndarray, n_before_per_rank: np.ndarray):
+    """Global rank positions of one target list handed to every rank.  status, score: [R, T] from Matcher.rank_positions on every rank (the columns of different shards
+    are disjoint, so at most one rank covers a target: the OWNER, the rank whose status is not AFIS_POS_NOT_COVERED); n_before_per_rank: [R, T] from Matcher.count_before
+    on every rank with the owner's score and the target's global index — every rank counts the entries of its own columns that stand before the target, the owner leaving
+    the target's own column out.  Returns (status [T], score [T], n_before [T], owner [T]): the owner's status and score; n_before the sum of the counts over the ranks
+    where the owner lists the target, else -1; owner -1, status AFIS_POS_NOT_COVERED, score -inf, n_before -1 for a target no rank covers.  Two ranks covering one
+    target raise ValueError: their columns are not disjoint."""
+    st = np.asarray(status, np.int32); sc = np.asarray(score, np.float32); nb = np.asarray(n_before_per_rank, np.int64)
+    if st.ndim != 2 or sc.shape != st.shape or nb.shape != st.shape:
+        raise ValueError("merge_positions: status, score and n_before_per_rank are [ranks, targets] arrays of one shape")
+    covered = st != POS_NOT_COVERED
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"merge_positions: targets {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    T = st.shape[1]
+    any_owner = covered.any(axis=0)
+    owner = np.where(any_owner, covered.argmax(axis=0) if st.shape[0] else 0, -1).astype(np.int64)
+    at = (np.maximum(owner, 0), np.arange(T))
+    out_status = np.where(any_owner, st[at] if st.shape[0] else POS_NOT_COVERED, POS_NOT_COVERED).astype(np.int32)
+    out_score = np.full(T, -np.inf, np.float32)
+    if st.shape[0]:
+        out_score[any_owner] = sc[at][any_owner]                            # (own bits: a masked copy, no arithmetic)
+    n_before = np.where(out_status == POS_LISTED, nb.sum(axis=0), -1).astype(np.int64)
+    return out_status, out_score, n_before, owner
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""
