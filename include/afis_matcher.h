@@ -253,7 +253,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     The matrix stays rankable from the successful return of the search until the next call on the context that queues device work or edits the gallery —
  *                     a search (a failed or timed-out one included), afis_queries_upload, afis_correspondences, afis_match_all_templates, every gallery
  *                     edit and export, afis_subset_create, afis_subset_free, a change of option "bound_cus" — after which afis_rank_subjects is AFIS_ESTATE.  It may itself
- *                     be repeated, with another k or another handle; afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
+ *                     be repeated, with another k or another handle; afis_correspondences_pairs, afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
  *                     afis_last_error and afis_gallery_size leave the matrix alone.  No result of a search changes because subjects exist.
  * Shards: every rank labels its own shard and ranks its own subjects; the per-rank lists merge exactly although a person's prints may lie in several shards
  * (host/sharding.py::merge_subject_topk). */
@@ -594,6 +594,31 @@ int afis_encode_rolled_dat(afis_ctx* ctx, const void* bytes, size_t len, void* o
 int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const int64_t* gallery_idx, int n,
                          int32_t* counts /*[n][3]*/, int16_t* xy /*[n][3][120][4]*/);
 
+/* Correspondence export for a whole candidate list: the surviving correspondences of n_pairs (latent, rolled print) pairs in one launch sequence — what an examiner opens
+ * after afis_rank_hits, whose flattened idx can be passed as it is.  q is a handle of afis_queries_upload or afis_queries_upload_reserved, typically the one the last
+ * search ran on; a handle of ANY gallery epoch is taken (the pairs read the latents' minutiae only; the launch-group cuts play no part).  query[i] is a query position of
+ * the handle, idx[i] a global index of the RESIDENT shard as it stands — never a subset's position, and whatever search ran last.  Pairs may come in any order and repeat.
+ *   counts[i*3 + s], xy[((i*3 + s)*120 + t)*4 + 0..3]   byte for byte what afis_correspondences(latent query[i], {idx[i]}) returns — AFIS_CORR_NOT_RUN (-1) included, under
+ *                                                      every value of "s3_tie_order" / "ref_tie_order"; the xy rows beyond counts are zero
+ *   part[i*3 + s]  (part may be NULL)                   the scorer's return value, bit for bit afis_search's parts[q][t][s], where counts >= 0; +0.0f elsewhere
+ * An idx outside [index_base, index_base + G) — the -1 that pads the list calls included — gives AFIS_CORR_NOT_COVERED (-2) three times and zeros, silently: the same pair
+ * list can go to every rank of a sharded gallery (host/sharding.py::merge_correspondences), as the targets of afis_rank_positions and the exclusion lists can.
+ * The call neither writes nor invalidates the last search's matrix: every ranking call may precede and follow it (afis_correspondences, by contrast, stays on the list of
+ * calls after which they answer AFIS_ESTATE).  AFIS_EINVAL: a null ctx or q, n_pairs < 0, a null array with n_pairs > 0, a query[i] outside 0 .. n_q - 1; AFIS_ESTATE
+ * before the first commit; n_pairs == 0 is AFIS_OK.  Device and pinned room is ensured before anything is queued: AFIS_EDEVICE when that fails, with nothing changed that a caller can see — the caller's arrays and the
+ * last search's matrix are untouched; the context's own scratch buffers may have been reallocated, and "correspondences_us" reads 0.
+ * Any n_pairs: the list is cut into chunks of at most option "corr_pairs_per_launch" pairs (1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH; about 5.8 KB of device
+ * memory per pair — candidates 2880 B, survivors 2880 B, counts, parts — and 2.9 KB pinned); per chunk and launch group of the handle one launch of the any-shape candidate
+ * kernel and one of the list kernel, over a device table of the group's pairs, against the resident shard itself.  Option "correspondences_us" (read-only): the device time
+ * of the last call's launches (afis_correspondences' too), from HIP events around every chunk's.  Host waits are bounded as a search's are ("search_timeout_s"). */
+#define AFIS_CORR_NOT_RUN      -1   /* the reference runs no scorer and writes no file (afis_correspondences' -1) */
+#define AFIS_CORR_NOT_COVERED  -2   /* idx is not a template of this shard */
+#define AFIS_CORR_PAIRS_PER_LAUNCH 8192
+int afis_correspondences_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
+                               const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
+                               int32_t* counts /*[n_pairs][3]*/, int16_t* xy /*[n_pairs][3][120][4]*/,
+                               float* part /*[n_pairs][3] or NULL*/);
+
 /* afis_get_timing2 copies min(struct_size, sizeof(afis_timing)) bytes: pass sizeof(afis_timing) of the header the caller was compiled
  * against, so that a library with a longer struct never writes past the caller's.  afis_get_timing (kept for callers of the round-2
  * header) fills only the fields up to `pairs` (48 bytes, the struct of that header); the fields after it need afis_get_timing2. */
@@ -641,6 +666,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "rank_positions_us" (read-only): the device time of the last afis_rank_positions', afis_rank_subject_positions' or afis_count_before's launches (for a filtered call the
  * filter pass of hit_filter.hip first, for persons the maxima's memset, k_subject_best and the exclusions' drops; then k_position_targets and k_count_before), from HIP
  * events around them; 0 when that call queued nothing.
+ * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
+ * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
+ * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.
  * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
  * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, correspondences, all-templates mode), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -60,6 +60,7 @@ struct QueryGroup {
     int64_t n_lm_points = 0;             // latent minutiae of the group's three selected templates per query, summed
     bool overlapped = false;             // how the last search scheduled this group (afis_search_resident)
     std::vector<int32_t> h_lt_n;
+    std::vector<uint8_t> h_has_lm;       // [nq][3] 1 = the latent carries selected minutiae template s (the host's copy of "lm_off's range is not empty": afis_correspondences_pairs' -1 rule)
     void release() { lm_off.release(); lm_xy.release(); lm_ori.release(); lm_des.release(); lm_frag.release(); lm_tile_off.release(); lt_off.release(); lt_xy.release(); lt_ori.release();
                      lt_des.release(); tile_off.release(); tile16_off.release(); tex_slot.release(); status.release(); }
 };
@@ -174,6 +175,9 @@ struct afis_ctx : Shard {
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
     DevBuf pos_tab, pos_out;             // afis_rank_positions / afis_rank_subject_positions / afis_count_before: the call's tables (the targets' composites [m] uint64 | rows | off | row [m] | position [m], int32) and its answers (count [m] uint64 | best_idx [m] int64 | status [m] int32 | score [m])
     int64_t rank_positions_us = 0;       // option rank_positions_us (read-only): device time of the last such call's launches (a filtered call's filter pass, for persons the maxima and the drops; k_position_targets, k_count_before)
+    DevBuf corr_buf;                     // afis_correspondences_pairs: one chunk's pair tables, candidate lists, survivors, counts and parts (about 5.8 KB per pair of option corr_pairs_per_launch)
+    int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
+    int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
     int64_t eligible_classes = 0;        // option eligible_classes (read-only): classes (distinct mask triples) of the last afis_search_eligible
     int64_t eligible_expand_us = 0;      // option eligible_expand_us (read-only): device time of that call's k_expand_rows launches, HIP events around each, summed over the classes
@@ -342,6 +346,11 @@ int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& se
 // afis_queries_upload (max_templates == 0: the launch groups are cut for the resident shard's size) and afis_queries_upload_reserved (afis_reverse.cpp: for a shard of
 // max_templates templates) behind their argument checks.  Hidden, as rank_subjects below.
 int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out) __attribute__((visibility("hidden")));
+// afis_corr.cpp
+// afis_correspondences_pairs behind its argument checks, and what afis_correspondences runs for its one latent: the pairs (query[i], idx[i]) of the query groups `groups`
+// (n_q queries in all, status per query) against the resident shard.  part may be NULL.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.
+int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
+                          const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part) __attribute__((visibility("hidden")));
 // afis_subjects.cpp
 void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
 // afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.

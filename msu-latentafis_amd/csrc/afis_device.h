@@ -230,6 +230,20 @@ hipError_t launch_minu_cands(const QueryDev& q, const GalleryDev& g, float* scra
 // S8a+S9 on those lists, one wave per list -> parts[(q*G+g)*4+{0,1,2}].  join: a second instance beside one that is already running (same list counter, no reset): it needs a slab of its own
 hipError_t launch_graph_minutiae(const QueryDev& q, const GalleryDev& g, const MinuCand* cands, const int32_t* cand_n,
                                  float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join = false);
+// afis_correspondences_pairs (afis_corr.cpp): S1-S3 and S8a+S9 over a TABLE of (latent, template) pairs instead of a latents x gallery cross product, against the resident
+// GalleryDev itself.  pair_tab (device): [n_pairs | (query of the group q, shard-local template) x n_pairs] int32.  Task 3 p + s — selected template s of pair p — owns the
+// compact slot of that number: cands[task][120], cand_n[task], corr_out[task][120], corr_n[task], parts[4 p + s].  One launch of the any-shape candidate kernel, its
+// workgroups striding over the tasks (n_wg workgroups, each with scratch_floats_per_wg of scratch: minu_scratch_floats over the group's longest latent list and the
+// shard's longest rolled template), and one of the list kernel in its survivor-exporting form (grid and slab: graph_minutiae_grid / _slab_bytes of 3 n_pairs tasks).
+// minu_cands_lds_bytes: the dynamic LDS of a candidate workgroup (how many fit a CU).
+constexpr int kCorrPairsPerLaunch = 8192;               // AFIS_CORR_PAIRS_PER_LAUNCH: option corr_pairs_per_launch's default (48 MB of device memory, 24 MB pinned)
+constexpr int kCorrPairsMax = 1 << 20;                  // ... and its ceiling: 3 tasks per pair stay far inside the launchers' 2^31 and a chunk's buffers below 6.1 GB
+constexpr size_t kCorrBytesPerPair = 2 * 3 * kTopMinu * 8 + 2 * 3 * 4 + 16 + 8;   // candidates, survivors, their two counts, parts, the table's entry: 5 808
+size_t minu_cands_lds_bytes(int s3_tie_order);
+hipError_t launch_minu_cands_pairs(const QueryDev& q, const GalleryDev& g, float* scratch, size_t scratch_floats_per_wg, int n_wg, int s3_tie_order,
+                                   const int32_t* pair_tab, int n_pairs, MinuCand* cands, int32_t* cand_n, hipStream_t stream);
+hipError_t launch_graph_minutiae_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const MinuCand* cands, const int32_t* cand_n,
+                                       float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream);
 // S10: fusion -> scores[q*G+g]
 hipError_t launch_fuse(const QueryDev& q, const GalleryDev& g, const float* parts, float* scores, hipStream_t stream);
 

@@ -167,6 +167,7 @@ int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup&
                 lm_des.insert(lm_des.end(), m.des, m.des + (size_t)m.n * kDes);
                 max_nL = std::max(max_nL, m.n);
             }
+            grp.h_has_lm.push_back(lm_off.back() < (int32_t)lm_xy.size());
             lm_off.push_back((int32_t)lm_xy.size());
         }
         int n_lt = 0;
@@ -708,73 +709,6 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     } else if (q->gallery_epoch != ctx->gallery_epoch)
         return fail_edited(ctx, "afis_search_resident", "these queries were uploaded; free the handle and upload them again");
     return search_shard(ctx, *ctx, nullptr, q, scores, parts, status, k, topk_idx, topk_score);
-}
-
-// Correspondence export (matcher.cpp:321-327 calling :376-417 with save_corr = true, :497-505): the minutiae scorers of the
-// three selected latent templates are re-run against each listed gallery template with the kernels' survivor lists switched on.
-int afis_correspondences(afis_ctx* ctx, const afis_template_view* query, const int64_t* gallery_idx, int n, int32_t* counts, int16_t* xy)
-{
-    if (!ctx || !query || n < 0 || (n > 0 && (!gallery_idx || !counts || !xy))) return fail(ctx, AFIS_EINVAL, "afis_correspondences: bad argument");
-    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_correspondences: commit the gallery first");
-    if (n == 0) return AFIS_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
-    const GalleryDev& g = ctx->gal;
-    for (int i = 0; i < n; ++i)
-        if (gallery_idx[i] < ctx->index_base || gallery_idx[i] >= ctx->index_base + g.G) return fail(ctx, AFIS_EINVAL, "afis_correspondences: gallery index outside this shard");
-    QueryGroup grp;
-    std::vector<int32_t> status;
-    int rc = build_group(ctx, query, 1, grp, status);
-    if (rc != AFIS_OK) { grp.release(); return rc; }
-    for (int i = 0; i < n * 3; ++i) counts[i] = -1;
-    memset(xy, 0, (size_t)n * 3 * kTopMinu * 4 * sizeof(int16_t));
-    DevBuf d_xy, d_n;
-    auto body = [&]() -> int {
-        if (status[0] != AFIS_QUERY_OK) return AFIS_OK;                    // matcher.cpp:383-386: nothing is matched, nothing written
-        const size_t per_wg = minu_scratch_floats(grp.max_nL, ctx->max_nR, ctx->s3_tie_order);
-        const int n_wg = 64;
-        HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * n_wg));
-        HIPCHK(ctx, ctx->cands.ensure((size_t)n * 3 * kTopMinu * sizeof(MinuCand)));
-        HIPCHK(ctx, ctx->cand_n.ensure((size_t)n * 3 * 4));
-        HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(3, 1) * 4));
-        HIPCHK(ctx, ctx->parts.ensure((size_t)n * 16));
-        HIPCHK(ctx, ctx->minu_slab.ensure(graph_minutiae_slab_bytes(3)));                  // three lists per launch, launches in stream order
-        HIPCHK(ctx, d_xy.ensure((size_t)n * 3 * kTopMinu * sizeof(short4)));
-        HIPCHK(ctx, d_n.ensure((size_t)n * 3 * 4));
-        hipStream_t s = ctx->stream;
-        int err = AFIS_OK;
-        for (int i = 0; i < n && err == AFIS_OK; ++i) {
-            const int64_t gi = gallery_idx[i] - ctx->index_base;
-            GalleryDev one = g;                                            // a one-template view: offsets are absolute, so only the CSR bases move
-            one.G = 1; one.minu_off += gi; one.minu_tile_off += gi; one.tex_off += gi; one.empty += gi;
-            MinuCand* cands = ctx->cands.as<MinuCand>() + (size_t)i * 3 * kTopMinu;
-            int32_t* cand_n = ctx->cand_n.as<int32_t>() + (size_t)i * 3;
-            if (launch_minu_cands(grp.dev, one, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), cands, cand_n, ctx->minu_fb.as<int32_t>(), grp.max_nL, ctx->max_nR, nullptr, s) != hipSuccess ||
-                launch_graph_minutiae(grp.dev, one, cands, cand_n, ctx->parts.as<float>() + (size_t)i * 4,
-                                      d_xy.as<short4>() + (size_t)i * 3 * kTopMinu, d_n.as<int32_t>() + (size_t)i * 3, ctx->minu_slab.p, ctx->minu_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s) != hipSuccess)
-                err = fail(ctx, AFIS_EDEVICE, "afis_correspondences: kernel launch failed");
-        }
-        if (err == AFIS_OK) {
-            if (hipMemcpyAsync(xy, d_xy.p, (size_t)n * 3 * kTopMinu * sizeof(short4), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(counts, d_n.p, (size_t)n * 3 * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                err = fail(ctx, AFIS_EDEVICE, "afis_correspondences: copy back failed");
-            // -1 where the reference does not run the scorer at all (no file): rolled empty (:388-391), rolled without a
-            // minutiae template (:399), latent without the selected template (:402-403)
-            for (int i = 0; i < n && err == AFIS_OK; ++i) {
-                const int64_t gi = gallery_idx[i] - ctx->index_base;
-                int32_t off[2] = {0, 0};
-                if (hipMemcpy(off, g.minu_off + gi, sizeof(off), hipMemcpyDeviceToHost) != hipSuccess) { err = fail(ctx, AFIS_EDEVICE, "afis_correspondences: copy back failed"); break; }
-                for (int sl = 0; sl < 3; ++sl)
-                    if (ctx->res_empty[(size_t)gi] || off[1] - off[0] <= 0 || query->n_minu <= kSelected[sl]) counts[i * 3 + sl] = -1;
-            }
-        } else (void)hipStreamSynchronize(s);
-        return err;
-    };
-    rc = body();
-    d_xy.release(); d_n.release();
-    grp.release();
-    return rc;
 }
 
 // One2One_matching_all_templates (matcher.cpp:339-374) for one latent against the whole resident gallery: EVERY latent minutiae

@@ -37,7 +37,7 @@ namespace afis {
 // optional per-phase cycle accounting (make PHASE_TIMING=1): slots 0..7 minutiae lists, 8..15 texture lists.  The stopwatch values are
 // accumulated in LDS (WaveSmem::ph) and flushed with one global atomic per slot at the end of the kernel: a global atomic inside
 // the loop stalls the global loads that follow it and distorts the phase it ends (round 1's timer did exactly that to the angle stage).
-#ifdef AFIS_PHASE_TIMING
+#if defined(AFIS_PHASE_TIMING) && !defined(AFIS_GRAPH_PAIRS_UNIT)   // (graph_pairs.hip compiles this file a second time for the pair form alone: no timers there — a PHASE_TIMING build's afis_debug_phase_cycles does not count the pair launches)
 __device__ u64 g_graph_phase[16];
 #define GPH_INIT() u64 gph_t0 = __builtin_readcyclecounter()
 #define GPH(i) do { if (threadIdx.x == 0) { const u64 t1_ = __builtin_readcyclecounter(); sm.ph[(i)] += t1_ - gph_t0; gph_t0 = t1_; } } while (0)
@@ -948,6 +948,7 @@ __device__ __forceinline__ void tap_write(const GraphTap& tap, const SM& sm, con
 // =====================================================================================================================
 // 14 lists per CU: 11 200 B of LDS (sort keys, picked rows and the angle stage's orientations share one union; the power iterations' values and neighbour indices live in
 // the workgroup's slab in global memory: kTexSlabWgBytes at slab + blockIdx.x * kTexSlabWgBytes) and 128 registers.
+#ifndef AFIS_GRAPH_PAIRS_UNIT
 #ifndef AFIS_TEX_WAVES
 #define AFIS_TEX_WAVES 4
 #endif
@@ -1214,6 +1215,7 @@ hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const fl
     else hipLaunchKernelGGL(k_graph_texture<0>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, (unsigned char*)slab, tap);
     return hipGetLastError();
 }
+#endif   // AFIS_GRAPH_PAIRS_UNIT
 
 // =====================================================================================================================
 // minutiae lists (produced by k_minu_cands, already in rank order): S8a + S9
@@ -1227,25 +1229,44 @@ typedef WaveSmem<kTopMinu, true> MinuGraphSmem;
 #ifndef AFIS_MINU_WAVES
 #define AFIS_MINU_WAVES 6
 #endif
-template <int REF_TIE>
+// PAIRS (afis_correspondences_pairs): the lists of a pair table [n_pairs | (query of the group, shard-local template) x n_pairs] instead of a latents x gallery cross
+// product — task 3 p + s is selected template s of pair p; it reads the compact slot cands[task][120] / cand_n[task] k_minu_cands<true> filled and writes
+// parts[4 p + s], corr_out[task][120], corr_n[task].  The table is a parameter PACK: the cross-product form keeps the parameter list, and with it the kernel-argument
+// segment, it always had.  The pair form is instantiated in a translation unit of its own (graph_pairs.hip compiles this file with AFIS_GRAPH_PAIRS_UNIT defined: the
+// shared device code, this kernel and launch_graph_minutiae_pairs, nothing else), so that the module the search's list kernels are compiled in — and what the inliner
+// makes of the filters they share — stays as it was
+__device__ __forceinline__ const int32_t* pair_tab_of() { return nullptr; }
+__device__ __forceinline__ const int32_t* pair_tab_of(const int32_t* tab) { return tab; }
+template <int REF_TIE, class... TAB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WAVES, AFIS_MINU_WAVES))) void k_graph_minutiae(QueryDev q, GalleryDev g, const MinuCand* __restrict__ cands,
                                                        const int32_t* __restrict__ cand_n, float* __restrict__ parts,
-                                                       short4* __restrict__ corr_out, int32_t* __restrict__ corr_n, unsigned char* slab_all, GraphTap tap)
+                                                       short4* __restrict__ corr_out, int32_t* __restrict__ corr_n, unsigned char* slab_all, GraphTap tap, TAB... tab)
 {
+    constexpr bool PAIRS = sizeof...(TAB) != 0;
+    const int32_t* const ptab = pair_tab_of(tab...);
     __shared__ MinuGraphSmem sm;
     const SlabBuf slab = g_slab_buf(slab_all + (size_t)blockIdx.x * kMinuSlabWgBytes, (uint32_t)kMinuSlabWgBytes);
     const int lane = threadIdx.x;
     GPH_ZERO();
-    const int n_tasks = q.nq * 3 * g.G;
+    int n_tasks;
+    if constexpr (PAIRS) n_tasks = 3 * ptab[0]; else n_tasks = q.nq * 3 * g.G;
     for (;;) {
         const int task = next_task(g.task_ctr + 1);
         if (task >= n_tasks) break;
         GPH_T0();
         // task order as in k_minu_cands: gallery template fastest, then selected template, then query
-        const int gi = task % g.G;
-        const int qs = task / g.G;
-        const int qi = qs / 3, s = qs - qi * 3;
-        float* out = parts + ((size_t)qi * g.G + gi) * 4 + s;
+        int gi, qs;
+        float* out;
+        if constexpr (PAIRS) {
+            const int p = task / 3, s = task - p * 3;
+            qs = ptab[1 + 2 * p] * 3 + s; gi = ptab[2 + 2 * p];
+            out = parts + (size_t)p * 4 + s;
+        } else {
+            gi = task % g.G;
+            qs = task / g.G;
+            const int qi = qs / 3, s = qs - qi * 3;
+            out = parts + ((size_t)qi * g.G + gi) * 4 + s;
+        }
         const int num = cand_n[task];
         if (num <= 0) { if (lane == 0) { *out = 0.0f; if (corr_n) corr_n[task] = 0; if (tap.out) tap.n[task] = -1; } continue; }   // matcher.cpp:400-404
         const int l0 = q.lm_off[qs], r0 = g.minu_off[gi];
@@ -1287,6 +1308,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WA
     GPH_FLUSH();
 }
 
+#ifndef AFIS_GRAPH_PAIRS_UNIT
 hipError_t launch_graph_minutiae(const QueryDev& q, const GalleryDev& g, const MinuCand* cands, const int32_t* cand_n,
                                  float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream, bool join)
 {
@@ -1303,6 +1325,25 @@ hipError_t launch_graph_minutiae(const QueryDev& q, const GalleryDev& g, const M
     else hipLaunchKernelGGL(k_graph_minutiae<0>, dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, (unsigned char*)slab, tap);
     return hipGetLastError();
 }
+#else    // AFIS_GRAPH_PAIRS_UNIT
+
+hipError_t launch_graph_minutiae_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const MinuCand* cands, const int32_t* cand_n,
+                                       float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream)
+{
+    if (n_pairs <= 0) return hipSuccess;
+    if (n_pairs > 0x7ffffff0 / 3 || !g.task_ctr || !pair_tab || !corr_out || !corr_n) return hipErrorInvalidValue;
+    const long long n_tasks = 3ll * n_pairs;
+    const int grid = graph_minutiae_grid(n_tasks);
+    if (!slab || slab_bytes < (size_t)grid * kMinuSlabWgBytes) return hipErrorInvalidValue;
+    const hipError_t e0 = hipMemsetAsync(g.task_ctr + 1, 0, 4, stream);
+    if (e0 != hipSuccess) return e0;
+    const GraphTap tap{nullptr, nullptr, 2};
+    if (s89_tie_order) hipLaunchKernelGGL((k_graph_minutiae<1, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, (unsigned char*)slab, tap, pair_tab);
+    else hipLaunchKernelGGL((k_graph_minutiae<0, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, cands, cand_n, parts, corr_out, corr_n, (unsigned char*)slab, tap, pair_tab);
+    return hipGetLastError();
+}
+#endif   // AFIS_GRAPH_PAIRS_UNIT
+#ifndef AFIS_GRAPH_PAIRS_UNIT
 
 // parity tap: the device's atan2 on the grid of integer coordinate differences, out[(dy + R) * (2R + 1) + (dx + R)]
 __global__ __launch_bounds__(256) void k_debug_atan2_grid(int R, float* __restrict__ out)
@@ -1387,5 +1428,7 @@ hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset)
     return hipSuccess;
 #endif
 }
+
+#endif   // AFIS_GRAPH_PAIRS_UNIT
 
 }  // namespace afis

@@ -163,6 +163,9 @@ template <typename I> __device__ void stdsort_prefix_wave(I* A, int n, int K, co
 }
 
 // Global scratch of one workgroup (pairs too large for the LDS fast path): simi[n] | keys[n] | rowsum[2048] | colsum[2048] (| order[n] | lpos[n] | rpos[n] with option s3_tie_order)
+// PAIRS (afis_correspondences_pairs): the tasks are not a latents x gallery cross product but a list of (latent, template) pairs — fb = [n_pairs | (query of the group,
+// shard-local template) x n_pairs], task 3 p + s is selected template s of pair p, and its list goes to the compact slot of that number: cands[3 p + s][120], cand_n[3 p + s]
+template <bool PAIRS>
 __global__ __launch_bounds__(kThreads) void k_minu_cands(QueryDev q, GalleryDev g, float* __restrict__ scratch, size_t scratch_per_wg,
                                                          MinuCand* __restrict__ cands, int32_t* __restrict__ cand_n,
                                                          const int32_t* __restrict__ fb /* NULL: every task; else fb[0] tasks listed in fb[1 ...] */,
@@ -176,13 +179,14 @@ __global__ __launch_bounds__(kThreads) void k_minu_cands(QueryDev q, GalleryDev 
     PHASE_DECL();
     const long long n_tasks = (long long)q.nq * 3 * g.G;
     const int tid = threadIdx.x;
-    const long long n_work = fb ? (long long)fb[0] : n_tasks;
+    const long long n_work = PAIRS ? 3ll * fb[0] : fb ? (long long)fb[0] : n_tasks;
     if (diag != nullptr && blockIdx.x == 0 && tid == 0) diag[kDiagFallback] = (unsigned long long)n_work;
     for (long long work = blockIdx.x; work < n_work; work += gridDim.x) {
-        const long long task = fb ? (long long)fb[1 + work] : work;
+        const long long task = PAIRS ? work : fb ? (long long)fb[1 + work] : work;
         // task order: gallery template fastest, then selected template, then query
-        const int gi = (int)(task % g.G);
-        const int qs = (int)(task / g.G);                    // qi*3 + s
+        int gi, qs;                                          // qs = qi*3 + s
+        if constexpr (PAIRS) { const int p = (int)(work / 3); qs = fb[1 + 2 * p] * 3 + (int)(work - 3ll * p); gi = fb[2 + 2 * p]; }
+        else { gi = (int)(task % g.G); qs = (int)(task / g.G); }
         const int l0 = q.lm_off[qs], nL = q.lm_off[qs + 1] - l0;
         const int r0 = g.minu_off[gi], nR = g.minu_off[gi + 1] - r0;
         if (nL <= 0 || nR <= 0) { if (tid == 0) cand_n[task] = 0; continue; }     // matcher.cpp:400-404
@@ -979,13 +983,28 @@ hipError_t launch_minu_cands(const QueryDev& q, const GalleryDev& g, float* scra
         }
     }
     // opt-in to > 64 KB of dynamic LDS: a per-device function attribute, set on every launch (cheap) rather than cached per process
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_minu_cands), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MinuSmem));
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_minu_cands<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MinuSmem));
     if (e != hipSuccess) return e;
     const int grid = (int)(n_tasks < n_wg ? n_tasks : n_wg);
     // (the arrays of the std::sort restatement — 50 KB at the end of MinuSmem — are asked for only when the option is on: two workgroups per CU otherwise, as before)
     const size_t smem = ref_tie_order ? sizeof(MinuSmem) : offsetof(MinuSmem, order);
-    hipLaunchKernelGGL(k_minu_cands, dim3(grid), dim3(kThreads), smem, stream, q, g, scratch, scratch_floats_per_wg, cands, cand_n,
+    hipLaunchKernelGGL(k_minu_cands<false>, dim3(grid), dim3(kThreads), smem, stream, q, g, scratch, scratch_floats_per_wg, cands, cand_n,
                        force_generic ? (const int32_t*)nullptr : fallback, diag, ref_tie_order);
+    return hipGetLastError();
+}
+
+size_t minu_cands_lds_bytes(int s3_tie_order) { return s3_tie_order ? sizeof(MinuSmem) : offsetof(MinuSmem, order); }
+
+hipError_t launch_minu_cands_pairs(const QueryDev& q, const GalleryDev& g, float* scratch, size_t scratch_floats_per_wg, int n_wg, int s3_tie_order,
+                                   const int32_t* pair_tab, int n_pairs, MinuCand* cands, int32_t* cand_n, hipStream_t stream)
+{
+    if (n_pairs <= 0) return hipSuccess;
+    if (n_wg < 1 || !pair_tab || !scratch || n_pairs > 0x7ffffff0 / 3) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_minu_cands<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MinuSmem));
+    if (e != hipSuccess) return e;
+    const int grid = 3 * n_pairs < n_wg ? 3 * n_pairs : n_wg;
+    hipLaunchKernelGGL(k_minu_cands<true>, dim3(grid), dim3(kThreads), minu_cands_lds_bytes(s3_tie_order), stream, q, g, scratch, scratch_floats_per_wg, cands, cand_n,
+                       pair_tab, (unsigned long long*)nullptr, s3_tie_order ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -234,6 +234,34 @@ def merge_positions(status: np.ndarray, score: np.ndarray, n_before_per_rank: np
     return out_status, out_score, n_before, owner
 
 
+CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                     # AFIS_CORR_* (include/afis_matcher.h)
+
+
+def merge_correspondences(per_rank_counts, per_rank_xy, per_rank_part=None):
+    """One pair list handed to every rank of a sharded gallery (Matcher.correspondences_pairs' raw arrays): per_rank_counts [R, P, 3], per_rank_xy [R, P, 3, 120, 4],
+    per_rank_part [R, P, 3] or None.  The shards' templates are disjoint, so at most one rank covers a pair — the rank whose counts are not AFIS_CORR_NOT_COVERED —
+    and the pair is taken from it, bytes as they are.  Returns (counts [P, 3], xy [P, 3, 120, 4], owner [P]) — with per_rank_part also part [P, 3], before owner — :
+    counts AFIS_CORR_NOT_COVERED, xy and part zero, owner -1 for a pair no rank covers.  Two ranks covering one pair raise ValueError."""
+    cn = np.asarray(per_rank_counts, np.int32); xy = np.asarray(per_rank_xy, np.int16)
+    if cn.ndim != 3 or cn.shape[2] != 3 or xy.shape != cn.shape + (120, 4):
+        raise ValueError("merge_correspondences: counts is [ranks, pairs, 3] and xy [ranks, pairs, 3, 120, 4]")
+    pt = None if per_rank_part is None else np.asarray(per_rank_part, np.float32)
+    if pt is not None and pt.shape != cn.shape:
+        raise ValueError("merge_correspondences: part is [ranks, pairs, 3], as counts")
+    covered = (cn != CORR_NOT_COVERED).any(axis=2)                          # (a rank answers a pair with three times -2 or not at all)
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"merge_correspondences: pairs {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    P = cn.shape[1]
+    any_owner = covered.any(axis=0) if cn.shape[0] else np.zeros(P, bool)
+    owner = np.where(any_owner, covered.argmax(axis=0) if cn.shape[0] else 0, -1).astype(np.int64)
+    out_c = np.full((P, 3), CORR_NOT_COVERED, np.int32); out_xy = np.zeros((P, 3, 120, 4), np.int16); out_p = np.zeros((P, 3), np.float32)
+    have = np.flatnonzero(any_owner)
+    out_c[have] = cn[owner[have], have]; out_xy[have] = xy[owner[have], have]
+    if pt is not None:
+        out_p[have] = pt[owner[have], have]
+    return (out_c, out_xy, owner) if pt is None else (out_c, out_xy, out_p, owner)
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""

@@ -1,0 +1,264 @@
+"""afis_correspondences_pairs: the surviving minutiae correspondences of a whole candidate list in one launch sequence, against the oracle's stage-2 traces
+(used as test_gpu_parity.py::test_correspondences_match_oracle uses them) and, for `part`, against afis_search's parts.  Every comparison is exact: coordinates byte for
+byte, part scores bit for bit.  Tie modes of the oracle as the parity tests map them: default order 1, option s3_tie_order 1 -> 4, option ref_tie_order 2 -> 0 (std::sort at
+every site; on the minutiae scorers that is mode 9)."""
+import importlib
+
+import numpy as np
+import pytest
+
+import cases
+
+pytestmark = pytest.mark.gpu
+T = importlib.import_module("msu-latentafis_amd.host.templates")
+M = importlib.import_module("msu-latentafis_amd.host.matcher")
+
+SEL = (26, 2, 11)
+ZERO = np.zeros(1, np.float32).view(np.uint32)[0]
+
+
+@pytest.fixture(scope="module")
+def cb(codebook_bytes):
+    return T.Codebook.from_bytes(codebook_bytes)
+
+
+@pytest.fixture(scope="module")
+def small(cb):
+    return cases.small_set(cb)
+
+
+class Expected:
+    """The yardstick of one (latents, gallery) set: per (latent, print) the three survivor lists the oracle's stage-2 trace gives, computed once per pair and tie mode."""
+
+    def __init__(self, oracle, codebook_bytes, lats, gal):
+        self.orc, self.lats, self.gal = oracle, lats, gal
+        self.ocb = oracle.codebook(codebook_bytes)
+        self.hl = [oracle.latent(self.ocb, T.write_latent(L))[0] for L in lats]
+        self.hr = [oracle.rolled(T.write_rolled(R))[0] if R.minu else None for R in gal]      # (a print without minutiae cannot be written as a file: nothing is scored)
+        self.cache = {}
+
+    def pair(self, q, g, tie_mode):
+        key = (q, g, tie_mode)
+        if key not in self.cache:
+            L, R = self.lats[q], self.gal[g]
+            latent_empty = len(L.minu) <= SEL[0] and not L.tex                                  # matcher.cpp:383-386: nothing is matched
+            out = []
+            for s in range(3):
+                tr = None if (latent_empty or not R.minu) else self.orc.trace(self.ocb, self.hl[q], self.hr[g], which=s + 1, stage=2, tie_mode=tie_mode)
+                if tr is None:
+                    out.append(None)
+                    continue
+                _, li, ri = tr
+                lm, rm = L.minu[SEL[s]], R.minu[0]
+                out.append(np.stack([lm.x[li], lm.y[li], rm.x[ri], rm.y[ri]], axis=1).astype(np.int16) if len(li) else np.zeros((0, 4), np.int16))
+            self.cache[key] = out
+        return self.cache[key]
+
+
+def check(res, exp, query, local, tie_mode, parts=None):
+    """Every pair of a correspondences_pairs result against the yardstick; local[i] = the print's place in exp.gal, or None for a pair the shard does not cover.
+    -> the number of (pair, scorer) lists with survivors."""
+    counts, xy, part = res["counts"], res["xy"], res["part"]
+    n_surv = 0
+    for i, (q, g) in enumerate(zip(query, local)):
+        if g is None:
+            assert (counts[i] == M.CORR_NOT_COVERED).all() and not xy[i].any() and all(c is M.NOT_COVERED for c in res["corr"][i]), i
+            assert part is None or (part[i].view(np.uint32) == ZERO).all(), i
+            continue
+        want = exp.pair(int(q), g, tie_mode)
+        for s in range(3):
+            if want[s] is None:
+                assert counts[i, s] == M.CORR_NOT_RUN and res["corr"][i][s] is None and not xy[i, s].any(), (i, q, g, s)
+                assert part is None or part[i, s].view(np.uint32) == ZERO, (i, q, g, s)
+                continue
+            n = len(want[s])
+            assert counts[i, s] == n, (i, q, g, s, counts[i, s], n)
+            assert np.array_equal(xy[i, s, :n], want[s]) and not xy[i, s, n:].any(), (i, q, g, s)
+            assert np.array_equal(res["corr"][i][s], want[s])
+            if parts is not None:
+                assert part[i, s].view(np.uint32) == parts[q, g, s].view(np.uint32), (i, q, g, s, part[i, s], parts[q, g, s])
+            n_surv += n > 0
+    return n_surv
+
+
+def _open(codebook_bytes, gal, index_base=0, **options):
+    m = M.Matcher(codebook_bytes)
+    for k, v in options.items():
+        m.set_option(k, v)
+    m.gallery_add(gal)
+    m.gallery_commit(index_base)
+    return m
+
+
+def test_all_pairs_shuffled_over_two_launch_groups_and_three_chunks(codebook_bytes, oracle, small):
+    lats, gal = small
+    m = _open(codebook_bytes, gal, query_batch=2, corr_pairs_per_launch=50)
+    assert m.get_option("corr_pairs_per_launch") == 50
+    qh = m.upload_queries(lats)                                            # launch groups {0, 1} and {2}
+    parts = m.search_resident(qh, k=0, want_parts=True)["parts"]
+    assert m.timing()["launch_groups"] == 2
+    rng = np.random.default_rng(12)
+    order = rng.permutation(len(lats) * len(gal))
+    order = np.concatenate([order, rng.choice(order, 10, replace=False)])  # 130 pairs, ten of them twice: chunks of 50, 50, 30
+    query, idx = (order // len(gal)).astype(np.int32), (order % len(gal)).astype(np.int64)
+    res = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    assert m.get_option("correspondences_us") > 0
+    exp = Expected(oracle, codebook_bytes, lats, gal)
+    n_surv = check(res, exp, query, [int(g) for g in idx], 1, parts)
+    mates = sum(int((res["counts"][np.flatnonzero((query == q) & (idx == 3 * q))[0]] > 0).any()) for q in range(len(lats)))
+    assert mates >= 3 and n_surv >= 3, (mates, n_surv)                      # the planted mates (prints 3 q) have survivors
+    for i in range(len(order) - 10, len(order)):                            # a repeated pair: identical bytes
+        j = int(np.flatnonzero(order[:len(order) - 10] == order[i])[0])
+        assert res["counts"][i].tobytes() == res["counts"][j].tobytes() and res["xy"][i].tobytes() == res["xy"][j].tobytes() and res["part"][i].tobytes() == res["part"][j].tobytes()
+    # the one-latent call runs on the same driver: the same bytes
+    for q in range(len(lats)):
+        one = m.correspondences(lats[q], list(range(len(gal))))
+        for g in range(len(gal)):
+            i = int(np.flatnonzero((query == q) & (idx == g))[0])
+            for s in range(3):
+                assert (one[g][s] is None) == (res["corr"][i][s] is None) and (one[g][s] is None or np.array_equal(one[g][s], res["corr"][i][s]))
+    m.free_queries(qh)
+    m.close()
+
+
+def _rules(cb):
+    base, named = cases.edge_latents(cb)
+    gal = cases.rules_gallery(cb, base)
+    gal += [T.FPTemplate(minu=[], tex=list(gal[1].tex)), T.FPTemplate()]    # a print without minutiae, an empty entry
+    return list(named.values()), gal
+
+
+def _shapes(cb):
+    return cases.edge_shapes_set(cb)
+
+
+def _packed(cb):
+    pairs = cases.packed_path_pairs(cb)
+    return [L for L, _ in pairs], [R for _, R in pairs]
+
+
+@pytest.mark.parametrize("make", [_rules, _shapes, _packed], ids=["selection_rules", "edge_shapes", "coordinates_beyond_2047"])
+def test_selection_rules_and_shapes_off_the_lds_path(codebook_bytes, cb, oracle, make):
+    lats, gal = make(cb)
+    if make is _rules:
+        assert sorted(len(R.minu[0].x) for R in gal[3:6]) == [200, 400, 600]                    # beyond kFastL x kFastR = 64 x 128: the similarity matrix in global scratch
+        assert {len(L.minu) for L in lats} >= {28, 12, 2, 0}                                    # latents without template 26 / 11 / 2
+    m = _open(codebook_bytes, gal)
+    qh = m.upload_queries(lats)
+    parts = m.search_resident(qh, k=0, want_parts=True)["parts"]
+    query = np.repeat(np.arange(len(lats), dtype=np.int32), len(gal)); idx = np.tile(np.arange(len(gal), dtype=np.int64), len(lats))
+    res = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    exp = Expected(oracle, codebook_bytes, lats, gal)
+    n_surv = check(res, exp, query, [int(g) for g in idx], 1, parts)
+    assert n_surv >= 3
+    if make is _rules:
+        c = res["counts"].reshape(len(lats), len(gal), 3)
+        assert (c[:, -2:] == M.CORR_NOT_RUN).all()                                             # the print without minutiae, the empty entry
+        empty = [i for i, L in enumerate(lats) if len(L.minu) <= 26 and not L.tex]
+        assert empty and all((c[i] == M.CORR_NOT_RUN).all() for i in empty)                    # the latent-empty query
+        assert (c[:, :9] >= 0).any(axis=(0, 1)).all() and (c[:, :9] == M.CORR_NOT_RUN).any()   # every scorer ran somewhere, and some latent lacked a selected template
+    m.free_queries(qh)
+    m.close()
+
+
+def test_degenerate_keys_in_the_reference_sort_order(codebook_bytes, cb, oracle):
+    pairs = cases.degenerate_key_pairs(cb)
+    lats, gal = [L for L, _ in pairs], [R for _, R in pairs]
+    m = _open(codebook_bytes, gal, s3_tie_order=1)
+    qh = m.upload_queries(lats)
+    parts = m.search_resident(qh, k=0, want_parts=True)["parts"]
+    query = np.repeat(np.arange(3, dtype=np.int32), 3); idx = np.tile(np.arange(3, dtype=np.int64), 3)
+    res = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    check(res, Expected(oracle, codebook_bytes, lats, gal), query, [int(g) for g in idx], 4, parts)
+    m.free_queries(qh)
+    m.close()
+
+
+def test_mates_under_ref_tie_order_2(codebook_bytes, oracle, small):
+    lats, gal = small
+    m = _open(codebook_bytes, gal, ref_tie_order=2)
+    qh = m.upload_queries(lats)
+    parts = m.search_resident(qh, k=0, want_parts=True)["parts"]
+    query = np.repeat(np.arange(3, dtype=np.int32), 4); idx = np.array([3 * q + j for q in range(3) for j in (0, 1, 2, 9 + q)], np.int64)   # every latent's three mates and a non-mate
+    res = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    n_surv = check(res, Expected(oracle, codebook_bytes, lats, gal), query, [int(g) for g in idx], 0, parts)
+    assert n_surv >= 3
+    m.free_queries(qh)
+    m.close()
+
+
+def test_the_last_search_matrix_survives_the_pair_call(codebook_bytes, oracle, small):
+    lats, gal = small
+    gal = gal[:20]
+    m = _open(codebook_bytes, gal)
+    qh = m.upload_queries(lats)
+    m.search_resident(qh, k=0)
+    ninf = float("-inf")
+    h1 = m.rank_hits(ninf, 24)                                              # cap 24 > G = 20: four -1 pads per list
+    idx = h1["idx"].reshape(-1); query = np.repeat(np.arange(len(lats), dtype=np.int32), 24)
+    assert (idx == -1).sum() == 4 * len(lats)
+    res = m.correspondences_pairs(qh, query, idx)
+    check(res, Expected(oracle, codebook_bytes, lats, gal), query, [int(g) if g >= 0 else None for g in idx], 1)
+    assert (res["counts"][idx == -1] == M.CORR_NOT_COVERED).all() and (res["counts"][idx >= 0] != M.CORR_NOT_COVERED).all()
+    h2 = m.rank_hits(ninf, 24)                                              # AFIS_OK, and the same lists
+    for k in ("n_hits", "idx", "score"):
+        assert h1[k].tobytes() == h2[k].tobytes(), k
+    # the one-latent call keeps its contract: it invalidates the matrix
+    m.correspondences(lats[0], [0, 1])
+    with pytest.raises(M.AfisError, match="afis error -3"):
+        m.rank_hits(ninf, 24)
+    m.free_queries(qh)
+    m.close()
+
+
+def test_a_handle_from_before_the_edits_and_a_shard_at_index_base_1000(codebook_bytes, oracle, small):
+    lats, gal = small
+    BASE = 1000
+    m = _open(codebook_bytes, gal[:30], index_base=BASE)
+    qh = m.upload_queries(lats)                                            # before the removal and before the appending commit
+    m.gallery_remove([BASE + 3])                                            # latent 1's best mate
+    m.gallery_reopen(); m.gallery_add(gal[30:36]); m.gallery_commit(BASE)
+    assert m.resident_size == 36
+    parts = m.search(lats, k=0, want_parts=True)["parts"]
+    local = [0, 3, 4, 29, 30, 33, 35, None, None, None, None]
+    glob = [BASE + 0, BASE + 3, BASE + 4, BASE + 29, BASE + 30, BASE + 33, BASE + 35, BASE + 36, BASE - 1, 3, -1]   # one past the shard, one before it, a local index, a pad
+    query = np.repeat(np.arange(len(lats), dtype=np.int32), len(glob)); idx = np.tile(np.array(glob, np.int64), len(lats))
+    res = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    shard = list(gal[:36]); shard[3] = T.FPTemplate()                       # the removed print is an empty entry
+    n_surv = check(res, Expected(oracle, codebook_bytes, lats, shard), query, local * len(lats), 1, parts)
+    c = res["counts"].reshape(len(lats), len(glob), 3)
+    assert (c[:, 1] == M.CORR_NOT_RUN).all() and (c[:, 7:] == M.CORR_NOT_COVERED).all() and (c[:, 4:7] >= 0).all() and n_surv >= 2
+    m.free_queries(qh)
+    m.close()
+
+
+def test_errors_and_the_empty_cases(codebook_bytes, cb, small):
+    lats, gal = small
+    _, named = cases.edge_latents(cb)
+    lats = [lats[0], named["minu26_notex"]]                                 # the second is latent-empty
+    m = M.Matcher(codebook_bytes)
+    m.gallery_add(gal[:6])
+    import ctypes as C
+    z32 = np.zeros(1, np.int32); z64 = np.zeros(1, np.int64); cn = np.zeros(3, np.int32); xy = np.zeros(3 * 120 * 4, np.int16)
+    args = (M._ptr(z32, C.c_int32), M._ptr(z64, C.c_int64), M._ptr(cn, C.c_int32), M._ptr(xy, C.c_int16), None)
+    other = M.Matcher(codebook_bytes)                                      # no handle can be made on a context before its first commit: a real one of a second context
+    other.gallery_add(gal[:2]); other.gallery_commit(0)
+    oh = other.upload_queries(lats[:1])
+    assert m.lib.afis_correspondences_pairs(m.ctx, oh[0], 1, *args) == -3   # AFIS_ESTATE before the first commit
+    other.free_queries(oh); other.close()
+    m.gallery_commit(0)
+    qh = m.upload_queries(lats)
+    assert m.lib.afis_correspondences_pairs(None, qh[0], 1, *args) == -1 and m.lib.afis_correspondences_pairs(m.ctx, None, 1, *args) == -1
+    assert m.lib.afis_correspondences_pairs(m.ctx, qh[0], -1, *args) == -1
+    assert m.lib.afis_correspondences_pairs(m.ctx, qh[0], 1, None, *args[1:]) == -1 and m.lib.afis_correspondences_pairs(m.ctx, qh[0], 1, args[0], args[1], None, args[3], None) == -1
+    for bad in (-1, 2):
+        with pytest.raises(M.AfisError, match="afis error -1"):
+            m.correspondences_pairs(qh, [0, bad], [0, 0])
+    assert m.lib.afis_correspondences_pairs(m.ctx, qh[0], 0, None, None, None, None, None) == 0
+    res = m.correspondences_pairs(qh, [], [])
+    assert res["counts"].shape == (0, 3) and res["corr"] == []
+    res = m.correspondences_pairs(qh, [1] * 6 + [0], list(range(6)) + [0], want_parts=True)
+    assert (res["counts"][:6] == M.CORR_NOT_RUN).all() and not res["xy"][:6].any() and (res["part"][:6].view(np.uint32) == ZERO).all()
+    assert (res["counts"][6] >= 0).all()                                    # the context is usable after the refused calls
+    m.free_queries(qh)
+    m.close()
