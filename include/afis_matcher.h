@@ -253,7 +253,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     The matrix stays rankable from the successful return of the search until the next call on the context that queues device work or edits the gallery —
  *                     a search (a failed or timed-out one included), afis_queries_upload, afis_correspondences, afis_match_all_templates, every gallery
  *                     edit and export, afis_subset_create, afis_subset_free, a change of option "bound_cus" — after which afis_rank_subjects is AFIS_ESTATE.  It may itself
- *                     be repeated, with another k or another handle; afis_correspondences_pairs, afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
+ *                     be repeated, with another k or another handle; afis_correspondences_pairs, afis_score_pairs, afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
  *                     afis_last_error and afis_gallery_size leave the matrix alone.  No result of a search changes because subjects exist.
  * Shards: every rank labels its own shard and ranks its own subjects; the per-rank lists merge exactly although a person's prints may lie in several shards
  * (host/sharding.py::merge_subject_topk). */
@@ -619,6 +619,44 @@ int afis_correspondences_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
                                int32_t* counts /*[n_pairs][3]*/, int16_t* xy /*[n_pairs][3][120][4]*/,
                                float* part /*[n_pairs][3] or NULL*/);
 
+/* Pair scoring: the fused score — and on request the four parts — of n_pairs (latent, rolled print) pairs, without scoring a matrix: one verification (1:1), the N labelled
+ * mates of a ROC study, the candidates of per-latent lists that came from another rank, an index or a first stage, the parts of a hit list after a search that was run
+ * without them.  The arguments follow afis_correspondences_pairs rule for rule: q is a handle of afis_queries_upload or afis_queries_upload_reserved of ANY gallery epoch,
+ * query[i] a query position of the handle, idx[i] a global index of the RESIDENT shard as it stands — never a subset's position, whatever search ran last.  Pairs may come
+ * in any order and repeat.
+ *   a covered pair (index_base <= idx[i] < index_base + G):  status[i] = AFIS_PAIR_OK; score[i] is bit for bit afis_search's scores[query[i]][idx[i] - index_base] — the -1
+ *                                                      of an empty or removed print and of a latent-empty query included —, parts[i*4 + 0..3] (parts may be NULL) bit for bit
+ *                                                      its parts of that cell (+0.0f four times where the score is that -1: no scorer ran), under every value of
+ *                                                      "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9 alike
+ *   an uncovered pair (the -1 that pads the list calls included):  status[i] = AFIS_PAIR_NOT_COVERED, score[i] = -inf, parts +0.0f, silently: the same pair list can go to
+ *                                                      every rank of a sharded gallery (host/sharding.py::merge_pair_scores)
+ * The call neither writes nor invalidates the last search's matrix: every ranking call may precede and follow it.  AFIS_EINVAL: a null ctx or q, n_pairs < 0, a null
+ * query, idx, status or score with n_pairs > 0, a query[i] outside 0 .. n_q - 1; AFIS_ESTATE before the first commit; n_pairs == 0 is AFIS_OK.  Device and pinned room is
+ * ensured before anything is queued: AFIS_EDEVICE when that fails, with nothing changed that a caller can see — the caller's arrays and the last search's matrix are
+ * untouched; the context's own scratch buffers may have been reallocated, and "score_pairs_us" reads 0.
+ * Any n_pairs: the pairs that are scored are cut into chunks of at most option "score_pairs_per_launch" pairs (1 .. 1 048 576; default AFIS_SCORE_PAIRS_PER_LAUNCH).  A pair
+ * costs about 5.8 KB of device memory for the minutiae stage (candidates 2880 B, a survivor scratch 2880 B, counts, parts, score, the tables' entries) plus lt_pad x 8 bytes
+ * for the dense texture row maxima (lt_pad: the longest latent texture template of the handle, at most 1000 rows: 8 KB) — the default keeps a chunk below 113 MB — and 36
+ * bytes pinned; beside them the list kernels' slabs for a chunk's launches (60 KB per pair up to 16 384 pairs for the texture lists, 3 x 20 KB up to 10 922 for the
+ * minutiae lists).  Per chunk one upload of the tables, then per launch group of the handle the any-shape candidate kernel and the minutiae list kernel over the group's
+ * pair table, the exact texture row maxima (k_adc_pairs: a workgroup per 8 latent rows and segment of at most 64 pairs of one latent, the look-up table tile built in LDS),
+ * the texture list kernel and the fusion in their pair forms, and one copy back.  Option "score_pairs_us" (read-only): the device time of the last call's launches, from
+ * HIP events around every chunk's, summed; 0 when nothing was queued.  Host waits are bounded as a search's are ("search_timeout_s").
+ * Cost against the route through a subset (afis_subset_create over the union of the list's prints, afis_search_subset_resident, afis_subset_free), device time on one
+ * MI355X, 100 latents x 100 000 prints, interleaved runs (profiles/score_pairs_timing.json): the flattened lists of
+ * afis_rank_hits(-inf, 100) — 10 000 pairs, 100 per latent, against a union of 9 511 prints x 100 latents — 26.3 ms against 191.4 ms (7.3 x); one pair per latent — 100
+ * pairs against 100 x 100 — 6.2 ms against 12.6 ms (2.0 x); ONE latent against its 4 096 best candidates — where the subset route scores exactly the same 4 096 pairs with
+ * the search's tuned kernels — 6.4 ms against 2.8 ms: there the subset is the better call, 2.3 x.  So: latents with candidate lists of their own — the pair call, at 100 pairs
+ * per latent and at 1; ONE latent (or latents that share their candidates) with thousands of pairs per latent — afis_subset_create + afis_search_subset_resident.  Per pair
+ * the call cost 1.6 - 2.6 us on the two long lists where a subset search cost 0.2 - 0.7 us per cell of its cross product: for lists of thousands of pairs the crossover lies
+ * where (latents x union of their prints) is some three to ten times the pair list (an estimate from these figures, not a measurement).  Nothing here is tuned. */
+#define AFIS_PAIR_OK           0
+#define AFIS_PAIR_NOT_COVERED  1
+#define AFIS_SCORE_PAIRS_PER_LAUNCH 8192
+int afis_score_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
+                     const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
+                     int32_t* status /*[n_pairs]*/, float* score /*[n_pairs]*/, float* parts /*[n_pairs][4] or NULL*/);
+
 /* afis_get_timing2 copies min(struct_size, sizeof(afis_timing)) bytes: pass sizeof(afis_timing) of the header the caller was compiled
  * against, so that a library with a longer struct never writes past the caller's.  afis_get_timing (kept for callers of the round-2
  * header) fills only the fields up to `pairs` (48 bytes, the struct of that header); the fields after it need afis_get_timing2. */
@@ -669,6 +707,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
  * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
  * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.
+ * "score_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_SCORE_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_score_pairs at most — about 5.8 KB of device
+ * memory each plus 8 bytes per row of the handle's longest latent texture template (at most 8 KB), and 36 bytes of pinned host memory.  "score_pairs_us" (read-only): the
+ * device time of the last afis_score_pairs' launches (per chunk and launch group k_minu_cands<true>, k_graph_minutiae in its pair form, k_adc_pairs, k_graph_texture in its
+ * pair form, k_fuse_pairs), from HIP events around every chunk's, summed; 0 when that call queued nothing.
  * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
  * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);

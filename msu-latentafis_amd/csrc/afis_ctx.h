@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -178,6 +178,9 @@ struct afis_ctx : Shard {
     DevBuf corr_buf;                     // afis_correspondences_pairs: one chunk's pair tables, candidate lists, survivors, counts and parts (about 5.8 KB per pair of option corr_pairs_per_launch)
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
+    DevBuf pair_buf, pair_tex_slab;      // afis_score_pairs: one chunk's candidate lists, survivor scratch, counts, dense row maxima, scores, parts and tables (kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch), and the texture list kernel's slab for a chunk's launches
+    int score_pairs_per_launch = kScorePairsPerLaunch;   // option score_pairs_per_launch: pairs per chunk of that call at most
+    int64_t score_pairs_us = 0;          // option score_pairs_us (read-only): device time of the last afis_score_pairs' launches (HIP events around every chunk's, summed)
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
     int64_t eligible_classes = 0;        // option eligible_classes (read-only): classes (distinct mask triples) of the last afis_search_eligible
     int64_t eligible_expand_us = 0;      // option eligible_expand_us (read-only): device time of that call's k_expand_rows launches, HIP events around each, summed over the classes

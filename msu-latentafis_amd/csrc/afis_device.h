@@ -246,6 +246,20 @@ hipError_t launch_graph_minutiae_pairs(const QueryDev& q, const GalleryDev& g, c
                                        float* parts, short4* corr_out, int32_t* corr_n, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream);
 // S10: fusion -> scores[q*G+g]
 hipError_t launch_fuse(const QueryDev& q, const GalleryDev& g, const float* parts, float* scores, hipStream_t stream);
+// afis_score_pairs (afis_pairs.cpp): the fused score and the four parts of a TABLE of pairs, group after group of the handle: after the two minutiae launches above (survivors
+// into a scratch area), launch_adc_pairs (adc_pairs.hip) — S4-S6 exactly, over the group's pair table and the work list `seg` of pair_tables.h ((first pair, pairs <=
+// kAdcPairsSegment) per segment of one latent's pairs; grid = segments x the group's 8-row tiles) -> the dense row maxima rm_val / rm_arg[p * q.lt_pad + row] —,
+// launch_graph_texture_pairs (graph_pairs.hip: S7+S8b+S9 of pair p from those -> parts[4 p + 3]; grid and slab: graph_texture_grid / _slab_bytes of n_pairs tasks) and
+// launch_fuse_pairs (S10 of pair p -> scores[p]: minu.hip::fuse_cell, the search's own expression).
+// A pair costs kScorePairBytes + 8 q.lt_pad bytes of device memory (lt_pad <= 1000: at most 13.8 KB) and 36 bytes of pinned host memory.
+constexpr int kScorePairsPerLaunch = 8192;              // AFIS_SCORE_PAIRS_PER_LAUNCH: option score_pairs_per_launch's default (at most 113 MB of device memory per chunk)
+constexpr int kScorePairsMax = 1 << 20;                 // ... and its ceiling
+constexpr size_t kScorePairBytes = 2 * 3 * kTopMinu * 8 + 2 * 3 * 4 + 16 + 4 + 16;   // candidates, survivors (scratch), their two counts, parts, score, the tables' entries: 5 820
+hipError_t launch_adc_pairs(const QueryDev& q, const GalleryDev& g, const float* codewords, const int32_t* pair_tab, const int32_t* seg, int n_seg,
+                            float* rm_val, int32_t* rm_arg, hipStream_t stream);
+hipError_t launch_graph_texture_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* table_dist, const float* rm_val, const int32_t* rm_arg,
+                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream);
+hipError_t launch_fuse_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* parts, float* scores, hipStream_t stream);
 
 // S11: per-query rank list over the shard's scores [n_q][G] on the device (score descending, index ascending); out_idx[n_q][k] carries
 // index_base + local index (-1 / -inf beyond G)

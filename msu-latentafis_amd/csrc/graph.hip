@@ -948,7 +948,6 @@ __device__ __forceinline__ void tap_write(const GraphTap& tap, const SM& sm, con
 // =====================================================================================================================
 // 14 lists per CU: 11 200 B of LDS (sort keys, picked rows and the angle stage's orientations share one union; the power iterations' values and neighbour indices live in
 // the workgroup's slab in global memory: kTexSlabWgBytes at slab + blockIdx.x * kTexSlabWgBytes) and 128 registers.
-#ifndef AFIS_GRAPH_PAIRS_UNIT
 #ifndef AFIS_TEX_WAVES
 #define AFIS_TEX_WAVES 4
 #endif
@@ -957,22 +956,32 @@ constexpr int kTexRegs = (kTexMax + 63) / 64;     // 16 row maxima per lane: the
 constexpr int kTexFast = 256;                     // a compact list of at most this many rows is ranked whole, four keys per lane (k_graph_texture)
 constexpr int kTexFastRegs = kTexFast / 64;
 
-template <int REF_TIE>   // 1: option ref_tie_order 2 (sort_scores); its own instantiation, so that the default kernel is the code it was
+// PAIRS (afis_score_pairs): the lists of a pair table [n_pairs | (query of the group, shard-local template) x n_pairs] instead of a latents x gallery cross product, by
+// k_graph_minutiae's mechanism below (a parameter pack resolved by pair_tab_of, instantiated in graph_pairs.hip only) — task p is pair p, its row maxima lie in the dense
+// form at rm_val / rm_arg[p * q.lt_pad + row] (k_adc_pairs wrote them; rm_n == NULL) and its score goes to parts[4 p + 3]
+__device__ __forceinline__ const int32_t* pair_tab_of() { return nullptr; }
+__device__ __forceinline__ const int32_t* pair_tab_of(const int32_t* tab) { return tab; }
+template <int REF_TIE, class... TAB>   // REF_TIE 1: option ref_tie_order 2 (sort_scores); its own instantiation, so that the default kernel is the code it was
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAVES, AFIS_TEX_WAVES))) void k_graph_texture(QueryDev q, GalleryDev g, const float* __restrict__ table_dist,
                                                       const float* __restrict__ rm_val, const int32_t* __restrict__ rm_arg,
                                                       const float* __restrict__ rm_cv, const int32_t* __restrict__ rm_n,
-                                                      float* __restrict__ parts, unsigned char* slab_all, GraphTap tap)
+                                                      float* __restrict__ parts, unsigned char* slab_all, GraphTap tap, TAB... tab)
 {
+    constexpr bool PAIRS = sizeof...(TAB) != 0;
+    const int32_t* const ptab = pair_tab_of(tab...);
     __shared__ TexSmem sm;
     const SlabBuf slab = g_slab_buf(slab_all + (size_t)blockIdx.x * kTexSlabWgBytes, (uint32_t)kTexSlabWgBytes);
     const int lane = threadIdx.x;
     GPH_ZERO();
-    const int n_tasks = q.nq * g.G;
+    int n_tasks;
+    if constexpr (PAIRS) n_tasks = ptab[0]; else n_tasks = q.nq * g.G;
     for (;;) {
         const int task = next_task(g.task_ctr + 0);                       // lists differ widely in cost (a mate's is 10 x a non-mate's): tasks are drawn, not dealt
         if (task >= n_tasks) break;
         GPH_T0();
-        const int qi = task / g.G, gi = task - qi * g.G;
+        int qi, gi;
+        if constexpr (PAIRS) { qi = ptab[1 + 2 * task]; gi = ptab[2 + 2 * task]; }
+        else { qi = task / g.G; gi = task - qi * g.G; }
         const int l0 = q.lt_off[qi], n_lt = q.lt_off[qi + 1] - l0;
         const int r0 = g.tex_off[gi], n_rt = g.tex_off[gi + 1] - r0;
         float* out = parts + (size_t)task * 4 + 3;
@@ -1200,6 +1209,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
     GPH_FLUSH();
 }
 
+#ifndef AFIS_GRAPH_PAIRS_UNIT
 hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const float* table_dist,
                                 const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream)
 {
@@ -1213,6 +1223,21 @@ hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const fl
     const GraphTap tap{tap_out, tap_n, tap_stage & 255};
     if ((tap_stage >> 8) & 1) hipLaunchKernelGGL(k_graph_texture<1>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, (unsigned char*)slab, tap);
     else hipLaunchKernelGGL(k_graph_texture<0>, dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, rm_cv, rm_n, parts, (unsigned char*)slab, tap);
+    return hipGetLastError();
+}
+#else    // AFIS_GRAPH_PAIRS_UNIT
+hipError_t launch_graph_texture_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* table_dist, const float* rm_val, const int32_t* rm_arg,
+                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream)
+{
+    if (n_pairs <= 0) return hipSuccess;
+    if (!g.task_ctr || !pair_tab || !rm_val || !rm_arg || !parts) return hipErrorInvalidValue;
+    const int grid = graph_texture_grid(n_pairs);
+    if (!slab || slab_bytes < (size_t)grid * kTexSlabWgBytes) return hipErrorInvalidValue;       // every workgroup writes its own kTexSlabWgBytes
+    const hipError_t e0 = hipMemsetAsync(g.task_ctr + 0, 0, 4, stream);
+    if (e0 != hipSuccess) return e0;
+    const GraphTap tap{nullptr, nullptr, 2};
+    if (s89_tie_order) hipLaunchKernelGGL((k_graph_texture<1, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, (const float*)nullptr, (const int32_t*)nullptr, parts, (unsigned char*)slab, tap, pair_tab);
+    else hipLaunchKernelGGL((k_graph_texture<0, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, (const float*)nullptr, (const int32_t*)nullptr, parts, (unsigned char*)slab, tap, pair_tab);
     return hipGetLastError();
 }
 #endif   // AFIS_GRAPH_PAIRS_UNIT
@@ -1235,8 +1260,7 @@ typedef WaveSmem<kTopMinu, true> MinuGraphSmem;
 // segment, it always had.  The pair form is instantiated in a translation unit of its own (graph_pairs.hip compiles this file with AFIS_GRAPH_PAIRS_UNIT defined: the
 // shared device code, this kernel and launch_graph_minutiae_pairs, nothing else), so that the module the search's list kernels are compiled in — and what the inliner
 // makes of the filters they share — stays as it was
-__device__ __forceinline__ const int32_t* pair_tab_of() { return nullptr; }
-__device__ __forceinline__ const int32_t* pair_tab_of(const int32_t* tab) { return tab; }
+// (pair_tab_of: above k_graph_texture)
 template <int REF_TIE, class... TAB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_MINU_WAVES, AFIS_MINU_WAVES))) void k_graph_minutiae(QueryDev q, GalleryDev g, const MinuCand* __restrict__ cands,
                                                        const int32_t* __restrict__ cand_n, float* __restrict__ parts,

@@ -1012,14 +1012,10 @@ hipError_t launch_minu_cands_pairs(const QueryDev& q, const GalleryDev& g, float
 // S10 fusion: final = score[0] + score[1] + score[2] + score[28]*0.3 (matcher.cpp:188), where the reference's score
 // vector holds the three minutiae scores at [0..2] and the texture score at index (#latent minutiae templates).
 // =====================================================================================================================
-__global__ __launch_bounds__(256) void k_fuse(QueryDev q, GalleryDev g, const float* __restrict__ parts, float* __restrict__ scores)
+// the fused score of one (latent qi, template gi) cell from its four parts p[0..3]: the one definition k_fuse (a search's matrix) and k_fuse_pairs (afis_score_pairs) share
+__device__ __forceinline__ float fuse_cell(const QueryDev& q, const GalleryDev& g, int qi, int gi, const float* __restrict__ p)
 {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long n = (long long)q.nq * g.G;
-    if (idx >= n) return;
-    const int qi = (int)(idx / g.G), gi = (int)(idx - (long long)qi * g.G);
-    if (q.status[qi] != 0 || g.empty[gi]) { scores[idx] = -1.0f; return; }     // :145, :181-187
-    const float* p = parts + (size_t)idx * 4;
+    if (q.status[qi] != 0 || g.empty[gi]) return -1.0f;                         // :145, :181-187
     const int slot = q.tex_slot[qi];
     const float tex = p[3];
     const float a0 = slot == 0 ? tex : p[0];
@@ -1028,7 +1024,24 @@ __global__ __launch_bounds__(256) void k_fuse(QueryDev q, GalleryDev g, const fl
     const float a28 = slot == 28 ? tex : 0.0f;
     float f = a0 + a1;
     f = f + a2;
-    scores[idx] = (float)((double)f + (double)a28 * 0.3);
+    return (float)((double)f + (double)a28 * 0.3);
+}
+
+__global__ __launch_bounds__(256) void k_fuse(QueryDev q, GalleryDev g, const float* __restrict__ parts, float* __restrict__ scores)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n = (long long)q.nq * g.G;
+    if (idx >= n) return;
+    const int qi = (int)(idx / g.G), gi = (int)(idx - (long long)qi * g.G);
+    scores[idx] = fuse_cell(q, g, qi, gi, parts + (size_t)idx * 4);
+}
+
+// afis_score_pairs: score[p] of pair p of the table [n_pairs | (query of the group, shard-local template) x n_pairs] from parts[4 p .. 4 p + 3]
+__global__ __launch_bounds__(256) void k_fuse_pairs(QueryDev q, GalleryDev g, const int32_t* __restrict__ pair_tab, const float* __restrict__ parts, float* __restrict__ scores)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= pair_tab[0]) return;
+    scores[p] = fuse_cell(q, g, pair_tab[1 + 2 * p], pair_tab[2 + 2 * p], parts + (size_t)p * 4);
 }
 
 // =====================================================================================================================
@@ -1099,6 +1112,14 @@ hipError_t launch_fuse(const QueryDev& q, const GalleryDev& g, const float* part
     const long long n = (long long)q.nq * g.G;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_fuse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, q, g, parts, scores);
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* parts, float* scores, hipStream_t stream)
+{
+    if (n_pairs <= 0) return hipSuccess;
+    if (!pair_tab || !parts || !scores) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fuse_pairs, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, q, g, pair_tab, parts, scores);
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@ class AfisError(RuntimeError):
 
 
 CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                     # AFIS_CORR_NOT_RUN, AFIS_CORR_NOT_COVERED (include/afis_matcher.h)
+PAIR_OK, PAIR_NOT_COVERED = 0, 1                                            # AFIS_PAIR_OK, AFIS_PAIR_NOT_COVERED
 
 
 class _NotCovered:
@@ -70,7 +71,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -146,6 +147,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     if hasattr(lib, "afis_correspondences_pairs"):                      # the pair-list export; absent from older builds compared by tools/lib_ab.py
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
+    if hasattr(lib, "afis_score_pairs"):                                # pair scoring; absent from older builds compared by tools/lib_ab.py
+        lib.afis_score_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, fp, fp]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
     lib.afis_pq_encode.argtypes = [vp, fp, C.c_int64, C.POINTER(C.c_uint8)]
@@ -767,6 +770,22 @@ class Matcher:
                                                       _ptr(counts, C.c_int32), _ptr(xy, C.c_int16), _ptr(part, C.c_float) if want_parts else None))
         corr = [[xy[i, s, :counts[i, s]].copy() if counts[i, s] >= 0 else (None if counts[i, s] == CORR_NOT_RUN else NOT_COVERED) for s in range(3)] for i in range(n)]
         return {"counts": counts[:n], "xy": xy[:n], "corr": corr, "part": part[:n] if want_parts else None}
+
+    def score_pairs(self, qhandle, query, idx, want_parts: bool = False):
+        """The fused scores of a LIST of (latent, print) pairs without a matrix (afis_score_pairs): pair i is (query[i], idx[i]), a query position of the upload_queries
+        handle — of any gallery epoch — and a GLOBAL index of the resident shard; any order, repeats allowed; the flattened idx of rank_hits can be passed as it is.
+        -> {"status": [n] int32 — PAIR_OK, or PAIR_NOT_COVERED where this shard does not hold idx[i] (the -1 padding of the list calls included) —, "score": [n] float32,
+        search()'s scores[query[i]][idx[i] - index_base] bit for bit (-1 for an empty or removed print and a latent-empty query; -inf where not covered), "parts": [n][4]
+        float32 with want_parts, search()'s parts of that cell bit for bit (+0.0 where not covered), else None}.  The last search's matrix stays rankable."""
+        qa = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); ia = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        if len(qa) != len(ia):
+            raise ValueError("score_pairs: query and idx must have one length")
+        n = len(qa)
+        status = np.zeros(max(n, 1), np.int32); score = np.zeros(max(n, 1), np.float32)
+        parts = np.zeros((max(n, 1), 4), np.float32) if want_parts else None
+        self._chk(self.lib.afis_score_pairs(self.ctx, qhandle[0], n, _ptr(qa, C.c_int32) if n else None, _ptr(ia, C.c_int64) if n else None,
+                                            _ptr(status, C.c_int32), _ptr(score, C.c_float), _ptr(parts, C.c_float) if want_parts else None))
+        return {"status": status[:n], "score": score[:n], "parts": parts[:n] if want_parts else None}
 
     def One2One_matching_all_templates(self, latent: FPTemplate):
         """matcher.cpp:339-374 against every gallery template: (query status, rolled status [G], scores [G][n_minu + n_tex])."""

@@ -235,6 +235,7 @@ def merge_positions(status: np.ndarray, score: np.ndarray, n_before_per_rank: np
 
 
 CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                     # AFIS_CORR_* (include/afis_matcher.h)
+PAIR_OK, PAIR_NOT_COVERED = 0, 1                                            # AFIS_PAIR_* (include/afis_matcher.h)
 
 
 def merge_correspondences(per_rank_counts, per_rank_xy, per_rank_part=None):
@@ -260,6 +261,34 @@ def merge_correspondences(per_rank_counts, per_rank_xy, per_rank_part=None):
     if pt is not None:
         out_p[have] = pt[owner[have], have]
     return (out_c, out_xy, owner) if pt is None else (out_c, out_xy, out_p, owner)
+
+
+def merge_pair_scores(per_rank):
+    """One pair list handed to every rank of a sharded gallery: per_rank is what Matcher.score_pairs returned on every rank, a sequence of {"status": [P], "score": [P],
+    "parts": [P, 4] or None}.  The shards' templates are disjoint, so at most one rank covers a pair — the rank whose status is AFIS_PAIR_OK — and the pair is taken from
+    it, bits as they are.  Returns {"status", "score", "parts" (None unless every rank gave parts), "owner": [P] the covering rank}: a pair no rank covers stays
+    AFIS_PAIR_NOT_COVERED / -inf / +0.0 with owner -1.  Two ranks covering one pair raise ValueError."""
+    per_rank = list(per_rank)
+    st = np.asarray([np.asarray(r["status"], np.int32).reshape(-1) for r in per_rank], np.int32).reshape(len(per_rank), -1)
+    sc = np.asarray([np.asarray(r["score"], np.float32).reshape(-1) for r in per_rank], np.float32).reshape(len(per_rank), -1)
+    if st.shape != sc.shape:
+        raise ValueError("merge_pair_scores: status and score are [pairs] on every rank, of one length")
+    P = st.shape[1]
+    with_parts = len(per_rank) > 0 and all(r.get("parts") is not None for r in per_rank)
+    pt = np.asarray([np.asarray(r["parts"], np.float32).reshape(-1, 4) for r in per_rank], np.float32).reshape(len(per_rank), -1, 4) if with_parts else None
+    if pt is not None and pt.shape != st.shape + (4,):
+        raise ValueError("merge_pair_scores: parts is [pairs, 4] on every rank")
+    covered = st == PAIR_OK
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"merge_pair_scores: pairs {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    any_owner = covered.any(axis=0) if st.shape[0] else np.zeros(P, bool)
+    owner = np.where(any_owner, covered.argmax(axis=0) if st.shape[0] else 0, -1).astype(np.int64)
+    out_st = np.full(P, PAIR_NOT_COVERED, np.int32); out_sc = np.full(P, -np.inf, np.float32); out_p = np.zeros((P, 4), np.float32) if with_parts else None
+    have = np.flatnonzero(any_owner)
+    out_st[have] = st[owner[have], have]; out_sc[have] = sc[owner[have], have]
+    if with_parts:
+        out_p[have] = pt[owner[have], have]
+    return {"status": out_st, "score": out_sc, "parts": out_p, "owner": owner}
 
 
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
