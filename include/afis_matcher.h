@@ -562,6 +562,61 @@ int afis_gallery_file_names(const char* path, int64_t first, int64_t count, char
  *   query_status  NULL or out : AFIS_QUERY_LATENT_EMPTY when the latent has no template at all (:345-348) */
 int afis_match_all_templates(afis_ctx* ctx, const afis_template_view* query, float* scores, int32_t* rolled_status, int32_t* query_status);
 
+/* Weighted search (no reference counterpart): afis_search fuses one fixed set of a latent's templates — minutiae templates 27, 3 and 12 and 0.3 x texture template 0,
+ * the layout of one extractor.  afis_search_weighted fuses ANY set, per query, as a weighted sum on the device, for a batch of latents, and leaves a matrix the whole
+ * ranking family reads: the accuracy of afis_match_all_templates (all 28 + 1 scores) for lists, hits, subjects, cases, filters and positions, and a sensible score for a
+ * latent of another extractor (a manual markup plus one automatic template, a re-encoding with 12 templates).
+ *   w_minu [n_q][n_wm], w_tex [n_q][n_wt]   one weight row per query; indices are post-strip, as everywhere in this header
+ * Active templates   minutiae template i of query q is ACTIVE when i < queries[q].n_minu, i < n_wm and w_minu[q * n_wm + i] != 0.0f; texture template t by the same
+ *          rule against n_wt / w_tex.  Only active templates are validated (afis_search's view rules) and uploaded; a template past the end of a weight row or with
+ *          weight +-0 costs nothing.
+ * Value of cell (q, g)   -1.0f when the rolled entry is empty or removed; -1.0f for the whole row when query q has no active template at all (status[q] is then
+ *          AFIS_QUERY_LATENT_EMPTY, otherwise AFIS_QUERY_OK); otherwise (float)acc with
+ *            double acc = +0.0;
+ *            for the active minutiae templates in ascending i:  acc = acc + (double)w * (double)v_i;
+ *            then for the active texture templates in ascending t:  the same
+ *          where v is, bit for bit, the entry afis_match_all_templates gives that (latent template, print) — the zeros it leaves included, e.g. for a print without a
+ *          minutiae template — under every value of "s3_tie_order", "ref_tie_order" and "adc_variant" 8 / 9.  The product of two fp32 values is exact in fp64, so the
+ *          definition does not depend on whether a compiler contracts the multiply-add.  Weights must be finite and >= 0 (-0.0f is a zero) so that -1 keeps meaning
+ *          "empty" and every other cell is finite or +inf and >= +0.0, the property all ranking calls state.
+ *          With weights 1 at minutiae templates 26, 2, 11 and 0.3f at texture 0 the call runs exactly the scorers afis_search runs.  It does NOT give afis_search's
+ *          bits: that fusion adds in fp32 and multiplies by the double 0.3 (the two differ by less than 2^-21 x max(1, score)); and it knows nothing of afis_search's
+ *          quirk for latents with fewer than 27 minutiae templates.
+ * The matrix afterwards   after AFIS_OK the context's last-search matrix is this [n_q][G] matrix: a full search's in every respect — no subset, the resident shard as it
+ *          stands — under afis_search's invalidation rules.  Every ranking call reads it unchanged: afis_rank_hits, afis_rank_subject_hits, afis_rank_latent_hits, the
+ *          case and filtered families, afis_rank_positions / afis_rank_subject_positions / afis_count_before and afis_rank_subjects.  afis_correspondences_pairs and
+ *          afis_score_pairs leave it alone, as they do after afis_search (they score afis_search's selection, not the weighted one).
+ * How     per query the active minutiae templates are packed three to a PSEUDO-QUERY in ascending order and the active texture templates one to a pseudo-query:
+ *          n_pq(q) = max(ceil(|A_m| / 3), |A_t|), afis_match_all_templates' packing over the active list.  A scorer's value depends on nothing but its (latent
+ *          template, print), so the packing changes no bit.  The pseudo-queries run through afis_search's launch sequence in BATCHES cut at query boundaries — at most
+ *          option "weighted_batch_pseudo" pseudo-queries (0 [default]: as many as an eighth of the launch-group budget holds the per-part scores of, 16 bytes per
+ *          pair; a query with more pseudo-queries than that is a batch of its own) — their per-part scores stay on the device, and one pass (csrc/template_fold.hip)
+ *          folds a batch's parts into its rows of the combined matrix: one thread per cell, in registers, in the order above.  The combined matrix lives in the spare
+ *          [n_q][G] buffer beside the search's (afis_search_eligible's) and is swapped in at the end; its room, the largest batch's per-part scores and the call's
+ *          tables are ensured before anything is queued (AFIS_EDEVICE when that fails).
+ * Arguments   AFIS_EINVAL: a null ctx, n_q < 0, n_q > 0 with queries NULL, n_wm < 0 or n_wt < 0, a null weight array whose width is > 0 (with n_q > 0), a weight
+ *          that is NaN, infinite or negative, a bad ACTIVE view; AFIS_ESTATE before the first commit.  n_q == 0 returns AFIS_OK as afis_search with no queries does.
+ *          After ANY return other than AFIS_OK — a refused argument included — the last-search matrix is invalid and the call holds nothing it allocated; the
+ *          caller's live subsets and query handles are untouched (afis_search_eligible's rules).  Host waits are bounded as a search's are ("search_timeout_s").
+ * Timing   afis_get_timing*: every additive field is the sum over the batches — pairs = pseudo-queries x G — and the two clock fields come from the batch with the
+ *          most pairs.  Options "weighted_pseudo_queries" and "weighted_fold_us" (read-only) describe the last call.
+ * Not in this interface: a subset form; a resident query-handle form; rank lists of afis_search's own kind (k, topk_idx) — afis_rank_hits(-INFINITY, cap) serves;
+ *          parts; fusion rules other than the weighted sum; the match CLI.
+ * Shards: the columns of different shards are disjoint and the weights common, so the per-rank lists read from this matrix are host/sharding.py::merge_hits /
+ *          merge_subject_hits input as they are.  No result of afis_search changes because this function exists.
+ * Cost    one MI355X, 100 latents of 28 + 1 templates x 100 000 prints, interleaved runs, medians of three after a discarded first, host clock
+ *          (tools/weighted_search_timing.py, profiles/weighted_search_timing.json): (a) all 28 + 1 templates — 1 000 pseudo-queries, 10^8 pairs — 10 384 ms (spread 10)
+ *          against 11 311 ms (spread 17) for the only route there was before, one afis_match_all_templates call per latent with the parent commit's library and the
+ *          fold on the host: 0.92 x, the same bits; nearly all of either is the scoring (device clock 10 339 ms), what the call adds is the matrix the ranking family
+ *          reads.  (b) The reference's selection as weights 1 853.2 ms (spread 19) against afis_search's 1 851.9 ms (spread 12) on the same context, device clock
+ *          1 824.9 against 1 823.8 ms: the plan and the fold cost about a millisecond.  (c) The fold of (a) — 1.64 GB read and written — 293 us (spread 14) where a
+ *          memory-bound pass at 16 bytes per pseudo-pair predicts 260 us at the 6.3 TB/s a float4 copy reaches here (205 us at the specified 8 TB/s): 5.6 TB/s.
+ *          The launch groups of (a) are afis_search's, cut for latents that all carry texture; nine in ten pseudo-queries carry none.  Nothing here is tuned. */
+int afis_search_weighted(afis_ctx* ctx, const afis_template_view* queries, int n_q,
+                         const float* w_minu /*[n_q][n_wm]*/, int n_wm,
+                         const float* w_tex  /*[n_q][n_wt]*/, int n_wt,
+                         float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/);
+
 /* The rank list of One2List_matching, matcher.cpp:306-309, from a score column (host memory, no device work): idx[0 .. k) / sc[0 .. k) = the k best of scores[0 .. n), descending
  * in afis_search's key rank_key(score) (csrc/rank_order.h: the bits of score + 0.0f in their total order; on a NaN-free column that is score descending).
  * ref_order 0: equal keys by ascending index (what afis_search's own top-k delivers); 1: the reference's statement itself — std::sort of the indices 0 .. n-1 on a non-strict
@@ -712,7 +767,11 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * device time of the last afis_score_pairs' launches (per chunk and launch group k_minu_cands<true>, k_graph_minutiae in its pair form, k_adc_pairs, k_graph_texture in its
  * pair form, k_fuse_pairs), from HIP events around every chunk's, summed; 0 when that call queued nothing.
  * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
- * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries. */
+ * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries.
+ * "weighted_batch_pseudo" (settable, >= 0; default 0): the pseudo-queries of one batch of afis_search_weighted at most; 0 = as many as an eighth of the launch-group
+ * budget holds the per-part scores of.  Results do not depend on it.  "weighted_pseudo_queries" (read-only): the pseudo-queries the last afis_search_weighted scored;
+ * "weighted_fold_us" (read-only): the device time of that call's fold launches (k_fold_templates), from HIP events around each, summed over the batches; both 0 after a
+ * call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -77,6 +77,15 @@ int afis_debug_transpose_stats(afis_ctx* ctx, long long* out2);
  * Words, not numbers: every bit pattern passes through unchanged.  AFIS_EINVAL for a list that breaks the rules above; no gallery is needed. */
 int afis_debug_expand_rows(afis_ctx* ctx, const float* cls /*[n_c][m]*/, int n_c, int64_t m, const int32_t* row_of /*[n_c]*/, const int32_t* sel /*[m] or NULL*/,
                            int n_q, int64_t G, float* out /*[n_q][G]*/);
+/* The fold of afis_search_weighted (template_fold.hip: k_fold_templates) on planted data, so that its shapes and bit patterns are swept without a search:
+ * parts [n_pseudo][G][4] stands for one batch's per-part scores, qd [n_q][4] holds per query of the batch (first pseudo-query, pseudo-queries n_pq, of which carry a
+ * texture template n_at <= n_pq, status: != 0 = the query has no active template), w [n_pseudo][4] the weights aligned to the part slots (0 = the slot is not summed),
+ * empty [G] 1 = the rolled entry is empty.  The kernel runs once over out [n_q][G] and out is copied back:
+ *   out[q][g] = -1 where status != 0 or empty[g]; otherwise (float) of the double sum, from +0.0, of (double)w * (double)part over slots 0..2 of pseudo-queries
+ *   first .. first + n_pq - 1 in order, then over slot 3 of first .. first + n_at - 1; a slot of weight +-0 is skipped whatever its part holds.
+ * AFIS_EINVAL for a query whose pseudo-queries leave [0, n_pseudo); no gallery is needed. */
+int afis_debug_fold_templates(afis_ctx* ctx, const float* parts /*[n_pseudo][G][4]*/, int64_t n_pseudo, int64_t G, const int32_t* qd /*[n_q][4]*/, int n_q,
+                              const float* w /*[n_pseudo][4]*/, const uint8_t* empty /*[G]*/, float* out /*[n_q][G]*/);
 
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -184,6 +184,10 @@ struct afis_ctx : Shard {
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
     int64_t eligible_classes = 0;        // option eligible_classes (read-only): classes (distinct mask triples) of the last afis_search_eligible
     int64_t eligible_expand_us = 0;      // option eligible_expand_us (read-only): device time of that call's k_expand_rows launches, HIP events around each, summed over the classes
+    DevBuf wt_tab;                       // afis_search_weighted: one batch's tables (query descriptors [queries][4] int32 | weights [pseudo-queries][4] float); the combined matrix is built in elig_scores and swapped in as afis_search_eligible's is
+    int weighted_batch_pseudo = 0;       // option weighted_batch_pseudo: pseudo-queries per batch of that call at most; 0 = as many as an eighth of the group budget holds the per-part scores of
+    int64_t weighted_pseudo_queries = 0; // option weighted_pseudo_queries (read-only): pseudo-queries the last afis_search_weighted scored
+    int64_t weighted_fold_us = 0;        // option weighted_fold_us (read-only): device time of that call's k_fold_templates launches, HIP events around each, summed over the batches
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -329,13 +333,17 @@ int adc_stage_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, hip
 // null in libafis_hip.so, which rejects those variants.  Hidden: with both libraries in one process, neither may bind to the other's copy.
 typedef int (*DirectAdcStage)(afis_ctx* ctx, Shard& sh, const QueryDev& d, int chunk, hipEvent_t after_lut);
 extern DirectAdcStage g_direct_adc_stage __attribute__((visibility("hidden")));
+int64_t group_budget_bytes(const afis_ctx* ctx);       // device bytes a launch group's buffers may take: option rowmax_budget_mb, or 60 % of what is free
+// afis_timing of a call that runs several searches (afis_eligible.cpp; afis_search_eligible, afis_search_weighted): additive fields summed, the clock fields from the search with the most pairs
+void add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pairs) __attribute__((visibility("hidden")));
 int64_t graph_slab_bytes(int64_t n_pairs);             // both slabs for a launch of n_pairs (latent, rolled) pairs (1.0 GB + 2 x 0.67 GB from 16 384 pairs on)
 int wait_streams(afis_ctx* ctx, std::initializer_list<hipStream_t> streams, const char* what);
 void register_context(afis_ctx* ctx); void unregister_context(afis_ctx* ctx);   // the process-wide list group_budget_bytes consults
 int drain_abandoned(afis_ctx* ctx, bool keep_last_search = false);   // waits (bounded) for a search that returned at its deadline; the caller is about to queue work: the last search's score matrix is no longer afis_rank_subjects' to rank (unless kept)
 // The launch sequence of a search over one shard: the context's resident one (sub == NULL, sh == *ctx) or a subset's (sh == sub->sh).  afis_search_resident and
 // afis_search_subset_resident check their handles and call it.
-int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score);
+// keep_parts: the per-part scores of all queries stay on the device in ctx->parts [n_q][G][4] and are not copied back (afis_search_weighted folds them there).
+int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score, bool keep_parts = false);
 // The host's rank lists (k > kDeviceTopK) of a score matrix [n_q][G] whose column j is template col[j] (a subset in the caller's order) or index_base + j (col == NULL);
 // the parity tap afis_debug_rank_rows runs it too.  Hidden, as rank_subjects below.
 void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* col, int64_t index_base, int64_t* topk_idx, float* topk_score) __attribute__((visibility("hidden")));
@@ -348,7 +356,8 @@ void release_subset(afis_subset* s);                   // its device buffers and
 int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, const std::vector<int64_t>& global, const std::vector<int32_t>& pos, DevBuf* sel_buf = nullptr) __attribute__((visibility("hidden")));
 // afis_queries_upload (max_templates == 0: the launch groups are cut for the resident shard's size) and afis_queries_upload_reserved (afis_reverse.cpp: for a shard of
 // max_templates templates) behind their argument checks.  Hidden, as rank_subjects below.
-int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out) __attribute__((visibility("hidden")));
+// spec != NULL: build_group's selection per query [n_q][4] (afis_search_weighted's pseudo-queries).
+int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out, const int* spec = nullptr) __attribute__((visibility("hidden")));
 // afis_corr.cpp
 // afis_correspondences_pairs behind its argument checks, and what afis_correspondences runs for its one latent: the pairs (query[i], idx[i]) of the query groups `groups`
 // (n_q queries in all, status per query) against the resident shard.  part may be NULL.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.

@@ -329,6 +329,11 @@ inline unsigned grid_clamp(size_t n) { return n < 65535 ? (unsigned)n : 65535u; 
 // index — expanded into the class's rows of the combined matrix: out[row_of[r]][t] = inv[t] >= 0 ? cls[r][inv[t]] : 0xffffffff for every t < G, every word of those rows
 // written once; inv [G] int32 (position in the sub-shard or -1), NULL = identity (m == G); m == 0: cls and inv are not read.  Rows row_of does not name stay untouched
 hipError_t launch_expand_rows(const float* cls, int n_c, int m, const int32_t* inv, const int32_t* row_of, int n_q, int G, float* out, hipStream_t stream);
+// afis_search_weighted (template_fold.hip): the per-part scores parts [n_pseudo][G][4] of one batch of queries, scored as pseudo-queries, folded into the batch's rows
+// out [nq][G]: qd [nq][4] int32 = (first pseudo-query, pseudo-queries n_pq, of which carry a texture template n_at <= n_pq, status: != 0 = no active template),
+// w [n_pseudo][4] the weights aligned to the part slots (0 = the slot is not summed); out[q][g] = -1 where status != 0 or empty[g], else the fp64 sum of weight x part
+// over slots 0..2 of the query's pseudo-queries in order, then over slot 3 of its first n_at, converted once.  Every word of out is written once
+hipError_t launch_fold_templates(const float* parts, const int32_t* qd, const float* w, const uint8_t* empty, int nq, int G, float* out, hipStream_t stream);
 // afis_rank_positions / afis_rank_subject_positions / afis_count_before (rank_position.hip): where named targets stand in the list launch_rank_hits would make of a
 // row at thr = kPosFloor, the ordered word of -inf.  The host resolves a target to (row, position) and sorts the targets into a CSR by row: rows [n_rows] the rows that
 // have targets, off [n_rows + 1] their ranges in the target arrays [m].

@@ -37,8 +37,10 @@ std::vector<EligClass> plan_classes(const std::vector<uint64_t>& label, int64_t 
     return cls;
 }
 
-// every additive field is the sum over the searches of the call; the two clock fields come from the search with the most pairs
-void add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pairs)
+}  // namespace
+
+// every additive field is the sum over the searches of the call; the two clock fields come from the search with the most pairs (afis_search_weighted's batches too)
+void afis::add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pairs)
 {
     acc.lut_ms += t.lut_ms; acc.adc_ms += t.adc_ms; acc.tex_tail_ms += t.tex_tail_ms; acc.minu_ms += t.minu_ms; acc.fuse_ms += t.fuse_ms; acc.topk_ms += t.topk_ms;
     acc.total_ms += t.total_ms; acc.adc_launches += t.adc_launches; acc.adc_lookups += t.adc_lookups; acc.pairs += t.pairs; acc.adc_bound_ms += t.adc_bound_ms;
@@ -47,6 +49,8 @@ void add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pairs)
     acc.minu_tasks_medium += t.minu_tasks_medium; acc.minu_tasks_large += t.minu_tasks_large;
     if (t.pairs > most_pairs) { most_pairs = t.pairs; acc.bound_clock_ghz = t.bound_clock_ghz; acc.cands_clock_ghz = t.cands_clock_ghz; }
 }
+
+namespace {
 
 // the host side of a temporary sub-shard, as afis_subset_create lays it out for a list that is already ascending; what an earlier class built in the same buffers goes
 void plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, std::vector<int64_t>& global)

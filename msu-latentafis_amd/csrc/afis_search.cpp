@@ -211,7 +211,8 @@ int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup&
 
 // The body of afis_queries_upload (max_templates == 0) and of afis_queries_upload_reserved (afis_reverse.cpp): the launch groups are cut for a shard of G templates — the
 // resident shard's size, or the size the handle is reserved for.
-int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out)
+// spec != NULL (afis_search_weighted): build_group's per-query selection [n_q][4]; the cuts count the texture rows of the template a pseudo-query really carries.
+int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out, const int* spec)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
@@ -234,8 +235,9 @@ int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, in
     std::vector<long long> rows((size_t)n_q + 1, 0);
     for (int i = 0; i < n_q; ++i) {
         const afis_template_view& t = queries[i];
-        const bool has = t.n_tex > 0 && t.tex && !(t.n_minu <= kSelected[0] && t.n_tex <= 0);
-        rows[(size_t)i + 1] = rows[(size_t)i] + (has ? std::min(std::max(t.tex[0].n, 0), kTexMax) : 0);
+        const int tex_ind = spec ? spec[(size_t)i * 4 + 3] : 0;
+        const bool has = tex_ind >= 0 && t.n_tex > tex_ind && t.tex && !(!spec && t.n_minu <= kSelected[0] && t.n_tex <= 0);
+        rows[(size_t)i + 1] = rows[(size_t)i] + (has ? std::min(std::max(t.tex[tex_ind].n, 0), kTexMax) : 0);
     }
     std::vector<int> cuts((size_t)std::max(n_q, 1));                        // group ends (exclusive)
     int n_cuts = 0;
@@ -260,7 +262,7 @@ int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, in
     int g0 = 0;
     for (int end : cuts) {
         q->groups.emplace_back();
-        int rc = build_group(ctx, queries + g0, end - g0, q->groups.back(), q->status);
+        int rc = build_group(ctx, queries + g0, end - g0, q->groups.back(), q->status, spec ? spec + (size_t)g0 * 4 : nullptr);
         if (rc != AFIS_OK) { afis_queries_free(ctx, q); return rc; }
         g0 = end;
     }
@@ -489,7 +491,8 @@ void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* c
 // The launch sequence of a search over the shard `sh`: the context's resident one (sub == NULL) or a subset's (sh == sub->sh, whose templates stand in ascending global
 // index order).  One body for both: group loop, overlapped schedule, buffer sizing before queuing, timing, deadlines.  What a subset adds lies at the two ends — the
 // rank-list kernel's positions are mapped to global indices, and the score / part columns go to the caller's order (on the device, so that they are copied once).
-int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score)
+// keep_parts (afis_search_weighted): the per-part scores of ALL queries stay in ctx->parts [n_q][G][4], as when the caller asks for them, and nothing of them is copied back.
+int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score, bool keep_parts)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
@@ -506,7 +509,8 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
     if (G > 0 && nq_all > 0) HIPCHK(ctx, ctx->scores.ensure((size_t)nq_all * G * 4));
     HIPCHK(ctx, ctx->diag.ensure(std::max<size_t>(n_groups, 1) * kDiagWords * 8));
     HIPCHK(ctx, hipMemsetAsync(ctx->diag.p, 0, std::max<size_t>(n_groups, 1) * kDiagWords * 8, s));    // before the first group's ev[0]: ordered before everything the side streams do
-    { const int rcp = prepare_search_buffers(ctx, sh, q, parts != nullptr); if (rcp != AFIS_OK) return rcp; }
+    const bool all_parts = parts != nullptr || keep_parts;                  // every group's block of ctx->parts stays until the search is done
+    { const int rcp = prepare_search_buffers(ctx, sh, q, all_parts); if (rcp != AFIS_OK) return rcp; }
     const bool dev_topk = k > 0 && k <= kDeviceTopK && G > 0 && nq_all > 0;
     const bool host_topk = k > 0 && !dev_topk;
     // a subset listed out of order: scores (asked for, or needed by the host's rank lists) and parts leave through out_perm in the caller's column order
@@ -532,7 +536,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
             if (ctx->adc_variant != 9) HIPCHK(ctx, ctx->rm_val.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
             HIPCHK(ctx, ctx->rm_arg.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
             if (ctx->adc_variant == 9) { HIPCHK(ctx, ctx->rm_cv.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16))); HIPCHK(ctx, ctx->rm_n.ensure(std::max<size_t>(n_pairs * 4, 16))); }
-            HIPCHK(ctx, ctx->parts.ensure(parts ? (size_t)nq_all * G * 16 : n_pairs * 16));
+            HIPCHK(ctx, ctx->parts.ensure(all_parts ? (size_t)nq_all * G * 16 : n_pairs * 16));
             // minutiae scratch per workgroup: simi[n] | keys[n] | rowsum[2048] | colsum[2048]  (only pairs the fast kernel cannot take use it)
             size_t per_wg = minu_scratch_floats(grp.max_nL, sh.max_nR, ctx->s3_tie_order);
             int n_wg = 1024;
@@ -542,7 +546,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
             HIPCHK(ctx, ctx->cand_n.ensure(n_pairs * 3 * 4));
             HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(n_pairs * 3, (size_t)G) * 4));
             float* grp_scores = ctx->scores.as<float>() + (size_t)q0 * G;
-            float* const grp_parts = ctx->parts.as<float>() + (parts ? (size_t)q0 * G * 4 : 0);
+            float* const grp_parts = ctx->parts.as<float>() + (all_parts ? (size_t)q0 * G * 4 : 0);
             // One ADC workgroup fills a CU (128 KB LUT tile), so nothing overlaps its tile load: chunks of ~640 templates keep that
             // under 3 % of a workgroup's life.  The blocks of XCD x are the chunks c % 8 == x, so the chunk COUNT is a multiple of 8
             // (measured at a 12.5k shard: 98 chunks of 128 -> 24 of 521: -9 % ADC time; at 100k: 196 of 512 -> 160 of 625: -2.5 %).

@@ -218,6 +218,33 @@ int afis_debug_expand_rows(afis_ctx* ctx, const float* cls, int n_c, int64_t m, 
     return AFIS_OK;
 }
 
+int afis_debug_fold_templates(afis_ctx* ctx, const float* parts, int64_t n_pseudo, int64_t G, const int32_t* qd, int n_q, const float* w, const uint8_t* empty, float* out)
+{
+    if (!ctx || n_q <= 0 || G <= 0 || G > 0x7fffffff || n_pseudo < 0 || n_pseudo > 0x7fffffff / 4 || !qd || !empty || !out || (n_pseudo > 0 && (!parts || !w)))
+        return fail(ctx, AFIS_EINVAL, "afis_debug_fold_templates: bad argument");
+    for (int q = 0; q < n_q; ++q) {
+        const int32_t* d = qd + (size_t)q * 4;
+        if (d[0] < 0 || d[1] < 0 || (int64_t)d[0] + d[1] > n_pseudo || d[2] < 0 || d[2] > d[1])
+            return fail(ctx, AFIS_EINVAL, "afis_debug_fold_templates: a query's pseudo-queries must lie inside parts, its texture count inside them");
+    }
+    { const int rcq = quiesce(ctx, "afis_debug_fold_templates"); if (rcq != AFIS_OK) return rcq; }
+    DevBuf d_parts, d_tab, d_empty, d_out;
+    struct Drop { DevBuf *a, *b, *c, *d; ~Drop() { a->release(); b->release(); c->release(); d->release(); } } drop{&d_parts, &d_tab, &d_empty, &d_out};
+    const size_t out_bytes = (size_t)n_q * (size_t)G * 4, parts_bytes = (size_t)n_pseudo * (size_t)G * 16, w_bytes = (size_t)n_pseudo * 16;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, d_out.ensure(out_bytes)); HIPCHK(ctx, d_empty.ensure((size_t)G));
+    HIPCHK(ctx, d_parts.ensure(std::max<size_t>(parts_bytes, 16))); HIPCHK(ctx, d_tab.ensure((size_t)n_q * 16 + std::max<size_t>(w_bytes, 16)));
+    HIPCHK(ctx, hipMemcpy(d_out.p, out, out_bytes, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(d_empty.p, empty, (size_t)G, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(d_tab.p, qd, (size_t)n_q * 16, hipMemcpyHostToDevice));
+    float* const d_w = reinterpret_cast<float*>(d_tab.as<uint8_t>() + (size_t)n_q * 16);
+    if (parts_bytes) { HIPCHK(ctx, hipMemcpy(d_parts.p, parts, parts_bytes, hipMemcpyHostToDevice)); HIPCHK(ctx, hipMemcpy(d_w, w, w_bytes, hipMemcpyHostToDevice)); }
+    HIPCHK(ctx, launch_fold_templates(d_parts.as<float>(), d_tab.as<int32_t>(), d_w, d_empty.as<uint8_t>(), n_q, (int)G, d_out.as<float>(), s));
+    { const int rcw = wait_streams(ctx, {s}, "afis_debug_fold_templates"); if (rcw != AFIS_OK) return rcw; }
+    HIPCHK(ctx, hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return AFIS_OK;
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

@@ -70,12 +70,12 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
-           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible",
+           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted",
            "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
-               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows"]
+               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -139,6 +139,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_rank_latent_hits_filtered.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int64, C.c_float, C.c_int, C.c_int64, i64p, i64p, fp]
     if hasattr(lib, "afis_search_eligible"):                            # eligible search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_eligible.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TemplateView), C.c_int, fp, i32p]
+    if hasattr(lib, "afis_search_weighted"):                            # weighted search; absent from older builds compared by tools/lib_ab.py
+        lib.afis_search_weighted.argtypes = [vp, C.POINTER(TemplateView), C.c_int, fp, C.c_int, fp, C.c_int, fp, i32p]
     if hasattr(lib, "afis_rank_positions"):                             # rank positions; absent from older builds compared by tools/lib_ab.py
         u64p = C.POINTER(C.c_uint64)
         lib.afis_rank_positions.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
@@ -184,6 +186,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_rank_rows.argtypes = [vp, vp, fp, C.c_int, C.c_int, i64p, fp]
     if hasattr(lib, "afis_debug_expand_rows"):
         lib.afis_debug_expand_rows.argtypes = [vp, fp, C.c_int, C.c_int64, i32p, i32p, C.c_int, C.c_int64, fp]
+    if hasattr(lib, "afis_debug_fold_templates"):
+        lib.afis_debug_fold_templates.argtypes = [vp, fp, C.c_int64, C.c_int64, i32p, C.c_int, fp, C.POINTER(C.c_uint8), fp]
     return lib
 
 
@@ -637,6 +641,44 @@ class Matcher:
         self._chk(self._tap("afis_debug_expand_rows")(self.ctx, _ptr(c, C.c_float) if c.size else None, n_c, m, _ptr(ro, C.c_int32), _ptr(se, C.c_int32) if se is not None and len(se) else None,
                                                       o.shape[0], o.shape[1], _ptr(o, C.c_float)))
         return o.view(np.asarray(out).dtype)
+
+    # ---- weighted search: any set of a latent's templates, fused on the device ---------------------------------------
+    def search_weighted(self, latents: Sequence[FPTemplate], w_minu, w_tex, want_scores: bool = True, n_wm=None, n_wt=None):
+        """search() over ANY set of each latent's templates: w_minu [n_q][n_wm] / w_tex [n_q][n_wt] float32 weights (a 1-D row is every query's row; None with width
+        0), a template being scored where its weight is not zero and it exists.  scores [n_q][G]: -1 for an empty entry and for the whole row of a latent without an
+        active template (status AFIS_QUERY_LATENT_EMPTY), otherwise the fp64 sum of weight x score over the active minutiae, then texture templates, in ascending
+        order, as one float32.  The matrix left on the device is a full search's: every rank_* call reads it.  n_wm / n_wt override the widths handed to the C call
+        (argument tests).  timing()["pairs"] = pseudo-queries x G; get_option("weighted_pseudo_queries"), get_option("weighted_fold_us")."""
+        v = _Views(latents)
+
+        def rows(w):
+            if w is None:
+                return None, 0
+            a = np.asarray(w, np.float32)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (v.n, a.shape[0]))
+            a = np.ascontiguousarray(a.reshape(v.n, -1) if v.n else a.reshape(0, a.shape[-1]))
+            return a, a.shape[1]
+        wm, nm = rows(w_minu); wt, nt = rows(w_tex)
+        G = self.resident_size
+        scores = np.empty((v.n, G), np.float32) if want_scores else None
+        status = np.zeros(v.n, np.int32)
+        self._chk(self.lib.afis_search_weighted(self.ctx, v.arr, v.n, _ptr(wm, C.c_float) if wm is not None and wm.size else None, nm if n_wm is None else n_wm,
+                                                _ptr(wt, C.c_float) if wt is not None and wt.size else None, nt if n_wt is None else n_wt,
+                                                _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32)))
+        self.last_n_q = v.n; self.last_n_templates = G
+        return {"scores": scores, "status": status}
+
+    def debug_fold_templates(self, parts: np.ndarray, qd, w: np.ndarray, empty) -> np.ndarray:
+        """k_fold_templates on planted data (parity tap): parts [n_pseudo][G][4] float32 (any bit patterns), qd [n_q][4] int32 = (first pseudo-query, n_pq, n_at,
+        status), w [n_pseudo][4] weights aligned to the part slots, empty [G] uint8.  -> out [n_q][G] float32."""
+        p = np.ascontiguousarray(parts).view(np.float32); d = np.ascontiguousarray(np.asarray(qd, np.int32).reshape(-1, 4))
+        ww = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1, 4)); e = np.ascontiguousarray(np.asarray(empty, np.uint8).reshape(-1))
+        n_pseudo, G = p.shape[0], len(e)
+        out = np.full((len(d), G), np.float32(7.0), np.float32)             # (every word must be overwritten)
+        self._chk(self._tap("afis_debug_fold_templates")(self.ctx, _ptr(p, C.c_float) if p.size else None, n_pseudo, G, _ptr(d, C.c_int32), len(d),
+                                                         _ptr(ww, C.c_float) if ww.size else None, _ptr(e, C.c_uint8), _ptr(out, C.c_float)))
+        return out
 
     # ---- case lists: the queries of one case fused into one list ----------------------------------------------------
     def _case_lists(self, fn, case_of, cap: int, subjects: bool):

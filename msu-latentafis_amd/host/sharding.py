@@ -8,6 +8,9 @@ gallery indices; the merged list is the top-k of the union in the lists' own ord
 The order is the one every path of the library lists by (csrc/rank_order.h, minu.hip::k_topk): rank_key is the ordered bits of score + 0.0f, so that the two
 zeros are one value and a NaN stands where its bits put it (above +inf with the sign clear, below -inf with it set).  On NaN-free scores that is plainly score
 descending.  The subject lists merge on subject_key, the ordered bits of the raw word (-0.0 below +0.0), the key include/afis_matcher.h documents for subjects.
+
+A weighted search (Matcher.search_weighted) needs no merge of its own: the columns of shards are disjoint and the weights common to every rank, so the per-rank
+lists read from its matrix are merge_hits / merge_subject_hits input as they are.
 """
 from __future__ import annotations
 
