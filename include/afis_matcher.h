@@ -238,7 +238,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     context.  Several handles may be live at once; afis_destroy releases those that are left.  A handle belongs to the gallery as it was: after an
  *                     appending commit or a removal that changed the shard afis_rank_subjects refuses it with AFIS_ESTATE (afis_subjects_free still works).
  * afis_rank_subjects   ranks the score matrix of the context's LAST search — any of afis_search, afis_search_dat, afis_search_resident, afis_search_subset,
- *                     afis_search_subset_resident, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
+ *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
  *                     search's (AFIS_EINVAL otherwise, as for k <= 0 or a null output).  Per query the k best subjects:
  *                       subject_score  the greatest fused score among the subject's templates that the search covered: all of them for a full search, the listed ones for a
  *                                      subset search (a subject without a listed template does not appear).  An empty or removed entry contributes its -1: a subject all of
@@ -617,6 +617,59 @@ int afis_search_weighted(afis_ctx* ctx, const afis_template_view* queries, int n
                          const float* w_tex  /*[n_q][n_wt]*/, int n_wt,
                          float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/);
 
+/* Print search (no reference counterpart): every search above starts from a latent.  "Is this person already enrolled?" — the duplicate check of every enrolment — and
+ * the linking of the entries of an unsolved-latent file that was enrolled as a gallery start from a RESIDENT PRINT.  afis_search_prints takes resident prints as the
+ * queries, builds their query views on the device from the resident shard — only an index list's offset tables cross PCIe, no template does — and leaves a matrix
+ * the whole ranking family reads, so that hit lists, subject lists, case lists, filtered lists, rank positions and column lists work for print-to-print search unchanged,
+ * with eligibility filters and exclusion lists.
+ *   idx [n_q]   GLOBAL indices of the resident shard (index_base included); entries may repeat and come in any order
+ *   s           NULL: the columns are the whole resident shard; or a live subset: the columns are the subset's, in the caller's order, exactly as afis_search_subset
+ *               lays them out (the query prints need not be in the subset) — a finger-position-restricted duplicate check holds one subset per finger
+ *   w_minu [n_q], w_tex [n_q]   one weight per query for the print's minutiae template and for its texture template
+ * The query view P of a print   n_minu = 1 when the print has a minutiae template, else 0; minu[0] is that template as the shard holds it — x, y, ori and des, bit for
+ *          bit.  n_tex = 1 when it has a texture template, else 0; tex[0] holds the resident points (already clamped to 1000 at enrolment), x, y and ori as held, and
+ *          des[r][6 m + k] = codewords[m][code[r][m]][k]: the PQ codes decoded, the codewords' bits copied, no arithmetic.
+ * Value of cell (q, column)   bit for bit the value afis_search_weighted gives for the query P, n_wm = 1, n_wt = 1 and the weight rows {w_minu[q]} and {w_tex[q]}:
+ *          its activity rule, (float) of the fp64 sum with minutiae before texture, -1 for an empty or removed column, AFIS_QUERY_LATENT_EMPTY and a row of -1 when
+ *          nothing is active — an empty or removed print, or both weights zero —, finite weights >= 0 only, and its behaviour under "s3_tie_order", "ref_tie_order"
+ *          and "adc_variant" 8 / 9.  A print against itself is an ordinary cell: the caller takes it out with an exclusion list (afis_rank_hits_filtered's excl).
+ * The matrix afterwards   after AFIS_OK the context's last-search matrix is this matrix — a full search's record with s == NULL, a subset search's with a subset — under
+ *          afis_search's invalidation rules; the call is one of the searches that count, for every ranking call.
+ * How     one PSEUDO-QUERY per print with something active, with the selection (0 or -1, -1, -1, 0 or -1); batches are cut as afis_search_weighted cuts them, under
+ *          "weighted_batch_pseudo", and a batch's launch groups by the prints' texture rows, from the host's copy of the shard's offsets.  Per launch group seven
+ *          query-side tables and three source offset tables are uploaded (one copy, under 128 bytes per query) and csrc/print_queries.hip fills the group's arrays from
+ *          the shard: segment copies of the minutiae arrays and the texture points, the print's descriptor fragment tiles as they stand, the texture descriptors
+ *          decoded from the PQ codes through the fp32 codebook (read through L2; every output word written once, 16-byte stores).  Then the launch sequence of a
+ *          search with the per-part scores kept, and the weighted search's fold (csrc/template_fold.hip), with the subset's empty flags when s is given.  The
+ *          combined matrix, the largest batch's per-part scores, the tables and a subset's column permutation are ensured before anything is queued.
+ * Arguments   AFIS_EINVAL: a null ctx, n_q < 0, a null idx or weight array with n_q > 0, an index outside the resident shard, a weight that is NaN, infinite or
+ *          negative, a subset that is not live in this context.  AFIS_ESTATE: a call before the first commit, an index that is staged but not committed, a subset
+ *          made before the last gallery edit.  n_q == 0 returns AFIS_OK as afis_search with no queries does.  After ANY other return the last-search matrix is
+ *          invalid and the call holds nothing it allocated.  Host waits are bounded as a search's are ("search_timeout_s").
+ * Timing   as afis_search_weighted: the additive fields summed over the batches, pairs = pseudo-queries x columns; "weighted_pseudo_queries" and "weighted_fold_us"
+ *          describe this call too.  "print_gather_us" and "print_h2d_bytes" (read-only): the device time of the call's gather launches, and the bytes it handed to
+ *          host-to-device copies (the groups' tables and the fold's); both 0 after a failed or empty call.
+ * Not in this interface: pair and verification forms for prints (afis_score_pairs and afis_correspondences_pairs take latents); rolled templates beyond index 0 (the
+ *          shard holds one minutiae and one texture template per print); the match CLI.  Shards: a print is a query only on the rank that holds it; against the
+ *          other shards its template must be present there, and the existing afis_search_weighted route over host views serves that.  The per-rank lists read from
+ *          the matrix are host/sharding.py::merge_hits / merge_subject_hits input as they are.  No result of any other search changes because this function exists.
+ * Cost    one MI355X, 100 resident prints (78 minutiae and 811 texture points on average) x 100 000 prints, weights 1 and 0.3f, interleaved runs, medians of three
+ *          after a discarded first, spread = max - min (tools/print_search_timing.py, profiles/print_search_timing.json): (a) the call 2 156.2 ms on the host clock
+ *          (spread 25.4), device clock 2 152.3 ms (spread 2.4), against 2 163.0 ms (spread 5.8) and 2 154.3 ms (spread 6.3) for afis_search_weighted over host views of
+ *          the same prints on the same context — the only route before, the same bits: the device times lie inside each other's spread, the host clock gains 6.9 ms,
+ *          about the upload of the views' 34.8 MB that is no longer made (the call hands 9 040 bytes to host-to-device copies).  (b) The gather: 130 us (spread 25)
+ *          for 38.1 MB written, three launch groups of seven launches, where a device-to-device copy of 38.1 MB takes 13.1 us (spread 0.7): 9.9 x the copy's time.
+ *          It is the launches, not the bytes: the gather of ONE print — seven launches over 0.4 MB — takes 22 us, so 66 of the 130 us are three groups' launch
+ *          sequences, and what remains is seven short kernels per group (at most 10 MB each) that end before they reach a byte rate: every thread first walks a
+ *          binary search of up to nine dependent loads, and each kernel waits for the previous one's tail.  Store width (16 bytes), occupancy (8 waves per SIMD) and
+ *          the codebook reads (cache-resident) are not what limits it; one fused launch per group would be.  Not built: the gather is 0.006 % of the call.
+ *          (c) The full search is untouched: tools/lib_ab.py against the parent commit's library, twice, scores bit-identical both times; this tree's median total_ms
+ *          1 860.0 against the parent's 1 862.1 (its steps 1 860.6 .. 1 864.4: 0.5 ms BELOW the parent's fastest step) and 1 877.1 against 1 878.2 (inside its
+ *          1 876.3 .. 1 880.0) — profiles/print_full_search_ab.txt. */
+int afis_search_prints(afis_ctx* ctx, afis_subset* s /* or NULL: the whole resident shard */, const int64_t* idx /*[n_q], GLOBAL*/, int n_q,
+                       const float* w_minu /*[n_q]*/, const float* w_tex /*[n_q]*/,
+                       float* scores /*[n_q][columns] or NULL*/, int32_t* status /*[n_q] or NULL*/);
+
 /* The rank list of One2List_matching, matcher.cpp:306-309, from a score column (host memory, no device work): idx[0 .. k) / sc[0 .. k) = the k best of scores[0 .. n), descending
  * in afis_search's key rank_key(score) (csrc/rank_order.h: the bits of score + 0.0f in their total order; on a NaN-free column that is score descending).
  * ref_order 0: equal keys by ascending index (what afis_search's own top-k delivers); 1: the reference's statement itself — std::sort of the indices 0 .. n-1 on a non-strict
@@ -771,7 +824,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "weighted_batch_pseudo" (settable, >= 0; default 0): the pseudo-queries of one batch of afis_search_weighted at most; 0 = as many as an eighth of the launch-group
  * budget holds the per-part scores of.  Results do not depend on it.  "weighted_pseudo_queries" (read-only): the pseudo-queries the last afis_search_weighted scored;
  * "weighted_fold_us" (read-only): the device time of that call's fold launches (k_fold_templates), from HIP events around each, summed over the batches; both 0 after a
- * call that failed or had no queries. */
+ * call that failed or had no queries (afis_search_prints sets the last two as well, and obeys the first).
+ * "print_gather_us" (read-only): the device time of the last afis_search_prints' gather launches (print_queries.hip), from HIP events around each launch group's,
+ * summed; "print_h2d_bytes" (read-only): the bytes that call handed to host-to-device copies — the launch groups' tables and the fold's —, counted where the copies
+ * are issued; both 0 after a call that failed or had no queries. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -86,6 +86,16 @@ int afis_debug_expand_rows(afis_ctx* ctx, const float* cls /*[n_c][m]*/, int n_c
  * AFIS_EINVAL for a query whose pseudo-queries leave [0, n_pseudo); no gallery is needed. */
 int afis_debug_fold_templates(afis_ctx* ctx, const float* parts /*[n_pseudo][G][4]*/, int64_t n_pseudo, int64_t G, const int32_t* qd /*[n_q][4]*/, int n_q,
                               const float* w /*[n_pseudo][4]*/, const uint8_t* empty /*[G]*/, float* out /*[n_q][G]*/);
+/* The query groups of afis_search_prints (print_queries.hip) without a search: ONE launch group is built from the resident prints idx [n] (global indices, any order,
+ * repeats allowed) — print i with its minutiae template where use_minu[i] != 0 and its texture template where use_tex[i] != 0, where it has one — exactly as that call
+ * builds a batch's groups: the tables on the host, the arrays by the gather on the device, over buffers planted with 0xA5 bytes.  counts [4] = (minutiae, fragment
+ * tiles, texture rows of the group, lt_pad).  With lm_off == NULL only counts is filled (the caller sizes its arrays and calls again); otherwise the tables —
+ * lm_off, lm_tile_off [3 n + 1], lt_off, tile_off, tile16_off [n + 1], tex_slot, status [n] — and the arrays — lm_xy [counts[0]][2], lm_ori [counts[0]], lm_des
+ * [counts[0]][96], lm_frag [counts[1]][6][64][4], lt_xy [counts[2]][2], lt_ori [counts[2]], lt_des [counts[2]][96] — are copied back as the device holds them.
+ * AFIS_EINVAL for an index outside the resident shard, AFIS_ESTATE before the first commit. */
+int afis_debug_print_queries(afis_ctx* ctx, const int64_t* idx /*[n]*/, int n, const uint8_t* use_minu /*[n]*/, const uint8_t* use_tex /*[n]*/, int32_t* counts /*[4]*/,
+                             int32_t* lm_off, int32_t* lm_tile_off, int32_t* lt_off, int32_t* tile_off, int32_t* tile16_off, int32_t* tex_slot, int32_t* status,
+                             int16_t* lm_xy, float* lm_ori, float* lm_des, float* lm_frag, int16_t* lt_xy, float* lt_ori, float* lt_des);
 
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */

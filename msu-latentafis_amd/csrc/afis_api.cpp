@@ -192,6 +192,8 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "weighted_batch_pseudo") *value = ctx->weighted_batch_pseudo;
     else if (n == "weighted_pseudo_queries") *value = ctx->weighted_pseudo_queries;    // read-only: pseudo-queries the last afis_search_weighted scored
     else if (n == "weighted_fold_us") *value = ctx->weighted_fold_us;                  // read-only: device time of that call's k_fold_templates launches, summed over the batches
+    else if (n == "print_gather_us") *value = ctx->print_gather_us;                    // read-only: device time of the last afis_search_prints' gather launches, summed over its launch groups
+    else if (n == "print_h2d_bytes") *value = ctx->print_h2d_bytes;                    // read-only: bytes that call handed to host-to-device copies
     else if (n == "rank_latents_us") *value = ctx->rank_latents_us;                    // read-only: device time of the last afis_rank_latent_hits' launches
     else if (n == "corr_pairs_per_launch") *value = ctx->corr_pairs_per_launch;
     else if (n == "correspondences_us") *value = ctx->correspondences_us;              // read-only: device time of the last afis_correspondences_pairs' / afis_correspondences' launches

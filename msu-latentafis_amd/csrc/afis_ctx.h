@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_reverse.cpp (reverse search: reserved query handles, column hit lists) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -24,6 +24,7 @@
 #include "afis_device.h"
 #include "template_io.h"
 #include <memory>
+#include <functional>
 
 namespace afis {
 
@@ -188,6 +189,8 @@ struct afis_ctx : Shard {
     int weighted_batch_pseudo = 0;       // option weighted_batch_pseudo: pseudo-queries per batch of that call at most; 0 = as many as an eighth of the group budget holds the per-part scores of
     int64_t weighted_pseudo_queries = 0; // option weighted_pseudo_queries (read-only): pseudo-queries the last afis_search_weighted scored
     int64_t weighted_fold_us = 0;        // option weighted_fold_us (read-only): device time of that call's k_fold_templates launches, HIP events around each, summed over the batches
+    int64_t print_gather_us = 0;         // option print_gather_us (read-only): device time of the last afis_search_prints' gather launches (print_queries.hip), HIP events around each group's, summed
+    int64_t print_h2d_bytes = 0;         // option print_h2d_bytes (read-only): bytes that call handed to host-to-device copies (the groups' tables and the fold's), counted where the copies are issued
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
@@ -358,6 +361,36 @@ int build_subset(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& se
 // max_templates templates) behind their argument checks.  Hidden, as rank_subjects below.
 // spec != NULL: build_group's selection per query [n_q][4] (afis_search_weighted's pseudo-queries).
 int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out, const int* spec = nullptr) __attribute__((visibility("hidden")));
+// ... and its sibling for query groups that are not made of views: the same cuts from the queries' texture rows (rows [n_q + 1], prefix sums), every group made by
+// `build` (first query, queries, the group to fill, the handle's status list to append to).  afis_search_prints fills its groups on the device through it (afis_prints.cpp).
+typedef std::function<int(int, int, QueryGroup&, std::vector<int32_t>&)> QueryGroupBuilder;
+int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build) __attribute__((visibility("hidden")));
+// The batches of afis_search_weighted and afis_search_prints: queries [q0, q1) with pseudo-queries [p0, p1) of the call's numbering, cut at query boundaries — at most
+// `cap` pseudo-queries; a query with more than that is a batch of its own, a query without pseudo-queries joins the batch that is open.
+struct PseudoBatch { int q0, q1; int64_t p0, p1; };
+inline std::vector<PseudoBatch> plan_pseudo_batches(const std::vector<int>& n_pq, int64_t cap)
+{
+    std::vector<PseudoBatch> b;
+    int64_t first = 0;
+    for (int i = 0; i < (int)n_pq.size(); ++i) {
+        if (b.empty() || (b.back().p1 > b.back().p0 && b.back().p1 - b.back().p0 + n_pq[(size_t)i] > cap)) b.push_back(PseudoBatch{i, i, first, first});
+        b.back().q1 = i + 1; b.back().p1 += n_pq[(size_t)i];
+        first += n_pq[(size_t)i];
+    }
+    return b;
+}
+// afis_prints.cpp
+// One launch group of afis_search_prints in two steps (the parity tap afis_debug_print_queries runs them too).  prepare_print_group: queries p < n are the prints
+// local[p] (shard-local indices of the resident shard) with their minutiae template where use_minu[p] and their texture template where use_tex[p], where the print has
+// one — build_group's group for the spec (0 or -1, -1, -1, 0 or -1): the host's copy of the group's tables (the seven query-side tables and the three source offset
+// tables, each padded to 16 bytes) in plan.tab, every DevBuf of the group at its size, grp.dev pointing into them; nothing is queued.  res_tile [G + 1]: the first
+// fragment tile of every resident template (resident_tile_offsets).  queue_print_group: the tables in one host-to-device copy and the gather (print_queries.hip) on the
+// context's stream; plan must live until the stream has passed the copy; *h2d_bytes grows by the bytes handed to the copy; the two events, where given, are recorded around the gather's launches.  Hidden, as rank_subjects below.
+struct PrintGroupPlan { std::vector<int32_t> tab; size_t first_at = 0; int n_lm = 0, n_lm_tiles = 0, n_lt = 0; };   // first_at: int32 position of first_minu | first_tile | first_tex in tab
+std::vector<int32_t> resident_tile_offsets(const afis_ctx* ctx) __attribute__((visibility("hidden")));
+int prepare_print_group(afis_ctx* ctx, const std::vector<int32_t>& res_tile, const int32_t* local, const uint8_t* use_minu, const uint8_t* use_tex, int n, QueryGroup& grp,
+                        PrintGroupPlan& plan, std::vector<int32_t>& status_out) __attribute__((visibility("hidden")));
+int queue_print_group(afis_ctx* ctx, const QueryGroup& grp, const PrintGroupPlan& plan, int64_t* h2d_bytes, hipEvent_t before_gather = nullptr, hipEvent_t after_gather = nullptr) __attribute__((visibility("hidden")));
 // afis_corr.cpp
 // afis_correspondences_pairs behind its argument checks, and what afis_correspondences runs for its one latent: the pairs (query[i], idx[i]) of the query groups `groups`
 // (n_q queries in all, status per query) against the resident shard.  part may be NULL.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.

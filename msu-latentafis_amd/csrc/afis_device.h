@@ -334,6 +334,13 @@ hipError_t launch_expand_rows(const float* cls, int n_c, int m, const int32_t* i
 // w [n_pseudo][4] the weights aligned to the part slots (0 = the slot is not summed); out[q][g] = -1 where status != 0 or empty[g], else the fp64 sum of weight x part
 // over slots 0..2 of the query's pseudo-queries in order, then over slot 3 of its first n_at, converted once.  Every word of out is written once
 hipError_t launch_fold_templates(const float* parts, const int32_t* qd, const float* w, const uint8_t* empty, int nq, int G, float* out, hipStream_t stream);
+// afis_search_prints (print_queries.hip): the arrays of a query group — q's lm_xy, lm_ori, lm_des, lm_frag, lt_xy, lt_ori, lt_des, allocated, the 4-byte ones in whole
+// 16-byte words — filled from the resident shard g on the device.  q's tables are on the device already: pseudo-query p is a print whose minutiae template fills slot 0
+// (entry 3 p of lm_off / lm_tile_off; entries 3 p + 1, 3 p + 2 are empty ranges) and whose texture template fills lt_off's entry p.  first_minu / first_tile / first_tex
+// [q.nq] (device): where p's print starts in g.minu_*, in g.minu_frag (tiles) and in g.tex_*; n_lm / n_lm_tiles / n_lt: the last entries of the three CSRs.  Segment
+// copies, the fragment tiles as they stand, and lt_des decoded from g.tex_codes through the fp32 codebook [16][256][6]; every output word written once
+hipError_t launch_print_queries(const GalleryDev& g, const float* codewords, const int32_t* first_minu, const int32_t* first_tile, const int32_t* first_tex,
+                                const QueryDev& q, int n_lm, int n_lm_tiles, int n_lt, hipStream_t stream);
 // afis_rank_positions / afis_rank_subject_positions / afis_count_before (rank_position.hip): where named targets stand in the list launch_rank_hits would make of a
 // row at thr = kPosFloor, the ordered word of -inf.  The host resolves a target to (row, position) and sorts the targets into a CSR by row: rows [n_rows] the rows that
 // have targets, off [n_rows + 1] their ranges in the target arrays [m].

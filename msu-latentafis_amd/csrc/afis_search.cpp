@@ -211,8 +211,9 @@ int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup&
 
 // The body of afis_queries_upload (max_templates == 0) and of afis_queries_upload_reserved (afis_reverse.cpp): the launch groups are cut for a shard of G templates — the
 // resident shard's size, or the size the handle is reserved for.
-// spec != NULL (afis_search_weighted): build_group's per-query selection [n_q][4]; the cuts count the texture rows of the template a pseudo-query really carries.
-int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out, const int* spec)
+// rows [n_q + 1]: the prefix sums of the queries' texture rows (what the cuts are placed by); build(g0, n, group, status) makes the group of queries [g0, g0 + n) —
+// build_group's upload for latents handed over as views (upload_queries), the device gather of afis_search_prints.
+int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
@@ -232,13 +233,6 @@ int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, in
     const int64_t budget = group_budget_bytes(ctx);
     // Launch groups are contiguous runs of at most `per` queries; with the matrix-core bound pass (adc_variant 9) the cuts are placed where its row groups of 768 latent
     // texture rows are fewest (launch_group_cuts, afis_device.h; tests/test_host.py checks the rule on the CPU).  Results do not depend on the cuts.
-    std::vector<long long> rows((size_t)n_q + 1, 0);
-    for (int i = 0; i < n_q; ++i) {
-        const afis_template_view& t = queries[i];
-        const int tex_ind = spec ? spec[(size_t)i * 4 + 3] : 0;
-        const bool has = tex_ind >= 0 && t.n_tex > tex_ind && t.tex && !(!spec && t.n_minu <= kSelected[0] && t.n_tex <= 0);
-        rows[(size_t)i + 1] = rows[(size_t)i] + (has ? std::min(std::max(t.tex[tex_ind].n, 0), kTexMax) : 0);
-    }
     std::vector<int> cuts((size_t)std::max(n_q, 1));                        // group ends (exclusive)
     int n_cuts = 0;
     // `per` so far is what the budget allows if every latent had 1000 texture rows.  The latents are known here: when that worst case is what limits the group, larger groups are tried
@@ -262,12 +256,28 @@ int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, in
     int g0 = 0;
     for (int end : cuts) {
         q->groups.emplace_back();
-        int rc = build_group(ctx, queries + g0, end - g0, q->groups.back(), q->status, spec ? spec + (size_t)g0 * 4 : nullptr);
+        int rc = build(g0, end - g0, q->groups.back(), q->status);
         if (rc != AFIS_OK) { afis_queries_free(ctx, q); return rc; }
         g0 = end;
     }
     *out = q;
     return AFIS_OK;
+}
+
+// Latents handed over as views.  spec != NULL (afis_search_weighted): build_group's per-query selection [n_q][4]; the cuts count the texture rows of the template a
+// pseudo-query really carries.
+int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, int64_t max_templates, afis_queries** out, const int* spec)
+{
+    std::vector<long long> rows((size_t)n_q + 1, 0);
+    for (int i = 0; i < n_q; ++i) {
+        const afis_template_view& t = queries[i];
+        const int tex_ind = spec ? spec[(size_t)i * 4 + 3] : 0;
+        const bool has = tex_ind >= 0 && t.n_tex > tex_ind && t.tex && !(!spec && t.n_minu <= kSelected[0] && t.n_tex <= 0);
+        rows[(size_t)i + 1] = rows[(size_t)i] + (has ? std::min(std::max(t.tex[tex_ind].n, 0), kTexMax) : 0);
+    }
+    return upload_query_groups(ctx, rows, n_q, max_templates, out, [&](int g0, int n, QueryGroup& grp, std::vector<int32_t>& status) {
+        return build_group(ctx, queries + g0, n, grp, status, spec ? spec + (size_t)g0 * 4 : nullptr);
+    });
 }
 
 }  // namespace afis

@@ -245,6 +245,43 @@ int afis_debug_fold_templates(afis_ctx* ctx, const float* parts, int64_t n_pseud
     return AFIS_OK;
 }
 
+int afis_debug_print_queries(afis_ctx* ctx, const int64_t* idx, int n, const uint8_t* use_minu, const uint8_t* use_tex, int32_t* counts, int32_t* lm_off, int32_t* lm_tile_off,
+                             int32_t* lt_off, int32_t* tile_off, int32_t* tile16_off, int32_t* tex_slot, int32_t* status, int16_t* lm_xy, float* lm_ori, float* lm_des, float* lm_frag,
+                             int16_t* lt_xy, float* lt_ori, float* lt_des)
+{
+    if (!ctx || n <= 0 || !idx || !use_minu || !use_tex || !counts) return fail(ctx, AFIS_EINVAL, "afis_debug_print_queries: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_debug_print_queries: commit the gallery first");
+    std::vector<int32_t> local((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (idx[i] < ctx->index_base || idx[i] - ctx->index_base >= (int64_t)ctx->res_empty.size()) return fail(ctx, AFIS_EINVAL, "afis_debug_print_queries: an index outside the resident shard");
+        local[(size_t)i] = (int32_t)(idx[i] - ctx->index_base);
+    }
+    { const int rcq = quiesce(ctx, "afis_debug_print_queries"); if (rcq != AFIS_OK) return rcq; }
+    QueryGroup grp;
+    struct Drop { QueryGroup* g; ~Drop() { g->release(); } } drop{&grp};
+    PrintGroupPlan plan;
+    std::vector<int32_t> st;
+    AFISCHK(prepare_print_group(ctx, resident_tile_offsets(ctx), local.data(), use_minu, use_tex, n, grp, plan, st));
+    counts[0] = plan.n_lm; counts[1] = plan.n_lm_tiles; counts[2] = plan.n_lt; counts[3] = grp.dev.lt_pad;
+    if (!lm_off) return AFIS_OK;                                            // the sizes only: the caller allocates and calls again
+    if (!lm_tile_off || !lt_off || !tile_off || !tile16_off || !tex_slot || !status || !lm_xy || !lm_ori || !lm_des || !lm_frag || !lt_xy || !lt_ori || !lt_des)
+        return fail(ctx, AFIS_EINVAL, "afis_debug_print_queries: a null output");
+    // every byte of the arrays is planted, so that a word the gather leaves out shows
+    for (DevBuf* b : {&grp.lm_off, &grp.lm_xy, &grp.lm_ori, &grp.lm_des, &grp.lm_frag, &grp.lt_xy, &grp.lt_ori, &grp.lt_des}) HIPCHK(ctx, hipMemsetAsync(b->p, 0xA5, b->bytes, ctx->stream));
+    int64_t h2d = 0;
+    AFISCHK(queue_print_group(ctx, grp, plan, &h2d));
+    { const int rcw = wait_streams(ctx, {ctx->stream}, "afis_debug_print_queries"); if (rcw != AFIS_OK) return rcw; }
+    const QueryDev& d = grp.dev;
+    const size_t nq = (size_t)n, n_lm = (size_t)plan.n_lm, n_tiles = (size_t)plan.n_lm_tiles, n_lt = (size_t)plan.n_lt;
+    struct Back { void* dst; const void* src; size_t bytes; };
+    for (const Back& b : {Back{lm_off, d.lm_off, (3 * nq + 1) * 4}, Back{lm_tile_off, d.lm_tile_off, (3 * nq + 1) * 4}, Back{lt_off, d.lt_off, (nq + 1) * 4}, Back{tile_off, d.tile_off, (nq + 1) * 4},
+                          Back{tile16_off, d.tile16_off, (nq + 1) * 4}, Back{tex_slot, d.tex_slot, nq * 4}, Back{status, d.status, nq * 4}, Back{lm_xy, d.lm_xy, n_lm * 4},
+                          Back{lm_ori, d.lm_ori, n_lm * 4}, Back{lm_des, d.lm_des, n_lm * kDes * 4}, Back{lm_frag, d.lm_frag, n_tiles * 6 * 64 * 16}, Back{lt_xy, d.lt_xy, n_lt * 4},
+                          Back{lt_ori, d.lt_ori, n_lt * 4}, Back{lt_des, d.lt_des, n_lt * kDes * 4}})
+        if (b.bytes) HIPCHK(ctx, hipMemcpy(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost));
+    return AFIS_OK;
+}
+
 int afis_debug_atan2_grid(afis_ctx* ctx, int R, float* out)
 {
     if (!ctx || !out || R < 0 || R > 4096) return fail(ctx, AFIS_EINVAL, "afis_debug_atan2_grid: bad argument");

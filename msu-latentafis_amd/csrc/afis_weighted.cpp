@@ -14,8 +14,7 @@ namespace {
 
 // one query of the call: its active templates (ascending) and where its pseudo-queries stand in the call's numbering
 struct WQuery { std::vector<int> am, at; int64_t first = 0; int n_pq = 0; };
-// one batch: queries [q0, q1), pseudo-queries [p0, p1) — cut at query boundaries
-struct WBatch { int q0, q1; int64_t p0, p1; };
+typedef PseudoBatch WBatch;                                                 // queries [q0, q1), pseudo-queries [p0, p1) — cut at query boundaries
 
 // template i of a query with n templates of that kind is ACTIVE when i < n, i < n_w and the weight is not a zero (of either sign)
 void active_list(int n, const float* w, int n_w, std::vector<int>& out)
@@ -24,15 +23,11 @@ void active_list(int n, const float* w, int n_w, std::vector<int>& out)
     for (int i = 0; i < n && i < n_w; ++i) if (w[i] != 0.0f) out.push_back(i);
 }
 
-// batches of at most `cap` pseudo-queries; a query with more than that is a batch of its own, a query without pseudo-queries joins the batch that is open
 std::vector<WBatch> plan_batches(const std::vector<WQuery>& wq, int64_t cap)
 {
-    std::vector<WBatch> b;
-    for (int i = 0; i < (int)wq.size(); ++i) {
-        if (b.empty() || (b.back().p1 > b.back().p0 && b.back().p1 - b.back().p0 + wq[(size_t)i].n_pq > cap)) b.push_back(WBatch{i, i, wq[(size_t)i].first, wq[(size_t)i].first});
-        b.back().q1 = i + 1; b.back().p1 += wq[(size_t)i].n_pq;
-    }
-    return b;
+    std::vector<int> n_pq;
+    for (const WQuery& q : wq) n_pq.push_back(q.n_pq);
+    return plan_pseudo_batches(n_pq, cap);
 }
 
 // Everything of the call that touches the device.  What it leaves in ctx->elig_scores / ctx->wt_tab after a failure is the caller's to release.

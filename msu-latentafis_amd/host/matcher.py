@@ -70,12 +70,12 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
-           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted",
+           "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
            "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
-               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates"]
+               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates", "afis_debug_print_queries"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -141,6 +141,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_search_eligible.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TemplateView), C.c_int, fp, i32p]
     if hasattr(lib, "afis_search_weighted"):                            # weighted search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_weighted.argtypes = [vp, C.POINTER(TemplateView), C.c_int, fp, C.c_int, fp, C.c_int, fp, i32p]
+    if hasattr(lib, "afis_search_prints"):                              # print search; absent from older builds compared by tools/lib_ab.py
+        lib.afis_search_prints.argtypes = [vp, vp, i64p, C.c_int, fp, fp, fp, i32p]
     if hasattr(lib, "afis_rank_positions"):                             # rank positions; absent from older builds compared by tools/lib_ab.py
         u64p = C.POINTER(C.c_uint64)
         lib.afis_rank_positions.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
@@ -188,6 +190,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_expand_rows.argtypes = [vp, fp, C.c_int, C.c_int64, i32p, i32p, C.c_int, C.c_int64, fp]
     if hasattr(lib, "afis_debug_fold_templates"):
         lib.afis_debug_fold_templates.argtypes = [vp, fp, C.c_int64, C.c_int64, i32p, C.c_int, fp, C.POINTER(C.c_uint8), fp]
+    if hasattr(lib, "afis_debug_print_queries"):
+        u8p, i16p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
+        lib.afis_debug_print_queries.argtypes = [vp, i64p, C.c_int, u8p, u8p, i32p] + [i32p] * 7 + [i16p, fp, fp, fp, i16p, fp, fp]
     return lib
 
 
@@ -668,6 +673,48 @@ class Matcher:
                                                 _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32)))
         self.last_n_q = v.n; self.last_n_templates = G
         return {"scores": scores, "status": status}
+
+    # ---- print search: resident prints as queries, built on the device -----------------------------------------------
+    def search_prints(self, idx, w_minu, w_tex, subset=None, want_scores: bool = True):
+        """search_weighted() with RESIDENT prints as the queries: idx [n_q] global indices of the resident shard (any order, repeats allowed), w_minu / w_tex one weight
+        per query (a scalar is every query's) for the print's minutiae and texture template.  The query views are built on the device from the shard — no template is
+        uploaded —, cell (q, column) is bit for bit search_weighted's for that view, a print against itself included (take it out with an exclusion list).
+        subset: a subset_create handle — the columns are its templates in the caller's order; otherwise the whole resident shard.  The matrix left on the device is a
+        search's: every rank_* call reads it.  get_option("print_gather_us"), get_option("print_h2d_bytes")."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        n = len(a)
+        wm = np.ascontiguousarray(np.broadcast_to(np.asarray(w_minu, np.float32), (n,)))
+        wt = np.ascontiguousarray(np.broadcast_to(np.asarray(w_tex, np.float32), (n,)))
+        cols = subset[1] if subset is not None else self.resident_size
+        scores = np.empty((n, cols), np.float32) if want_scores else None
+        status = np.zeros(n, np.int32)
+        self._chk(self.lib.afis_search_prints(self.ctx, subset[0] if subset is not None else None, _ptr(a, C.c_int64) if n else None, n,
+                                              _ptr(wm, C.c_float) if n else None, _ptr(wt, C.c_float) if n else None,
+                                              _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32)))
+        self.last_n_q = n; self.last_n_templates = cols
+        return {"scores": scores, "status": status}
+
+    def debug_print_queries(self, idx, use_minu=None, use_tex=None) -> dict:
+        """One launch group of search_prints built from the resident prints idx (parity tap) and copied back: the seven tables and the seven arrays of the group,
+        as the device holds them; use_minu / use_tex [n] select what of a print is active (default: everything it has)."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        n = len(a)
+        um = np.ascontiguousarray(np.ones(n, np.uint8) if use_minu is None else np.asarray(use_minu, np.uint8).reshape(n))
+        ut = np.ascontiguousarray(np.ones(n, np.uint8) if use_tex is None else np.asarray(use_tex, np.uint8).reshape(n))
+        counts = np.zeros(4, np.int32)
+        fn = self._tap("afis_debug_print_queries")
+        head = (self.ctx, _ptr(a, C.c_int64), n, _ptr(um, C.c_uint8), _ptr(ut, C.c_uint8), _ptr(counts, C.c_int32))
+        self._chk(fn(*head, *([None] * 14)))
+        n_lm, n_tiles, n_lt = (int(c) for c in counts[:3])
+        out = {"lm_off": np.full(3 * n + 1, -7, np.int32), "lm_tile_off": np.full(3 * n + 1, -7, np.int32), "lt_off": np.full(n + 1, -7, np.int32),
+               "tile_off": np.full(n + 1, -7, np.int32), "tile16_off": np.full(n + 1, -7, np.int32), "tex_slot": np.full(n, -7, np.int32), "status": np.full(n, -7, np.int32),
+               "lm_xy": np.zeros((n_lm, 2), np.int16), "lm_ori": np.zeros(n_lm, np.float32), "lm_des": np.zeros((n_lm, 96), np.float32),
+               "lm_frag": np.zeros((n_tiles, 6, 64, 4), np.float32), "lt_xy": np.zeros((n_lt, 2), np.int16), "lt_ori": np.zeros(n_lt, np.float32),
+               "lt_des": np.zeros((n_lt, 96), np.float32)}
+        ptrs = [_ptr(out[k], C.c_int16 if k.endswith("_xy") else C.c_int32 if out[k].dtype == np.int32 else C.c_float) for k in out]
+        self._chk(fn(*head, *ptrs))
+        out["lt_pad"] = int(counts[3])
+        return out
 
     def debug_fold_templates(self, parts: np.ndarray, qd, w: np.ndarray, empty) -> np.ndarray:
         """k_fold_templates on planted data (parity tap): parts [n_pseudo][G][4] float32 (any bit patterns), qd [n_q][4] int32 = (first pseudo-query, n_pq, n_at,

@@ -11,6 +11,10 @@ descending.  The subject lists merge on subject_key, the ordered bits of the raw
 
 A weighted search (Matcher.search_weighted) needs no merge of its own: the columns of shards are disjoint and the weights common to every rank, so the per-rank
 lists read from its matrix are merge_hits / merge_subject_hits input as they are.
+
+A print search (Matcher.search_prints) builds its queries from the resident shard, so a print is a query only on the rank that holds it.  Against the other
+shards its template must be present there: the existing search_weighted route over host views of the print (n_wm = n_wt = 1) serves that, with the same bits.  Either
+way the per-rank lists read from the matrix are merge_hits / merge_subject_hits input as they are.
 """
 from __future__ import annotations
 
