@@ -238,7 +238,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     context.  Several handles may be live at once; afis_destroy releases those that are left.  A handle belongs to the gallery as it was: after an
  *                     appending commit or a removal that changed the shard afis_rank_subjects refuses it with AFIS_ESTATE (afis_subjects_free still works).
  * afis_rank_subjects   ranks the score matrix of the context's LAST search — any of afis_search, afis_search_dat, afis_search_resident, afis_search_subset,
- *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
+ *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, afis_search_cascade, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
  *                     search's (AFIS_EINVAL otherwise, as for k <= 0 or a null output).  Per query the k best subjects:
  *                       subject_score  the greatest fused score among the subject's templates that the search covered: all of them for a full search, the listed ones for a
  *                                      subset search (a subject without a listed template does not appear).  An empty or removed entry contributes its -1: a subject all of
@@ -765,6 +765,65 @@ int afis_score_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
                      const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
                      int32_t* status /*[n_pairs]*/, float* score /*[n_pairs]*/, float* parts /*[n_pairs][4] or NULL*/);
 
+/* Cascade search (no reference counterpart): a cheap first stage in front of the expensive one.  afis_search scores every (latent, print) cell with all four scorers, and
+ * about 60 % of its device time is the texture path, spent on cells of which a handful per latent ever reach an examiner.  afis_search_cascade runs the
+ * three MINUTIAE scorers for every cell of the resident shard, keeps per latent the `keep` best prints by that partial score — selected on the device — and runs the
+ * TEXTURE scorer for the kept cells only.  No host round trip lies between the stages; there is one wait at the end.
+ * Handle   q is a handle as afis_search_resident takes it, under that call's epoch rules: a handle from before a gallery edit is AFIS_ESTATE, a reserved handle
+ *          (afis_queries_upload_reserved) is accepted while the shard fits.  The columns are the whole resident shard.
+ * keep     1 <= keep <= AFIS_HITS_MAX, anything else is AFIS_EINVAL; n_kept[q] = min(keep, G).
+ * Stage-1 value m(q, t)   the fusion of afis_search (csrc/fuse_cell.h: the one definition of the expression) with the texture score taken as +0.0f: -1.0f for an empty
+ *          or removed print or a latent-empty query, otherwise (a0 + a1) + a2 in fp32, where a_s = +0.0f if the latent's texture slot is s, else parts[s].  The
+ *          texture's slot rule for latents with fewer than three minutiae templates stays in force: the slot the texture would occupy contributes zero.
+ * Selection   per query the kept columns are the first n_kept entries of the list afis_rank_hits(min_score = -INFINITY, cap = keep) would give on the matrix of m: rank_key
+ *          descending, equal keys by ascending GLOBAL index (csrc/rank_order.h).  Every column is an entry; the -1 cells stand last and are kept only when keep exceeds
+ *          the non-empty prints.  kept_idx[q] is that list (global indices, index_base included), padded with -1.
+ * Values   a kept cell holds, bit for bit, afis_search's scores[q][t], and kept_parts holds that cell's four parts (+0.0f four times where the score is the -1; +0.0f
+ *          in the padding), in kept_idx order — under every value of "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9 alike.  Every other cell holds the word
+ *          0xffffffff, the "no entry" word (csrc/score_order.h: kNoEntryWord), in the matrix left on the device and in scores [n_q][G] (NULL: not copied).  status
+ *          [n_q] (or NULL) is afis_search's.  n_kept, kept_idx and kept_parts may each be NULL.
+ * The matrix afterwards   after AFIS_OK the context's last-search matrix is this [n_q][G] matrix: a full search's record under afis_search's invalidation rules; the
+ *          call is one of the searches that count.  It reads as afis_search_eligible's matrix reads: afis_rank_hits, afis_rank_subject_hits, afis_rank_latent_hits,
+ *          their _filtered forms, and afis_rank_positions / afis_rank_subject_positions / afis_count_before see the kept cells as the only entries; the CASE lists
+ *          must be read through their _filtered forms; afis_rank_subjects is not in this interface.  A mate that stage 1 dropped is AFIS_POS_NO_ENTRY in
+ *          afis_rank_positions: that is how a caller measures what a given keep costs in accuracy.  After any return other than AFIS_OK the matrix is invalid and the
+ *          call holds nothing it allocated.  A following afis_search_resident on the same context returns the bytes it returned before the cascade call.
+ * Arguments   AFIS_EINVAL: a null ctx or q, keep out of range; AFIS_ESTATE: a call before the first commit, a stale handle.  n_q == 0 or G == 0 returns AFIS_OK as
+ *          afis_search does (n_kept 0, kept_idx -1).  Room — the two matrices, the per-part scores of all queries [n_q][G][4], the minutiae stage's buffers for the
+ *          largest launch group, the kept lists and pair tables, one chunk's dense row maxima and the texture list kernel's slab — is ensured before anything is
+ *          queued: AFIS_EDEVICE otherwise.  Host waits are bounded by "search_timeout_s".
+ * Options  "cascade_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CASCADE_PAIRS_PER_LAUNCH): the pairs of one chunk of the second stage at most; results do
+ *          not depend on it.  "cascade_stage1_us", "cascade_select_us", "cascade_stage2_us" (read-only): the device time of the last call's three parts, each from its
+ *          own pair of HIP events; "cascade_kept_pairs" (read-only): the pairs its second stage scored.  All four read 0 after a call that failed or was empty.
+ * Timing   afis_get_timing* reports stage 1: cands_ms, minu_graph_ms, minu_ms, fuse_ms (k_fuse_stage1), total_ms their sum, pairs = n_q x G, launch_groups and the
+ *          minutiae task counters; the texture fields are 0.
+ * How      csrc/afis_cascade.cpp.  Stage 1 is the minutiae stage of a search, per launch group of the handle on the context's stream, unconfined (no CU-masked side
+ *          streams); k_fuse_stage1 writes m.  The selection is k_rank_hits, unchanged.  The structure of the second stage's pair tables is known before anything runs
+ *          (csrc/cascade_tables.h) and uploaded once; k_cascade_gather (csrc/cascade.hip) fills them from the kept lists; per chunk and launch group the pair kernels
+ *          of afis_score_pairs (k_adc_pairs, k_graph_texture in its pair form, k_fuse_pairs); k_cascade_scatter writes the combined matrix, which was filled with the
+ *          no-entry word first, so every matrix word is written at most twice.
+ * Cost     against the full search — afis_search_resident(k = 0) on the same context — on one MI355X, 100 latents x 100 000 prints, interleaved runs, medians of three
+ *          after a discarded first, device clock (profiles/cascade_search_timing.json, tools/cascade_search_timing.py; the host clock agrees within 0.5 ms).  Headline
+ *          workload: keep 100 — 819.3 ms (stage 1 801.0, selection 0.29, stage 2 18.1) against 1 875.8 ms: 0.44 x; keep 1000 — 923.9 ms (803.6 / 0.30 / 120.6)
+ *          against 1 881.8 ms: 0.49 x; keep 4096 — 1 237.9 ms (801.1 / 0.33 / 436.5) against 1 879.3 ms: 0.66 x.  Structured workload: keep 100 — 853.8 ms (839.3 / 0.29 / 14.3) against
+ *          2 220.5 ms: 0.38 x; keep 1000 — 937.1 ms (840.5 / 0.31 / 96.4) against 2 226.2 ms: 0.42 x; keep 4096 — 1 200.6 ms (840.5 / 0.34 / 359.8) against
+ *          2 223.8 ms: 0.54 x.  Spreads (max - min) at most 3.3 ms for the cascade, 5.3 ms for the full search.
+ *          Stage 1 alone is 0.43 of the full step on the headline workload (cands_ms 380, minu_graph_ms 421) and 0.38 on the structured one (389, 451): the two
+ *          minutiae kernels back to back on the whole chip.  Stage 2 costs 0.9 - 1.8 us per pair and at keep 4096 is a third of the call: k_adc_pairs is untuned
+ *          (its comment says where to look first) — the follow-up.
+ *          What keep costs in accuracy, on these SYNTHETIC galleries (facts about the generator, not about fingerprints; read through afis_rank_positions on both
+ *          matrices): of the 400 planted mates of either workload every one is kept at keep 100, 1000 and 4096, and the 100 that stand at rank 1 under afis_search
+ *          still stand at rank 1.  The generator's non-mates score next to nothing with the minutiae scorers, so these shares say little about real prints.
+ * Shards: every rank keeps `keep` of its OWN shard.  The per-rank lists are host/sharding.py::merge_hits / merge_subject_hits input as they are; their union contains
+ *          the global stage-1 top `keep`, so the merged result is a superset of the single-context cascade, not the same list.
+ * Not in this interface: a subset form; a host-view form (afis_search style: upload the latents with afis_queries_upload first); a keep above AFIS_HITS_MAX; a first stage
+ *          other than the minutiae scorers; the match CLI.  No result of afis_search changes because this function exists. */
+#define AFIS_CASCADE_PAIRS_PER_LAUNCH 16384
+int afis_search_cascade(afis_ctx* ctx, afis_queries* q, int keep,
+                        float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/,
+                        int64_t* n_kept /*[n_q] or NULL*/,
+                        int64_t* kept_idx /*[n_q][keep] or NULL*/, float* kept_parts /*[n_q][keep][4] or NULL*/);
+
 /* afis_get_timing2 copies min(struct_size, sizeof(afis_timing)) bytes: pass sizeof(afis_timing) of the header the caller was compiled
  * against, so that a library with a longer struct never writes past the caller's.  afis_get_timing (kept for callers of the round-2
  * header) fills only the fields up to `pairs` (48 bytes, the struct of that header); the fields after it need afis_get_timing2. */
@@ -827,7 +886,13 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * call that failed or had no queries (afis_search_prints sets the last two as well, and obeys the first).
  * "print_gather_us" (read-only): the device time of the last afis_search_prints' gather launches (print_queries.hip), from HIP events around each launch group's,
  * summed; "print_h2d_bytes" (read-only): the bytes that call handed to host-to-device copies — the launch groups' tables and the fold's —, counted where the copies
- * are issued; both 0 after a call that failed or had no queries. */
+ * are issued; both 0 after a call that failed or had no queries.
+ * "cascade_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CASCADE_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_search_cascade's second stage at most —
+ * 8 bytes per row of the handle's longest latent texture template each (at most 8 KB) for the dense row maxima; results do not depend on it.
+ * "cascade_stage1_us" (read-only): the device time of the last afis_search_cascade's first stage (per launch group the candidate kernel, the minutiae list kernel,
+ * k_fuse_stage1); "cascade_select_us" (read-only): of its selection (k_rank_hits); "cascade_stage2_us" (read-only): of its second stage (the no-entry fill,
+ * k_cascade_gather, per chunk and launch group k_adc_pairs, k_graph_texture in its pair form, k_fuse_pairs, then k_cascade_scatter) — each from its own pair of HIP
+ * events; "cascade_kept_pairs" (read-only): the pairs that second stage scored; all four 0 after a call that failed or was empty. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -112,7 +112,7 @@ void afis_destroy(afis_ctx* c)
     for (afis_labels* lb : c->label_sets) release_labels(lb);                // label handles that are still live
     c->label_sets.clear();
     free_gallery_dev(c);
-    c->out_perm.release(); c->subj_best.release(); c->subj_out.release(); c->hits_out.release(); c->scores_t.release(); c->case_fused.release(); c->case_tab.release(); c->filt_scores.release(); c->filt_tab.release(); c->pos_tab.release(); c->pos_out.release(); c->corr_buf.release(); c->pair_buf.release(); c->pair_tex_slab.release(); c->elig_scores.release(); c->wt_tab.release();
+    c->out_perm.release(); c->subj_best.release(); c->subj_out.release(); c->hits_out.release(); c->scores_t.release(); c->case_fused.release(); c->case_tab.release(); c->filt_scores.release(); c->filt_tab.release(); c->pos_tab.release(); c->pos_out.release(); c->corr_buf.release(); c->pair_buf.release(); c->pair_tex_slab.release(); c->elig_scores.release(); c->wt_tab.release(); c->casc_buf.release(); c->casc_slab.release();
     c->codewords.release(); c->table.release(); c->lut.release(); c->rm_val.release(); c->rm_arg.release(); c->rm_cv.release(); c->rm_n.release();
     c->parts.release(); c->scores.release(); c->scratch.release(); c->cands.release(); c->cand_n.release(); c->minu_fb.release(); c->diag.release(); c->topk_idx.release(); c->topk_score.release(); c->lutq.release(); c->lutq_min.release(); c->lutq_rng.release(); c->lutq_rowc.release(); c->lut32.release();
     c->mf_cw16.release(); c->mf_cwn.release(); c->mf_bfrag.release(); c->mf_rowk.release(); c->mf_rec.release(); c->mf_stats.release(); c->tex_slab.release(); c->minu_slab.release();
@@ -199,6 +199,11 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "correspondences_us") *value = ctx->correspondences_us;              // read-only: device time of the last afis_correspondences_pairs' / afis_correspondences' launches
     else if (n == "score_pairs_per_launch") *value = ctx->score_pairs_per_launch;
     else if (n == "score_pairs_us") *value = ctx->score_pairs_us;                     // read-only: device time of the last afis_score_pairs' launches
+    else if (n == "cascade_pairs_per_launch") *value = ctx->cascade_pairs_per_launch;
+    else if (n == "cascade_stage1_us") *value = ctx->cascade_stage1_us;               // read-only: device time of the last afis_search_cascade's first stage, selection and second stage, each from its own pair of events
+    else if (n == "cascade_select_us") *value = ctx->cascade_select_us;
+    else if (n == "cascade_stage2_us") *value = ctx->cascade_stage2_us;
+    else if (n == "cascade_kept_pairs") *value = ctx->cascade_kept_pairs;             // read-only: pairs that call's second stage scored
     else if (n == "mf_stats") *value = ctx->mf_collect_stats;
     else if (n == "rowmax_budget_mb") *value = ctx->rowmax_budget_bytes >> 20;
     else if (n == "lut_dtype") *value = 32;
@@ -225,6 +230,7 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value)
     else if (n == "ref_tie_order") { if (value < 0 || value > 2) return fail(ctx, AFIS_EINVAL, "ref_tie_order must be 0 (equal sort keys by ascending index), 1 (candidate norms in the order libstdc++'s std::sort leaves them: = s3_tie_order 1) or 2 (the scores of the greedy selections of S8 and S9 as well)"); ctx->s3_tie_order = value >= 1; ctx->s89_tie_order = value >= 2; }
     else if (n == "corr_pairs_per_launch") { if (value < 1 || value > kCorrPairsMax) return fail(ctx, AFIS_EINVAL, "corr_pairs_per_launch must be 1.." + std::to_string(kCorrPairsMax)); ctx->corr_pairs_per_launch = (int)value; }
     else if (n == "score_pairs_per_launch") { if (value < 1 || value > kScorePairsMax) return fail(ctx, AFIS_EINVAL, "score_pairs_per_launch must be 1.." + std::to_string(kScorePairsMax)); ctx->score_pairs_per_launch = (int)value; }
+    else if (n == "cascade_pairs_per_launch") { if (value < 1 || value > kCascadePairsMax) return fail(ctx, AFIS_EINVAL, "cascade_pairs_per_launch must be 1.." + std::to_string(kCascadePairsMax)); ctx->cascade_pairs_per_launch = (int)value; }
     else if (n == "weighted_batch_pseudo") { if (value < 0 || value > 0x7fffffff) return fail(ctx, AFIS_EINVAL, "weighted_batch_pseudo must be 0 (auto) or a positive count of pseudo-queries"); ctx->weighted_batch_pseudo = (int)value; }
     else if (n == "mf_stats") { ctx->mf_collect_stats = value ? 1 : 0; }
     else if (n == "search_timeout_s") { ctx->search_timeout_s = (double)value; }        // <= 0: unbounded hipStreamSynchronize

@@ -260,6 +260,19 @@ hipError_t launch_adc_pairs(const QueryDev& q, const GalleryDev& g, const float*
 hipError_t launch_graph_texture_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* table_dist, const float* rm_val, const int32_t* rm_arg,
                                       float* parts, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream);
 hipError_t launch_fuse_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* parts, float* scores, hipStream_t stream);
+// afis_search_cascade (afis_cascade.cpp, cascade.hip): the minutiae scorers for every cell, the texture scorer for the `keep` best prints of every latent.
+// launch_fuse_stage1: S10 of a launch group with the texture score taken as +0.0f (fuse_cell.h) from parts[(q*G+g)*4 + 0..2] -> scores[q*G+g], the matrix the kept lists
+// are selected from (launch_rank_hits at the ordered word of -inf, cap = keep).  launch_cascade_gather: one thread per (query, rank < n_kept) of those lists kept
+// [n_q][keep] — the pair's entry of the second stage's pair tables (cascade_tables.h: q_slot [n_q + 1], piece_first [n_pieces + 1], piece_q0 [n_pieces]; tab 2 total +
+// n_pieces ints, the count words of the pieces included) and parts[q][t][0..2] | +0.0f -> pair_parts[slot]; a query whose slot range is empty has no pairs.
+// launch_cascade_scatter: out[q][t] = pair_score[slot], or -1.0f for a query without pairs, for every kept (q, t); nothing else of out [n_q][G] is written.
+constexpr int kCascadePairsPerLaunch = 16384;           // AFIS_CASCADE_PAIRS_PER_LAUNCH: option cascade_pairs_per_launch's default (131 MB of dense row maxima at lt_pad 1000, the texture slab at its full 1.0 GB)
+constexpr int kCascadePairsMax = 1 << 20;               // ... and its ceiling
+hipError_t launch_fuse_stage1(const QueryDev& q, const GalleryDev& g, const float* parts, float* scores, hipStream_t stream);
+hipError_t launch_cascade_gather(int n_q, int G, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot, const int32_t* piece_first,
+                                 int n_pieces, const int32_t* piece_q0, const float* parts, int32_t* tab, float* pair_parts, hipStream_t stream);
+hipError_t launch_cascade_scatter(int n_q, int G, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot, const float* pair_score,
+                                  float* out, hipStream_t stream);
 
 // S11: per-query rank list over the shard's scores [n_q][G] on the device (score descending, index ascending); out_idx[n_q][k] carries
 // index_base + local index (-1 / -inf beyond G)

@@ -10,6 +10,7 @@
 // Canonical arithmetic (see oracle/afis_oracle.cpp): descriptor dot products are k-ascending fmaf chains, row/column sums are
 // index-ascending, the normalisation is evaluated in double exactly as the reference's expression promotes it.
 #include "afis_device.h"
+#include "fuse_cell.h"
 #include "stdsort_order.h"
 #include <cstdlib>
 
@@ -1012,28 +1013,14 @@ hipError_t launch_minu_cands_pairs(const QueryDev& q, const GalleryDev& g, float
 // S10 fusion: final = score[0] + score[1] + score[2] + score[28]*0.3 (matcher.cpp:188), where the reference's score
 // vector holds the three minutiae scores at [0..2] and the texture score at index (#latent minutiae templates).
 // =====================================================================================================================
-// the fused score of one (latent qi, template gi) cell from its four parts p[0..3]: the one definition k_fuse (a search's matrix) and k_fuse_pairs (afis_score_pairs) share
-__device__ __forceinline__ float fuse_cell(const QueryDev& q, const GalleryDev& g, int qi, int gi, const float* __restrict__ p)
-{
-    if (q.status[qi] != 0 || g.empty[gi]) return -1.0f;                         // :145, :181-187
-    const int slot = q.tex_slot[qi];
-    const float tex = p[3];
-    const float a0 = slot == 0 ? tex : p[0];
-    const float a1 = slot == 1 ? tex : p[1];
-    const float a2 = slot == 2 ? tex : p[2];
-    const float a28 = slot == 28 ? tex : 0.0f;
-    float f = a0 + a1;
-    f = f + a2;
-    return (float)((double)f + (double)a28 * 0.3);
-}
-
+// fuse_cell (fuse_cell.h): the one definition of the expression k_fuse (a search's matrix), k_fuse_pairs (afis_score_pairs) and k_fuse_stage1 (cascade.hip) share
 __global__ __launch_bounds__(256) void k_fuse(QueryDev q, GalleryDev g, const float* __restrict__ parts, float* __restrict__ scores)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long n = (long long)q.nq * g.G;
     if (idx >= n) return;
     const int qi = (int)(idx / g.G), gi = (int)(idx - (long long)qi * g.G);
-    scores[idx] = fuse_cell(q, g, qi, gi, parts + (size_t)idx * 4);
+    scores[idx] = fuse_cell(q, g, qi, gi, parts + (size_t)idx * 4, parts[(size_t)idx * 4 + 3]);
 }
 
 // afis_score_pairs: score[p] of pair p of the table [n_pairs | (query of the group, shard-local template) x n_pairs] from parts[4 p .. 4 p + 3]
@@ -1041,7 +1028,7 @@ __global__ __launch_bounds__(256) void k_fuse_pairs(QueryDev q, GalleryDev g, co
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= pair_tab[0]) return;
-    scores[p] = fuse_cell(q, g, pair_tab[1 + 2 * p], pair_tab[2 + 2 * p], parts + (size_t)p * 4);
+    scores[p] = fuse_cell(q, g, pair_tab[1 + 2 * p], pair_tab[2 + 2 * p], parts + (size_t)p * 4, parts[(size_t)p * 4 + 3]);
 }
 
 // =====================================================================================================================

@@ -15,6 +15,10 @@ lists read from its matrix are merge_hits / merge_subject_hits input as they are
 A print search (Matcher.search_prints) builds its queries from the resident shard, so a print is a query only on the rank that holds it.  Against the other
 shards its template must be present there: the existing search_weighted route over host views of the print (n_wm = n_wt = 1) serves that, with the same bits.  Either
 way the per-rank lists read from the matrix are merge_hits / merge_subject_hits input as they are.
+
+A cascade search (Matcher.search_cascade) keeps per latent the `keep` best prints by the minutiae scorers alone: every rank keeps `keep` of its own shard.  The per-rank
+lists read from its matrix are merge_hits / merge_subject_hits input as they are; their union contains the global stage-1 top `keep`, so the merged result is a
+superset of the single-context cascade over the whole gallery, not the same list.
 """
 from __future__ import annotations
 
