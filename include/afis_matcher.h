@@ -253,7 +253,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     The matrix stays rankable from the successful return of the search until the next call on the context that queues device work or edits the gallery —
  *                     a search (a failed or timed-out one included), afis_queries_upload, afis_correspondences, afis_match_all_templates, every gallery
  *                     edit and export, afis_subset_create, afis_subset_free, a change of option "bound_cus" — after which afis_rank_subjects is AFIS_ESTATE.  It may itself
- *                     be repeated, with another k or another handle; afis_correspondences_pairs, afis_score_pairs, afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
+ *                     be repeated, with another k or another handle; afis_correspondences_pairs, afis_score_pairs, afis_score_print_pairs, afis_correspondences_print_pairs, afis_subjects_create, afis_subjects_free, afis_queries_free, afis_get_timing*, afis_get_option,
  *                     afis_last_error and afis_gallery_size leave the matrix alone.  No result of a search changes because subjects exist.
  * Shards: every rank labels its own shard and ranks its own subjects; the per-rank lists merge exactly although a person's prints may lie in several shards
  * (host/sharding.py::merge_subject_topk). */
@@ -649,7 +649,8 @@ int afis_search_weighted(afis_ctx* ctx, const afis_template_view* queries, int n
  * Timing   as afis_search_weighted: the additive fields summed over the batches, pairs = pseudo-queries x columns; "weighted_pseudo_queries" and "weighted_fold_us"
  *          describe this call too.  "print_gather_us" and "print_h2d_bytes" (read-only): the device time of the call's gather launches, and the bytes it handed to
  *          host-to-device copies (the groups' tables and the fold's); both 0 after a failed or empty call.
- * Not in this interface: pair and verification forms for prints (afis_score_pairs and afis_correspondences_pairs take latents); rolled templates beyond index 0 (the
+ * Not in this interface: the pair and verification forms for prints (afis_score_print_pairs and afis_correspondences_print_pairs below give them, without a matrix);
+ *          rolled templates beyond index 0 (the
  *          shard holds one minutiae and one texture template per print); the match CLI.  Shards: a print is a query only on the rank that holds it; against the
  *          other shards its template must be present there, and the existing afis_search_weighted route over host views serves that.  The per-rank lists read from
  *          the matrix are host/sharding.py::merge_hits / merge_subject_hits input as they are.  No result of any other search changes because this function exists.
@@ -764,6 +765,70 @@ int afis_correspondences_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
 int afis_score_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
                      const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
                      int32_t* status /*[n_pairs]*/, float* score /*[n_pairs]*/, float* parts /*[n_pairs][4] or NULL*/);
+
+/* Print pairs (no reference counterpart): the pair forms for RESIDENT PRINT pairs — what afis_score_pairs and afis_correspondences_pairs are for latents, for the
+ * queries of afis_search_prints.  Verification (1:1) of two enrolled prints; card against card (ten pairs, finger i against finger i, no 10 x 10 cross product); the
+ * second half of the operator's transaction after afis_rank_hits on a print search — the parts behind each score and the surviving correspondences of every (query
+ * print, candidate) pair —; labelled print pairs (a ROC over mated and non-mated impressions, a de-duplication audit) without scoring a matrix.
+ *   a_idx [n_pairs], b_idx [n_pairs]   the query print and the column print of pair i: GLOBAL indices of the resident shard as it stands (index_base included) — never
+ *               a subset's position, whatever search ran last.  Pairs may come in any order and may repeat; a pair (a, a) is an ordinary pair.  No handle is involved:
+ *               the calls see the shard as it stands after any edit.
+ *   w_minu [n_pairs], w_tex [n_pairs]   afis_score_print_pairs: one weight per PAIR for a's minutiae template and for a's texture template; finite and >= 0 (-0.0f is a
+ *               zero), as afis_search_prints': a violation is AFIS_EINVAL before anything is written or queued.
+ * Covered     a pair is covered when BOTH indices lie in [index_base, index_base + G) of the resident shard.  Anything else — the -1 that pads the list calls, an
+ *               index of another shard, a template staged but not committed — is uncovered, silently: status[i] = AFIS_PAIR_NOT_COVERED, score[i] = -inf, parts +0.0f;
+ *               counts[i] = AFIS_CORR_NOT_COVERED, zeros.  This differs on purpose from afis_search_prints, where a query outside the shard is AFIS_EINVAL: the same
+ *               pair list can go to every rank of a sharded gallery, and the rank that holds both prints answers it (host/sharding.py::merge_print_pair_scores,
+ *               merge_print_correspondences).  A pair whose prints lie in two shards is answered by NO rank: the existing afis_search_weighted route over host views
+ *               serves those pairs.
+ * Values of afis_score_print_pairs, a covered pair   status[i] = AFIS_PAIR_OK; score[i] is bit for bit the cell afis_search_prints writes for query a, column b and the
+ *               weights (w_minu[i], w_tex[i]).  The minutiae term is active when a holds a minutiae template and w_minu[i] != 0.0f, the texture term likewise.  The
+ *               score is -1.0f when b is empty or removed, or when nothing of a is active.  Otherwise double acc = +0.0; minutiae active: acc = acc + (double)w_minu *
+ *               (double)v_m; then texture active: acc = acc + (double)w_tex * (double)v_t; score = (float)acc — v_m and v_t being the entries afis_match_all_templates
+ *               gives the print's view (P of the print-search paragraph) against b; a print b without a minutiae template leaves a zero, and that zero is included.
+ *               parts[i*2 + 0..1] (parts may be NULL) = (v_m if active else +0.0f, v_t if active else +0.0f), +0.0f twice where the score is that -1.  All of it under
+ *               every value of "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9 alike.
+ * Values of afis_correspondences_print_pairs, a covered pair   a or b holds no minutiae template (empty and removed entries included): counts[i] = AFIS_CORR_NOT_RUN,
+ *               zeros.  Otherwise counts[i] is the number of survivors of both graph filters, xy[(i*120 + t)*4 + 0..3] a's x, a's y, b's x, b's y of survivor t in the
+ *               scorer's order (rows beyond the count zero), and part[i] (part may be NULL) the scorer's return value: bit for bit parts[i*2 + 0] of the score call with
+ *               a non-zero w_minu; +0.0f where counts < 0.  Byte for byte these are counts[.][0], xy[.][0] and the part afis_correspondences(_pairs) gives for a latent
+ *               view of 27 minutiae templates whose 27th is a's minutiae template as the shard holds it, against b: a scorer's value depends on nothing but its
+ *               (latent template, print) pair.
+ * State       as afis_score_pairs: the last search's matrix is neither written nor invalidated — every ranking call may precede and follow, and a following
+ *               afis_search_resident returns the bytes it returned before.  AFIS_EINVAL: a null ctx, n_pairs < 0, a null required array with n_pairs > 0 (parts and part
+ *               may be NULL), a bad weight.  AFIS_ESTATE: a call before the first commit.  n_pairs == 0 is AFIS_OK.  Every batch ensures its room before it queues
+ *               anything, and the caller's arrays are written once, after the last batch: a call that fails — AFIS_EDEVICE — has changed nothing a caller can see
+ *               (the context's own scratch buffers may have been reallocated).  Host waits are bounded as a search's are ("search_timeout_s").
+ * How         the distinct covered query prints that have something a pair wants, in order of first appearance, are cut into batches (csrc/print_pairs_plan.h) of at
+ *               most option "print_pairs_batch_prints" prints — 0, the default: as many consecutive prints as an eighth of the launch-group budget holds the views of (392
+ *               bytes per minutia and per texture point, 6 144 per fragment tile), and at least one.  Every pair belongs to the batch of its a; results do not depend
+ *               on the option.  Per batch a temporary query handle is filled on the device exactly as a batch of afis_search_prints is (a template no pair of a print
+ *               weights is not gathered; the correspondence call gathers minutiae only), then the pair drivers of afis_score_pairs / afis_correspondences_pairs run over
+ *               the batch's pairs, in chunks of "score_pairs_per_launch" / "corr_pairs_per_launch" pairs, and the handle is freed under afis_queries_free's rules.  The
+ *               one device piece of its own is the fold of a print pair (csrc/template_fold.hip::k_fold_print_pairs) in the place of the latent call's fusion.
+ *               "print_pairs_us" (read-only): the device time of the last call's launches, gathers included, summed over batches and chunks; "print_pairs_query_prints"
+ *               (read-only): the distinct query prints it gathered; both 0 after a call that failed or queued nothing.
+ * Cost        one MI355X, 100 000 resident prints, weights 1 and 0.3f, against the only route there was — afis_subset_create over the union of the b's,
+ *               afis_search_prints of the distinct a's over it, afis_subset_free —, interleaved runs, medians of three after a discarded first, spread = max - min
+ *               (tools/print_pairs_timing.py, profiles/print_pairs_timing.json), the same bits on both routes and in the full print search's cells.  (a) Card against
+ *               card, 10 pairs: 0.94 ms on the host clock (spread 0.02), device clock 615 us (spread 7), against 2.16 ms (0.04) and 856 us (9): 2.3 x on the host,
+ *               1.4 x on the device.  (b) 100 query prints x their 100 best from afis_rank_hits, 10 000 pairs against a union of 9 507 prints x 100: 31.1 ms (0.1)
+ *               and 29.99 ms (0.03) against 217.8 ms (0.5) and 211.4 ms (0.5): 7.0 x.  (c) ONE print against its 4 096 best, where the subset route scores exactly the
+ *               same 4 096 cells with the search's tuned kernels: 9.98 ms (0.11) and 9.60 ms (0.06) against 6.77 ms (0.07) and 3.40 ms (0.05) — there the subset is
+ *               the better call, 2.8 x on the device clock and 1.5 x on the host's.  afis_correspondences_print_pairs on list (b): 9.65 ms (0.26) and 7.52 ms (0.03);
+ *               9 338 of the 10 000 pairs have survivors.  Where the time goes (a kernel trace of all three lists together, a run of its own): of the score calls'
+ *               device time k_adc_pairs 50 %, the texture list kernel 21 %, the two minutiae launches 28 %, the gathers about 1 % (5 % of the call on list (a): 31 us
+ *               for ten prints; 0.4 % on (b), 0.25 % on (c)) and k_fold_print_pairs 0.07 % (4.6 us a launch).  So: prints with candidate lists of their own — the pair
+ *               call; ONE print (or prints that share their candidates) against thousands — afis_subset_create + afis_search_prints.  Nothing here is tuned.  The full
+ *               search is untouched: tools/lib_ab.py against the parent commit's library, scores bit-identical, this tree's median total_ms 1 882.6 inside the
+ *               parent's steps 1 881.9 .. 1 884.8 (median 1 884.4) — profiles/print_pairs_full_search_ab.txt. */
+int afis_score_print_pairs(afis_ctx* ctx, int64_t n_pairs,
+                           const int64_t* a_idx /*[n_pairs], GLOBAL: the query print*/, const int64_t* b_idx /*[n_pairs], GLOBAL: the column print*/,
+                           const float* w_minu /*[n_pairs]*/, const float* w_tex /*[n_pairs]*/,
+                           int32_t* status /*[n_pairs]*/, float* score /*[n_pairs]*/, float* parts /*[n_pairs][2] or NULL*/);
+int afis_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs,
+                                     const int64_t* a_idx, const int64_t* b_idx,
+                                     int32_t* counts /*[n_pairs]*/, int16_t* xy /*[n_pairs][120][4]*/, float* part /*[n_pairs] or NULL*/);
 
 /* Cascade search (no reference counterpart): a cheap first stage in front of the expensive one.  afis_search scores every (latent, print) cell with all four scorers, and
  * about 60 % of its device time is the texture path, spent on cells of which a handful per latent ever reach an examiner.  afis_search_cascade runs the
@@ -887,6 +952,11 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "print_gather_us" (read-only): the device time of the last afis_search_prints' gather launches (print_queries.hip), from HIP events around each launch group's,
  * summed; "print_h2d_bytes" (read-only): the bytes that call handed to host-to-device copies — the launch groups' tables and the fold's —, counted where the copies
  * are issued; both 0 after a call that failed or had no queries.
+ * "print_pairs_batch_prints" (settable, >= 0; default 0): the query prints of one batch — one temporary query handle — of afis_score_print_pairs and
+ * afis_correspondences_print_pairs at most; 0 = as many consecutive prints as an eighth of the launch-group budget holds the views of, and at least one.  Results do not
+ * depend on it.  "print_pairs_us" (read-only): the device time of the last such call's launches — the gathers of print_queries.hip and every chunk's pair kernels, the
+ * score call's ending in k_fold_print_pairs —, from HIP events, summed over batches and chunks; "print_pairs_query_prints" (read-only): the distinct query prints that
+ * call gathered; both 0 after a call that failed or queued nothing.
  * "cascade_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CASCADE_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_search_cascade's second stage at most —
  * 8 bytes per row of the handle's longest latent texture template each (at most 8 KB) for the dense row maxima; results do not depend on it.
  * "cascade_stage1_us" (read-only): the device time of the last afis_search_cascade's first stage (per launch group the candidate kernel, the minutiae list kernel,

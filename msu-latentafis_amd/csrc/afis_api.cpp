@@ -199,6 +199,9 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "correspondences_us") *value = ctx->correspondences_us;              // read-only: device time of the last afis_correspondences_pairs' / afis_correspondences' launches
     else if (n == "score_pairs_per_launch") *value = ctx->score_pairs_per_launch;
     else if (n == "score_pairs_us") *value = ctx->score_pairs_us;                     // read-only: device time of the last afis_score_pairs' launches
+    else if (n == "print_pairs_batch_prints") *value = ctx->print_pairs_batch_prints;
+    else if (n == "print_pairs_us") *value = ctx->print_pairs_us;                     // read-only: device time of the last afis_score_print_pairs' / afis_correspondences_print_pairs' launches, gathers included
+    else if (n == "print_pairs_query_prints") *value = ctx->print_pairs_query_prints; // read-only: distinct query prints that call gathered
     else if (n == "cascade_pairs_per_launch") *value = ctx->cascade_pairs_per_launch;
     else if (n == "cascade_stage1_us") *value = ctx->cascade_stage1_us;               // read-only: device time of the last afis_search_cascade's first stage, selection and second stage, each from its own pair of events
     else if (n == "cascade_select_us") *value = ctx->cascade_select_us;
@@ -232,6 +235,7 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value)
     else if (n == "score_pairs_per_launch") { if (value < 1 || value > kScorePairsMax) return fail(ctx, AFIS_EINVAL, "score_pairs_per_launch must be 1.." + std::to_string(kScorePairsMax)); ctx->score_pairs_per_launch = (int)value; }
     else if (n == "cascade_pairs_per_launch") { if (value < 1 || value > kCascadePairsMax) return fail(ctx, AFIS_EINVAL, "cascade_pairs_per_launch must be 1.." + std::to_string(kCascadePairsMax)); ctx->cascade_pairs_per_launch = (int)value; }
     else if (n == "weighted_batch_pseudo") { if (value < 0 || value > 0x7fffffff) return fail(ctx, AFIS_EINVAL, "weighted_batch_pseudo must be 0 (auto) or a positive count of pseudo-queries"); ctx->weighted_batch_pseudo = (int)value; }
+    else if (n == "print_pairs_batch_prints") { if (value < 0 || value > 0x7fffffff) return fail(ctx, AFIS_EINVAL, "print_pairs_batch_prints must be 0 (auto) or a positive count of query prints"); ctx->print_pairs_batch_prints = (int)value; }
     else if (n == "mf_stats") { ctx->mf_collect_stats = value ? 1 : 0; }
     else if (n == "search_timeout_s") { ctx->search_timeout_s = (double)value; }        // <= 0: unbounded hipStreamSynchronize
     else if (n == "search_timeout_ms") { ctx->search_timeout_s = (double)value * 1e-3; }

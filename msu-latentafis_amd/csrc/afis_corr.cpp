@@ -14,9 +14,10 @@ static_assert(kCorrPairsPerLaunch == AFIS_CORR_PAIRS_PER_LAUNCH, "option corr_pa
 namespace afis {
 
 int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
-                          const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part)
+                          const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part, int out_slots)
 {
     const std::string w(who);
+    const size_t S = out_slots == 1 ? 1 : 3;                               // selected templates per pair in the caller's arrays: all three, or slot 0 alone (a print's view has no other)
     const int64_t G = ctx->gal.G, base = ctx->index_base;
     ctx->correspondences_us = 0;
     for (int64_t i = 0; i < n_pairs; ++i)
@@ -43,7 +44,7 @@ int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<Quer
         const int64_t t = idx[i] - base;
         if (t < 0 || t >= G) continue;
         const uint8_t* h = &has[(size_t)query[i] * 3];
-        if (ctx->res_empty[(size_t)t] || ctx->res_mo[(size_t)t + 1] - ctx->res_mo[(size_t)t] <= 0 || !(h[0] | h[1] | h[2])) continue;
+        if (ctx->res_empty[(size_t)t] || ctx->res_mo[(size_t)t + 1] - ctx->res_mo[(size_t)t] <= 0 || !(S == 1 ? h[0] : h[0] | h[1] | h[2])) continue;
         dev.push_back(i);
     }
     // ---- room first: every allocation precedes all device work and the first write into the caller's arrays
@@ -71,10 +72,10 @@ int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<Quer
         HIPCHK(ctx, ensure_pin(ctx, pin_bytes));
     }
     // ---- what holds without the device: -2 outside the shard, -1 where the reference runs no scorer
-    memset(xy, 0, (size_t)n_pairs * 3 * kTopMinu * 4 * sizeof(int16_t));
+    memset(xy, 0, (size_t)n_pairs * S * kTopMinu * 4 * sizeof(int16_t));
     for (int64_t i = 0; i < n_pairs; ++i) {
         const int64_t t = idx[i] - base;
-        for (int s = 0; s < 3; ++s) { counts[i * 3 + s] = (t < 0 || t >= G) ? AFIS_CORR_NOT_COVERED : AFIS_CORR_NOT_RUN; if (part) part[i * 3 + s] = 0.0f; }
+        for (size_t s = 0; s < S; ++s) { counts[(size_t)i * S + s] = (t < 0 || t >= G) ? AFIS_CORR_NOT_COVERED : AFIS_CORR_NOT_RUN; if (part) part[(size_t)i * S + s] = 0.0f; }
     }
     if (P == 0) return AFIS_OK;
 
@@ -121,13 +122,13 @@ int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<Quer
         // ---- into the caller's order; a scorer the reference does not run keeps its -1 (its slot holds an empty list)
         for (size_t slot = 0; slot < m; ++slot) {
             const int64_t i = dev[c0 + (size_t)slot_of[slot]];
-            for (int sl = 0; sl < 3; ++sl) {
+            for (size_t sl = 0; sl < S; ++sl) {
                 if (!has[(size_t)query[i] * 3 + sl]) continue;
                 int32_t n; memcpy(&n, pin + (corr_n_at - corr_at) + (slot * 3 + sl) * 4, 4);
                 n = std::min(std::max(n, 0), kTopMinu);
-                counts[i * 3 + sl] = n;
-                memcpy(xy + ((size_t)i * 3 + sl) * kTopMinu * 4, pin + (slot * 3 + sl) * kTopMinu * sizeof(short4), (size_t)n * sizeof(short4));
-                if (part) memcpy(part + i * 3 + sl, pin + (parts_at - corr_at) + (slot * 4 + sl) * 4, 4);
+                counts[(size_t)i * S + sl] = n;
+                memcpy(xy + ((size_t)i * S + sl) * kTopMinu * 4, pin + (slot * 3 + sl) * kTopMinu * sizeof(short4), (size_t)n * sizeof(short4));
+                if (part) memcpy(part + (size_t)i * S + sl, pin + (parts_at - corr_at) + (slot * 4 + sl) * 4, 4);
             }
         }
     }

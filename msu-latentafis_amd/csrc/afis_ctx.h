@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -191,6 +191,9 @@ struct afis_ctx : Shard {
     int64_t weighted_fold_us = 0;        // option weighted_fold_us (read-only): device time of that call's k_fold_templates launches, HIP events around each, summed over the batches
     int64_t print_gather_us = 0;         // option print_gather_us (read-only): device time of the last afis_search_prints' gather launches (print_queries.hip), HIP events around each group's, summed
     int64_t print_h2d_bytes = 0;         // option print_h2d_bytes (read-only): bytes that call handed to host-to-device copies (the groups' tables and the fold's), counted where the copies are issued
+    int print_pairs_batch_prints = 0;    // option print_pairs_batch_prints: query prints per batch (one temporary handle) of afis_score_print_pairs / afis_correspondences_print_pairs at most; 0 = as many as an eighth of the group budget holds the views of
+    int64_t print_pairs_us = 0;          // option print_pairs_us (read-only): device time of the last such call's launches, gathers included, summed over batches and chunks
+    int64_t print_pairs_query_prints = 0;   // option print_pairs_query_prints (read-only): distinct query prints that call gathered
     DevBuf casc_buf, casc_slab;          // afis_search_cascade: the kept lists, the second stage's pair tables, parts and scores, one chunk's dense row maxima (afis_cascade.cpp has the layout), and the texture list kernel's slab for a chunk's launches; the combined matrix is built in elig_scores and swapped in as afis_search_eligible's is
     int cascade_pairs_per_launch = kCascadePairsPerLaunch;   // option cascade_pairs_per_launch: pairs per chunk of that call's second stage at most
     int64_t cascade_stage1_us = 0, cascade_select_us = 0, cascade_stage2_us = 0;   // options of those names (read-only): device time of the last afis_search_cascade's three parts, each from its own pair of HIP events
@@ -368,7 +371,9 @@ int upload_queries(afis_ctx* ctx, const afis_template_view* queries, int n_q, in
 // ... and its sibling for query groups that are not made of views: the same cuts from the queries' texture rows (rows [n_q + 1], prefix sums), every group made by
 // `build` (first query, queries, the group to fill, the handle's status list to append to).  afis_search_prints fills its groups on the device through it (afis_prints.cpp).
 typedef std::function<int(int, int, QueryGroup&, std::vector<int32_t>&)> QueryGroupBuilder;
-int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build) __attribute__((visibility("hidden")));
+// keep_last_search: drain_abandoned's (the pair calls for prints build their handles without invalidating the last search's matrix).
+int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build,
+                        bool keep_last_search = false) __attribute__((visibility("hidden")));
 // The batches of afis_search_weighted and afis_search_prints: queries [q0, q1) with pseudo-queries [p0, p1) of the call's numbering, cut at query boundaries — at most
 // `cap` pseudo-queries; a query with more than that is a batch of its own, a query without pseudo-queries joins the batch that is open.
 struct PseudoBatch { int q0, q1; int64_t p0, p1; };
@@ -395,11 +400,25 @@ std::vector<int32_t> resident_tile_offsets(const afis_ctx* ctx) __attribute__((v
 int prepare_print_group(afis_ctx* ctx, const std::vector<int32_t>& res_tile, const int32_t* local, const uint8_t* use_minu, const uint8_t* use_tex, int n, QueryGroup& grp,
                         PrintGroupPlan& plan, std::vector<int32_t>& status_out) __attribute__((visibility("hidden")));
 int queue_print_group(afis_ctx* ctx, const QueryGroup& grp, const PrintGroupPlan& plan, int64_t* h2d_bytes, hipEvent_t before_gather = nullptr, hipEvent_t after_gather = nullptr) __attribute__((visibility("hidden")));
+// A temporary query handle of n prints' views (afis_search_prints' batches, the batches of the pair calls for prints): the launch groups cut by upload_query_groups from
+// the texture rows gathered, every group prepared, its tables and gather queued, then ONE bounded wait on the context's stream.  local / use_minu / use_tex [n] as
+// prepare_print_group's; plans: the host's copies of the groups' tables, the caller's to keep until the device is known idle (a timed-out copy may still read them);
+// *h2d_bytes and *gather_us grow by the bytes handed to copies and the device time of the gathers.  *q is the caller's to free (afis_queries_free), after a failure too.
+int build_print_queries(afis_ctx* ctx, const char* who, const std::vector<int32_t>& res_tile, const int32_t* local, const uint8_t* use_minu, const uint8_t* use_tex, int n,
+                        bool keep_last_search, std::vector<PrintGroupPlan>& plans, afis_queries** q, int64_t* h2d_bytes, int64_t* gather_us) __attribute__((visibility("hidden")));
 // afis_corr.cpp
 // afis_correspondences_pairs behind its argument checks, and what afis_correspondences runs for its one latent: the pairs (query[i], idx[i]) of the query groups `groups`
-// (n_q queries in all, status per query) against the resident shard.  part may be NULL.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.
+// (n_q queries in all, status per query) against the resident shard.  part may be NULL.  out_slots 1 (afis_correspondences_print_pairs): counts [n_pairs], xy [n_pairs][120][4]
+// and part [n_pairs] hold selected template 0 alone.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.
 int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
-                          const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part) __attribute__((visibility("hidden")));
+                          const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part, int out_slots = 3) __attribute__((visibility("hidden")));
+// afis_pairs.cpp
+// afis_score_pairs behind its argument checks: the pairs (query[i], idx[i]) of the handle q against the resident shard.  The caller has drained the context.
+// fold != NULL (afis_score_print_pairs): q's queries are prints' views; w_minu / w_tex [n_pairs] are the pairs' weights — zero where the query print does not hold the
+// template — the fusion is launch_fold_print_pairs and parts is [n_pairs][2].  Counts its device time in ctx->score_pairs_us.  Hidden, as rank_subjects below.
+struct PrintPairWeights { const float* w_minu; const float* w_tex; };
+int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs, const int32_t* query, const int64_t* idx, int32_t* status, float* score, float* parts,
+                const PrintPairWeights* fold = nullptr) __attribute__((visibility("hidden")));
 // afis_subjects.cpp
 void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
 // afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.

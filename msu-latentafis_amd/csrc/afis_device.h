@@ -347,6 +347,10 @@ hipError_t launch_expand_rows(const float* cls, int n_c, int m, const int32_t* i
 // w [n_pseudo][4] the weights aligned to the part slots (0 = the slot is not summed); out[q][g] = -1 where status != 0 or empty[g], else the fp64 sum of weight x part
 // over slots 0..2 of the query's pseudo-queries in order, then over slot 3 of its first n_at, converted once.  Every word of out is written once
 hipError_t launch_fold_templates(const float* parts, const int32_t* qd, const float* w, const uint8_t* empty, int nq, int G, float* out, hipStream_t stream);
+// afis_score_print_pairs (template_fold.hip): the fold of n_pairs pair slots whose latent side is a print's view — parts [n_pairs][4] (16-byte aligned; slot 0 the
+// minutiae template's part, slot 3 the texture template's), w [n_pairs][2] (8-byte aligned) the slot's weights (w_minu, w_tex), zero = not active: score[p] = -1 where
+// neither is active, else (float) of the fp64 sum w_minu x parts[p][0] then w_tex x parts[p][3] over the active ones; +0.0f is stored over an inactive part
+hipError_t launch_fold_print_pairs(float* parts, const float* w, size_t n_pairs, float* score, hipStream_t stream);
 // afis_search_prints (print_queries.hip): the arrays of a query group — q's lm_xy, lm_ori, lm_des, lm_frag, lt_xy, lt_ori, lt_des, allocated, the 4-byte ones in whole
 // 16-byte words — filled from the resident shard g on the device.  q's tables are on the device already: pseudo-query p is a print whose minutiae template fills slot 0
 // (entry 3 p of lm_off / lm_tile_off; entries 3 p + 1, 3 p + 2 are empty ranges) and whose texture template fills lt_off's entry p.  first_minu / first_tile / first_tex

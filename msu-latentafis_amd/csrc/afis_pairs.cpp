@@ -11,6 +11,7 @@
 // for a scorer the reference does not run (k_minu_cands: nL <= 0 || nR <= 0; k_graph_minutiae: num <= 0), and such a pair still has a texture score.
 // The last search's matrix is neither written nor invalidated: the call uses buffers of its own, the scratch and the slab of the minutiae stage, which nothing outlives, and
 // the list counters, which every launcher resets.
+// afis_score_print_pairs (afis_print_pairs.cpp) drives the same function over temporary handles of prints' views, with the fold of a print pair as the fuse step.
 #include "afis_ctx.h"
 #include "pair_tables.h"
 
@@ -20,12 +21,17 @@ using namespace afis;
 
 static_assert(kScorePairsPerLaunch == AFIS_SCORE_PAIRS_PER_LAUNCH, "option score_pairs_per_launch's default is the header's");
 
-namespace {
+namespace afis {
 
-inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+static inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 
-int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs, const int32_t* query, const int64_t* idx, int32_t* status, float* score, float* parts)
+// fold == NULL: afis_score_pairs — the fusion is fuse_cell, parts is [n_pairs][4].  fold != NULL: afis_score_print_pairs (afis_print_pairs.cpp) — the handle's queries are
+// prints' views, the fusion is the weighted fold of a print pair (template_fold.hip::k_fold_print_pairs) with the pair's two weights, uploaded in slot order beside the
+// chunk's tables, and parts is [n_pairs][2]: the minutiae template's part and the texture template's, +0.0f where the pair's weight is zero.
+int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs, const int32_t* query, const int64_t* idx, int32_t* status, float* score, float* parts,
+                const PrintPairWeights* fold)
 {
+    const size_t part_w = fold ? 2 : 4;                                    // floats of parts per pair in the caller's array
     const std::string w(who);
     const std::vector<QueryGroup>& groups = q->groups;
     const int64_t G = ctx->gal.G, base = ctx->index_base;
@@ -53,9 +59,10 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
     const size_t Lp = (size_t)lt_pad;
     const size_t cands_at = 0, corr_at = up256(cands_at + P * 3 * kTopMinu * sizeof(MinuCand)), corr_n_at = up256(corr_at + P * 3 * kTopMinu * sizeof(short4)), cand_n_at = up256(corr_n_at + P * 3 * 4),
                  rmv_at = up256(cand_n_at + P * 3 * 4), rma_at = up256(rmv_at + P * Lp * 4), parts_at = up256(rma_at + P * Lp * 4), score_at = parts_at + P * 16, tab_at = up256(score_at + P * 4),
-                 tab_ints = 4 * P + n_grp, buf_bytes = tab_at + tab_ints * 4;
+                 tab_ints = 4 * P + n_grp, w_at = (tab_ints + 1) / 2 * 2,           // (the weights of a print pair: [P][2] floats behind the tables, 8-byte aligned)
+                 all_ints = fold ? w_at + 2 * P : tab_ints, buf_bytes = tab_at + all_ints * 4;
     const size_t back_bytes = P * 20;                                     // parts | scores: what returns, through the pinned buffer
-    const size_t pin_tab_at = up256(back_bytes), pin_bytes = pin_tab_at + tab_ints * 4;   // ... behind them a chunk's tables on their way up: pinned memory of the context, so that
+    const size_t pin_tab_at = up256(back_bytes), pin_bytes = pin_tab_at + all_ints * 4;   // ... behind them a chunk's tables on their way up: pinned memory of the context, so that
                                                                           // an early return leaves nothing queued that reads memory of this call
     static_assert(sizeof(MinuCand) == 8 && sizeof(short4) == 8, "5.8 KB per pair");
     size_t per_wg = 0; int n_wg = 1;
@@ -79,7 +86,7 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
         const bool covered = t >= 0 && t < G;
         status[i] = covered ? AFIS_PAIR_OK : AFIS_PAIR_NOT_COVERED;
         score[i] = covered ? -1.0f : -std::numeric_limits<float>::infinity();
-        if (parts) for (int s = 0; s < 4; ++s) parts[i * 4 + s] = 0.0f;
+        if (parts) for (size_t s = 0; s < part_w; ++s) parts[(size_t)i * part_w + s] = 0.0f;
     }
     if (P == 0) return AFIS_OK;
 
@@ -97,6 +104,14 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
         Events ev{2};
         for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
         HIPCHK(ctx, hipMemcpyAsync(d + tab_at, tab, (2 * m + n_grp + 2 * n_seg) * 4, hipMemcpyHostToDevice, s));
+        if (fold) {                                                         // the slots' weights, in slot order
+            float* const w = reinterpret_cast<float*>(tab + w_at);
+            for (size_t slot = 0; slot < m; ++slot) {
+                const int64_t i = dev[c0 + (size_t)t.slot_of[slot]];
+                w[2 * slot] = fold->w_minu[i]; w[2 * slot + 1] = fold->w_tex[i];
+            }
+            HIPCHK(ctx, hipMemcpyAsync(d + tab_at + w_at * 4, w, m * 8, hipMemcpyHostToDevice, s));
+        }
         HIPCHK(ctx, hipEventRecord(ev[0], s));
         for (size_t gi = 0; gi < n_grp; ++gi) {
             const size_t b = t.first[gi]; const int n = (int)(t.first[gi + 1] - b);
@@ -114,7 +129,8 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
                                                     ctx->minu_slab.p, ctx->minu_slab.bytes, ctx->s89_tie_order, s));
             HIPCHK(ctx, launch_adc_pairs(qd, ctx->gal, ctx->codewords.as<float>(), d_tab, d_seg, (int)(t.seg_first[gi + 1] - t.seg_first[gi]), rm_val, rm_arg, s));
             HIPCHK(ctx, launch_graph_texture_pairs(qd, ctx->gal, d_tab, n, ctx->table.as<float>(), rm_val, rm_arg, g_parts, ctx->pair_tex_slab.p, ctx->pair_tex_slab.bytes, ctx->s89_tie_order, s));
-            HIPCHK(ctx, launch_fuse_pairs(qd, ctx->gal, d_tab, n, g_parts, (float*)(d + score_at) + b, s));
+            if (fold) HIPCHK(ctx, launch_fold_print_pairs(g_parts, (const float*)(d + tab_at + w_at * 4) + 2 * b, (size_t)n, (float*)(d + score_at) + b, s));
+            else HIPCHK(ctx, launch_fuse_pairs(qd, ctx->gal, d_tab, n, g_parts, (float*)(d + score_at) + b, s));
         }
         HIPCHK(ctx, hipEventRecord(ev[1], s));
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d + parts_at, back_bytes, hipMemcpyDeviceToHost, s));
@@ -125,13 +141,14 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
         for (size_t slot = 0; slot < m; ++slot) {
             const int64_t i = dev[c0 + (size_t)t.slot_of[slot]];
             memcpy(score + i, pin + P * 16 + slot * 4, 4);
-            if (parts) memcpy(parts + i * 4, pin + slot * 16, 16);
+            if (parts && !fold) memcpy(parts + i * 4, pin + slot * 16, 16);
+            if (parts && fold) { memcpy(parts + i * 2, pin + slot * 16, 4); memcpy(parts + i * 2 + 1, pin + slot * 16 + 12, 4); }
         }
     }
     return AFIS_OK;
 }
 
-}  // namespace
+}  // namespace afis
 
 extern "C" {
 
@@ -145,7 +162,7 @@ int afis_score_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs, const int3
     if (n_pairs == 0) return AFIS_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     AFISCHK(drain_abandoned(ctx, true));                                   // the last search's matrix stays rankable
-    return score_pairs(ctx, who, q, n_pairs, query, idx, status, score, parts);
+    return score_pairs(ctx, who, q, n_pairs, query, idx, status, score, parts, nullptr);
 }
 
 }  // extern "C"

@@ -87,17 +87,44 @@ int queue_print_group(afis_ctx* ctx, const QueryGroup& grp, const PrintGroupPlan
     return AFIS_OK;
 }
 
+namespace {
+struct EventList {                                                          // two events per launch group of a batch, destroyed with the batch
+    std::vector<hipEvent_t> e;
+    ~EventList() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+}  // namespace
+
+int build_print_queries(afis_ctx* ctx, const char* who, const std::vector<int32_t>& res_tile, const int32_t* local, const uint8_t* use_minu, const uint8_t* use_tex, int n,
+                        bool keep_last_search, std::vector<PrintGroupPlan>& plans, afis_queries** q, int64_t* h2d_bytes, int64_t* gather_us)
+{
+    std::vector<long long> rows(1, 0);
+    for (int p = 0; p < n; ++p) rows.push_back(rows.back() + (use_tex[p] ? ctx->res_to[(size_t)local[p] + 1] - ctx->res_to[(size_t)local[p]] : 0));
+    // the launch groups: cut as upload_queries cuts them, every DevBuf sized — then the tables and the gathers queued group after group
+    plans.clear();
+    AFISCHK(upload_query_groups(ctx, rows, n, 0, q, [&](int g0, int m, QueryGroup& grp, std::vector<int32_t>& status) {
+        plans.emplace_back();
+        return prepare_print_group(ctx, res_tile, local + g0, use_minu + g0, use_tex + g0, m, grp, plans.back(), status);
+    }, keep_last_search));
+    EventList gev;
+    gev.e.assign((*q)->groups.size() * 2, nullptr);
+    for (hipEvent_t& e : gev.e) HIPCHK(ctx, hipEventCreate(&e));
+    for (size_t gi = 0; gi < (*q)->groups.size(); ++gi) AFISCHK(queue_print_group(ctx, (*q)->groups[gi], plans[gi], h2d_bytes, gev.e[2 * gi], gev.e[2 * gi + 1]));
+    // the bounded wait: the groups are what upload_queries would have left — complete — before anything sizes its buffers on an idle device
+    AFISCHK(wait_streams(ctx, {ctx->stream}, who));
+    for (size_t gi = 0; gi < (*q)->groups.size(); ++gi) {
+        float ms = 0.0f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, gev.e[2 * gi], gev.e[2 * gi + 1]));
+        *gather_us += (int64_t)((double)ms * 1000.0 + 0.5);
+    }
+    return AFIS_OK;
+}
+
 }  // namespace afis
 
 namespace {
 
 // one query of the call: its print (shard-local), what of it is active, and its pseudo-query (n_pq is 0 or 1)
 struct PQuery { int32_t local; bool am, at; int n_pq; };
-
-struct EventList {                                                          // two events per launch group of a batch, destroyed with the batch
-    std::vector<hipEvent_t> e;
-    ~EventList() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // Everything of the call that touches the device.  What it leaves in ctx->elig_scores / ctx->wt_tab after a failure is the caller's to release; `plans` (the host's
 // copies of tables a copy may still read) lives in the caller, beyond its bounded wait.
@@ -126,11 +153,10 @@ int search_batches(afis_ctx* ctx, afis_subset* sub, const std::vector<PQuery>& p
     int64_t most_pairs = -1, fold_us = 0, gather_us = 0, h2d = 0, n_pseudo = 0;
     std::vector<int32_t> local;
     std::vector<uint8_t> use_m, use_t;
-    std::vector<long long> rows;
     for (const PseudoBatch& b : batches) {
         const int nq_b = b.q1 - b.q0;
         const int np_b = (int)(b.p1 - b.p0);
-        local.clear(); use_m.clear(); use_t.clear(); rows.assign(1, 0);
+        local.clear(); use_m.clear(); use_t.clear();
         fold_tab.assign((size_t)nq_b * 4 + (size_t)np_b * 4, 0);           // qd [nq_b][4] int32 | wt [np_b][4] float, as the weighted search's
         float* const wt = reinterpret_cast<float*>(fold_tab.data() + (size_t)nq_b * 4);
         for (int i = b.q0; i < b.q1; ++i) {
@@ -140,30 +166,12 @@ int search_batches(afis_ctx* ctx, afis_subset* sub, const std::vector<PQuery>& p
             if (q.n_pq == 0) continue;
             wt[local.size() * 4 + 0] = q.am ? w_minu[i] : 0.0f; wt[local.size() * 4 + 3] = q.at ? w_tex[i] : 0.0f;
             local.push_back(q.local); use_m.push_back(q.am); use_t.push_back(q.at);
-            rows.push_back(rows.back() + (q.at ? ctx->res_to[(size_t)q.local + 1] - ctx->res_to[(size_t)q.local] : 0));
         }
         afis_queries* q = nullptr;
         struct FreeQ { afis_ctx* c; afis_queries** q; ~FreeQ() { afis_queries_free(c, *q); } } free_q{ctx, &q};
         if (np_b > 0) {
-            // the batch's launch groups: cut as upload_queries cuts them, every DevBuf sized — then the tables and the gathers queued group after group
-            plans.clear();
-            AFISCHK(upload_query_groups(ctx, rows, np_b, 0, &q, [&](int g0, int n, QueryGroup& grp, std::vector<int32_t>& status) {
-                plans.emplace_back();
-                return prepare_print_group(ctx, res_tile, local.data() + g0, use_m.data() + g0, use_t.data() + g0, n, grp, plans.back(), status);
-            }));
-            EventList gev;
-            gev.e.assign(q->groups.size() * 2, nullptr);
-            for (hipEvent_t& e : gev.e) HIPCHK(ctx, hipEventCreate(&e));
-            for (size_t gi = 0; gi < q->groups.size(); ++gi) {
-                AFISCHK(queue_print_group(ctx, q->groups[gi], plans[gi], &h2d, gev.e[2 * gi], gev.e[2 * gi + 1]));
-            }
-            // the bounded wait: the groups are what upload_queries would have left — complete — before the search sizes its buffers on an idle device
-            AFISCHK(wait_streams(ctx, {s}, "afis_search_prints"));
-            for (size_t gi = 0; gi < q->groups.size(); ++gi) {
-                float ms = 0.0f;
-                HIPCHK(ctx, hipEventElapsedTime(&ms, gev.e[2 * gi], gev.e[2 * gi + 1]));
-                gather_us += (int64_t)((double)ms * 1000.0 + 0.5);
-            }
+            // the batch's temporary handle: launch groups cut, tables and gathers queued, one bounded wait (the pair calls for prints build theirs the same way)
+            AFISCHK(build_print_queries(ctx, "afis_search_prints", res_tile, local.data(), use_m.data(), use_t.data(), np_b, false, plans, &q, &h2d, &gather_us));
             AFISCHK(search_shard(ctx, sh, sub, q, nullptr, nullptr, nullptr, 0, nullptr, nullptr, true));
             ctx->last_search.valid = false;                                 // (a batch's pseudo-query matrix is nobody's to rank)
             add_timing(acc, ctx->timing, most_pairs);

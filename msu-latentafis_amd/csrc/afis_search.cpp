@@ -213,10 +213,10 @@ int build_group(afis_ctx* ctx, const afis_template_view* qs, int nq, QueryGroup&
 // resident shard's size, or the size the handle is reserved for.
 // rows [n_q + 1]: the prefix sums of the queries' texture rows (what the cuts are placed by); build(g0, n, group, status) makes the group of queries [g0, g0 + n) —
 // build_group's upload for latents handed over as views (upload_queries), the device gather of afis_search_prints.
-int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build)
+int upload_query_groups(afis_ctx* ctx, const std::vector<long long>& rows, int n_q, int64_t max_templates, afis_queries** out, const QueryGroupBuilder& build, bool keep_last_search)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    { const int rcd = drain_abandoned(ctx); if (rcd != AFIS_OK) return rcd; }
+    { const int rcd = drain_abandoned(ctx, keep_last_search); if (rcd != AFIS_OK) return rcd; }
     // group size: bounded by the option and by the memory budget of a group's per-pair buffers
     const int64_t G = max_templates > 0 ? max_templates : std::max<int64_t>(1, ctx->gal.G);
     const int64_t by_mem = std::max<int64_t>(0, group_budget_bytes(ctx) - graph_slab_bytes(INT64_C(1) << 40)) / group_bytes_per_query(ctx, G);

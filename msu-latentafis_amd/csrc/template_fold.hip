@@ -15,6 +15,7 @@
 // loop counter only: they are read through const __restrict__ tables as scalar loads.  One (float) conversion, one coalesced 4-byte store; every word of the batch's
 // rows is written exactly once: no memset before the launch, no atomics, no LDS.  Every index into parts and out is a size_t: pseudo-queries x G x 4 may pass 2^31.
 // A grid's second dimension holds 65 535 blocks; more queries than that are walked in a loop.
+// Below it k_fold_print_pairs: the same fold for the pair slots of afis_score_print_pairs, one view of (minutiae, texture) per slot.
 #include "afis_device.h"
 
 namespace afis {
@@ -66,6 +67,39 @@ hipError_t launch_fold_templates(const float* parts, const int32_t* qd, const fl
     if (!qd || !w || !empty || !out || !parts) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(((size_t)G + kFoldThreads - 1) / kFoldThreads), grid_clamp((size_t)nq));
     hipLaunchKernelGGL(k_fold_templates, grid, dim3(kFoldThreads), 0, stream, (const float4*)parts, (const int4*)qd, (const float4*)w, empty, nq, G, out);
+    return hipGetLastError();
+}
+
+// The fold of a PRINT PAIR (afis_print_pairs.cpp: afis_score_print_pairs): the pair calls keep one float4 of parts per pair slot, and a print's view has its minutiae
+// template in slot 0 and its texture template in slot 3.  With the slot's two weights (w_minu, w_tex) — the host has written a zero where the query print does not hold
+// the template, so "active" is w != 0.0f — the score is k_fold_templates' for one pseudo-query of that view:
+//   score[p] = -1                                    where nothing is active
+//            = (float)acc                            otherwise: double acc = +0.0; minutiae active: acc = acc + (double)w_minu * (double)parts[p].x; then texture active:
+//                                                    acc = acc + (double)w_tex * (double)parts[p].w
+// and +0.0f is stored over an inactive part, so that the copy back is final.  Both products are formed whether used or not and left out by a select, as above.
+// One thread per pair slot, a 16-byte and an 8-byte load, a 16-byte and a 4-byte store; per-thread data only: nothing here is uniform, so nothing goes through the scalar
+// path.  No LDS, and no word is touched by two threads; every index is a size_t; a one-dimensional grid of at most 65 535 workgroups strides over longer lists.
+__global__ __launch_bounds__(kFoldThreads) void k_fold_print_pairs(float4* parts, const float2* __restrict__ w, size_t n, float* __restrict__ score)
+{
+    const size_t stride = (size_t)gridDim.x * kFoldThreads;
+    for (size_t p = (size_t)blockIdx.x * kFoldThreads + threadIdx.x; p < n; p += stride) {
+        const float4 v = parts[p];
+        const float2 ww = w[p];
+        const bool am = ww.x != 0.0f, at = ww.y != 0.0f;
+        const double pm = (double)ww.x * (double)v.x, pt = (double)ww.y * (double)v.w;
+        double acc = 0.0;
+        acc = am ? acc + pm : acc;
+        acc = at ? acc + pt : acc;
+        score[p] = am || at ? (float)acc : -1.0f;
+        parts[p] = make_float4(am ? v.x : 0.0f, v.y, v.z, at ? v.w : 0.0f);
+    }
+}
+
+hipError_t launch_fold_print_pairs(float* parts, const float* w, size_t n_pairs, float* score, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipSuccess;
+    if (!parts || !w || !score || ((uintptr_t)parts & 15) || ((uintptr_t)w & 7)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fold_print_pairs, dim3(grid_clamp((n_pairs + kFoldThreads - 1) / kFoldThreads)), dim3(kFoldThreads), 0, stream, (float4*)parts, (const float2*)w, n_pairs, score);
     return hipGetLastError();
 }
 

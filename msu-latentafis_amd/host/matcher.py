@@ -71,7 +71,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_search_cascade",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -153,6 +153,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
     if hasattr(lib, "afis_score_pairs"):                                # pair scoring; absent from older builds compared by tools/lib_ab.py
         lib.afis_score_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, fp, fp]
+    if hasattr(lib, "afis_score_print_pairs"):                          # print pairs; absent from older builds compared by tools/lib_ab.py
+        lib.afis_score_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, fp, fp, i32p, fp, fp]
+        lib.afis_correspondences_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, i32p, C.POINTER(C.c_int16), fp]
     if hasattr(lib, "afis_search_cascade"):                             # cascade search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_cascade.argtypes = [vp, vp, C.c_int, fp, i32p, i64p, i64p, fp]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
@@ -899,6 +902,44 @@ class Matcher:
         self._chk(self.lib.afis_score_pairs(self.ctx, qhandle[0], n, _ptr(qa, C.c_int32) if n else None, _ptr(ia, C.c_int64) if n else None,
                                             _ptr(status, C.c_int32), _ptr(score, C.c_float), _ptr(parts, C.c_float) if want_parts else None))
         return {"status": status[:n], "score": score[:n], "parts": parts[:n] if want_parts else None}
+
+    # ---- print pairs: scores and correspondences of (resident print, resident print) pairs ---------------------------
+    def score_print_pairs(self, a_idx, b_idx, w_minu, w_tex, want_parts: bool = False):
+        """The weighted scores of a LIST of (query print, column print) pairs of the resident shard without a matrix (afis_score_print_pairs): pair i is (a_idx[i],
+        b_idx[i]), both GLOBAL indices of the shard as it stands; any order, repeats allowed, (a, a) an ordinary pair; w_minu / w_tex one weight per pair (a scalar is
+        every pair's).  -> {"status": [n] int32 — PAIR_OK, or PAIR_NOT_COVERED where this shard does not hold both prints (the -1 padding of the list calls included)
+        —, "score": [n] float32, search_prints()' cell for query a, column b and the pair's weights bit for bit (-1 for an empty or removed b and where nothing of a is
+        active; -inf where not covered), "parts": [n][2] float32 with want_parts — the minutiae and the texture entry of the print's view against b, +0.0 where not
+        active —, else None}.  The last search's matrix stays rankable.  get_option("print_pairs_us"), get_option("print_pairs_query_prints")."""
+        a = np.ascontiguousarray(np.asarray(a_idx, np.int64).reshape(-1)); b = np.ascontiguousarray(np.asarray(b_idx, np.int64).reshape(-1))
+        if len(a) != len(b):
+            raise ValueError("score_print_pairs: a_idx and b_idx must have one length")
+        n = len(a)
+        wm = np.ascontiguousarray(np.broadcast_to(np.asarray(w_minu, np.float32), (n,)))
+        wt = np.ascontiguousarray(np.broadcast_to(np.asarray(w_tex, np.float32), (n,)))
+        status = np.zeros(max(n, 1), np.int32); score = np.zeros(max(n, 1), np.float32)
+        parts = np.zeros((max(n, 1), 2), np.float32) if want_parts else None
+        self._chk(self.lib.afis_score_print_pairs(self.ctx, n, _ptr(a, C.c_int64) if n else None, _ptr(b, C.c_int64) if n else None,
+                                                  _ptr(wm, C.c_float) if n else None, _ptr(wt, C.c_float) if n else None,
+                                                  _ptr(status, C.c_int32), _ptr(score, C.c_float), _ptr(parts, C.c_float) if want_parts else None))
+        return {"status": status[:n], "score": score[:n], "parts": parts[:n] if want_parts else None}
+
+    def correspondences_print_pairs(self, a_idx, b_idx, want_parts: bool = False):
+        """The surviving minutiae correspondences of a LIST of (query print, column print) pairs of the resident shard (afis_correspondences_print_pairs); the pairs as
+        score_print_pairs'.  -> {"counts": [n] int32, "xy": [n][120][4] int16 = (a's x, a's y, b's x, b's y), rows beyond counts zero, "corr": per pair an array
+        [n_s][4] — None where a or b holds no minutiae template (counts -1), the marker NOT_COVERED where this shard does not hold both prints (counts -2) —, "part":
+        [n] float32 with want_parts, the scorer's return value (score_print_pairs' parts[i][0] bit for bit where counts >= 0, +0.0 elsewhere), else None}.  The last
+        search's matrix stays rankable."""
+        a = np.ascontiguousarray(np.asarray(a_idx, np.int64).reshape(-1)); b = np.ascontiguousarray(np.asarray(b_idx, np.int64).reshape(-1))
+        if len(a) != len(b):
+            raise ValueError("correspondences_print_pairs: a_idx and b_idx must have one length")
+        n = len(a)
+        counts = np.zeros(max(n, 1), np.int32); xy = np.zeros((max(n, 1), 120, 4), np.int16)
+        part = np.zeros(max(n, 1), np.float32) if want_parts else None
+        self._chk(self.lib.afis_correspondences_print_pairs(self.ctx, n, _ptr(a, C.c_int64) if n else None, _ptr(b, C.c_int64) if n else None,
+                                                            _ptr(counts, C.c_int32), _ptr(xy, C.c_int16), _ptr(part, C.c_float) if want_parts else None))
+        corr = [xy[i, :counts[i]].copy() if counts[i] >= 0 else (None if counts[i] == CORR_NOT_RUN else NOT_COVERED) for i in range(n)]
+        return {"counts": counts[:n], "xy": xy[:n], "corr": corr, "part": part[:n] if want_parts else None}
 
     def One2One_matching_all_templates(self, latent: FPTemplate):
         """matcher.cpp:339-374 against every gallery template: (query status, rolled status [G], scores [G][n_minu + n_tex])."""

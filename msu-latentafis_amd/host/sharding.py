@@ -302,6 +302,60 @@ def merge_pair_scores(per_rank):
     return {"status": out_st, "score": out_sc, "parts": out_p, "owner": owner}
 
 
+def merge_print_pair_scores(per_rank):
+    """merge_pair_scores for Matcher.score_print_pairs' answers: per_rank a sequence of {"status": [P], "score": [P], "parts": [P, 2] or None}, one pair list handed to
+    every rank.  A pair is covered by the one rank that holds BOTH prints and taken from it, bits as they are; a pair whose prints lie in two shards is covered by no
+    rank and stays AFIS_PAIR_NOT_COVERED / -inf / +0.0 with owner -1.  Returns {"status", "score", "parts" [P, 2] (None unless every rank gave parts), "owner": [P]}.
+    Two ranks covering one pair raise ValueError."""
+    per_rank = list(per_rank)
+    R = len(per_rank)
+    st = np.asarray([np.asarray(r["status"], np.int32).reshape(-1) for r in per_rank], np.int32).reshape(R, -1)
+    sc = np.asarray([np.asarray(r["score"], np.float32).reshape(-1) for r in per_rank], np.float32).reshape(R, -1)
+    if st.shape != sc.shape:
+        raise ValueError("merge_print_pair_scores: status and score are [pairs] on every rank, of one length")
+    P = st.shape[1]
+    with_parts = R > 0 and all(r.get("parts") is not None for r in per_rank)
+    pt = np.asarray([np.asarray(r["parts"], np.float32).reshape(-1, 2) for r in per_rank], np.float32).reshape(R, -1, 2) if with_parts else None
+    if pt is not None and pt.shape != st.shape + (2,):
+        raise ValueError("merge_print_pair_scores: parts is [pairs, 2] on every rank")
+    covered = st == PAIR_OK
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"merge_print_pair_scores: pairs {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    any_owner = covered.any(axis=0) if R else np.zeros(P, bool)
+    owner = np.where(any_owner, covered.argmax(axis=0) if R else 0, -1).astype(np.int64)
+    out_st = np.full(P, PAIR_NOT_COVERED, np.int32); out_sc = np.full(P, -np.inf, np.float32); out_p = np.zeros((P, 2), np.float32) if with_parts else None
+    have = np.flatnonzero(any_owner)
+    out_st[have] = st[owner[have], have]; out_sc[have] = sc[owner[have], have]
+    if with_parts:
+        out_p[have] = pt[owner[have], have]
+    return {"status": out_st, "score": out_sc, "parts": out_p, "owner": owner}
+
+
+def merge_print_correspondences(per_rank_counts, per_rank_xy, per_rank_part=None):
+    """merge_correspondences for Matcher.correspondences_print_pairs' raw arrays: per_rank_counts [R, P], per_rank_xy [R, P, 120, 4], per_rank_part [R, P] or None.  The
+    rank whose count is not AFIS_CORR_NOT_COVERED holds both prints of the pair and the pair is taken from it, bytes as they are.  Returns (counts [P], xy [P, 120, 4],
+    owner [P]) — with per_rank_part also part [P], before owner —: counts AFIS_CORR_NOT_COVERED, xy and part zero, owner -1 for a pair no rank covers (its prints lie in
+    two shards, or in none).  Two ranks covering one pair raise ValueError."""
+    cn = np.asarray(per_rank_counts, np.int32); xy = np.asarray(per_rank_xy, np.int16)
+    if cn.ndim != 2 or xy.shape != cn.shape + (120, 4):
+        raise ValueError("merge_print_correspondences: counts is [ranks, pairs] and xy [ranks, pairs, 120, 4]")
+    pt = None if per_rank_part is None else np.asarray(per_rank_part, np.float32)
+    if pt is not None and pt.shape != cn.shape:
+        raise ValueError("merge_print_correspondences: part is [ranks, pairs], as counts")
+    covered = cn != CORR_NOT_COVERED
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"merge_print_correspondences: pairs {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    P = cn.shape[1]
+    any_owner = covered.any(axis=0) if cn.shape[0] else np.zeros(P, bool)
+    owner = np.where(any_owner, covered.argmax(axis=0) if cn.shape[0] else 0, -1).astype(np.int64)
+    out_c = np.full(P, CORR_NOT_COVERED, np.int32); out_xy = np.zeros((P, 120, 4), np.int16); out_p = np.zeros(P, np.float32)
+    have = np.flatnonzero(any_owner)
+    out_c[have] = cn[owner[have], have]; out_xy[have] = xy[owner[have], have]
+    if pt is not None:
+        out_p[have] = pt[owner[have], have]
+    return (out_c, out_xy, owner) if pt is None else (out_c, out_xy, out_p, owner)
+
+
 def gather_topk(idx: np.ndarray, score: np.ndarray, k: int, device=None, force: bool = False):
     """The one exchange step: all_gather of [Q, kk] (int64 idx, f32 score) from every rank, then merge on every rank.
     Messages are tiny (24 x 12 B per query per rank); this is latency-, not bandwidth-bound."""
