@@ -238,7 +238,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     context.  Several handles may be live at once; afis_destroy releases those that are left.  A handle belongs to the gallery as it was: after an
  *                     appending commit or a removal that changed the shard afis_rank_subjects refuses it with AFIS_ESTATE (afis_subjects_free still works).
  * afis_rank_subjects   ranks the score matrix of the context's LAST search — any of afis_search, afis_search_dat, afis_search_resident, afis_search_subset,
- *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, afis_search_cascade, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
+ *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, afis_search_cascade, afis_search_prints_cascade, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
  *                     search's (AFIS_EINVAL otherwise, as for k <= 0 or a null output).  Per query the k best subjects:
  *                       subject_score  the greatest fused score among the subject's templates that the search covered: all of them for a full search, the listed ones for a
  *                                      subset search (a subject without a listed template does not appear).  An empty or removed entry contributes its -1: a subject all of
@@ -889,6 +889,84 @@ int afis_search_cascade(afis_ctx* ctx, afis_queries* q, int keep,
                         int64_t* n_kept /*[n_q] or NULL*/,
                         int64_t* kept_idx /*[n_q][keep] or NULL*/, float* kept_parts /*[n_q][keep][4] or NULL*/);
 
+/* Print cascade (no reference counterpart): the duplicate check of an enrolment with the texture scorer for the best `keep` columns only.  afis_search_prints pays the
+ * full price of a search for every query print, and nearly all of it is the texture path: a print's view carries about 811 decoded texture rows, more than a latent's.
+ * Rolled against rolled the minutiae scorer is the strong one, and a print's view has ONE minutiae template: afis_search_prints_cascade runs that one scorer for every
+ * (query print, column print) cell of the resident shard, keeps per query the `keep` best columns by that partial score — selected on the device — and runs the texture
+ * scorer for the kept cells only.  The columns are the whole resident shard as it stands; no handle is involved, the call is valid after any gallery edit.
+ *   idx [n_q], w_minu [n_q], w_tex [n_q]   as afis_search_prints', rule for rule: GLOBAL indices (index_base included) in any order, entries may repeat; one weight per
+ *          query for the print's minutiae template and for its texture template, finite and >= 0.  The minutiae term of query q is ACTIVE when the print holds a
+ *          minutiae template and w_minu[q] != 0.0f, the texture term likewise.
+ * keep     1 <= keep <= AFIS_HITS_MAX, anything else is AFIS_EINVAL; n_kept[q] = min(keep, G).
+ * Stage-1 value m(q, t)   the word afis_search_prints writes at (q, t) for the weights (w_minu[q], +0.0f): -1.0f for an empty or removed column; -1.0f for the WHOLE
+ *          ROW when the minutiae term of query q is not active — a print without a minutiae template, an empty or removed print, w_minu[q] == 0 —; otherwise
+ *          (float)(+0.0 + (double)w_minu[q] * (double)v_m).  There is no special case: a row that stage 1 cannot rank is a row of equal keys and keeps its first
+ *          min(keep, G) columns by index.  Such a query belongs to afis_search_prints, not here.
+ * Selection   the rule of afis_search_cascade: per query the kept columns are the first n_kept entries of the list afis_rank_hits(min_score = -INFINITY, cap = keep)
+ *          would give on the matrix of m: rank_key descending, equal keys by ascending GLOBAL index (csrc/rank_order.h).  Every column is an entry; the -1 cells stand
+ *          last.  kept_idx[q] is that list (global indices, index_base included), padded with -1.
+ * Values   a kept cell holds, bit for bit, the word afis_search_prints writes at (q, t) for the weights (w_minu[q], w_tex[q]); every other cell holds the word
+ *          0xffffffff, the "no entry" word (csrc/score_order.h: kNoEntryWord), in the matrix left on the device and in scores [n_q][G] (NULL: not copied).
+ *          kept_parts[q][r][0..1] are the parts afis_score_print_pairs defines for the pair (idx[q], kept_idx[q][r]) with those weights: (v_m if the minutiae term is
+ *          active else +0.0f, v_t if the texture term is active else +0.0f); +0.0f twice where the cell is the -1, and in the padding.  status [n_q] (or NULL) is
+ *          afis_search_prints' for the real weights: AFIS_QUERY_LATENT_EMPTY where nothing is active.  n_kept, kept_idx and kept_parts may each be NULL.  All of it
+ *          under every value of "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9 alike.
+ * The matrix afterwards   after AFIS_OK the context's last-search matrix is this [n_q][G] matrix: a full search's record under afis_search's invalidation rules; the
+ *          call is one of the searches that count, for every ranking call.  It reads as afis_search_cascade's matrix reads: the hit lists, subject hit lists, column
+ *          lists, their _filtered forms and the position calls see the kept cells as the only entries (a mate that stage 1 dropped is AFIS_POS_NO_ENTRY); the CASE
+ *          lists must be read through their _filtered forms; afis_rank_subjects is not in this interface.  A print against itself is an ordinary kept cell: the
+ *          caller takes it out with an exclusion list.  After any return other than AFIS_OK the matrix is invalid and the call holds nothing it allocated.  A
+ *          following afis_search_prints on the same context returns the bytes it returned before.
+ * Arguments   AFIS_EINVAL: a null ctx, n_q < 0, a null idx or weight array with n_q > 0, an index outside the resident shard, a weight that is NaN, infinite or
+ *          negative, keep out of range, n_q x keep or n_q x G beyond what afis_search_cascade takes.  AFIS_ESTATE: a call before the first commit, an index that is
+ *          staged but not committed.  n_q == 0 or G == 0 returns AFIS_OK as afis_search_cascade does (n_kept 0, kept_idx -1, kept_parts +0.0f).  Room — the two
+ *          matrices, the per-part scores of all pseudo-queries [n_pseudo][G][4], the minutiae stage's buffers for the largest launch group, the kept lists and pair
+ *          tables, one chunk's dense row maxima and the texture list kernel's slab — is ensured before anything of the cascade is queued: AFIS_EDEVICE otherwise.
+ *          Host waits are bounded by "search_timeout_s".
+ * Options  "cascade_pairs_per_launch" applies to this call too; results do not depend on it.  "print_cascade_stage1_us", "print_cascade_select_us",
+ *          "print_cascade_stage2_us" (read-only): the device time of the last call's three parts, each from its own pair of HIP events; "print_cascade_kept_pairs"
+ *          (read-only): the pairs its second stage scored.  All four read 0 after a call that failed or was empty.  "print_gather_us" and "print_h2d_bytes" describe
+ *          this call as they describe afis_search_prints (the bytes: the launch groups' tables and the cascade's).
+ * Timing   afis_get_timing* reports stage 1 as the latent cascade does: cands_ms, minu_graph_ms, minu_ms, fuse_ms (k_print_cascade_stage1), total_ms their sum, pairs
+ *          = pseudo-queries x G, launch_groups and the minutiae task counters; the texture fields are 0.
+ * How      csrc/afis_print_cascade.cpp.  One pseudo-query per print with something active, in ONE temporary query handle built as a batch of afis_search_prints is
+ *          (the texture view is gathered only where the texture term is active), which has its own bounded wait; after it the cascade is one launch sequence with one
+ *          wait.  Stage 1 is the minutiae stage of a search, per launch group on the context's stream, unconfined; k_print_cascade_stage1 (csrc/print_cascade.hip)
+ *          writes m from slot 0 of the pseudo-queries' parts.  The selection is k_rank_hits, unchanged.  The second stage's pair tables (csrc/cascade_tables.h, a
+ *          query having pairs when its texture term is active) are uploaded once; k_print_cascade_gather fills them from the kept lists; per chunk and launch group
+ *          k_adc_pairs and k_graph_texture in its pair form; k_print_cascade_finish folds v_m and v_t of every kept cell in fp64 — csrc/print_fold.h, the expression
+ *          of k_fold_templates and k_fold_print_pairs — into the combined matrix, which was filled with the no-entry word first.
+ * Cost     against the full print search — afis_search_prints on the same context, the only route before — on one MI355X, 100 resident prints (of each of 100 synthetic
+ *          latents the first planted mate) x 100 000 prints, weights 1 and 0.3f, interleaved runs, medians of three after a discarded first, device clock
+ *          (profiles/print_cascade_timing.json, tools/print_cascade_timing.py; the host clock, which includes both calls' temporary handles, agrees within 1.5 ms).
+ *          Headline workload: keep 100 — 669.8 ms (stage 1 650.5, selection 0.28, stage 2 19.0) against 2 183.7 ms: 0.31 x; keep 1000 — 783.9 ms (651.1 / 0.30 /
+ *          132.3) against 2 181.1 ms: 0.36 x; keep 4096 — 1 159.9 ms (650.6 / 0.33 / 508.8) against 2 182.6 ms: 0.53 x.  Structured workload: keep 100 — 676.5 ms
+ *          (659.8 / 0.29 / 16.4) against 2 403.6 ms: 0.28 x; keep 1000 — 774.1 ms (659.0 / 0.30 / 114.8) against 2 409.5 ms: 0.32 x; keep 4096 — 1 098.0 ms (659.5 /
+ *          0.33 / 438.0) against 2 401.6 ms: 0.46 x.  Spreads (max - min) at most 1.9 ms for the cascade, 5.7 ms for the full print search; the gather of the handle
+ *          0.10 ms.  Every kept cell bit-equal to the full print search's.
+ *          The estimate this call was proposed with — stage 1 a third of the latent cascade's 801 ms, the whole call 0.15 x at keep 100 — did NOT hold: stage 1 alone
+ *          is 0.30 of the full print search on the headline workload (cands_ms 272, minu_graph_ms 378) and 0.27 on the structured one (274, 385), 0.81 of the latent
+ *          cascade's first stage.  A print's view has one minutiae template where a latent has three, but that template holds about 80 minutiae where each of the
+ *          latent's holds 20 - 60: by the generator's sizes the candidate kernel's similarity cells drop by a third, not by two thirds (cands_ms 272 against the
+ *          latent cascade's 380), and the list kernel's time hardly moves (378 ms against 421).  Stage 2 costs 1.1 - 1.9 us per pair and at keep 4096 is 0.40 -
+ *          0.44 of the call: k_adc_pairs is untuned, as the latent cascade's paragraph says.  Nothing here is tuned.
+ *          What keep costs in accuracy, on these SYNTHETIC galleries (facts about the generator, not about fingerprints; read through afis_rank_positions on both
+ *          matrices with the query's own print excluded): the print mates are the other three planted mates of the query's latent, 300 per workload.  Headline: all
+ *          300 are kept at keep 100, 1000 and 4096.  Structured: 297 are kept at keep 100, 298 at keep 1000 and at 4096 (why the last two are dropped was not
+ *          examined).  On both workloads the 100 mates that stand at rank 1 under afis_search_prints still stand at rank 1 at every keep.  The generator's non-mates
+ *          score next to nothing with the minutiae scorer, so these counts say little about real prints.
+ *          The full search is untouched: tools/lib_ab.py against the parent commit's library, scores bit-identical, this tree's median total_ms 1 880.9 inside the
+ *          parent's steps 1 879.4 .. 1 886.0 (median 1 879.7) — profiles/print_cascade_full_search_ab.txt.
+ * Shards: a print is a query only on the rank that holds it, and every rank keeps `keep` of its OWN shard: the merged lists are a superset of the single-context
+ *          result, as for afis_search_cascade.
+ * Not in this interface: a subset form (the kept lists are global: put a finger restriction on the ranking call, with masks); a keep above AFIS_HITS_MAX; batching over
+ *          queries (everything for all n_q queries is resident at once); the match CLI.  No result of any other search changes because this function exists. */
+int afis_search_prints_cascade(afis_ctx* ctx, const int64_t* idx /*[n_q], GLOBAL*/, int n_q,
+                               const float* w_minu /*[n_q]*/, const float* w_tex /*[n_q]*/, int keep,
+                               float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/,
+                               int64_t* n_kept /*[n_q] or NULL*/, int64_t* kept_idx /*[n_q][keep] or NULL*/,
+                               float* kept_parts /*[n_q][keep][2] or NULL*/);
+
 /* afis_get_timing2 copies min(struct_size, sizeof(afis_timing)) bytes: pass sizeof(afis_timing) of the header the caller was compiled
  * against, so that a library with a longer struct never writes past the caller's.  afis_get_timing (kept for callers of the round-2
  * header) fills only the fields up to `pairs` (48 bytes, the struct of that header); the fields after it need afis_get_timing2. */
@@ -962,7 +1040,12 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "cascade_stage1_us" (read-only): the device time of the last afis_search_cascade's first stage (per launch group the candidate kernel, the minutiae list kernel,
  * k_fuse_stage1); "cascade_select_us" (read-only): of its selection (k_rank_hits); "cascade_stage2_us" (read-only): of its second stage (the no-entry fill,
  * k_cascade_gather, per chunk and launch group k_adc_pairs, k_graph_texture in its pair form, k_fuse_pairs, then k_cascade_scatter) — each from its own pair of HIP
- * events; "cascade_kept_pairs" (read-only): the pairs that second stage scored; all four 0 after a call that failed or was empty. */
+ * events; "cascade_kept_pairs" (read-only): the pairs that second stage scored; all four 0 after a call that failed or was empty.
+ * "print_cascade_stage1_us" (read-only): the device time of the last afis_search_prints_cascade's first stage (per launch group the candidate kernel and the minutiae
+ * list kernel, then k_print_cascade_stage1); "print_cascade_select_us" (read-only): of its selection (k_rank_hits); "print_cascade_stage2_us" (read-only): of its
+ * second stage (the no-entry fill, k_print_cascade_gather, per chunk and launch group k_adc_pairs and k_graph_texture in its pair form, then k_print_cascade_finish) —
+ * each from its own pair of HIP events; "print_cascade_kept_pairs" (read-only): the pairs that second stage scored; all four 0 after a call that failed or was empty.
+ * That call obeys "cascade_pairs_per_launch" and sets "print_gather_us" and "print_h2d_bytes" as afis_search_prints does. */
 int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value);
 
 /* The parity-test taps (stage intermediates: afis_debug_*) are NOT part of this library: they are declared in

@@ -207,6 +207,10 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "cascade_select_us") *value = ctx->cascade_select_us;
     else if (n == "cascade_stage2_us") *value = ctx->cascade_stage2_us;
     else if (n == "cascade_kept_pairs") *value = ctx->cascade_kept_pairs;             // read-only: pairs that call's second stage scored
+    else if (n == "print_cascade_stage1_us") *value = ctx->print_cascade_stage1_us;   // read-only: device time of the last afis_search_prints_cascade's first stage, selection and second stage, each from its own pair of events
+    else if (n == "print_cascade_select_us") *value = ctx->print_cascade_select_us;
+    else if (n == "print_cascade_stage2_us") *value = ctx->print_cascade_stage2_us;
+    else if (n == "print_cascade_kept_pairs") *value = ctx->print_cascade_kept_pairs; // read-only: pairs that call's second stage scored
     else if (n == "mf_stats") *value = ctx->mf_collect_stats;
     else if (n == "rowmax_budget_mb") *value = ctx->rowmax_budget_bytes >> 20;
     else if (n == "lut_dtype") *value = 32;

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones), afis_print_cascade.cpp (print cascade: the same two stages with resident prints as queries) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -198,6 +198,8 @@ struct afis_ctx : Shard {
     int cascade_pairs_per_launch = kCascadePairsPerLaunch;   // option cascade_pairs_per_launch: pairs per chunk of that call's second stage at most
     int64_t cascade_stage1_us = 0, cascade_select_us = 0, cascade_stage2_us = 0;   // options of those names (read-only): device time of the last afis_search_cascade's three parts, each from its own pair of HIP events
     int64_t cascade_kept_pairs = 0;      // option cascade_kept_pairs (read-only): pairs that call's second stage scored
+    int64_t print_cascade_stage1_us = 0, print_cascade_select_us = 0, print_cascade_stage2_us = 0;   // options of those names (read-only): device time of the last afis_search_prints_cascade's three parts, each from its own pair of HIP events; the call builds its lists and tables in casc_buf / casc_slab and its matrix in elig_scores, as afis_search_cascade does
+    int64_t print_cascade_kept_pairs = 0;   // option print_cascade_kept_pairs (read-only): pairs that call's second stage scored
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
     int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)

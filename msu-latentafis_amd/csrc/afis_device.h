@@ -387,4 +387,19 @@ hipError_t launch_debug_graph_arith(unsigned long long* cnt8, hipStream_t stream
 // debug tap: LUT in the reference layout [n][16][256]
 hipError_t launch_lut_reference_layout(const float* des, int n, const float* codewords, float* out, hipStream_t stream);
 
+// afis_search_prints_cascade (afis_print_cascade.cpp, print_cascade.hip): resident prints as queries, the minutiae scorer for every cell, the texture scorer for the
+// `keep` best columns of every query.  A query with something active is one pseudo-query of the temporary handle: q_row [n_q] is its row of parts [n_pseudo][G][4] (-1:
+// none), q_w [n_q][2] (8-byte aligned) its weights (w_minu, w_tex) with a zero where the term is not active.
+// launch_print_cascade_stage1: m [n_q][G] = -1.0f where column g is empty, q_row[q] < 0 or q_w[q][0] == 0, else (float)(+0.0 + (double)w_minu x (double)parts[row][g][0])
+// (print_fold.h); every word written once.  launch_print_cascade_gather: launch_cascade_gather's tables for the queries whose slot range (q_slot) is not empty, the
+// pair's query being q_row[q] - piece_p0[piece] (piece_p0 [n_pieces]: the first pseudo-query of the piece's launch group); no parts are copied.
+// launch_print_cascade_finish: for every kept (q, t) the cell's word -> out[q][t] and (v_m, v_t) -> kept_parts[q][rank] ([n_q][keep][2], 8-byte aligned, zeroed by the
+// caller): v_m = parts[row][t][0] where the minutiae term is active, v_t = pair_parts[slot][3] where the texture term is; -1.0f and +0.0f twice for an empty column or a
+// query with nothing active; nothing else of out is written.
+hipError_t launch_print_cascade_stage1(const float* parts, const int32_t* q_row, const float* q_w, const uint8_t* empty, int n_q, int G, float* m, hipStream_t stream);
+hipError_t launch_print_cascade_gather(int n_q, int G, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot, const int32_t* piece_first,
+                                       int n_pieces, const int32_t* piece_p0, const int32_t* q_row, int32_t* tab, hipStream_t stream);
+hipError_t launch_print_cascade_finish(int n_q, int G, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot, const int32_t* q_row,
+                                       const float* q_w, const uint8_t* empty, const float* parts, const float* pair_parts, float* out, float* kept_parts, hipStream_t stream);
+
 }  // namespace afis

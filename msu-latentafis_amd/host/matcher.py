@@ -71,7 +71,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -158,6 +158,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_correspondences_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, i32p, C.POINTER(C.c_int16), fp]
     if hasattr(lib, "afis_search_cascade"):                             # cascade search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_cascade.argtypes = [vp, vp, C.c_int, fp, i32p, i64p, i64p, fp]
+    if hasattr(lib, "afis_search_prints_cascade"):                      # print cascade; absent from older builds compared by tools/lib_ab.py
+        lib.afis_search_prints_cascade.argtypes = [vp, i64p, C.c_int, fp, fp, C.c_int, fp, i32p, i64p, i64p, fp]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
     lib.afis_pq_encode.argtypes = [vp, fp, C.c_int64, C.POINTER(C.c_uint8)]
@@ -718,6 +720,34 @@ class Matcher:
         self._chk(self.lib.afis_search_cascade(self.ctx, h, keep, _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32),
                                                _ptr(n_kept, C.c_int64) if want_kept else None, _ptr(kept_idx, C.c_int64) if want_kept else None,
                                                _ptr(kept_parts, C.c_float) if want_kept else None))
+        self.last_n_q = n; self.last_n_templates = G
+        return {"scores": scores, "status": status, "n_kept": n_kept, "kept_idx": kept_idx, "kept_parts": kept_parts}
+
+    # ---- print cascade: resident prints as queries, minutiae for every column, texture for the best `keep` only ----------
+    def search_prints_cascade(self, idx, w_minu, w_tex, keep: int, want_scores: bool = True, want_kept: bool = True):
+        """afis_search_prints_cascade: search_prints() with a minutiae first stage.  idx [n_q] global indices of the resident shard, w_minu / w_tex one weight per query
+        (a scalar is every query's).  The print's minutiae scorer runs for every column, per query the `keep` best columns by that partial score are selected on the
+        device, the texture scorer runs for those only.  A kept cell is bit for bit search_prints()' for the same weights; every other cell of "scores" [n_q][G] holds
+        the no-entry word 0xffffffff.  want_kept: "n_kept" [n_q], "kept_idx" [n_q][keep] (global indices in stage-1 rank order, -1 padded) and "kept_parts"
+        [n_q][keep][2] = score_print_pairs()' parts of the kept pairs.  The matrix left on the device reads as search_cascade's: rank_hits, rank_positions (a column
+        stage 1 dropped is POS_NO_ENTRY) and the _filtered calls see the kept cells only; take the self cell out with an exclusion list.
+        get_option("print_cascade_stage1_us" / "print_cascade_select_us" / "print_cascade_stage2_us" / "print_cascade_kept_pairs"); set_option("cascade_pairs_per_launch", n)."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        n = len(a)
+        wm = np.ascontiguousarray(np.broadcast_to(np.asarray(w_minu, np.float32), (n,)))
+        wt = np.ascontiguousarray(np.broadcast_to(np.asarray(w_tex, np.float32), (n,)))
+        keep = int(keep)
+        G = self.resident_size
+        wide = max(keep, 1)
+        scores = np.empty((n, G), np.float32) if want_scores else None
+        status = np.zeros(n, np.int32)
+        n_kept = np.zeros(n, np.int64) if want_kept else None
+        kept_idx = np.full((n, wide), -1, np.int64) if want_kept else None
+        kept_parts = np.zeros((n, wide, 2), np.float32) if want_kept else None
+        self._chk(self.lib.afis_search_prints_cascade(self.ctx, _ptr(a, C.c_int64) if n else None, n, _ptr(wm, C.c_float) if n else None, _ptr(wt, C.c_float) if n else None,
+                                                      keep, _ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32),
+                                                      _ptr(n_kept, C.c_int64) if want_kept else None, _ptr(kept_idx, C.c_int64) if want_kept else None,
+                                                      _ptr(kept_parts, C.c_float) if want_kept else None))
         self.last_n_q = n; self.last_n_templates = G
         return {"scores": scores, "status": status, "n_kept": n_kept, "kept_idx": kept_idx, "kept_parts": kept_parts}
 
