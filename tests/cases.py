@@ -782,10 +782,11 @@ def _list_texture(rng, cb, geometry, N):
             T.TextureTemplate(rx.astype(np.int16), ry.astype(np.int16), rori, codes=codes))
 
 
-def _list_minutiae(rng, n_r, n_l3, jitter):
+def _list_minutiae(rng, n_r, n_l3, jitter, second_jitter=None):
     """28 latent minutiae templates (the selected ones hold the first n_l3[i] points of a pool, the others two) and a rolled one of the pool's first n_r points, moved and
     jittered: min(n_l, n_r) true correspondences per list.  Pool points sit on a 110-px grid (+-8): far enough apart for the jitter not to turn the line between two of them, and spread widely enough
-    for two FALSE correspondences to agree in distance (within 30 px) only rarely — the true ones have to win the power iteration even where there are only two or three."""
+    for two FALSE correspondences to agree in distance (within 30 px) only rarely — the true ones have to win the power iteration even where there are only two or three.
+    second_jitter: a third value, a second rolled view of the same points (its own order, noise and move, drawn after everything else) with that jitter."""
     P = max(n_r, *n_l3)
     cells = rng.permutation(16 * 17)[:P]
     px = 60 + 110 * (cells % 16) + rng.integers(-8, 9, P); py = 60 + 110 * (cells // 16) + rng.integers(-8, 9, P)   # <= 1828: with the move and the jitter inside [0, 2047]
@@ -802,7 +803,9 @@ def _list_minutiae(rng, n_r, n_l3, jitter):
     sizes = dict(zip(LIST_SELECTED, n_l3))
     lat = [view(sizes.get(i, min(2, P)), 0.02) for i in range(28)]
     rol = view(n_r, 0.08, (int(rng.integers(-20, 21)), int(rng.integers(-20, 21))), jitter, 0.05)
-    return lat, rol
+    if second_jitter is None:
+        return lat, rol
+    return lat, rol, view(n_r, 0.08, (int(rng.integers(-20, 21)), int(rng.integers(-20, 21))), second_jitter, 0.05)
 
 
 def list_length_set(cb, seed=70):
@@ -825,3 +828,107 @@ def list_length_shifted(t, tex_shift=0, minu_shift=0):
     mv = lambda v, s: (v.astype(np.int64) + s).astype(np.int16)
     return T.FPTemplate(minu=[T.MinutiaeTemplate(mv(m.x, minu_shift), mv(m.y, minu_shift), m.ori, m.des) for m in t.minu],
                         tex=[T.TextureTemplate(mv(x.x, tex_shift), mv(x.y, tex_shift), x.ori, des=x.des, codes=x.codes) for x in t.tex])
+
+
+# ---- the any-shape candidate kernel at its own route borders, and the pair-table forms (tests/test_gpu_pair_forms.py) ----
+# k_minu_cands (csrc/minu.hip) chooses its routes by the SHAPE of a list, nL latent x nR rolled minutiae, n = nL nR similarities: the similarity matrix in LDS (nL <= 64 and
+# nR <= 128) or in the workgroup's global scratch; the keys of the threshold search in 16 registers per thread (n <= 4096) or in scratch; GEMM tiles of 64 rows x 32 columns
+# with tails; and, with option s3_tie_order, std::sort's arrays in LDS with 16-bit indices (n <= 8192) or in scratch with 32-bit ones.  In a search the kernel receives what
+# the matrix-core classes leave over; in the pair-table calls it is the only candidate kernel, for every shape, in persistent workgroups.
+# (rolled minutiae, latent minutiae of templates 26 / 2 / 11), as LIST_MINU_SPECS: n = 4095 / 4096 / 4158 / 4160 with the matrix on either side of the LDS border, 8192 / 8255 /
+# 8256 / 8320, tile tails of 31 / 32 / 33, 63 / 64 / 65 and 127 / 128 / 129 points, lists of 118 .. 121 cells, and shapes that use the scratch fully (the pool of
+# _list_minutiae holds 272 points).
+PAIR_BORDER_SPECS = ((128, (64, 65, 63)), (129, (64, 32, 31)), (127, (64, 65, 33)), (64, (64, 65, 63)), (65, (64, 63, 62)), (63, (65, 66, 64)), (32, (128, 129, 127)),
+                     (31, (132, 133, 129)), (33, (124, 125, 128)), (96, (42, 43, 86)), (160, (25, 26, 52)), (256, (16, 17, 32)), (272, (15, 16, 31)), (40, (100, 103, 102)),
+                     (60, (65, 68, 69)), (200, (200, 150, 256)), (272, (272, 140, 152)), (1, (119, 120, 121)), (2, (60, 61, 59)), (120, (1, 2, 3)))
+PAIR_BORDER_RESEED = {}                                                 # {spec number: n}: the n-th draw, where the first missed a condition of the rehearsal
+CANDS_LDS_ROWS, CANDS_LDS_COLS, CANDS_KEY_REGS, CANDS_SORT_LDS = 64, 128, 4096, 8192      # minu.hip: kFastL, kFastR, kThreads * kKeyRegs, kFastN
+CANDS_TILE_ROWS, CANDS_TILE_COLS = 64, 32                               # minu.hip: kGemmRows, kGemmCols
+DEGENERATE_SHAPES = ((64, 64), (64, 65), (65, 63), (66, 63), (32, 128), (31, 129), (33, 129), (64, 128), (65, 127), (128, 64), (129, 64), (64, 129), (65, 128), (200, 272))
+
+
+def cands_route(nL, nR):
+    """The routes k_minu_cands takes for a list of nL x nR similarities: (matrix in "lds" / "scratch", keys in "regs" / "scratch", std::sort's arrays in "lds16" / "scratch32")."""
+    n = nL * nR
+    return ("lds" if nL <= CANDS_LDS_ROWS and nR <= CANDS_LDS_COLS else "scratch", "regs" if n <= CANDS_KEY_REGS else "scratch", "lds16" if n <= CANDS_SORT_LDS else "scratch32")
+
+
+# every combination the three rules allow: a matrix in LDS has at most 8192 cells, keys in registers at most 4096
+CANDS_ROUTES = (("lds", "regs", "lds16"), ("lds", "scratch", "lds16"), ("scratch", "regs", "lds16"), ("scratch", "scratch", "lds16"), ("scratch", "scratch", "scratch32"))
+
+
+def cands_border_coverage(shapes):
+    """{name: reached} for a set of (nL, nR) shapes — every route combination, both sides of every route border (within one tile of it), every tile tail class.  A pure
+    function of the shapes: tests/test_gpu_pair_forms.py asserts that every entry holds for PAIR_BORDER_SPECS."""
+    shapes = sorted(set(shapes))
+    routes = {cands_route(*s) for s in shapes}
+    out = {"route " + "/".join(r): r in routes for r in CANDS_ROUTES}
+    cells = lambda lo, hi, matrix: any(lo <= nL * nR <= hi and cands_route(nL, nR)[0] == matrix for nL, nR in shapes)
+    for matrix in ("lds", "scratch"):
+        out["keys: %d cells or just below, matrix in %s" % (CANDS_KEY_REGS, matrix)] = cells(CANDS_KEY_REGS - 1, CANDS_KEY_REGS, matrix)
+        out["keys: exactly %d cells, matrix in %s" % (CANDS_KEY_REGS, matrix)] = cells(CANDS_KEY_REGS, CANDS_KEY_REGS, matrix)
+        out["keys: just beyond %d cells, matrix in %s" % (CANDS_KEY_REGS, matrix)] = cells(CANDS_KEY_REGS + 1, CANDS_KEY_REGS + CANDS_TILE_ROWS, matrix)
+    out["sort arrays: exactly %d cells" % CANDS_SORT_LDS] = cells(CANDS_SORT_LDS, CANDS_SORT_LDS, "lds")
+    out["sort arrays: just beyond %d cells" % CANDS_SORT_LDS] = cells(CANDS_SORT_LDS + 1, CANDS_SORT_LDS + 2 * CANDS_TILE_ROWS, "scratch")
+    for name, side, unit in (("latent", 0, CANDS_TILE_ROWS), ("rolled", 1, CANDS_TILE_COLS), ("rolled", 1, CANDS_LDS_COLS)):
+        for d in (-1, 0, 1):
+            out["%s points: a multiple of %d %+d" % (name, unit, d)] = any(s[side] > unit // 2 and (s[side] - d) % unit == 0 for s in shapes)
+    out["lists of fewer than 120 cells"] = any(nL * nR < 120 for nL, nR in shapes)
+    out["lists of exactly 120 cells"] = any(nL * nR == 120 for nL, nR in shapes)
+    out["the full pool on both sides"] = any(nL == 272 and nR == 272 for nL, nR in shapes)
+    return out
+
+
+def pair_border_shapes(specs=PAIR_BORDER_SPECS):
+    return [(n_l, n_r) for n_r, n_l3 in specs for n_l in n_l3]
+
+
+def pair_border_set(cb, seed=71, specs=PAIR_BORDER_SPECS):
+    """Per spec one latent, its mate (jitter LIST_MINU_JITTER[0]: every true correspondence agrees with every other) and a second rolled view of the same points (jitter
+    LIST_MINU_JITTER[1], its own descriptor noise: another S3 list); every template carries a small texture template (12 .. 40 latent rows), so the texture scorer runs.
+    -> list of dicts: spec, L, R, R2."""
+    out = []
+    for i, (n_r, n_l3) in enumerate(specs):
+        draw = PAIR_BORDER_RESEED.get(i, 0)
+        lm, rm, rm2 = _list_minutiae(np.random.default_rng([seed, 1, i, draw]), n_r, n_l3, LIST_MINU_JITTER[0], LIST_MINU_JITTER[1])
+        lt, rt = _list_texture(np.random.default_rng([seed, 0, i, draw]), cb, "dense", 12 + 7 * i % 29)
+        _, rt2 = _list_texture(np.random.default_rng([seed, 2, i, draw]), cb, "sparse", 12 + 7 * i % 29)
+        out.append(dict(spec=(n_r, n_l3), L=T.FPTemplate(minu=lm, tex=[lt]), R=T.FPTemplate(minu=[rm], tex=[rt]), R2=T.FPTemplate(minu=[rm2], tex=[rt2])))
+    return out
+
+
+def degenerate_keys_at(cb, nL, nR, seed=5):
+    """The three cases of degenerate_key_pairs at the shape nL x nR (latent template 26 against the rolled minutiae template) -> [(case, latent, rolled)]: "a" fewer than 120
+    non-zero similarities (k rolled descriptors point along the latent's, nL k < 120, the others away; left out where nL >= 120), "b" every similarity identical, "c" a few
+    levels with large blocks of exact ties."""
+    rng = np.random.default_rng([seed, nL, nR])
+    base = S.make_latent(rng, n_tex_lo=40, n_tex_hi=60)
+    d = rng.standard_normal(96).astype(np.float32); d *= np.float32(1.73) / np.linalg.norm(d)
+    e = rng.standard_normal(96).astype(np.float32); e -= d * (e @ d) / (d @ d); e *= np.float32(1.73) / np.linalg.norm(e)     # orthogonal to d
+
+    def latent_with(des_rows):
+        L = T.FPTemplate(minu=list(base.minu), tex=list(base.tex))
+        n = len(des_rows)
+        L.minu[26] = T.MinutiaeTemplate(rng.integers(50, 700, n).astype(np.int16), rng.integers(50, 700, n).astype(np.int16),
+                                        rng.uniform(-3, 3, n).astype(np.float32), np.stack(des_rows).astype(np.float32))
+        return L
+
+    def rolled_with(des_rows):
+        n = len(des_rows)
+        R = S.make_rolled(rng, cb, n_minu=n, n_tex=60)
+        R.minu[0] = T.MinutiaeTemplate(R.minu[0].x, R.minu[0].y, R.minu[0].ori, np.stack(des_rows).astype(np.float32))
+        return R
+
+    out = []
+    if nL < 120:
+        k = min(119 // nL, nR - 1)
+        assert k >= 1 and nL * k < 120
+        out.append(("a", latent_with([d] * nL), rolled_with([-d] * (nR - k) + [d] * k)))
+    out.append(("b", latent_with([d] * nL), rolled_with([d] * nR)))
+    out.append(("c", latent_with([d] * (nL // 3) + [e] * (nL - nL // 3)), rolled_with([d] * (nR // 4) + [0.5 * d + 0.5 * e] * (nR - nR // 4))))
+    return out
+
+
+def degenerate_border_set(cb):
+    """degenerate_keys_at over DEGENERATE_SHAPES -> list of dicts: shape, case, L, R."""
+    return [dict(shape=(nL, nR), case=c, L=L, R=R) for nL, nR in DEGENERATE_SHAPES for c, L, R in degenerate_keys_at(cb, nL, nR)]

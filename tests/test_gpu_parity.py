@@ -1297,7 +1297,9 @@ def test_off_envelope_shapes_against_oracle(codebook_bytes, cb, oracle):
 def test_candidate_shape_classes_lists_match_oracle_traces(codebook_bytes, cb, oracle):
     """The candidate list (S3: members, order, similarity bits) of pairs in every shape class of k_minu_cands_rt — small (<= 64 x 128), medium (<= 16 384 similarities),
     large (<= 512 rolled minutiae, <= 38 912 similarities incl. the padding column), at the classes' own borders (rt_max_rows) — and just beyond them (any-shape kernel), against the oracle's stage-0 trace; then the same pairs'
-    scores through the generic kernel alone (option minu_generic) must be the same bits.  matcher.cpp:440-488."""
+    scores through the generic kernel alone (option minu_generic) must be the same bits.  matcher.cpp:440-488.
+    The tapped lists are the matrix-core path's (they are taken before minu_generic is set; the any-shape kernel only sees what the classes leave over).  The any-shape kernel's
+    own lists, at its own route borders, are held to the oracle in tests/test_gpu_pair_forms.py."""
     rng = np.random.default_rng(314)
     # (latent minutiae, rolled minutiae) at the class borders of rt_max_rows(): 64 x 128 | 65 x 128, 64 x 129 | 128 x 128 (S = 2: 16 640 / 129 = 128) | 129 x 128 |
     # 64 x 256 (S = 2: two row phases) | 65 x 256 (S = 4) | 128 x 256 (the last shape whose keys all stay in registers) | 129 x 256, 151 x 256 (S = 4 with a second key block;
