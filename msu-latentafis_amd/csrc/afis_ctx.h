@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones), afis_print_cascade.cpp (print cascade: the same two stages with resident prints as queries) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -255,8 +255,10 @@ __attribute__((visibility("hidden"))) inline int fail_edited(afis_ctx* ctx, cons
     return fail(ctx, AFIS_ESTATE, std::string(who) + ": the gallery was edited " + (name_calls ? "(afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove) " : "") + "after " + then);
 }
 
-struct Events {                                     // the HIP events of one call (for (hipEvent_t& e : ev) creates them), destroyed when it returns
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }   // the parts of a call's device and pinned buffers begin on 256-byte boundaries
+
+struct Events {                                     // the HIP events of one call, 8 at most (for (hipEvent_t& e : ev) creates them), destroyed when it returns
+    hipEvent_t e[8] = {};
     const int n;
     explicit Events(int count) : n(count) {}  Events(const Events&) = delete;
     __attribute__((visibility("hidden"))) ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -356,6 +358,21 @@ int drain_abandoned(afis_ctx* ctx, bool keep_last_search = false);   // waits (b
 // afis_search_subset_resident check their handles and call it.
 // keep_parts: the per-part scores of all queries stay on the device in ctx->parts [n_q][G][4] and are not copied back (afis_search_weighted folds them there).
 int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries* q, float* scores, float* parts, int32_t* status, int k, int64_t* topk_idx, float* topk_score, bool keep_parts = false);
+// The rule every call that takes a query handle applies to it: a reserved handle (afis_queries_upload_reserved) while `templates` — the size of what is searched — fits
+// what it was cut for, any other handle only in the epoch it was uploaded in.  subset: afis_search_subset_resident's wording (`templates` is the subset's size).
+int check_query_handle(afis_ctx* ctx, const char* who, const afis_queries* q, int64_t templates, bool subset = false);
+// The minutiae stage of a launch group — the candidate kernel, then the minutiae list kernel — in the one form every driver of the search family queues it in.
+//   ensure_minutiae_stage  cands, cand_n, minu_fb, minu_slab (slab_instances instances of the list kernel at once: 2 where the overlapped schedule may run) and the
+//                          candidate kernel's scratch, for the LARGEST group of `groups`; the scratch for the largest need of any group (afis_device.h: minu_scratch_bytes).
+//                          The only sizing of these buffers in a search: called before anything is queued, nothing below allocates
+//   queue_minutiae_stage   launch_minu_cands with the group's own grid (minu_cands_grid), `between` recorded, launch_graph_minutiae, on stream s; the three per-part scores
+//                          go to grp_parts [grp.nq][G][4].  shared_counter (the overlapped schedule): the list counter is reset between the two kernels and the list kernel
+//                          runs in its `join` form, so that a second instance on another stream may draw from the same counter
+//   minutiae_diagnostics   ctx->h_diag's rows of n_groups launch groups summed into acc [kDiagWords] (or a row of its own), and afis_timing's minu_tasks*,
+//                          minu_fallback_tasks and cands_clock_ghz from the sum
+int ensure_minutiae_stage(afis_ctx* ctx, const Shard& sh, const std::vector<QueryGroup>& groups, int slab_instances);
+int queue_minutiae_stage(afis_ctx* ctx, const Shard& sh, const QueryGroup& grp, float* grp_parts, unsigned long long* diag_row, hipStream_t s, hipEvent_t between, bool shared_counter = false);
+void minutiae_diagnostics(const afis_ctx* ctx, size_t n_groups, afis_timing& tm, unsigned long long* acc = nullptr);
 // The host's rank lists (k > kDeviceTopK) of a score matrix [n_q][G] whose column j is template col[j] (a subset in the caller's order) or index_base + j (col == NULL);
 // the parity tap afis_debug_rank_rows runs it too.  Hidden, as rank_subjects below.
 void host_rank_rows(const float* sc, int n_q, int64_t G, int k, const int64_t* col, int64_t index_base, int64_t* topk_idx, float* topk_score) __attribute__((visibility("hidden")));
@@ -484,6 +501,45 @@ struct __attribute__((visibility("hidden"))) FilterPass {
     const float* matrix() const { return copy ? ctx->filt_scores.as<float>() : ctx->scores.as<float>(); }
     int queue_cells();
     int queue_drop_subjects(int64_t S);
+};
+// afis_cascade.cpp
+// One cascade call, whatever its queries are: the minutiae stage for every cell, the selection of the `keep` best columns per query, the texture scorer for the kept
+// cells.  The driver owns the launch sequence, the layout of casc_buf and of the pinned buffer, the times and the ends of the entry points; afis_search_cascade and
+// afis_search_prints_cascade (afis_print_cascade.cpp) state their queries and the kernels that differ.  In the order of a call:
+//   clear()         the four options (opts: stage 1, selection, stage 2 in us, kept pairs) to 0
+//   empty(rc, ..)   n_q == 0 or G == 0, rc the answer of the empty search: no list holds anything
+//   check_limits()  n_q x keep and n_q x G within what one call takes
+//   run(..)         after the caller has filled in groups .. finish: the pair tables' structure (cascade_tables.h), room for everything before anything is queued, the
+//                   tables with the caller's extra ones to the device through the pinned buffer (h2d_bytes), stage 1 group after group (queue_minutiae_stage,
+//                   fuse_group), fuse_all, launch_rank_hits, the combined matrix in ctx->elig_scores filled with the no-entry word, gather, per piece launch_adc_pairs,
+//                   launch_graph_texture_pairs and (fuse_pairs) launch_fuse_pairs, finish, the read-back, ONE bounded wait, the options, afis_timing (stage 1), the
+//                   kept lists into the caller's arrays, the two matrices swapped
+//   end(rc, scores) the scores copy; after a failure the bounded wait, the call's buffers released, options and timing cleared; last_search either way
+struct CascadeTables;
+struct __attribute__((visibility("hidden"))) CascadeCall {
+    afis_ctx* const ctx; const char* const who; const int n_q, keep;
+    int64_t* const opts[4];
+    const int kept_w;                               // floats of kept_parts per kept cell
+    const bool own_kept_parts;                      // kept_parts is a device array of the call's own [n_q][keep][kept_w], zeroed before gather(), that finish() fills; false: the kept cells' pair parts, through q_slot
+    // the caller's, before run()
+    std::vector<QueryGroup>* groups = nullptr;      // the launch groups of the handle whose (pseudo-)queries stage 1 scores (NULL: none); their per-part scores lie in ctx->parts in the handle's order
+    std::vector<int32_t> q_first;                   // [groups + 1] the query of the CALL every group begins at (cascade_tables.h), n_q last
+    std::vector<uint8_t> has;                       // [n_q] 1 = the query's kept cells are pairs of stage 2
+    bool fuse_pairs = false;                        // a piece ends in launch_fuse_pairs -> d_pscore
+    std::function<void(std::vector<int32_t>&)> extra_tables;          // appends to the tables that go up (t->dev first): they then stand at d_dev + their position
+    std::function<int(const QueryGroup&, int)> fuse_group;            // (group, its first query of the handle) after a group's list kernel: stage 1's matrix from the parts, timed per group as fuse_ms
+    std::function<int()> fuse_all, gather, finish;                    // stage 1's matrix in one launch behind the groups (fuse_ms), the pair tables from the kept lists, the kept cells into ctx->elig_scores
+    // run()'s, for the caller's kernels
+    const CascadeTables* t = nullptr;
+    int nk = 0; long long base = 0;                 // min(keep, G), ctx->index_base
+    long long* d_kept = nullptr; const int32_t* d_dev = nullptr; const int32_t* d_q_slot = nullptr; int32_t* d_tab = nullptr;
+    float* d_pparts = nullptr; float* d_pscore = nullptr; float* d_kparts = nullptr;    // pair parts [total][4], pair scores [total], own_kept_parts' array
+    int64_t h2d_bytes = 0;
+    void clear() { for (int64_t* o : opts) *o = 0; }
+    int empty(int rc, int64_t* n_kept, int64_t* kept_idx, float* kept_parts);
+    int check_limits();
+    int run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts);
+    int end(int rc, float* scores);
 };
 
 }  // namespace afis

@@ -194,6 +194,22 @@ inline size_t minu_scratch_floats(int max_nL, int max_nR, int s3_tie_order)
     const size_t n = ((size_t)(max_nL > 1 ? max_nL : 1) * (size_t)(max_nR > 1 ? max_nR : 1) + 63) / 64 * 64;
     return (s3_tie_order ? 5 : 2) * n + 4096;
 }
+// The grid of k_minu_cands for a launch group of a search (launch_minu_cands' scratch_floats_per_wg and n_wg): 1024 workgroups, halved while their scratch exceeds 8 GiB,
+// never below 64.  A group of shorter latent lists may keep MORE workgroups under the cap than a longer one, and then needs more scratch: what is prepared for several
+// groups is minu_scratch_bytes, the largest of their needs, not the longest group's.
+struct MinuGrid { size_t wg_floats; int n_wg; size_t bytes() const { return wg_floats * 4 * (size_t)n_wg; } };
+inline MinuGrid minu_cands_grid(int max_nL, int max_nR, int s3_tie_order)
+{
+    MinuGrid g{minu_scratch_floats(max_nL, max_nR, s3_tie_order), 1024};
+    while (g.n_wg > 64 && g.bytes() > ((size_t)8 << 30)) g.n_wg /= 2;
+    return g;
+}
+inline size_t minu_scratch_bytes(const int* max_nL, size_t n_groups, int max_nR, int s3_tie_order)   // max_nL [n_groups]: the longest latent list of every launch group
+{
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_groups; ++i) { const size_t b = minu_cands_grid(max_nL[i], max_nR, s3_tie_order).bytes(); if (b > bytes) bytes = b; }
+    return bytes;
+}
 // One row of 16 unsigned 64-bit diagnostics per launch group, zeroed at the start of a search and read back with its results (afis_timing):
 enum { kDiagFallback = 0,       // candidate tasks handed to the any-shape kernel
        kDiagSmall = 1,          // tasks done by k_minu_cands_rt<1>, <2>, <4> (kDiagSmall + class)

@@ -23,8 +23,6 @@ static_assert(kScorePairsPerLaunch == AFIS_SCORE_PAIRS_PER_LAUNCH, "option score
 
 namespace afis {
 
-static inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
 // fold == NULL: afis_score_pairs — the fusion is fuse_cell, parts is [n_pairs][4].  fold != NULL: afis_score_print_pairs (afis_print_pairs.cpp) — the handle's queries are
 // prints' views, the fusion is the weighted fold of a print pair (template_fold.hip::k_fold_print_pairs) with the pair's two weights, uploaded in slot order beside the
 // chunk's tables, and parts is [n_pairs][2]: the minutiae template's part and the texture template's, +0.0f where the pair's weight is zero.

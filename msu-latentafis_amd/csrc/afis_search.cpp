@@ -399,6 +399,58 @@ int adc_refine_mfma(afis_ctx* ctx, Shard& sh, QueryGroup& grp, bool all_rows, bo
     return AFIS_OK;
 }
 
+int check_query_handle(afis_ctx* ctx, const char* who, const afis_queries* q, int64_t templates, bool subset)
+{
+    if (q->max_templates > 0) {
+        if (templates > q->max_templates)
+            return fail(ctx, AFIS_EINVAL, std::string(who) + (subset ? ": the subset lists " : ": the resident shard holds ") + std::to_string((long long)templates) +
+                                              " templates, these queries were uploaded for at most " + std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
+    } else if (q->gallery_epoch != ctx->gallery_epoch)
+        return fail_edited(ctx, who, "these queries were uploaded; free the handle and upload them again", !subset);
+    return AFIS_OK;
+}
+
+int ensure_minutiae_stage(afis_ctx* ctx, const Shard& sh, const std::vector<QueryGroup>& groups, int slab_instances)
+{
+    size_t nq_max = 0;
+    std::vector<int> max_nL;
+    for (const QueryGroup& grp : groups) { nq_max = std::max(nq_max, (size_t)grp.nq); max_nL.push_back(grp.max_nL); }
+    const size_t n_pairs = nq_max * (size_t)sh.gal.G;
+    if (n_pairs == 0) return AFIS_OK;
+    HIPCHK(ctx, ctx->cands.ensure(n_pairs * 3 * kTopMinu * sizeof(MinuCand)));
+    HIPCHK(ctx, ctx->cand_n.ensure(n_pairs * 3 * 4));
+    HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(n_pairs * 3, (size_t)sh.gal.G) * 4));
+    HIPCHK(ctx, ctx->minu_slab.ensure((size_t)slab_instances * graph_minutiae_slab_bytes(3 * (long long)n_pairs)));
+    // minutiae scratch per workgroup: simi[n] | keys[n] | rowsum[2048] | colsum[2048]  (only pairs the fast kernel cannot take use it)
+    HIPCHK(ctx, ctx->scratch.ensure(minu_scratch_bytes(max_nL.data(), max_nL.size(), sh.max_nR, ctx->s3_tie_order)));
+    return AFIS_OK;
+}
+
+int queue_minutiae_stage(afis_ctx* ctx, const Shard& sh, const QueryGroup& grp, float* grp_parts, unsigned long long* diag_row, hipStream_t s, hipEvent_t between, bool shared_counter)
+{
+    const GalleryDev& g = sh.gal;
+    const MinuGrid grid = minu_cands_grid(grp.max_nL, sh.max_nR, ctx->s3_tie_order);
+    HIPCHK(ctx, launch_minu_cands(grp.dev, g, ctx->scratch.as<float>(), grid.wg_floats, grid.n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(),
+                                  ctx->minu_fb.as<int32_t>(), grp.max_nL, sh.max_nR, diag_row, s));
+    if (shared_counter) HIPCHK(ctx, hipMemsetAsync(g.task_ctr + 1, 0, 4, s));
+    HIPCHK(ctx, hipEventRecord(between, s));
+    HIPCHK(ctx, launch_graph_minutiae(grp.dev, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p,
+                                      graph_minutiae_slab_bytes(3 * (long long)grp.nq * (long long)g.G), nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s, shared_counter));
+    return AFIS_OK;
+}
+
+// where the candidate tasks went, and the clock the sampled workgroups saw (shader cycles per tick of the constant 100 MHz counter)
+void minutiae_diagnostics(const afis_ctx* ctx, size_t n_groups, afis_timing& tm, unsigned long long* acc)
+{
+    unsigned long long own[kDiagWords];
+    if (!acc) acc = own;
+    std::fill(acc, acc + kDiagWords, 0ull);
+    for (size_t i = 0; i < n_groups; ++i) for (int w = 0; w < kDiagWords; ++w) acc[w] += ctx->h_diag[i * kDiagWords + w];
+    tm.minu_fallback_tasks = (int64_t)acc[kDiagFallback];
+    tm.minu_tasks_small = (int64_t)acc[kDiagSmall]; tm.minu_tasks_medium = (int64_t)acc[kDiagSmall + 1]; tm.minu_tasks_large = (int64_t)acc[kDiagSmall + 2];
+    tm.minu_tasks = tm.minu_tasks_small + tm.minu_tasks_medium + tm.minu_tasks_large + tm.minu_fallback_tasks;
+    tm.cands_clock_ghz = acc[kDiagCandsWall] ? (float)((double)acc[kDiagCandsClk] / (double)acc[kDiagCandsWall] * 0.1) : 0.0f;
+}
 
 // (1 of 3) Every buffer of the launch groups, brought to its size while the device is idle and before anything of the search is queued.
 static int prepare_search_buffers(afis_ctx* ctx, Shard& sh, const afis_queries* q, bool want_parts)
@@ -411,9 +463,9 @@ static int prepare_search_buffers(afis_ctx* ctx, Shard& sh, const afis_queries* 
     // re-allocate.  A hipMalloc of 6-13 GB takes 0.3 ms on an idle device; issued behind queued work (the row records used to be allocated inside adc_stage_mfma, after
     // the group's first kernels) it took 510-790 ms in three runs of ten (match -ldir: one search call in seven; profiles/r04_alloc_trace.txt).
     if (G > 0) {
-        int nq_max = 0, nL_max = 1; size_t rows_pad_max = 32, pair_rows_max = 0;
+        int nq_max = 0; size_t rows_pad_max = 32, pair_rows_max = 0;
         for (const QueryGroup& grp : q->groups) {
-            nq_max = std::max(nq_max, grp.nq); nL_max = std::max(nL_max, grp.max_nL);
+            nq_max = std::max(nq_max, grp.nq);
             rows_pad_max = std::max(rows_pad_max, ((size_t)std::max(grp.n_lt_rows, 0) + 31) / 32 * 32);
             pair_rows_max = std::max(pair_rows_max, (size_t)grp.nq * (size_t)grp.dev.lt_pad);          // a group's row-maximum arrays: [pair][lt_pad]
         }
@@ -423,17 +475,8 @@ static int prepare_search_buffers(afis_ctx* ctx, Shard& sh, const afis_queries* 
             if (ctx->adc_variant != 9) HIPCHK(ctx, ctx->rm_val.ensure(rm_bytes));      // variant 9: the values live in the compact list (rm_cv) only
             HIPCHK(ctx, ctx->rm_arg.ensure(rm_bytes));
             HIPCHK(ctx, ctx->parts.ensure(parts ? (size_t)nq_all * G * 16 : n_pairs * 16));   // per-part scores on request: every group's block stays on the device until the search is done
-            HIPCHK(ctx, ctx->cands.ensure(n_pairs * 3 * kTopMinu * sizeof(MinuCand)));
-            HIPCHK(ctx, ctx->cand_n.ensure(n_pairs * 3 * 4));
-            HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(n_pairs * 3, (size_t)G) * 4));
             HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs)));
-            HIPCHK(ctx, ctx->minu_slab.ensure(2 * graph_minutiae_slab_bytes(3 * (long long)n_pairs)));     // two instances at once in the overlapped schedule
-            {   // the generic candidate kernel's scratch (sized as in the loop below, for the longest latent minutiae template of the search)
-                const size_t per_wg = minu_scratch_floats(nL_max, sh.max_nR, ctx->s3_tie_order);
-                int n_wg = 1024;
-                while (n_wg > 64 && per_wg * 4 * n_wg > (8ull << 30)) n_wg /= 2;
-                HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * n_wg));
-            }
+            AFISCHK(ensure_minutiae_stage(ctx, sh, q->groups, 2));             // two instances of the list kernel at once in the overlapped schedule
             if (ctx->adc_variant == 9) {
                 HIPCHK(ctx, ctx->rm_cv.ensure(rm_bytes)); HIPCHK(ctx, ctx->rm_n.ensure(n_pairs * 4));
                 const size_t R_cap = rows_pad_max;
@@ -458,12 +501,8 @@ static int collect_timing(afis_ctx* ctx, const Shard& sh, const afis_queries* q,
     const int64_t G = sh.gal.G;
     const size_t n_groups = q->groups.size();
     {   // where the candidate tasks went, and the clocks the sampled workgroups saw (shader cycles per tick of the constant 100 MHz counter)
-        unsigned long long acc[kDiagWords] = {};
-        for (size_t i = 0; i < n_groups; ++i) for (int w = 0; w < kDiagWords; ++w) acc[w] += ctx->h_diag[i * kDiagWords + w];
-        tm.minu_fallback_tasks = (int64_t)acc[kDiagFallback];
-        tm.minu_tasks_small = (int64_t)acc[kDiagSmall]; tm.minu_tasks_medium = (int64_t)acc[kDiagSmall + 1]; tm.minu_tasks_large = (int64_t)acc[kDiagSmall + 2];
-        tm.minu_tasks = tm.minu_tasks_small + tm.minu_tasks_medium + tm.minu_tasks_large + tm.minu_fallback_tasks;
-        tm.cands_clock_ghz = acc[kDiagCandsWall] ? (float)((double)acc[kDiagCandsClk] / (double)acc[kDiagCandsWall] * 0.1) : 0.0f;
+        unsigned long long acc[kDiagWords];
+        minutiae_diagnostics(ctx, n_groups, tm, acc);
         tm.bound_clock_ghz = acc[kDiagBoundWall] ? (float)((double)acc[kDiagBoundClk] / (double)acc[kDiagBoundWall] * 0.1) : 0.0f;
     }
     if (G > 0) {
@@ -541,20 +580,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
         hipEvent_t* ev = &ctx->evpool[gi * 10];
         unsigned long long* const diag_row = ctx->diag.as<unsigned long long>() + gi * kDiagWords;
         if (G > 0) {
-            const size_t n_pairs = (size_t)nq * G;
-            const size_t lt_cap = (size_t)d.lt_pad;                          // (already large enough: the top of the search sized them for its largest group)
-            if (ctx->adc_variant != 9) HIPCHK(ctx, ctx->rm_val.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
-            HIPCHK(ctx, ctx->rm_arg.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16)));
-            if (ctx->adc_variant == 9) { HIPCHK(ctx, ctx->rm_cv.ensure(std::max<size_t>(n_pairs * lt_cap * 4, 16))); HIPCHK(ctx, ctx->rm_n.ensure(std::max<size_t>(n_pairs * 4, 16))); }
-            HIPCHK(ctx, ctx->parts.ensure(all_parts ? (size_t)nq_all * G * 16 : n_pairs * 16));
-            // minutiae scratch per workgroup: simi[n] | keys[n] | rowsum[2048] | colsum[2048]  (only pairs the fast kernel cannot take use it)
-            size_t per_wg = minu_scratch_floats(grp.max_nL, sh.max_nR, ctx->s3_tie_order);
-            int n_wg = 1024;
-            while (n_wg > 64 && per_wg * 4 * n_wg > (8ull << 30)) n_wg /= 2;
-            HIPCHK(ctx, ctx->scratch.ensure(per_wg * 4 * n_wg));
-            HIPCHK(ctx, ctx->cands.ensure(n_pairs * 3 * kTopMinu * sizeof(MinuCand)));
-            HIPCHK(ctx, ctx->cand_n.ensure(n_pairs * 3 * 4));
-            HIPCHK(ctx, ctx->minu_fb.ensure(minu_fb_ints(n_pairs * 3, (size_t)G) * 4));
+            const size_t n_pairs = (size_t)nq * G;                            // (every buffer below has its size: prepare_search_buffers is the only sizing of a search)
             float* grp_scores = ctx->scores.as<float>() + (size_t)q0 * G;
             float* const grp_parts = ctx->parts.as<float>() + (all_parts ? (size_t)q0 * G * 4 : 0);
             // One ADC workgroup fills a CU (128 KB LUT tile), so nothing overlaps its tile load: chunks of ~640 templates keep that
@@ -577,15 +603,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
             const bool minutiae_light = cells_m <= ctx->overlap_cell_ratio * cells_t;
             const bool overlap = ctx->adc_variant == 9 && ctx->stream_lo != nullptr && !ctx->overlap_failed && n_pairs >= 65536 && minutiae_light;
             grp.overlapped = overlap;
-            const size_t minu_slab_1 = graph_minutiae_slab_bytes(3 * (long long)n_pairs);      // one instance's slab of the minutiae list kernel (minu_slab holds two)
-            HIPCHK(ctx, ctx->tex_slab.ensure(graph_texture_slab_bytes((long long)n_pairs))); HIPCHK(ctx, ctx->minu_slab.ensure(2 * minu_slab_1));   // (already large enough, as the buffers above)
             const bool compact9 = ctx->adc_variant == 9;                  // the recomputation kernel's compact list of the rows that matter (S7 reads a third of the rows)
-            auto minutiae_stage = [&]() -> int {
-                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, sh.max_nR, diag_row, s));
-                HIPCHK(ctx, hipEventRecord(ev[7], s));
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
-                return AFIS_OK;
-            };
             if (overlap) {
                 // The bound pass is power-limited: half of the chip's CUs deliver 0.64 of the whole chip's matrix throughput (profiles/r04_cu_mask_probe.json).  It runs on a
                 // stream confined to the low `bound_cus` CUs; the minutiae stage — candidates, then lists: independent of the texture path — runs beside it on a stream
@@ -598,10 +616,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
                 HIPCHK(ctx, hipStreamWaitEvent(s_hi, ev[0], 0));
                 int rc9 = adc_stage_mfma(ctx, sh, grp, false, ev[1], ev[6], true, sl, false, diag_row);
                 if (rc9 != AFIS_OK) return rc9;
-                HIPCHK(ctx, launch_minu_cands(d, g, ctx->scratch.as<float>(), per_wg, n_wg, ctx->minu_generic | (ctx->s3_tie_order << 1), ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), ctx->minu_fb.as<int32_t>(), grp.max_nL, sh.max_nR, diag_row, s_hi));
-                HIPCHK(ctx, hipMemsetAsync(g.task_ctr + 1, 0, 4, s_hi));                     // the list counter both instances of the list kernel draw from: reset BEFORE either may start
-                HIPCHK(ctx, hipEventRecord(ev[7], s_hi));
-                HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.p, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s_hi, true));
+                AFISCHK(queue_minutiae_stage(ctx, sh, grp, grp_parts, diag_row, s_hi, ev[7], true));   // the list counter both instances of the list kernel draw from is reset BEFORE either may start
                 HIPCHK(ctx, hipEventRecord(ev[4], s_hi));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[6], 0));
                 HIPCHK(ctx, hipEventRecord(ev[8], s));                                     // the bound pass is done
@@ -611,6 +626,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
                 HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), ctx->rm_cv.as<float>(), ctx->rm_n.as<int32_t>(), grp_parts, ctx->tex_slab.p, ctx->tex_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
                 HIPCHK(ctx, hipEventRecord(ev[3], s));
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[7], 0));                              // every candidate list exists: help with whatever lists are left
+                const size_t minu_slab_1 = graph_minutiae_slab_bytes(3 * (long long)n_pairs);      // one instance's slab of the minutiae list kernel (minu_slab holds two)
                 HIPCHK(ctx, launch_graph_minutiae(d, g, ctx->cands.as<MinuCand>(), ctx->cand_n.as<int32_t>(), grp_parts, nullptr, nullptr, ctx->minu_slab.as<unsigned char>() + minu_slab_1, minu_slab_1, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s, true));   // beside the side stream's instance: the slab's second half
                 HIPCHK(ctx, hipStreamWaitEvent(s, ev[4], 0));
                 // No host wait here: the groups of a search follow one another on the three streams through events alone, and the search's final wait polls ALL THREE streams
@@ -633,7 +649,7 @@ int search_shard(afis_ctx* ctx, Shard& sh, const afis_subset* sub, afis_queries*
             HIPCHK(ctx, launch_graph_texture(d, g, ctx->table.as<float>(), ctx->rm_val.as<float>(), ctx->rm_arg.as<int32_t>(), compact9 ? ctx->rm_cv.as<float>() : nullptr,
                                              compact9 ? ctx->rm_n.as<int32_t>() : nullptr, grp_parts, ctx->tex_slab.p, ctx->tex_slab.bytes, nullptr, nullptr, 2 | (ctx->s89_tie_order << 8), s));
             HIPCHK(ctx, hipEventRecord(ev[3], s));
-            { int rcm = minutiae_stage(); if (rcm != AFIS_OK) return rcm; }
+            AFISCHK(queue_minutiae_stage(ctx, sh, grp, grp_parts, diag_row, s, ev[7]));
             HIPCHK(ctx, hipEventRecord(ev[4], s));
             }
             HIPCHK(ctx, hipEventRecord(ev[9], s));
@@ -716,12 +732,7 @@ int afis_search_resident(afis_ctx* ctx, afis_queries* q, float* scores, float* p
     // A handle's launch groups were cut for the shard size (and the free memory) of the moment it was uploaded: against a shard that has grown since, a group's per-pair
     // buffers could exceed the budget.  Such a handle is refused; uploading the latents again takes milliseconds.
     // (a handle of afis_queries_upload_reserved was cut for a shard of max_templates templates: any shard up to that size, whatever edits led to it)
-    if (q->max_templates > 0) {
-        if ((int64_t)ctx->gal.G > q->max_templates)
-            return fail(ctx, AFIS_EINVAL, "afis_search_resident: the resident shard holds " + std::to_string((long long)ctx->gal.G) + " templates, these queries were uploaded for at most " +
-                                              std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
-    } else if (q->gallery_epoch != ctx->gallery_epoch)
-        return fail_edited(ctx, "afis_search_resident", "these queries were uploaded; free the handle and upload them again");
+    AFISCHK(check_query_handle(ctx, "afis_search_resident", q, (int64_t)ctx->gal.G));
     return search_shard(ctx, *ctx, nullptr, q, scores, parts, status, k, topk_idx, topk_score);
 }
 

@@ -158,12 +158,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q, 
         return fail_edited(ctx, "afis_search_subset", "this subset was created; free it and create it again");
     // (the launch groups of a handle were cut for the whole shard, G >= n: they fit any subset of the same epoch)
     // (... and those of afis_queries_upload_reserved for a shard of max_templates templates: any subset up to that size, of any epoch)
-    if (q->max_templates > 0) {
-        if (s->n > q->max_templates)
-            return fail(ctx, AFIS_EINVAL, "afis_search_subset_resident: the subset lists " + std::to_string((long long)s->n) + " templates, these queries were uploaded for at most " +
-                                              std::to_string((long long)q->max_templates) + " (afis_queries_upload_reserved)");
-    } else if (q->gallery_epoch != ctx->gallery_epoch)
-        return fail_edited(ctx, "afis_search_subset_resident", "these queries were uploaded; free the handle and upload them again", false);
+    AFISCHK(check_query_handle(ctx, "afis_search_subset_resident", q, s->n, true));
     return search_shard(ctx, s->sh, s, q, scores, parts, status, k, topk_idx, topk_score);
 }
 

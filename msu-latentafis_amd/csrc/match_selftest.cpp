@@ -9,9 +9,11 @@
 //   match_selftest -selftest-offsets <counts file>          the gallery's derived offset tables (afis_offsets.h: derived_offsets) for the listed (minutiae, texture point) counts per template
 //   match_selftest -selftest-merge <file>                    the exchange's merge of per-rank rank lists (rank_exchange.cpp: merge_topk) on gathered idx / score words
 //   match_selftest -selftest-classes                        the candidate kernel's shape-class rule (afis_device.h: rt_max_rows) as a table: nR  L1 L2 L4  stride1 stride2 stride4
+//   match_selftest -selftest-scratch <file>                  the candidate kernel's grid (afis_device.h: minu_cands_grid) and the scratch prepared for a search (minu_scratch_bytes): per line "max_nR s3_tie_order max_nL...", one max_nL per launch group
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 #include <vector>
 
 #include "afis_device.h"
@@ -29,6 +31,19 @@ int main(int argc, char** argv)
                   << rt_class_keys_per_thread(4) << " " << rt_class_max_rolled(4) << " " << rt_class_max_latent(4) << std::endl;
         for (int nR = 0; nR <= 2000; ++nR)
             std::cout << nR << " " << rt_max_rows(1, nR) << " " << rt_max_rows(2, nR) << " " << rt_max_rows(4, nR) << " " << rt_row_stride(1, nR) << " " << rt_row_stride(2, nR) << " " << rt_row_stride(4, nR) << std::endl;
+        return 0;
+    }
+    if (args.cmdOptionExists("-selftest-scratch")) {                            // the candidate kernel's grid and the scratch prepared for a search's launch groups (no GPU): one group set per line
+        std::ifstream f(args.getCmdOption("-selftest-scratch"));
+        std::string line;
+        while (std::getline(f, line)) {
+            std::istringstream in(line);
+            int max_nR = 0, tie = 0, v; std::vector<int> nL;
+            if (!(in >> max_nR >> tie)) continue;
+            while (in >> v) nL.push_back(v);
+            for (int n : nL) { const MinuGrid g = minu_cands_grid(n, max_nR, tie); std::cout << "grid " << n << " " << max_nR << " " << tie << " " << g.wg_floats << " " << g.n_wg << " " << g.bytes() << std::endl; }
+            std::cout << "prepared " << minu_scratch_bytes(nL.data(), nL.size(), max_nR, tie) << std::endl;
+        }
         return 0;
     }
     if (args.cmdOptionExists("-selftest-offsets")) {                            // the shard's derived tables (no GPU): one "minutiae texture-points" pair per line

@@ -56,12 +56,18 @@ def test_the_kernel_and_the_driver_are_product_objects_and_the_fusion_has_one_de
     body = open(os.path.join(CSRC, "cascade.hip")).read().split("namespace afis {", 1)[1]
     assert body.count("__global__") == 3 and "atomic" not in body and "__shared__" not in body
     drv = open(os.path.join(CSRC, "afis_cascade.cpp")).read().split("#include", 1)[1]
-    for call in ("launch_minu_cands(", "launch_graph_minutiae(", "launch_fuse_stage1(", "launch_rank_hits(", "launch_cascade_gather(", "launch_adc_pairs(",
+    for call in ("queue_minutiae_stage(", "launch_fuse_stage1(", "launch_rank_hits(", "launch_cascade_gather(", "launch_adc_pairs(",
                  "launch_graph_texture_pairs(", "launch_fuse_pairs(", "launch_cascade_scatter(", "build_cascade_tables("):
         assert call in drv, call
     assert "stream_lo" not in drv and "stream_hi" not in drv and "launch_graph_texture(" not in drv and drv.count("wait_streams(") == 1      # unconfined; one wait
     search = open(os.path.join(CSRC, "afis_search.cpp")).read()
     assert "cascade" not in search                                          # the measured launch sequence got no flag
+    stage = search[search.index("int queue_minutiae_stage("):]               # the minutiae stage every driver queues: the two kernels, called nowhere else in the product
+    stage = stage[:stage.index("\n}\n")]
+    assert "launch_minu_cands(" in stage and "launch_graph_minutiae(" in stage
+    product = [f for f in sorted(os.listdir(CSRC)) if f.endswith(".cpp") and f.startswith("afis_") and f != "afis_taps.cpp"]
+    calls = {f: len(re.findall(r"\blaunch_minu_cands\(", open(os.path.join(CSRC, f)).read())) for f in product}
+    assert {f: n for f, n in calls.items() if n} == {"afis_search.cpp": 1}
     tabs = open(os.path.join(CSRC, "cascade_tables.h")).read()
     assert not re.search(r'#include\s*[<"](hip|afis_)', tabs)                 # device-free
 

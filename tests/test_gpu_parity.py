@@ -1219,13 +1219,26 @@ def test_minutiae_coordinates_beyond_the_packed_path(codebook_bytes, cb, oracle)
         m.close()
 
 
+def _alloc_trace(code):
+    """Runs `code` in a child process under AFIS_ALLOC_TRACE=1 and sorts its "alloc:" lines by the "mark:" they follow: (before the search's "queue:" line, after it)."""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, AFIS_ALLOC_TRACE="1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    allocs, late, where, queued = {}, {}, None, False
+    for line in r.stderr.splitlines():
+        if line.startswith("mark: "): where = line[6:]; allocs[where] = []; late[where] = []; queued = False
+        elif line.startswith("queue: "): queued = True
+        elif line.startswith("alloc: ") and where is not None: (late if queued else allocs)[where].append(line)
+    return allocs, late
+
+
 def test_a_search_allocates_before_it_queues_and_never_again(codebook_bytes, tmp_path):
     """The allocation rule: the buffers of a search's launch groups are brought to the size of the search's largest group — what it really takes: its own latent
     texture rows (round 6; rounds 4-5 sized them for 1000 rows per latent) — BEFORE anything of the search is queued: a hipMalloc behind queued work was seen to take 0.5-0.8 s
     (profiles/r04_alloc_trace.txt), on the idle device 0.3 ms.  Observable through AFIS_ALLOC_TRACE=1 (every (re)allocation of 64 MB or more, and the point where a search starts
     queuing): no search allocates after that point, in either schedule; a search of longer latents grows the row buffers (before it queues), the same search again allocates
     nothing, fewer latents never allocate, more latents per search do."""
-    import subprocess, sys, textwrap
+    import textwrap
     cbp = tmp_path / "cb.dat"; cbp.write_bytes(codebook_bytes)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = textwrap.dedent(f"""
@@ -1251,18 +1264,45 @@ def test_a_search_allocates_before_it_queues_and_never_again(codebook_bytes, tmp
         mark("more"); m.search(short + long_, k=4)
         mark("end"); m.close()
     """)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, AFIS_ALLOC_TRACE="1"))
-    assert r.returncode == 0, r.stderr[-2000:]
-    allocs, late, where, queued = {}, {}, None, False
-    for line in r.stderr.splitlines():
-        if line.startswith("mark: "): where = line[6:]; allocs[where] = []; late[where] = []; queued = False
-        elif line.startswith("queue: "): queued = True
-        elif line.startswith("alloc: ") and where is not None: (late if queued else allocs)[where].append(line)
+    allocs, late = _alloc_trace(code)
     assert all(v == [] for v in late.values()), late               # nothing is (re)allocated once a search has started queuing
     assert len(allocs["short"]) >= 4, allocs                       # the first search of a context allocates (row maxima x 2, records, candidate lists ...)
     assert 1 <= len(allocs["long"]) <= 4, allocs                   # longer latents: the row-indexed buffers grow (row maxima x 2, records), the candidate lists do not
     assert allocs["long again"] == [] and allocs["fewer"] == [] and allocs["back to back"] == [], allocs
     assert len(allocs["more"]) >= 4, allocs                        # 16 latents per search: larger buffers, once
+
+
+def test_a_shorter_launch_group_allocates_nothing_behind_the_longest(codebook_bytes, tmp_path):
+    """The candidate kernel's scratch is prepared for the largest NEED of a search's launch groups, not for the longest group: the grid rule (afis_device.h: minu_cands_grid —
+    1024 workgroups, halved while their scratch exceeds 8 GiB) lets a group of SHORTER latent lists keep more workgroups, and then it needs more.  Against a rolled template of
+    2000 minutiae a group whose longest latent list has 600 points runs 512 workgroups on 4 923 588 608 bytes, a group of 500 points 1024 workgroups on 8 208 777 216: sized by the
+    longest group alone the second group (re)allocated 8 GB behind the first group's queued work.  query_batch 1 makes the two latents two launch groups; no smaller shape crosses
+    the border.  The scores are those of the two latents searched one per call."""
+    import textwrap
+    cbp = tmp_path / "cb.dat"; cbp.write_bytes(codebook_bytes)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = textwrap.dedent(f"""
+        import importlib, sys
+        sys.path.insert(0, {root!r})
+        import numpy as np
+        T = importlib.import_module("msu-latentafis_amd.host.templates"); S = importlib.import_module("msu-latentafis_amd.host.synth"); M = importlib.import_module("msu-latentafis_amd.host.matcher")
+        cbb = open({str(cbp)!r}, "rb").read(); cb = T.Codebook.from_bytes(cbb)
+        rng = np.random.default_rng(11)
+        lats = [S.make_latent(rng, n_tex_lo=8, n_tex_hi=8, n_minu_lo=n, n_minu_hi=n) for n in (600, 500)]
+        gal = [S.make_rolled(rng, cb, n_minu=2000), S.make_rolled(rng, cb)]
+        m = M.Matcher(cbb); m.gallery_add(gal); m.gallery_commit(0)
+        m.set_option("query_batch", 1); m.set_option("bound_cus", 0)
+        def mark(s): sys.stderr.write("mark: " + s + "\\n"); sys.stderr.flush()
+        mark("both"); both = m.search(lats, k=0)
+        assert m.timing()["launch_groups"] == 2, m.timing()
+        mark("one by one"); single = [m.search([l], k=0)["scores"] for l in lats]
+        assert both["scores"].shape == (2, 2) and np.array_equal(both["scores"].view(np.uint32), np.concatenate(single).view(np.uint32)), (both["scores"], single)
+        mark("end"); m.close()
+    """)
+    allocs, late = _alloc_trace(code)
+    assert all(v == [] for v in late.values()), late               # nothing is (re)allocated once a search has started queuing
+    assert any("alloc: 8.209 GB" in a for a in allocs["both"]), allocs   # the 500-point group's need, before the search queued
+    assert allocs["one by one"] == [], allocs
 
 
 def test_off_envelope_shapes_against_oracle(codebook_bytes, cb, oracle):

@@ -353,6 +353,48 @@ def test_candidate_shape_class_rule_keeps_every_task_inside_its_class_limits():
     assert rows[128][1] == 64 and rows[129][1] == 0 and rows[128][2] == 128 and rows[129][2] == 96 and rows[256][2] == 64 and rows[256][3] == 151 and rows[257][2] == 0 and rows[400][3] == 97 and rows[512][3] == 75 and rows[513][3] == 0
 
 
+def test_candidate_scratch_is_prepared_for_the_largest_need_of_any_launch_group(tmp_path):
+    """The candidate kernel's grid for a launch group of a search (afis_device.h: minu_cands_grid) is 1024 workgroups, halved while their scratch — per workgroup
+    (2, or 5 with s3_tie_order) x ceil64(max_nL x max_nR) + 4096 floats — exceeds 8 GiB, never below 64.  A group of SHORTER latent lists may therefore keep more workgroups
+    than a longer one and need MORE scratch: what a search prepares before it queues (minu_scratch_bytes) must cover every group's own grid, not the longest group's.  The byte
+    counts are computed here from the rule; {600, 500} against 2000 rolled minutiae is the case in which sizing by the longest group gave 4 923 588 608 < 8 208 777 216."""
+    import subprocess
+    csrc = os.path.join(ROOT, "msu-latentafis_amd", "csrc")
+    exe = os.path.join(csrc, "match_selftest")
+    subprocess.run(["make", "-s", "-C", csrc, "match_selftest"], check=True)
+    sets = [(2000, 0, [600, 500]), (2000, 1, [250, 200]), (2000, 0, [524, 523]), (2000, 0, [2000]), (2000, 0, [1]),
+            (2000, 1, [2000, 1]), (200, 0, [60, 20]), (2000, 0, [4, 3, 600, 262, 263])]
+    f = tmp_path / "sets.txt"
+    f.write_text("".join("%d %d %s\n" % (nR, tie, " ".join(str(n) for n in nL)) for nR, tie, nL in sets))
+    out = subprocess.run([exe, "-selftest-scratch", str(f)], capture_output=True, text=True, check=True).stdout.split("\n")
+    cap = 8 << 30
+
+    def need(nL, nR, tie):
+        wg_floats = (5 if tie else 2) * ((max(nL, 1) * max(nR, 1) + 63) // 64 * 64) + 4096
+        n_wg = 1024
+        while n_wg > 64 and wg_floats * 4 * n_wg > cap: n_wg //= 2
+        return wg_floats, n_wg, wg_floats * 4 * n_wg
+
+    line = 0
+    for nR, tie, nL in sets:
+        needs = []
+        for n in nL:
+            tag, a, b, c, wg_floats, n_wg, nbytes = out[line].split(); line += 1
+            assert tag == "grid" and (int(a), int(b), int(c)) == (n, nR, tie)
+            wg_floats, n_wg, nbytes = int(wg_floats), int(n_wg), int(nbytes)
+            assert (wg_floats, n_wg, nbytes) == need(n, nR, tie), (n, nR, tie)
+            assert n_wg in (64, 128, 256, 512, 1024) and nbytes == wg_floats * 4 * n_wg      # a power-of-two fraction of 1024, never below 64
+            assert nbytes <= cap or n_wg == 64, (n, nR, tie)
+            assert n_wg == 1024 or wg_floats * 4 * n_wg * 2 > cap, (n, nR, tie)               # halved no further than the cap asks
+            needs.append(nbytes)
+        tag, prepared = out[line].split(); line += 1
+        assert tag == "prepared" and int(prepared) == max(needs), (nR, tie, nL)
+        assert all(int(prepared) >= b for b in needs), (nR, tie, nL, prepared, needs)
+    assert need(600, 2000, 0) == (2404096, 512, 4923588608) and need(500, 2000, 0) == (2004096, 1024, 8208777216)     # the worked case
+    assert need(524, 2000, 0)[1] == 512 and need(523, 2000, 0)[1] == 1024                                            # either side of the first halving
+    assert need(250, 2000, 1)[2] < need(200, 2000, 1)[2]                                                              # the same border for the five-array form
+
+
 def test_launch_group_rule_places_the_cuts_where_the_row_groups_are_fewest(tmp_path):
     """The latents of a search are cut into launch groups on the host (afis_device.h: launch_group_cuts / launch_group_latents; used by afis_queries_upload).  With the matrix-core
     bound pass a launch pays for row groups of 768 latent texture rows, so the rule must (1) cover the latents with contiguous runs of at most `per`, (2) reach the smallest total

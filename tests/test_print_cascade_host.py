@@ -51,11 +51,17 @@ def test_the_kernels_and_the_driver_are_product_objects():
     defs = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".cpp")) and re.search(r"float\s+fold_print_cell\s*\(", open(os.path.join(CSRC, f)).read())]
     assert defs == ["print_fold.h"]
     drv = open(os.path.join(CSRC, "afis_print_cascade.cpp")).read().split("#include", 1)[1]
-    for call in ("build_print_queries(", "launch_minu_cands(", "launch_graph_minutiae(", "launch_print_cascade_stage1(", "launch_rank_hits(", "build_cascade_tables(",
-                 "launch_print_cascade_gather(", "launch_adc_pairs(", "launch_graph_texture_pairs(", "launch_print_cascade_finish("):
-        assert call in drv, call
+    for call in ("build_print_queries(", "launch_print_cascade_stage1(", "launch_print_cascade_gather(", "launch_print_cascade_finish(", "CascadeCall", ".run("):
+        assert call in drv, call                                            # the call's own: its handle and its three kernels; the rest is the cascade driver's
+    run = open(os.path.join(CSRC, "afis_cascade.cpp")).read()
+    run = run[run.index("int CascadeCall::run("):]
+    run = run[:run.index("\n}\n")]
+    for call in ("queue_minutiae_stage(", "fuse_all()", "launch_rank_hits(", "build_cascade_tables(", "gather()", "launch_adc_pairs(", "launch_graph_texture_pairs(", "finish()"):
+        assert call in run, call
     assert "stream_lo" not in drv and "stream_hi" not in drv and "launch_graph_texture(" not in drv and "search_shard(" not in drv
-    assert drv.count("wait_streams(") == 1                                  # after the handle's own wait: one launch sequence, one wait
+    assert "stream_lo" not in run and "stream_hi" not in run and "launch_graph_texture(" not in run and "search_shard(" not in run
+    assert drv.count("wait_streams(") == 0 and run.count("wait_streams(") == 1     # after the handle's own wait: one launch sequence, one wait
+    assert "launch_adc_pairs(" not in drv and "launch_minu_cands(" not in drv and "queue_minutiae_stage(" not in drv   # no launch loop of its own
 
 
 def test_the_options_and_the_contract_are_documented():
