@@ -238,7 +238,7 @@ int afis_search_subset_resident(afis_ctx* ctx, afis_subset* s, afis_queries* q,
  *                     context.  Several handles may be live at once; afis_destroy releases those that are left.  A handle belongs to the gallery as it was: after an
  *                     appending commit or a removal that changed the shard afis_rank_subjects refuses it with AFIS_ESTATE (afis_subjects_free still works).
  * afis_rank_subjects   ranks the score matrix of the context's LAST search — any of afis_search, afis_search_dat, afis_search_resident, afis_search_subset,
- *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, afis_search_cascade, afis_search_prints_cascade, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
+ *                     afis_search_subset_resident, afis_search_eligible, afis_search_weighted, afis_search_prints, afis_search_cascade, afis_search_cascade_subset, afis_search_cascade_eligible, afis_search_prints_cascade, whatever outputs that call was asked for — as afis_get_timing reports the last search's times.  n_q must be that
  *                     search's (AFIS_EINVAL otherwise, as for k <= 0 or a null output).  Per query the k best subjects:
  *                       subject_score  the greatest fused score among the subject's templates that the search covered: all of them for a full search, the listed ones for a
  *                                      subset search (a subject without a listed template does not appear).  An empty or removed entry contributes its -1: a subject all of
@@ -881,13 +881,90 @@ int afis_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs,
  *          still stand at rank 1.  The generator's non-mates score next to nothing with the minutiae scorers, so these shares say little about real prints.
  * Shards: every rank keeps `keep` of its OWN shard.  The per-rank lists are host/sharding.py::merge_hits / merge_subject_hits input as they are; their union contains
  *          the global stage-1 top `keep`, so the merged result is a superset of the single-context cascade, not the same list.
- * Not in this interface: a subset form; a host-view form (afis_search style: upload the latents with afis_queries_upload first); a keep above AFIS_HITS_MAX; a first stage
- *          other than the minutiae scorers; the match CLI.  No result of afis_search changes because this function exists. */
+ * Not in this interface: a keep above AFIS_HITS_MAX; a first stage other than the minutiae scorers; the match CLI.  What this list used to name as missing is below:
+ *          a subset form is afis_search_cascade_subset; a host-view form is afis_search_cascade_eligible (a zero mask triple passes every template).  No result of
+ *          afis_search changes because this function exists. */
 #define AFIS_CASCADE_PAIRS_PER_LAUNCH 16384
 int afis_search_cascade(afis_ctx* ctx, afis_queries* q, int keep,
                         float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/,
                         int64_t* n_kept /*[n_q] or NULL*/,
                         int64_t* kept_idx /*[n_q][keep] or NULL*/, float* kept_parts /*[n_q][keep][4] or NULL*/);
+
+/* Cascade search over a part of the shard (no reference counterpart).  A latent that may only come from some fingers pays, under afis_search_cascade, for stage 1 on
+ * every cell, and its `keep` slots go to the best of ALL columns: the ranking call's masks then drop most of them.  The two calls below run the cascade over the columns
+ * that matter only — stage 1, the selection and the texture scorer.
+ *
+ * afis_search_cascade_subset is afis_search_cascade with the columns of a live subset (afis_subset_create).
+ * Handles  afis_search_subset_resident's rules: s a live subset of this context (else AFIS_EINVAL) created in the current gallery epoch (else AFIS_ESTATE); q under that
+ *          call's handle rules — a handle of the current epoch, or a reserved one (afis_queries_upload_reserved) while the subset's size n fits it.
+ * keep     1 <= keep <= AFIS_HITS_MAX, anything else is AFIS_EINVAL; n_kept[q] = min(keep, n).
+ * Stage-1 value and selection   afis_search_cascade's, sentence for sentence, over the listed templates: rank_key of m descending, equal keys by ascending GLOBAL index
+ *          whatever order the subset's list had.  kept_idx holds global indices, padded with -1.
+ * Values   a kept cell holds, bit for bit, the word afis_search_subset_resident writes at (q, column j), kept_parts its four parts (+0.0f four times where the score is
+ *          the -1, and in the padding); every other cell the no-entry word 0xffffffff.  Column j of scores [n_q][n] belongs to idx[j], the caller's order.  status is
+ *          afis_search's.  Under every value of "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9.
+ * The matrix afterwards   a subset search's record of n_q queries over s, held on the device as every subset search holds it; the call is one of the searches that
+ *          count.  The ranking family reads it exactly as it reads afis_search_cascade's matrix, naming templates by global index: the kept cells are the only entries,
+ *          the case lists go through their _filtered forms, afis_rank_subjects is not in this interface.  After any return other than AFIS_OK the matrix is invalid and
+ *          the call holds nothing it allocated.
+ * Arguments   n == 0 or n_q == 0 returns AFIS_OK as afis_search_cascade answers G == 0 (n_kept 0, kept_idx -1, kept_parts +0.0f).  Room is ensured before anything is
+ *          queued; host waits are bounded by "search_timeout_s".  Options and timing are afis_search_cascade's ("cascade_*"; pairs = n_q x n).
+ *
+ * afis_search_cascade_eligible takes afis_search_eligible's arguments, and refuses what it refuses, plus keep: labels and masks are both required, a labels handle that
+ * is not live is AFIS_EINVAL, one from an older gallery epoch AFIS_ESTATE, keep outside 1 .. AFIS_HITS_MAX AFIS_EINVAL.
+ * Eligibility   E(q) = the resident templates whose label passes masks[q] — the label test of the filtered hit lists, word for word.  The result is what
+ *          afis_search_cascade would give latent q on a shard that held only E(q), at their own global indices.
+ * Values   n_kept[q] = min(keep, |E(q)|).  The kept columns are the first n_kept[q] entries of the list afis_rank_hits_filtered(labels, masks, min_score = -INFINITY,
+ *          cap = keep) would give on the stage-1 matrix m.  A kept cell is bit for bit afis_search's scores[q][t], kept_parts its parts (+0.0f four times where the
+ *          score is the -1, and in the padding).  Every other cell of the [n_q][G] matrix — eligible but dropped, or not eligible — is the no-entry word.  A latent-empty
+ *          query keeps its first min(keep, |E(q)|) eligible columns by index at -1.  |E(q)| == 0: n_kept 0, a row of no-entry words, the status a search would report.
+ *          status is afis_search's.  Under every value of "s3_tie_order" / "ref_tie_order" and "adc_variant" 8 and 9.
+ * The matrix afterwards   a full search's record [n_q][G], as after afis_search_eligible; the call is one of the searches that count.  After any return other than
+ *          AFIS_OK the matrix is invalid and the call holds nothing it allocated; a following afis_search_resident or afis_search_eligible returns the bytes it
+ *          returned before.  Exclusion lists stay a matter of the ranking call, as they are for afis_search_eligible: an excluded print may take a kept slot.
+ * How      csrc/afis_cascade_eligible.cpp.  The latents are grouped into classes of identical mask triples; per class one temporary sub-shard of the class's eligible
+ *          templates (gathered on the device, class after class into the same buffers; "subset_device_bytes", "gallery_h2d_bytes" and "subset_gather_us" read as
+ *          before), the class's latents uploaded, one cascade over the sub-shard.  k_cascade_gather_mapped / k_cascade_scatter_mapped (csrc/cascade_mapped.hip) go from a kept
+ *          global index to the sub-shard's position and write the kept cell straight into the combined matrix, which is filled with the no-entry word once per call.
+ *          A class whose masks pass every template runs on the resident shard itself; a class nothing passes scores nothing.  Room for a class is ensured before that
+ *          class queues anything; host waits are bounded by "search_timeout_s".
+ * Options  "cascade_stage1_us", "cascade_select_us", "cascade_stage2_us", "cascade_kept_pairs": the sums over the classes; "eligible_classes": the classes.
+ *          afis_get_timing* adds the classes' stage-1 figures up (pairs = the cells stage 1 scored).
+ * Cost     about (eligible share) x afis_search_cascade's time, plus a fixed cost per class.  Measured on one MI355X, 100 latents x 100 000 prints, labels = ten one-hot
+ *          finger classes, interleaved with the two routes that existed before on the same context, medians of three after a discarded first, HOST clock around the C
+ *          calls (profiles/cascade_eligible_timing.json, tools/cascade_eligible_timing.py; device clock in brackets: the "cascade_*" options, afis_timing.total_ms).
+ *          Every latent one finger (ten classes of ten latents, 10 000 columns each), headline workload: keep 100 — 171.5 ms (117.1: stage 1 91.6, selection 0.35,
+ *          stage 2 25.2) against 285.4 ms (230.5) for afis_search_eligible and 823.2 ms for afis_search_cascade + afis_rank_hits_filtered: 0.60 x / 0.21 x; keep 1000 —
+ *          261.0 ms (206.2) against 285.9 and 924.6 ms: 0.91 x / 0.28 x.  Structured workload: keep 100 — 171.8 ms (118.9) against 320.5 and 852.4 ms: 0.54 x / 0.20 x;
+ *          keep 1000 — 255.7 ms (202.5) against 319.9 and 933.8 ms: 0.80 x / 0.27 x.
+ *          Every latent the same two fingers (one class of 20 000 columns), headline: keep 100 — 191.8 ms (177.6: 163.2 / 0.05 / 14.4) against 392.0 and 823.9 ms:
+ *          0.49 x / 0.23 x; keep 1000 — 292.0 ms (277.6) against 392.1 and 925.3 ms: 0.74 x / 0.32 x.  Structured: keep 100 — 204.2 ms (183.8) against 467.1 and
+ *          852.9 ms: 0.44 x / 0.24 x; keep 1000 — 286.9 ms (266.4) against 466.7 and 935.4 ms: 0.61 x / 0.31 x.  Spreads (max - min) at most 8.2 ms.
+ *          The fixed cost per class — the sub-shard's gather, the class's query upload, its wait: what the host clock holds beyond the device clock, per class —
+ *            5.3 - 5.5 ms for a class of 10 latents x 10 000 columns, 14 - 21 ms for the class of 100 latents x 20 000 columns.
+ *            afis_search_eligible pays the same per class (its host clock exceeds its device clock by 5.5 and 14 ms per class on the same headline runs).
+ *          It decides where the call stops paying.  Against afis_search_cascade + filter a class saves stage 1 on the cells it does not score, 0.09 us per cell
+ *          (91.6 ms for 10^6 cells), and pays the fixed cost: a class of n_c latents over m of G columns pays from about n_c x (G - m) > 60 000 cells on — ten latents
+ *          that exclude 6 000 prints; one latent alone only in a shard where it excludes 60 000.  Against afis_search_eligible the fixed cost is the same and the
+ *          question is stage 2: a kept pair costs 1.2 - 2.5 us where the texture path of a search costs 0.14 us per cell, so the call pays while keep stays below about
+ *          a tenth of the class's columns (0.91 x at keep 1000 of 10 000, where stage 2's 115.1 ms already outweigh stage 1's 90.8 ms).
+ *          What the routes list, on these SYNTHETIC galleries (facts about the generator, not about fingerprints; through afis_rank_positions on each route's
+ *          matrix): of the 29 (one finger) and 76 (two fingers) eligible planted mates every route lists all, 27 and 54 of them at rank 1, at both keeps and on both
+ *          workloads.  The generator's non-mates score next to nothing with the minutiae scorers, so afis_search_cascade's global keep loses no planted mate here; on
+ *          real prints its `keep` slots go to all fingers, which is what this call is for.  The full search is untouched: bit-identical scores and a median total_ms
+ *          within 0.2 % of the parent commit's library, of either sign over two runs (profiles/cascade_eligible_full_search_ab.txt).
+ * Shards: no new merge.  Every rank keeps `keep` of its own shard's eligible prints; the per-rank lists are host/sharding.py::merge_hits input as they are, a superset
+ *          of the single-context result.
+ * Not in this interface: a subset or eligible form of afis_search_prints_cascade; exclusion lists applied before the selection; a keep above AFIS_HITS_MAX. */
+int afis_search_cascade_subset(afis_ctx* ctx, afis_subset* s, afis_queries* q, int keep,
+                               float* scores /*[n_q][n] or NULL*/, int32_t* status /*[n_q] or NULL*/,
+                               int64_t* n_kept /*[n_q] or NULL*/,
+                               int64_t* kept_idx /*[n_q][keep] or NULL, global indices*/, float* kept_parts /*[n_q][keep][4] or NULL*/);
+int afis_search_cascade_eligible(afis_ctx* ctx, afis_labels* labels, const uint64_t* masks /*[n_q][3]*/,
+                                 const afis_template_view* queries, int n_q, int keep,
+                                 float* scores /*[n_q][G] or NULL*/, int32_t* status /*[n_q] or NULL*/,
+                                 int64_t* n_kept /*[n_q] or NULL*/,
+                                 int64_t* kept_idx /*[n_q][keep] or NULL, global indices*/, float* kept_parts /*[n_q][keep][4] or NULL*/);
 
 /* Print cascade (no reference counterpart): the duplicate check of an enrolment with the texture scorer for the best `keep` columns only.  afis_search_prints pays the
  * full price of a search for every query print, and nearly all of it is the texture path: a print's view carries about 811 decoded texture rows, more than a latent's.

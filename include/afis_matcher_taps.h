@@ -97,6 +97,24 @@ int afis_debug_print_queries(afis_ctx* ctx, const int64_t* idx /*[n]*/, int n, c
                              int32_t* lm_off, int32_t* lm_tile_off, int32_t* lt_off, int32_t* tile_off, int32_t* tile16_off, int32_t* tex_slot, int32_t* status,
                              int16_t* lm_xy, float* lm_ori, float* lm_des, float* lm_frag, int16_t* lt_xy, float* lt_ori, float* lt_des);
 
+/* The two mapped kernels of a two-stage search over a sub-shard (the mapped gather and scatter of the kept cells: csrc, the .hip unit whose name ends in _mapped) on
+ * planted tables, without a search.  The call stands for n_q queries over a sub-shard of m templates of a resident shard of G_res:
+ * kept [n_q][keep] are the kept lists as the selection leaves them (global indices, -1 padding), has [n_q] 1 = the query's kept cells are pairs, q_first [n_grp + 1]
+ * the launch groups' first queries (ascending, 0 .. n_q) and per_launch the chunk size — from these the pair tables' structure is built as the driver builds it
+ * (the driver's tables header) —, sel [m] the resident positions of the sub-shard's templates, strictly ascending (NULL with m == G_res: the identity), parts [n_q][m][4] the
+ * per-part scores of stage 1, pair_score [pairs] what the pair kernels would have left (pairs = n_kept x the queries with has), row_of [n_q] / out_col [m] the rows and
+ * columns of out [out_rows][out_stride] (NULL: q and the sub-shard position).  tab (tab_ints >= 2 pairs + pieces ints), pair_parts [pairs][4] and out are uploaded as the
+ * caller filled them, each kernel runs once, and the three come back; *n_pieces = the pieces of the structure:
+ *   piece i's table at tab + 2 piece_first[i] + i = [count | (q - first query of the piece's group, sub-shard position) x count]; pair_parts[slot] = (parts[q][t][0..2], +0.0f);
+ *   out[row_of[q]][out_col[t]] = pair_score[slot], or -1.0f for a query without pairs, for every kept (q, t) that names a template of the sub-shard.
+ * A kept entry that names none (padding, outside the shard, not in sel) is routed to template 0 with parts of +0.0f and written nowhere.  Words, not numbers.
+ * 1 <= n_kept <= min(keep, m).  AFIS_EINVAL for tables that break the rules above; no gallery is needed. */
+int afis_debug_kept_cells_mapped(afis_ctx* ctx, int n_q, int64_t G_res, int64_t m, int keep, int n_kept, int64_t index_base, const int64_t* kept /*[n_q][keep]*/,
+                              const uint8_t* has /*[n_q]*/, const int32_t* q_first /*[n_grp + 1]*/, int n_grp, int per_launch, const int32_t* sel /*[m] or NULL*/,
+                              const float* parts /*[n_q][m][4]*/, const float* pair_score /*[pairs]*/, const int32_t* row_of /*[n_q] or NULL*/,
+                              const int32_t* out_col /*[m] or NULL*/, int64_t out_rows, int64_t out_stride, int32_t* tab, int64_t tab_ints, int32_t* n_pieces,
+                              float* pair_parts /*[pairs][4]*/, float* out /*[out_rows][out_stride]*/);
+
 /* In-kernel phase timers (only when the library is built with PHASE_TIMING=1; all zeros otherwise): 32 cycle counters
  * accumulated since the last reset.  Development aid. */
 int afis_debug_phase_cycles(afis_ctx* ctx, unsigned long long* out32, int reset);

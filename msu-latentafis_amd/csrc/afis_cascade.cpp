@@ -15,6 +15,8 @@
 //             (ctx->elig_scores, filled with the no-entry word by a memset of 0xff bytes; here k_cascade_scatter), which is swapped in at the end
 // A kept pair whose print is empty or carries no texture template goes through the pair kernels as it is: k_adc_pairs skips a print without texture points before it
 // reads one (n_rt <= 0), k_graph_texture's pair form writes +0.0f for such a pair before it reads a row maximum (n_lt <= 0 || n_rt <= 0), fuse_cell gives an empty print its -1.
+// The driver runs over the resident shard or over a SUB-SHARD (CascadeCall::sub; afis_cascade_eligible.cpp): stage 1, the selection — which then names the kept prints
+// through the sub-shard's d_global — and the pair kernels take CascadeCall::shard(); with own_matrix false the combined matrix is the caller's to size, fill and swap.
 // casc_buf:  n_hits [n_q] int64 | kept [n_q][keep] int64 | kept score [n_q][keep] | own_kept_parts' [n_q][keep][kept_w] | pair parts [total][4] | pair score [total] | tab |
 //            the tables that went up (cascade_tables.h's, then the caller's) | rm_val [P][lt_pad] | rm_arg [P][lt_pad], P = pairs of a chunk at most, lt_pad the handle's
 //            longest texture template
@@ -43,7 +45,8 @@ int CascadeCall::empty(int rc, int64_t* n_kept, int64_t* kept_idx, float* kept_p
 
 int CascadeCall::check_limits()
 {
-    if ((int64_t)n_q * std::min<int64_t>(keep, ctx->gal.G) > 0x7fffffffLL || (int64_t)n_q * ctx->gal.G > 0x7ffffff0LL)
+    const int64_t G = shard().gal.G;
+    if ((int64_t)n_q * std::min<int64_t>(keep, G) > 0x7fffffffLL || (int64_t)n_q * G > 0x7ffffff0LL)
         return fail(ctx, AFIS_EINVAL, std::string(who) + ": n_q x keep or n_q x G exceeds what one call takes");
     return AFIS_OK;
 }
@@ -51,7 +54,8 @@ int CascadeCall::check_limits()
 // Everything of the call that touches the device, for n_q > 0 and G > 0.  end() releases what the call allocated when this fails.
 int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
 {
-    const int64_t G = ctx->gal.G;
+    Shard& sh = shard();                                                    // the resident shard, or the sub-shard of the call
+    const int64_t G = sh.gal.G;
     base = ctx->index_base; nk = (int)std::min<int64_t>(keep, G);
     std::vector<QueryGroup> no_groups;
     std::vector<QueryGroup>& grps = groups ? *groups : no_groups;
@@ -81,9 +85,10 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
     // ---- room first: every allocation precedes everything the call queues and the first write into the caller's arrays
     const size_t n_cells = (size_t)n_q * (size_t)G;
     HIPCHK(ctx, ctx->scores.ensure(n_cells * 4));
-    HIPCHK(ctx, ctx->elig_scores.ensure(n_cells * 4));
+    if (own_matrix) HIPCHK(ctx, ctx->elig_scores.ensure(n_cells * 4));
+    if (own_matrix && sub && !sub->identity) HIPCHK(ctx, ctx->out_perm.ensure(n_cells * 4));     // (the scores leave in the caller's column order: afis_search_cascade_subset)
     HIPCHK(ctx, ctx->parts.ensure(std::max<size_t>(n_pseudo * (size_t)G * 16, 16)));
-    AFISCHK(ensure_minutiae_stage(ctx, *ctx, grps, 1));
+    AFISCHK(ensure_minutiae_stage(ctx, sh, grps, 1));
     HIPCHK(ctx, ctx->diag.ensure(diag_bytes));
     HIPCHK(ctx, ctx->casc_buf.ensure(buf_bytes));
     if (P > 0) HIPCHK(ctx, ctx->casc_slab.ensure(graph_texture_slab_bytes((long long)P)));
@@ -108,7 +113,7 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
         hipEvent_t* gev = &ctx->evpool[gi * 10];
         grp.overlapped = false;
         HIPCHK(ctx, hipEventRecord(gev[0], s));
-        AFISCHK(queue_minutiae_stage(ctx, *ctx, grp, ctx->parts.as<float>() + (size_t)p0 * (size_t)G * 4, ctx->diag.as<unsigned long long>() + gi * kDiagWords, s, gev[1]));
+        AFISCHK(queue_minutiae_stage(ctx, sh, grp, ctx->parts.as<float>() + (size_t)p0 * (size_t)G * 4, ctx->diag.as<unsigned long long>() + gi * kDiagWords, s, gev[1]));
         HIPCHK(ctx, hipEventRecord(gev[2], s));
         if (fuse_group) { AFISCHK(fuse_group(grp, p0)); HIPCHK(ctx, hipEventRecord(gev[3], s)); }
         p0 += grp.nq;
@@ -117,11 +122,11 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
     HIPCHK(ctx, hipEventRecord(ev[1], s));
     // ---- selection: per query the nk best by m — rank_key descending, equal keys by ascending global index; every column is an entry
     HIPCHK(ctx, hipEventRecord(ev[2], s));
-    HIPCHK(ctx, launch_rank_hits(ctx->scores.as<float>(), n_q, (int)G, nullptr, 0, nullptr, nullptr, base, kPosFloor, keep, (long long*)d, d_kept, (float*)(d + kscore_at), nullptr, s));
+    HIPCHK(ctx, launch_rank_hits(ctx->scores.as<float>(), n_q, (int)G, nullptr, 0, nullptr, sub ? sub->d_global.as<long long>() : nullptr, base, kPosFloor, keep, (long long*)d, d_kept, (float*)(d + kscore_at), nullptr, s));
     HIPCHK(ctx, hipEventRecord(ev[3], s));
     // ---- stage 2: the texture scorer for the kept cells that are pairs, the caller's closing kernel for every kept cell
     HIPCHK(ctx, hipEventRecord(ev[4], s));
-    HIPCHK(ctx, hipMemsetAsync(ctx->elig_scores.p, 0xff, n_cells * 4, s));
+    if (own_matrix) HIPCHK(ctx, hipMemsetAsync(ctx->elig_scores.p, 0xff, n_cells * 4, s));
     if (own_kept_parts) HIPCHK(ctx, hipMemsetAsync(d_kparts, 0, kparts_bytes, s));
     AFISCHK(gather());
     for (size_t i = 0; i < n_pieces; ++i) {
@@ -132,9 +137,9 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
         float* const rm_val = (float*)(d + rmv_at) + in_chunk * Lp;
         int32_t* const rm_arg = (int32_t*)(d + rma_at) + in_chunk * Lp;
         float* const p_parts = d_pparts + pc.first * 4;
-        HIPCHK(ctx, launch_adc_pairs(qd, ctx->gal, ctx->codewords.as<float>(), p_tab, d_dev + tabs.seg_at + 2 * pc.seg_first, (int)pc.n_seg, rm_val, rm_arg, s));
-        HIPCHK(ctx, launch_graph_texture_pairs(qd, ctx->gal, p_tab, (int)pc.n, ctx->table.as<float>(), rm_val, rm_arg, p_parts, ctx->casc_slab.p, ctx->casc_slab.bytes, ctx->s89_tie_order, s));
-        if (fuse_pairs) HIPCHK(ctx, launch_fuse_pairs(qd, ctx->gal, p_tab, (int)pc.n, p_parts, d_pscore + pc.first, s));
+        HIPCHK(ctx, launch_adc_pairs(qd, sh.gal, ctx->codewords.as<float>(), p_tab, d_dev + tabs.seg_at + 2 * pc.seg_first, (int)pc.n_seg, rm_val, rm_arg, s));
+        HIPCHK(ctx, launch_graph_texture_pairs(qd, sh.gal, p_tab, (int)pc.n, ctx->table.as<float>(), rm_val, rm_arg, p_parts, ctx->casc_slab.p, ctx->casc_slab.bytes, ctx->s89_tie_order, s));
+        if (fuse_pairs) HIPCHK(ctx, launch_fuse_pairs(qd, sh.gal, p_tab, (int)pc.n, p_parts, d_pscore + pc.first, s));
     }
     AFISCHK(finish());
     HIPCHK(ctx, hipEventRecord(ev[5], s));
@@ -174,14 +179,14 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
             if (has[(size_t)i]) memcpy(kept_parts + o * w, pin + pin_parts_at + tabs.q_slot[(size_t)i] * 16, (size_t)nk * 16);
         }
     }
-    std::swap(ctx->scores, ctx->elig_scores);                               // the combined matrix is the last search's from here on
+    if (own_matrix) std::swap(ctx->scores, ctx->elig_scores);               // the combined matrix is the last search's from here on
     ctx->timing = tm;
     return AFIS_OK;
 }
 
 int CascadeCall::end(int rc, float* scores)
 {
-    const int64_t G = ctx->gal.G;
+    const int64_t G = shard().gal.G;
     if (rc == AFIS_OK && scores) {                                          // the device is idle: a plain copy, as at the end of a search
         const hipError_t e = hipMemcpy(scores, ctx->scores.p, (size_t)n_q * (size_t)G * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(ctx, AFIS_EDEVICE, std::string(who) + ": the scores: " + hipGetErrorString(e));
@@ -194,7 +199,7 @@ int CascadeCall::end(int rc, float* scores)
         clear();
         ctx->timing = afis_timing{};
     }
-    ctx->last_search = rc == AFIS_OK ? LastSearch{true, n_q, G, nullptr, ctx->gallery_epoch} : LastSearch{};
+    ctx->last_search = rc == AFIS_OK ? LastSearch{true, n_q, G, sub, ctx->gallery_epoch} : LastSearch{};
     t = nullptr;
     return rc;
 }
@@ -202,10 +207,11 @@ int CascadeCall::end(int rc, float* scores)
 }  // namespace afis
 
 // afis_search_cascade's queries are the handle's queries, its groups the handle's groups; a pair's four parts are the kept cell's
-static int latent_cascade(CascadeCall& c, afis_queries* q, int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
+int afis::latent_cascade(CascadeCall& c, afis_queries* q, const CascadeMap* map, int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
 {
     afis_ctx* const ctx = c.ctx;
-    const int n_q = c.n_q, keep = c.keep, G = (int)ctx->gal.G;
+    const GalleryDev& gal = c.shard().gal;
+    const int n_q = c.n_q, keep = c.keep, G = (int)gal.G, G_res = (int)ctx->gal.G;
     hipStream_t s = ctx->stream;
     AFISCHK(c.check_limits());
     c.q_first.assign(1, 0);
@@ -216,15 +222,32 @@ static int latent_cascade(CascadeCall& c, afis_queries* q, int64_t* n_kept, int6
     c.groups = &q->groups;
     c.fuse_pairs = true;
     c.fuse_group = [&](const QueryGroup& grp, int q0) -> int {
-        HIPCHK(ctx, launch_fuse_stage1(grp.dev, ctx->gal, ctx->parts.as<float>() + (size_t)q0 * (size_t)G * 4, ctx->scores.as<float>() + (size_t)q0 * (size_t)G, s));
+        HIPCHK(ctx, launch_fuse_stage1(grp.dev, gal, ctx->parts.as<float>() + (size_t)q0 * (size_t)G * 4, ctx->scores.as<float>() + (size_t)q0 * (size_t)G, s));
         return AFIS_OK;
     };
+    size_t inv_at = 0, col_at = 0, row_at = 0;                              // int positions of the map's tables behind cascade_tables.h's
+    if (map) c.extra_tables = [&](std::vector<int32_t>& up) {
+        inv_at = up.size(); up.insert(up.end(), map->inv->begin(), map->inv->end());
+        col_at = up.size(); up.insert(up.end(), map->out_col->begin(), map->out_col->end());
+        row_at = up.size(); up.insert(up.end(), map->row_of->begin(), map->row_of->end());
+    };
+    const auto table = [&](const std::vector<int32_t>* v, size_t at) { return v->empty() ? nullptr : c.d_dev + at; };
     c.gather = [&]() -> int {
+        if (map) {
+            HIPCHK(ctx, launch_cascade_gather_mapped(n_q, G_res, G, keep, c.nk, c.base, c.d_kept, c.d_q_slot, c.d_dev + c.t->piece_first_at, (int)c.t->pieces.size(),
+                                                     c.d_dev + c.t->piece_q0_at, table(map->inv, inv_at), ctx->parts.as<float>(), c.d_tab, c.d_pparts, s));
+            return AFIS_OK;
+        }
         HIPCHK(ctx, launch_cascade_gather(n_q, G, keep, c.nk, c.base, c.d_kept, c.d_q_slot, c.d_dev + c.t->piece_first_at, (int)c.t->pieces.size(), c.d_dev + c.t->piece_q0_at,
                                           ctx->parts.as<float>(), c.d_tab, c.d_pparts, s));
         return AFIS_OK;
     };
     c.finish = [&]() -> int {
+        if (map) {
+            HIPCHK(ctx, launch_cascade_scatter_mapped(n_q, G_res, G, keep, c.nk, c.base, c.d_kept, c.d_q_slot, c.d_pscore, table(map->inv, inv_at), table(map->row_of, row_at),
+                                                      table(map->out_col, col_at), (long long)map->out_rows, (long long)map->out_stride, ctx->elig_scores.as<float>(), s));
+            return AFIS_OK;
+        }
         HIPCHK(ctx, launch_cascade_scatter(n_q, G, keep, c.nk, c.base, c.d_kept, c.d_q_slot, c.d_pscore, ctx->elig_scores.as<float>(), s));
         return AFIS_OK;
     };
@@ -247,7 +270,7 @@ int afis_search_cascade(afis_ctx* ctx, afis_queries* q, int keep, float* scores,
         return c.empty(search_shard(ctx, *ctx, nullptr, q, scores, nullptr, status, 0, nullptr, nullptr), n_kept, kept_idx, kept_parts);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     AFISCHK(drain_abandoned(ctx));
-    const int rc = c.end(latent_cascade(c, q, n_kept, kept_idx, kept_parts), scores);
+    const int rc = c.end(latent_cascade(c, q, nullptr, n_kept, kept_idx, kept_parts), scores);
     if (rc == AFIS_OK && status) for (int i = 0; i < q->n_q; ++i) status[i] = q->status[(size_t)i];
     return rc;
 }

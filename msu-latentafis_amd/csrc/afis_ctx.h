@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -522,6 +522,8 @@ struct __attribute__((visibility("hidden"))) CascadeCall {
     const int kept_w;                               // floats of kept_parts per kept cell
     const bool own_kept_parts;                      // kept_parts is a device array of the call's own [n_q][keep][kept_w], zeroed before gather(), that finish() fills; false: the kept cells' pair parts, through q_slot
     // the caller's, before run()
+    afis_subset* sub = nullptr;                     // the sub-shard the call runs over — stage 1, the selection (its d_global names the kept prints) and the pair kernels —; NULL: the resident shard, positions named index_base + position
+    bool own_matrix = true;                         // run() sizes ctx->elig_scores [n_q][G of the shard], fills it with the no-entry word and swaps it in; false (afis_search_cascade_eligible: one combined matrix for all classes): the caller's to size, fill and swap
     std::vector<QueryGroup>* groups = nullptr;      // the launch groups of the handle whose (pseudo-)queries stage 1 scores (NULL: none); their per-part scores lie in ctx->parts in the handle's order
     std::vector<int32_t> q_first;                   // [groups + 1] the query of the CALL every group begins at (cascade_tables.h), n_q last
     std::vector<uint8_t> has;                       // [n_q] 1 = the query's kept cells are pairs of stage 2
@@ -535,11 +537,29 @@ struct __attribute__((visibility("hidden"))) CascadeCall {
     long long* d_kept = nullptr; const int32_t* d_dev = nullptr; const int32_t* d_q_slot = nullptr; int32_t* d_tab = nullptr;
     float* d_pparts = nullptr; float* d_pscore = nullptr; float* d_kparts = nullptr;    // pair parts [total][4], pair scores [total], own_kept_parts' array
     int64_t h2d_bytes = 0;
+    Shard& shard() const { return sub ? sub->sh : static_cast<Shard&>(*ctx); }
     void clear() { for (int64_t* o : opts) *o = 0; }
     int empty(int rc, int64_t* n_kept, int64_t* kept_idx, float* kept_parts);
     int check_limits();
     int run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts);
     int end(int rc, float* scores);
 };
+// Where a latent cascade over a sub-shard reads and writes (afis_cascade_eligible.cpp; the kernels of cascade_mapped.hip): inv [templates of the resident shard] the
+// sub-shard position of a resident position or -1, out_col [m] the column of the combined matrix a sub-shard position is written to, row_of [n_q] its row — each may be
+// empty: the identity —, and the matrix ctx->elig_scores as [out_rows][out_stride].  The three tables go up with the call's other tables
+struct CascadeMap { const std::vector<int32_t>* inv; const std::vector<int32_t>* out_col; const std::vector<int32_t>* row_of; int64_t out_rows, out_stride; };
+// afis_search_cascade's side of the driver behind its argument checks: the handle's queries and groups, the kernels of cascade.hip — with map == NULL its gather and
+// scatter for the resident shard, else cascade_mapped.hip's pair — and the driver's run.  Hidden, as rank_subjects above.
+int latent_cascade(CascadeCall& c, afis_queries* q, const CascadeMap* map, int64_t* n_kept, int64_t* kept_idx, float* kept_parts) __attribute__((visibility("hidden")));
+// afis_eligible.cpp: the class plan of a batch (afis_search_eligible, afis_search_cascade_eligible) and the host side of a class's temporary sub-shard
+// one class: the queries (ascending position) that share a mask triple, and the templates of the shard (ascending shard-local index) the triple passes
+struct EligClass {
+    uint64_t any_of, all_of, none_of;
+    std::vector<int32_t> rows, sel;
+};
+// classes in order of first query position; a triple of zeros lists every template without looking at the labels
+std::vector<EligClass> plan_classes(const std::vector<uint64_t>& label, int64_t G, const uint64_t* masks, int n_q) __attribute__((visibility("hidden")));
+// the host side of a temporary sub-shard, as afis_subset_create lays it out for a list that is already ascending; what an earlier class built in the same buffers goes
+void plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, std::vector<int64_t>& global) __attribute__((visibility("hidden")));
 
 }  // namespace afis

@@ -289,6 +289,16 @@ hipError_t launch_cascade_gather(int n_q, int G, int keep, int n_kept, long long
                                  int n_pieces, const int32_t* piece_q0, const float* parts, int32_t* tab, float* pair_parts, hipStream_t stream);
 hipError_t launch_cascade_scatter(int n_q, int G, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot, const float* pair_score,
                                   float* out, hipStream_t stream);
+// The mapped forms (cascade_mapped.hip), for a cascade over a sub-shard of m templates of the resident shard (G_res templates): inv [G_res] int32 = the sub-shard position of a resident
+// position or -1 (NULL: the identity, m == G_res), parts [n_q][m][4].  A kept entry that names no template of the sub-shard is routed to template 0 and scattered
+// nowhere.  launch_cascade_scatter_mapped writes the kept cell (q, template gi) at out[row_of[q] * out_stride + out_col[gi]] (NULL tables: q, gi), out being
+// [out_rows][out_stride]; a target outside it is not written.
+hipError_t launch_cascade_gather_mapped(int n_q, int G_res, int m, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot,
+                                        const int32_t* piece_first, int n_pieces, const int32_t* piece_q0, const int32_t* inv, const float* parts, int32_t* tab,
+                                        float* pair_parts, hipStream_t stream);
+hipError_t launch_cascade_scatter_mapped(int n_q, int G_res, int m, int keep, int n_kept, long long index_base, const long long* kept, const int32_t* q_slot,
+                                         const float* pair_score, const int32_t* inv, const int32_t* row_of, const int32_t* out_col, long long out_rows, long long out_stride,
+                                         float* out, hipStream_t stream);
 
 // S11: per-query rank list over the shard's scores [n_q][G] on the device (score descending, index ascending); out_idx[n_q][k] carries
 // index_base + local index (-1 / -inf beyond G)

@@ -10,19 +10,14 @@ using namespace afis;
 
 namespace {
 
-// one class: the queries (ascending position) that share a mask triple, and the templates of the shard (ascending shard-local index) the triple passes
-struct EligClass {
-    uint64_t any_of, all_of, none_of;
-    std::vector<int32_t> rows, sel;
-};
-
 inline bool label_passes(uint64_t L, uint64_t any_of, uint64_t all_of, uint64_t none_of)
 {
     return (any_of == 0 || (L & any_of) != 0) && (L & all_of) == all_of && (L & none_of) == 0;
 }
 
-// classes in order of first query position; a triple of zeros lists every template without looking at the labels
-std::vector<EligClass> plan_classes(const std::vector<uint64_t>& label, int64_t G, const uint64_t* masks, int n_q)
+}  // namespace
+
+std::vector<EligClass> afis::plan_classes(const std::vector<uint64_t>& label, int64_t G, const uint64_t* masks, int n_q)
 {
     std::vector<EligClass> cls;
     for (int i = 0; i < n_q; ++i) {
@@ -37,8 +32,6 @@ std::vector<EligClass> plan_classes(const std::vector<uint64_t>& label, int64_t 
     return cls;
 }
 
-}  // namespace
-
 // every additive field is the sum over the searches of the call; the two clock fields come from the search with the most pairs (afis_search_weighted's batches too)
 void afis::add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pairs)
 {
@@ -50,10 +43,7 @@ void afis::add_timing(afis_timing& acc, const afis_timing& t, int64_t& most_pair
     if (t.pairs > most_pairs) { most_pairs = t.pairs; acc.bound_clock_ghz = t.bound_clock_ghz; acc.cands_clock_ghz = t.cands_clock_ghz; }
 }
 
-namespace {
-
-// the host side of a temporary sub-shard, as afis_subset_create lays it out for a list that is already ascending; what an earlier class built in the same buffers goes
-void plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, std::vector<int64_t>& global)
+void afis::plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>& sel, std::vector<int64_t>& global)
 {
     const size_t n = sel.size();
     Shard& sh = sub->sh;
@@ -71,6 +61,8 @@ void plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int32_t>&
     sub->idx = global;
     sh.mf_gal_built = false; sh.codes_q_built = false; sh.codes_cf_built = false;      // the derived streams are this class's to lay out (their buffers stay)
 }
+
+namespace {
 
 // Everything of the call that touches the device.  tmp, d_sel and d_tab are the caller's to release, whatever this returns.
 int search_classes(afis_ctx* ctx, const std::vector<EligClass>& classes, const afis_template_view* queries, int n_q, int32_t* status, afis_subset* tmp, DevBuf& d_sel, DevBuf& d_tab)

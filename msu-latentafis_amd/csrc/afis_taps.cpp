@@ -2,6 +2,8 @@
 // (adc_direct.hip, adc_variant 0-3, 6, 7).  Built ONLY into libafis_hip_test.so, with adc_direct.o; the product library exports none of the taps and has none of the kernels.
 #include "afis_ctx.h"
 #include "../../include/afis_matcher_taps.h"
+#include "cascade_tables.h"
+#include "pair_tables.h"
 
 using namespace afis;
 
@@ -215,6 +217,57 @@ int afis_debug_expand_rows(afis_ctx* ctx, const float* cls, int n_c, int64_t m, 
     HIPCHK(ctx, launch_expand_rows(d_cls.as<float>(), n_c, (int)m, inv.empty() ? nullptr : d_inv.as<int32_t>(), d_rows.as<int32_t>(), n_q, (int)G, d_out.as<float>(), s));
     { const int rcw = wait_streams(ctx, {s}, "afis_debug_expand_rows"); if (rcw != AFIS_OK) return rcw; }
     HIPCHK(ctx, hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return AFIS_OK;
+}
+
+// k_cascade_gather_mapped and k_cascade_scatter_mapped on planted tables: the structure is made as the cascade driver makes it (cascade_tables.h), in buffers of the call's own
+int afis_debug_kept_cells_mapped(afis_ctx* ctx, int n_q, int64_t G_res, int64_t m, int keep, int n_kept, int64_t index_base, const int64_t* kept, const uint8_t* has,
+                              const int32_t* q_first, int n_grp, int per_launch, const int32_t* sel, const float* parts, const float* pair_score, const int32_t* row_of,
+                              const int32_t* out_col, int64_t out_rows, int64_t out_stride, int32_t* tab, int64_t tab_ints, int32_t* n_pieces, float* pair_parts, float* out)
+{
+    const char* const who = "afis_debug_kept_cells_mapped";
+    if (!ctx || n_q <= 0 || G_res <= 0 || G_res > 0x7fffffff || m <= 0 || m > G_res || (!sel && m != G_res) || keep < 1 || keep > AFIS_HITS_MAX || n_kept < 1 || n_kept > keep ||
+        n_kept > m || !kept || !has || !q_first || n_grp < 1 || per_launch < 1 || !parts || !pair_score || out_rows <= 0 || out_stride <= 0 ||
+        out_rows * out_stride > 0x7ffffff0LL || (int64_t)n_q * m > 0x7ffffff0LL / 4 || !tab || !n_pieces || !pair_parts || !out)
+        return fail(ctx, AFIS_EINVAL, std::string(who) + ": bad argument");
+    if (q_first[0] != 0 || q_first[n_grp] != n_q) return fail(ctx, AFIS_EINVAL, std::string(who) + ": q_first must run from 0 to n_q");
+    for (int g = 0; g < n_grp; ++g) if (q_first[g + 1] < q_first[g]) return fail(ctx, AFIS_EINVAL, std::string(who) + ": q_first must ascend");
+    std::vector<int32_t> inv;
+    if (sel) {
+        inv.assign((size_t)G_res, -1);
+        for (int64_t i = 0; i < m; ++i) {
+            if (sel[i] < 0 || sel[i] >= G_res || (i > 0 && sel[i] <= sel[i - 1])) return fail(ctx, AFIS_EINVAL, std::string(who) + ": sel must be strictly ascending positions of the resident shard");
+            inv[(size_t)sel[i]] = (int32_t)i;
+        }
+    }
+    for (int q = 0; q < n_q && row_of; ++q) if (row_of[q] < 0 || row_of[q] >= out_rows) return fail(ctx, AFIS_EINVAL, std::string(who) + ": row_of must hold rows of out");
+    for (int64_t t = 0; t < m && out_col; ++t) if (out_col[t] < 0 || out_col[t] >= out_stride) return fail(ctx, AFIS_EINVAL, std::string(who) + ": out_col must hold columns of out");
+    CascadeTables t;
+    if (!build_cascade_tables((size_t)n_q, has, (size_t)n_kept, (size_t)n_grp, q_first, kAdcPairsSegment, (size_t)per_launch, t) || (int64_t)t.tab_ints() > tab_ints)
+        return fail(ctx, AFIS_EINVAL, std::string(who) + ": tab does not hold the pair tables");
+    *n_pieces = (int32_t)t.pieces.size();
+    { const int rcq = quiesce(ctx, who); if (rcq != AFIS_OK) return rcq; }
+    DevBuf b[10];
+    struct Drop { DevBuf* b; ~Drop() { for (int i = 0; i < 10; ++i) b[i].release(); } } drop{b};
+    const size_t total = t.total, out_bytes = (size_t)out_rows * (size_t)out_stride * 4;
+    const struct Up { const void* src; size_t bytes; } ups[10] = {{kept, (size_t)n_q * (size_t)keep * 8}, {t.dev.data(), t.dev.size() * 4}, {inv.data(), inv.size() * 4},
+        {parts, (size_t)n_q * (size_t)m * 16}, {pair_score, total * 4}, {row_of, row_of ? (size_t)n_q * 4 : 0}, {out_col, out_col ? (size_t)m * 4 : 0}, {tab, (size_t)tab_ints * 4},
+        {pair_parts, total * 16}, {out, out_bytes}};
+    for (int i = 0; i < 10; ++i) {
+        HIPCHK(ctx, b[i].ensure(std::max<size_t>(ups[i].bytes, 16)));
+        if (ups[i].bytes) HIPCHK(ctx, hipMemcpy(b[i].p, ups[i].src, ups[i].bytes, hipMemcpyHostToDevice));
+    }
+    hipStream_t s = ctx->stream;
+    const int32_t* const d_dev = b[1].as<int32_t>();
+    const int32_t* const d_inv = sel ? b[2].as<int32_t>() : nullptr;
+    HIPCHK(ctx, launch_cascade_gather_mapped(n_q, (int)G_res, (int)m, keep, n_kept, index_base, b[0].as<long long>(), d_dev + t.q_slot_at, d_dev + t.piece_first_at, (int)t.pieces.size(),
+                                             d_dev + t.piece_q0_at, d_inv, b[3].as<float>(), b[7].as<int32_t>(), b[8].as<float>(), s));
+    HIPCHK(ctx, launch_cascade_scatter_mapped(n_q, (int)G_res, (int)m, keep, n_kept, index_base, b[0].as<long long>(), d_dev + t.q_slot_at, b[4].as<float>(), d_inv,
+                                              row_of ? b[5].as<int32_t>() : nullptr, out_col ? b[6].as<int32_t>() : nullptr, (long long)out_rows, (long long)out_stride, b[9].as<float>(), s));
+    { const int rcw = wait_streams(ctx, {s}, who); if (rcw != AFIS_OK) return rcw; }
+    HIPCHK(ctx, hipMemcpy(tab, b[7].p, (size_t)tab_ints * 4, hipMemcpyDeviceToHost));
+    if (total) HIPCHK(ctx, hipMemcpy(pair_parts, b[8].p, total * 16, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, b[9].p, out_bytes, hipMemcpyDeviceToHost));
     return AFIS_OK;
 }
 

@@ -71,11 +71,11 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
-               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates", "afis_debug_print_queries"]
+               "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates", "afis_debug_print_queries", "afis_debug_kept_cells_mapped"]
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -158,6 +158,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_correspondences_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, i32p, C.POINTER(C.c_int16), fp]
     if hasattr(lib, "afis_search_cascade"):                             # cascade search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_cascade.argtypes = [vp, vp, C.c_int, fp, i32p, i64p, i64p, fp]
+    if hasattr(lib, "afis_search_cascade_subset"):                      # cascade over a subset / the eligible prints; absent from older builds compared by tools/lib_ab.py
+        lib.afis_search_cascade_subset.argtypes = [vp, vp, vp, C.c_int, fp, i32p, i64p, i64p, fp]
+        lib.afis_search_cascade_eligible.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TemplateView), C.c_int, C.c_int, fp, i32p, i64p, i64p, fp]
     if hasattr(lib, "afis_search_prints_cascade"):                      # print cascade; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_prints_cascade.argtypes = [vp, i64p, C.c_int, fp, fp, C.c_int, fp, i32p, i64p, i64p, fp]
     lib.afis_queries_free.argtypes = [vp, vp]; lib.afis_queries_free.restype = None
@@ -197,6 +200,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_debug_expand_rows.argtypes = [vp, fp, C.c_int, C.c_int64, i32p, i32p, C.c_int, C.c_int64, fp]
     if hasattr(lib, "afis_debug_fold_templates"):
         lib.afis_debug_fold_templates.argtypes = [vp, fp, C.c_int64, C.c_int64, i32p, C.c_int, fp, C.POINTER(C.c_uint8), fp]
+    if hasattr(lib, "afis_debug_kept_cells_mapped"):
+        u8p = C.POINTER(C.c_uint8)
+        lib.afis_debug_kept_cells_mapped.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, i64p, u8p, i32p, C.c_int, C.c_int, i32p, fp, fp, i32p, i32p,
+                                                  C.c_int64, C.c_int64, i32p, C.c_int64, i32p, fp, fp]
     if hasattr(lib, "afis_debug_print_queries"):
         u8p, i16p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
         lib.afis_debug_print_queries.argtypes = [vp, i64p, C.c_int, u8p, u8p, i32p] + [i32p] * 7 + [i16p, fp, fp, fp, i16p, fp, fp]
@@ -722,6 +729,67 @@ class Matcher:
                                                _ptr(kept_parts, C.c_float) if want_kept else None))
         self.last_n_q = n; self.last_n_templates = G
         return {"scores": scores, "status": status, "n_kept": n_kept, "kept_idx": kept_idx, "kept_parts": kept_parts}
+
+    def _cascade_out(self, n: int, cols: int, keep: int, want_scores: bool, want_kept: bool):
+        wide = max(keep, 1)
+        scores = np.empty((n, cols), np.float32) if want_scores else None
+        status = np.zeros(n, np.int32)
+        n_kept = np.zeros(n, np.int64) if want_kept else None
+        kept_idx = np.full((n, wide), -1, np.int64) if want_kept else None
+        kept_parts = np.zeros((n, wide, 4), np.float32) if want_kept else None
+        args = (_ptr(scores, C.c_float) if want_scores else None, _ptr(status, C.c_int32), _ptr(n_kept, C.c_int64) if want_kept else None,
+                _ptr(kept_idx, C.c_int64) if want_kept else None, _ptr(kept_parts, C.c_float) if want_kept else None)
+        return {"scores": scores, "status": status, "n_kept": n_kept, "kept_idx": kept_idx, "kept_parts": kept_parts}, args
+
+    def search_cascade_subset(self, subset, handle, keep: int, want_scores: bool = True, want_kept: bool = True):
+        """afis_search_cascade_subset: search_cascade() over the columns of a subset_create handle.  "scores" [n_q][n] in the caller's column order — a kept cell is bit
+        for bit search_subset_resident()'s, every other the no-entry word —, "n_kept" = min(keep, n), "kept_idx" global indices in stage-1 rank order (equal keys by
+        ascending global index), "kept_parts" [n_q][keep][4].  The matrix left on the device is a subset search's: the rank_* calls name its columns by global index
+        and see the kept cells only.  The options are search_cascade's."""
+        sh, n_cols = subset
+        h, n = handle
+        keep = int(keep)
+        out, args = self._cascade_out(n, n_cols, keep, want_scores, want_kept)
+        self._chk(self.lib.afis_search_cascade_subset(self.ctx, sh, h, keep, *args))
+        self.last_n_q = n; self.last_n_templates = n_cols
+        return out
+
+    def search_cascade_eligible(self, latents: Sequence[FPTemplate], labels, masks, keep: int, want_scores: bool = True, want_kept: bool = True):
+        """afis_search_cascade_eligible: search_eligible()'s arguments plus keep — per latent the cascade over the templates whose label passes its masks only.  "n_kept"
+        = min(keep, eligible templates); the kept prints are the best `keep` ELIGIBLE ones by the stage-1 score; a kept cell of "scores" [n_q][G] is bit for bit
+        search()'s, every other cell — dropped or not eligible — the no-entry word.  The matrix left on the device reads as search_eligible's.
+        get_option("eligible_classes"); the "cascade_*" options hold the sums over the classes."""
+        v = _Views(latents)
+        mk = None if masks is None else np.ascontiguousarray(np.asarray(masks, np.uint64).reshape(v.n, 3))
+        if mk is not None and v.n == 0:
+            mk = np.zeros((1, 3), np.uint64)                                 # (no query: the C call still wants a masks pointer)
+        keep = int(keep)
+        G = self.resident_size
+        out, args = self._cascade_out(v.n, G, keep, want_scores, want_kept)
+        self._chk(self.lib.afis_search_cascade_eligible(self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, v.arr, v.n,
+                                                        keep, *args))
+        self.last_n_q = v.n; self.last_n_templates = G
+        return out
+
+    def debug_kept_cells_mapped(self, G_res: int, m: int, keep: int, n_kept: int, index_base: int, kept, has, q_first, per_launch: int, sel, parts, pair_score, row_of, out_col,
+                             out: np.ndarray, tab_ints: int):
+        """k_cascade_gather_mapped and k_cascade_scatter_mapped on planted tables (parity tap; include/afis_matcher_taps.h has the shapes).  sel / row_of / out_col may be
+        None (the identity).  -> {"tab" [tab_ints] int32 (planted with -7 before the call), "n_pieces", "pair_parts" [pairs][4] uint32 (planted with 0xa5a5a5a5), "out"}."""
+        kp = np.ascontiguousarray(np.asarray(kept, np.int64)); n_q = kp.shape[0]
+        hs = np.ascontiguousarray(np.asarray(has, np.uint8)); qf = np.ascontiguousarray(np.asarray(q_first, np.int32))
+        pt = np.ascontiguousarray(parts).view(np.float32).reshape(n_q, m, 4)
+        ps = np.ascontiguousarray(pair_score).view(np.float32).reshape(-1)
+        opt = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+        se, ro, oc = opt(sel), opt(row_of), opt(out_col)
+        p32 = lambda a: None if a is None else _ptr(a, C.c_int32)
+        o = np.array(out, copy=True, order="C").view(np.float32)
+        tab = np.full(tab_ints, -7, np.int32); n_pieces = np.zeros(1, np.int32)
+        pp = np.full((max(len(ps), 1), 4), 0xA5A5A5A5, np.uint32)
+        self._chk(self._tap("afis_debug_kept_cells_mapped")(self.ctx, n_q, G_res, m, keep, n_kept, index_base, _ptr(kp, C.c_int64), _ptr(hs, C.c_uint8), _ptr(qf, C.c_int32), len(qf) - 1,
+                                                         per_launch, p32(se), _ptr(pt, C.c_float), _ptr(ps, C.c_float) if len(ps) else _ptr(pp.view(np.float32), C.c_float),
+                                                         p32(ro), p32(oc), o.shape[0], o.shape[1], _ptr(tab, C.c_int32), tab_ints, _ptr(n_pieces, C.c_int32),
+                                                         _ptr(pp.view(np.float32), C.c_float), _ptr(o, C.c_float)))
+        return {"tab": tab, "n_pieces": int(n_pieces[0]), "pair_parts": pp[:len(ps)], "out": o.view(np.asarray(out).dtype)}
 
     # ---- print cascade: resident prints as queries, minutiae for every column, texture for the best `keep` only ----------
     def search_prints_cascade(self, idx, w_minu, w_tex, keep: int, want_scores: bool = True, want_kept: bool = True):

@@ -19,7 +19,9 @@ way the per-rank lists read from the matrix are merge_hits / merge_subject_hits 
 A cascade search (Matcher.search_cascade) keeps per latent the `keep` best prints by the minutiae scorers alone: every rank keeps `keep` of its own shard.  The per-rank
 lists read from its matrix are merge_hits / merge_subject_hits input as they are; their union contains the global stage-1 top `keep`, so the merged result is a
 superset of the single-context cascade over the whole gallery, not the same list.  A print cascade (Matcher.search_prints_cascade) combines both rules: a print is a
-query only on the rank that holds it, every rank keeps `keep` of its own shard, and the merged lists are a superset of the single-context result.
+query only on the rank that holds it, every rank keeps `keep` of its own shard, and the merged lists are a superset of the single-context result.  A cascade over a part
+of the shard (Matcher.search_cascade_eligible, Matcher.search_cascade_subset) needs no new merge either: every rank keeps `keep` of its own shard's eligible (or listed)
+prints, and the per-rank lists are merge_hits input as they are, a superset of the single-context result.
 """
 from __future__ import annotations
 
