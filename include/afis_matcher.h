@@ -692,6 +692,58 @@ int afis_pq_encode(afis_ctx* ctx, const float* des, int64_t n, uint8_t* codes);
  * (:178-272), texture descriptors replaced by PQ codes.  out == NULL only reports *out_len.  load_rc: the reader's code. */
 int afis_encode_rolled_dat(afis_ctx* ctx, const void* bytes, size_t len, void* out, size_t out_cap, size_t* out_len, int* load_rc);
 
+/* Codebook training — replaces training (extraction/descriptor_PQ.py:41-77: scipy.cluster.vq.kmeans2 per sub-space, minit='points') for the one geometry
+ * afis_create accepts, codebook [16][256][6] fp32 over points des [n][96] fp32.  No context: a context needs a codebook; device_id as afis_device_info's, the error text
+ * where afis_create's goes (afis_last_error with a NULL context).
+ *
+ * One Lloyd step is defined bit for bit and independent of the order of its additions, so that the device, a numpy model (tests/pq_train_model.py) and, later, the
+ * ranks of a sharded training set agree to the bit.  With C the current codebook, for every point i and sub-quantizer m:
+ *   assignment    label[i][m] = the code afis_pq_encode returns for point i under C (the fp32 |x|^2 + |c|^2 - 2 x.c expansion, fma chain over d ascending, first
+ *                 strict minimum from +inf: csrc/pq_nearest.h, the one definition the encoder's kernel and the trainer's share)
+ *   accumulation  q(x) = (int64) rint((double) x * 2^30), round to nearest even (the widening and the scaling are exact: one rounding); per (m, k) count[m][k] = the
+ *                 points with label[i][m] == k and S[m][k][d] = the int64 sum of q(des[i][6m + d]) over them.  Integer addition is associative: atomics,
+ *                 per-workgroup partial sums and any tiling give the same words
+ *   update        count > 0: C'[m][k][d] = (float)((double) S / ((double) count * 1073741824.0)) — one int64 -> fp64 conversion (nearest even), one IEEE fp64
+ *                 division (the divisor is exact), one fp64 -> fp32 rounding, done on the host between steps; count == 0: the codeword keeps its old BITS
+ *                 (kmeans2's missing='warn' without the warning)
+ *   range         every component of des finite with |x| <= 64 and n <= 2^26 (then |q| <= 2^36 and |S| <= 2^62); init finite.  A violation is AFIS_EINVAL before
+ *                 any output is written: des is checked on the device in the first pass over the points.
+ * afis_pq_train runs `iters` such steps from init.
+ *   codewords  [16][256][6]   the codebook after the last step
+ *   counts     [16][256] or NULL : count[m][k] of the last executed assignment (the assignment that produced codewords)
+ *   changed    [iters] or NULL   : changed[t] = the (i, m) labels of step t that differ from step t - 1's; changed[0] = 16 n
+ *   iters_run  or NULL           : the steps executed.  When changed[t] == 0 for a t >= 1 the codebook is a fixed point — step t + 1 would reproduce step t's labels,
+ *                                  sums and codewords — and the call stops after step t: iters_run = t + 1, the remaining changed entries are 0, and every output
+ *                                  is what the full run of `iters` steps would have given
+ * iters == 0 or n == 0: AFIS_OK without device work, codewords = init's bits, counts 0, changed 0, iters_run 0.  iters outside 0 .. 1000, n < 0 or n > 2^26, a NULL
+ * des / init / codewords, a device_id out of range: AFIS_EINVAL; no usable gfx950 device or a failed allocation: AFIS_EDEVICE.  The points stay resident on the device
+ * across the steps — 384 n bytes transposed to [16][n][6], 16 n bytes of labels, one upload slice of at most 96 MiB — all allocated before anything is queued; per step
+ * only the codebook (96 KB down) and the sums and counts (224 KB up) move.  Every host wait is bounded by AFIS_SEARCH_TIMEOUT_S as a search's is.
+ *
+ * afis_pq_train_init_points (host only, as afis_rank_list): kmeans2's minit='points' made reproducible.  Per sub-quantizer m it draws 256 DISTINCT point indices and
+ * copies those points' sub-vectors: init[m][k] = des[idx(m, k)][6m .. 6m + 5].  The generator is counter-based, splitmix64's output function
+ *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31   (uint64 arithmetic)
+ *   draw(m, j) = mix(mix(seed) + 256 m + j)
+ * and the indices are the first 256 steps of a Fisher-Yates shuffle of a = (0, .., n - 1): step j = 0 .. 255 swaps a[j] with a[j + draw(m, j) mod (n - j)], and
+ * idx(m, j) is the new a[j] (csrc/pq_train_plan.h).  n < 256 is AFIS_EINVAL (the reference's assert Ks < N).  Distinct points may hold equal values: the later of two
+ * equal codewords never wins the first-minimum rule, so its cluster stays empty (and keeps its bits) until its twin has moved — kmeans2 behaves the same way.
+ *
+ * afis_codebook_write: the bytes afis_create_from_codebook reads — the 3 x int16 header 16, 256, 6 and the 24 576 floats (98 310 bytes); out == NULL only reports
+ * *out_len; another geometry or a buffer too small is AFIS_EINVAL.
+ *
+ * Not in this interface: geometries other than 16 x 256 x 6; k-means++ or any other initialisation (the caller may pass any finite init); a per-rank partial-sum
+ * call for sharded training sets (the integer sums make it exact when someone builds it); training from a resident gallery (the shard holds codes, not descriptors).
+ *
+ * Cost (profiles/pq_train_timing.json, one MI355X; 10^6 clustered points x 20 steps, medians of three interleaved rounds after a discarded first, spread in brackets):
+ * the call 40.1 ms on the host's clock (0.8) — the first pass, 384 MB of upload and the transpose, 7.1 ms (0.3), a step 1.283 ms of device time (0.011) — where
+ * scipy's kmeans2 per sub-space on the same machine's CPUs, 16 threads, takes 10.9 s for two iterations (108.6 s scaled to twenty).  The step kernel takes 0.98 of
+ * the encoder kernel's time at the same n (1.427 ms against 1.450 ms under the profiler): the accumulation costs nothing measurable beside the 256-codeword search.
+ * DESIGN section 7, "Codebook training (row 23)", has the kernels and the breakdown. */
+int afis_pq_train(int device_id, const float* des /*[n][96]*/, int64_t n, const float* init /*[16][256][6]*/, int iters,
+                  float* codewords /*[16][256][6]*/, int64_t* counts /*[16][256] or NULL*/, int64_t* changed /*[iters] or NULL*/, int* iters_run /*or NULL*/);
+int afis_pq_train_init_points(const float* des /*[n][96]*/, int64_t n, uint64_t seed, float* init /*[16][256][6]*/);
+int afis_codebook_write(const float* codewords, int M, int K, int dsub, void* out, size_t out_cap, size_t* out_len);
+
 /* Correspondence export — replaces One2One_matching_selected_templates(..., save_corr = true, corr_file) as called for the
  * top-24 of One2List_matching (matching/matcher.cpp:321-327, :376-417, :497-505).  For one latent and each of the n listed
  * gallery templates (indices as reported by afis_search, i.e. including index_base) it re-runs the three minutiae scorers and

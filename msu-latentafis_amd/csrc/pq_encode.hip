@@ -11,10 +11,12 @@
 // in LDS and walks tiles of 64 points; wave m owns sub-quantizer m, lane = point.  Every lane of a wave reads the same codeword (LDS broadcast,
 // conflict-free); the descriptor tile is staged through LDS with coalesced 4-byte loads and a padded row (97 floats) so the
 // per-lane reads of 6 consecutive floats hit distinct banks.  9 VALU + 1 compare + 2 selects per (point, codeword).
+// The search itself is pq_nearest.h's, shared with the codebook trainer (pq_train.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "afis_device.h"
+#include "pq_nearest.h"
 
 namespace afis {
 
@@ -31,12 +33,7 @@ __global__ __launch_bounds__(1024) void k_pq_encode(const float* __restrict__ de
     const int tid = threadIdx.x, lane = tid & 63;
     const int m = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int i = tid; i < kM * kK * kDsub; i += 1024) s_cw[i] = codewords[i];
-    for (int e = tid; e < kM * kK; e += 1024) {
-        float s = 0.0f;
-#pragma unroll
-        for (int d = 0; d < kDsub; ++d) { const float w = codewords[e * kDsub + d]; const float t = w * w; s += t; }
-        s_csq[e] = s;
-    }
+    for (int e = tid; e < kM * kK; e += 1024) s_csq[e] = pq_sqnorm6(codewords + e * kDsub);
     const long long n_tiles = (n + kEncPts - 1) / kEncPts;
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long p0 = tile * kEncPts;
@@ -45,21 +42,10 @@ __global__ __launch_bounds__(1024) void k_pq_encode(const float* __restrict__ de
         for (int i = tid; i < np * kDes; i += 1024) s_des[(i / kDes) * kEncStride + (i % kDes)] = des[p0 * kDes + i];
         __syncthreads();
         if (lane < np) {
-            float x[kDsub], xsq = 0.0f;
+            float x[kDsub];
 #pragma unroll
-            for (int d = 0; d < kDsub; ++d) { x[d] = s_des[lane * kEncStride + m * kDsub + d]; const float t = x[d] * x[d]; xsq += t; }
-            const float* cw = s_cw + m * kK * kDsub;
-            const float* csq = s_csq + m * kK;
-            float best = INFINITY; int arg = 0;
-#pragma unroll 4
-            for (int k = 0; k < kK; ++k) {
-                float dot = 0.0f;
-#pragma unroll
-                for (int d = 0; d < kDsub; ++d) dot = __builtin_fmaf(cw[k * kDsub + d], x[d], dot);
-                const float t = -2.0f * dot + xsq;             // (-ffp-contract=off: the product -2 dot is exact, the sum rounds once)
-                const float dist = t + csq[k];
-                if (dist < best) { best = dist; arg = k; }     // strict: the first minimum wins
-            }
+            for (int d = 0; d < kDsub; ++d) x[d] = s_des[lane * kEncStride + m * kDsub + d];
+            const int arg = pq_nearest(s_cw + m * kK * kDsub, s_csq + m * kK, x);       // pq_nearest.h: the search the trainer's assignment shares
             reinterpret_cast<uint8_t*>(s_codes)[lane * kM + m] = (uint8_t)arg;
         }
         __syncthreads();

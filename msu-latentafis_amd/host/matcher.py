@@ -72,7 +72,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
            "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
-           "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
+           "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
                "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates", "afis_debug_print_queries", "afis_debug_kept_cells_mapped"]
@@ -167,6 +167,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.afis_match_all_templates.argtypes = [vp, vp, fp, i32p, i32p]
     lib.afis_pq_encode.argtypes = [vp, fp, C.c_int64, C.POINTER(C.c_uint8)]
     lib.afis_encode_rolled_dat.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), i32p]
+    if hasattr(lib, "afis_pq_train"):
+        lib.afis_pq_train.argtypes = [C.c_int, fp, C.c_int64, fp, C.c_int, fp, i64p, i64p, i32p]
+        lib.afis_pq_train_init_points.argtypes = [fp, C.c_int64, C.c_uint64, fp]
+        lib.afis_codebook_write.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.afis_get_timing.argtypes = [vp, C.POINTER(Timing)]
     if hasattr(lib, "afis_get_timing2"):                                # absent from older builds compared by tools/lib_ab.py
         lib.afis_get_timing2.argtypes = [vp, C.POINTER(Timing), C.c_size_t]
@@ -212,6 +216,46 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
 
 def _ptr(a: np.ndarray, t):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+def _train_chk(lib, rc, who):
+    if rc != 0:
+        raise AfisError(f"{who} failed ({rc}): {lib.afis_last_error(None).decode()}")
+
+
+def pq_train(des, init, iters: int = 20, device: int = 0, lib_path: Optional[str] = None) -> dict:
+    """afis_pq_train: `iters` Lloyd steps of the codebook [16][256][6] over the points des [n][96] on the device, from `init`, in the order-independent definition
+    of include/afis_matcher.h.  Returns codewords [16][256][6], counts [16][256] (the last executed assignment's), changed [iters] and iters_run."""
+    lib = load_library(lib_path or LIB_PATH)
+    des = np.ascontiguousarray(des, np.float32).reshape(-1, 96)
+    init = np.ascontiguousarray(init, np.float32).reshape(16, 256, 6)
+    cw = np.zeros((16, 256, 6), np.float32); counts = np.zeros((16, 256), np.int64); changed = np.zeros(max(int(iters), 1), np.int64); run = C.c_int32(0)
+    rc = lib.afis_pq_train(device, _ptr(des, C.c_float) if len(des) else None, des.shape[0], _ptr(init, C.c_float), int(iters), _ptr(cw, C.c_float),
+                           _ptr(counts, C.c_int64), _ptr(changed, C.c_int64), C.byref(run))
+    _train_chk(lib, rc, "afis_pq_train")
+    return {"codewords": cw, "counts": counts, "changed": changed[:max(int(iters), 0)], "iters_run": int(run.value)}
+
+
+def pq_train_init_points(des, seed: int, lib_path: Optional[str] = None) -> np.ndarray:
+    """afis_pq_train_init_points (host only): kmeans2's minit='points' from a seed — per sub-quantizer the sub-vectors of 256 distinct points."""
+    lib = load_library(lib_path or LIB_PATH)
+    des = np.ascontiguousarray(des, np.float32).reshape(-1, 96)
+    init = np.zeros((16, 256, 6), np.float32)
+    _train_chk(lib, lib.afis_pq_train_init_points(_ptr(des, C.c_float), des.shape[0], C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(init, C.c_float)), "afis_pq_train_init_points")
+    return init
+
+
+def codebook_bytes(codewords, lib_path: Optional[str] = None) -> bytes:
+    """afis_codebook_write: the codebook file afis_create_from_codebook (and Matcher) reads, for codewords [16][256][6]."""
+    lib = load_library(lib_path or LIB_PATH)
+    cw = np.ascontiguousarray(codewords, np.float32)
+    if cw.shape != (16, 256, 6):
+        raise AfisError(f"codebook_bytes: codewords must be [16][256][6], not {list(cw.shape)}")
+    need = C.c_size_t(0)
+    _train_chk(lib, lib.afis_codebook_write(_ptr(cw, C.c_float), 16, 256, 6, None, 0, C.byref(need)), "afis_codebook_write")
+    out = C.create_string_buffer(need.value)
+    _train_chk(lib, lib.afis_codebook_write(_ptr(cw, C.c_float), 16, 256, 6, out, need.value, C.byref(need)), "afis_codebook_write")
+    return out.raw[:need.value]
 
 
 class _Views:
