@@ -10,8 +10,8 @@
 //   select    launch_rank_hits, unchanged, on that matrix at the ordered word of -inf with cap = keep: its device outputs are the kept lists
 //   stage 2   the STRUCTURE of the pair tables is known beforehand (cascade_tables.h: every query that has pairs keeps n_kept = min(keep, G) prints) and goes up once,
 //             before stage 1, with the caller's extra tables; the caller's gather kernel fills the tables from the kept lists (here k_cascade_gather, which also fills the
-//             pairs' parts blocks); per chunk of option cascade_pairs_per_launch pairs and launch group the pair kernels afis_score_pairs proved bit-exact —
-//             launch_adc_pairs, launch_graph_texture_pairs and, here, launch_fuse_pairs —; the caller's closing kernel writes the kept cells into the combined matrix
+//             pairs' parts blocks); per chunk of option cascade_pairs_per_launch pairs and launch group the pair kernels afis_score_pairs proved bit-exact, as
+//             that call queues them (queue_texture_pairs: the ADC kernel, the texture list kernel and, here, the fusion); the caller's closing kernel writes the kept cells into the combined matrix
 //             (ctx->elig_scores, filled with the no-entry word by a memset of 0xff bytes; here k_cascade_scatter), which is swapped in at the end
 // A kept pair whose print is empty or carries no texture template goes through the pair kernels as it is: k_adc_pairs skips a print without texture points before it
 // reads one (n_rt <= 0), k_graph_texture's pair form writes +0.0f for such a pair before it reads a row maximum (n_lt <= 0 || n_rt <= 0), fuse_cell gives an empty print its -1.
@@ -133,13 +133,8 @@ int CascadeCall::run(int64_t* n_kept, int64_t* kept_idx, float* kept_parts)
         const CascadePiece& pc = tabs.pieces[i];
         const QueryDev& qd = grps[pc.group].dev;
         const size_t in_chunk = pc.first - pc.chunk * (size_t)ctx->cascade_pairs_per_launch;      // the piece's place in its chunk's row maxima: in_chunk + n <= P, and the group's stride qd.lt_pad <= Lp
-        const int32_t* const p_tab = d_tab + 2 * pc.first + i;
-        float* const rm_val = (float*)(d + rmv_at) + in_chunk * Lp;
-        int32_t* const rm_arg = (int32_t*)(d + rma_at) + in_chunk * Lp;
-        float* const p_parts = d_pparts + pc.first * 4;
-        HIPCHK(ctx, launch_adc_pairs(qd, sh.gal, ctx->codewords.as<float>(), p_tab, d_dev + tabs.seg_at + 2 * pc.seg_first, (int)pc.n_seg, rm_val, rm_arg, s));
-        HIPCHK(ctx, launch_graph_texture_pairs(qd, sh.gal, p_tab, (int)pc.n, ctx->table.as<float>(), rm_val, rm_arg, p_parts, ctx->casc_slab.p, ctx->casc_slab.bytes, ctx->s89_tie_order, s));
-        if (fuse_pairs) HIPCHK(ctx, launch_fuse_pairs(qd, sh.gal, p_tab, (int)pc.n, p_parts, d_pscore + pc.first, s));
+        AFISCHK(queue_texture_pairs(ctx, sh.gal, qd, d_tab + 2 * pc.first + i, (int)pc.n, d_dev + tabs.seg_at + 2 * pc.seg_first, (int)pc.n_seg, (float*)(d + rmv_at) + in_chunk * Lp,
+                                    (int32_t*)(d + rma_at) + in_chunk * Lp, d_pparts + pc.first * 4, ctx->casc_slab, fuse_pairs ? d_pscore + pc.first : nullptr, s));
     }
     AFISCHK(finish());
     HIPCHK(ctx, hipEventRecord(ev[5], s));

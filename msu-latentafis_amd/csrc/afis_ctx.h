@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export: a pair list in one launch sequence), afis_pairs.cpp (pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -176,10 +176,9 @@ struct afis_ctx : Shard {
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
     DevBuf pos_tab, pos_out;             // afis_rank_positions / afis_rank_subject_positions / afis_count_before: the call's tables (the targets' composites [m] uint64 | rows | off | row [m] | position [m], int32) and its answers (count [m] uint64 | best_idx [m] int64 | status [m] int32 | score [m])
     int64_t rank_positions_us = 0;       // option rank_positions_us (read-only): device time of the last such call's launches (a filtered call's filter pass, for persons the maxima and the drops; k_position_targets, k_count_before)
-    DevBuf corr_buf;                     // afis_correspondences_pairs: one chunk's pair tables, candidate lists, survivors, counts and parts (about 5.8 KB per pair of option corr_pairs_per_launch)
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
-    DevBuf pair_buf, pair_tex_slab;      // afis_score_pairs: one chunk's candidate lists, survivor scratch, counts, dense row maxima, scores, parts and tables (kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch), and the texture list kernel's slab for a chunk's launches
+    DevBuf pair_buf, pair_tex_slab;      // every pair-list call (PairCall below has the layout), grown on demand: one chunk's candidate lists, survivors, counts, parts and tables — about 5.8 KB per pair of option corr_pairs_per_launch for afis_correspondences_pairs; with afis_score_pairs' dense row maxima and scores kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch —, and the texture list kernel's slab for a chunk's launches of afis_score_pairs
     int score_pairs_per_launch = kScorePairsPerLaunch;   // option score_pairs_per_launch: pairs per chunk of that call at most
     int64_t score_pairs_us = 0;          // option score_pairs_us (read-only): device time of the last afis_score_pairs' launches (HIP events around every chunk's, summed)
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
@@ -438,6 +437,44 @@ int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<Quer
 struct PrintPairWeights { const float* w_minu; const float* w_tex; };
 int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs, const int32_t* query, const int64_t* idx, int32_t* status, float* score, float* parts,
                 const PrintPairWeights* fold = nullptr) __attribute__((visibility("hidden")));
+// The texture stage of one pair table — [count | (query of the group qd, template of gal) x n] on the device, with its work list seg (pair_tables.h) — as the pair calls
+// and stage 2 of every cascade (CascadeCall::run) queue it: launch_adc_pairs -> the dense row maxima rm_val / rm_arg [n][qd.lt_pad], launch_graph_texture_pairs ->
+// parts[4 p + 3] (slab: the list kernel's, sized by the caller for its largest table) and, where score is given, launch_fuse_pairs -> score[p]
+int queue_texture_pairs(afis_ctx* ctx, const GalleryDev& gal, const QueryDev& qd, const int32_t* pair_tab, int n, const int32_t* seg, int n_seg, float* rm_val, int32_t* rm_arg,
+                        float* parts, const DevBuf& slab, float* score_or_null, hipStream_t stream) __attribute__((visibility("hidden")));
+// One pair-list call, whatever it returns: the pairs (query[i], idx[i]) of a handle's launch groups against the resident shard, in chunks of `per_launch` pairs, every
+// chunk one launch sequence with one upload and one copy back.  correspondences_pairs and score_pairs state what differs — the constants below and four callbacks —
+// run() is everything else, in this order:
+//   checks          *us = 0; query[] inside 0 .. n_q - 1; the groups add up to n_q
+//   needs_device(i) after the checks: the list of pairs that go to the device, in the caller's order; P = the pairs of a chunk at most
+//   room            the candidate grid (minu_cands_pairs_grid), scratch, minu_slab, with texture the call's texture slab, the call's device buffer ctx->pair_buf and the
+//                   pinned buffer: every allocation precedes the first write into the caller's arrays and everything queued — a failed one leaves the arrays untouched
+//   defaults()      what the caller's arrays hold without the device; no pair for the device: done
+//   per chunk       the tables in pinned memory (pair_tables.h::build_pair_tables: slots by launch group, then latent), event 0, ONE upload (the weights in slot order
+//                   behind it), per launch group with pairs launch_minu_cands_pairs, launch_graph_minutiae_pairs and stage(group), event 1, ONE copy back,
+//                   wait_elapsed, *us += the chunk's device time, then take(i, slot, back) for every slot: the caller's pair i from slot `slot` of the pinned copy
+// ctx->pair_buf, every area on a 256-byte boundary (P pairs, n_grp launch groups, lt_pad the handle's longest texture template):
+//   cands [3 P][120] | cand_n [3 P] | texture: rm_val [P][lt_pad] | rm_arg [P][lt_pad] | survivors [3 P][120] | their counts [3 P] | parts [P][4] | texture: score [P] |
+//   tab 2 P + n_grp ints, with texture the work list behind it, 2 P more | weights [P][2]
+// An area the call does not use takes no room.  What returns is one run of it — parts | score with texture, else survivors | counts | parts —, to the start of the pinned
+// buffer; behind it, in pinned memory too, a chunk's tables and weights on their way up (so that an early return leaves nothing queued that reads memory of this call).
+struct PairGroup {                                  // one launch group's share of a chunk, for stage(): its pair table and, of every per-pair area, the group's first slot
+    const QueryDev& qd; const int32_t* tab; int n; const int32_t* seg; int n_seg;
+    float* parts; float* rm_val; int32_t* rm_arg; float* score; const float* weights;
+};
+struct PairBack { const short4* corr; const int32_t* corr_n; const float* parts; const float* score; };   // the pinned copy's areas (slot 0 of each; NULL: not returned)
+struct __attribute__((visibility("hidden"))) PairCall {
+    afis_ctx* const ctx; const char* const who;
+    const std::vector<QueryGroup>& groups; const int n_q; const int64_t n_pairs; const int32_t* const query; const int64_t* const idx;
+    const int per_launch; int64_t* const us;        // the options the caller names: pairs per chunk at most, the device time summed over the chunks
+    const bool texture;                             // the score form: row maxima, scores and the work list have room, pair_tex_slab is sized, parts | score return
+    const PrintPairWeights* const weights;          // a print pair's two weights [n_pairs] each (NULL: no such area)
+    std::function<bool(int64_t)> needs_device;
+    std::function<void()> defaults;
+    std::function<int(const PairGroup&)> stage;     // (empty: nothing follows the minutiae launches)
+    std::function<void(int64_t, size_t, const PairBack&)> take;
+    int run();
+};
 // afis_subjects.cpp
 void release_subjects(afis_subjects* s);               // its device buffers and the handle itself
 // afis_rank_subjects behind its argument checks; the parity tap afis_debug_rank_subjects runs it too.  Hidden, as g_direct_adc_stage: each library calls its own copy.
@@ -511,8 +548,8 @@ struct __attribute__((visibility("hidden"))) FilterPass {
 //   check_limits()  n_q x keep and n_q x G within what one call takes
 //   run(..)         after the caller has filled in groups .. finish: the pair tables' structure (cascade_tables.h), room for everything before anything is queued, the
 //                   tables with the caller's extra ones to the device through the pinned buffer (h2d_bytes), stage 1 group after group (queue_minutiae_stage,
-//                   fuse_group), fuse_all, launch_rank_hits, the combined matrix in ctx->elig_scores filled with the no-entry word, gather, per piece launch_adc_pairs,
-//                   launch_graph_texture_pairs and (fuse_pairs) launch_fuse_pairs, finish, the read-back, ONE bounded wait, the options, afis_timing (stage 1), the
+//                   fuse_group), fuse_all, launch_rank_hits, the combined matrix in ctx->elig_scores filled with the no-entry word, gather, per piece
+//                   queue_texture_pairs (with the fusion where fuse_pairs), finish, the read-back, ONE bounded wait, the options, afis_timing (stage 1), the
 //                   kept lists into the caller's arrays, the two matrices swapped
 //   end(rc, scores) the scores copy; after a failure the bounded wait, the call's buffers released, options and timing cleared; last_search either way
 struct CascadeTables;

@@ -204,6 +204,21 @@ inline MinuGrid minu_cands_grid(int max_nL, int max_nR, int s3_tie_order)
     while (g.n_wg > 64 && g.bytes() > ((size_t)8 << 30)) g.n_wg /= 2;
     return g;
 }
+// ... and for a chunk of n_pairs pairs of a pair-list call (launch_minu_cands_pairs; afis_ctx.h: PairCall): what fits the chip at once — n_cus CUs of 160 KB of LDS, a
+// workgroup taking lds_bytes_per_wg (minu_cands_lds_bytes) — since its workgroups stride over the 3 n_pairs tasks, within the scratch the context can afford: what the
+// searches have made it hold already (scratch_bytes_held), or 1 GB — a pair of 2000 x 2000 minutiae takes 32 MB of it per workgroup.  At least one workgroup.
+inline MinuGrid minu_cands_pairs_grid(int max_nL, int max_nR, int s3_tie_order, int n_cus, size_t lds_bytes_per_wg, size_t scratch_bytes_held, size_t n_pairs)
+{
+    MinuGrid g{minu_scratch_floats(max_nL, max_nR, s3_tie_order), 1};
+    const size_t afford = scratch_bytes_held > ((size_t)1 << 30) ? scratch_bytes_held : (size_t)1 << 30;
+    const size_t per_cu = (size_t)(160 << 10) / lds_bytes_per_wg;
+    size_t n = (size_t)(n_cus > 1 ? n_cus : 1) * (per_cu > 1 ? per_cu : 1);
+    if (afford / (g.wg_floats * 4) < n) n = afford / (g.wg_floats * 4);
+    if (n < 1) n = 1;
+    if (3 * n_pairs < n) n = 3 * n_pairs;
+    g.n_wg = (int)n;
+    return g;
+}
 inline size_t minu_scratch_bytes(const int* max_nL, size_t n_groups, int max_nR, int s3_tie_order)   // max_nL [n_groups]: the longest latent list of every launch group
 {
     size_t bytes = 0;

@@ -10,6 +10,7 @@
 //   match_selftest -selftest-merge <file>                    the exchange's merge of per-rank rank lists (rank_exchange.cpp: merge_topk) on gathered idx / score words
 //   match_selftest -selftest-classes                        the candidate kernel's shape-class rule (afis_device.h: rt_max_rows) as a table: nR  L1 L2 L4  stride1 stride2 stride4
 //   match_selftest -selftest-scratch <file>                  the candidate kernel's grid (afis_device.h: minu_cands_grid) and the scratch prepared for a search (minu_scratch_bytes): per line "max_nR s3_tie_order max_nL...", one max_nL per launch group
+//   match_selftest -selftest-pairs-grid <file>               the candidate kernel's grid for a chunk of a pair-list call (afis_device.h: minu_cands_pairs_grid): per line "max_nL max_nR s3_tie_order n_cus lds_bytes_per_wg scratch_bytes_held n_pairs"
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -46,7 +47,16 @@ int main(int argc, char** argv)
         }
         return 0;
     }
-    if (args.cmdOptionExists("-selftest-offsets")) {                            // the shard's derived tables (no GPU): one "minutiae texture-points" pair per line
+    if (args.cmdOptionExists("-selftest-pairs-grid")) {                         // the candidate kernel's grid for a chunk of a pair-list call (no GPU): one case per line
+        std::ifstream f(args.getCmdOption("-selftest-pairs-grid"));
+        long long nL, nR, tie, cus, lds, held, pairs;
+        while (f >> nL >> nR >> tie >> cus >> lds >> held >> pairs) {
+            const MinuGrid g = minu_cands_pairs_grid((int)nL, (int)nR, (int)tie, (int)cus, (size_t)lds, (size_t)held, (size_t)pairs);
+            std::cout << "pairs_grid " << nL << " " << nR << " " << tie << " " << cus << " " << lds << " " << held << " " << pairs << " " << g.wg_floats << " " << g.n_wg << " " << g.bytes() << std::endl;
+        }
+        return 0;
+    }
+    if (args.cmdOptionExists("-selftest-offsets")) {                          // the shard's derived tables (no GPU): one "minutiae texture-points" pair per line
         std::ifstream f(args.getCmdOption("-selftest-offsets"));
         std::vector<int32_t> mo{0}, to{0}, toff, qb, tb; long long a, b;
         while (f >> a >> b) { mo.push_back((int32_t)(mo.back() + a)); to.push_back((int32_t)(to.back() + b)); }

@@ -1,4 +1,4 @@
-// pair_tables.h — the tables one chunk of afis_score_pairs goes to the device with (afis_pairs.cpp), built on the host alone: nothing here knows of a device, so the
+// pair_tables.h — the tables one chunk of a pair-list call goes to the device with (afis_pairs.cpp: PairCall), built on the host alone: nothing here knows of a device, so the
 // construction is a program of its own under the host sanitizers (pair_tables_check.cpp, tests/test_score_pairs_host.py).
 //
 // A chunk is m pairs (position of the latent in the query handle, shard-local template).  The handle's queries lie in launch groups — contiguous runs, group g holding the
@@ -26,6 +26,7 @@ struct PairChunkTables {
 };
 
 // query [m] in [0, n_q), tmpl [m]; q_first [n_grp + 1] ascending from 0 to n_q; tab [2 m + n_grp], seg [2 m].  Returns the number of segments.
+// seg == NULL (afis_correspondences_pairs: no ADC kernel runs): no work list is written, seg_first is all zeros, 0 segments.
 inline size_t build_pair_tables(size_t m, const int32_t* query, const int32_t* tmpl, size_t n_grp, const int32_t* q_first, int seg_pairs, int32_t* tab, int32_t* seg, PairChunkTables& t)
 {
     const size_t n_q = n_grp ? (size_t)q_first[n_grp] : 0, S = seg_pairs > 0 ? (size_t)seg_pairs : 1;
@@ -38,7 +39,7 @@ inline size_t build_pair_tables(size_t m, const int32_t* query, const int32_t* t
     for (size_t g = 0; g < n_grp; ++g) {
         t.seg_first[g] = n_seg;
         tab[2 * t.first[g] + g] = (int32_t)(t.first[g + 1] - t.first[g]);
-        for (size_t q = (size_t)q_first[g]; q < (size_t)q_first[g + 1]; ++q)
+        for (size_t q = (size_t)q_first[g]; seg && q < (size_t)q_first[g + 1]; ++q)
             for (size_t s = t.run[q]; s < t.run[q + 1]; s += S) {
                 seg[2 * n_seg] = (int32_t)(s - t.first[g]);
                 seg[2 * n_seg + 1] = (int32_t)(t.run[q + 1] - s < S ? t.run[q + 1] - s : S);

@@ -4,6 +4,7 @@
 //   - every pair of the chunk sits in exactly one slot, inside its launch group's table, with its (query of the group, template) entry, and slot_of leads back to it;
 //   - a group's slots are sorted by latent, and the pairs of one latent keep the caller's order;
 //   - the segments of a group cover every latent's run exactly once, in order, each inside ONE latent and of 1 .. S pairs; a latent without pairs has none.
+// Every case runs a second time as afis_correspondences_pairs calls the builder — seg == NULL, no work list: the same checks of tab and slot_of, and 0 segments.
 // Prints "pair_tables_check: N cases ok" and returns 0, or says what broke and returns 1.
 #include "pair_tables.h"
 
@@ -18,17 +19,19 @@ using namespace afis;
 
 static int g_cases = 0;
 
-static bool check(const std::string& name, const std::vector<int32_t>& query, const std::vector<int32_t>& tmpl, const std::vector<int32_t>& q_first, int S)
+// work_list false: the form of afis_correspondences_pairs — no seg array exists at all, tab is all the builder may write —: the same tab and slot_of, no segment
+static bool check_form(const std::string& name, const std::vector<int32_t>& query, const std::vector<int32_t>& tmpl, const std::vector<int32_t>& q_first, int S, bool work_list)
 {
     ++g_cases;
     const size_t m = query.size(), n_grp = q_first.size() - 1;
-    std::unique_ptr<int32_t[]> tab(new int32_t[2 * m + n_grp]), seg(new int32_t[m ? 2 * m : 1]);
+    std::unique_ptr<int32_t[]> tab(new int32_t[2 * m + n_grp]), seg(work_list ? new int32_t[m ? 2 * m : 1] : nullptr);
     for (size_t i = 0; i < 2 * m + n_grp; ++i) tab[i] = -7;
     PairChunkTables t;
     const size_t n_seg = build_pair_tables(m, query.data(), tmpl.data(), n_grp, q_first.data(), S, tab.get(), seg.get(), t);
-    auto bad = [&](const char* what) { fprintf(stderr, "pair_tables_check: %s: %s\n", name.c_str(), what); return false; };
+    auto bad = [&](const char* what) { fprintf(stderr, "pair_tables_check: %s%s: %s\n", name.c_str(), work_list ? "" : ", no work list", what); return false; };
     if (t.first.size() != n_grp + 1 || t.seg_first.size() != n_grp + 1 || t.slot_of.size() != m) return bad("table sizes");
     if (t.first[0] != 0 || t.first[n_grp] != m || t.seg_first[0] != 0 || t.seg_first[n_grp] != n_seg || n_seg > m) return bad("group ranges");
+    if (!work_list && (n_seg != 0 || std::count(t.seg_first.begin(), t.seg_first.end(), (size_t)0) != (long)(n_grp + 1))) return bad("segments without a work list");
     std::vector<int> seen(m, 0);
     for (size_t g = 0; g < n_grp; ++g) {
         if (t.first[g] > t.first[g + 1] || t.seg_first[g] > t.seg_first[g + 1]) return bad("a group's range runs backwards");
@@ -48,6 +51,7 @@ static bool check(const std::string& name, const std::vector<int32_t>& query, co
             if (lq == prev_q && k < prev_k) return bad("the pairs of one latent lost the caller's order");
             prev_q = lq; prev_k = k;
         }
+        if (!work_list) continue;
         // the segments: in order, back to back over the slots that hold pairs, never across two latents
         size_t at = 0;
         for (size_t s = t.seg_first[g]; s < t.seg_first[g + 1]; ++s) {
@@ -63,6 +67,13 @@ static bool check(const std::string& name, const std::vector<int32_t>& query, co
     }
     for (size_t k = 0; k < m; ++k) if (seen[k] != 1) return bad("a pair sits in no slot");
     return true;
+}
+
+// every shape in both forms
+static bool check(const std::string& name, const std::vector<int32_t>& query, const std::vector<int32_t>& tmpl, const std::vector<int32_t>& q_first, int S)
+{
+    const bool with = check_form(name, query, tmpl, q_first, S, true), without = check_form(name, query, tmpl, q_first, S, false);
+    return with && without;
 }
 
 static std::vector<int32_t> cuts(std::mt19937& rng, int n_q, int n_grp)

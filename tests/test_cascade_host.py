@@ -56,9 +56,16 @@ def test_the_kernel_and_the_driver_are_product_objects_and_the_fusion_has_one_de
     body = open(os.path.join(CSRC, "cascade.hip")).read().split("namespace afis {", 1)[1]
     assert body.count("__global__") == 3 and "atomic" not in body and "__shared__" not in body
     drv = open(os.path.join(CSRC, "afis_cascade.cpp")).read().split("#include", 1)[1]
-    for call in ("queue_minutiae_stage(", "launch_fuse_stage1(", "launch_rank_hits(", "launch_cascade_gather(", "launch_adc_pairs(",
-                 "launch_graph_texture_pairs(", "launch_fuse_pairs(", "launch_cascade_scatter(", "build_cascade_tables("):
+    for call in ("queue_minutiae_stage(", "launch_fuse_stage1(", "launch_rank_hits(", "launch_cascade_gather(", "queue_texture_pairs(",
+                 "launch_cascade_scatter(", "build_cascade_tables("):
         assert call in drv, call
+    pairs = open(os.path.join(CSRC, "afis_pairs.cpp")).read()
+    tex = pairs[pairs.index("int queue_texture_pairs("):]                    # the texture stage of a pair table, as the pair calls queue it: the three kernels, called nowhere else in the product
+    tex = tex[:tex.index("\n}\n")]
+    for call in ("launch_adc_pairs(", "launch_graph_texture_pairs(", "launch_fuse_pairs("):
+        assert call in tex, call
+        n_calls = {f: len(re.findall(r"\b" + re.escape(call), open(os.path.join(CSRC, f)).read())) for f in os.listdir(CSRC) if f.endswith(".cpp") and f.startswith("afis_")}
+        assert {f: n for f, n in n_calls.items() if n} == {"afis_pairs.cpp": 1}, call
     assert "stream_lo" not in drv and "stream_hi" not in drv and "launch_graph_texture(" not in drv and drv.count("wait_streams(") == 1      # unconfined; one wait
     search = open(os.path.join(CSRC, "afis_search.cpp")).read()
     assert "cascade" not in search                                          # the measured launch sequence got no flag

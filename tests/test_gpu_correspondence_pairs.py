@@ -121,6 +121,31 @@ def test_all_pairs_shuffled_over_two_launch_groups_and_three_chunks(codebook_byt
     m.close()
 
 
+def test_alternating_latents_of_one_launch_group_answer_as_the_sorted_list(codebook_bytes, oracle, small):
+    """The slots of a launch group are ordered by latent, whatever order the caller lists the pairs in: a list in which the pairs of latents 0 and 1 — one launch group —
+    strictly alternate and the same list sorted by latent give every pair the same bytes, and both the oracle's."""
+    lats, gal = small
+    m = _open(codebook_bytes, gal, query_batch=2, corr_pairs_per_launch=50)
+    qh = m.upload_queries(lats)                                            # launch groups {0, 1} and {2}
+    parts = m.search_resident(qh, k=0, want_parts=True)["parts"]
+    assert m.timing()["launch_groups"] == 2
+    query = np.array([0, 1] * 20 + [2] * 12, np.int32)                      # 52 pairs: chunks of 50 and 2
+    idx = np.array([g for g in range(20) for _ in (0, 1)] + list(range(12)), np.int64)
+    assert (query[:40:2] == 0).all() and (query[1:40:2] == 1).all()
+    by_latent = np.argsort(query, kind="stable")
+    assert (np.diff(query[by_latent]) >= 0).all() and not np.array_equal(by_latent, np.arange(len(query)))
+    alt = m.correspondences_pairs(qh, query, idx, want_parts=True)
+    srt = m.correspondences_pairs(qh, query[by_latent], idx[by_latent], want_parts=True)
+    for j, i in enumerate(by_latent):                                       # pair i of the alternating list is pair j of the sorted one
+        for k in ("counts", "xy", "part"):
+            assert alt[k][i].tobytes() == srt[k][j].tobytes(), (k, i, j)
+    exp = Expected(oracle, codebook_bytes, lats, gal)
+    n_surv = check(alt, exp, query, [int(g) for g in idx], 1, parts)
+    assert n_surv >= 3 and check(srt, exp, query[by_latent], [int(g) for g in idx[by_latent]], 1, parts) == n_surv
+    m.free_queries(qh)
+    m.close()
+
+
 def _rules(cb):
     base, named = cases.edge_latents(cb)
     gal = cases.rules_gallery(cb, base)

@@ -395,6 +395,52 @@ def test_candidate_scratch_is_prepared_for_the_largest_need_of_any_launch_group(
     assert need(250, 2000, 1)[2] < need(200, 2000, 1)[2]                                                              # the same border for the five-array form
 
 
+def test_pair_call_candidate_grid_is_the_chip_within_the_scratch_the_context_affords(tmp_path):
+    """The candidate kernel's grid for a chunk of a pair-list call (afis_device.h: minu_cands_pairs_grid; the one driver of the pair calls sizes its scratch by it): as many
+    workgroups as fit the chip at once — CUs x (160 KB of LDS / a workgroup's LDS, at least 1) —, within the scratch the context can afford — what it holds already, or 1 GB —,
+    at least one, and never more than the chunk's 3 x n_pairs tasks.  The formula is written out here; on 256 CUs with two workgroups per CU it gives the 512 that
+    tests/test_gpu_pair_forms.py (N_WORKGROUPS_MAX) sizes its lists by."""
+    import subprocess
+    csrc = os.path.join(ROOT, "msu-latentafis_amd", "csrc")
+    exe = os.path.join(csrc, "match_selftest")
+    subprocess.run(["make", "-s", "-C", csrc, "match_selftest"], check=True)
+    GB = 1 << 30
+    # (max_nL, max_nR, s3_tie_order, n_cus, lds_bytes_per_wg, scratch_bytes_held, n_pairs)
+    cases_ = [(64, 128, 0, 256, 70000, 0, 8192), (64, 128, 1, 256, 80000, 0, 8192),          # a large chip, two workgroups per CU, either tie order
+              (64, 128, 0, 256, 70000, 0, 1), (64, 128, 1, 256, 80000, 0, 1), (64, 128, 0, 256, 70000, 0, 170), (64, 128, 0, 256, 70000, 0, 171),   # n_pairs = 1; either side of 3 n_pairs = 512
+              (2000, 2000, 0, 256, 70000, 0, 8192), (2000, 2000, 1, 256, 80000, 0, 8192),    # the 1 GB rule binds
+              (2000, 2000, 0, 256, 70000, 4 * GB, 8192), (2000, 2000, 1, 256, 80000, GB + 1, 8192), (2000, 2000, 0, 256, 70000, GB - 1, 8192),   # ... or what the context holds
+              (64, 128, 0, 256, 81920, 0, 8192), (64, 128, 0, 256, 81921, 0, 8192), (64, 128, 0, 256, 200000, 0, 8192),   # the border of two per CU; an LDS need beyond a CU: one
+              (64, 128, 0, 0, 70000, 0, 8192), (2000, 2000, 1, 256, 80000, 1, 8192), (1, 1, 0, 304, 40000, 0, 100000), (0, 0, 0, 8, 70000, 0, 5)]
+    f = tmp_path / "grids.txt"
+    f.write_text("".join(" ".join(str(v) for v in c) + "\n" for c in cases_))
+    out = subprocess.run([exe, "-selftest-pairs-grid", str(f)], capture_output=True, text=True, check=True).stdout.split("\n")
+
+    def want(nL, nR, tie, cus, lds, held, pairs):
+        wg_floats = (5 if tie else 2) * ((max(nL, 1) * max(nR, 1) + 63) // 64 * 64) + 4096
+        afford = max(held, GB)
+        per_cu = max(1, (160 << 10) // lds)
+        n_wg = max(1, min(max(cus, 1) * per_cu, afford // (wg_floats * 4)))
+        n_wg = min(n_wg, 3 * pairs)
+        return wg_floats, n_wg, wg_floats * 4 * n_wg
+
+    got = {}
+    for c, line in zip(cases_, out):
+        w = line.split()
+        assert w[0] == "pairs_grid" and tuple(int(x) for x in w[1:8]) == c, line
+        got[c] = tuple(int(x) for x in w[8:])
+        assert got[c] == want(*c), (c, got[c], want(*c))
+        assert 1 <= got[c][1] <= 3 * c[6] and got[c][2] == got[c][0] * 4 * got[c][1]
+        assert got[c][1] == 1 or got[c][2] <= max(c[5], GB), c                                  # more than one workgroup only within what is afforded
+    assert len(got) == len(cases_)
+    assert got[cases_[0]][1] == 512 and got[cases_[1]][1] == 512                              # 256 CUs x 2
+    assert [got[c][1] for c in cases_[2:6]] == [3, 3, 510, 512]
+    assert got[cases_[6]] == (8004096, 33, 8004096 * 4 * 33) and got[cases_[7]][1] == 13     # 32 MB and 80 MB per workgroup under 1 GB
+    assert [got[c][1] for c in cases_[8:11]] == [134, 13, 33]
+    assert [got[c][1] for c in cases_[11:14]] == [512, 256, 256]
+    assert got[cases_[14]][1] == 2 and got[cases_[16]][1] == 304 * 4 and got[cases_[17]][1] == 15
+
+
 def test_launch_group_rule_places_the_cuts_where_the_row_groups_are_fewest(tmp_path):
     """The latents of a search are cut into launch groups on the host (afis_device.h: launch_group_cuts / launch_group_latents; used by afis_queries_upload).  With the matrix-core
     bound pass a launch pays for row groups of 768 latent texture rows, so the rule must (1) cover the latents with contiguous runs of at most `per`, (2) reach the smallest total

@@ -56,8 +56,12 @@ def test_the_kernels_and_the_driver_are_product_objects():
     run = open(os.path.join(CSRC, "afis_cascade.cpp")).read()
     run = run[run.index("int CascadeCall::run("):]
     run = run[:run.index("\n}\n")]
-    for call in ("queue_minutiae_stage(", "fuse_all()", "launch_rank_hits(", "build_cascade_tables(", "gather()", "launch_adc_pairs(", "launch_graph_texture_pairs(", "finish()"):
+    for call in ("queue_minutiae_stage(", "fuse_all()", "launch_rank_hits(", "build_cascade_tables(", "gather()", "queue_texture_pairs(", "finish()"):
         assert call in run, call
+    tex = open(os.path.join(CSRC, "afis_pairs.cpp")).read()
+    tex = tex[tex.index("int queue_texture_pairs("):]                        # the texture stage of a pair table that run() queues per piece: the pair kernels
+    tex = tex[:tex.index("\n}\n")]
+    assert "launch_adc_pairs(" in tex and "launch_graph_texture_pairs(" in tex and "launch_graph_texture(" not in tex
     assert "stream_lo" not in drv and "stream_hi" not in drv and "launch_graph_texture(" not in drv and "search_shard(" not in drv
     assert "stream_lo" not in run and "stream_hi" not in run and "launch_graph_texture(" not in run and "search_shard(" not in run
     assert drv.count("wait_streams(") == 0 and run.count("wait_streams(") == 1     # after the handle's own wait: one launch sequence, one wait
