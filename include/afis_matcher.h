@@ -342,6 +342,55 @@ int afis_count_before(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint
                       int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const float* score /*[n_targets]*/, const int64_t* idx /*[n_targets], GLOBAL*/,
                       int64_t* n_before /*[n_targets]*/);
 
+/* Cohort statistics and z-normalised scores (no reference counterpart): every list above is cut by one decision score, and a raw fused score grows with the minutiae a
+ * latent carries and with a print that scores high against everything.  Cohort normalisation puts the matrix on a common scale: a latent's scores in units of that
+ * latent's own non-mate distribution (per row, "T-norm", axis 0), or a print's scores in units of that print's distribution over many latents (per column, "Z-norm",
+ * axis 1: what the reverse search needs) — on the device, without the [n_q][G] matrix leaving it.
+ * Definitions (csrc/score_stats.h holds them once, for the kernels and the host; the tests hold the device to them bit for bit):
+ *   cell classes   a cell (word w, float v) is NO ENTRY (w == 0xffffffff: a filter took it out, or afis_search_eligible left it unscored), VALUED (v finite, the sign
+ *                  bit of v + 0.0f clear, v < 65536.0f) or OUTSIDE (everything else: -1 of an empty template or latent, negative values, +-inf, NaN, values >= 2^16)
+ *   quantisation   q(v) = llrint((double)v * 1048576.0) under round-to-nearest-even, for a valued v: the product is exact in fp64 and 0 <= q < 2^36
+ *   statistic      of a set of cells — a row's (axis 0) or a column's (axis 1) after the call's eligibility filter —: n the valued cells, n_outside the outside
+ *                  cells, s1 = sum q, s2 = sum q^2 as a 128-bit unsigned integer (s2_lo, s2_hi), min / max the valued cells' least and greatest value by rank_key
+ *                  (the two zeros are one value, +0.0); +inf / -inf while n == 0.  Exact integers: statistics of disjoint cell sets — the shards of a gallery —
+ *                  add up to the statistic of their union bit for bit, whatever the order of the sums and wherever the shards were cut
+ *   THE BOUND      n <= 2^27, for a shard and for a sum of shards.  Then s1 < 2^63, s2 < 2^99, and n x s2 and s1^2 stay below 2^126.  The add helper checks it
+ *   moments        mean = double(s1) / (double(n) * 1048576.0); N = n x s2 - s1^2, exact in 128 bits; sd = sqrt(double(N)) / (double(n) * 1048576.0) — the
+ *                  population deviation; double(.) is the correctly rounded conversion of the integer; n == 0 gives (0, 0)
+ *   normalised     z = (float)(((double)v - offset) * scale): an fp64 subtraction, an fp64 multiplication (no fused multiply-add) and one conversion.  Every valued
+ *                  cell becomes its z, every outside cell becomes no entry (a template without a print has no z-score), every no-entry cell stays
+ * afis_score_stats        reads the LAST search's matrix, whatever left it (a full, subset, eligible, weighted, print or cascade search), through the filtered ranking
+ *                         calls' own checks and filter pass (afis_rank_hits_filtered's rules for labels, masks and the exclusions' CSR at min_score = -inf): the
+ *                         filter decides which cells are in the cohort — elimination prints and a known mate go into excl.  axis 0: out [n_q], one statistic per
+ *                         query; axis 1: out [columns], one per column in the order of the search's scores output (for a subset the caller's column order).  The
+ *                         matrix is neither written nor invalidated.  AFIS_EINVAL in addition: an axis other than 0 or 1, a null out, a row or column of more than
+ *                         2^27 cells.  An empty shard or n_q == 0: every statistic is (0, 0, 0, 0, 0, +inf, -inf), no device work.  Device and pinned room — the
+ *                         filtered copy, 72 bytes per row, 48 bytes per statistic — is ensured before anything is queued (AFIS_EDEVICE otherwise)
+ * afis_normalize_scores   applies "normalised" to every cell of the UNFILTERED matrix with its row's (axis 0: offset, scale [n_q]) or column's (axis 1: [columns], in
+ *                         the order above) pair: a mate is normalised against the cohort it was left out of.  offset must be finite and scale finite and > 0, else
+ *                         AFIS_EINVAL before anything is queued, with the matrix unchanged and rankable.  After AFIS_OK the last-search matrix holds the z-scores:
+ *                         every ranking call reads them and takes min_score in z units; scores_out, where given, receives the normalised matrix in the search's
+ *                         column order.  The matrix is then marked normalised: both calls refuse it with AFIS_ESTATE, and the next search clears the mark.  n_q must
+ *                         be the last search's.  Normalising along both axes of one matrix is not offered
+ * The three helpers are host arithmetic on statistics — no context, no device:
+ * afis_score_stat_add     acc += other, field by field with carry, min of mins and max of maxes; AFIS_EINVAL, acc unchanged, where n would pass 2^27
+ * afis_score_stat_remove  takes one valued cell's contribution out of acc exactly, so that trimming a cohort by its best k cells is integer arithmetic over the top-k a
+ *                         search already returns, and works across shards.  AFIS_EINVAL, acc unchanged, for a score that is not valued or where a field would go
+ *                         below zero.  min and max are LEFT AS THEY ARE: they stay the extremes of the cohort before the removal
+ * afis_score_stat_moments "moments" above; AFIS_EINVAL for a statistic outside the bound or one that no set of cells has (n x s2 < s1^2)
+ * Options "score_stats_us" and "normalize_us" (read-only): the device time of the last call's launches.  The sharded recipe — statistics per rank, merged on the
+ * host, every rank normalised with the merged pair, then the usual rank exchange — is INTEGRATION.md's (host/sharding.py::merge_score_stats, trim_score_stats).
+ * These calls do not give: quantiles and histograms (afis_count_before counts a row's tail), an exchange of statistics between ranks inside the library. */
+typedef struct { int64_t n, n_outside; uint64_t s1, s2_lo, s2_hi; float min, max; } afis_score_stat;   /* 48 bytes */
+int afis_score_stats(afis_ctx* ctx, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                     const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/, int n_q,
+                     afis_score_stat* out /*axis 0: [n_q]; axis 1: [columns]*/);
+int afis_normalize_scores(afis_ctx* ctx, int axis, int n_q, const double* offset, const double* scale /*[n_q] or [columns]*/,
+                          float* scores_out /*[n_q][columns] or NULL*/);
+int afis_score_stat_add(afis_score_stat* acc, const afis_score_stat* other);
+int afis_score_stat_remove(afis_score_stat* acc, float score);
+int afis_score_stat_moments(const afis_score_stat* st, double* mean, double* sd);
+
 /* Case lists (no reference counterpart): an examiner's unit of work is a CASE — the same impression encoded twice, several lifts of one finger, several fingers of one
  * hand — and fusing the queries of a case is one list per case instead of one per query.  Both calls rank the matrix of the context's LAST search; a case cannot span
  * searches: all its latents must be queries of the one search that is ranked.  On the device the member rows of every case are folded into one fused row
@@ -1143,6 +1192,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * "rank_positions_us" (read-only): the device time of the last afis_rank_positions', afis_rank_subject_positions' or afis_count_before's launches (for a filtered call the
  * filter pass of hit_filter.hip first, for persons the maxima's memset, k_subject_best and the exclusions' drops; then k_position_targets and k_count_before), from HIP
  * events around them; 0 when that call queued nothing.
+ * "score_stats_us" (read-only): the device time of the last afis_score_stats' launches (for a filtered call the filter pass of hit_filter.hip first; then, axis 0, the
+ * limb table's memset, k_score_stats_rows and k_score_stats_finish, or, axis 1, k_score_stats_cols), from HIP events around them; 0 when that call queued nothing.
+ * "normalize_us" (read-only): the device time of the last afis_normalize_scores' launches (k_normalize_scores; for a subset listed out of order with scores_out given
+ * the columns' permutation too), from HIP events around them; 0 when that call queued nothing.
  * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
  * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
  * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -134,7 +134,7 @@ struct afis_labels {
 
 // The score matrix the last search left in afis_ctx::scores ([n_q][G] in the order of the shard searched: the resident one, or sub's sub-shard), while nothing has
 // touched it or what it refers to: afis_rank_subjects ranks it.  Set by a search that succeeded, cleared by drain_abandoned at the top of every entry point that queues work.
-struct LastSearch { bool valid = false; int n_q = 0; int64_t G = 0; const afis_subset* sub = nullptr; uint64_t gallery_epoch = 0; };   // (gallery_epoch: the shard the matrix was scored against)
+struct LastSearch { bool valid = false; int n_q = 0; int64_t G = 0; const afis_subset* sub = nullptr; uint64_t gallery_epoch = 0; bool normalized = false; };   // (gallery_epoch: the shard the matrix was scored against; normalized: afis_normalize_scores has replaced the scores by z-scores — that call and afis_score_stats refuse the matrix, every search starts a record without the flag)
 
 struct afis_ctx : Shard {
     int device = 0;
@@ -176,6 +176,9 @@ struct afis_ctx : Shard {
     int64_t filter_us = 0;               // option filter_us (read-only): of which everything before k_rank_hits, from its own pair of events
     DevBuf pos_tab, pos_out;             // afis_rank_positions / afis_rank_subject_positions / afis_count_before: the call's tables (the targets' composites [m] uint64 | rows | off | row [m] | position [m], int32) and its answers (count [m] uint64 | best_idx [m] int64 | status [m] int32 | score [m])
     int64_t rank_positions_us = 0;       // option rank_positions_us (read-only): device time of the last such call's launches (a filtered call's filter pass, for persons the maxima and the drops; k_position_targets, k_count_before)
+    DevBuf stat_tab, stat_out;           // afis_score_stats: the limb table [rows][9] uint64 and the statistics [rows or columns] x 48 bytes; afis_normalize_scores: the (offset, scale) pairs [rows or columns][2] double in stat_tab (its matrix is built in elig_scores and swapped in as afis_search_eligible's is)
+    int64_t score_stats_us = 0;          // option score_stats_us (read-only): device time of the last afis_score_stats' launches (the filter pass, the table's memset, the statistics kernels)
+    int64_t normalize_us = 0;            // option normalize_us (read-only): device time of the last afis_normalize_scores' launches (k_normalize_scores; for a subset listed out of order the columns' permutation of scores_out)
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
     DevBuf pair_buf, pair_tex_slab;      // every pair-list call (PairCall below has the layout), grown on demand: one chunk's candidate lists, survivors, counts, parts and tables — about 5.8 KB per pair of option corr_pairs_per_launch for afis_correspondences_pairs; with afis_score_pairs' dense row maxima and scores kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch —, and the texture list kernel's slab for a chunk's launches of afis_score_pairs

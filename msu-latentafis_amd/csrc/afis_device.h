@@ -419,6 +419,15 @@ hipError_t launch_position_targets(int mode, const float* scores, int G, const u
                                    long long* best_idx, hipStream_t stream);
 hipError_t launch_count_before(const float* scores, const unsigned long long* best, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets,
                                const unsigned long long* comp, unsigned long long* count, hipStream_t stream);
+// Cohort statistics and z-normalised scores (score_stats.hip; the definitions: score_stats.h).
+// launch_score_stats       axis 0: per row of matrix [n_q][G] one statistic -> out [n_q] (48 bytes each, afis_score_stat's layout) through the limb table tab
+//                          [n_q][9] uint64, which the launcher zeroes: a workgroup takes kSsChunkScalar adjacent columns of a row, kSsChunkVec where rows take 16-byte
+//                          loads, and adds its sums to the row's words with integer atomics.  axis 1: per column -> out [G]; tab is not used
+// launch_normalize_scores  out[q][t] = the normalised cell of scores[q][t] with pair[q] (axis 0) or pair[t] (axis 1), pair = (offset, scale) as two doubles on a
+//                          16-byte boundary; out != scores
+constexpr int kSsChunkScalar = 1024, kSsChunkVec = 4096;
+hipError_t launch_score_stats(int axis, const float* matrix, int n_q, int G, unsigned long long* tab, void* out, hipStream_t stream);
+hipError_t launch_normalize_scores(int axis, const float* scores, int n_q, int G, const double* pair, float* out, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

@@ -63,6 +63,10 @@ class Timing(C.Structure):
                 ("bound_clock_ghz", C.c_float), ("cands_clock_ghz", C.c_float)]
 
 
+# afis_score_stat (include/afis_matcher.h), 48 bytes: what Matcher.score_stats returns and host/sharding.py::merge_score_stats / trim_score_stats take
+SCORE_STAT = np.dtype([("n", "<i8"), ("n_outside", "<i8"), ("s1", "<u8"), ("s2_lo", "<u8"), ("s2_hi", "<u8"), ("min", "<f4"), ("max", "<f4")])
+assert SCORE_STAT.itemsize == 48
+
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
@@ -71,7 +75,8 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments",
+           "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
@@ -148,6 +153,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_rank_positions.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
         lib.afis_rank_subject_positions.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp, i64p]
         lib.afis_count_before.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, fp, i64p, i64p]
+    if hasattr(lib, "afis_score_stats"):                                # cohort statistics and z-normalised scores; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64); dp = C.POINTER(C.c_double)
+        lib.afis_score_stats.argtypes = [vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, vp]
+        lib.afis_normalize_scores.argtypes = [vp, C.c_int, C.c_int, dp, dp, fp]
+        lib.afis_score_stat_add.argtypes = [vp, vp]
+        lib.afis_score_stat_remove.argtypes = [vp, C.c_float]
+        lib.afis_score_stat_moments.argtypes = [vp, dp, dp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     if hasattr(lib, "afis_correspondences_pairs"):                      # the pair-list export; absent from older builds compared by tools/lib_ab.py
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
@@ -674,6 +686,45 @@ class Matcher:
         before a hypothetical entry (score[i], idx[i]); a column whose global index is idx[i] is never counted, and idx[i] need not be covered.  Summed over the ranks
         of a sharded gallery (host/sharding.py::merge_positions) that is the target's global position."""
         return self._positions(lambda f, nq, n, q, a, sc, nb: self.lib.afis_count_before(self.ctx, *f, nq, n, q, sc, a, nb), query, idx, labels, masks, excl, n_q, False, in_score=score)
+
+    # ---- cohort statistics and z-normalised scores -----------------------------------------------------------------------
+    def score_stats(self, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
+        """Exact integer statistics of the LAST search's matrix, per query (axis 0: [n_q]) or per column (axis 1: [columns], in the order of the search's scores
+        output), over the cells the filter leaves — labels / masks / excl are rank_hits_filtered's: elimination prints and a known mate go into excl.  -> a structured
+        array of dtype SCORE_STAT: n valued cells, n_outside, s1 = sum q, s2 = s2_hi x 2^64 + s2_lo = sum q^2 with q = rint(score x 2^20), min, max.  Statistics of
+        disjoint shards add up bit for bit (host/sharding.py::merge_score_stats); score_moments gives mean and deviation.  The matrix stays as it is."""
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        out = np.zeros(n_q if axis == 0 else self.last_n_templates, SCORE_STAT)
+        self._chk(self.lib.afis_score_stats(self.ctx, axis, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
+                                            _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q,
+                                            out.ctypes.data_as(C.c_void_p) if len(out) else None))
+        return out
+
+    def normalize_scores(self, offset, scale, axis: int = 0, want_scores: bool = False, n_q: Optional[int] = None):
+        """Every valued cell v of the LAST search's matrix becomes z = float32((float64(v) - offset) * scale) with its row's (axis 0) or column's (axis 1) pair, every
+        other cell no entry; every ranking call then reads z-scores and takes min_score in z units.  offset finite, scale finite and > 0.  A second call, or
+        score_stats, on the normalised matrix is AFIS_ESTATE until the next search.  -> the normalised matrix [n_q][columns] if want_scores, else None."""
+        n_q = self.last_n_q if n_q is None else n_q
+        o = np.ascontiguousarray(np.asarray(offset, np.float64).reshape(-1)); s = np.ascontiguousarray(np.asarray(scale, np.float64).reshape(-1))
+        n = n_q if axis == 0 else self.last_n_templates
+        if len(o) != n or len(s) != n:
+            raise ValueError("one (offset, scale) pair per %s" % ("query" if axis == 0 else "column"))
+        out = np.empty((n_q, self.last_n_templates), np.float32) if want_scores else None
+        self._chk(self.lib.afis_normalize_scores(self.ctx, axis, n_q, _ptr(o, C.c_double) if n else None, _ptr(s, C.c_double) if n else None,
+                                                 _ptr(out, C.c_float) if want_scores else None))
+        return out
+
+    def score_moments(self, stats):
+        """(mean, sd) float64 arrays of a SCORE_STAT array, by afis_score_stat_moments: the population deviation from exact integers; n == 0 gives (0, 0)."""
+        st = np.ascontiguousarray(np.asarray(stats, SCORE_STAT).reshape(-1))
+        mean = np.zeros(len(st)); sd = np.zeros(len(st))
+        m, d = C.c_double(), C.c_double()
+        for i in range(len(st)):
+            if self.lib.afis_score_stat_moments(C.c_void_p(st.ctypes.data + i * SCORE_STAT.itemsize), C.byref(m), C.byref(d)) != 0:
+                raise AfisError("afis_score_stat_moments: statistic %d is outside the bound n <= 2^27 or inconsistent" % i)
+            mean[i] = m.value; sd[i] = d.value
+        return mean, sd
 
     # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
     def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):

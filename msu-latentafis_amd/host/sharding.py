@@ -248,7 +248,64 @@ def merge_positions(status: np.ndarray, score: np.ndarray, n_before_per_rank: np
     return out_status, out_score, n_before, owner
 
 
-CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                     # AFIS_CORR_* (include/afis_matcher.h)
+# afis_score_stat (include/afis_matcher.h), 48 bytes: Matcher.score_stats' rows
+SCORE_STAT = np.dtype([("n", "<i8"), ("n_outside", "<i8"), ("s1", "<u8"), ("s2_lo", "<u8"), ("s2_hi", "<u8"), ("min", "<f4"), ("max", "<f4")])
+STAT_MAX_CELLS = 1 << 27                                                    # the bound of csrc/score_stats.h: n <= 2^27, for a shard and for a sum of shards
+_M64 = (1 << 64) - 1
+
+
+def _valued(score: np.float32) -> bool:
+    """csrc/score_stats.h::stat_cell_class == valued, for a score that is not the no-entry word: finite, the sign of score + 0 clear, below 2^16."""
+    s = np.float32(score)
+    return bool(np.isfinite(s) and not np.signbit(s + np.float32(0.0)) and s < np.float32(65536.0) and s.view(np.uint32) != np.uint32(0xffffffff))
+
+
+def merge_score_stats(per_rank) -> np.ndarray:
+    """Statistics of disjoint shards added up.  per_rank: [R, rows] SCORE_STAT — Matcher.score_stats(axis=0) of every rank for one query list (or, along axis 1,
+    of disjoint latent files against one print list).  -> [rows]: n, n_outside, s1 and the 128-bit s2 added in Python integers, min of mins and max of maxes over the
+    ranks that hold a valued cell (+inf / -inf where none does): what one context over the whole gallery returns, bit for bit, wherever the shards were cut.
+    ValueError where a row's n would pass 2^27."""
+    a = np.asarray(per_rank, SCORE_STAT)
+    if a.ndim != 2:
+        raise ValueError("merge_score_stats: per_rank is a [ranks, rows] array of SCORE_STAT")
+    out = np.zeros(a.shape[1], SCORE_STAT)
+    out["min"] = np.inf; out["max"] = -np.inf
+    for i in range(a.shape[1]):
+        n = n_out = s1 = s2 = 0
+        lo, hi = np.float32(np.inf), np.float32(-np.inf)
+        for r in range(a.shape[0]):
+            e = a[r, i]
+            n += int(e["n"]); n_out += int(e["n_outside"]); s1 += int(e["s1"]); s2 += (int(e["s2_hi"]) << 64) | int(e["s2_lo"])
+            if int(e["n"]) > 0:
+                lo = e["min"] if rank_key(e["min"]) < rank_key(lo) else lo
+                hi = e["max"] if rank_key(e["max"]) > rank_key(hi) else hi
+        if n > STAT_MAX_CELLS:
+            raise ValueError(f"merge_score_stats: row {i} would hold {n} valued cells, a statistic takes 2^27")
+        out[i] = (n, n_out, s1, s2 & _M64, s2 >> 64, lo, hi)
+    return out
+
+
+def trim_score_stats(stats, top_scores) -> np.ndarray:
+    """A cohort without its best cells: from row i of stats [rows] the valued scores of top_scores[i] (a sequence per row: the row's merged top-k, say) are taken out
+    exactly, as afis_score_stat_remove takes them — n - 1, s1 - q, s2 - q^2 with q = rint(float64(score) x 2^20).  Scores that are not valued (a list's -inf padding,
+    -1) are skipped: they were never in n.  min and max stay as they are.  ValueError where a field would go below zero: the score was not in the cohort."""
+    st = np.asarray(stats, SCORE_STAT).reshape(-1).copy()
+    if len(top_scores) != len(st):
+        raise ValueError("trim_score_stats: one sequence of scores per row")
+    for i in range(len(st)):
+        n, s1, s2 = int(st[i]["n"]), int(st[i]["s1"]), (int(st[i]["s2_hi"]) << 64) | int(st[i]["s2_lo"])
+        for s in np.asarray(top_scores[i], np.float32).reshape(-1):
+            if not _valued(s):
+                continue
+            q = int(np.rint(np.float64(s) * 1048576.0))
+            n -= 1; s1 -= q; s2 -= q * q
+            if n < 0 or s1 < 0 or s2 < 0:
+                raise ValueError(f"trim_score_stats: row {i} does not hold the score {float(s)!r}")
+        st[i]["n"] = n; st[i]["s1"] = s1; st[i]["s2_lo"] = s2 & _M64; st[i]["s2_hi"] = s2 >> 64
+    return st
+
+
+CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                    # AFIS_CORR_* (include/afis_matcher.h)
 PAIR_OK, PAIR_NOT_COVERED = 0, 1                                            # AFIS_PAIR_* (include/afis_matcher.h)
 
 
