@@ -157,6 +157,31 @@ int64_t afis_gallery_size(const afis_ctx* ctx);
  * After every edit the results are, bit for bit, those of a context freshly committed with the final gallery. */
 int afis_gallery_reopen(afis_ctx* ctx);
 int afis_gallery_remove(afis_ctx* ctx, const int64_t* idx, int64_t n);
+/* Replace enrolled prints in place.  Valid on a reopened gallery with templates staged through any route above (afis_gallery_add with codes or fp32 descriptors,
+ * afis_gallery_add_dat, _add_dat_batch, _add_packed, afis_gallery_load with or without a first / count slice): staged template i takes the place of resident entry
+ * idx[i] (global indices, in staging order, in any order).  Nothing is appended: the shard keeps its size and every other template its index.  The final gallery is the old
+ * one with entry idx[i] = staged template i, and the sentence above holds for it: results bit for bit those of a fresh commit of that gallery, afis_gallery_export byte for
+ * byte the file afis_gallery_save writes of it.
+ *   - a staged EMPTY template (no minutiae, no texture) makes the entry an empty entry, as afis_gallery_remove does; a live template onto an entry that is empty or was
+ *     removed is re-enrolment at that index; minutiae-only and texture-only templates go in both directions; the staging routes clip and check as always.
+ *   - AFIS_EINVAL, nothing changed (shard searchable, staged templates still staged, afis_gallery_size as before): idx NULL with n > 0; n not the number of staged
+ *     templates; an index outside [index_base, index_base + G); an index listed twice; point sums beyond a shard's limits (2^31 - 1 minutiae or texture points, the bound
+ *     pass's code stream).  AFIS_ESTATE, nothing changed: gallery not committed; not reopened; nothing staged.  After either a correct call succeeds, and a plain
+ *     afis_gallery_commit(index_base) still appends what is staged.
+ *   - on success it is an edit like the other two: it waits for the context's device work (the last search's matrix is gone), plain query handles, subsets, labels and
+ *     subjects made before it are refused afterwards (handles of afis_queries_upload_reserved are taken), the code layouts built on first use are built again, the staging
+ *     area is released and the gallery is no longer reopened.
+ *   - only the staged points, the offset tables (five of G + 1 words, two source tables of G words) and the empty flags cross PCIe (option gallery_h2d_bytes counts
+ *     them).  On the device every SoA array is written once into a buffer of its new size by one splice kernel (csrc/gallery_edit.hip: resident ranges from the old array,
+ *     replaced ones from the staged points), swapped in and the old one released, the descriptors first: the transient memory is one array plus the staged points.  The
+ *     derived layouts are then laid out whole in buffers of their new sizes.
+ *   - device memory failure (AFIS_EDEVICE): before the first array has been switched the old shard is intact and the staged templates stay staged; after that the
+ *     resident shard is dropped and the context is back to "not committed" with nothing staged, as after a removal that failed half-way.
+ * Measured (profiles/gallery_replace_timing.json; MI355X, 10 000 resident templates, 500 replaced, medians of five): the transaction reopen + stage + afis_gallery_commit_at 20.9 ms
+ * (20.7 - 21.7) against 31.6 ms (22.8 - 39.3) for afis_gallery_remove of the same 500 entries + reopen + stage + appending commit of the same 500 templates, interleaved in
+ * one process, host wall-clock with the device idle at return; the six splice launches write 505.5 MB in 347 us of device time (HIP events around each), the removal's
+ * compaction 480.5 MB in 327 us. */
+int afis_gallery_commit_at(afis_ctx* ctx, const int64_t* idx /* [n], global */, int64_t n);
 int afis_gallery_export(afis_ctx* ctx, const char* path, const char* const* names);
 
 /* The hot path.  Replaces the body of the OpenMP loop of One2List_matching / List2List_matching

@@ -38,8 +38,9 @@ int afis_debug_graph_arith(afis_ctx* ctx, unsigned long long* out8);
  * [5] rows whose exact maximum lay outside the bounds the selection used (a self-check: must be 0). */
 int afis_debug_refine_stats(afis_ctx* ctx, unsigned long long* out8, int reset);
 
-/* The compaction kernels of the last afis_gallery_remove (gallery_edit.hip): out2[0] = their device time in microseconds (HIP events around each of the six
- * launches, summed), out2[1] = the bytes they copied.  tools/bench_live_gallery.py sets them beside a device-to-device copy of the same bytes. */
+/* The compaction kernels of the last afis_gallery_remove, or the splice kernels of the last afis_gallery_commit_at, whichever edit came last (gallery_edit.hip):
+ * out2[0] = their device time in microseconds (HIP events around each of the six launches, summed), out2[1] = the bytes they copied.  tools/bench_live_gallery.py sets
+ * the removal's beside a device-to-device copy of the same bytes; tools/bench_gallery_replace.py reports the replace's. */
 int afis_debug_compact_stats(afis_ctx* ctx, long long* out2);
 
 /* Subject rank lists (afis_rank_subjects) over a caller-made score matrix: scores [n_q][G] for the resident shard is uploaded in place of the matrix a search leaves,

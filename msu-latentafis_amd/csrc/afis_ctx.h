@@ -204,7 +204,7 @@ struct afis_ctx : Shard {
     int64_t print_cascade_kept_pairs = 0;   // option print_cascade_kept_pairs (read-only): pairs that call's second stage scored
     DevBuf out_perm;                     // a subset search's scores / parts in the caller's column order (sized before the search queues)
     int64_t gallery_h2d_bytes = 0;       // option gallery_h2d_bytes (read-only): host-to-device bytes of every commit and removal so far
-    int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
+    int64_t compact_us = 0, compact_bytes = 0;   // the last removal's compaction kernels, or the last afis_gallery_commit_at's splice kernels: device time (events around each launch) and the bytes they copied (parity tap afis_debug_compact_stats)
     // adc_variant 9: fp16 codebook + |cw|^2 (once), per group B fragments, row constants and the bound pass's records (the gallery's own streams: Shard)
     DevBuf mf_cw16, mf_cwn, mf_bfrag, mf_rowk, mf_rec, mf_stats;
     bool mf_cb_built = false;

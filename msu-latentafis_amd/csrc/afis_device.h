@@ -326,6 +326,9 @@ hipError_t launch_fragment_tiles(const float* des, const int32_t* off, const int
 // afis_gallery_remove (gallery_edit.hip): one SoA array of the shard copied into a new buffer with every surviving template's range moved from old_off[t] to new_off[t]
 // (device offset tables [G + 1]); elem_bytes 384 (descriptors), 16 (PQ codes) or 4 ((x, y), orientations); n_new = new_off[G]
 hipError_t launch_compact_ranges(const void* src, void* dst, int elem_bytes, const int32_t* old_off, const int32_t* new_off, int G, long long n_new, hipStream_t stream);
+// afis_gallery_commit_at (gallery_edit.hip): one SoA array of the shard written into a new buffer in which template t's range starts at new_off[t] and comes from the resident
+// array at src_tab[t] (>= 0: the template stays) or from the staged array at ~src_tab[t] (< 0: it is replaced).  Device tables: src_tab [G], new_off [G + 1]; elem_bytes as above
+hipError_t launch_splice_ranges(const void* res, const void* stg, void* dst, int elem_bytes, const int32_t* src_tab, const int32_t* new_off, int G, long long n_new, hipStream_t stream);
 // afis_subset_create (gallery_subset.hip): one SoA array of the resident shard gathered by a template list — template t of the output takes the src_off[sel[t]] .. range of
 // src and lands at dst_off[t] (device tables: src_off [G + 1], sel [n], dst_off [n + 1]; ranges in any order, possibly empty); elem_bytes 384, 16 or 4; n_out = dst_off[n]
 hipError_t launch_gather_ranges(const void* src, void* dst, int elem_bytes, const int32_t* src_off, const int32_t* sel, const int32_t* dst_off, int n, long long n_out, hipStream_t stream);

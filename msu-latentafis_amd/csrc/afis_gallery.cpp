@@ -3,6 +3,7 @@
 // Replaces the per-pair load_FP_template(rolled) of matching/matcher.cpp:173 / :278: parse once, keep the shard resident in HBM.
 #include "afis_ctx.h"
 #include "afis_offsets.h"
+#include "gallery_splice_plan.h"
 #include <sys/stat.h>
 
 using namespace afis;
@@ -559,7 +560,7 @@ static void release_staging(afis_ctx* ctx)
     ctx->pend.reset(); ctx->pend_first = ctx->pend_count = 0;
 }
 
-// ---- the live gallery: afis_gallery_reopen, the appending commit, afis_gallery_remove, afis_gallery_export ---------------------------------
+// ---- the live gallery: afis_gallery_reopen, the appending commit, afis_gallery_remove, afis_gallery_commit_at, afis_gallery_export ---------------------------------
 // An edit replaces device buffers that searches read: nothing of the context may be running.  The search that timed out (if any) first, then all three streams.
 // (afis_subset_create / afis_subset_free wait the same way: afis_subset.cpp)
 }  // extern "C"
@@ -803,6 +804,145 @@ int afis_gallery_remove(afis_ctx* ctx, const int64_t* idx, int64_t n)
     ctx->compact_us = (int64_t)compact_us; ctx->compact_bytes = compact_bytes;
     invalidate_lazy_streams(ctx);
     ++ctx->gallery_epoch;
+    return AFIS_OK;
+}
+
+// The third edit: staged template i takes the place of resident entry idx[i].  Order: (1) the plan on the host (gallery_splice_plan.h: validation, the shard's offsets and
+// flags after the edit, one source table per point kind); (2) the staged points and every table go to buffers of their own; (3) each SoA array is spliced into a fresh buffer
+// of its new size — resident ranges from the old array, replaced ones from the staged points — which is swapped in and the old one released, descriptors first as in the
+// removal; (4) the tables are switched; (5) the derived layouts get buffers of their new sizes (they may have GROWN) and are laid out whole.  Up to the first swap of (3) the
+// resident shard is what it was and the staged templates stay staged; a failure after it drops the shard, as a removal's does.
+int afis_gallery_commit_at(afis_ctx* ctx, const int64_t* idx, int64_t n)
+{
+    if (!ctx) return AFIS_EINVAL;
+    if (n < 0 || (n > 0 && !idx)) return fail(ctx, AFIS_EINVAL, "afis_gallery_commit_at: bad argument");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, "afis_gallery_commit_at: commit the gallery first");
+    if (!ctx->reopened) return fail(ctx, AFIS_ESTATE, "afis_gallery_commit_at: the gallery is not reopened (afis_gallery_reopen, then stage the replacements)");
+    HostGallery& hg = ctx->hg;
+    const GalleryMapping* gm = ctx->pend.get();
+    const int64_t Gn = gm ? ctx->pend_count : hg.size();
+    if (Gn == 0) return fail(ctx, AFIS_ESTATE, "afis_gallery_commit_at: nothing is staged");
+    const int64_t G = ctx->gal.G;
+    const int64_t* src_mo = gm ? gm->minu_off + ctx->pend_first : hg.minu_off.data();
+    const int64_t* src_to = gm ? gm->tex_off + ctx->pend_first : hg.tex_off.data();
+    const uint8_t* s_empty = gm ? gm->empty + ctx->pend_first : hg.empty.data();
+    SplicePlan plan;
+    { const int e = plan_gallery_splice(ctx->res_mo.data(), ctx->res_to.data(), ctx->res_empty.data(), G, ctx->index_base, idx, n, Gn, src_mo, src_to, s_empty, plan);
+      if (e != kSpliceOk) return fail(ctx, AFIS_EINVAL, std::string("afis_gallery_commit_at: ") + splice_plan_message(e)); }
+    const int64_t m0 = src_mo[0], t0 = src_to[0];
+    const size_t NMs = (size_t)(src_mo[Gn] - m0), NTs = (size_t)(src_to[Gn] - t0);
+    const int16_t* s_mx = gm ? gm->mx + m0 : hg.mx.data(); const int16_t* s_my = gm ? gm->my + m0 : hg.my.data();
+    const float* s_mori = gm ? gm->mori + m0 : hg.mori.data(); const float* s_mdes = gm ? gm->mdes + (size_t)m0 * kDes : hg.mdes.data();
+    const int16_t* s_tx = gm ? gm->tx + t0 : hg.tx.data(); const int16_t* s_ty = gm ? gm->ty + t0 : hg.ty.data();
+    const float* s_tori = gm ? gm->tori + t0 : hg.tori.data(); const uint8_t* s_tcodes = gm ? gm->tcodes + (size_t)t0 * kM : hg.tcodes.data();
+    if (gm && gm->fd_ >= 0) {
+        struct stat st;
+        if (fstat(gm->fd_, &st) != 0 || (size_t)st.st_size < gm->len_) return fail(ctx, AFIS_EFORMAT, "gallery container: " + gm->path + " was truncated after it was loaded");
+    }
+    std::vector<int32_t> toff, qb, tb;
+    int64_t q_blocks = 0, t32 = 0; int max_nR = 0;
+    derived_offsets(plan.mo, plan.to, toff, qb, tb, q_blocks, t32, max_nR);
+    { const int rcq = quiesce(ctx, "afis_gallery_commit_at"); if (rcq != AFIS_OK) return rcq; }
+    hipStream_t s = ctx->stream;
+    const bool clock_it = getenv("AFIS_COMMIT_TIMING") != nullptr;           // development aid, as in commit_shard
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t_prev = now();
+    auto lap = [&](const char* what) { if (clock_it) { (void)hipStreamSynchronize(s); const double t = now(); fprintf(stderr, "replace: %-28s %8.1f ms\n", what, t - t_prev); t_prev = t; } };
+    const int64_t NM1 = plan.mo[(size_t)G], NT1 = plan.to[(size_t)G];
+    // the parity tap afis_debug_compact_stats, as in the removal: device time of the splice kernels of this call and the bytes they wrote
+    double compact_us = 0; int64_t compact_bytes = 0;
+    hipEvent_t ev_c[2] = {nullptr, nullptr};
+    for (hipEvent_t& e : ev_c) HIPCHK(ctx, hipEventCreate(&e));
+    bool touched = false;                                                   // an array has been replaced: from here on a failure cannot leave the old shard behind
+    auto body = [&]() -> int {
+        // (2) the staged points and the two source tables in ONE device buffer, its parts on 256-byte boundaries (an allocation and a release instead of eight of each); the
+        // offset tables beside the resident ones.  As in the append, arrays below 256 MB go without the pinned pipe.
+        struct Staged { DevBuf buf; ~Staged() { buf.release(); } } sd;
+        enum { kMdes, kTcodes, kMxy, kMori, kTxy, kTori, kSrcM, kSrcT, kParts };
+        const size_t part_bytes[kParts] = {NMs * kDes * 4, NTs * kM, NMs * 4, NMs * 4, NTs * 4, NTs * 4, (size_t)G * 4, (size_t)G * 4};
+        size_t part_at[kParts], total = 0;
+        for (int k = 0; k < kParts; ++k) { part_at[k] = total; total += up256(part_bytes[k]); }
+        HIPCHK(ctx, sd.buf.ensure(std::max<size_t>(total, 16)));
+        auto part = [&](int k) { return sd.buf.as<uint8_t>() + part_at[k]; };
+        PinnedPipe pp;
+        pp.h2d = &ctx->gallery_h2d_bytes;
+        pp.direct_below = (size_t)256 << 20;
+        HIPCHK(ctx, upload_bulk_at(pp, part(kMdes), s_mdes, part_bytes[kMdes], s));
+        std::vector<short2> mxy(NMs), txy(NTs);
+        parallel_for((int64_t)NMs, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) mxy[(size_t)i] = make_short2(s_mx[i], s_my[i]); });
+        parallel_for((int64_t)NTs, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) txy[(size_t)i] = make_short2(s_tx[i], s_ty[i]); });
+        HIPCHK(ctx, upload_bulk_at(pp, part(kTcodes), s_tcodes, part_bytes[kTcodes], s));
+        HIPCHK(ctx, upload_bulk_at(pp, part(kMxy), mxy.data(), part_bytes[kMxy], s)); HIPCHK(ctx, upload_bulk_at(pp, part(kMori), s_mori, part_bytes[kMori], s));
+        HIPCHK(ctx, upload_bulk_at(pp, part(kTxy), txy.data(), part_bytes[kTxy], s)); HIPCHK(ctx, upload_bulk_at(pp, part(kTori), s_tori, part_bytes[kTori], s));
+        HIPCHK(ctx, h2d_copy(ctx, part(kSrcM), plan.src_m.data(), part_bytes[kSrcM], s)); HIPCHK(ctx, h2d_copy(ctx, part(kSrcT), plan.src_t.data(), part_bytes[kSrcT], s));
+        TableSet nt;
+        HIPCHK(ctx, upload_table(ctx, nt.minu_off, plan.mo, s)); HIPCHK(ctx, upload_table(ctx, nt.tile_off, toff, s)); HIPCHK(ctx, upload_table(ctx, nt.tex_off, plan.to, s));
+        HIPCHK(ctx, upload_table(ctx, nt.q_blk, qb, s)); HIPCHK(ctx, upload_table(ctx, nt.t32_blk, tb, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));                               // (mxy / txy are pageable host memory of this scope)
+        lap("staged points and tables");
+        // (3) one array at a time, the largest first: the transient memory is one array plus the staged buffer
+        struct Arr { DevBuf* b; int stg; int elem; bool minu; };
+        const Arr arrs[] = {{&ctx->g_minu_des, kMdes, kDes * 4, true}, {&ctx->g_tex_codes, kTcodes, kM, false}, {&ctx->g_minu_xy, kMxy, 4, true}, {&ctx->g_minu_ori, kMori, 4, true},
+                            {&ctx->g_tex_xy, kTxy, 4, false}, {&ctx->g_tex_ori, kTori, 4, false}};
+        for (const Arr& a : arrs) {
+            const int64_t n_new = a.minu ? NM1 : NT1;
+            DevBuf fresh;
+            HIPCHK(ctx, fresh.ensure(std::max<size_t>((size_t)n_new * (size_t)a.elem, 16)));
+            hipError_t e = hipEventRecord(ev_c[0], s);
+            if (e == hipSuccess) e = launch_splice_ranges(a.b->p, part(a.stg), fresh.p, a.elem, (const int32_t*)part(a.minu ? kSrcM : kSrcT),
+                                                          a.minu ? nt.minu_off.as<int32_t>() : nt.tex_off.as<int32_t>(), (int)G, n_new, s);
+            if (e == hipSuccess) e = hipEventRecord(ev_c[1], s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            float ms = 0;
+            if (e == hipSuccess && n_new > 0) e = hipEventElapsedTime(&ms, ev_c[0], ev_c[1]);
+            if (e != hipSuccess) { fresh.release(); HIPCHK(ctx, e); }
+            compact_us += (double)ms * 1e3; compact_bytes += n_new * a.elem;
+            std::swap(*a.b, fresh); fresh.release();
+            touched = true;
+            refresh_gallery_view(ctx);
+        }
+        lap("splice");
+        // (4) the switch of the tables; the flags in place ([G] as before)
+        std::swap(ctx->g_minu_off, nt.minu_off); std::swap(ctx->g_minu_tile_off, nt.tile_off); std::swap(ctx->g_tex_off, nt.tex_off);
+        std::swap(ctx->g_tex_q_blk, nt.q_blk); std::swap(ctx->g_tex_t32_blk, nt.t32_blk);
+        HIPCHK(ctx, h2d_copy(ctx, ctx->g_empty.p, plan.empty.data(), (size_t)G, s));
+        // (5) the derived layouts, whole, into buffers of the new sizes (DevBuf::ensure keeps a buffer that is large enough: nothing of the old contents is needed)
+        HIPCHK(ctx, ctx->g_minu_frag.ensure(std::max<size_t>((size_t)toff[(size_t)G] * 6 * 64 * 16, 16)));
+        if (ctx->mf_gal_built) {
+            const size_t n_ent = std::max<size_t>((size_t)t32 * 32, 1);
+            HIPCHK(ctx, ctx->g_codes_p.ensure(n_ent * 16)); HIPCHK(ctx, ctx->g_nrm_p.ensure(n_ent * 4)); HIPCHK(ctx, ctx->g_tile_meta.ensure(std::max<size_t>((size_t)t32 * 8, 16)));
+        }
+        refresh_gallery_view(ctx);
+        HIPCHK(ctx, launch_fragment_tiles(ctx->g_minu_des.as<float>(), ctx->g_minu_off.as<int32_t>(), ctx->g_minu_tile_off.as<int32_t>(), (int)G, ctx->g_minu_frag.p, s));
+        if (ctx->mf_gal_built)
+            HIPCHK(ctx, launch_mf_tiles(ctx->gal, ctx->g_tex_t32_blk.as<int32_t>(), ctx->mf_cwn.as<float>(), ctx->g_codes_p.p, ctx->g_nrm_p.as<float>(), ctx->g_tile_meta.p, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        lap("tables and derived layouts");
+        return AFIS_OK;
+    };
+    const int rc = body();
+    for (hipEvent_t e : ev_c) (void)hipEventDestroy(e);
+    if (rc != AFIS_OK) {
+        if (touched) {                                                      // half-spliced arrays are no gallery: the context is back to "not committed", nothing staged
+            (void)hipStreamSynchronize(s);
+            free_gallery_dev(ctx);
+            ctx->gal = GalleryDev(); ctx->committed = false; ctx->reopened = false;
+            ++ctx->gallery_epoch;
+            ctx->res_empty.clear(); ctx->res_mo.clear(); ctx->res_to.clear();
+            release_staging(ctx);
+            ctx->err += " [afis_gallery_commit_at failed half-way: the resident shard was dropped; stage and commit the gallery again]";
+        }
+        return rc;
+    }
+    ctx->max_nR = max_nR; ctx->q_blocks = q_blocks; ctx->t32_tiles = t32; ctx->minu_tiles = toff[(size_t)G];
+    ctx->total_minutiae = NM1; ctx->total_tex_points = NT1;
+    ctx->res_empty = std::move(plan.empty); ctx->res_mo = std::move(plan.mo); ctx->res_to = std::move(plan.to);
+    ctx->compact_us = (int64_t)compact_us; ctx->compact_bytes = compact_bytes;
+    invalidate_lazy_streams(ctx);
+    ++ctx->gallery_epoch;
+    release_staging(ctx);
+    ctx->reopened = false;
+    lap("staging released");
     return AFIS_OK;
 }
 

@@ -68,7 +68,7 @@ SCORE_STAT = np.dtype([("n", "<i8"), ("n_outside", "<i8"), ("s1", "<u8"), ("s2_l
 assert SCORE_STAT.itemsize == 48
 
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
-           "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
+           "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_commit_at", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
            "afis_gallery_file_info", "afis_gallery_file_names", "afis_rank_list", "afis_search", "afis_search_dat", "afis_queries_upload",
            "afis_subset_create", "afis_subset_free", "afis_search_subset", "afis_search_subset_resident",
            "afis_subjects_create", "afis_subjects_free", "afis_rank_subjects", "afis_rank_hits", "afis_rank_subject_hits", "afis_queries_upload_reserved", "afis_rank_latent_hits",
@@ -110,6 +110,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_gallery_reopen.argtypes = [vp]
         lib.afis_gallery_remove.argtypes = [vp, i64p, C.c_int64]
         lib.afis_gallery_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p)]
+    if hasattr(lib, "afis_gallery_commit_at"):                          # (absent from older builds, as above)
+        lib.afis_gallery_commit_at.argtypes = [vp, i64p, C.c_int64]
     lib.afis_search.argtypes = [vp, C.POINTER(TemplateView), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_search_dat.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, fp, fp, i32p, C.c_int, i64p, fp]
     lib.afis_queries_upload.argtypes = [vp, C.POINTER(TemplateView), C.c_int, C.POINTER(vp)]
@@ -420,6 +422,12 @@ class Matcher:
         """Turn the listed entries (global indices, as search reports them) into empty entries (score -1); every other template keeps its index."""
         a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
         self._chk(self.lib.afis_gallery_remove(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a)))
+
+    def gallery_commit_at(self, idx: Sequence[int]):
+        """Replace in place: on a reopened gallery, staged template i takes the place of the resident entry idx[i] (global indices, in staging order, any order).  Nothing
+        is appended; every other template keeps its index.  A staged empty template makes the entry an empty entry; a live one onto an empty entry re-enrols there."""
+        a = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        self._chk(self.lib.afis_gallery_commit_at(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a)))
 
     def gallery_export(self, path: str, names: Sequence[str] = None):
         """Write the RESIDENT shard as a packed container: the file gallery_save writes from a context staged with the same entries."""
@@ -1196,7 +1204,7 @@ class Matcher:
         return dict(zip(("pairs", "rows", "rows_evaluated", "cells_evaluated", "rows_evaluated_in_full", "bound_violations"), list(out)[:6]))
 
     def compact_stats(self):
-        """(device microseconds, bytes copied) of the compaction kernels of the last gallery_remove."""
+        """(device microseconds, bytes copied) of the compaction kernels of the last gallery_remove, or of the splice kernels of the last gallery_commit_at, whichever came last."""
         out = (C.c_longlong * 2)()
         self._chk(self._tap("afis_debug_compact_stats")(self.ctx, out))
         return int(out[0]), int(out[1])
