@@ -175,6 +175,11 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "minu_fast_max_cells") *value = rt_class_simi_floats(4);
     else if (n == "graph_slab_steps_texture") *value = kTexSlabSteps;                 // read-only: neighbours per row whose values the list kernels keep in their slabs (afis_device.h); longer rows recompute the rest
     else if (n == "graph_slab_steps_minutiae") *value = kMinuSlabSteps;
+    else if (n == "graph_texture_lists_per_cu") {                                       // read-only: texture lists resident on a CU of the context's device (the runtime's occupancy of k_graph_texture)
+        int lists = 0;
+        if (hipSetDevice(ctx->device) != hipSuccess || graph_texture_lists_per_cu(&lists) != hipSuccess) return AFIS_EDEVICE;
+        *value = lists;
+    }
     else if (n == "gallery_resident") *value = (int64_t)ctx->res_empty.size();           // read-only: templates of the committed shard (afis_gallery_size also counts what is staged beside it)
     else if (n == "gallery_h2d_bytes") *value = ctx->gallery_h2d_bytes;                // read-only: the bytes handed to every host-to-device copy of the gallery's commits and removals (counted where the copies are issued)
     else if (n == "subset_device_bytes") *value = (int64_t)subset_device_bytes(ctx);    // read-only: device bytes held by the live subsets (afis_subset_create)

@@ -250,6 +250,9 @@ inline size_t graph_minutiae_slab_bytes(long long n_tasks) { return n_tasks > 0 
 // kernel: equal selectable scores of S8 / S9 in std::sort's order, graph.hip::sort_scores)
 hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const float* table_dist,
                                 const float* rm_val, const int32_t* rm_arg, const float* rm_cv, const int32_t* rm_n, float* parts, void* slab, size_t slab_bytes, MinuCand* tap_out, int32_t* tap_n, int tap_stage, hipStream_t stream);
+// texture lists (one-wave workgroups of k_graph_texture) that the current device keeps resident on one CU: 16, the wave slots its 128 registers leave, as long as a list's LDS
+// stays within a sixteenth of the CU's (graph.hip: static_assert below TexSmem); afis_get_option reports it (graph_texture_lists_per_cu)
+hipError_t graph_texture_lists_per_cu(int* lists);
 // S1-S3 for the three selected latent minutiae templates: correspondence lists in rank order, cands[task][120], cand_n[task]
 // (task = (q*3+s)*G + g).  Pairs of up to 256 latent x 512 rolled minutiae and 38 912 similarities go through the rolled-template-stationary MFMA kernel in one of its
 // three shape classes (above); what it cannot take (other shapes, degenerate key distributions) it appends to `fallback` (count, task ids), which the

@@ -107,6 +107,7 @@ template <int N> struct SimStore<N, false> {};
 #ifndef AFIS_MINU_ALIAS
 #define AFIS_MINU_ALIAS 1
 #endif
+constexpr int kSortShort = 48;             // sort_scores ranks a list of at most this many candidates (the angle stage's) without bins
 template <int NMAX_, bool OWN_SIM_>
 struct __attribute__((aligned(16))) WaveSmem : SimStore<NMAX_, OWN_SIM_> {
     static constexpr int NMAX = NMAX_;
@@ -122,15 +123,20 @@ struct __attribute__((aligned(16))) WaveSmem : SimStore<NMAX_, OWN_SIM_> {
     } y;
     short li[NMAX], ri[NMAX];
     int2 xy[NMAX];                         // .x = latent point, .y = rolled point: (x, y) as two fp16 on the packed paths (graph_arith.h), x | y << 16 as 16-bit integers otherwise and after S8
-    uint32_t hb[NMAX][W];                  // bit rows: non-zero pattern of H (distance stage), then the boolean H of the angle stage
     // LDS is what limits how many lists a CU works on at once, so buffers with disjoint lifetimes share storage:
     union {
-        uint32_t sortbuf[N4 + 128];                                                 // sort_scores: the keys in index order + 128 bin counters (the power iterations keep nothing here: their values and indices live in the slab)
-        struct { u64 keys[N4]; float lo[ALIAS_ORI ? 1 : NMAX], ro[ALIAS_ORI ? 1 : NMAX]; } s;   // sorts (after the iterations); orientations (angle stage, unless they borrow b / cc)
-        struct { uint32_t keys[N4]; short te[NMAX], targ[NMAX]; } pick;          // texture rows picked by S7, before they are ranked (32-bit keys)
+        uint32_t hb[NMAX][W];              // bit rows: non-zero pattern of H (distance stage), then the boolean H of the angle stage
+        // S7's scratch (k_graph_texture's prologue; hb is not touched before dist_filter zeroes the rows it is going to use, which is after the list is built):
+        struct { uint32_t keys[N4]; short te[NMAX], targ[NMAX]; } pick;          // texture rows picked by the dense S7, before they are ranked (32-bit keys)
+        uint32_t s7key[NMAX > 128 ? 256 : 1];                                      // the compact S7's keys grouped by bin (kTexFast of them)
+    };
+    union {
+        uint32_t cnt[128];                                                          // sort_scores, lists of more than kSortShort candidates: 64 bin fill pointers + 64 bin starts; then the stack of the std::sort restatement
+        u64 keys[kSortShort];                                                            // sort_scores, short lists: the (key, ~index) composites
+        struct { float lo[ALIAS_ORI ? 1 : NMAX], ro[ALIAS_ORI ? 1 : NMAX]; } s;     // orientations (angle stage, unless they borrow b / cc)
     } x;
 #ifdef AFIS_PHASE_TIMING
-    u64 ph[16];
+    u64 ph[16];                            // 128 B: a texture list then takes exactly 10 240 B, the most at which sixteen share a CU (static_assert below TexSmem) — nothing more fits such a build
 #endif
 };
 // Texture lists (OWN_SIM false) carry, in the spare bits of li / ri (latent row and rolled point are both < 1024: the 1000-row clamp, matcher.cpp:544-547), the SLOT of the row in the
@@ -181,28 +187,28 @@ __device__ __forceinline__ void sort_scores(SM& sm, int num, double thr)
 {
     const int lane = threadIdx.x;
     constexpr int U = SM::U;
-    uint32_t* const s_key = reinterpret_cast<uint32_t*>(sm.x.s.keys);         // [NMAX] keys in index order, then [128] bin fill pointers / starts
-    uint32_t* const s_cnt = s_key + SM::N4;
+    uint32_t* const s_cnt = sm.x.cnt;                                         // [128] bin fill pointers / starts
     uint32_t* const s_gkey = reinterpret_cast<uint32_t*>(sm.y.cc);            // [NMAX] keys grouped by bin (cc is dead; order[] / sel[], which alias it, are written after the ranking)
-    static_assert(sizeof(sm.x) >= (size_t)(SM::N4 + 128) * 4, "sort scratch exceeds the union");
+    uint32_t* const s_key = s_gkey;                                           // [NMAX] keys in index order: only where scores tie, and after the grouped keys' last read
     uint32_t m32[U]; int r[U];
-    if (num <= 48) {                                                          // short lists (the angle stage's): the bins' bookkeeping costs more than it saves
+    if (num <= kSortShort) {                                                  // short lists (the angle stage's): the bins' bookkeeping costs more than it saves
         const u64 mine = lane < num ? g_make_key(sm.b[lane], lane) : 0ull;
-        if (lane < num) sm.x.s.keys[lane] = mine;
+        if (lane < num) sm.x.keys[lane] = mine;
         WSYNC();
         int rr = 0;
-        for (int k = 0; k < num; ++k) rr += sm.x.s.keys[k] > mine;
+        for (int k = 0; k < num; ++k) rr += sm.x.keys[k] > mine;
         if (ref_tie && num > 16) {                                            // (uniform)
             int gg = 0;                                                       // the strictly larger SCORES: fewer than rr = an equal score with a lower index in front of this one
-            for (int k = 0; k < num; ++k) gg += (uint32_t)(sm.x.s.keys[k] >> 32) > (uint32_t)(mine >> 32);
+            for (int k = 0; k < num; ++k) gg += (uint32_t)(sm.x.keys[k] >> 32) > (uint32_t)(mine >> 32);
             const bool tied = lane < num && gg != rr && !((double)sm.b[lane] < thr);
             if (__ballot(tied) != 0ull) {
-                uint32_t* const k32 = reinterpret_cast<uint32_t*>(sm.x.s.keys) + 96;          // behind the 48 composites: 48 keys, then the sort's stack
-                static_assert(sizeof(sm.x.s.keys) >= (96 + 48 + 48) * 4, "no room for the keys and the stack of the std::sort restatement");
+                constexpr int kOrd = kSortShort / 2;                          // order[0 .. 48) takes the first 24 words of cc (dead, as above); behind them 48 keys, then the sort's stack (3 (2 log2 48 + 1) = 33 words)
+                uint32_t* const k32 = s_gkey + kOrd;
+                static_assert(SM::N4 >= kOrd + 2 * kSortShort, "no room in cc for the keys and the stack of the std::sort restatement");
                 WSYNC();
                 if (lane < num) { k32[lane] = (uint32_t)(mine >> 32); sm.y.os.order[lane] = (short)lane; }
                 WSYNC();
-                if (lane == 0) stdsort_prefix<uint16_t>(reinterpret_cast<uint16_t*>(sm.y.os.order), num, num, k32, reinterpret_cast<int*>(k32 + 48));
+                if (lane == 0) stdsort_prefix<uint16_t>(reinterpret_cast<uint16_t*>(sm.y.os.order), num, num, k32, reinterpret_cast<int*>(k32 + kSortShort));
                 WSYNC();
                 return;
             }
@@ -217,7 +223,7 @@ __device__ __forceinline__ void sort_scores(SM& sm, int num, double thr)
     for (int u = 0; u < U; ++u) {
         const int t = lane + 64 * u;
         m32[u] = t < num ? rank_key(sm.b[t]) : 0u;
-        if (t < num) { s_key[t] = m32[u]; kmin = min(kmin, m32[u]); kmax = max(kmax, m32[u]); }
+        if (t < num) { kmin = min(kmin, m32[u]); kmax = max(kmax, m32[u]); }
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, off)); kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off)); }
@@ -257,6 +263,10 @@ __device__ __forceinline__ void sort_scores(SM& sm, int num, double thr)
     if (g_wave_sum(rsum) != num * (num - 1) / 2) {                            // equal scores: rank the (key, ~index) composites
         u64 mine[U];
         int gg[U];
+        WSYNC();                                                              // every lane has read the grouped keys: the keys in index order take their place
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; if (t < num) s_key[t] = m32[u]; }
+        WSYNC();
 #pragma unroll
         for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; mine[u] = t < num ? ((u64)m32[u] << 32) | (uint32_t)(~(uint32_t)t) : 0ull; r[u] = 0; gg[u] = 0; }
         for (int k = 0; k < num; ++k) {
@@ -269,11 +279,20 @@ __device__ __forceinline__ void sort_scores(SM& sm, int num, double thr)
 #pragma unroll
             for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; tied |= t < num && gg[u] != r[u] && !((double)sm.b[t] < thr); }
             if (__ballot(tied) != 0ull) {
-                WSYNC();                                                      // s_gkey (= cc, which order[] aliases) has been read by every lane
+                // order[] aliases the keys in cc, so the restatement reads them from b[], where each score's key stands in for the score while lane 0 sorts
+                // (the lanes keep their scores and put them back: greedy reads b[])
+                uint32_t* const bkey = reinterpret_cast<uint32_t*>(sm.b);
+                float keep[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; if (t < num) sm.y.os.order[t] = (short)t; }
+                for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; keep[u] = t < num ? sm.b[t] : 0.0f; }
+                WSYNC();                                                      // s_key (= cc, which order[] aliases) and b[] have been read by every lane
+#pragma unroll
+                for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; if (t < num) { sm.y.os.order[t] = (short)t; bkey[t] = m32[u]; } }
                 WSYNC();
-                if (lane == 0) stdsort_prefix<uint16_t>(reinterpret_cast<uint16_t*>(sm.y.os.order), num, num, s_key, reinterpret_cast<int*>(s_cnt));   // s_cnt: 128 words, dead; the stack takes 3 (2 log2 num + 1) <= 48
+                if (lane == 0) stdsort_prefix<uint16_t>(reinterpret_cast<uint16_t*>(sm.y.os.order), num, num, bkey, reinterpret_cast<int*>(s_cnt));   // s_cnt: 128 words, dead; the stack takes 3 (2 log2 num + 1) <= 48
+                WSYNC();
+#pragma unroll
+                for (int u = 0; u < U; ++u) { const int t = lane + 64 * u; if (t < num) sm.b[t] = keep[u]; }
                 WSYNC();
                 return;
             }
@@ -946,12 +965,16 @@ __device__ __forceinline__ void tap_write(const GraphTap& tap, const SM& sm, con
 // =====================================================================================================================
 // texture lists: S7 (top-200 rows of the ADC row maxima) + S8b + S9
 // =====================================================================================================================
-// 14 lists per CU: 11 200 B of LDS (sort keys, picked rows and the angle stage's orientations share one union; the power iterations' values and neighbour indices live in
-// the workgroup's slab in global memory: kTexSlabWgBytes at slab + blockIdx.x * kTexSlabWgBytes) and 128 registers.
+// 16 lists per CU, the four waves per SIMD that 128 registers allow: 10 112 B of LDS (S7's scratch lies on the bit rows' storage, the sorts' keys on cc; the power iterations'
+// values and neighbour indices live in the workgroup's slab in global memory: kTexSlabWgBytes at slab + blockIdx.x * kTexSlabWgBytes).
 #ifndef AFIS_TEX_WAVES
 #define AFIS_TEX_WAVES 4
 #endif
 typedef WaveSmem<kTopTex, false> TexSmem;
+// a CU's 160 KiB of LDS over the 16 wave slots that 128 registers leave it: 163 840 / 16.  One byte more and the sixteenth list does not fit, whatever the allocation granule
+// (10 240 = 8 x 1 280 = 20 x 512); graph_texture_lists_per_cu (afis_get_option) reports what the device makes of it
+static_assert(sizeof(TexSmem) <= 10240, "a texture list's LDS exceeds a sixteenth of a CU's: two of the CU's 16 wave slots would stay empty");
+static_assert(sizeof(TexSmem::pick) <= sizeof(TexSmem::hb), "S7's scratch exceeds the bit rows it borrows");
 constexpr int kTexRegs = (kTexMax + 63) / 64;     // 16 row maxima per lane: the wave holds all <= 1000 keys in registers
 constexpr int kTexFast = 256;                     // a compact list of at most this many rows is ranked whole, four keys per lane (k_graph_texture)
 constexpr int kTexFastRegs = kTexFast / 64;
@@ -1012,8 +1035,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                 // 64 bins of equal width between the smallest and the largest key, highest bin first, as below; HALF the span is what fits an int (maxima of both signs: see the shift below)
                 const int shift = max(0, 27 - __clz((int)((kmax - kmin) >> 1) | 1));   // bin = (key - kmin) >> shift in [0, 63]
                 uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(sm.b);   // [64] fill pointers, [64..128) bin starts (b[] is free until the distance stage)
-                uint32_t* const s_gkey = sm.x.sortbuf;                       // [256] the keys grouped by bin (nothing is picked into x: keys and rows stay in registers)
-                static_assert(TexSmem::N4 >= 128 && sizeof(sm.x.sortbuf) >= (size_t)kTexFast * 4, "the counting arrays of the compact S7 exceed their buffers");
+                uint32_t* const s_gkey = sm.s7key;                           // [256] the keys grouped by bin, on hb's storage (nothing is picked: keys and rows stay in registers)
+                static_assert(TexSmem::N4 >= 128 && sizeof(sm.s7key) >= (size_t)kTexFast * 4 && sizeof(sm.s7key) <= sizeof(sm.hb), "the counting arrays of the compact S7 exceed their buffers");
                 int bin[kTexFastRegs], r[kTexFastRegs];
 #pragma unroll
                 for (int u = 0; u < kTexFastRegs; ++u) bin[u] = min((int)((key[u] - kmin) >> shift), 63);
@@ -1091,7 +1114,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                 for (int u = 0; u < kTexRegs; ++u) if (u < n_regs) n_gt += g_wave_popc(key[u] > T);
                 const int need = kTopTex - n_gt;                             // of the keys equal to T keep the lowest indices
                 int base_gt = 0, base_eq = 0;
-                uint32_t* const key32 = sm.x.pick.keys;   // 200 ordered-float keys, read four at a time below
+                uint32_t* const key32 = sm.pick.keys;     // 200 ordered-float keys (the picked rows live on hb's storage until the list is built)
 #pragma unroll
                 for (int u = 0; u < kTexRegs; ++u) {                         // u ascending, lane ascending = index ascending
                     if (u < n_regs) {
@@ -1101,7 +1124,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                         int pos = -1;
                         if (gt) pos = base_gt + g_lane_prefix(mg);
                         else if (eq) { const int r = base_eq + g_lane_prefix(me); if (r < need) pos = n_gt + r; }
-                        if (pos >= 0) { key32[pos] = key[u]; sm.x.pick.te[pos] = tex_pack_l(compact ? arg[u] & 0xffff : e, e); sm.x.pick.targ[pos] = tex_pack_r(compact ? arg[u] >> 16 : arg[u], e); }   // e = the row's slot in the array the values came from
+                        if (pos >= 0) { key32[pos] = key[u]; sm.pick.te[pos] = tex_pack_l(compact ? arg[u] & 0xffff : e, e); sm.pick.targ[pos] = tex_pack_r(compact ? arg[u] >> 16 : arg[u], e); }   // e = the row's slot in the array the values came from
                         base_gt += __popcll(mg); base_eq += __popcll(me);
                     }
                 }
@@ -1161,9 +1184,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
                 if (g_wave_sum(rsum) != kTopTex * (kTopTex - 1) / 2) {
                     u64 mine[TexSmem::U];
 #pragma unroll
-                    for (int u = 0; u < TexSmem::U; ++u) { const int t = lane + 64 * u; mine[u] = t < num ? ((u64)key32[t] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[t] & 1023)) : 0ull; r[u] = 0; }
+                    for (int u = 0; u < TexSmem::U; ++u) { const int t = lane + 64 * u; mine[u] = t < num ? ((u64)key32[t] << 32) | (uint32_t)(~(uint32_t)(sm.pick.te[t] & 1023)) : 0ull; r[u] = 0; }
                     for (int k = 0; k < num; ++k) {
-                        const u64 kk = ((u64)key32[k] << 32) | (uint32_t)(~(uint32_t)(sm.x.pick.te[k] & 1023));
+                        const u64 kk = ((u64)key32[k] << 32) | (uint32_t)(~(uint32_t)(sm.pick.te[k] & 1023));
 #pragma unroll
                         for (int u = 0; u < TexSmem::U; ++u) r[u] += kk > mine[u];
                     }
@@ -1171,7 +1194,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AFIS_TEX_WAV
 #pragma unroll
                 for (int u = 0; u < TexSmem::U; ++u) {
                     const int t = lane + 64 * u;
-                    if (t < num) { sm.li[r[u]] = sm.x.pick.te[t]; sm.ri[r[u]] = sm.x.pick.targ[t]; }
+                    if (t < num) { sm.li[r[u]] = sm.pick.te[t]; sm.ri[r[u]] = sm.pick.targ[t]; }
                 }
             }
         } else {                                                         // :748-749 rows stay in index order
@@ -1438,6 +1461,12 @@ hipError_t launch_debug_graph_arith(unsigned long long* cnt8, hipStream_t stream
     hipLaunchKernelGGL(k_debug_graph_arith, dim3((kMaxN + 256) / 256), dim3(256), 0, stream, 2, cnt8);
     hipLaunchKernelGGL(k_debug_graph_arith, dim3(4095, 16), dim3(256), 0, stream, 3, cnt8 + 7);
     return hipGetLastError();
+}
+
+// option graph_texture_lists_per_cu: the one-wave workgroups of k_graph_texture that the current device keeps resident on a CU (registers, LDS and its granule, wave slots)
+hipError_t graph_texture_lists_per_cu(int* lists)
+{
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(lists, k_graph_texture<0>, 64, 0);
 }
 
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset)
