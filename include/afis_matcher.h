@@ -405,7 +405,7 @@ int afis_count_before(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint
  * afis_score_stat_moments "moments" above; AFIS_EINVAL for a statistic outside the bound or one that no set of cells has (n x s2 < s1^2)
  * Options "score_stats_us" and "normalize_us" (read-only): the device time of the last call's launches.  The sharded recipe — statistics per rank, merged on the
  * host, every rank normalised with the merged pair, then the usual rank exchange — is INTEGRATION.md's (host/sharding.py::merge_score_stats, trim_score_stats).
- * These calls do not give: quantiles and histograms (afis_count_before counts a row's tail), an exchange of statistics between ranks inside the library. */
+ * These calls do not give: an exchange of statistics between ranks inside the library (histograms and the entry at a rank: the score distributions below). */
 typedef struct { int64_t n, n_outside; uint64_t s1, s2_lo, s2_hi; float min, max; } afis_score_stat;   /* 48 bytes */
 int afis_score_stats(afis_ctx* ctx, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
                      const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/, int n_q,
@@ -415,6 +415,55 @@ int afis_normalize_scores(afis_ctx* ctx, int axis, int n_q, const double* offset
 int afis_score_stat_add(afis_score_stat* acc, const afis_score_stat* other);
 int afis_score_stat_remove(afis_score_stat* acc, float score);
 int afis_score_stat_moments(const afis_score_stat* st, double* mean, double* sd);
+
+/* Score distributions (no reference counterpart): the lists say who is at the top, the positions where a named print stands, the statistics what mean and deviation
+ * are; these two calls answer the opposite questions — how many entries lie between two scores, for many scores at once (the non-mate distribution behind a DET curve,
+ * the threshold that gives a chosen false-positive rate or a candidate list of a chosen length), and WHICH entry stands at a given rank (the score at rank 5 000 of
+ * 100 000: a median, a cohort trimmed by its best 1 %) — on the device, without the [n_q][G] matrix leaving it.  Both read the score matrix of the context's LAST
+ * search through the filtered ranking calls' own checks and filter pass (afis_rank_hits_filtered's rules for labels, masks and the exclusions' CSR at min_score =
+ * -inf), and both ACCEPT a normalised matrix: edges are then in z units, as min_score is for the hit lists, and negative z-scores are ordinary entries.  Integer
+ * arithmetic only.  The matrix is neither written nor invalidated.
+ * Definitions (csrc/score_hist.h holds them once, for the kernels and the host; the tests hold the device to them exactly):
+ *   entry          a cell whose rank_key >= rank_key(-inf), exactly as the hit lists and the positions define it: a cell that holds 0xffffffff, or any other NaN with
+ *                  the sign set, is counted nowhere and stands at no rank
+ *   bin            an entry goes to bin b = the number of edges e with rank_key(e) <= rank_key(cell) (csrc/score_order.h).  Bin 0 holds the entries below edges[0] — the
+ *                  -1 of empty templates and -inf among them —, bin n_edges those that reach the last edge — NaNs with the sign clear among them.  An edge is inclusive
+ *                  from below, and the two zeros are one value, for cells and for edges
+ *   THE PROPERTY   for every j, counts[r][j + 1] + ... + counts[r][n_edges] is the n_hits afis_rank_hits_filtered returns row r for min_score = edges[j] under the
+ *                  same filters, and the sum of all bins its n_hits at -INFINITY.  Counts of disjoint cell sets — the shards of a gallery — add up bit for bit
+ * afis_score_histogram  axis 0: counts [n_q][n_edges + 1], one histogram per query; axis 1: counts [columns][n_edges + 1], one per column in the order of the search's
+ *                       scores output (for a subset the caller's column order).  AFIS_EINVAL, before anything is queued and with the matrix still rankable: an axis
+ *                       other than 0 or 1, n_edges outside 1 .. AFIS_HIST_EDGES_MAX, an edge that is a NaN, edges that do not ascend strictly by rank_key, outputs x
+ *                       (n_edges + 1) above AFIS_HIST_COUNTS_MAX, a null edges or counts where there is something to count.  An empty shard or n_q == 0: every count
+ *                       0, no device work.  Device and pinned room — the filtered copy, axis 1's transposed copy, 8 bytes per count — is ensured before anything is
+ *                       queued (AFIS_EDEVICE otherwise)
+ * afis_entries_at       for target (q, r) — query[i] a query position of the last search, rank[i] >= 0, in any order, repeated or not; a query may have no target —
+ *                       idx and score are entry r of the list afis_rank_hits_filtered(labels, masks, excl, ..., min_score = -INFINITY, cap) gives query q, for any cap >
+ *                       r: defined for every r, not only the first AFIS_HITS_MAX.  The order is csrc/rank_order.h::rank_before: rank_key descending, equal keys by
+ *                       ascending GLOBAL index, also for a subset listed out of order.  status AFIS_POS_LISTED: idx the GLOBAL index, score the cell's own bits (a cell
+ *                       that holds -0.0 returns -0.0).  r at or beyond the row's number of entries: AFIS_POS_NO_ENTRY, idx -1, score -inf.  The round trip:
+ *                       afis_rank_positions(q, idx) returns n_before == r.  AFIS_EINVAL in addition to afis_rank_positions' cases: a negative rank.  n_targets == 0
+ *                       returns AFIS_OK; with an empty shard every target is AFIS_POS_NO_ENTRY.  Device room: 2 KB per target besides the filtered copy; 16 bytes per
+ *                       target return.  On the device a radix select over the row's 64-bit composites (key, ~position), which are unique inside a row: no tie handling
+ * Everything else is afis_score_stats' and afis_rank_positions': which searches count and what invalidates the matrix, the AFIS_ESTATE and AFIS_EINVAL cases, the
+ * handles' life cycles, the rules of masks and of the exclusions' CSR.  No result of a search changes because these functions exist.
+ * Options "score_histogram_us" and "entries_at_us" (read-only): the device time of the last call's launches.  Measured on one MI355X on a planted matrix of 100 latents
+ * x 100 000 templates (tools/score_distribution_timing.py, profiles/score_distribution_timing.json; medians of five): afis_score_histogram along the rows 44 / 60 / 156
+ * us at 16 / 256 / 1024 bins on cells uniform in [0, 300) with 5 % of -1, 37 / 54 / 95 us where every cell is 0.0 — one bin, the shape of real non-mate rows: the wave
+ * aggregation works, the one-bin matrix is the faster of the two —, 207 us along the columns at 16 bins; afis_entries_at 203 us with one rank per row and 1224 us with
+ * 64 (207 and 687 us on the one-bin matrix); afis_score_stats along the rows of the same matrix in the same process, which also reads every word once, 52 us.
+ * Shards: histograms add (host/sharding.py::merge_score_histograms); ranks do not, so there is no global afis_entries_at — the sharded quantile recipe of INTEGRATION.md
+ * brackets the rank with the merged histogram (histogram_rank_bin) and settles it with afis_count_before.
+ * These calls do not give: persons at a rank or histograms of persons' scores; ranks in case lists and in column (reverse) lists; bins of unequal weight. */
+#define AFIS_HIST_EDGES_MAX 1023          /* 1024 bins */
+#define AFIS_HIST_COUNTS_MAX (1 << 24)    /* counts one call returns: outputs x (n_edges + 1) */
+int afis_score_histogram(afis_ctx* ctx, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                         const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/, int n_q,
+                         int n_edges, const float* edges /*[n_edges]*/, int64_t* counts /*axis 0: [n_q][n_edges + 1]; axis 1: [columns][n_edges + 1]*/);
+int afis_entries_at(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                    const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
+                    int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* rank /*[n_targets], >= 0*/,
+                    int32_t* status /*[n_targets]*/, int64_t* idx /*[n_targets], GLOBAL*/, float* score /*[n_targets]*/);
 
 /* Case lists (no reference counterpart): an examiner's unit of work is a CASE — the same impression encoded twice, several lifts of one finger, several fingers of one
  * hand — and fusing the queries of a case is one list per case instead of one per query.  Both calls rank the matrix of the context's LAST search; a case cannot span
@@ -1221,6 +1270,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * limb table's memset, k_score_stats_rows and k_score_stats_finish, or, axis 1, k_score_stats_cols), from HIP events around them; 0 when that call queued nothing.
  * "normalize_us" (read-only): the device time of the last afis_normalize_scores' launches (k_normalize_scores; for a subset listed out of order with scores_out given
  * the columns' permutation too), from HIP events around them; 0 when that call queued nothing.
+ * "score_histogram_us" (read-only): the device time of the last afis_score_histogram's launches (for a filtered call the filter pass of hit_filter.hip first; axis 1:
+ * k_transpose_scores; then the counts' memset and k_score_hist_rows), from HIP events around them; 0 when that call queued nothing.
+ * "entries_at_us" (read-only): the device time of the last afis_entries_at's launches (for a filtered call the filter pass of hit_filter.hip first; then per digit of the
+ * select the bins' memset, k_select_count and k_select_step, and k_select_finish), from HIP events around them; 0 when that call queued nothing.
  * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
  * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
  * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.

@@ -434,6 +434,24 @@ hipError_t launch_count_before(const float* scores, const unsigned long long* be
 constexpr int kSsChunkScalar = 1024, kSsChunkVec = 4096;
 hipError_t launch_score_stats(int axis, const float* matrix, int n_q, int G, unsigned long long* tab, void* out, hipStream_t stream);
 hipError_t launch_normalize_scores(int axis, const float* scores, int n_q, int G, const double* pair, float* out, hipStream_t stream);
+// Score distributions (score_hist.hip; the definitions: score_hist.h).
+// launch_score_hist        per row of matrix [rows][cols] the histogram of its entries under edge_keys [n_edges] (device; ascending rank keys) -> tab [rows][n_edges + 1]
+//                          uint64, which the launcher zeroes: a workgroup takes kShChunkScalar adjacent columns of a row, kShChunkVec where rows take 16-byte loads, and
+//                          adds its non-zero bins to the row's with integer atomics.  Columns: the same launcher over launch_transpose_scores' output
+// launch_entries_at        the entry at rank remain[t] of row row[t], for m targets sorted into a CSR by row (rows [n_rows], off [n_rows + 1], as launch_count_before's;
+//                          max_row_targets: the longest range of off): a radix select over the row's composites, 4 + select_position_digits(n) passes of a counting
+//                          kernel (tab [m][256] uint64, zeroed per pass; a row's targets pass through LDS kSelTargetChunk at a time) and a step kernel that fixes
+//                          one byte of prefix [m] and reduces remain [m] (~0: the rank is not below the row's entries) -> idx (index_base + position, or
+//                          d_global[position]; -1), score (the cell's own bits; -inf), status (kPosListed / kPosNoEntry).  A row's targets stand in ascending
+//                          rank, first [m] is off of the target's row: targets of one chunk with the same fixed digits share one count.  prefix comes in with the
+//                          skipped position bytes set, remain with the ranks; both are left changed, and prefix_spare [m] is the step kernel's other copy
+constexpr int kShChunkScalar = 256, kShChunkVec = 1024;      // k_score_hist_rows: columns per workgroup, one column per thread or four where a thread takes 16 bytes
+constexpr int kSelChunkScalar = 1024, kSelChunkVec = 4096;   // k_select_count: four loads per thread
+constexpr int kSelTargetChunk = 16;                     // k_select_count: targets staged in LDS at a time (256 bins x 4 bytes each: 16 KB)
+hipError_t launch_score_hist(const float* matrix, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream);
+hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* row, const int32_t* first, size_t m,
+                             unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, const long long* d_global, long long index_base,
+                             long long* idx, float* score, int32_t* status, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

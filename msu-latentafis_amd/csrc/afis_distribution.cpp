@@ -1,0 +1,174 @@
+// afis_distribution.cpp — score distributions of the C ABI (include/afis_matcher.h): afis_score_histogram counts, per query of the last search (axis 0) or per column
+// (axis 1), the entries of the matrix into the bins a list of edges makes — afis_rank_hits_filtered's n_hits for many thresholds in one pass — and afis_entries_at
+// returns the entry at a given rank of a query's list, for every rank, not only the first AFIS_HITS_MAX: the inverse of afis_rank_positions.  The definitions (an entry,
+// its bin, one digit of the select) are score_hist.h's.  The checks are the filtered ranking calls' (check_filtered at min_score = -inf), the filter runs as it runs
+// there (FilterPass: no second definition of eligibility), and the kernels of score_hist.hip read the matrix, or its filtered copy; axis 1 reads the transposed copy
+// afis_rank_latent_hits_filtered makes (launch_transpose_scores into ctx->scores_t).  Integer counts only: histograms of disjoint shards add up bit for bit.  8 bytes
+// per count, or 16 bytes per target, return through the context's pinned buffer; the [n_q][G] matrix stays where it is, and as it is — normalised or not.
+// A subset listed out of order: the sub-shard stands in ascending global index order, so a row's tie rule (ascending position) is the rule on global indices; axis 1's
+// histograms are put in the caller's column order here (column_order, afis_normalize.cpp).
+#include "afis_ctx.h"
+#include "score_hist.h"
+
+using namespace afis;
+
+static_assert(kHistEdgesMax == AFIS_HIST_EDGES_MAX && kHistCountsMax == AFIS_HIST_COUNTS_MAX, "score_hist.h holds the limits of include/afis_matcher.h");
+
+namespace afis {
+
+// afis_score_histogram behind its checks; keys: the edges as rank keys; pairs: the exclusions as check_filtered resolved them
+static int score_histogram(afis_ctx* ctx, int axis, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, const std::vector<uint32_t>& keys, int64_t* counts)
+{
+    const char* const who = "afis_score_histogram";
+    const LastSearch ls = ctx->last_search;
+    const int n_q = ls.n_q, n_edges = (int)keys.size();
+    const int64_t G = ls.G, n_out = axis == 0 ? n_q : G, n_bins = n_edges + 1;
+    const size_t out_bytes = (size_t)n_out * (size_t)n_bins * 8, row_bytes = (size_t)n_bins * 8;
+    if (n_q == 0 || G == 0) {                                               // no cell: no device work
+        if (out_bytes) memset(counts, 0, out_bytes);
+        return AFIS_OK;
+    }
+    const std::vector<int32_t> order = axis == 1 ? column_order(ls) : std::vector<int32_t>();
+    FilterPass fp{ctx, labels, masks, pairs, false};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, fp.ensure());
+    if (axis == 1) HIPCHK(ctx, ctx->scores_t.ensure((size_t)G * (size_t)n_q * 4));
+    HIPCHK(ctx, ctx->hist_tab.ensure(out_bytes + keys.size() * 4));
+    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
+    Events ev{2};
+    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    hipStream_t s = ctx->stream;
+    uint32_t* const d_keys = (uint32_t*)(ctx->hist_tab.as<uint8_t>() + out_bytes);
+    for (const HitCall::H2D& u : {HitCall::H2D{d_keys, keys.data(), keys.size() * 4}, fp.masks_up(), fp.pairs_up()})
+        if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipEventRecord(ev[0], s));
+    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is read
+    if (axis == 1) HIPCHK(ctx, launch_transpose_scores(fp.matrix(), ctx->scores_t.as<float>(), n_q, (int)G, s));
+    HIPCHK(ctx, launch_score_hist(axis == 0 ? fp.matrix() : ctx->scores_t.as<float>(), axis == 0 ? n_q : (int)G, axis == 0 ? (int)G : n_q, d_keys, n_edges,
+                                  ctx->hist_tab.as<unsigned long long>(), s));
+    HIPCHK(ctx, hipEventRecord(ev[1], s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->hist_tab.p, out_bytes, hipMemcpyDeviceToHost, s));
+    int64_t total_us = 0;
+    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
+    ctx->score_histogram_us = total_us;
+    const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
+    if (order.empty()) memcpy(counts, pin, out_bytes);
+    else for (size_t t = 0; t < order.size(); ++t) memcpy((uint8_t*)counts + (size_t)order[t] * row_bytes, pin + t * row_bytes, row_bytes);
+    return AFIS_OK;
+}
+
+// afis_entries_at behind its checks; pairs: the exclusions as check_filtered resolved them
+static int entries_at(afis_ctx* ctx, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, int64_t nt, const int32_t* query, const int64_t* rank,
+                      int32_t* status, int64_t* idx, float* score)
+{
+    const char* const who = "afis_entries_at";
+    const LastSearch ls = ctx->last_search;
+    const int n_q = ls.n_q;
+    const int64_t G = ls.G;
+    const std::string w(who);
+    if (nt > (int64_t)INT32_MAX) return fail(ctx, AFIS_EINVAL, w + ": more than 2^31 - 1 targets");
+    for (int64_t i = 0; i < nt; ++i) {
+        if (query[i] < 0 || query[i] >= n_q) return fail(ctx, AFIS_EINVAL, w + ": a target's query is outside 0 .. n_q - 1");
+        if (rank[i] < 0) return fail(ctx, AFIS_EINVAL, w + ": a target's rank is negative");
+    }
+    for (int64_t i = 0; i < nt; ++i) { status[i] = AFIS_POS_NO_ENTRY; idx[i] = -1; score[i] = -INFINITY; }   // what holds for every target of an empty shard
+    if (nt == 0 || G == 0) return AFIS_OK;
+
+    // ---- a CSR by row, a row's targets in ascending rank: targets whose entries share their leading digits become neighbours, and the select counts once for them
+    const size_t m = (size_t)nt;
+    std::vector<int32_t> order(m);                                          // order[t]: the caller's target at place t of the CSR
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [query, rank](int32_t a, int32_t b) { return query[a] != query[b] ? query[a] < query[b] : rank[a] < rank[b]; });
+    std::vector<int32_t> rows, off(1, 0);
+    int max_row_targets = 0;
+    for (size_t t = 0; t < m; ++t) {
+        if (t == 0 || query[order[t]] != query[order[t - 1]]) { rows.push_back(query[order[t]]); off.push_back(off.back()); }
+        max_row_targets = std::max(max_row_targets, ++off.back() - off[off.size() - 2]);
+    }
+    const size_t n_rows = rows.size();
+    // the tables as two uploads: state = prefix [m] | its spare [m] | remain [m]; tab = rows [n_rows] | off [n_rows + 1] | row [m] | first [m]
+    std::vector<int32_t> tab(2 * n_rows + 1 + 2 * m);
+    std::copy(rows.begin(), rows.end(), tab.begin());
+    std::copy(off.begin(), off.end(), tab.begin() + (ptrdiff_t)n_rows);
+    int32_t* const t_row = tab.data() + 2 * n_rows + 1, * const t_first = t_row + m;
+    const uint64_t prefix0 = (uint64_t)0xffffffffu & ~(((uint64_t)1 << (8 * select_position_digits(G))) - 1);   // the position bytes no entry of a row of G differs in
+    std::vector<uint64_t> state(3 * m, prefix0);
+    for (size_t r = 0; r < n_rows; ++r)
+        for (int32_t t = off[r]; t < off[r + 1]; ++t) { t_row[t] = rows[r]; t_first[t] = off[r]; state[2 * m + (size_t)t] = (uint64_t)rank[order[(size_t)t]]; }
+
+    // ---- the device: room first, then the filter pass exactly as the filtered hit lists run it, then the select
+    const size_t state_bytes = 3 * m * 8, bins_at = up256(state_bytes), bins_bytes = m * kSelectBins * 8, csr_at = bins_at + bins_bytes, tab_bytes = csr_at + tab.size() * 4;
+    const size_t idx_at = 0, score_at = m * 8, status_at = score_at + m * 4, out_bytes = status_at + m * 4;
+    FilterPass fp{ctx, labels, masks, pairs, false};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, fp.ensure());
+    HIPCHK(ctx, ctx->sel_tab.ensure(tab_bytes));
+    HIPCHK(ctx, ctx->sel_out.ensure(out_bytes));
+    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
+    Events ev{2};
+    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    hipStream_t s = ctx->stream;
+    uint8_t* const d_tab = ctx->sel_tab.as<uint8_t>(), * const d_out = ctx->sel_out.as<uint8_t>();
+    const HitCall::H2D ups[] = {{d_tab, state.data(), state_bytes}, {d_tab + csr_at, tab.data(), tab.size() * 4}, fp.masks_up(), fp.pairs_up()};
+    for (const HitCall::H2D& u : ups) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipEventRecord(ev[0], s));
+    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is read
+    unsigned long long* const d_prefix = (unsigned long long*)d_tab, * const d_remain = d_prefix + 2 * m;
+    const int32_t* const d_rows = (const int32_t*)(d_tab + csr_at), * const d_off = d_rows + n_rows, * const d_row = d_off + n_rows + 1, * const d_first = d_row + m;
+    HIPCHK(ctx, launch_entries_at(fp.matrix(), (int)G, d_rows, d_off, (int)n_rows, max_row_targets, d_row, d_first, m, d_prefix, d_prefix + m, d_remain,
+                                  (unsigned long long*)(d_tab + bins_at), global_map(ls), (long long)ctx->index_base, (long long*)(d_out + idx_at), (float*)(d_out + score_at),
+                                  (int32_t*)(d_out + status_at), s));
+    HIPCHK(ctx, hipEventRecord(ev[1], s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    int64_t total_us = 0;
+    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
+    ctx->entries_at_us = total_us;
+
+    // ---- back into the caller's order
+    const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
+    for (size_t t = 0; t < m; ++t) {
+        const size_t i = (size_t)order[t];
+        memcpy(idx + i, pin + idx_at + t * 8, 8);
+        memcpy(score + i, pin + score_at + t * 4, 4);
+        memcpy(status + i, pin + status_at + t * 4, 4);
+    }
+    return AFIS_OK;
+}
+
+}  // namespace afis
+
+extern "C" {
+
+int afis_score_histogram(afis_ctx* ctx, int axis, afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl, int n_q,
+                         int n_edges, const float* edges, int64_t* counts)
+{
+    const char* const who = "afis_score_histogram";
+    if (!ctx) return fail(ctx, AFIS_EINVAL, std::string(who) + ": null argument");
+    ctx->score_histogram_us = 0;
+    if (axis != 0 && axis != 1) return fail(ctx, AFIS_EINVAL, std::string(who) + ": axis must be 0 (rows) or 1 (columns)");
+    if (n_edges < 1 || n_edges > AFIS_HIST_EDGES_MAX) return fail(ctx, AFIS_EINVAL, std::string(who) + ": n_edges must be in 1 .. AFIS_HIST_EDGES_MAX (1023)");
+    std::vector<uint32_t> keys((size_t)n_edges);
+    if (edges && hist_edge_keys(edges, n_edges, keys.data()) != 0)
+        return fail(ctx, AFIS_EINVAL, std::string(who) + ": no edge may be a NaN, and the edges must ascend strictly (by rank key: the two zeros are one value)");
+    std::vector<int32_t> pairs;
+    AFISCHK(check_filtered(ctx, who, nullptr, labels, masks, excl_off, excl, n_q, -INFINITY, 1, true, pairs));
+    const int64_t G = ctx->last_search.G, n_out = axis == 0 ? (int64_t)n_q : G;
+    if (n_out * (n_edges + 1) > AFIS_HIST_COUNTS_MAX) return fail(ctx, AFIS_EINVAL, std::string(who) + ": more than AFIS_HIST_COUNTS_MAX counts (outputs x (n_edges + 1))");
+    if (n_out > 0 && !counts) return fail(ctx, AFIS_EINVAL, std::string(who) + ": counts is null");
+    if (n_q > 0 && G > 0 && !edges) return fail(ctx, AFIS_EINVAL, std::string(who) + ": edges is null");
+    return score_histogram(ctx, axis, labels, masks, pairs, keys, counts);
+}
+
+int afis_entries_at(afis_ctx* ctx, afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl,
+                    int n_q, int64_t n_targets, const int32_t* query, const int64_t* rank, int32_t* status, int64_t* idx, float* score)
+{
+    const char* const who = "afis_entries_at";
+    if (!ctx) return fail(ctx, AFIS_EINVAL, std::string(who) + ": null argument");
+    ctx->entries_at_us = 0;
+    if (n_targets < 0 || (n_targets > 0 && !(query && rank && status && idx && score))) return fail(ctx, AFIS_EINVAL, std::string(who) + ": n_targets must be >= 0 and every target array given");
+    std::vector<int32_t> pairs;
+    AFISCHK(check_filtered(ctx, who, nullptr, labels, masks, excl_off, excl, n_q, -INFINITY, 1, true, pairs));
+    return entries_at(ctx, labels, masks, pairs, n_targets, query, rank, status, idx, score);
+}
+
+}  // extern "C"

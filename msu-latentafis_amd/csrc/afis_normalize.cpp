@@ -18,8 +18,8 @@ static_assert(sizeof(afis_score_stat) == sizeof(ScoreStat) && offsetof(afis_scor
 
 namespace afis {
 
-// order[t]: the caller's column of sub-shard position t; empty: the identity
-static std::vector<int32_t> column_order(const LastSearch& ls)
+// order[t]: the caller's column of sub-shard position t; empty: the identity (afis_distribution.cpp orders its columns by it too)
+std::vector<int32_t> column_order(const LastSearch& ls)
 {
     std::vector<int32_t> order(ls.sub && !ls.sub->identity ? (size_t)ls.G : 0);
     if (!order.empty()) {

@@ -75,7 +75,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at",
            "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
@@ -162,6 +162,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.afis_score_stat_add.argtypes = [vp, vp]
         lib.afis_score_stat_remove.argtypes = [vp, C.c_float]
         lib.afis_score_stat_moments.argtypes = [vp, dp, dp]
+    if hasattr(lib, "afis_score_histogram"):                            # score distributions; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64)
+        lib.afis_score_histogram.argtypes = [vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, C.c_int, fp, i64p]
+        lib.afis_entries_at.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     if hasattr(lib, "afis_correspondences_pairs"):                      # the pair-list export; absent from older builds compared by tools/lib_ab.py
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
@@ -733,6 +737,40 @@ class Matcher:
                 raise AfisError("afis_score_stat_moments: statistic %d is outside the bound n <= 2^27 or inconsistent" % i)
             mean[i] = m.value; sd[i] = d.value
         return mean, sd
+
+    # ---- score distributions: per-row histograms and the entry at any rank ------------------------------------------------
+    def score_histogram(self, edges, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
+        """Histograms of the LAST search's matrix, per query (axis 0: [n_q][len(edges) + 1]) or per column (axis 1: [columns][len(edges) + 1], in the order of the
+        search's scores output), over the entries the filter leaves — labels / masks / excl are rank_hits_filtered's.  edges: 1 .. 1023 float32, no NaN, strictly
+        ascending.  An entry goes to bin b = the number of edges <= its score (by rank key: the two zeros are one value); bin 0 lies below edges[0], the last bin
+        reaches edges[-1]; the no-entry word and NaNs with the sign set are counted nowhere.  counts[r, j + 1:].sum() is rank_hits_filtered(edges[j])'s n_hits.  int64;
+        histograms of disjoint shards add up (host/sharding.py::merge_score_histograms).  A normalised matrix is accepted: edges in z units.  The matrix stays as it is."""
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
+        out = np.zeros((n_q if axis == 0 else self.last_n_templates, len(e) + 1), np.int64)
+        self._chk(self.lib.afis_score_histogram(self.ctx, axis, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
+                                                _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q,
+                                                len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
+        return out
+
+    def entries_at(self, query, rank, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """Which entry stands at a rank of the lists of the LAST search: target i is (query[i], rank[i]), a query position of that search and a rank >= 0, in any order,
+        repeated or not.  -> status [n] (AFIS_POS_LISTED 0, AFIS_POS_NO_ENTRY 1), idx [n] — the GLOBAL index of entry rank[i] of the list rank_hits_filtered(-inf, cap,
+        labels, masks, excl) gives its query, for every rank, not only the first 4096; -1 where the row has no more than rank[i] entries — and score [n], the cell's
+        own bits (-inf unless listed).  The inverse of rank_positions: rank_positions(query, idx)["n_before"] == rank.  labels / masks / excl are rank_hits_filtered's."""
+        n_q = self.last_n_q if n_q is None else n_q
+        q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); r = np.ascontiguousarray(np.asarray(rank, np.int64).reshape(-1))
+        if len(q) != len(r):
+            raise ValueError("one query position per rank")
+        n = len(q)
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        st = np.empty(n, np.int32); ix = np.empty(n, np.int64); sc = np.empty(n, np.float32)
+        self._chk(self.lib.afis_entries_at(self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
+                                           _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q, n,
+                                           _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
+                                           _ptr(ix, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None))
+        return {"status": st, "idx": ix, "score": sc}
 
     # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
     def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):

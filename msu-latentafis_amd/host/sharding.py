@@ -305,6 +305,40 @@ def trim_score_stats(stats, top_scores) -> np.ndarray:
     return st
 
 
+def merge_score_histograms(per_rank) -> np.ndarray:
+    """Histograms of disjoint shards added up.  per_rank: [R, rows, bins] int64 — Matcher.score_histogram(edges, axis=0) of every rank for one query list and ONE list
+    of edges (or, along axis 1, of disjoint latent files against one print list).  -> [rows, bins] int64, a plain integer sum: what one context over the whole gallery
+    returns, bit for bit, wherever the shards were cut.  ValueError where the ranks' shapes differ or a count is negative."""
+    parts = [np.asarray(p) for p in per_rank]
+    if not parts or any(p.ndim != 2 or p.shape != parts[0].shape or p.dtype.kind not in "iu" for p in parts):
+        raise ValueError("merge_score_histograms: per_rank is [ranks, rows, bins] integer counts, every rank with the same edges")
+    a = np.stack([p.astype(np.int64) for p in parts])
+    if (a < 0).any():
+        raise ValueError("merge_score_histograms: a count is negative")
+    return a.sum(axis=0, dtype=np.int64)
+
+
+def histogram_rank_bin(counts, rank):
+    """Where a rank falls in a histogram: counts [rows, bins] (or [bins]) int64 — merged, for a global rank — and rank [rows] (or a number) >= 0, counted from the
+    best entry as afis_entries_at counts.  -> (bin, residual): the bin that holds the entry at that rank when the bins are walked from the top, and the rank among
+    that bin's entries — the entries of all higher bins stand before it; (-1, rank) where the rank is not below the row's total.  With edges e, the entry's score
+    lies in [e[bin - 1], e[bin]): the bracket INTEGRATION.md's sharded quantile recipe settles with afis_count_before."""
+    c = np.asarray(counts, np.int64); one = c.ndim == 1
+    c = c.reshape(1, -1) if one else c
+    r = np.asarray(rank, np.int64).reshape(-1)
+    if c.ndim != 2 or c.shape[1] == 0 or len(r) not in (1, c.shape[0]) or (c < 0).any() or (r < 0).any():
+        raise ValueError("histogram_rank_bin: counts is [rows, bins] (or [bins]) of counts >= 0, rank one number >= 0 per row")
+    r = np.broadcast_to(r, (c.shape[0],))
+    above = np.cumsum(c[:, ::-1], axis=1)[:, ::-1]                          # above[i, b]: the entries of bins b .. of row i
+    inside = above > r[:, None]                                             # bins b whose tail holds the rank: 0 .. the bin we want
+    b = inside.sum(axis=1) - 1
+    ok = b >= 0
+    higher = np.where(ok, np.take_along_axis(above, np.maximum(b, 0)[:, None], axis=1)[:, 0] - np.take_along_axis(c, np.maximum(b, 0)[:, None], axis=1)[:, 0], 0)
+    res = np.where(ok, r - higher, r).astype(np.int64)
+    b = np.where(ok, b, -1).astype(np.int64)
+    return (int(b[0]), int(res[0])) if one else (b, res)
+
+
 CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                    # AFIS_CORR_* (include/afis_matcher.h)
 PAIR_OK, PAIR_NOT_COVERED = 0, 1                                            # AFIS_PAIR_* (include/afis_matcher.h)
 
