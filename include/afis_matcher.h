@@ -465,6 +465,70 @@ int afis_entries_at(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64
                     int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* rank /*[n_targets], >= 0*/,
                     int32_t* status /*[n_targets]*/, int64_t* idx /*[n_targets], GLOBAL*/, float* score /*[n_targets]*/);
 
+/* Link groups (no reference counterpart): every call above answers a question about one row or one column; these two look at rows and columns together and return the
+ * GROUPS the last search's matrix makes above a decision score — consolidation: which enrolled prints, or persons, are one finger or person (if A hits B and B hits C
+ * that is one group {A, B, C}, not three lists to reconcile); cross-case linking: which latents hit the same print, or the same person — as the connected components of
+ * a graph, on the device, without the [n_q][G] matrix leaving it.  Both read the score matrix of the context's LAST search through the filtered ranking calls' own checks
+ * and filter pass (afis_rank_hits_filtered's rules for labels, masks and the exclusions' CSR; afis_link_subject_groups' excl holds SUBJECT ids as
+ * afis_rank_subject_hits_filtered's, and a person excluded for a row takes every cell of that row at a print of theirs out), and both ACCEPT a normalised matrix:
+ * min_score is then in z units.  Integers and names only: no float is added anywhere.  The matrix is neither written nor invalidated.
+ * Definitions (csrc/link_groups.h holds them once, for the kernels and the host; the tests hold the device to them exactly):
+ *   reaches        a cell reaches when rank_key(cell) >= rank_key(min_score): afis_rank_hits' decision and its + 0.0f, so the two zeros are one value.  A cell that holds
+ *                  0xffffffff, or any other NaN with the sign set, is no entry and never an edge
+ *   nodes          every column is a node: its name is its GLOBAL template index (afis_link_groups) or the subject id of its template (afis_link_subject_groups: all
+ *                  columns of one person are ONE node).  Row q is the node row_node[q] names — a global template index (the resident print the row is, as passed to
+ *                  afis_search_prints), or a subject id — or, at -1, a node of its own (a latent), reported as -1 - q; row_node NULL: every row is -1.  A named row whose
+ *                  name is a column's name IS that column's node; a named row that matches no column — a print outside the subset's columns, a person the handle does
+ *                  not hold, a print of another rank that arrived as a host view — is a node with that name; several rows with one name are one node
+ *   edges          AFIS_LINK_ANY: cell (q, c) is an edge when it reaches and row q and column c are different nodes.  AFIS_LINK_MUTUAL: and the REVERSE cell reaches too
+ *                  — the matcher is not symmetric: cell (A, B) is A as a query view against B as a gallery template —: the cell in the first row whose node is c's
+ *                  node, at the column of row q's print.  afis_link_subject_groups' row_node names only a person: the column is the FIRST column, by ascending global
+ *                  template index, whose node is q's node; a reverse cell at another print of the same person is not seen.  Where no such row or no such column
+ *                  exists in this matrix the cell is not an edge: it cannot be confirmed here.  The reverse cell is read from the same matrix, filtered or not, as the
+ *                  forward cell.  A cell between a node and itself is never an edge and never counted: a print against itself, two prints of one person, a repeated
+ *                  query print.  n_edges is the number of cells that are edges: a mutual pair counts as two.  In AFIS_LINK_ANY mode with row_node NULL it is the sum
+ *                  of afis_rank_hits_filtered's n_hits at min_score
+ *   groups         the connected components of that graph that hold at least two nodes (single linkage).  The order of nodes: named nodes by ascending name, then
+ *                  anonymous rows by ascending q; a group's members stand in that order and the groups are ordered by their first member.  A group always holds a
+ *                  named node.  A subset listed out of order behaves as everywhere else: names are global and the order is by name
+ * Outputs: n_groups and n_members are the true totals; group_off[0 .. n_listed] is a CSR into member over the longest prefix of the groups that fits both caps, n_listed
+ * the groups in it.  The caps may be 0: counts only (group_off still takes group_off[0]).  The result is a function of the matrix and the arguments only, never of the
+ * order in which the device meets the edges.
+ * AFIS_EINVAL, before anything is queued and with the matrix still rankable, in addition to afis_rank_hits_filtered's cases: a NaN min_score, a mode other than 0 or 1, a
+ * row_node below -1, a negative cap, a null output (member may be null at cap_members 0).  An empty shard or n_q == 0: AFIS_OK, every count 0, no device work.  Device
+ * and pinned room — the filtered copy, 12 bytes per node (columns or persons, named rows, anonymous rows) and the tables, 8 bytes per node to return — is ensured before
+ * anything is queued (AFIS_EDEVICE otherwise).  AFIS_EDEVICE "the union did not settle": a step bound of the device's union-find (csrc/link_groups.h derives it) was
+ * reached, which a correct run never does; the matrix stays rankable.  Everything else is afis_rank_hits_filtered's: which searches count and what invalidates the
+ * matrix, the AFIS_ESTATE cases, the handles' life cycles.  No result of a search changes because these functions exist.
+ * On the device (csrc/link_groups.hip): one pass over the matrix in k_score_hist_rows' access pattern, with work only where a cell reaches — mutual mode adds one
+ * dependent read there — and a lock-free union-find whose hooks always hang the greater root under the smaller; labels, group sizes and the compaction of the linked
+ * nodes follow behind a kernel boundary.  The counts return first, then 8 bytes per linked node: what crosses PCIe is proportional to the linked nodes, not to G.
+ * Options "link_groups_us" (read-only): the device time of the last call's launches; "link_d2h_bytes" (read-only): the bytes it returned from the device, 32 where
+ * nothing links.
+ * Measured on one MI355X on planted matrices of cells uniform in [0, 1) (tools/link_groups_timing.py, profiles/link_groups_timing.json; medians of three rounds after
+ * a discarded first, the cases interleaved, spread in brackets), AFIS_LINK_ANY: 100 latents x 100 000 — 32 us [2] where no cell reaches (afis_score_histogram with
+ * one edge over the same matrix, which reads it once: 32 us [13]; ratio 1.0), 282 us [4] where 1e-3 of the cells reach (9 983 edges, one group of 9 568 nodes, 76 576
+ * bytes returned), 2 997 us [44] where every cell reaches (1e7 edges); 1 000 prints x 100 000 — 121 us [6] (the histogram: 155 us [1]; ratio 0.78; 32 bytes
+ * returned), 1 247 us [48] at 1e-3 (100 024 edges, 63 757 nodes linked, 510 088 bytes), 188 us [4] at 1e-3 in AFIS_LINK_MUTUAL (2 edges), 3 359 us [221] where every
+ * cell reaches (1e8 edges).  The host route — the matrix's bytes copied to the host (0.7 / 7.2 ms) plus numpy keys and a Python union-find — took 66 and 74 ms for
+ * the latents' matrix and 492 and 573 ms for the prints' at the first two thresholds.
+ * Shards (host/sharding.py::merge_link_groups): a host union over the per-rank CSRs by member name.  Named nodes share one name space across ranks; the anonymous rows
+ * -1 - q are shared when every rank ran the same queries.  AFIS_LINK_MUTUAL groups merge correctly only where a pair's two cells lie on one rank.
+ * These calls do not give: linkage rules other than single linkage — average or complete linkage, a per-group weakest link: a later call on top of the same labels —;
+ * mutual confirmation across ranks; the `match` CLI. */
+#define AFIS_LINK_ANY    0
+#define AFIS_LINK_MUTUAL 1
+int afis_link_groups(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                     const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/, int n_q,
+                     const int64_t* row_node /*[n_q] or NULL*/, float min_score, int mode, int64_t cap_groups, int64_t cap_members,
+                     int64_t* n_edges, int64_t* n_groups, int64_t* n_members, int64_t* n_listed,
+                     int64_t* group_off /*[cap_groups + 1]*/, int64_t* member /*[cap_members]*/);
+int afis_link_subject_groups(afis_ctx* ctx, afis_subjects* s, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                             const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/, int n_q,
+                             const int64_t* row_node /*[n_q] subject ids, or NULL*/, float min_score, int mode, int64_t cap_groups, int64_t cap_members,
+                             int64_t* n_edges, int64_t* n_groups, int64_t* n_members, int64_t* n_listed,
+                             int64_t* group_off /*[cap_groups + 1]*/, int64_t* member /*[cap_members]*/);
+
 /* Case lists (no reference counterpart): an examiner's unit of work is a CASE — the same impression encoded twice, several lifts of one finger, several fingers of one
  * hand — and fusing the queries of a case is one list per case instead of one per query.  Both calls rank the matrix of the context's LAST search; a case cannot span
  * searches: all its latents must be queries of the one search that is ranked.  On the device the member rows of every case are folded into one fused row
@@ -1274,6 +1338,10 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * k_transpose_scores; then the counts' memset and k_score_hist_rows), from HIP events around them; 0 when that call queued nothing.
  * "entries_at_us" (read-only): the device time of the last afis_entries_at's launches (for a filtered call the filter pass of hit_filter.hip first; then per digit of the
  * select the bins' memset, k_select_count and k_select_step, and k_select_finish), from HIP events around them; 0 when that call queued nothing.
+ * "link_groups_us" (read-only): the device time of the last afis_link_groups' or afis_link_subject_groups' launches (for a filtered call the filter pass of hit_filter.hip
+ * first; then the counters' memset, k_link_init, for persons in mutual mode k_link_first_cols and k_link_row_cols, k_link_scan, k_link_flatten and k_link_compact), from
+ * HIP events around them; 0 when that call queued nothing.
+ * "link_d2h_bytes" (read-only): the bytes that call returned from the device: 32 of counters, then 8 per node in a group of two or more; 0 when that call queued nothing.
  * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
  * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
  * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.

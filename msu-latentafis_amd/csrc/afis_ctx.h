@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -183,6 +183,9 @@ struct afis_ctx : Shard {
     int64_t score_histogram_us = 0;      // option score_histogram_us (read-only): device time of the last afis_score_histogram's launches (the filter pass, axis 1: the transposition, the table's memset, k_score_hist_rows)
     DevBuf sel_tab, sel_out;             // afis_entries_at: the call's tables (prefix [m] | its spare [m] | remain [m] uint64, the bins [m][256] uint64, rows | off | row [m] | first [m] int32) and its answers (idx [m] int64 | score [m] | status [m] int32)
     int64_t entries_at_us = 0;           // option entries_at_us (read-only): device time of the last afis_entries_at's launches (the filter pass, then per digit the bins' memset, k_select_count and k_select_step; k_select_finish)
+    DevBuf link_tab, link_out;           // afis_link_groups / afis_link_subject_groups: the call's words (afis_link.cpp has the layout: counters, parent | label | size [n_nodes] int32, the subject form's first_col, the uploaded tables) and the (node, label) pairs of the linked nodes
+    int64_t link_groups_us = 0;          // option link_groups_us (read-only): device time of the last such call's launches (the filter pass, the counters' memset, k_link_init, the subject form's two column kernels in mutual mode, k_link_scan, k_link_flatten, k_link_compact)
+    int64_t link_d2h_bytes = 0;          // option link_d2h_bytes (read-only): bytes that call returned from the device: 32 of counters, then 8 per linked node
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
     DevBuf pair_buf, pair_tex_slab;      // every pair-list call (PairCall below has the layout), grown on demand: one chunk's candidate lists, survivors, counts, parts and tables — about 5.8 KB per pair of option corr_pairs_per_launch for afis_correspondences_pairs; with afis_score_pairs' dense row maxima and scores kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch —, and the texture list kernel's slab for a chunk's launches of afis_score_pairs

@@ -452,6 +452,29 @@ hipError_t launch_score_hist(const float* matrix, int rows, int cols, const uint
 hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* row, const int32_t* first, size_t m,
                              unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, const long long* d_global, long long index_base,
                              long long* idx, float* score, int32_t* status, hipStream_t stream);
+// Link groups (link_groups.hip; the definitions: link_groups.h).
+// launch_link_groups       the connected components of the graph the cells of matrix [n_q][G] that reach scan.thr make of rows and columns: k_link_init, in the subject
+//                          form's mutual mode (n_first = the handle's slots > 0) the first column of every person (first_col [n_first]) and from it col_of_row_out
+//                          [n_q] — the array scan.col_of_row names —, k_link_scan (the one pass over the matrix: a workgroup takes kLinkChunkScalar adjacent columns of a
+//                          strip of kFilterRows rows, kLinkChunkVec where rows take 16-byte loads; it counts the edges into *scan.n_edges and unites their nodes in
+//                          scan.parent), then, behind the kernel boundary, k_link_flatten (label [n_nodes], size [n_nodes]) and k_link_compact: the (node, label) pairs
+//                          of the nodes in groups of two or more -> out_pairs [n_nodes][2] at most, *n_pairs how many.  The caller zeroes *scan.n_edges, *scan.err and *n_pairs.
+struct LinkScan {
+    uint32_t thr;                         // rank_key(min_score)
+    int32_t n_nodes;
+    const int32_t* row_node;              // [n_q] the node of a row
+    const int32_t* first_row;             // [n_nodes] mutual mode: the first row whose node this is, -1: none; NULL: any mode
+    const int32_t* col_of_row;            // [n_q] mutual mode: the column of the row's print, -1: none
+    const int32_t* slot_of;               // the subject form: the slot of a template of the resident shard (afis_subjects::d_slot_of); NULL: a column's node is its position
+    const long long* d_global;            // ... of column p: template d_global[p] - index_base (a subset's matrix), NULL: template p
+    long long index_base;
+    const u64* excl; size_t n_excl;       // the subject form: the excluded (row << 32 | slot) keys, ascending
+    int32_t* parent;                      // [n_nodes]
+    u64* n_edges; uint32_t* err;          // the cells that are edges; != 0: a step bound was reached (the union did not settle)
+};
+constexpr int kLinkChunkScalar = 256, kLinkChunkVec = 1024;   // k_link_scan: columns per workgroup, one column per thread or four where a thread takes 16 bytes
+hipError_t launch_link_groups(const float* matrix, int n_q, int G, const LinkScan& scan, int32_t* label, int32_t* size, int32_t* first_col, int32_t n_first, int32_t* col_of_row_out,
+                              uint32_t* n_pairs, int32_t* out_pairs, hipStream_t stream);
 hipError_t read_phase_cycles(unsigned long long* out32, bool reset);
 hipError_t read_graph_phase_cycles(unsigned long long* out16, bool reset);
 

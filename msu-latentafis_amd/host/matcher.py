@@ -75,7 +75,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at", "afis_link_groups", "afis_link_subject_groups",
            "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
@@ -166,6 +166,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         u64p = C.POINTER(C.c_uint64)
         lib.afis_score_histogram.argtypes = [vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, C.c_int, fp, i64p]
         lib.afis_entries_at.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
+    if hasattr(lib, "afis_link_groups"):                                # link groups; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64)
+        lib.afis_link_groups.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, i64p, C.c_float, C.c_int, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, i64p, i64p]
+        lib.afis_link_subject_groups.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, i64p, C.c_float, C.c_int, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, i64p, i64p]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     if hasattr(lib, "afis_correspondences_pairs"):                      # the pair-list export; absent from older builds compared by tools/lib_ab.py
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
@@ -771,6 +775,50 @@ class Matcher:
                                            _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
                                            _ptr(ix, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None))
         return {"status": st, "idx": ix, "score": sc}
+
+    # ---- link groups: the connected components rows and columns make above a decision score ----------------------------------
+    def _link(self, fn, min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q):
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        rn = None if row_node is None else np.ascontiguousarray(np.asarray(row_node, np.int64).reshape(-1))
+        if rn is not None and len(rn) != n_q:
+            raise ValueError("one row_node per query")
+        flt = (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+               _ptr(ent, C.c_int64) if ent is not None else None)
+
+        def call(cg, cm):
+            cnt = np.zeros(4, np.int64)
+            goff = np.zeros(max(cg, 0) + 1, np.int64); mem = np.zeros(max(cm, 1), np.int64)
+            c = [C.cast(cnt.ctypes.data + 8 * i, C.POINTER(C.c_int64)) for i in range(4)]
+            self._chk(fn(flt, n_q, _ptr(rn, C.c_int64) if rn is not None and n_q else None, min_score, mode, cg, cm, c[0], c[1], c[2], c[3], _ptr(goff, C.c_int64), _ptr(mem, C.c_int64)))
+            return cnt, goff, mem
+
+        if cap_groups is None or cap_members is None:                       # the counts first, then lists of exactly that size
+            cnt, _, _ = call(0, 0)
+            cap_groups = int(cnt[1]) if cap_groups is None else cap_groups; cap_members = int(cnt[2]) if cap_members is None else cap_members
+        cnt, goff, mem = call(cap_groups, cap_members)
+        listed = int(cnt[3])
+        return {"n_edges": int(cnt[0]), "n_groups": int(cnt[1]), "n_members": int(cnt[2]), "n_listed": listed, "group_off": goff[:listed + 1].copy(), "member": mem[:int(goff[listed])].copy()}
+
+    def link_groups(self, min_score: float, mode: int = 0, row_node=None, labels=None, masks=None, excl=None, cap_groups: Optional[int] = None, cap_members: Optional[int] = None,
+                    n_q: Optional[int] = None):
+        """The groups the LAST search's matrix makes at min_score: the connected components, of two or more nodes, of the graph whose nodes are the columns (named by GLOBAL
+        template index) and the rows — row q is the node row_node[q] (a global template index: the resident print the row is; a name that is a column's is that column's
+        node) or, at -1 / row_node None, a latent reported as -1 - q — and whose edges are the cells that reach min_score between different nodes (mode 0,
+        AFIS_LINK_ANY), in mode 1 (AFIS_LINK_MUTUAL) only where the reverse cell reaches too.  labels / masks / excl are rank_hits_filtered's.  -> n_edges (cells that are
+        edges), n_groups, n_members (true totals), n_listed, group_off [n_listed + 1], member [group_off[-1]]: a CSR over the longest prefix of the groups that fits both
+        caps; members by ascending name, then latents; groups by their first member.  A cap of None: the call runs twice, the first time for the counts.  Groups of
+        disjoint shards merge by name (host/sharding.py::merge_link_groups).  A normalised matrix is accepted: min_score in z units.  The matrix stays as it is."""
+        return self._link(lambda f, nq, rn, ms, md, cg, cm, *out: self.lib.afis_link_groups(self.ctx, *f, nq, rn, ms, md, cg, cm, *out),
+                          min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q)
+
+    def link_subject_groups(self, handle, min_score: float, mode: int = 0, row_node=None, labels=None, masks=None, excl=None, cap_groups: Optional[int] = None,
+                            cap_members: Optional[int] = None, n_q: Optional[int] = None):
+        """link_groups over the enrolled persons of a subjects_create handle: all columns of one person are ONE node, named by the subject id; row_node and excl hold
+        SUBJECT ids (an id the handle does not hold is a node of its own name); two prints of one person never link.  Mode 1 reads the reverse cell at the person's
+        first column by ascending global index."""
+        return self._link(lambda f, nq, rn, ms, md, cg, cm, *out: self.lib.afis_link_subject_groups(self.ctx, handle[0], *f, nq, rn, ms, md, cg, cm, *out),
+                          min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q)
 
     # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
     def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):

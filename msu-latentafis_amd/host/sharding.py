@@ -339,6 +339,46 @@ def histogram_rank_bin(counts, rank):
     return (int(b[0]), int(res[0])) if one else (b, res)
 
 
+def merge_link_groups(per_rank):
+    """Link groups of the ranks of a sharded gallery merged by member name: per_rank is what Matcher.link_groups / link_subject_groups returned on every rank — a sequence
+    of {"group_off": [g + 1], "member": [group_off[-1]]}, every rank's lists complete (n_listed == n_groups) —; groups of different ranks that share a member become one
+    group (a host union over the names).  Named nodes share one name space across ranks: global template indices, or subject ids.  The anonymous rows -1 - q are shared
+    only when every rank ran the SAME queries, the usual sharded latent search; otherwise rename them before merging.  -> {"n_groups", "n_members", "group_off",
+    "member"} in the calls' own order: members by ascending name, then the anonymous rows by ascending q; groups by their first member.  With AFIS_LINK_ANY that is
+    what one context over the whole gallery returns.  AFIS_LINK_MUTUAL groups merge correctly only where a pair's two cells lie on one rank: a rank confirms a cell
+    by a reverse cell of its own matrix, so a pair of prints enrolled on two ranks is confirmed by neither.  ValueError where a CSR is malformed."""
+    parent = {}
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for r in per_rank:
+        off = np.asarray(r["group_off"], np.int64).reshape(-1); mem = np.asarray(r["member"], np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or (np.diff(off) < 2).any() or off[-1] != len(mem):
+            raise ValueError("merge_link_groups: group_off is a CSR into member, from 0 to len(member), every group of two or more")
+        for g in range(len(off) - 1):
+            names = [int(t) for t in mem[off[g]:off[g + 1]]]
+            for t in names:
+                parent.setdefault(t, t)
+            a = find(names[0])
+            for t in names[1:]:
+                b = find(t)
+                if a != b:
+                    parent[b] = a
+    key = lambda t: (0, t) if t >= 0 else (1, -1 - t)                       # named nodes by name, then the anonymous rows by q
+    groups = {}
+    for t in parent:
+        groups.setdefault(find(t), []).append(t)
+    out = sorted((sorted(g, key=key) for g in groups.values()), key=lambda g: key(g[0]))
+    off = np.zeros(len(out) + 1, np.int64)
+    off[1:] = np.cumsum([len(g) for g in out])
+    member = np.array([t for g in out for t in g], np.int64)
+    return {"n_groups": len(out), "n_members": len(member), "group_off": off, "member": member}
+
+
 CORR_NOT_RUN, CORR_NOT_COVERED = -1, -2                                    # AFIS_CORR_* (include/afis_matcher.h)
 PAIR_OK, PAIR_NOT_COVERED = 0, 1                                            # AFIS_PAIR_* (include/afis_matcher.h)
 
