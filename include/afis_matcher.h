@@ -454,7 +454,7 @@ int afis_score_stat_moments(const afis_score_stat* st, double* mean, double* sd)
  * 64 (207 and 687 us on the one-bin matrix); afis_score_stats along the rows of the same matrix in the same process, which also reads every word once, 52 us.
  * Shards: histograms add (host/sharding.py::merge_score_histograms); ranks do not, so there is no global afis_entries_at — the sharded quantile recipe of INTEGRATION.md
  * brackets the rank with the merged histogram (histogram_rank_bin) and settles it with afis_count_before.
- * These calls do not give: persons at a rank or histograms of persons' scores; ranks in case lists and in column (reverse) lists; bins of unequal weight. */
+ * These calls do not give: ranks in case lists and in column (reverse) lists; bins of unequal weight (persons: the person distributions below). */
 #define AFIS_HIST_EDGES_MAX 1023          /* 1024 bins */
 #define AFIS_HIST_COUNTS_MAX (1 << 24)    /* counts one call returns: outputs x (n_edges + 1) */
 int afis_score_histogram(afis_ctx* ctx, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
@@ -464,6 +464,68 @@ int afis_entries_at(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint64
                     const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl /*[excl_off[n_q]]*/,
                     int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* rank /*[n_targets], >= 0*/,
                     int32_t* status /*[n_targets]*/, int64_t* idx /*[n_targets], GLOBAL*/, float* score /*[n_targets]*/);
+
+/* Person distributions (no reference counterpart): afis_score_stats, afis_score_histogram and afis_entries_at over enrolled PERSONS — the three calls that turn a
+ * matrix into a decision score, for the lists an examiner is handed.  A person's score is the maximum over their templates: someone enrolled with two ten-print cards
+ * puts 20 cells into a latent's cohort under afis_score_stats and a single flat print one, so the z-score that cuts afis_rank_subject_hits must come from the persons'
+ * statistics; and "the score at which 1 latent in 100 raises a false person alarm" is a question about the distribution of persons' best scores.  All three read the
+ * score matrix of the context's LAST search through afis_rank_subject_hits_filtered's own checks and pre-passes — the handle's, labels and masks on the TEMPLATES, excl
+ * as SUBJECT ids, the filter pass, k_subject_best over the filtered rows, the excluded persons dropped: no second definition of eligibility, none of a person's best.
+ * Definitions (csrc/score_cell.h, csrc/score_hist.h and csrc/score_stats.h hold them once, for the kernels and the host; the tests hold the device to them exactly):
+ *   person cell    of (query q, person s): the best eligible covered cell of the person's templates by the RAW ordered word (csrc/score_order.h::ordered_word), ties to
+ *                  the lowest position — not rank_key: -0.0 stands below +0.0, and a NaN with the sign clear stands above +inf and wins.  There is NO cell where the
+ *                  search covered none of the person's templates (a subset search), the person is on q's excl list, or every template of theirs is ineligible or
+ *                  itself holds 0xffffffff
+ *   entry          a person cell whose ordered word >= ordered_word(-inf): what afis_rank_subject_hits counts at min_score = -INFINITY
+ *   bin            an entry goes to bin b = the number of edges e with ordered_word(e) <= the cell's ordered word.  Edges must not be NaN and must ascend strictly BY
+ *                  THAT KEY: (-0.0, +0.0) is a valid pair of edges here — three bins — although afis_score_histogram refuses it, and a person whose best is -0.0
+ *                  falls below an edge at +0.0.  THE PROPERTY: for every j, counts[q][j + 1] + ... + counts[q][n_edges] is the n_hits
+ *                  afis_rank_subject_hits_filtered returns query q at min_score = edges[j] under the same arguments; the sum of all bins its n_hits at -INFINITY
+ *   statistic      afis_score_stats' definitions, unchanged, over the persons' score words: a person whose best is -1 (all their prints empty) is outside, a best of
+ *                  -0.0 is valued with q = 0, a NaN with the sign clear is outside; min and max by rank_key.  THE BOUND n <= 2^27 holds per statistic
+ *   entry at r     entry r of the list afis_rank_subject_hits_filtered(..., -INFINITY, cap) gives query q, for any cap > r and every r, not only the first
+ *                  AFIS_HITS_MAX: ordered word descending, equal words by ascending subject id
+ * "[subjects]" below is one output per distinct id of the handle in ascending id order (the handle's slots), whatever the search covered.
+ * afis_subject_score_stats      axis 0: out [n_q], per query the statistic over the persons (the person cohort: T-norm at the person level); axis 1: out [subjects],
+ *                               per person the statistic over the queries (the per-person Z-norm).  Refuses a normalised matrix with AFIS_ESTATE, as afis_score_stats
+ * afis_subject_score_histogram  axis 0: counts [n_q][n_edges + 1]; axis 1: counts [subjects][n_edges + 1] (the reverse-direction threshold).  Accepts a normalised
+ *                               matrix: edges are then in z units
+ * afis_subject_entries_at       for target (q, r): status AFIS_POS_LISTED, subject_id, subject_score (the bits of the person's best cell) and best_idx (the GLOBAL index
+ *                               of the template that holds it, as afis_rank_subject_hits names it); r at or beyond the row's number of entries: AFIS_POS_NO_ENTRY, id
+ *                               -1, score -inf, best_idx -1.  The round trip: afis_rank_subject_positions(q, subject_id) returns n_before == r.  Accepts a normalised
+ *                               matrix.  On the device the select runs over the composites (ordered word, ~slot), unique inside a row
+ * A person the search did not cover (a subset search) has no cell in any row: along axis 1 their statistic is (0, 0, 0, 0, 0, +inf, -inf) and their counts are 0; the
+ * names stay global.  The matrix is neither written nor invalidated; a refused call leaves it rankable.  AFIS_EINVAL, before anything is queued: a handle that is not a
+ * live subject handle of this context, an axis other than 0 or 1, n_edges outside 1 .. AFIS_HIST_EDGES_MAX, a NaN edge, edges that do not ascend strictly, outputs x
+ * (n_edges + 1) above AFIS_HIST_COUNTS_MAX, a statistic over more than 2^27 cells, a negative rank, a query outside 0 .. n_q - 1, a null output where there is
+ * something to return, and afis_rank_subject_hits_filtered's cases.  n_q == 0, an empty shard or a handle without subjects: AFIS_OK, no device work — statistics empty,
+ * counts 0, every target AFIS_POS_NO_ENTRY.  Device and pinned room — the filtered copy, 12 bytes per (query, person) for the maxima and their keys, axis 1's transposed
+ * keys, the template forms' tables and outputs — is ensured before anything is queued (AFIS_EDEVICE otherwise).  Everything else is afis_rank_subject_hits_filtered's.
+ * NO NEW NORMALISING CALL: z = (v - offset) x scale with scale > 0 is increasing, so a person's best z is the z of their best score; afis_normalize_scores(axis 1),
+ * fed with every column's PERSON pair (host/matcher.py::expand_subject_pairs), or axis 0 with the person cohort's pair, leaves exactly the person z-scores in every
+ * subject list.
+ * On the device: k_subject_keys takes the high halves of the maxima [n_q][S] into a matrix of 4-byte person cells in one coalesced pass, and the kernels of the
+ * template forms run over it — the same counting bodies, instantiated for a cell that is its own key (csrc/score_cell.h); only the select's last kernel differs.
+ * Options "subject_score_stats_us", "subject_score_histogram_us" and "subject_entries_at_us" (read-only): the device time of the last call's launches, the pre-passes
+ * included.  Measured on one MI355X on a planted matrix of 100 latents x 100 000 templates (tools/subject_distribution_timing.py,
+ * profiles/subject_distribution_timing.json; medians of five rounds after a discarded first, the cases interleaved), 10 000 persons of ten templates / every template a
+ * person: afis_subject_score_stats per latent 93 / 145 us, afis_subject_score_histogram at 256 bins 85 / 140 us, afis_subject_entries_at with one rank per row 152 / 283
+ * us — beside afis_rank_subject_hits at cap 1 with the same handle (the fold and one rank pass) 77 / 360 us and the template forms over the 100 000 columns 64, 68 and
+ * 207 us: every person call stays below the sum of its two yardsticks (0.23 to 0.83 of it).
+ * Shards: person distributions merge only for galleries SHARDED BY PERSON — the maxima of two ranks over one person's prints neither add nor concatenate, the caveat
+ * of merge_case_subject_hits' sums — (host/sharding.py::merge_subject_score_stats, merge_subject_score_histograms: ValueError where an id appears on two ranks).
+ * These calls do not give: distributions of case lists or of column (reverse) lists; an exchange between ranks inside the library; persons whose prints straddle
+ * shards. */
+int afis_subject_score_stats(afis_ctx* ctx, afis_subjects* s, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                             const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/, int n_q,
+                             afis_score_stat* out /*axis 0: [n_q]; axis 1: [subjects]*/);
+int afis_subject_score_histogram(afis_ctx* ctx, afis_subjects* s, int axis, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                                 const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/, int n_q,
+                                 int n_edges, const float* edges /*[n_edges]*/, int64_t* counts /*axis 0: [n_q][n_edges + 1]; axis 1: [subjects][n_edges + 1]*/);
+int afis_subject_entries_at(afis_ctx* ctx, afis_subjects* s, afis_labels* labels /*or NULL*/, const uint64_t* masks /*[n_q][3] or NULL*/,
+                            const int64_t* excl_off /*[n_q + 1] or NULL*/, const int64_t* excl_subject /*[excl_off[n_q]]*/,
+                            int n_q, int64_t n_targets, const int32_t* query /*[n_targets]*/, const int64_t* rank /*[n_targets], >= 0*/,
+                            int32_t* status /*[n_targets]*/, int64_t* subject_id /*[n_targets]*/, float* subject_score /*[n_targets]*/, int64_t* best_idx /*[n_targets], GLOBAL*/);
 
 /* Link groups (no reference counterpart): every call above answers a question about one row or one column; these two look at rows and columns together and return the
  * GROUPS the last search's matrix makes above a decision score — consolidation: which enrolled prints, or persons, are one finger or person (if A hits B and B hits C
@@ -1338,6 +1400,13 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * k_transpose_scores; then the counts' memset and k_score_hist_rows), from HIP events around them; 0 when that call queued nothing.
  * "entries_at_us" (read-only): the device time of the last afis_entries_at's launches (for a filtered call the filter pass of hit_filter.hip first; then per digit of the
  * select the bins' memset, k_select_count and k_select_step, and k_select_finish), from HIP events around them; 0 when that call queued nothing.
+ * "subject_score_stats_us" (read-only): the device time of the last afis_subject_score_stats' launches (for a filtered call the filter pass of hit_filter.hip first; then
+ * the maxima's memset, k_subject_best, the excluded persons' drops and k_subject_keys; then afis_score_stats' kernels over the person cells), from HIP events around
+ * them; 0 when that call queued nothing.
+ * "subject_score_histogram_us" (read-only): the same for the last afis_subject_score_histogram (behind k_subject_keys: axis 1's transposition, the table's memset,
+ * k_score_hist_rows over the person cells); 0 when that call queued nothing.
+ * "subject_entries_at_us" (read-only): the same for the last afis_subject_entries_at (behind k_subject_keys: per digit of the select the bins' memset, k_select_count and
+ * k_select_step, and k_subject_select_finish); 0 when that call queued nothing.
  * "link_groups_us" (read-only): the device time of the last afis_link_groups' or afis_link_subject_groups' launches (for a filtered call the filter pass of hit_filter.hip
  * first; then the counters' memset, k_link_init, for persons in mutual mode k_link_first_cols and k_link_row_cols, k_link_scan, k_link_flatten and k_link_compact), from
  * HIP events around them; 0 when that call queued nothing.

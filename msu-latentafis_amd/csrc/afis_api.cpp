@@ -112,7 +112,7 @@ void afis_destroy(afis_ctx* c)
     for (afis_labels* lb : c->label_sets) release_labels(lb);                // label handles that are still live
     c->label_sets.clear();
     free_gallery_dev(c);
-    c->out_perm.release(); c->subj_best.release(); c->subj_out.release(); c->hits_out.release(); c->scores_t.release(); c->case_fused.release(); c->case_tab.release(); c->filt_scores.release(); c->filt_tab.release(); c->pos_tab.release(); c->pos_out.release(); c->stat_tab.release(); c->stat_out.release(); c->hist_tab.release(); c->sel_tab.release(); c->sel_out.release(); c->link_tab.release(); c->link_out.release(); c->pair_buf.release(); c->pair_tex_slab.release(); c->elig_scores.release(); c->wt_tab.release(); c->casc_buf.release(); c->casc_slab.release();
+    c->out_perm.release(); c->subj_best.release(); c->subj_out.release(); c->hits_out.release(); c->scores_t.release(); c->case_fused.release(); c->case_tab.release(); c->filt_scores.release(); c->filt_tab.release(); c->pos_tab.release(); c->pos_out.release(); c->stat_tab.release(); c->stat_out.release(); c->hist_tab.release(); c->sel_tab.release(); c->sel_out.release(); c->subj_keys.release(); c->link_tab.release(); c->link_out.release(); c->pair_buf.release(); c->pair_tex_slab.release(); c->elig_scores.release(); c->wt_tab.release(); c->casc_buf.release(); c->casc_slab.release();
     c->codewords.release(); c->table.release(); c->lut.release(); c->rm_val.release(); c->rm_arg.release(); c->rm_cv.release(); c->rm_n.release();
     c->parts.release(); c->scores.release(); c->scratch.release(); c->cands.release(); c->cand_n.release(); c->minu_fb.release(); c->diag.release(); c->topk_idx.release(); c->topk_score.release(); c->lutq.release(); c->lutq_min.release(); c->lutq_rng.release(); c->lutq_rowc.release(); c->lut32.release();
     c->mf_cw16.release(); c->mf_cwn.release(); c->mf_bfrag.release(); c->mf_rowk.release(); c->mf_rec.release(); c->mf_stats.release(); c->tex_slab.release(); c->minu_slab.release();
@@ -194,6 +194,9 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "normalize_us") *value = ctx->normalize_us;                          // read-only: device time of the last afis_normalize_scores' launches
     else if (n == "score_histogram_us") *value = ctx->score_histogram_us;              // read-only: device time of the last afis_score_histogram's launches
     else if (n == "entries_at_us") *value = ctx->entries_at_us;                        // read-only: device time of the last afis_entries_at's launches
+    else if (n == "subject_score_stats_us") *value = ctx->subject_score_stats_us;      // read-only: device time of the last afis_subject_score_stats' launches
+    else if (n == "subject_score_histogram_us") *value = ctx->subject_score_histogram_us;   // read-only: device time of the last afis_subject_score_histogram's launches
+    else if (n == "subject_entries_at_us") *value = ctx->subject_entries_at_us;        // read-only: device time of the last afis_subject_entries_at's launches
     else if (n == "link_groups_us") *value = ctx->link_groups_us;                      // read-only: device time of the last afis_link_groups' / afis_link_subject_groups' launches
     else if (n == "link_d2h_bytes") *value = ctx->link_d2h_bytes;                      // read-only: bytes that call returned from the device (the counts, then 8 per linked node)
     else if (n == "rank_positions_us") *value = ctx->rank_positions_us;                // read-only: device time of the last afis_rank_positions' / afis_rank_subject_positions' / afis_count_before's launches

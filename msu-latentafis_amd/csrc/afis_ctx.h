@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -183,6 +183,8 @@ struct afis_ctx : Shard {
     int64_t score_histogram_us = 0;      // option score_histogram_us (read-only): device time of the last afis_score_histogram's launches (the filter pass, axis 1: the transposition, the table's memset, k_score_hist_rows)
     DevBuf sel_tab, sel_out;             // afis_entries_at: the call's tables (prefix [m] | its spare [m] | remain [m] uint64, the bins [m][256] uint64, rows | off | row [m] | first [m] int32) and its answers (idx [m] int64 | score [m] | status [m] int32)
     int64_t entries_at_us = 0;           // option entries_at_us (read-only): device time of the last afis_entries_at's launches (the filter pass, then per digit the bins' memset, k_select_count and k_select_step; k_select_finish)
+    DevBuf subj_keys;                    // afis_subject_score_stats / afis_subject_score_histogram / afis_subject_entries_at: the person cells [n_q][S] uint32, the high halves of subj_best (k_subject_keys); their tables and answers go through the template forms' buffers (stat_tab, stat_out, hist_tab, scores_t, sel_tab, sel_out)
+    int64_t subject_score_stats_us = 0, subject_score_histogram_us = 0, subject_entries_at_us = 0;   // options of those names (read-only): device time of the last such call's launches (the filter pass, the maxima's memset, k_subject_best, the drops, k_subject_keys, then the template form's kernels over the person cells)
     DevBuf link_tab, link_out;           // afis_link_groups / afis_link_subject_groups: the call's words (afis_link.cpp has the layout: counters, parent | label | size [n_nodes] int32, the subject form's first_col, the uploaded tables) and the (node, label) pairs of the linked nodes
     int64_t link_groups_us = 0;          // option link_groups_us (read-only): device time of the last such call's launches (the filter pass, the counters' memset, k_link_init, the subject form's two column kernels in mutual mode, k_link_scan, k_link_flatten, k_link_compact)
     int64_t link_d2h_bytes = 0;          // option link_d2h_bytes (read-only): bytes that call returned from the device: 32 of counters, then 8 per linked node
@@ -549,6 +551,12 @@ struct __attribute__((visibility("hidden"))) FilterPass {
     int queue_cells();
     int queue_drop_subjects(int64_t S);
 };
+// afis_distribution.cpp
+// The person cells of a person distribution call (afis_distribution.cpp, afis_normalize.cpp): ensure_subject_keys with the caller's other DevBuf::ensure()s — subj_best
+// and subj_keys [n_q][S] —; queue_subject_keys after the uploads: afis_rank_subject_hits_filtered's pre-passes, unchanged and in its order (fp.queue_cells(),
+// queue_subject_best(fp.matrix()), fp.queue_drop_subjects(S)), then k_subject_keys -> ctx->subj_keys
+hipError_t ensure_subject_keys(afis_ctx* ctx, const afis_subjects* subj) __attribute__((visibility("hidden")));
+int queue_subject_keys(afis_ctx* ctx, const afis_subjects* subj, FilterPass& fp) __attribute__((visibility("hidden")));
 // afis_normalize.cpp
 // order[t]: the caller's column of position t of the last search's matrix — a subset listed out of order stands in ascending global index order on the device; empty: the identity
 std::vector<int32_t> column_order(const LastSearch& ls) __attribute__((visibility("hidden")));

@@ -452,6 +452,19 @@ hipError_t launch_score_hist(const float* matrix, int rows, int cols, const uint
 hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* row, const int32_t* first, size_t m,
                              unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, const long long* d_global, long long index_base,
                              long long* idx, float* score, int32_t* status, hipStream_t stream);
+// Person distributions (score_hist.hip, score_stats.hip; the person cell: score_cell.h): the launchers above over persons instead of templates.
+// launch_subject_keys      best [n_q][S] as launch_subject_best (and the drops behind it) left it -> keys [n_q][S], the composites' high halves: the person cells
+// launch_subject_stats     launch_score_stats over keys [n_q][S]: a cell stands for the score word whose ordered word it is
+// launch_subject_hist      launch_score_hist over keys [rows][cols] (or their transposition); edge_keys are ordered words, and a cell is its own key
+// launch_subject_entries_at  launch_entries_at over keys [n_q][S], a position being a slot -> id (ids[slot]; -1), score (the bits of the person's best cell; -inf),
+//                          best_idx (the position in the low half of best [n_q][S], named index_base + position or d_global[position]; -1), status
+hipError_t launch_subject_keys(const unsigned long long* best, int n_q, int S, uint32_t* keys, hipStream_t stream);
+hipError_t launch_subject_stats(int axis, const uint32_t* keys, int n_q, int S, unsigned long long* tab, void* out, hipStream_t stream);
+hipError_t launch_subject_hist(const uint32_t* keys, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream);
+hipError_t launch_subject_entries_at(const uint32_t* keys, const unsigned long long* best, int S, int G, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets,
+                                     const int32_t* row, const int32_t* first, size_t m, unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain,
+                                     unsigned long long* tab, const long long* ids, const long long* d_global, long long index_base, long long* id, float* score, long long* best_idx,
+                                     int32_t* status, hipStream_t stream);
 // Link groups (link_groups.hip; the definitions: link_groups.h).
 // launch_link_groups       the connected components of the graph the cells of matrix [n_q][G] that reach scan.thr make of rows and columns: k_link_init, in the subject
 //                          form's mutual mode (n_first = the handle's slots > 0) the first column of every person (first_col [n_first]) and from it col_of_row_out

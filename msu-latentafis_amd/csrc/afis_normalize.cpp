@@ -1,4 +1,5 @@
-// afis_normalize.cpp — cohort statistics and z-normalised scores of the C ABI (include/afis_matcher.h).  afis_score_stats reads the last search's matrix along its rows
+// afis_normalize.cpp — cohort statistics and z-normalised scores of the C ABI (include/afis_matcher.h); afis_subject_score_stats is afis_score_stats over persons
+// (score_cell.h: a person's cell is the best of their eligible covered templates).  afis_score_stats reads the last search's matrix along its rows
 // (axis 0: one statistic per query, "T-norm") or its columns (axis 1: one per print, "Z-norm") and returns exact integer statistics (score_stats.h) of the cells the
 // call's filter leaves: the checks are the filtered ranking calls' (check_filtered at min_score = -inf) and the filter runs as it runs there (FilterPass: no second
 // definition of eligibility).  afis_normalize_scores puts every cell of the UNFILTERED matrix on the scale of its row's or column's (offset, scale) pair; the result is
@@ -30,24 +31,26 @@ std::vector<int32_t> column_order(const LastSearch& ls)
     return order;
 }
 
-// afis_score_stats behind its checks; pairs: the exclusions as check_filtered resolved them
-static int score_stats(afis_ctx* ctx, int axis, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, afis_score_stat* out)
+// afis_score_stats (subj == NULL: the cells of the matrix) and afis_subject_score_stats (the person cells [n_q][S] of the handle: queue_subject_keys,
+// afis_distribution.cpp; a column is a slot, the distinct ids ascending) behind their checks; pairs: the exclusions as check_filtered resolved them
+static int score_stats(afis_ctx* ctx, afis_subjects* subj, int axis, const afis_labels* labels, const uint64_t* masks, const std::vector<int32_t>& pairs, afis_score_stat* out)
 {
-    const char* const who = "afis_score_stats";
+    const char* const who = subj ? "afis_subject_score_stats" : "afis_score_stats";
     const LastSearch ls = ctx->last_search;
     const int n_q = ls.n_q;
-    const int64_t G = ls.G, n_out = axis == 0 ? n_q : G, len = axis == 0 ? G : n_q;
+    const int64_t G = ls.G, cols = subj ? subj->S : G, n_out = axis == 0 ? n_q : cols, len = axis == 0 ? cols : n_q;
     if (len > kStatMaxCells) return fail(ctx, AFIS_EINVAL, std::string(who) + ": a statistic takes 2^27 cells at most");
     ScoreStat none{}; none.min = INFINITY; none.max = -INFINITY;
-    if (n_q == 0 || G == 0) {                                               // no cell: no device work
+    if (n_q == 0 || G == 0 || cols == 0) {                                  // no cell: no device work
         for (int64_t i = 0; i < n_out; ++i) memcpy(out + i, &none, sizeof none);
         return AFIS_OK;
     }
-    const std::vector<int32_t> order = axis == 1 ? column_order(ls) : std::vector<int32_t>();
+    const std::vector<int32_t> order = axis == 1 && !subj ? column_order(ls) : std::vector<int32_t>();
     const size_t out_bytes = (size_t)n_out * sizeof(ScoreStat);
-    FilterPass fp{ctx, labels, masks, pairs, false};
+    FilterPass fp{ctx, labels, masks, pairs, subj != nullptr};
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, fp.ensure());
+    if (subj) HIPCHK(ctx, ensure_subject_keys(ctx, subj));
     if (axis == 0) HIPCHK(ctx, ctx->stat_tab.ensure((size_t)n_q * kStatWords * 8));
     HIPCHK(ctx, ctx->stat_out.ensure(out_bytes));
     HIPCHK(ctx, ensure_pin(ctx, out_bytes));
@@ -56,13 +59,18 @@ static int score_stats(afis_ctx* ctx, int axis, const afis_labels* labels, const
     hipStream_t s = ctx->stream;
     for (const HitCall::H2D& u : {fp.masks_up(), fp.pairs_up()}) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipEventRecord(ev[0], s));
-    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is read
-    HIPCHK(ctx, launch_score_stats(axis, fp.matrix(), n_q, (int)G, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, s));
+    if (subj) {
+        AFISCHK(queue_subject_keys(ctx, subj, fp));
+        HIPCHK(ctx, launch_subject_stats(axis, ctx->subj_keys.as<uint32_t>(), n_q, (int)cols, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, s));
+    } else {
+        AFISCHK(fp.queue_cells());                                          // neither masks nor exclusions: nothing, and the search's matrix itself is read
+        HIPCHK(ctx, launch_score_stats(axis, fp.matrix(), n_q, (int)G, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, s));
+    }
     HIPCHK(ctx, hipEventRecord(ev[1], s));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->stat_out.p, out_bytes, hipMemcpyDeviceToHost, s));
     int64_t total_us = 0;
     AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
-    ctx->score_stats_us = total_us;
+    (subj ? ctx->subject_score_stats_us : ctx->score_stats_us) = total_us;
     const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
     if (order.empty()) memcpy(out, pin, out_bytes);
     else for (size_t t = 0; t < order.size(); ++t) memcpy(out + order[t], pin + t * sizeof(ScoreStat), sizeof(ScoreStat));
@@ -128,7 +136,22 @@ int afis_score_stats(afis_ctx* ctx, int axis, afis_labels* labels, const uint64_
     AFISCHK(check_filtered(ctx, who, nullptr, labels, masks, excl_off, excl, n_q, -INFINITY, 1, true, pairs));
     if (ctx->last_search.normalized) return refuse_normalized(ctx, who);
     if (!out && (axis == 0 ? (int64_t)n_q : ctx->last_search.G) > 0) return fail(ctx, AFIS_EINVAL, std::string(who) + ": out is null");
-    return score_stats(ctx, axis, labels, masks, pairs, out);
+    return score_stats(ctx, nullptr, axis, labels, masks, pairs, out);
+}
+
+int afis_subject_score_stats(afis_ctx* ctx, afis_subjects* s, int axis, afis_labels* labels, const uint64_t* masks, const int64_t* excl_off, const int64_t* excl_subject, int n_q,
+                             afis_score_stat* out)
+{
+    const char* const who = "afis_subject_score_stats";
+    if (!ctx || !s) return fail(ctx, AFIS_EINVAL, std::string(who) + ": null argument");
+    ctx->subject_score_stats_us = 0;
+    AFISCHK(check_subject_handle(ctx, who, s));
+    if (axis != 0 && axis != 1) return fail(ctx, AFIS_EINVAL, std::string(who) + ": axis must be 0 (queries) or 1 (subjects)");
+    std::vector<int32_t> pairs;
+    AFISCHK(check_filtered(ctx, who, s, labels, masks, excl_off, excl_subject, n_q, -INFINITY, 1, true, pairs));
+    if (ctx->last_search.normalized) return refuse_normalized(ctx, who);
+    if (!out && (axis == 0 ? (int64_t)n_q : s->S) > 0) return fail(ctx, AFIS_EINVAL, std::string(who) + ": out is null");
+    return score_stats(ctx, s, axis, labels, masks, pairs, out);
 }
 
 int afis_normalize_scores(afis_ctx* ctx, int axis, int n_q, const double* offset, const double* scale, float* scores_out)

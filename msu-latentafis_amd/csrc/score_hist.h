@@ -9,9 +9,13 @@
 // THE ENTRY AT RANK r of a row is the (r + 1)-th greatest composite rank_composite(rank_key, position) of its entries: unique inside a row, so a radix select on the
 // composite needs no tie rule.  Its digits are taken from the top, 8 bits at a time; select_step is one digit's decision over the 256 counts of the entries that share
 // the digits fixed so far.  The low word of a composite is ~position: the bytes of it above the highest position's are 0xff in every entry and are not counted.
+// PERSONS (afis_subject_score_histogram, afis_subject_entries_at): the same three definitions over a row of person cells (score_cell.h: PersonCell) — the cell is the
+// high half K of subj_best, its own key, the RAW ordered word; an edge's key is ordered_word(edge).  So -0.0 and +0.0 are two values, for cells and for edges: (-0.0,
+// +0.0) is a valid pair of edges, and sum(bins j + 1 ..) is what afis_rank_subject_hits counts at min_score = edge j.  The position of a composite is the slot.
 #pragma once
 #include <cstdint>
 
+#include "score_cell.h"
 #include "score_order.h"
 
 namespace afis {
@@ -22,11 +26,12 @@ constexpr int64_t kHistCountsMax = (int64_t)1 << 24;                        // A
 constexpr int kSelectBins = 256;                                            // one digit of the select: 8 bits
 
 // edges [n] as keys: 0, or -1 where an edge is a NaN or the keys do not ascend strictly
+template <class Cell = ScoreCell>
 inline int hist_edge_keys(const float* edges, int n, uint32_t* keys)
 {
     for (int j = 0; j < n; ++j) {
         if (edges[j] != edges[j]) return -1;
-        keys[j] = rank_key(edges[j]);
+        keys[j] = Cell::edge_key(edges[j]);
         if (j > 0 && keys[j] <= keys[j - 1]) return -1;
     }
     return 0;
@@ -42,9 +47,10 @@ AFIS_ORDER_FN int hist_top_step(int n)
 
 // The bin of the cell w under keys [n] (1 <= n <= kHistEdgesMax, ascending), -1 for a cell that is no entry.  A binary search without a branch: at most 10 steps, each
 // one load and one select; keys[pos + s - 1] is read only where pos + s <= n.
+template <class Cell = ScoreCell>
 AFIS_ORDER_FN int hist_bin(const uint32_t* keys, int n, int top_step, uint32_t w)
 {
-    const uint32_t key = rank_key(__builtin_bit_cast(float, w));
+    const uint32_t key = Cell::key(w);
     int pos = 0;
     for (int s = top_step; s >= 1; s >>= 1) {
         const int at = pos + s;

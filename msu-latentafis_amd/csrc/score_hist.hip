@@ -32,6 +32,10 @@
 //                    and the status.
 // Every barrier sits in a loop whose bounds come from block indices and launch arguments or the CSR: the same trips in every thread.  Matrix indices are size_t.
 // A workgroup counts at most 256 x 4 x 4 cells per row and target in 32 bits; the tables are 64-bit.  No float atomics anywhere.
+//
+// Persons (afis_subject_score_histogram, afis_subject_entries_at): k_subject_keys takes the high halves of ctx->subj_best [n_q][S] into a matrix [n_q][S] of 4-byte
+// person cells, and k_score_hist_rows and k_select_count run over it as they run over a score matrix — the same bodies, instantiated with score_cell.h's PersonCell,
+// for which a cell is its own key; a position is a slot.  Only the last kernel differs: k_subject_select_finish names the person and the person's best template.
 #include "afis_device.h"
 #include "score_hist.h"
 #include <type_traits>
@@ -70,11 +74,13 @@ __device__ __forceinline__ void sh_count(uint32_t* bins, int bin, int lane)
     if (live) atomicAdd(bins + bin, 1u);
 }
 
-template <bool kVec>
+// Cell (score_cell.h): what a cell's key is — ScoreCell for a matrix of score words, PersonCell for k_subject_keys' matrix
+template <bool kVec, class Cell>
 __global__ __launch_bounds__(kShThreads) void k_score_hist_rows(const uint32_t* __restrict__ matrix, int rows_n, int cols, const uint32_t* __restrict__ edge_keys, int n_edges,
                                                                 int top_step, u64* __restrict__ tab)
 {
     constexpr int kCols = kVec ? 4 : 1;
+    constexpr uint32_t kNone = Cell::kNone;
     using W = typename std::conditional<kVec, uint4, uint32_t>::type;
     __shared__ uint32_t s_edge[kHistEdgesMax + 1];
     extern __shared__ uint32_t s_hist[];                                    // a strip's histograms [kFilterRows][n_edges + 1], sized by the launcher (32 KB at 1024 bins): the rows of a strip are counted without a barrier between them
@@ -94,8 +100,8 @@ __global__ __launch_bounds__(kShThreads) void k_score_hist_rows(const uint32_t* 
             for (int l = 0; l < kShLoads; ++l) {                            // (kVec: cols % 4 == 0, so col < cols means col + 3 < cols)
                 const size_t col = col0 + (size_t)l * (size_t)(kShThreads * kCols);
                 const bool in = r < rows && col < (size_t)cols;
-                if constexpr (kVec) v[r][l] = in ? *reinterpret_cast<const uint4*>(matrix + row + col) : make_uint4(kNoEntryWord, kNoEntryWord, kNoEntryWord, kNoEntryWord);
-                else v[r][l] = in ? matrix[row + col] : kNoEntryWord;
+                if constexpr (kVec) v[r][l] = in ? *reinterpret_cast<const uint4*>(matrix + row + col) : make_uint4(kNone, kNone, kNone, kNone);
+                else v[r][l] = in ? matrix[row + col] : kNone;
             }
         }
 #pragma unroll
@@ -105,9 +111,9 @@ __global__ __launch_bounds__(kShThreads) void k_score_hist_rows(const uint32_t* 
 #pragma unroll
             for (int l = 0; l < kShLoads; ++l) {                            // every search before the first count: the LDS reads of a thread's cells overlap
                 if constexpr (kVec) {
-                    b[4 * l] = hist_bin(s_edge, n_edges, top_step, v[r][l].x); b[4 * l + 1] = hist_bin(s_edge, n_edges, top_step, v[r][l].y);
-                    b[4 * l + 2] = hist_bin(s_edge, n_edges, top_step, v[r][l].z); b[4 * l + 3] = hist_bin(s_edge, n_edges, top_step, v[r][l].w);
-                } else b[l] = hist_bin(s_edge, n_edges, top_step, v[r][l]);
+                    b[4 * l] = hist_bin<Cell>(s_edge, n_edges, top_step, v[r][l].x); b[4 * l + 1] = hist_bin<Cell>(s_edge, n_edges, top_step, v[r][l].y);
+                    b[4 * l + 2] = hist_bin<Cell>(s_edge, n_edges, top_step, v[r][l].z); b[4 * l + 3] = hist_bin<Cell>(s_edge, n_edges, top_step, v[r][l].w);
+                } else b[l] = hist_bin<Cell>(s_edge, n_edges, top_step, v[r][l]);
             }
 #pragma unroll
             for (int j = 0; j < kShLoads * kCols; ++j) sh_count(s_hist + r * n_bins, b[j], lane);
@@ -123,11 +129,12 @@ __global__ __launch_bounds__(kShThreads) void k_score_hist_rows(const uint32_t* 
 
 // scores [n_q][n] words; rows [n_rows] the rows that have targets, off [n_rows + 1] their targets' ranges in prefix / remain [m] and tab [m][256]; a target's prefix
 // holds the digits above shift + 8 that are fixed (high_mask covers them: 0 in the first pass); kCols 4: n % 4 == 0 and the matrix 16-byte aligned
-template <int kCols>
+template <int kCols, class Cell>
 __global__ __launch_bounds__(kShThreads) void k_select_count(const uint32_t* __restrict__ scores, int n, const int32_t* __restrict__ rows, const int32_t* __restrict__ off, int n_rows,
                                                              const u64* __restrict__ prefix, int shift, u64 high_mask, u64* __restrict__ tab)
 {
     constexpr int kPer = kSelLoads * kCols;
+    constexpr uint32_t kNone = Cell::kNone;
     __shared__ uint32_t s_bins[kSelTargets * kSelectBins];
     __shared__ u64 s_prefix[kSelTargets];
     __shared__ uint32_t s_counts[kSelTargets];
@@ -145,22 +152,22 @@ __global__ __launch_bounds__(kShThreads) void k_select_count(const uint32_t* __r
 #pragma unroll
             for (int j = 0; j < kSelLoads; ++j) {                            // (n % 4 == 0: with e inside the row, e + 3 is too)
                 const size_t e = col0 + (size_t)(j * kShThreads + tid) * 4;
-                v[j] = e < (size_t)n ? *reinterpret_cast<const uint4*>(scores + at + e) : make_uint4(kNoEntryWord, kNoEntryWord, kNoEntryWord, kNoEntryWord);
+                v[j] = e < (size_t)n ? *reinterpret_cast<const uint4*>(scores + at + e) : make_uint4(kNone, kNone, kNone, kNone);
             }
 #pragma unroll
             for (int j = 0; j < kSelLoads; ++j) {
                 const uint32_t e = (uint32_t)(col0 + (size_t)(j * kShThreads + tid) * 4);
                 const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const uint32_t key = rank_key(__builtin_bit_cast(float, w[k])); c[4 * j + k] = key >= kEntryFloor ? rank_composite(key, e + k) : (u64)0; }
+                for (int k = 0; k < 4; ++k) { const uint32_t key = Cell::key(w[k]); c[4 * j + k] = key >= kEntryFloor ? rank_composite(key, e + k) : (u64)0; }
             }
         } else {
             uint32_t v[kSelLoads];
 #pragma unroll
-            for (int j = 0; j < kSelLoads; ++j) { const size_t e = col0 + (size_t)(j * kShThreads + tid); v[j] = e < (size_t)n ? scores[at + e] : kNoEntryWord; }
+            for (int j = 0; j < kSelLoads; ++j) { const size_t e = col0 + (size_t)(j * kShThreads + tid); v[j] = e < (size_t)n ? scores[at + e] : kNone; }
 #pragma unroll
             for (int j = 0; j < kSelLoads; ++j) {
-                const uint32_t key = rank_key(__builtin_bit_cast(float, v[j]));
+                const uint32_t key = Cell::key(v[j]);
                 c[j] = key >= kEntryFloor ? rank_composite(key, (uint32_t)(col0 + (size_t)(j * kShThreads + tid))) : (u64)0;
             }
         }
@@ -225,31 +232,76 @@ __global__ __launch_bounds__(kShThreads) void k_select_finish(const uint32_t* __
     status[i] = found ? kPosListed : kPosNoEntry;
 }
 
-hipError_t launch_score_hist(const float* matrix, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream)
+// The person form of k_select_finish: the fixed digits are (K, ~slot); the slot names the person, its composite in best [n_q][S] holds the score (K is its ordered
+// word) and, in the low half, the position of the best template, named as k_topk_subjects names it
+__global__ __launch_bounds__(kShThreads) void k_subject_select_finish(const u64* __restrict__ best, int S, int G, const int32_t* __restrict__ row, const u64* __restrict__ prefix,
+                                                                      const u64* __restrict__ remain, size_t m, const long long* __restrict__ ids,
+                                                                      const long long* __restrict__ d_global, long long index_base, long long* __restrict__ id,
+                                                                      uint32_t* __restrict__ score, long long* __restrict__ best_idx, int32_t* __restrict__ status)
 {
-    if (rows <= 0 || cols <= 0) return hipSuccess;
-    if (!matrix || !edge_keys || !tab || n_edges < 1 || n_edges > kHistEdgesMax) return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(tab, 0, (size_t)rows * (size_t)(n_edges + 1) * 8, stream);
-    if (e != hipSuccess) return e;
-    const bool vec = rows_take_16_bytes(cols, matrix, matrix);
-    const size_t chunk = vec ? kShChunkVec : kShChunkScalar;
-    const dim3 grid((unsigned)(((size_t)cols + chunk - 1) / chunk), grid_clamp((size_t)((rows + kFilterRows - 1) / kFilterRows)));
-    const uint32_t* const m = (const uint32_t*)matrix;
-    const int top = hist_top_step(n_edges);
-    const size_t lds = (size_t)kFilterRows * (size_t)(n_edges + 1) * 4;
-    if (vec) hipLaunchKernelGGL(k_score_hist_rows<true>, grid, dim3(kShThreads), lds, stream, m, rows, cols, edge_keys, n_edges, top, tab);
-    else hipLaunchKernelGGL(k_score_hist_rows<false>, grid, dim3(kShThreads), lds, stream, m, rows, cols, edge_keys, n_edges, top, tab);
+    const size_t i = (size_t)blockIdx.x * kShThreads + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t slot = composite_position(prefix[i]);
+    const bool in = remain[i] != kSelDead && slot < (uint32_t)S;
+    const u64 b = in ? best[(size_t)row[i] * (size_t)S + slot] : (u64)0;
+    const uint32_t pos = composite_position(b);                             // < G: an entry's composite was made from a position of the row
+    const bool found = in && pos < (uint32_t)G;
+    id[i] = found ? ids[slot] : -1;
+    score[i] = found ? score_bits_of(person_cell(b)) : 0xff800000u;
+    best_idx[i] = found ? (d_global ? d_global[pos] : index_base + (long long)pos) : -1;
+    status[i] = found ? kPosListed : kPosNoEntry;
+}
+
+// best [n] composites of subj_best -> keys [n] person cells (score_cell.h): one coalesced pass, 8 bytes in and 4 bytes out per cell
+__global__ __launch_bounds__(kShThreads) void k_subject_keys(const u64* __restrict__ best, size_t n, uint32_t* __restrict__ keys)
+{
+    const size_t step = (size_t)gridDim.x * kShThreads;
+    for (size_t i = (size_t)blockIdx.x * kShThreads + threadIdx.x; i < n; i += step) keys[i] = person_cell(best[i]);
+}
+
+hipError_t launch_subject_keys(const unsigned long long* best, int n_q, int S, uint32_t* keys, hipStream_t stream)
+{
+    if (n_q <= 0 || S <= 0) return hipSuccess;
+    if (!best || !keys) return hipErrorInvalidValue;
+    const size_t n = (size_t)n_q * (size_t)S, blocks = (n + kShThreads - 1) / kShThreads;
+    hipLaunchKernelGGL(k_subject_keys, dim3((unsigned)(blocks < ((size_t)1 << 20) ? blocks : (size_t)1 << 20)), dim3(kShThreads), 0, stream, best, n, keys);
     return hipGetLastError();
 }
 
-hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* row, const int32_t* first, size_t m,
-                             unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, const long long* d_global, long long index_base,
-                             long long* idx, float* score, int32_t* status, hipStream_t stream)
+template <class Cell>
+static hipError_t score_hist(const uint32_t* m, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream)
 {
-    if (m == 0 || n_rows <= 0) return hipSuccess;
-    if (!scores || n <= 0 || !rows || !off || !row || !first || !prefix || !prefix_spare || !remain || !tab || !idx || !score || !status || max_row_targets <= 0) return hipErrorInvalidValue;
-    const uint32_t* const sc = (const uint32_t*)scores;
-    const bool vec = rows_take_16_bytes(n, scores, scores);
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (!m || !edge_keys || !tab || n_edges < 1 || n_edges > kHistEdgesMax) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(tab, 0, (size_t)rows * (size_t)(n_edges + 1) * 8, stream);
+    if (e != hipSuccess) return e;
+    const bool vec = rows_take_16_bytes(cols, m, m);
+    const size_t chunk = vec ? kShChunkVec : kShChunkScalar;
+    const dim3 grid((unsigned)(((size_t)cols + chunk - 1) / chunk), grid_clamp((size_t)((rows + kFilterRows - 1) / kFilterRows)));
+    const int top = hist_top_step(n_edges);
+    const size_t lds = (size_t)kFilterRows * (size_t)(n_edges + 1) * 4;
+    if (vec) hipLaunchKernelGGL((k_score_hist_rows<true, Cell>), grid, dim3(kShThreads), lds, stream, m, rows, cols, edge_keys, n_edges, top, tab);
+    else hipLaunchKernelGGL((k_score_hist_rows<false, Cell>), grid, dim3(kShThreads), lds, stream, m, rows, cols, edge_keys, n_edges, top, tab);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_hist(const float* matrix, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream)
+{
+    return score_hist<ScoreCell>((const uint32_t*)matrix, rows, cols, edge_keys, n_edges, tab, stream);
+}
+
+hipError_t launch_subject_hist(const uint32_t* keys, int rows, int cols, const uint32_t* edge_keys, int n_edges, unsigned long long* tab, hipStream_t stream)
+{
+    return score_hist<PersonCell>(keys, rows, cols, edge_keys, n_edges, tab, stream);
+}
+
+// the digits of the select, for both forms; *prefix is left pointing at the copy that holds every target's fixed digits
+template <class Cell>
+static hipError_t select_digits(const uint32_t* sc, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* first, size_t m,
+                                unsigned long long** prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, hipStream_t stream)
+{
+    unsigned long long* p = *prefix;
+    const bool vec = rows_take_16_bytes(n, sc, sc);
     const size_t chunk = vec ? kSelChunkVec : kSelChunkScalar;
     const int depth = (max_row_targets + kSelTargets - 1) / kSelTargets;
     const dim3 grid((unsigned)(((size_t)n + chunk - 1) / chunk), grid_clamp((size_t)n_rows), (unsigned)(depth < kSelDepth ? depth : kSelDepth));
@@ -260,12 +312,41 @@ hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, co
         const u64 high_mask = shift == 56 ? (u64)0 : ~(u64)0 << (shift + 8);
         const hipError_t e = hipMemsetAsync(tab, 0, m * kSelectBins * 8, stream);
         if (e != hipSuccess) return e;
-        if (vec) hipLaunchKernelGGL(k_select_count<4>, grid, dim3(kShThreads), 0, stream, sc, n, rows, off, n_rows, prefix, shift, high_mask, tab);
-        else hipLaunchKernelGGL(k_select_count<1>, grid, dim3(kShThreads), 0, stream, sc, n, rows, off, n_rows, prefix, shift, high_mask, tab);
-        hipLaunchKernelGGL(k_select_step, per_target, dim3(kShThreads), 0, stream, tab, m, shift, high_mask, first, prefix, prefix_spare, remain);
-        std::swap(prefix, prefix_spare);                                    // the step wrote the other copy: no thread reads a neighbour's prefix while it changes
+        if (vec) hipLaunchKernelGGL((k_select_count<4, Cell>), grid, dim3(kShThreads), 0, stream, sc, n, rows, off, n_rows, p, shift, high_mask, tab);
+        else hipLaunchKernelGGL((k_select_count<1, Cell>), grid, dim3(kShThreads), 0, stream, sc, n, rows, off, n_rows, p, shift, high_mask, tab);
+        hipLaunchKernelGGL(k_select_step, per_target, dim3(kShThreads), 0, stream, tab, m, shift, high_mask, first, p, prefix_spare, remain);
+        std::swap(p, prefix_spare);                                         // the step wrote the other copy: no thread reads a neighbour's prefix while it changes
     }
-    hipLaunchKernelGGL(k_select_finish, per_target, dim3(kShThreads), 0, stream, sc, n, row, prefix, remain, m, d_global, index_base, idx, (uint32_t*)score, status);
+    *prefix = p;
+    return hipGetLastError();
+}
+
+hipError_t launch_entries_at(const float* scores, int n, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets, const int32_t* row, const int32_t* first, size_t m,
+                             unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain, unsigned long long* tab, const long long* d_global, long long index_base,
+                             long long* idx, float* score, int32_t* status, hipStream_t stream)
+{
+    if (m == 0 || n_rows <= 0) return hipSuccess;
+    if (!scores || n <= 0 || !rows || !off || !row || !first || !prefix || !prefix_spare || !remain || !tab || !idx || !score || !status || max_row_targets <= 0) return hipErrorInvalidValue;
+    const uint32_t* const sc = (const uint32_t*)scores;
+    const hipError_t e = select_digits<ScoreCell>(sc, n, rows, off, n_rows, max_row_targets, first, m, &prefix, prefix_spare, remain, tab, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_select_finish, dim3((unsigned)((m + kShThreads - 1) / kShThreads)), dim3(kShThreads), 0, stream, sc, n, row, prefix, remain, m, d_global, index_base, idx,
+                       (uint32_t*)score, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_subject_entries_at(const uint32_t* keys, const unsigned long long* best, int S, int G, const int32_t* rows, const int32_t* off, int n_rows, int max_row_targets,
+                                     const int32_t* row, const int32_t* first, size_t m, unsigned long long* prefix, unsigned long long* prefix_spare, unsigned long long* remain,
+                                     unsigned long long* tab, const long long* ids, const long long* d_global, long long index_base, long long* id, float* score, long long* best_idx,
+                                     int32_t* status, hipStream_t stream)
+{
+    if (m == 0 || n_rows <= 0) return hipSuccess;
+    if (!keys || !best || S <= 0 || G <= 0 || !rows || !off || !row || !first || !prefix || !prefix_spare || !remain || !tab || !ids || !id || !score || !best_idx || !status ||
+        max_row_targets <= 0) return hipErrorInvalidValue;
+    const hipError_t e = select_digits<PersonCell>(keys, S, rows, off, n_rows, max_row_targets, first, m, &prefix, prefix_spare, remain, tab, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_subject_select_finish, dim3((unsigned)((m + kShThreads - 1) / kShThreads)), dim3(kShThreads), 0, stream, best, S, G, row, prefix, remain, m, ids, d_global,
+                       index_base, id, (uint32_t*)score, best_idx, status);
     return hipGetLastError();
 }
 

@@ -12,8 +12,11 @@
 // columns' statistics itself: no cross-lane traffic, no atomics.
 // k_normalize_scores: scores [n_q][G] -> out [n_q][G], one pass, 4 bytes in and 4 bytes out per cell, fp64 arithmetic.  Grid and row walk as k_filter_rows.  Axis 0:
 // the row's (offset, scale) pair is indexed by the block index and the loop counter only, so it is a scalar load; axis 1: a thread loads its columns' pairs once.
+// Persons (afis_subject_score_stats): the same two kernels over launch_subject_keys' matrix [n_q][S] of person cells, instantiated with score_cell.h's PersonCell —
+// a cell stands for the score word whose ordered word it is; nothing else differs.
 // Every index into the matrices is a size_t: n_q x G may pass 2^31.  A grid's second dimension holds 65 535 blocks; more strips than that are walked in a loop.
 #include "afis_device.h"
+#include "score_cell.h"
 #include "score_stats.h"
 #include <type_traits>
 
@@ -31,14 +34,15 @@ __device__ __forceinline__ void ss_zero(uint64_t* t)
     for (int i = 0; i < kStatWords; ++i) t[i] = 0;
 }
 
-template <bool kVec>
+// Cell (score_cell.h): which score word a cell stands for — ScoreCell: the cell itself; PersonCell: the word whose ordered word the cell is
+template <bool kVec, class Cell>
 __device__ __forceinline__ void ss_cells(uint64_t* t, typename std::conditional<kVec, uint4, uint32_t>::type v)
 {
-    if constexpr (kVec) { stat_limbs_cell(t, v.x); stat_limbs_cell(t, v.y); stat_limbs_cell(t, v.z); stat_limbs_cell(t, v.w); }
-    else stat_limbs_cell(t, v);
+    if constexpr (kVec) { stat_limbs_cell(t, Cell::word(v.x)); stat_limbs_cell(t, Cell::word(v.y)); stat_limbs_cell(t, Cell::word(v.z)); stat_limbs_cell(t, Cell::word(v.w)); }
+    else stat_limbs_cell(t, Cell::word(v));
 }
 
-template <bool kVec>
+template <bool kVec, class Cell>
 __global__ __launch_bounds__(kSsThreads) void k_score_stats_rows(const uint32_t* __restrict__ matrix, int n_q, int G, u64* __restrict__ tab)
 {
     constexpr int kCols = kVec ? 4 : 1;
@@ -55,13 +59,13 @@ __global__ __launch_bounds__(kSsThreads) void k_score_stats_rows(const uint32_t*
 #pragma unroll
             for (int l = 0; l < kSsLoads; ++l) {                            // (kVec: G % 4 == 0, so col < G means col + 3 < G)
                 const size_t col = col0 + (size_t)l * (size_t)(kSsThreads * kCols);
-                if constexpr (kVec) v[l] = col < (size_t)G ? *reinterpret_cast<const uint4*>(matrix + row + col) : make_uint4(kNoEntryWord, kNoEntryWord, kNoEntryWord, kNoEntryWord);
-                else v[l] = col < (size_t)G ? matrix[row + col] : kNoEntryWord;
+                if constexpr (kVec) v[l] = col < (size_t)G ? *reinterpret_cast<const uint4*>(matrix + row + col) : make_uint4(Cell::kNone, Cell::kNone, Cell::kNone, Cell::kNone);
+                else v[l] = col < (size_t)G ? matrix[row + col] : Cell::kNone;
             }
             uint64_t t[kStatWords];
             ss_zero(t);
 #pragma unroll
-            for (int l = 0; l < kSsLoads; ++l) ss_cells<kVec>(t, v[l]);
+            for (int l = 0; l < kSsLoads; ++l) ss_cells<kVec, Cell>(t, v[l]);
 #pragma unroll
             for (int i = 0; i < kStatWords; ++i)
 #pragma unroll
@@ -95,7 +99,7 @@ __global__ __launch_bounds__(256) void k_score_stats_finish(const u64* __restric
     out[i] = stat_from_limbs(t);
 }
 
-template <bool kVec>
+template <bool kVec, class Cell>
 __global__ __launch_bounds__(kSsColThreads) void k_score_stats_cols(const uint32_t* __restrict__ matrix, int n_q, int G, ScoreStat* __restrict__ out)
 {
     constexpr int kCols = kVec ? 4 : 1;
@@ -106,8 +110,8 @@ __global__ __launch_bounds__(kSsColThreads) void k_score_stats_cols(const uint32
 #pragma unroll
     for (int j = 0; j < kCols; ++j) ss_zero(t[j]);
     const auto cells = [&](W v) {
-        if constexpr (kVec) { stat_limbs_cell(t[0], v.x); stat_limbs_cell(t[1], v.y); stat_limbs_cell(t[2], v.z); stat_limbs_cell(t[3], v.w); }
-        else stat_limbs_cell(t[0], v);
+        if constexpr (kVec) { stat_limbs_cell(t[0], Cell::word(v.x)); stat_limbs_cell(t[1], Cell::word(v.y)); stat_limbs_cell(t[2], Cell::word(v.z)); stat_limbs_cell(t[3], Cell::word(v.w)); }
+        else stat_limbs_cell(t[0], Cell::word(v));
     };
     int q = 0;
     for (; q + kSsRows <= n_q; q += kSsRows) {                              // a whole strip: its kSsRows loads are in flight together
@@ -161,27 +165,38 @@ __global__ __launch_bounds__(kSsThreads) void k_normalize_scores(const uint32_t*
 
 static_assert(sizeof(ScoreStat) == 48, "a statistic is 48 bytes");
 
-hipError_t launch_score_stats(int axis, const float* matrix, int n_q, int G, unsigned long long* tab, void* out, hipStream_t stream)
+template <class Cell>
+static hipError_t score_stats(int axis, const uint32_t* m, int n_q, int G, unsigned long long* tab, void* out, hipStream_t stream)
 {
     if (n_q <= 0 || G <= 0) return hipSuccess;
-    if (!matrix || !out || (axis == 0 && !tab) || (axis != 0 && axis != 1)) return hipErrorInvalidValue;
-    const bool vec = rows_take_16_bytes(G, matrix, matrix);
-    const uint32_t* const m = (const uint32_t*)matrix;
+    if (!m || !out || (axis == 0 && !tab) || (axis != 0 && axis != 1)) return hipErrorInvalidValue;
+    const bool vec = rows_take_16_bytes(G, m, m);
     if (axis == 0) {
         const hipError_t e = hipMemsetAsync(tab, 0, (size_t)n_q * kStatWords * 8, stream);
         if (e != hipSuccess) return e;
         const size_t chunk = vec ? kSsChunkVec : kSsChunkScalar;
         const dim3 grid((unsigned)(((size_t)G + chunk - 1) / chunk), grid_clamp((size_t)((n_q + kSsRows - 1) / kSsRows)));
-        if (vec) hipLaunchKernelGGL(k_score_stats_rows<true>, grid, dim3(kSsThreads), 0, stream, m, n_q, G, tab);
-        else hipLaunchKernelGGL(k_score_stats_rows<false>, grid, dim3(kSsThreads), 0, stream, m, n_q, G, tab);
+        if (vec) hipLaunchKernelGGL((k_score_stats_rows<true, Cell>), grid, dim3(kSsThreads), 0, stream, m, n_q, G, tab);
+        else hipLaunchKernelGGL((k_score_stats_rows<false, Cell>), grid, dim3(kSsThreads), 0, stream, m, n_q, G, tab);
         hipLaunchKernelGGL(k_score_stats_finish, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, stream, tab, n_q, (ScoreStat*)out);
         return hipGetLastError();
     }
     const size_t threads = vec ? (size_t)G / 4 : (size_t)G;
     const dim3 grid((unsigned)((threads + kSsColThreads - 1) / kSsColThreads));
-    if (vec) hipLaunchKernelGGL(k_score_stats_cols<true>, grid, dim3(kSsColThreads), 0, stream, m, n_q, G, (ScoreStat*)out);
-    else hipLaunchKernelGGL(k_score_stats_cols<false>, grid, dim3(kSsColThreads), 0, stream, m, n_q, G, (ScoreStat*)out);
+    if (vec) hipLaunchKernelGGL((k_score_stats_cols<true, Cell>), grid, dim3(kSsColThreads), 0, stream, m, n_q, G, (ScoreStat*)out);
+    else hipLaunchKernelGGL((k_score_stats_cols<false, Cell>), grid, dim3(kSsColThreads), 0, stream, m, n_q, G, (ScoreStat*)out);
     return hipGetLastError();
+}
+
+hipError_t launch_score_stats(int axis, const float* matrix, int n_q, int G, unsigned long long* tab, void* out, hipStream_t stream)
+{
+    return score_stats<ScoreCell>(axis, (const uint32_t*)matrix, n_q, G, tab, out, stream);
+}
+
+// keys [n_q][S] person cells as launch_subject_keys left them: axis 0 one statistic per query over the persons, axis 1 one per person over the queries
+hipError_t launch_subject_stats(int axis, const uint32_t* keys, int n_q, int S, unsigned long long* tab, void* out, hipStream_t stream)
+{
+    return score_stats<PersonCell>(axis, keys, n_q, S, tab, out, stream);
 }
 
 hipError_t launch_normalize_scores(int axis, const float* scores, int n_q, int G, const double* pair, float* out, hipStream_t stream)

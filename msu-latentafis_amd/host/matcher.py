@@ -75,7 +75,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_rank_case_hits", "afis_rank_case_subject_hits",
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
-           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at", "afis_link_groups", "afis_link_subject_groups",
+           "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at", "afis_subject_score_stats", "afis_subject_score_histogram", "afis_subject_entries_at", "afis_link_groups", "afis_link_subject_groups",
            "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
@@ -166,6 +166,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         u64p = C.POINTER(C.c_uint64)
         lib.afis_score_histogram.argtypes = [vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, C.c_int, fp, i64p]
         lib.afis_entries_at.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp]
+    if hasattr(lib, "afis_subject_score_stats"):                        # person distributions; absent from older builds compared by tools/lib_ab.py
+        u64p = C.POINTER(C.c_uint64)
+        lib.afis_subject_score_stats.argtypes = [vp, vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, vp]
+        lib.afis_subject_score_histogram.argtypes = [vp, vp, C.c_int, vp, u64p, i64p, i64p, C.c_int, C.c_int, fp, i64p]
+        lib.afis_subject_entries_at.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, C.c_int64, i32p, i64p, i32p, i64p, fp, i64p]
     if hasattr(lib, "afis_link_groups"):                                # link groups; absent from older builds compared by tools/lib_ab.py
         u64p = C.POINTER(C.c_uint64)
         lib.afis_link_groups.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, i64p, C.c_float, C.c_int, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, i64p, i64p]
@@ -554,11 +559,12 @@ class Matcher:
     # ---- subject rank lists: the last search's scores grouped by enrolled person ---------------------------------
     def subjects_create(self, ids: Sequence[int]):
         """One subject id (any int64 >= 0) per template of the resident shard, in shard order; -> handle for rank_subjects.  The handle is refused (AFIS_ESTATE) once
-        the gallery has been edited; subjects_free releases it."""
+        the gallery has been edited; subjects_free releases it.  handle[2]: the distinct ids ascending — the handle's slots, the order of every per-person output;
+        handle[3]: the ids as given, one per template."""
         a = np.ascontiguousarray(np.asarray(ids, np.int64).reshape(-1))
         h = C.c_void_p()
         self._chk(self.lib.afis_subjects_create(self.ctx, _ptr(a, C.c_int64) if len(a) else None, len(a), C.byref(h)))
-        return (h, len(a))
+        return (h, len(a), np.unique(a), a)
 
     def subjects_free(self, handle):
         self.lib.afis_subjects_free(self.ctx, handle[0])
@@ -775,6 +781,63 @@ class Matcher:
                                            _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
                                            _ptr(ix, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None))
         return {"status": st, "idx": ix, "score": sc}
+
+    # ---- person distributions: the three calls above over enrolled persons ---------------------------------------------------------
+    def _subject_filter(self, handle, labels, masks, excl, n_q):
+        n_q = self.last_n_q if n_q is None else n_q
+        mk, off, ent = self._filter_args(n_q, masks, excl)
+        keep = (mk, off, ent)                                               # (the arrays live as long as the tuple the caller holds)
+        return n_q, keep, (handle[0],), (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
+                                         _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None)
+
+    def subject_score_stats(self, handle, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
+        """score_stats over the enrolled persons of a subjects_create handle: a person's cell is the best score among their eligible covered templates (as
+        rank_subject_hits_filtered's), per query (axis 0: [n_q], the cohort of persons) or per person over the queries (axis 1: [subjects], ascending id: handle[2]).
+        excl: per query a sequence of SUBJECT ids.  A person nothing covers gives the empty statistic.  AFIS_ESTATE on a normalised matrix, as score_stats."""
+        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        out = np.zeros(n_q if axis == 0 else len(handle[2]), SCORE_STAT)
+        self._chk(self.lib.afis_subject_score_stats(self.ctx, *h, axis, *flt, n_q, out.ctypes.data_as(C.c_void_p) if len(out) else None))
+        return out
+
+    def subject_score_histogram(self, handle, edges, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
+        """score_histogram over the enrolled persons of a subjects_create handle, per query (axis 0: [n_q][len(edges) + 1]) or per person (axis 1: [subjects][...],
+        ascending id: handle[2]).  A person's key is the RAW ordered word of their best cell, as in rank_subject_hits: -0.0 lies below +0.0, for persons and for edges,
+        so (-0.0, +0.0) are two edges.  counts[q, j + 1:].sum() is rank_subject_hits_filtered(edges[j])'s n_hits.  excl: per query a sequence of SUBJECT ids."""
+        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
+        out = np.zeros((n_q if axis == 0 else len(handle[2]), len(e) + 1), np.int64)
+        self._chk(self.lib.afis_subject_score_histogram(self.ctx, *h, axis, *flt, n_q, len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
+        return out
+
+    def subject_entries_at(self, handle, query, rank, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
+        """entries_at over the enrolled persons of a subjects_create handle: -> status [n], subject [n] — the id of entry rank[i] of the list
+        rank_subject_hits_filtered(-inf, cap, labels, masks, excl) gives query[i], for every rank; -1 where the row has no more than rank[i] persons —, score [n] and
+        best_idx [n], the person's best score and the GLOBAL index of the template that holds it.  The inverse of rank_subject_positions."""
+        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); r = np.ascontiguousarray(np.asarray(rank, np.int64).reshape(-1))
+        if len(q) != len(r):
+            raise ValueError("one query position per rank")
+        n = len(q)
+        st = np.empty(n, np.int32); sid = np.empty(n, np.int64); sc = np.empty(n, np.float32); bi = np.empty(n, np.int64)
+        self._chk(self.lib.afis_subject_entries_at(self.ctx, *h, *flt, n_q, n, _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
+                                                   _ptr(sid, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None, _ptr(bi, C.c_int64) if n else None))
+        return {"status": st, "subject": sid, "score": sc, "best_idx": bi}
+
+    def expand_subject_pairs(self, handle, offset, scale, columns=None):
+        """Per-person (offset, scale) — one pair per distinct id of the subjects_create handle, ascending: handle[2], the order of subject_score_stats(handle, axis=1) —
+        as the per-column arrays normalize_scores(axis=1) takes, in the search's column order.  columns: None — a search of the whole resident shard —, or the GLOBAL
+        template indices of the search's columns in the order of its scores output (a subset's list as given to subset_create).  z = (v - offset) x scale with
+        scale > 0 is increasing, so after normalize_scores(*expand_subject_pairs(...), axis=1) a person's best z is the z of their best score: every subject list then
+        holds person z-scores."""
+        names, per_template = handle[2], handle[3]
+        o = np.asarray(offset, np.float64).reshape(-1); s = np.asarray(scale, np.float64).reshape(-1)
+        if len(o) != len(names) or len(s) != len(names):
+            raise ValueError("one (offset, scale) pair per subject of the handle")
+        local = np.arange(len(per_template)) if columns is None else np.asarray(columns, np.int64).reshape(-1) - self.index_base
+        if len(local) and (local.min() < 0 or local.max() >= len(per_template)):
+            raise ValueError("a column is not a template of the resident shard")
+        slot = np.searchsorted(names, per_template[local])
+        return o[slot], s[slot]
 
     # ---- link groups: the connected components rows and columns make above a decision score ----------------------------------
     def _link(self, fn, min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q):

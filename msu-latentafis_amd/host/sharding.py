@@ -318,6 +318,49 @@ def merge_score_histograms(per_rank) -> np.ndarray:
     return a.sum(axis=0, dtype=np.int64)
 
 
+def _person_aligned(who: str, ids_per_rank):
+    """The ranks' id lists as int64 arrays; ValueError where an id appears in two of them."""
+    ids = [np.asarray(i, np.int64).reshape(-1) for i in ids_per_rank]
+    if not ids:
+        raise ValueError(f"{who}: no rank")
+    every = np.concatenate(ids)
+    u, n = np.unique(every, return_counts=True)
+    if (n > 1).any():
+        raise ValueError(f"{who}: person distributions merge only for galleries sharded by person — a person's best score is a maximum over ALL their prints, and "
+                         f"maxima of two ranks neither add nor concatenate; ids {u[n > 1][:8].tolist()} appear in two ranks' lists")
+    return ids, every
+
+
+def _merge_subject_rows(who: str, per_rank, ids_per_rank, axis: int, add):
+    if axis not in (0, 1):
+        raise ValueError(f"{who}: axis {axis} is neither 0 (queries) nor 1 (subjects)")
+    ids, every = _person_aligned(who, ids_per_rank)
+    parts = list(per_rank)
+    if len(parts) != len(ids):
+        raise ValueError(f"{who}: one id list per rank")
+    if axis == 0:
+        return add(parts)
+    if any(len(p) != len(i) for p, i in zip(parts, ids)):
+        raise ValueError(f"{who}: along axis 1 a rank returns one row per id of its list")
+    order = np.argsort(every, kind="stable")
+    return every[order], np.concatenate([np.asarray(p) for p in parts])[order]
+
+
+def merge_subject_score_stats(per_rank, ids_per_rank, axis: int):
+    """Person statistics of the ranks of a gallery SHARDED BY PERSON.  per_rank: every rank's Matcher.subject_score_stats(handle, axis) for one query list;
+    ids_per_rank: every rank's distinct subject ids (handle[2]).  ValueError where an id appears in two ranks' lists: that person's prints straddle two shards, each rank
+    holds the maximum over its own share, and neither the sum nor either value is the person's cell (merge_case_subject_hits' AFIS_CASE_SUM caveat).  axis 0: the
+    ranks hold disjoint persons of one query's cohort, so the statistics add -> merge_score_stats' [n_q].  axis 1: every person lies on one rank ->
+    (ids ascending, rows): the ranks' rows concatenated in id order."""
+    return _merge_subject_rows("merge_subject_score_stats", per_rank, ids_per_rank, axis, merge_score_stats)
+
+
+def merge_subject_score_histograms(per_rank, ids_per_rank, axis: int):
+    """merge_subject_score_stats for Matcher.subject_score_histogram(handle, edges, axis) with ONE list of edges on every rank: axis 0 adds through
+    merge_score_histograms -> [n_q, bins]; axis 1 -> (ids ascending, [subjects, bins]).  ValueError where an id appears in two ranks' lists."""
+    return _merge_subject_rows("merge_subject_score_histograms", per_rank, ids_per_rank, axis, merge_score_histograms)
+
+
 def histogram_rank_bin(counts, rank):
     """Where a rank falls in a histogram: counts [rows, bins] (or [bins]) int64 — merged, for a global rank — and rank [rows] (or a number) >= 0, counted from the
     best entry as afis_entries_at counts.  -> (bin, residual): the bin that holds the entry at that rank when the bins are walked from the top, and the rank among
