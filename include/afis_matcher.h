@@ -1131,6 +1131,76 @@ int afis_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs,
                                      const int64_t* a_idx, const int64_t* b_idx,
                                      int32_t* counts /*[n_pairs]*/, int16_t* xy /*[n_pairs][120][4]*/, float* part /*[n_pairs] or NULL*/);
 
+/* Texture correspondences (no reference file: matcher.cpp writes none for the texture scorer): the evidence behind the FOURTH part of a fused score, for a list of pairs —
+ * which virtual minutiae of the latent the texture scorer matched to which points of the print (S7's 200 best rows after the filters S8b and S9: corr3 of
+ * matcher.cpp:767-781).  A latent of a few minutiae often gets most of its score here, and without this call the examiner has nothing to overlay on such a hit.
+ * The arguments, AFIS_EINVAL / AFIS_ESTATE / AFIS_EDEVICE, the chunks (option "corr_pairs_per_launch") and the rule that the last search's matrix is neither written
+ * nor invalidated follow afis_correspondences_pairs rule for rule; pairs may come in any order and may repeat; pt, sim and part may be NULL.  For pair i:
+ *   counts[i]                        the survivors of S9, 0 .. AFIS_TEX_CORR_MAX.  AFIS_CORR_NOT_RUN (-1): the reference does not call the texture scorer — a latent-empty
+ *                                    query, an empty or removed print, a latent without a texture template, a print without one (matcher.cpp:411).  AFIS_CORR_NOT_COVERED
+ *                                    (-2): idx outside the shard, the -1 that pads the list calls included, silently (host/sharding.py::merge_texture_correspondences)
+ *   xy[(i*200 + t)*4 + 0..3]         latent x, latent y, rolled x, rolled y of survivor t in the templates' own BLOCK units, exactly as stored (a pixel is 16 b + 24)
+ *   pt[(i*200 + t)*2 + 0..1]         the latent's texture row and the print's texture point, as indices into the templates
+ *   sim[i*200 + t]                   the survivor's similarity: the row maximum the list carries, bit for bit
+ *   part[i]                          the scorer's return value: bit for bit afis_search's parts[q][t][3] where counts >= 0 — the fp32 sum of sim[i*200 + 0 .. counts) in
+ *                                    that order —, +0.0f elsewhere
+ * all in the reference's list order under every value of "ref_tie_order"; rows at or beyond counts are zero.
+ * The print form takes two RESIDENT prints under afis_correspondences_print_pairs' rules (covered: both in the shard; a pair (a, a) is an ordinary pair); a's texture
+ * view is the one afis_search_prints builds, so pt's first component indexes a's texture points; AFIS_CORR_NOT_RUN where a or b holds no texture template.
+ * How: the pair driver's score sequence with the texture list kernel's tap after S9 switched on — 1 600 bytes a pair on the device — and one wave per pair behind it
+ * (csrc/pair_evidence.hip) that gathers the coordinates; 3 208 bytes a pair return through the pinned buffer, one copy per chunk.  Option "texture_correspondences_us"
+ * (read-only): the device time of the last call's launches — the print form's gathers included —, from HIP events around every chunk's, summed; 0 when nothing was queued. */
+#define AFIS_TEX_CORR_MAX 200
+int afis_texture_correspondences_pairs(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
+                                       const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
+                                       int32_t* counts /*[n_pairs]*/, int16_t* xy /*[n_pairs][200][4]*/,
+                                       int16_t* pt /*[n_pairs][200][2] or NULL*/, float* sim /*[n_pairs][200] or NULL*/, float* part /*[n_pairs] or NULL*/);
+int afis_texture_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs,
+                                             const int64_t* a_idx, const int64_t* b_idx,
+                                             int32_t* counts /*[n_pairs]*/, int16_t* xy /*[n_pairs][200][4]*/,
+                                             int16_t* pt /*[n_pairs][200][2] or NULL*/, float* sim /*[n_pairs][200] or NULL*/, float* part /*[n_pairs] or NULL*/);
+
+/* Pair alignments (no reference counterpart): where the latent lies on the print — the rotation and translation every workstation draws — without pulling the
+ * correspondences over the bus.  The device sums, per pair and scorer, the MOMENTS of the surviving correspondences (l, r) in PIXELS — a minutia's coordinates as they are,
+ * a texture point's block coordinate b as 16 b + 24 —
+ *   n  the survivors;  slx, sly, srx, sry  the coordinate sums;  dot = sum (lx rx + ly ry);  cross = sum (lx ry - ly rx);  ll = sum (lx^2 + ly^2);  rr = sum (rx^2 + ry^2)
+ * in exact integer arithmetic (csrc/pair_moments.h, shared by the kernel and the host: with int16 coordinates and at most 560 points in a record the sums stay below
+ * 2^29 and the sums of products below 2^50): the order of the additions cannot matter, every field EQUALS the value computed from the exported correspondences, and
+ * records add.  A scorer that did not run, or left no survivor, is all zeros.
+ *   afis_pair_alignments        arguments and rules as afis_score_pairs; status[i] = AFIS_PAIR_OK or AFIS_PAIR_NOT_COVERED (zeros; host/sharding.py::merge_pair_alignments);
+ *                               out[i*4 + 0..2] the minutiae scorers' records (selected templates 27, 3, 12), out[i*4 + 3] the texture scorer's.  288 bytes a pair
+ *                               return instead of the 2.9 KB + 3.2 KB of the two correspondence calls
+ *   afis_print_pair_alignments  arguments and rules as afis_correspondences_print_pairs; out[i*2 + 0] a's minutiae template against b, out[i*2 + 1] a's texture template
+ *   afis_corr_moments_add       host only: acc += other, field by field — pools scorers (all four into one placement), exactly.  AFIS_EINVAL, acc unchanged: a null
+ *                               pointer, an operand or a sum outside the bound above (n beyond 560 included)
+ *   afis_alignment_fit          host only: the rigid least-squares placement r ~ R l + t, R = [[c, -s], [s, c]], of one record.  P = n dot - (slx srx + sly sry) and
+ *                               Q = n cross - (slx sry - sly srx) exactly (128-bit integers); p, q their correctly rounded doubles; h = sqrt(p p + q q); c = p / h;
+ *                               s = q / h; tx = (srx - (c slx - s sly)) / n; ty = (sry - (s slx + c sly)) / n; with the exact integers U = n ll - slx^2 - sly^2 and
+ *                               V = n rr - srx^2 - sry^2, rms = sqrt(max(0, double(U + V) - 2 h)) / n, the root mean square residual in pixels.  Every operation is one
+ *                               correctly rounded fp64 operation, no fused multiply-add.  AFIS_EINVAL with the outputs untouched: a null record, one outside the bound,
+ *                               n < 2, or P = Q = 0 (no rotation is determined).  Every output may be NULL
+ * The device calls chunk by "corr_pairs_per_launch" and neither write nor invalidate the last search's matrix.  Option "pair_alignments_us" (read-only): the device time
+ * of the last call's launches (the print form's gathers included), summed over the chunks; 0 when nothing was queued.
+ * Cost        one MI355X, 100 latents x their 100 best candidates — the flattened lists of afis_rank_hits(-inf, 100), 10 000 pairs — of a 100 000-print planted gallery,
+ *               the routes interleaved on one context, medians of five after a discarded first, spread = max - min (tools/pair_evidence_timing.py,
+ *               profiles/pair_evidence_timing.json).  afis_pair_alignments: 26.4 ms on the device clock (spread 0.4) and 27.1 ms on the host's (0.5), 2.9 MB returned.
+ *               afis_texture_correspondences_pairs with pt, sim and part: 26.4 ms (0.2) and 29.2 ms (0.3), 32 MB.  The route there was for the same moments —
+ *               afis_correspondences_pairs (6.8 ms on the device, 9.2 ms on the host), plus the texture export, plus the moments of the four lists in numpy (106 ms,
+ *               spread 1.6) —: 33.1 ms (0.1) of device time and 144.4 ms (1.5) on the host, 61 MB.  So the alignment call takes 0.80 x the device time of the two
+ *               exports — both routes run the same four scorers, whose exact texture row maxima and list kernels are nearly all of either; the copy back is not on
+ *               the device clock — and 0.19 x the host time of that route as measured, most of which is the numpy pass: against the two C calls alone (38.2 ms) it
+ *               is 0.71 x.  The records equalled the numpy moments of the exports; 8 594 .. 8 796 of the 10 000 records of a scorer held survivors; afis_rank_hits
+ *               returned afterwards what it had returned before.  Nothing here is tuned. */
+typedef struct { int64_t n, slx, sly, srx, sry, dot, cross, ll, rr; } afis_corr_moments;  /* 72 bytes */
+int afis_pair_alignments(afis_ctx* ctx, afis_queries* q, int64_t n_pairs,
+                         const int32_t* query /*[n_pairs]*/, const int64_t* idx /*[n_pairs], GLOBAL*/,
+                         int32_t* status /*[n_pairs]*/, afis_corr_moments* out /*[n_pairs][4]*/);
+int afis_print_pair_alignments(afis_ctx* ctx, int64_t n_pairs,
+                               const int64_t* a_idx, const int64_t* b_idx,
+                               int32_t* status /*[n_pairs]*/, afis_corr_moments* out /*[n_pairs][2]*/);
+int afis_corr_moments_add(afis_corr_moments* acc, const afis_corr_moments* other);
+int afis_alignment_fit(const afis_corr_moments* m, double* c, double* s, double* tx, double* ty, double* rms);
+
 /* Cascade search (no reference counterpart): a cheap first stage in front of the expensive one.  afis_search scores every (latent, print) cell with all four scorers, and
  * about 60 % of its device time is the texture path, spent on cells of which a handful per latent ever reach an examiner.  afis_search_cascade runs the
  * three MINUTIAE scorers for every cell of the resident shard, keeps per latent the `keep` best prints by that partial score — selected on the device — and runs the
@@ -1418,6 +1488,11 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * memory each plus 8 bytes per row of the handle's longest latent texture template (at most 8 KB), and 36 bytes of pinned host memory.  "score_pairs_us" (read-only): the
  * device time of the last afis_score_pairs' launches (per chunk and launch group k_minu_cands<true>, k_graph_minutiae in its pair form, k_adc_pairs, k_graph_texture in its
  * pair form, k_fuse_pairs), from HIP events around every chunk's, summed; 0 when that call queued nothing.
+ * "texture_correspondences_us" (read-only): the device time of the last afis_texture_correspondences_pairs' or afis_texture_correspondences_print_pairs' launches (per
+ * chunk and launch group the score call's kernels without the fusion, the texture list kernel with its tap, and k_pair_evidence; the print form's gathers), from HIP
+ * events around every chunk's, summed; 0 when that call queued nothing.  "pair_alignments_us" (read-only): the same for the last afis_pair_alignments or
+ * afis_print_pair_alignments.  Both calls chunk by "corr_pairs_per_launch": a pair takes the score call's device memory plus 1.6 KB for the tap and 3.2 KB (the export)
+ * or 288 bytes (the moments) of device and of pinned host memory.
  * "eligible_classes" (read-only): the classes — distinct mask triples — of the last afis_search_eligible; "eligible_expand_us" (read-only): the device time of that
  * call's expand launches (k_expand_rows), from HIP events around each, summed over the classes; both 0 after a call that failed or had no queries.
  * "weighted_batch_pseudo" (settable, >= 0; default 0): the pseudo-queries of one batch of afis_search_weighted at most; 0 = as many as an eighth of the launch-group

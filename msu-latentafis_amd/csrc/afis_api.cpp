@@ -211,6 +211,8 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "rank_latents_us") *value = ctx->rank_latents_us;                    // read-only: device time of the last afis_rank_latent_hits' launches
     else if (n == "corr_pairs_per_launch") *value = ctx->corr_pairs_per_launch;
     else if (n == "correspondences_us") *value = ctx->correspondences_us;              // read-only: device time of the last afis_correspondences_pairs' / afis_correspondences' launches
+    else if (n == "texture_correspondences_us") *value = ctx->texture_correspondences_us;   // read-only: device time of the last afis_texture_correspondences_pairs' / _print_pairs' launches
+    else if (n == "pair_alignments_us") *value = ctx->pair_alignments_us;              // read-only: device time of the last afis_pair_alignments' / afis_print_pair_alignments' launches
     else if (n == "score_pairs_per_launch") *value = ctx->score_pairs_per_launch;
     else if (n == "score_pairs_us") *value = ctx->score_pairs_us;                     // read-only: device time of the last afis_score_pairs' launches
     else if (n == "print_pairs_batch_prints") *value = ctx->print_pairs_batch_prints;

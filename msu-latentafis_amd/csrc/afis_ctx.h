@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_print_pairs.cpp (pair scoring and correspondence export for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_evidence.cpp (the evidence calls of a pair list: the texture scorer's correspondences, the exact moments of every scorer's survivors and the fit they give; what they ask of the pair driver), afis_print_pairs.cpp (pair scoring, correspondence export and the evidence calls for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -22,6 +22,7 @@
 #include <sys/mman.h>
 
 #include "afis_device.h"
+#include "pair_moments.h"
 #include "template_io.h"
 #include <memory>
 #include <functional>
@@ -191,6 +192,7 @@ struct afis_ctx : Shard {
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
     DevBuf pair_buf, pair_tex_slab;      // every pair-list call (PairCall below has the layout), grown on demand: one chunk's candidate lists, survivors, counts, parts and tables — about 5.8 KB per pair of option corr_pairs_per_launch for afis_correspondences_pairs; with afis_score_pairs' dense row maxima and scores kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch —, and the texture list kernel's slab for a chunk's launches of afis_score_pairs
+    int64_t texture_correspondences_us = 0, pair_alignments_us = 0;   // options of those names (read-only): device time of the last afis_texture_correspondences_pairs' / afis_pair_alignments' launches (HIP events around every chunk's, summed), or of their forms' for print pairs, gathers included; both calls chunk by corr_pairs_per_launch
     int score_pairs_per_launch = kScorePairsPerLaunch;   // option score_pairs_per_launch: pairs per chunk of that call at most
     int64_t score_pairs_us = 0;          // option score_pairs_us (read-only): device time of the last afis_score_pairs' launches (HIP events around every chunk's, summed)
     DevBuf elig_scores;                  // afis_search_eligible: the combined matrix [n_q][G] while the classes are searched (every class search overwrites `scores`); swapped with `scores` at the end, so between calls it holds the spare of the two
@@ -442,6 +444,14 @@ int build_print_queries(afis_ctx* ctx, const char* who, const std::vector<int32_
 // and part [n_pairs] hold selected template 0 alone.  The caller has drained the context (drain_abandoned).  Hidden, as rank_subjects below.
 int correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
                           const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, float* part, int out_slots = 3) __attribute__((visibility("hidden")));
+// afis_evidence.cpp
+// afis_texture_correspondences_pairs and afis_pair_alignments behind their argument checks, over the query groups `groups` as correspondences_pairs above; pt, sim and part
+// may be NULL.  records 2 (afis_print_pair_alignments): out [n_pairs][2] holds scorer 0's record and the texture scorer's.  They count their device time in
+// ctx->texture_correspondences_us / ctx->pair_alignments_us.  The caller has drained the context.  Hidden, as rank_subjects below.
+int texture_correspondences_pairs(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
+                                  const int32_t* query, const int64_t* idx, int32_t* counts, int16_t* xy, int16_t* pt, float* sim, float* part) __attribute__((visibility("hidden")));
+int pair_alignments(afis_ctx* ctx, const char* who, const std::vector<QueryGroup>& groups, const std::vector<int32_t>& status, int n_q, int64_t n_pairs,
+                    const int32_t* query, const int64_t* idx, int32_t* pair_status, afis_corr_moments* out, int records = 4) __attribute__((visibility("hidden")));
 // afis_pairs.cpp
 // afis_score_pairs behind its argument checks: the pairs (query[i], idx[i]) of the handle q against the resident shard.  The caller has drained the context.
 // fold != NULL (afis_score_print_pairs): q's queries are prints' views; w_minu / w_tex [n_pairs] are the pairs' weights — zero where the query print does not hold the
@@ -453,7 +463,7 @@ int score_pairs(afis_ctx* ctx, const char* who, afis_queries* q, int64_t n_pairs
 // and stage 2 of every cascade (CascadeCall::run) queue it: launch_adc_pairs -> the dense row maxima rm_val / rm_arg [n][qd.lt_pad], launch_graph_texture_pairs ->
 // parts[4 p + 3] (slab: the list kernel's, sized by the caller for its largest table) and, where score is given, launch_fuse_pairs -> score[p]
 int queue_texture_pairs(afis_ctx* ctx, const GalleryDev& gal, const QueryDev& qd, const int32_t* pair_tab, int n, const int32_t* seg, int n_seg, float* rm_val, int32_t* rm_arg,
-                        float* parts, const DevBuf& slab, float* score_or_null, hipStream_t stream) __attribute__((visibility("hidden")));
+                        float* parts, const DevBuf& slab, float* score_or_null, hipStream_t stream, MinuCand* tap_out = nullptr, int32_t* tap_n = nullptr) __attribute__((visibility("hidden")));   // (tap: launch_graph_texture_pairs', the evidence calls')
 // One pair-list call, whatever it returns: the pairs (query[i], idx[i]) of a handle's launch groups against the resident shard, in chunks of `per_launch` pairs, every
 // chunk one launch sequence with one upload and one copy back.  correspondences_pairs and score_pairs state what differs — the constants below and four callbacks —
 // run() is everything else, in this order:
@@ -473,14 +483,23 @@ int queue_texture_pairs(afis_ctx* ctx, const GalleryDev& gal, const QueryDev& qd
 struct PairGroup {                                  // one launch group's share of a chunk, for stage(): its pair table and, of every per-pair area, the group's first slot
     const QueryDev& qd; const int32_t* tab; int n; const int32_t* seg; int n_seg;
     float* parts; float* rm_val; int32_t* rm_arg; float* score; const float* weights;
+    PairEvidence ev;                                // the evidence form: the group's first slot of the survivors, the texture tap and the call's outputs (all NULL otherwise)
 };
-struct PairBack { const short4* corr; const int32_t* corr_n; const float* parts; const float* score; };   // the pinned copy's areas (slot 0 of each; NULL: not returned)
+struct PairBack {                                   // the pinned copy's areas (slot 0 of each; NULL: not returned)
+    const short4* corr; const int32_t* corr_n; const float* parts; const float* score;
+    const int32_t* ex_n = nullptr; const float* ex_part = nullptr; const short4* ex_xy = nullptr; const short2* ex_pt = nullptr; const float* ex_sim = nullptr;   // evidence kPairTexExport
+    const CorrMoments* mom = nullptr;               // evidence kPairMoments: [4] per slot
+};
+enum { kPairNoEvidence = 0, kPairTexExport = 1, kPairMoments = 2 };
 struct __attribute__((visibility("hidden"))) PairCall {
     afis_ctx* const ctx; const char* const who;
     const std::vector<QueryGroup>& groups; const int n_q; const int64_t n_pairs; const int32_t* const query; const int64_t* const idx;
     const int per_launch; int64_t* const us;        // the options the caller names: pairs per chunk at most, the device time summed over the chunks
     const bool texture;                             // the score form: row maxima, scores and the work list have room, pair_tex_slab is sized, parts | score return
     const PrintPairWeights* const weights;          // a print pair's two weights [n_pairs] each (NULL: no such area)
+    const int evidence = kPairNoEvidence;           // the evidence form (with texture): the texture list kernel's tap [P][200] | [P] has room, and what pair_evidence.hip makes of a
+                                                    // chunk's lists returns INSTEAD of parts | score — kPairTexExport: ex_n [P] | ex_part [P] | ex_xy [P][200] | ex_pt [P][200] |
+                                                    // ex_sim [P][200], 3 208 bytes a pair; kPairMoments: mom [P][4], 288 bytes a pair.  These areas lie behind the weights
     std::function<bool(int64_t)> needs_device;
     std::function<void()> defaults;
     std::function<int(const PairGroup&)> stage;     // (empty: nothing follows the minutiae launches)

@@ -291,9 +291,21 @@ constexpr int kScorePairsMax = 1 << 20;                 // ... and its ceiling
 constexpr size_t kScorePairBytes = 2 * 3 * kTopMinu * 8 + 2 * 3 * 4 + 16 + 4 + 16;   // candidates, survivors (scratch), their two counts, parts, score, the tables' entries: 5 820
 hipError_t launch_adc_pairs(const QueryDev& q, const GalleryDev& g, const float* codewords, const int32_t* pair_tab, const int32_t* seg, int n_seg,
                             float* rm_val, int32_t* rm_arg, hipStream_t stream);
+// tap_out [n_pairs][200] / tap_n [n_pairs] (both or neither; NULL for a score): pair p's list after S9 as (similarity, latent row, print point) in the reference's order
+// and its length, -1 where the scorer does not run — the evidence calls read them (launch_pair_evidence below)
 hipError_t launch_graph_texture_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* table_dist, const float* rm_val, const int32_t* rm_arg,
-                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream);
+                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, MinuCand* tap_out, int32_t* tap_n, hipStream_t stream);
 hipError_t launch_fuse_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* parts, float* scores, hipStream_t stream);
+// The evidence calls (afis_evidence.cpp; pair_evidence.hip): behind a group's list launches, one wave per pair of its table.  In: the minutiae survivors corr [3 n][120] /
+// corr_n [3 n] (read for the moments only), the texture tap [n][200] / tap_n [n] and parts [n][4].  Out, each where given: mom [n][4] (pair_moments.h: scorers 0, 1, 2
+// and the texture scorer), and the texture export ex_n [n] | ex_part [n] | ex_xy [n][200] with, optionally, ex_pt [n][200] and ex_sim [n][200] — every row written, zeros
+// at and beyond the count.  At least one of mom and ex_xy.
+struct CorrMoments;
+struct PairEvidence {
+    const short4* corr; const int32_t* corr_n; MinuCand* tap; int32_t* tap_n; const float* parts;       // (tap / tap_n: the texture list kernel of the same group writes them first)
+    CorrMoments* mom; int32_t* ex_n; float* ex_part; short4* ex_xy; short2* ex_pt; float* ex_sim;
+};
+hipError_t launch_pair_evidence(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const PairEvidence& e, hipStream_t stream);
 // afis_search_cascade (afis_cascade.cpp, cascade.hip): the minutiae scorers for every cell, the texture scorer for the `keep` best prints of every latent.
 // launch_fuse_stage1: S10 of a launch group with the texture score taken as +0.0f (fuse_cell.h) from parts[(q*G+g)*4 + 0..2] -> scores[q*G+g], the matrix the kept lists
 // are selected from (launch_rank_hits at the ordered word of -inf, cap = keep).  launch_cascade_gather: one thread per (query, rank < n_kept) of those lists kept

@@ -16,6 +16,8 @@
 // The last search's matrix is neither written nor invalidated: a pair call uses a buffer of its own, the scratch and the slab of the minutiae stage, which nothing outlives,
 // and the list counters, which every launcher resets.
 // afis_score_print_pairs (afis_print_pairs.cpp) drives score_pairs over temporary handles of prints' views, with the fold of a print pair as the fuse step.
+// The evidence form (afis_evidence.cpp: afis_texture_correspondences_pairs, afis_pair_alignments) is the score form without the fusion: the same areas and slab, the texture
+// list kernel's tap [P][200] | [P] behind the weights and, behind that, what pair_evidence.hip's kernel makes of a launch group's lists — the one run that returns.
 #include "afis_ctx.h"
 #include "pair_tables.h"
 
@@ -28,10 +30,10 @@ static_assert(kScorePairsPerLaunch == AFIS_SCORE_PAIRS_PER_LAUNCH, "option score
 namespace afis {
 
 int queue_texture_pairs(afis_ctx* ctx, const GalleryDev& gal, const QueryDev& qd, const int32_t* pair_tab, int n, const int32_t* seg, int n_seg, float* rm_val, int32_t* rm_arg,
-                        float* parts, const DevBuf& slab, float* score_or_null, hipStream_t stream)
+                        float* parts, const DevBuf& slab, float* score_or_null, hipStream_t stream, MinuCand* tap_out, int32_t* tap_n)
 {
     HIPCHK(ctx, launch_adc_pairs(qd, gal, ctx->codewords.as<float>(), pair_tab, seg, n_seg, rm_val, rm_arg, stream));
-    HIPCHK(ctx, launch_graph_texture_pairs(qd, gal, pair_tab, n, ctx->table.as<float>(), rm_val, rm_arg, parts, slab.p, slab.bytes, ctx->s89_tie_order, stream));
+    HIPCHK(ctx, launch_graph_texture_pairs(qd, gal, pair_tab, n, ctx->table.as<float>(), rm_val, rm_arg, parts, slab.p, slab.bytes, ctx->s89_tie_order, tap_out, tap_n, stream));
     if (score_or_null) HIPCHK(ctx, launch_fuse_pairs(qd, gal, pair_tab, n, parts, score_or_null, stream));
     return AFIS_OK;
 }
@@ -58,8 +60,15 @@ int PairCall::run()
     static_assert(sizeof(MinuCand) == 8 && sizeof(short4) == 8, "5.8 KB per pair");
     const size_t cands_at = 0, cand_n_at = up256(cands_at + P * 3 * kTopMinu * sizeof(MinuCand)), rmv_at = up256(cand_n_at + P * 3 * 4), rma_at = up256(rmv_at + P * Lp * 4),
                  corr_at = up256(rma_at + P * Lp * 4), corr_n_at = up256(corr_at + P * 3 * kTopMinu * sizeof(short4)), parts_at = up256(corr_n_at + P * 3 * 4),
-                 score_at = up256(parts_at + P * 16), tab_at = up256(score_at + (texture ? P * 4 : 0)), w_at = up256(tab_at + tab_ints * 4), buf_bytes = w_at + w_bytes;
-    const size_t back_at = texture ? parts_at : corr_at, back_bytes = (texture ? score_at + P * 4 : parts_at + P * 16) - back_at;      // what returns, through the pinned buffer
+                 score_at = up256(parts_at + P * 16), tab_at = up256(score_at + (texture ? P * 4 : 0)), w_at = up256(tab_at + tab_ints * 4);
+    // the evidence form: the tap, then the call's outputs in one run (afis_ctx.h has the areas)
+    static_assert(sizeof(CorrMoments) == 72 && sizeof(short2) == 4, "288 bytes of moments, 3 208 of texture export per pair");
+    const bool ex = evidence == kPairTexExport, mo = evidence == kPairMoments;
+    const size_t tap_at = up256(w_at + w_bytes), tap_n_at = up256(tap_at + (evidence ? P * kTopTex * sizeof(MinuCand) : 0)), ev_at = up256(tap_n_at + (evidence ? P * 4 : 0)),
+                 ex_part_at = up256(ev_at + (ex ? P * 4 : 0)), ex_xy_at = up256(ex_part_at + (ex ? P * 4 : 0)), ex_pt_at = up256(ex_xy_at + (ex ? P * kTopTex * sizeof(short4) : 0)),
+                 ex_sim_at = up256(ex_pt_at + (ex ? P * kTopTex * sizeof(short2) : 0)), ev_end = ex_sim_at + (ex ? P * kTopTex * 4 : 0) + (mo ? P * 4 * sizeof(CorrMoments) : 0),
+                 buf_bytes = evidence ? ev_end : w_at + w_bytes;
+    const size_t back_at = evidence ? ev_at : texture ? parts_at : corr_at, back_bytes = (evidence ? ev_end : texture ? score_at + P * 4 : parts_at + P * 16) - back_at;      // what returns, through the pinned buffer
     const size_t pin_tab_at = up256(back_bytes), pin_w_at = up256(pin_tab_at + tab_ints * 4), pin_bytes = pin_w_at + w_bytes;           // ... behind it the chunk's tables and weights on their way up
     MinuGrid grid{0, 1};
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -80,8 +89,11 @@ int PairCall::run()
     uint8_t* const pin = (uint8_t*)ctx->h_pin;
     int32_t* const tab = (int32_t*)(pin + pin_tab_at);                     // one chunk's tables: the groups' pair tables, then the work list (rewritten only after the chunk's wait)
     const int32_t* const d_tabs = (const int32_t*)(d + tab_at);
-    const PairBack back{texture ? nullptr : (const short4*)pin, texture ? nullptr : (const int32_t*)(pin + corr_n_at - back_at), (const float*)(pin + parts_at - back_at),
-                        texture ? (const float*)(pin + score_at - back_at) : nullptr};
+    PairBack back{texture ? nullptr : (const short4*)pin, texture ? nullptr : (const int32_t*)(pin + corr_n_at - back_at), evidence ? nullptr : (const float*)(pin + parts_at - back_at),
+                  texture && !evidence ? (const float*)(pin + score_at - back_at) : nullptr};
+    if (ex) { back.ex_n = (const int32_t*)pin; back.ex_part = (const float*)(pin + ex_part_at - back_at); back.ex_xy = (const short4*)(pin + ex_xy_at - back_at);
+              back.ex_pt = (const short2*)(pin + ex_pt_at - back_at); back.ex_sim = (const float*)(pin + ex_sim_at - back_at); }
+    if (mo) back.mom = (const CorrMoments*)pin;
     PairChunkTables t;
     std::vector<int32_t> c_query(P), c_tmpl(P);
     for (size_t c0 = 0; c0 < dev.size(); c0 += P) {
@@ -104,14 +116,18 @@ int PairCall::run()
             const size_t b = t.first[gi]; const int n = (int)(t.first[gi + 1] - b);
             if (n == 0) continue;
             // (the row maxima at the group's own stride qd.lt_pad <= Lp: its n pairs stay inside n * Lp)
-            const PairGroup g{groups[gi].dev, d_tabs + 2 * b + gi, n, texture ? d_tabs + 2 * m + n_grp + 2 * t.seg_first[gi] : nullptr, (int)(t.seg_first[gi + 1] - t.seg_first[gi]),
+            PairGroup g{groups[gi].dev, d_tabs + 2 * b + gi, n, texture ? d_tabs + 2 * m + n_grp + 2 * t.seg_first[gi] : nullptr, (int)(t.seg_first[gi + 1] - t.seg_first[gi]),
                               (float*)(d + parts_at) + b * 4, texture ? (float*)(d + rmv_at) + b * Lp : nullptr, texture ? (int32_t*)(d + rma_at) + b * Lp : nullptr,
-                              texture ? (float*)(d + score_at) + b : nullptr, weights ? (const float*)(d + w_at) + 2 * b : nullptr};
+                              texture ? (float*)(d + score_at) + b : nullptr, weights ? (const float*)(d + w_at) + 2 * b : nullptr, PairEvidence{}};
             MinuCand* cands = (MinuCand*)(d + cands_at) + b * 3 * kTopMinu;
             int32_t* cand_n = (int32_t*)(d + cand_n_at) + b * 3;
+            short4* const corr = (short4*)(d + corr_at) + b * 3 * kTopMinu;
+            int32_t* const corr_n = (int32_t*)(d + corr_n_at) + b * 3;
+            if (evidence) g.ev = PairEvidence{corr, corr_n, (MinuCand*)(d + tap_at) + b * kTopTex, (int32_t*)(d + tap_n_at) + b, g.parts, mo ? (CorrMoments*)(d + ev_at) + b * 4 : nullptr,
+                                              ex ? (int32_t*)(d + ev_at) + b : nullptr, ex ? (float*)(d + ex_part_at) + b : nullptr, ex ? (short4*)(d + ex_xy_at) + b * kTopTex : nullptr,
+                                              ex ? (short2*)(d + ex_pt_at) + b * kTopTex : nullptr, ex ? (float*)(d + ex_sim_at) + b * kTopTex : nullptr};
             HIPCHK(ctx, launch_minu_cands_pairs(g.qd, ctx->gal, ctx->scratch.as<float>(), grid.wg_floats, grid.n_wg, ctx->s3_tie_order, g.tab, n, cands, cand_n, s));
-            HIPCHK(ctx, launch_graph_minutiae_pairs(g.qd, ctx->gal, g.tab, n, cands, cand_n, g.parts, (short4*)(d + corr_at) + b * 3 * kTopMinu, (int32_t*)(d + corr_n_at) + b * 3,
-                                                    ctx->minu_slab.p, ctx->minu_slab.bytes, ctx->s89_tie_order, s));
+            HIPCHK(ctx, launch_graph_minutiae_pairs(g.qd, ctx->gal, g.tab, n, cands, cand_n, g.parts, corr, corr_n, ctx->minu_slab.p, ctx->minu_slab.bytes, ctx->s89_tie_order, s));
             if (stage) AFISCHK(stage(g));
         }
         HIPCHK(ctx, hipEventRecord(ev[1], s));

@@ -48,7 +48,8 @@ struct Call {                                                               // w
     }
 
     // after a failure a launch or a copy may still read the tables: the bounded wait first (the last search's matrix stays), the error the caller sees is the first one
-    int end(int rc)
+    // us_option: where the call's device time goes (NULL: "print_pairs_us", with "print_pairs_query_prints" beside it)
+    int end(int rc, int64_t* us_option = nullptr)
     {
         if (rc != AFIS_OK) {
             const std::string keep = ctx->err;
@@ -56,6 +57,7 @@ struct Call {                                                               // w
             ctx->err = keep;
             return rc;
         }
+        if (us_option) { *us_option = us; return AFIS_OK; }
         ctx->print_pairs_us = us; ctx->print_pairs_query_prints = (int64_t)plan.prints.size();
         return AFIS_OK;
     }
@@ -168,6 +170,93 @@ int afis_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs, const int64
         if (part) memcpy(part, pt.data(), N * 4);
     }
     return c.end(rc);
+}
+
+// The evidence calls for print pairs (afis_evidence.cpp has the latent forms): the batches' temporary handles carry what the call reads — the texture export a's texture
+// template alone, the alignments both templates — and the latent forms' functions run over every batch's pairs.  Their device time, gathers included, goes to the latent
+// forms' options; "print_pairs_us" and "print_pairs_query_prints" keep describing the last score or minutiae correspondence call.
+int afis_texture_correspondences_print_pairs(afis_ctx* ctx, int64_t n_pairs, const int64_t* a_idx, const int64_t* b_idx, int32_t* counts, int16_t* xy, int16_t* pt, float* sim, float* part)
+{
+    const char* const who = "afis_texture_correspondences_print_pairs";
+    if (!ctx) return fail(ctx, AFIS_EINVAL, std::string(who) + ": null context");
+    if (n_pairs < 0 || (n_pairs > 0 && !(a_idx && b_idx && counts && xy))) return fail(ctx, AFIS_EINVAL, std::string(who) + ": n_pairs must be >= 0 and every pair array but pt, sim and part given");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, std::string(who) + ": commit the gallery first");
+    ctx->texture_correspondences_us = 0;
+    if (n_pairs == 0) return AFIS_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    AFISCHK(drain_abandoned(ctx, true));                                   // the last search's matrix stays rankable
+    Call c{ctx, who, n_pairs, a_idx, b_idx};
+    c.G = (int64_t)ctx->res_empty.size(); c.base = ctx->index_base;
+    const size_t N = (size_t)n_pairs, row = (size_t)kTopTex;               // entries per pair
+    std::vector<int32_t> cn(N);
+    std::vector<int16_t> out_xy(N * row * 4, 0), out_pt(N * row * 2, 0);
+    std::vector<float> out_sim(N * row, 0.0f), out_part(N, 0.0f);
+    for (size_t i = 0; i < N; ++i) cn[i] = c.covered((int64_t)i) ? AFIS_CORR_NOT_RUN : AFIS_CORR_NOT_COVERED;
+    const std::vector<uint8_t> want_t(N, 1);                                // texture only: a query print without a texture template is in no batch and keeps its NOT_RUN
+    c.make_plan(nullptr, want_t.data());
+    std::vector<int32_t> query, b_cn;
+    std::vector<int64_t> idx;
+    std::vector<int16_t> b_xy, b_pt;
+    std::vector<float> b_sim, b_part;
+    const int rc = c.batches([&](afis_queries* q, size_t first, size_t m) {
+        query.assign(c.plan.pos.begin() + first, c.plan.pos.begin() + first + m);
+        idx.resize(m); b_cn.assign(m, 0); b_xy.assign(m * row * 4, 0); b_pt.assign(m * row * 2, 0); b_sim.assign(m * row, 0.0f); b_part.assign(m, 0.0f);
+        for (size_t k = 0; k < m; ++k) idx[k] = b_idx[(size_t)c.plan.pair[first + k]];
+        const int r = texture_correspondences_pairs(ctx, who, q->groups, q->status, q->n_q, (int64_t)m, query.data(), idx.data(), b_cn.data(), b_xy.data(), b_pt.data(), b_sim.data(), b_part.data());
+        c.us += ctx->texture_correspondences_us;
+        if (r != AFIS_OK) return r;
+        for (size_t k = 0; k < m; ++k) {
+            const size_t i = (size_t)c.plan.pair[first + k];
+            cn[i] = b_cn[k]; out_part[i] = b_part[k];
+            memcpy(&out_xy[i * row * 4], &b_xy[k * row * 4], row * 4 * sizeof(int16_t)); memcpy(&out_pt[i * row * 2], &b_pt[k * row * 2], row * 2 * sizeof(int16_t));
+            memcpy(&out_sim[i * row], &b_sim[k * row], row * sizeof(float));
+        }
+        return (int)AFIS_OK;
+    });
+    ctx->texture_correspondences_us = 0;
+    if (rc == AFIS_OK) {
+        memcpy(counts, cn.data(), N * 4); memcpy(xy, out_xy.data(), N * row * 4 * sizeof(int16_t));
+        if (pt) memcpy(pt, out_pt.data(), N * row * 2 * sizeof(int16_t));
+        if (sim) memcpy(sim, out_sim.data(), N * row * sizeof(float));
+        if (part) memcpy(part, out_part.data(), N * 4);
+    }
+    return c.end(rc, &ctx->texture_correspondences_us);
+}
+
+int afis_print_pair_alignments(afis_ctx* ctx, int64_t n_pairs, const int64_t* a_idx, const int64_t* b_idx, int32_t* status, afis_corr_moments* out)
+{
+    const char* const who = "afis_print_pair_alignments";
+    if (!ctx) return fail(ctx, AFIS_EINVAL, std::string(who) + ": null context");
+    if (n_pairs < 0 || (n_pairs > 0 && !(a_idx && b_idx && status && out))) return fail(ctx, AFIS_EINVAL, std::string(who) + ": n_pairs must be >= 0 and every pair array given");
+    if (!ctx->committed) return fail(ctx, AFIS_ESTATE, std::string(who) + ": commit the gallery first");
+    ctx->pair_alignments_us = 0;
+    if (n_pairs == 0) return AFIS_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    AFISCHK(drain_abandoned(ctx, true));                                   // the last search's matrix stays rankable
+    Call c{ctx, who, n_pairs, a_idx, b_idx};
+    c.G = (int64_t)ctx->res_empty.size(); c.base = ctx->index_base;
+    const size_t N = (size_t)n_pairs;
+    std::vector<int32_t> st(N);
+    std::vector<afis_corr_moments> mo(N * 2, afis_corr_moments{0, 0, 0, 0, 0, 0, 0, 0, 0});
+    for (size_t i = 0; i < N; ++i) st[i] = c.covered((int64_t)i) ? AFIS_PAIR_OK : AFIS_PAIR_NOT_COVERED;
+    const std::vector<uint8_t> want(N, 1);                                  // both templates of a; a print with neither is in no batch and keeps its zeros
+    c.make_plan(want.data(), want.data());
+    std::vector<int32_t> query, b_st;
+    std::vector<int64_t> idx;
+    std::vector<afis_corr_moments> b_mo;
+    const int rc = c.batches([&](afis_queries* q, size_t first, size_t m) {
+        query.assign(c.plan.pos.begin() + first, c.plan.pos.begin() + first + m);
+        idx.resize(m); b_st.assign(m, 0); b_mo.resize(m * 2);
+        for (size_t k = 0; k < m; ++k) idx[k] = b_idx[(size_t)c.plan.pair[first + k]];
+        const int r = pair_alignments(ctx, who, q->groups, q->status, q->n_q, (int64_t)m, query.data(), idx.data(), b_st.data(), b_mo.data(), 2);
+        c.us += ctx->pair_alignments_us;
+        if (r != AFIS_OK) return r;
+        for (size_t k = 0; k < m; ++k) { const size_t i = (size_t)c.plan.pair[first + k]; mo[2 * i] = b_mo[2 * k]; mo[2 * i + 1] = b_mo[2 * k + 1]; }
+        return (int)AFIS_OK;
+    });
+    ctx->pair_alignments_us = 0;
+    if (rc == AFIS_OK) { memcpy(status, st.data(), N * 4); memcpy(out, mo.data(), N * 2 * sizeof(afis_corr_moments)); }
+    return c.end(rc, &ctx->pair_alignments_us);
 }
 
 }  // extern "C"

@@ -1250,15 +1250,15 @@ hipError_t launch_graph_texture(const QueryDev& q, const GalleryDev& g, const fl
 }
 #else    // AFIS_GRAPH_PAIRS_UNIT
 hipError_t launch_graph_texture_pairs(const QueryDev& q, const GalleryDev& g, const int32_t* pair_tab, int n_pairs, const float* table_dist, const float* rm_val, const int32_t* rm_arg,
-                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, hipStream_t stream)
+                                      float* parts, void* slab, size_t slab_bytes, int s89_tie_order, MinuCand* tap_out, int32_t* tap_n, hipStream_t stream)
 {
     if (n_pairs <= 0) return hipSuccess;
-    if (!g.task_ctr || !pair_tab || !rm_val || !rm_arg || !parts) return hipErrorInvalidValue;
+    if (!g.task_ctr || !pair_tab || !rm_val || !rm_arg || !parts || !tap_out != !tap_n) return hipErrorInvalidValue;
     const int grid = graph_texture_grid(n_pairs);
     if (!slab || slab_bytes < (size_t)grid * kTexSlabWgBytes) return hipErrorInvalidValue;       // every workgroup writes its own kTexSlabWgBytes
     const hipError_t e0 = hipMemsetAsync(g.task_ctr + 0, 0, 4, stream);
     if (e0 != hipSuccess) return e0;
-    const GraphTap tap{nullptr, nullptr, 2};
+    const GraphTap tap{tap_out, tap_n, 2};                                 // (a score passes none; the evidence calls take the list after S9)
     if (s89_tie_order) hipLaunchKernelGGL((k_graph_texture<1, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, (const float*)nullptr, (const int32_t*)nullptr, parts, (unsigned char*)slab, tap, pair_tab);
     else hipLaunchKernelGGL((k_graph_texture<0, const int32_t*>), dim3(grid), dim3(64), 0, stream, q, g, table_dist, rm_val, rm_arg, (const float*)nullptr, (const int32_t*)nullptr, parts, (unsigned char*)slab, tap, pair_tab);
     return hipGetLastError();

@@ -66,6 +66,10 @@ class Timing(C.Structure):
 # afis_score_stat (include/afis_matcher.h), 48 bytes: what Matcher.score_stats returns and host/sharding.py::merge_score_stats / trim_score_stats take
 SCORE_STAT = np.dtype([("n", "<i8"), ("n_outside", "<i8"), ("s1", "<u8"), ("s2_lo", "<u8"), ("s2_hi", "<u8"), ("min", "<f4"), ("max", "<f4")])
 assert SCORE_STAT.itemsize == 48
+# afis_corr_moments (include/afis_matcher.h), 72 bytes: what Matcher.pair_alignments returns and alignment_fit / host/sharding.py::merge_pair_alignments take
+CORR_MOMENTS = np.dtype([(f, "<i8") for f in ("n", "slx", "sly", "srx", "sry", "dot", "cross", "ll", "rr")])
+assert CORR_MOMENTS.itemsize == 72
+TEX_CORR_MAX = 200
 
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_commit_at", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
@@ -76,11 +80,31 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
            "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at", "afis_subject_score_stats", "afis_subject_score_histogram", "afis_subject_entries_at", "afis_link_groups", "afis_link_subject_groups",
-           "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
+           "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs",
+           "afis_texture_correspondences_pairs", "afis_texture_correspondences_print_pairs", "afis_pair_alignments", "afis_print_pair_alignments", "afis_corr_moments_add", "afis_alignment_fit", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
 # include/afis_matcher_taps.h: exported by libafis_hip_test.so only
 TAP_EXPORTS = ["afis_debug_lut", "afis_debug_texture_rowmax", "afis_debug_stage_list", "afis_debug_phase_cycles", "afis_debug_atan2_grid", "afis_debug_graph_arith", "afis_debug_refine_stats", "afis_debug_compact_stats", "afis_debug_rank_subjects", "afis_debug_rank_hits", "afis_debug_rank_latent_hits",
                "afis_debug_transpose_stats", "afis_debug_rank_rows", "afis_debug_expand_rows", "afis_debug_fold_templates", "afis_debug_print_queries", "afis_debug_kept_cells_mapped"]
+
+
+def alignment_fit(lib, moments):
+    """afis_alignment_fit of one CORR_MOMENTS record through `lib` (no context, no device) -> (c, s, tx, ty, rms), or None where the call answers AFIS_EINVAL."""
+    rec = np.ascontiguousarray(np.asarray(moments, CORR_MOMENTS).reshape(-1)[:1])
+    out = [C.c_double(0.0) for _ in range(5)]
+    if lib.afis_alignment_fit(C.c_void_p(rec.ctypes.data), *[C.byref(o) for o in out]) != 0:
+        return None
+    return tuple(o.value for o in out)
+
+
+def add_moments(lib, records):
+    """The sum of CORR_MOMENTS records (afis_corr_moments_add, exact) as one record [1]; ValueError where the sum leaves the bound."""
+    acc = np.zeros(1, CORR_MOMENTS)
+    for r in np.asarray(records, CORR_MOMENTS).reshape(-1):
+        one = np.array([r], CORR_MOMENTS)
+        if lib.afis_corr_moments_add(C.c_void_p(acc.ctypes.data), C.c_void_p(one.ctypes.data)) != 0:
+            raise ValueError("add_moments: a record or the sum is outside the bound of include/afis_matcher.h")
+    return acc
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -183,6 +207,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "afis_score_print_pairs"):                          # print pairs; absent from older builds compared by tools/lib_ab.py
         lib.afis_score_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, fp, fp, i32p, fp, fp]
         lib.afis_correspondences_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, i32p, C.POINTER(C.c_int16), fp]
+    if hasattr(lib, "afis_pair_alignments"):                            # texture correspondences and pair alignments; absent from older builds compared by tools/lib_ab.py
+        i16p = C.POINTER(C.c_int16); dp = C.POINTER(C.c_double)
+        lib.afis_texture_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, i16p, i16p, fp, fp]
+        lib.afis_texture_correspondences_print_pairs.argtypes = [vp, C.c_int64, i64p, i64p, i32p, i16p, i16p, fp, fp]
+        lib.afis_pair_alignments.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, vp]
+        lib.afis_print_pair_alignments.argtypes = [vp, C.c_int64, i64p, i64p, i32p, vp]
+        lib.afis_corr_moments_add.argtypes = [vp, vp]
+        lib.afis_alignment_fit.argtypes = [vp, dp, dp, dp, dp, dp]
     if hasattr(lib, "afis_search_cascade"):                             # cascade search; absent from older builds compared by tools/lib_ab.py
         lib.afis_search_cascade.argtypes = [vp, vp, C.c_int, fp, i32p, i64p, i64p, fp]
     if hasattr(lib, "afis_search_cascade_subset"):                      # cascade over a subset / the eligible prints; absent from older builds compared by tools/lib_ab.py
@@ -1290,6 +1322,63 @@ class Matcher:
                                                             _ptr(counts, C.c_int32), _ptr(xy, C.c_int16), _ptr(part, C.c_float) if want_parts else None))
         corr = [xy[i, :counts[i]].copy() if counts[i] >= 0 else (None if counts[i] == CORR_NOT_RUN else NOT_COVERED) for i in range(n)]
         return {"counts": counts[:n], "xy": xy[:n], "corr": corr, "part": part[:n] if want_parts else None}
+
+    # ---- the evidence of the texture scorer, and where a latent lies on a print ---------------------------------------
+    def _texture_export(self, call, head, n, want_parts):
+        counts = np.zeros(max(n, 1), np.int32); xy = np.zeros((max(n, 1), TEX_CORR_MAX, 4), np.int16); pt = np.zeros((max(n, 1), TEX_CORR_MAX, 2), np.int16)
+        sim = np.zeros((max(n, 1), TEX_CORR_MAX), np.float32); part = np.zeros(max(n, 1), np.float32) if want_parts else None
+        self._chk(call(*head, _ptr(counts, C.c_int32), _ptr(xy, C.c_int16), _ptr(pt, C.c_int16), _ptr(sim, C.c_float), _ptr(part, C.c_float) if want_parts else None))
+        corr = [xy[i, :counts[i]].copy() if counts[i] >= 0 else (None if counts[i] == CORR_NOT_RUN else NOT_COVERED) for i in range(n)]
+        return {"counts": counts[:n], "xy": xy[:n], "pt": pt[:n], "sim": sim[:n], "corr": corr, "part": part[:n] if want_parts else None}
+
+    def texture_correspondences_pairs(self, qhandle, query, idx, want_parts: bool = False):
+        """The surviving correspondences of the TEXTURE scorer for a LIST of (latent, print) pairs (afis_texture_correspondences_pairs); the pairs as
+        correspondences_pairs'.  -> {"counts": [n] int32 (-1: the reference does not call the scorer, -2: not covered), "xy": [n][200][4] int16 = (latent x, latent y,
+        rolled x, rolled y) in BLOCK units, "pt": [n][200][2] int16 = (latent texture row, rolled texture point), "sim": [n][200] float32, all in the reference's list
+        order with zeros beyond counts, "corr": per pair xy[:counts] — None / NOT_COVERED as correspondences_pairs' —, "part": [n] float32 with want_parts (search()'s
+        parts[q][t][3] bit for bit where counts >= 0), else None}.  The last search's matrix stays rankable.  get_option("texture_correspondences_us")."""
+        qa = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); ia = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        if len(qa) != len(ia):
+            raise ValueError("texture_correspondences_pairs: query and idx must have one length")
+        n = len(qa)
+        return self._texture_export(self.lib.afis_texture_correspondences_pairs, (self.ctx, qhandle[0], n, _ptr(qa, C.c_int32) if n else None, _ptr(ia, C.c_int64) if n else None), n, want_parts)
+
+    def texture_correspondences_print_pairs(self, a_idx, b_idx, want_parts: bool = False):
+        """texture_correspondences_pairs for (query print, column print) pairs of the resident shard (afis_texture_correspondences_print_pairs); the pairs as
+        score_print_pairs'; pt's first component indexes a's texture points.  "part" is score_print_pairs' parts[i][1] for a non-zero w_tex."""
+        a = np.ascontiguousarray(np.asarray(a_idx, np.int64).reshape(-1)); b = np.ascontiguousarray(np.asarray(b_idx, np.int64).reshape(-1))
+        if len(a) != len(b):
+            raise ValueError("texture_correspondences_print_pairs: a_idx and b_idx must have one length")
+        n = len(a)
+        return self._texture_export(self.lib.afis_texture_correspondences_print_pairs, (self.ctx, n, _ptr(a, C.c_int64) if n else None, _ptr(b, C.c_int64) if n else None), n, want_parts)
+
+    def pair_alignments(self, qhandle, query, idx):
+        """The exact moments of every scorer's surviving correspondences for a LIST of (latent, print) pairs (afis_pair_alignments); the pairs as score_pairs'.
+        -> {"status": [n] int32 (PAIR_OK / PAIR_NOT_COVERED), "moments": [n][4] CORR_MOMENTS — scorers 0, 1, 2 in pixels, the texture scorer at 16 b + 24; zeros where a
+        scorer did not run or left nothing}.  alignment_fit() places the latent from a record, add_moments() pools records.  get_option("pair_alignments_us")."""
+        qa = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); ia = np.ascontiguousarray(np.asarray(idx, np.int64).reshape(-1))
+        if len(qa) != len(ia):
+            raise ValueError("pair_alignments: query and idx must have one length")
+        n = len(qa)
+        status = np.zeros(max(n, 1), np.int32); mom = np.zeros((max(n, 1), 4), CORR_MOMENTS)
+        self._chk(self.lib.afis_pair_alignments(self.ctx, qhandle[0], n, _ptr(qa, C.c_int32) if n else None, _ptr(ia, C.c_int64) if n else None, _ptr(status, C.c_int32), C.c_void_p(mom.ctypes.data)))
+        return {"status": status[:n], "moments": mom[:n]}
+
+    def print_pair_alignments(self, a_idx, b_idx):
+        """pair_alignments for (query print, column print) pairs of the resident shard (afis_print_pair_alignments): "moments" is [n][2] — a's minutiae template, a's
+        texture template — against b."""
+        a = np.ascontiguousarray(np.asarray(a_idx, np.int64).reshape(-1)); b = np.ascontiguousarray(np.asarray(b_idx, np.int64).reshape(-1))
+        if len(a) != len(b):
+            raise ValueError("print_pair_alignments: a_idx and b_idx must have one length")
+        n = len(a)
+        status = np.zeros(max(n, 1), np.int32); mom = np.zeros((max(n, 1), 2), CORR_MOMENTS)
+        self._chk(self.lib.afis_print_pair_alignments(self.ctx, n, _ptr(a, C.c_int64) if n else None, _ptr(b, C.c_int64) if n else None, _ptr(status, C.c_int32), C.c_void_p(mom.ctypes.data)))
+        return {"status": status[:n], "moments": mom[:n]}
+
+    def alignment_fit(self, moments):
+        """The rigid placement r ~ R l + t, R = [[c, -s], [s, c]], of one CORR_MOMENTS record (afis_alignment_fit, host only) -> (c, s, tx, ty, rms) as floats, or None
+        where the record fixes none (fewer than two points, or all points of one side coincide)."""
+        return alignment_fit(self.lib, moments)
 
     def One2One_matching_all_templates(self, latent: FPTemplate):
         """matcher.cpp:339-374 against every gallery template: (query status, rolled status [G], scores [G][n_minu + n_tex])."""

@@ -604,3 +604,66 @@ class CppExchange:
     def close(self):
         if self.h:
             self.lib.afis_exchange_destroy(self.h); self.h = None
+
+
+CORR_MOMENTS = np.dtype([(f, "<i8") for f in ("n", "slx", "sly", "srx", "sry", "dot", "cross", "ll", "rr")])   # afis_corr_moments (include/afis_matcher.h), 72 bytes
+
+
+def _one_owner(who, covered):
+    """covered [R, P] -> (any_owner [P] bool, owner [P] int64, -1 where no rank covers); two ranks covering one pair raise ValueError."""
+    R, P = covered.shape
+    if (covered.sum(axis=0) > 1).any():
+        raise ValueError(f"{who}: pairs {np.flatnonzero(covered.sum(axis=0) > 1)[:8].tolist()} are covered by two ranks")
+    any_owner = covered.any(axis=0) if R else np.zeros(P, bool)
+    return any_owner, np.where(any_owner, covered.argmax(axis=0) if R else 0, -1).astype(np.int64)
+
+
+def merge_texture_correspondences(per_rank):
+    """One pair list handed to every rank of a sharded gallery: per_rank is what Matcher.texture_correspondences_pairs (or its print form) returned on every rank, a
+    sequence of {"counts": [P], "xy": [P, 200, 4], "pt": [P, 200, 2], "sim": [P, 200], "part": [P] or None}.  At most one rank covers a pair — the rank whose count is
+    not AFIS_CORR_NOT_COVERED — and the pair is taken from it, bytes as they are, as merge_correspondences does.  Returns {"counts", "xy", "pt", "sim", "part" (None
+    unless every rank gave it), "owner": [P]}: counts AFIS_CORR_NOT_COVERED, everything else zero and owner -1 for a pair no rank covers.  Two ranks covering one pair
+    raise ValueError."""
+    per_rank = list(per_rank)
+    R = len(per_rank)
+    cn = np.asarray([np.asarray(r["counts"], np.int32).reshape(-1) for r in per_rank], np.int32).reshape(R, -1)
+    P = cn.shape[1]
+    xy = np.asarray([np.asarray(r["xy"], np.int16).reshape(-1, 200, 4) for r in per_rank], np.int16).reshape(R, -1, 200, 4)
+    pt = np.asarray([np.asarray(r["pt"], np.int16).reshape(-1, 200, 2) for r in per_rank], np.int16).reshape(R, -1, 200, 2)
+    sim = np.asarray([np.asarray(r["sim"], np.float32).reshape(-1, 200) for r in per_rank], np.float32).reshape(R, -1, 200)
+    if xy.shape[:2] != cn.shape or pt.shape[:2] != cn.shape or sim.shape[:2] != cn.shape:
+        raise ValueError("merge_texture_correspondences: counts is [pairs], xy [pairs, 200, 4], pt [pairs, 200, 2] and sim [pairs, 200] on every rank, of one length")
+    with_part = R > 0 and all(r.get("part") is not None for r in per_rank)
+    part = np.asarray([np.asarray(r["part"], np.float32).reshape(-1) for r in per_rank], np.float32).reshape(R, -1) if with_part else None
+    if part is not None and part.shape != cn.shape:
+        raise ValueError("merge_texture_correspondences: part is [pairs] on every rank")
+    any_owner, owner = _one_owner("merge_texture_correspondences", cn != CORR_NOT_COVERED)
+    out = {"counts": np.full(P, CORR_NOT_COVERED, np.int32), "xy": np.zeros((P, 200, 4), np.int16), "pt": np.zeros((P, 200, 2), np.int16), "sim": np.zeros((P, 200), np.float32),
+           "part": np.zeros(P, np.float32) if with_part else None, "owner": owner}
+    have = np.flatnonzero(any_owner)
+    out["counts"][have] = cn[owner[have], have]; out["xy"][have] = xy[owner[have], have]; out["pt"][have] = pt[owner[have], have]; out["sim"][have] = sim[owner[have], have]
+    if with_part:
+        out["part"][have] = part[owner[have], have]
+    return out
+
+
+def merge_pair_alignments(per_rank):
+    """One pair list handed to every rank: per_rank is what Matcher.pair_alignments (or print_pair_alignments) returned on every rank, a sequence of {"status": [P],
+    "moments": [P, K] CORR_MOMENTS} (K = 4, or 2 for print pairs).  The rank whose status is AFIS_PAIR_OK covers the pair and its records are taken, bytes as they are.
+    Returns {"status", "moments", "owner": [P]}: AFIS_PAIR_NOT_COVERED, zero records and owner -1 for a pair no rank covers.  Two ranks covering one pair raise
+    ValueError."""
+    per_rank = list(per_rank)
+    R = len(per_rank)
+    st = np.asarray([np.asarray(r["status"], np.int32).reshape(-1) for r in per_rank], np.int32).reshape(R, -1)
+    P = st.shape[1]
+    moms = [np.asarray(r["moments"], CORR_MOMENTS) for r in per_rank]
+    K = moms[0].shape[-1] if R and moms[0].ndim == 2 else 4
+    if any(m.shape != (P, K) for m in moms):
+        raise ValueError("merge_pair_alignments: moments is [pairs, 4] (or [pairs, 2]) on every rank, one row per status entry")
+    any_owner, owner = _one_owner("merge_pair_alignments", st == PAIR_OK)
+    out_st = np.full(P, PAIR_NOT_COVERED, np.int32); out_m = np.zeros((P, K), CORR_MOMENTS)
+    have = np.flatnonzero(any_owner)
+    if len(have):
+        mo = np.stack(moms)
+        out_st[have] = st[owner[have], have]; out_m[have] = mo[owner[have], have]
+    return {"status": out_st, "moments": out_m, "owner": owner}
