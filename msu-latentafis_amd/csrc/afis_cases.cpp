@@ -5,6 +5,7 @@
 // transposed matrix: rows = the cases, entries = the columns of the search or the slots of the subject handle (the ids in ascending order, so that "ascending
 // position" is "ascending subject id").  Only n_cases x (8 + cap x 12) bytes return; the [n_q][G] matrix stays where it is.
 #include "afis_ctx.h"
+#include "target_tables.h"
 
 using namespace afis;
 
@@ -26,17 +27,12 @@ static int rank_case_hits(afis_ctx* ctx, const char* who, afis_subjects* subj, c
     HitCall hc{ctx, who, n_cases, cap, n_hits, out_a, out_score, nullptr};
     ctx->rank_cases_us = 0; ctx->case_fuse_us = 0; ctx->case_rank_us = 0;
     if (hc.empty(ls.G == 0 || cols == 0)) { std::copy(ids.begin(), ids.end(), case_id); return AFIS_OK; }
-    // the cases as a CSR: a counting sort of the query positions by the row of their case keeps the positions of a case in ascending order
-    std::vector<int32_t> tab((size_t)n_cases + 1 + (size_t)n_q, 0);
-    int32_t* const off = tab.data();
-    int32_t* const member = tab.data() + n_cases + 1;
+    // the cases as a CSR (target_tables.h: every case has a member, so its rows are the cases): the positions of a case stay in ascending order; off [n_cases + 1] | member [n_q]
     std::vector<int32_t> row_of((size_t)n_q);
-    for (int i = 0; i < n_q; ++i) {
-        row_of[(size_t)i] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), case_of[i]) - ids.begin());
-        ++off[row_of[(size_t)i] + 1];
-    }
-    for (int64_t c = 0; c < n_cases; ++c) off[c + 1] += off[c];
-    { std::vector<int32_t> next(off, off + n_cases); for (int i = 0; i < n_q; ++i) member[next[(size_t)row_of[(size_t)i]]++] = i; }
+    for (int i = 0; i < n_q; ++i) row_of[(size_t)i] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), case_of[i]) - ids.begin());
+    const TargetTables tt = build_target_tables(row_of.data(), nullptr, (size_t)n_q, nullptr);
+    std::vector<int32_t> tab(tt.off);
+    tab.insert(tab.end(), tt.order.begin(), tt.order.end());
     FilterPass fp{ctx, f.labels, f.masks, pairs, subj != nullptr};
     const bool eligible = fp.filters();
     HIPCHK(ctx, hipSetDevice(ctx->device));

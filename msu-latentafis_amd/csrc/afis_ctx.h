@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, and the driver and checks every hit-list call goes through), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_evidence.cpp (the evidence calls of a pair list: the texture scorer's correspondences, the exact moments of every scorer's survivors and the fit they give; what they ask of the pair driver), afis_print_pairs.cpp (pair scoring, correspondence export and the evidence calls for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, the driver and checks every hit-list call goes through, and the driver of every other call that reads the last search's matrix in place), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_evidence.cpp (the evidence calls of a pair list: the texture scorer's correspondences, the exact moments of every scorer's survivors and the fit they give; what they ask of the pair driver), afis_print_pairs.cpp (pair scoring, correspondence export and the evidence calls for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -22,6 +22,7 @@
 #include <sys/mman.h>
 
 #include "afis_device.h"
+#include "column_names.h"
 #include "pair_moments.h"
 #include "template_io.h"
 #include <memory>
@@ -112,6 +113,7 @@ struct afis_subset {
     uint64_t gallery_epoch = 0;          // afis_ctx::gallery_epoch at creation: both search calls refuse the handle after an edit
     bool identity = true;                // the caller listed the indices in ascending order: no column permutation on the way out
     std::vector<int64_t> idx;            // [n] the caller's list (global indices, the caller's order): column j of the outputs
+    std::vector<int64_t> held;           // [n] the same indices ascending: the name of every position of the sub-shard (column_names), filled where idx is
     DevBuf d_global, d_pos;              // [n] int64 global index of position t; [n] int32 position of the caller's column j
     size_t device_bytes() const { return sh.device_bytes() + d_global.bytes + d_pos.bytes; }
 };
@@ -576,6 +578,24 @@ struct __attribute__((visibility("hidden"))) FilterPass {
 // queue_subject_best(fp.matrix()), fp.queue_drop_subjects(S)), then k_subject_keys -> ctx->subj_keys
 hipError_t ensure_subject_keys(afis_ctx* ctx, const afis_subjects* subj) __attribute__((visibility("hidden")));
 int queue_subject_keys(afis_ctx* ctx, const afis_subjects* subj, FilterPass& fp) __attribute__((visibility("hidden")));
+// One call that reads the last search's matrix in place, whatever it computes (afis_hits.cpp; the entry points: afis_positions.cpp, afis_normalize.cpp, afis_distribution.cpp,
+// afis_link.cpp): behind their checks — the filtered ranking calls' (check_filtered) — and defaults — no cell or no covered target: no device work — the entry points state their
+// buffers, uploads and kernels and read the pinned copy; the filter runs as it runs for the hit lists (fp: no second definition of eligibility); the matrix stays as it is.
+//   room(own, pin_bytes)   hipSetDevice, fp.ensure(), the person cells' buffers, the call's own DevBufs in the order given (0 bytes: not needed), the pinned buffer:
+//                          every allocation precedes the first write into a caller's array and everything queued — a failed one leaves everything as it was
+//   begin(uploads)         the two events, the call's tables, then the masks and the exclusions, to the device — not timed; the host arrays live until finish() returns —, event 0,
+//                          the pre-passes of `cells`: the kernels then read fp.matrix() — the filtered copy, or the search's matrix itself —, ctx->subj_best or ctx->subj_keys
+//   finish(src, bytes, us) after the call's kernels: event 1, `bytes` of src to the pinned buffer, wait_elapsed; *us = the device time between the events, on success only (more to return: afis_link.cpp)
+enum { kTemplateCells = 0, kPersonBest = 1, kPersonKeys = 2 };              // the cells of the matrix; afis_rank_subject_hits_filtered's maxima; ensure_ / queue_subject_keys above
+struct __attribute__((visibility("hidden"))) MatrixCall {
+    afis_ctx* const ctx; const char* const who; const afis_subjects* const subj; const int cells;   // subj: the handle of a person form (unused with kTemplateCells)
+    FilterPass fp; Events ev{2};                    // fp holds a REFERENCE to the caller's pairs: a named vector that outlives the call, never a temporary
+    int room(std::initializer_list<std::pair<DevBuf*, size_t>> own, size_t pin_bytes);   // (a buffer of the call's own, the bytes it needs)
+    int begin(std::initializer_list<HitCall::H2D> uploads = {});
+    int finish(const void* src, size_t bytes, int64_t* us);
+};
+// The names of what the last search covered — a handle's ids, else index_base + position or a subset's afis_subset::held: what resolves exclusions, targets and row_node
+ColumnNames column_names(const afis_ctx* ctx, const afis_subjects* s) __attribute__((visibility("hidden")));
 // afis_normalize.cpp
 // order[t]: the caller's column of position t of the last search's matrix — a subset listed out of order stands in ascending global index order on the device; empty: the identity
 std::vector<int32_t> column_order(const LastSearch& ls) __attribute__((visibility("hidden")));

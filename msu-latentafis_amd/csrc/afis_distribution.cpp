@@ -1,17 +1,16 @@
 // afis_distribution.cpp — score distributions of the C ABI (include/afis_matcher.h), of templates and of persons: afis_score_histogram counts, per query of the last search (axis 0) or per column
 // (axis 1), the entries of the matrix into the bins a list of edges makes — afis_rank_hits_filtered's n_hits for many thresholds in one pass — and afis_entries_at
 // returns the entry at a given rank of a query's list, for every rank, not only the first AFIS_HITS_MAX: the inverse of afis_rank_positions.  The definitions (an entry,
-// its bin, one digit of the select) are score_hist.h's.  The checks are the filtered ranking calls' (check_filtered at min_score = -inf), the filter runs as it runs
-// there (FilterPass: no second definition of eligibility), and the kernels of score_hist.hip read the matrix, or its filtered copy; axis 1 reads the transposed copy
-// afis_rank_latent_hits_filtered makes (launch_transpose_scores into ctx->scores_t).  Integer counts only: histograms of disjoint shards add up bit for bit.  8 bytes
-// per count, or 16 bytes per target, return through the context's pinned buffer; the [n_q][G] matrix stays where it is, and as it is — normalised or not.
+// its bin, one digit of the select) are score_hist.h's.  Both are matrix calls (MatrixCall, afis_ctx.h) whose kernels are score_hist.hip's; axis 1 reads the transposed copy
+// afis_rank_latent_hits_filtered makes (launch_transpose_scores into ctx->scores_t).  Integer counts only: histograms of disjoint shards add up bit for bit; the matrix may be normalised.
 // A subset listed out of order: the sub-shard stands in ascending global index order, so a row's tie rule (ascending position) is the rule on global indices; axis 1's
 // histograms are put in the caller's column order here (column_order, afis_normalize.cpp).
 // The person forms, afis_subject_score_histogram and afis_subject_entries_at, run through the same two functions with a subject handle, as afis_filter.cpp's hit lists
-// do: the checks and pre-passes are afis_rank_subject_hits_filtered's (queue_subject_keys below), the cells are the person cells [n_q][S] k_subject_keys makes of
-// ctx->subj_best (score_cell.h), a column is a slot — the distinct ids ascending, so no column order is to be restored — and an edge's key is its raw ordered word.
+// do: the cells are the person cells [n_q][S] k_subject_keys makes of ctx->subj_best (queue_subject_keys below; score_cell.h), a column is a slot — the distinct ids
+// ascending, so no column order is to be restored — and an edge's key is its raw ordered word.
 #include "afis_ctx.h"
 #include "score_hist.h"
+#include "target_tables.h"
 
 using namespace afis;
 
@@ -50,32 +49,17 @@ static int score_histogram(afis_ctx* ctx, afis_subjects* subj, int axis, const a
         return AFIS_OK;
     }
     const std::vector<int32_t> order = axis == 1 && !subj ? column_order(ls) : std::vector<int32_t>();
-    FilterPass fp{ctx, labels, masks, pairs, subj != nullptr};
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, fp.ensure());
-    if (subj) HIPCHK(ctx, ensure_subject_keys(ctx, subj));
-    if (axis == 1) HIPCHK(ctx, ctx->scores_t.ensure((size_t)cols * (size_t)n_q * 4));
-    HIPCHK(ctx, ctx->hist_tab.ensure(out_bytes + keys.size() * 4));
-    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
-    Events ev{2};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    MatrixCall mc{ctx, who, subj, subj ? kPersonKeys : kTemplateCells, {ctx, labels, masks, pairs, subj != nullptr}};
+    AFISCHK(mc.room({{&ctx->scores_t, axis == 1 ? (size_t)cols * (size_t)n_q * 4 : 0}, {&ctx->hist_tab, out_bytes + keys.size() * 4}}, out_bytes));
     hipStream_t s = ctx->stream;
     uint32_t* const d_keys = (uint32_t*)(ctx->hist_tab.as<uint8_t>() + out_bytes);
-    for (const HitCall::H2D& u : {HitCall::H2D{d_keys, keys.data(), keys.size() * 4}, fp.masks_up(), fp.pairs_up()})
-        if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
-    if (subj) AFISCHK(queue_subject_keys(ctx, subj, fp));
-    else AFISCHK(fp.queue_cells());                                         // neither masks nor exclusions: nothing, and the search's matrix itself is read
-    const float* cells = subj ? ctx->subj_keys.as<float>() : fp.matrix();  // (4-byte cells either way: the transposition moves words)
+    AFISCHK(mc.begin({{d_keys, keys.data(), keys.size() * 4}}));
+    const float* cells = subj ? ctx->subj_keys.as<float>() : mc.fp.matrix();   // (4-byte cells either way: the transposition moves words)
     if (axis == 1) { HIPCHK(ctx, launch_transpose_scores(cells, ctx->scores_t.as<float>(), n_q, (int)cols, s)); cells = ctx->scores_t.as<float>(); }
     const int h_rows = axis == 0 ? n_q : (int)cols, h_cols = axis == 0 ? (int)cols : n_q;
     if (subj) HIPCHK(ctx, launch_subject_hist((const uint32_t*)cells, h_rows, h_cols, d_keys, n_edges, ctx->hist_tab.as<unsigned long long>(), s));
     else HIPCHK(ctx, launch_score_hist(cells, h_rows, h_cols, d_keys, n_edges, ctx->hist_tab.as<unsigned long long>(), s));
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->hist_tab.p, out_bytes, hipMemcpyDeviceToHost, s));
-    int64_t total_us = 0;
-    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
-    (subj ? ctx->subject_score_histogram_us : ctx->score_histogram_us) = total_us;
+    AFISCHK(mc.finish(ctx->hist_tab.p, out_bytes, subj ? &ctx->subject_score_histogram_us : &ctx->score_histogram_us));
     const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
     if (order.empty()) memcpy(counts, pin, out_bytes);
     else for (size_t t = 0; t < order.size(); ++t) memcpy((uint8_t*)counts + (size_t)order[t] * row_bytes, pin + t * row_bytes, row_bytes);
@@ -101,67 +85,41 @@ static int entries_at(afis_ctx* ctx, afis_subjects* subj, const afis_labels* lab
     if (nt == 0 || G == 0 || cols == 0) return AFIS_OK;
 
     // ---- a CSR by row, a row's targets in ascending rank: targets whose entries share their leading digits become neighbours, and the select counts once for them
-    const size_t m = (size_t)nt;
-    std::vector<int32_t> order(m);                                          // order[t]: the caller's target at place t of the CSR
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [query, rank](int32_t a, int32_t b) { return query[a] != query[b] ? query[a] < query[b] : rank[a] < rank[b]; });
-    std::vector<int32_t> rows, off(1, 0);
-    int max_row_targets = 0;
-    for (size_t t = 0; t < m; ++t) {
-        if (t == 0 || query[order[t]] != query[order[t - 1]]) { rows.push_back(query[order[t]]); off.push_back(off.back()); }
-        max_row_targets = std::max(max_row_targets, ++off.back() - off[off.size() - 2]);
-    }
-    const size_t n_rows = rows.size();
+    const TargetTables tt = build_target_tables(query, nullptr, (size_t)nt, rank);   // tt.order[t]: the caller's target at place t of the CSR
+    const size_t m = (size_t)nt, n_rows = tt.rows.size();
     // the tables as two uploads: state = prefix [m] | its spare [m] | remain [m]; tab = rows [n_rows] | off [n_rows + 1] | row [m] | first [m]
     std::vector<int32_t> tab(2 * n_rows + 1 + 2 * m);
-    std::copy(rows.begin(), rows.end(), tab.begin());
-    std::copy(off.begin(), off.end(), tab.begin() + (ptrdiff_t)n_rows);
-    int32_t* const t_row = tab.data() + 2 * n_rows + 1, * const t_first = t_row + m;
+    int32_t* const t_first = tt.write(tab.data());
     const uint64_t prefix0 = (uint64_t)0xffffffffu & ~(((uint64_t)1 << (8 * select_position_digits(cols))) - 1);   // the position bytes no entry of a row differs in
     std::vector<uint64_t> state(3 * m, prefix0);
     for (size_t r = 0; r < n_rows; ++r)
-        for (int32_t t = off[r]; t < off[r + 1]; ++t) { t_row[t] = rows[r]; t_first[t] = off[r]; state[2 * m + (size_t)t] = (uint64_t)rank[order[(size_t)t]]; }
+        for (int32_t t = tt.off[r]; t < tt.off[r + 1]; ++t) { t_first[t] = tt.off[r]; state[2 * m + (size_t)t] = (uint64_t)rank[tt.order[(size_t)t]]; }
 
-    // ---- the device: room first, then the filter pass exactly as the filtered hit lists run it, then the select
+    // ---- the device: the select
     const size_t state_bytes = 3 * m * 8, bins_at = up256(state_bytes), bins_bytes = m * kSelectBins * 8, csr_at = bins_at + bins_bytes, tab_bytes = csr_at + tab.size() * 4;
     const size_t idx_at = 0, best_at = m * 8, score_at = best_at + (subj ? m * 8 : 0), status_at = score_at + m * 4, out_bytes = status_at + m * 4;
-    FilterPass fp{ctx, labels, masks, pairs, subj != nullptr};
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, fp.ensure());
-    if (subj) HIPCHK(ctx, ensure_subject_keys(ctx, subj));
-    HIPCHK(ctx, ctx->sel_tab.ensure(tab_bytes));
-    HIPCHK(ctx, ctx->sel_out.ensure(out_bytes));
-    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
-    Events ev{2};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    MatrixCall mc{ctx, who, subj, subj ? kPersonKeys : kTemplateCells, {ctx, labels, masks, pairs, subj != nullptr}};
+    AFISCHK(mc.room({{&ctx->sel_tab, tab_bytes}, {&ctx->sel_out, out_bytes}}, out_bytes));
     hipStream_t s = ctx->stream;
     uint8_t* const d_tab = ctx->sel_tab.as<uint8_t>(), * const d_out = ctx->sel_out.as<uint8_t>();
-    const HitCall::H2D ups[] = {{d_tab, state.data(), state_bytes}, {d_tab + csr_at, tab.data(), tab.size() * 4}, fp.masks_up(), fp.pairs_up()};
-    for (const HitCall::H2D& u : ups) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
-    if (subj) AFISCHK(queue_subject_keys(ctx, subj, fp));
-    else AFISCHK(fp.queue_cells());                                         // neither masks nor exclusions: nothing, and the search's matrix itself is read
+    AFISCHK(mc.begin({{d_tab, state.data(), state_bytes}, {d_tab + csr_at, tab.data(), tab.size() * 4}}));
     unsigned long long* const d_prefix = (unsigned long long*)d_tab, * const d_remain = d_prefix + 2 * m;
     const int32_t* const d_rows = (const int32_t*)(d_tab + csr_at), * const d_off = d_rows + n_rows, * const d_row = d_off + n_rows + 1, * const d_first = d_row + m;
     if (subj)
-        HIPCHK(ctx, launch_subject_entries_at(ctx->subj_keys.as<uint32_t>(), ctx->subj_best.as<unsigned long long>(), (int)cols, (int)G, d_rows, d_off, (int)n_rows, max_row_targets, d_row,
+        HIPCHK(ctx, launch_subject_entries_at(ctx->subj_keys.as<uint32_t>(), ctx->subj_best.as<unsigned long long>(), (int)cols, (int)G, d_rows, d_off, (int)n_rows, tt.max_row_targets, d_row,
                                               d_first, m, d_prefix, d_prefix + m, d_remain, (unsigned long long*)(d_tab + bins_at), subj->d_ids.as<long long>(), global_map(ls),
                                               (long long)ctx->index_base, (long long*)(d_out + idx_at), (float*)(d_out + score_at), (long long*)(d_out + best_at),
                                               (int32_t*)(d_out + status_at), s));
     else
-        HIPCHK(ctx, launch_entries_at(fp.matrix(), (int)G, d_rows, d_off, (int)n_rows, max_row_targets, d_row, d_first, m, d_prefix, d_prefix + m, d_remain,
+        HIPCHK(ctx, launch_entries_at(mc.fp.matrix(), (int)G, d_rows, d_off, (int)n_rows, tt.max_row_targets, d_row, d_first, m, d_prefix, d_prefix + m, d_remain,
                                       (unsigned long long*)(d_tab + bins_at), global_map(ls), (long long)ctx->index_base, (long long*)(d_out + idx_at), (float*)(d_out + score_at),
                                       (int32_t*)(d_out + status_at), s));
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    int64_t total_us = 0;
-    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
-    (subj ? ctx->subject_entries_at_us : ctx->entries_at_us) = total_us;
+    AFISCHK(mc.finish(d_out, out_bytes, subj ? &ctx->subject_entries_at_us : &ctx->entries_at_us));
 
     // ---- back into the caller's order
     const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
     for (size_t t = 0; t < m; ++t) {
-        const size_t i = (size_t)order[t];
+        const size_t i = (size_t)tt.order[t];
         memcpy(idx + i, pin + idx_at + t * 8, 8);
         if (subj) memcpy(best_idx + i, pin + best_at + t * 8, 8);
         memcpy(score + i, pin + score_at + t * 4, 4);

@@ -58,7 +58,7 @@ void afis::plan_sub_shard(afis_ctx* ctx, afis_subset* sub, const std::vector<int
         sh.res_mo[t + 1] = (int32_t)nm; sh.res_to[t + 1] = (int32_t)nt;      // (sums of a part of a shard that passed the commit's 2^31 check)
         sh.res_empty[t] = ctx->res_empty[g];
     }
-    sub->idx = global;
+    sub->idx = global; sub->held = global;                                  // (sel ascends: the caller's order is the sub-shard's)
     sh.mf_gal_built = false; sh.codes_q_built = false; sh.codes_cf_built = false;      // the derived streams are this class's to lay out (their buffers stay)
 }
 

@@ -83,21 +83,19 @@ int check_filtered(afis_ctx* ctx, const char* who, const afis_subjects* s, const
     if (total > 0 && !excl) return fail(ctx, AFIS_EINVAL, w + ": excl_off lists entries, the entries are null");
     for (int64_t e = 0; e < total; ++e) if (excl[e] < 0) return fail(ctx, AFIS_EINVAL, w + ": an exclusion is negative");
     // an entry that names nothing the search covered is ignored: another shard's template, one the subset does not list, an id the handle does not hold
-    const LastSearch& ls = ctx->last_search;
-    std::vector<int64_t> held;                                              // a subset's device order: its listed indices ascending
-    if (!s && ls.sub) { held = ls.sub->idx; std::sort(held.begin(), held.end()); }
-    const std::vector<int64_t>& names = s ? s->ids : held;
+    const ColumnNames names = column_names(ctx, s);
     for (int i = 0; i < n_q; ++i)
         for (int64_t e = excl_off[i]; e < excl_off[i + 1]; ++e) {
-            int64_t c;
-            if (!s && !ls.sub) c = excl[e] - ctx->index_base;
-            else {
-                const auto it = std::lower_bound(names.begin(), names.end(), excl[e]);
-                c = (it != names.end() && *it == excl[e]) ? (int64_t)(it - names.begin()) : -1;
-            }
-            if (c >= 0 && c < (s ? s->S : ls.G)) { pairs.push_back((int32_t)i); pairs.push_back((int32_t)c); }
+            const int64_t c = names.find(excl[e]);
+            if (c >= 0) { pairs.push_back((int32_t)i); pairs.push_back((int32_t)c); }
         }
     return AFIS_OK;
+}
+
+ColumnNames column_names(const afis_ctx* ctx, const afis_subjects* s)
+{
+    const LastSearch& ls = ctx->last_search;
+    return s ? ColumnNames{s->ids.data(), s->S, 0} : ls.sub ? ColumnNames{ls.sub->held.data(), (int64_t)ls.sub->held.size(), 0} : ColumnNames{nullptr, ls.G, ctx->index_base};
 }
 
 }  // namespace afis

@@ -1,6 +1,6 @@
 // afis_hits.cpp — hit lists of the C ABI (include/afis_matcher.h): afis_rank_hits lists, per query of the last search, every template whose score reaches a decision
 // score, afis_rank_subject_hits every enrolled person — how many there are, and the `cap` best in rank-list order (rank_hits.hip).  Only n_q x (8 + cap x 12 or 20)
-// bytes return; the [n_q][G] matrix stays where it is.  The host sequence of a hit-list call (HitCall, afis_ctx.h) and the ranking calls' checks live here, for every entry point.
+// bytes return; the [n_q][G] matrix stays where it is.  The host sequences of a hit-list call and of a call that reads the matrix in place (HitCall, MatrixCall: afis_ctx.h) and the ranking calls' checks live here, for every entry point.
 #include "afis_ctx.h"
 
 using namespace afis;
@@ -18,14 +18,47 @@ bool HitCall::empty(bool nothing_scored)
     return true;
 }
 
+// the start of both drivers' device work: the call's events, its tables to the device — not timed —, event 0
+static int start_call(afis_ctx* ctx, Events& ev, std::initializer_list<HitCall::H2D> uploads, std::initializer_list<HitCall::H2D> filter = {})
+{
+    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    for (const auto& list : {uploads, filter}) for (const HitCall::H2D& u : list) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
+    return AFIS_OK;
+}
+
 int HitCall::begin(std::initializer_list<H2D> uploads)
 {
     HIPCHK(ctx, ctx->hits_out.ensure(out_bytes));
     HIPCHK(ctx, ensure_pin(ctx, out_bytes));
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    for (const H2D& u : uploads) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
+    return start_call(ctx, ev, uploads);
+}
+
+int MatrixCall::room(std::initializer_list<std::pair<DevBuf*, size_t>> own, size_t pin_bytes)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, fp.ensure());
+    if (cells == kPersonBest) HIPCHK(ctx, ctx->subj_best.ensure((size_t)fp.n_q * (size_t)subj->S * 8));
+    if (cells == kPersonKeys) HIPCHK(ctx, ensure_subject_keys(ctx, subj));
+    for (const auto& r : own) HIPCHK(ctx, r.first->ensure(r.second));
+    HIPCHK(ctx, ensure_pin(ctx, pin_bytes));
     return AFIS_OK;
+}
+
+int MatrixCall::begin(std::initializer_list<HitCall::H2D> uploads)
+{
+    AFISCHK(start_call(ctx, ev, uploads, {fp.masks_up(), fp.pairs_up()}));
+    if (cells == kPersonKeys) return queue_subject_keys(ctx, subj, fp);
+    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is read
+    if (cells == kPersonBest) { AFISCHK(queue_subject_best(ctx, subj, fp.matrix())); AFISCHK(fp.queue_drop_subjects(subj->S)); }   // rank_hits_filtered's sequence: the maxima of the filtered rows, then the excluded persons
+    return AFIS_OK;
+}
+
+int MatrixCall::finish(const void* src, size_t bytes, int64_t* us)
+{
+    HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return wait_elapsed(ctx, who, ev, us);                                  // (*us is written on success only)
 }
 
 int HitCall::finish(const HitMatrix& m, float min_score, const int32_t* out_row)

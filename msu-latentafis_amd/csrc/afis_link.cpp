@@ -1,11 +1,10 @@
 // afis_link.cpp — link groups of the C ABI (include/afis_matcher.h): afis_link_groups and afis_link_subject_groups return the connected components — of two or more
 // nodes — of the graph the last search's matrix makes of its rows and columns above a decision score: which enrolled prints, or persons, are one finger or person
 // (a print search), which latents hit the same print or person (a latent search).  The definitions (a cell that reaches, the nodes, an edge under either mode, the
-// groups and their order, the union and its bound) are link_groups.h's.  The checks are the filtered ranking calls' (check_filtered), the filter runs as it runs there
-// (FilterPass: no second definition of eligibility) and the kernels of link_groups.hip read the matrix, or its filtered copy.  In the subject form the exclusions name
-// persons: where a filtered subject list drops them from a row's maxima, the scan drops them from the row's cells (sorted (row, slot) keys, looked up only where a cell
-// reaches).  The counts return first, then only the (node, label) pairs of the linked nodes, through the context's pinned buffer: what crosses PCIe is 32 bytes + 8 per
-// linked node, whatever G is; the [n_q][G] matrix stays where it is, and as it is — normalised or not.  link_arrange puts the pairs into the caller's CSR.
+// groups and their order, the union and its bound) are link_groups.h's.  A matrix call (MatrixCall, afis_ctx.h) whose kernels are link_groups.hip's.  In the subject form
+// the exclusions name persons: where a filtered subject list drops them from a row's maxima, the scan drops them from the row's cells (sorted (row, slot) keys, looked
+// up only where a cell reaches).  The counts return first, then — a second copy and a second bounded wait, here — only the (node, label) pairs of the linked nodes: what
+// crosses PCIe is 32 bytes + 8 per linked node, whatever G is; the matrix may be normalised.  link_arrange puts the pairs into the caller's CSR.
 // The call's device words, ctx->link_tab, every area on a 256-byte boundary:
 //   counters (n_edges u64 | n_pairs u32 | err u32 | 16 spare bytes) | parent [n_nodes] | label [n_nodes] | size [n_nodes] | the subject form in mutual mode: first_col
 //   [S] | the tables, ONE upload: row_node [n_q] | mutual mode: first_row [n_nodes] | col_of_row [n_q] (the template form's; the subject form's is made on the device) |
@@ -34,9 +33,7 @@ static int link_groups(afis_ctx* ctx, const char* who, const afis_subjects* subj
     if (n_q == 0 || G == 0) return AFIS_OK;                                 // no cell: no edge, no device work
 
     // ---- the node tables
-    std::vector<int64_t> held;                                              // a subset's device order: its listed indices ascending
-    if (!subj && ls.sub) { held = ls.sub->idx; std::sort(held.begin(), held.end()); }
-    const LinkColumns cols = subj ? LinkColumns{subj->ids.data(), subj->S, 0} : ls.sub ? LinkColumns{held.data(), (int64_t)held.size(), 0} : LinkColumns{nullptr, G, ctx->index_base};
+    const LinkColumns cols = column_names(ctx, subj);
     LinkNodes nodes;
     if (!link_build_nodes(cols, row_node, n_q, nodes)) return fail(ctx, AFIS_EINVAL, std::string(who) + ": more than 2^31 - 1 nodes");
     const bool mutual = mode == kLinkMutual;
@@ -59,24 +56,15 @@ static int link_groups(afis_ctx* ctx, const char* who, const afis_subjects* subj
         if (!keys.empty()) memcpy(tab.data() + keys_at_rel, keys.data(), keys.size() * 8);
     }
 
-    // ---- the device: room first, then the filter pass exactly as the filtered hit lists run it, then the scan and the labels
+    // ---- the device: the counters' memset, the scan and the labels
     const size_t parent_at = up256(kLinkCounterBytes), label_at = parent_at + up256(nn * 4), size_at = label_at + up256(nn * 4), first_at = size_at + up256(nn * 4),
                  tab_at = first_at + up256(n_first * 4), total = tab_at + tab_bytes, pin_bytes = kLinkCounterBytes + nn * 8;
     const std::vector<int32_t> no_cells;                                    // the subject form's exclusions are not cells of the copy
-    FilterPass fp{ctx, labels, masks, subj ? no_cells : pairs, subj != nullptr};
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, fp.ensure());
-    HIPCHK(ctx, ctx->link_tab.ensure(total));
-    HIPCHK(ctx, ctx->link_out.ensure(std::max<size_t>(nn * 8, 16)));
-    HIPCHK(ctx, ensure_pin(ctx, pin_bytes));
-    Events ev{2};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    MatrixCall mc{ctx, who, subj, kTemplateCells, {ctx, labels, masks, subj ? no_cells : pairs, subj != nullptr}};   // (the template cells in either form: FilterPass drops no cell for a person)
+    AFISCHK(mc.room({{&ctx->link_tab, total}, {&ctx->link_out, std::max<size_t>(nn * 8, 16)}}, pin_bytes));
     hipStream_t s = ctx->stream;
     uint8_t* const d = ctx->link_tab.as<uint8_t>();
-    for (const HitCall::H2D& u : {HitCall::H2D{d + tab_at, tab.data(), tab_bytes}, fp.masks_up(), fp.pairs_up()})
-        if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
-    AFISCHK(fp.queue_cells());                                              // neither masks nor exclusions: nothing, and the search's matrix itself is read
+    AFISCHK(mc.begin({{d + tab_at, tab.data(), tab_bytes}}));
     HIPCHK(ctx, hipMemsetAsync(d, 0, kLinkCounterBytes, s));
     const int32_t* const d_tab = (const int32_t*)(d + tab_at);
     int32_t* const d_col_of_row = mutual ? (int32_t*)(d + tab_at) + (size_t)n_q + nn : nullptr;
@@ -86,15 +74,11 @@ static int link_groups(afis_ctx* ctx, const char* who, const afis_subjects* subj
     scan.slot_of = subj ? subj->d_slot_of.as<int32_t>() : nullptr; scan.d_global = subj ? global_map(ls) : nullptr; scan.index_base = (long long)ctx->index_base;
     scan.excl = keys.empty() ? nullptr : (const u64*)(d + tab_at + keys_at_rel); scan.n_excl = keys.size();
     scan.parent = (int32_t*)(d + parent_at); scan.n_edges = (u64*)d; scan.err = (uint32_t*)(d + 12);
-    HIPCHK(ctx, launch_link_groups(fp.matrix(), n_q, (int)G, scan, (int32_t*)(d + label_at), (int32_t*)(d + size_at), n_first ? (int32_t*)(d + first_at) : nullptr, (int32_t)n_first,
+    HIPCHK(ctx, launch_link_groups(mc.fp.matrix(), n_q, (int)G, scan, (int32_t*)(d + label_at), (int32_t*)(d + size_at), n_first ? (int32_t*)(d + first_at) : nullptr, (int32_t)n_first,
                                    n_first ? d_col_of_row : nullptr, (uint32_t*)(d + 8), ctx->link_out.as<int32_t>(), s));
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    uint8_t* const pin = (uint8_t*)ctx->h_pin;
-    HIPCHK(ctx, hipMemcpyAsync(pin, d, kLinkCounterBytes, hipMemcpyDeviceToHost, s));   // the counts first
-    int64_t total_us = 0;
-    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
-    ctx->link_groups_us = total_us; ctx->link_d2h_bytes = (int64_t)kLinkCounterBytes;
-    uint64_t edges; uint32_t n_pairs, err;
+    AFISCHK(mc.finish(d, kLinkCounterBytes, &ctx->link_groups_us));         // the counts first
+    ctx->link_d2h_bytes = (int64_t)kLinkCounterBytes;
+    uint8_t* const pin = (uint8_t*)ctx->h_pin; uint64_t edges; uint32_t n_pairs, err;
     memcpy(&edges, pin, 8); memcpy(&n_pairs, pin + 8, 4); memcpy(&err, pin + 12, 4);
     if (err || (size_t)n_pairs > nn) return fail(ctx, AFIS_EDEVICE, std::string(who) + ": the union did not settle (a step bound of link_groups.h was reached); the matrix is as it was");
     if (n_pairs) {                                                          // ... then only the linked nodes

@@ -1,10 +1,9 @@
 // afis_normalize.cpp — cohort statistics and z-normalised scores of the C ABI (include/afis_matcher.h); afis_subject_score_stats is afis_score_stats over persons
 // (score_cell.h: a person's cell is the best of their eligible covered templates).  afis_score_stats reads the last search's matrix along its rows
 // (axis 0: one statistic per query, "T-norm") or its columns (axis 1: one per print, "Z-norm") and returns exact integer statistics (score_stats.h) of the cells the
-// call's filter leaves: the checks are the filtered ranking calls' (check_filtered at min_score = -inf) and the filter runs as it runs there (FilterPass: no second
-// definition of eligibility).  afis_normalize_scores puts every cell of the UNFILTERED matrix on the scale of its row's or column's (offset, scale) pair; the result is
-// built in ctx->elig_scores and swapped with ctx->scores, the way afis_search_eligible ends, so that every ranking call then reads z-scores.  The three host helpers add
-// statistics of disjoint cell sets, take one cell out, and give mean and deviation: plain integer arithmetic, no context.
+// call's filter leaves: a matrix call (MatrixCall, afis_ctx.h).  afis_normalize_scores puts every cell of the UNFILTERED matrix on the scale of its row's or column's
+// (offset, scale) pair; the result is built in ctx->elig_scores and swapped with ctx->scores, the way afis_search_eligible ends, so that every ranking call then reads
+// z-scores — no filter pass, no pinned copy, two matrices swapped: not that driver's.  The three host helpers (add, remove, moments) are plain integer arithmetic, no context.
 // A subset listed out of order: the sub-shard stands in ascending global index order; statistics per column, pairs per column and scores_out are put in the caller's
 // column order here — the rank of idx[j] among the listed indices is its position in the sub-shard (afis_subset_create), as afis_rank_latent_hits orders its rows.
 #include "afis_ctx.h"
@@ -47,30 +46,12 @@ static int score_stats(afis_ctx* ctx, afis_subjects* subj, int axis, const afis_
     }
     const std::vector<int32_t> order = axis == 1 && !subj ? column_order(ls) : std::vector<int32_t>();
     const size_t out_bytes = (size_t)n_out * sizeof(ScoreStat);
-    FilterPass fp{ctx, labels, masks, pairs, subj != nullptr};
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, fp.ensure());
-    if (subj) HIPCHK(ctx, ensure_subject_keys(ctx, subj));
-    if (axis == 0) HIPCHK(ctx, ctx->stat_tab.ensure((size_t)n_q * kStatWords * 8));
-    HIPCHK(ctx, ctx->stat_out.ensure(out_bytes));
-    HIPCHK(ctx, ensure_pin(ctx, out_bytes));
-    Events ev{2};
-    for (hipEvent_t& e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    hipStream_t s = ctx->stream;
-    for (const HitCall::H2D& u : {fp.masks_up(), fp.pairs_up()}) if (u.bytes) HIPCHK(ctx, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipEventRecord(ev[0], s));
-    if (subj) {
-        AFISCHK(queue_subject_keys(ctx, subj, fp));
-        HIPCHK(ctx, launch_subject_stats(axis, ctx->subj_keys.as<uint32_t>(), n_q, (int)cols, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, s));
-    } else {
-        AFISCHK(fp.queue_cells());                                          // neither masks nor exclusions: nothing, and the search's matrix itself is read
-        HIPCHK(ctx, launch_score_stats(axis, fp.matrix(), n_q, (int)G, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, s));
-    }
-    HIPCHK(ctx, hipEventRecord(ev[1], s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->stat_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-    int64_t total_us = 0;
-    AFISCHK(wait_elapsed(ctx, who, ev, &total_us));
-    (subj ? ctx->subject_score_stats_us : ctx->score_stats_us) = total_us;
+    MatrixCall mc{ctx, who, subj, subj ? kPersonKeys : kTemplateCells, {ctx, labels, masks, pairs, subj != nullptr}};
+    AFISCHK(mc.room({{&ctx->stat_tab, axis == 0 ? (size_t)n_q * kStatWords * 8 : 0}, {&ctx->stat_out, out_bytes}}, out_bytes));
+    AFISCHK(mc.begin());
+    if (subj) HIPCHK(ctx, launch_subject_stats(axis, ctx->subj_keys.as<uint32_t>(), n_q, (int)cols, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, ctx->stream));
+    else HIPCHK(ctx, launch_score_stats(axis, mc.fp.matrix(), n_q, (int)G, ctx->stat_tab.as<unsigned long long>(), ctx->stat_out.p, ctx->stream));
+    AFISCHK(mc.finish(ctx->stat_out.p, out_bytes, subj ? &ctx->subject_score_stats_us : &ctx->score_stats_us));
     const uint8_t* const pin = (const uint8_t*)ctx->h_pin;
     if (order.empty()) memcpy(out, pin, out_bytes);
     else for (size_t t = 0; t < order.size(); ++t) memcpy(out + order[t], pin + t * sizeof(ScoreStat), sizeof(ScoreStat));

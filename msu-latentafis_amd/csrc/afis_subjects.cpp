@@ -57,8 +57,7 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
     // bijection of the word) and the position; a subset's positions are its listed indices in ascending order.
     std::vector<unsigned long long> best((size_t)n_q * (size_t)S);
     HIPCHK(ctx, hipMemcpy(best.data(), ctx->subj_best.p, best.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<int64_t> global;
-    if (ls.sub) { global = ls.sub->idx; std::sort(global.begin(), global.end()); }
+    const ColumnNames columns = column_names(ctx, nullptr);
     std::vector<unsigned long long> keys;
     for (int i = 0; i < n_q; ++i) {
         const unsigned long long* row = best.data() + (size_t)i * (size_t)S;
@@ -72,7 +71,7 @@ int rank_subjects(afis_ctx* ctx, afis_subjects* subj, int n_q, int k, int64_t* s
             const uint32_t slot = composite_position(keys[(size_t)r]), pos = composite_position(row[slot]), bits = score_bits_of(composite_word(keys[(size_t)r]));
             subject_id[o] = subj->ids[slot];
             memcpy(subject_score + o, &bits, 4);
-            best_idx[o] = ls.sub ? global[pos] : ctx->index_base + (int64_t)pos;
+            best_idx[o] = columns.name(pos);
         }
     }
     return AFIS_OK;

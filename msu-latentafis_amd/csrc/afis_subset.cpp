@@ -117,6 +117,7 @@ int afis_subset_create(afis_ctx* ctx, const int64_t* idx, int64_t n, afis_subset
         sh.res_mo[(size_t)t + 1] = (int32_t)nm; sh.res_to[(size_t)t + 1] = (int32_t)nt;      // (sums of a part of a shard that passed the commit's 2^31 check)
         sh.res_empty[(size_t)t] = ctx->res_empty[g];
     }
+    sub->held = global;
     { const int rcq = quiesce(ctx, "afis_subset_create"); if (rcq != AFIS_OK) return rcq; }
     if (n > 0) {
         const int64_t h2d_before = ctx->gallery_h2d_bytes;

@@ -35,6 +35,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "column_names.h"
 #include "score_order.h"
 
 namespace afis {
@@ -96,17 +97,7 @@ struct LinkSeq {
     bool hook(int32_t hi, int32_t lo) { if (parent[hi] != hi) return false; parent[hi] = lo; return true; }
 };
 
-// The names of the column nodes, ascending and distinct: names [n] (a subset's listed indices sorted; a subject handle's ids) or, names == NULL, base + 0 .. n - 1.
-struct LinkColumns {
-    const int64_t* names; int64_t n; int64_t base;
-    int64_t name(int64_t v) const { return names ? names[v] : base + v; }
-    int64_t find(int64_t name_) const                                       // the column node of that name, -1: none
-    {
-        if (!names) return name_ >= base && name_ - base < n ? name_ - base : -1;
-        const int64_t* const it = std::lower_bound(names, names + n, name_);
-        return it != names + n && *it == name_ ? (int64_t)(it - names) : -1;
-    }
-};
+using LinkColumns = ColumnNames;                                            // the names of the column nodes, ascending and distinct (column_names.h)
 
 struct LinkNodes {
     int32_t n_col = 0, n_nodes = 0;

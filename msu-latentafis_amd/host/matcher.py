@@ -678,35 +678,34 @@ class Matcher:
             ent = np.ascontiguousarray(np.concatenate(rows)) if rows and off[-1] else np.zeros(1, np.int64)
         return mk, off, ent
 
+    def _filter(self, labels, masks, excl, n_q: Optional[int] = None):
+        """The filter of a call on the LAST search's matrix -> (n_q — None: that search's —, _filter_args' arrays, which live as long as the caller holds them, and
+        the four filter arguments of the C calls: a labels_create handle's pointer, masks, excl_off, excl)."""
+        n_q = self.last_n_q if n_q is None else n_q
+        keep = mk, off, ent = self._filter_args(n_q, masks, excl)
+        return n_q, keep, (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
+                           _ptr(ent, C.c_int64) if ent is not None else None)
+
     def rank_hits_filtered(self, min_score: float, cap: int, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
         """rank_hits over the cells each query is eligible for.  labels: a labels_create handle (needed with masks); masks: [n_q][3] uint64, per query (any_of, all_of,
         none_of) tested against the label L of a column's template: (any_of == 0 or L & any_of) and L & all_of == all_of and not L & none_of; excl: per query a
         sequence of GLOBAL template indices that are no entries for it (what the search did not cover is ignored).  None: no label test / no exclusions."""
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
-        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_hits_filtered(
-            self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
-            _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc), n_q, cap, False)
+        n_q, keep, f = self._filter(labels, masks, excl, n_q)
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_hits_filtered(self.ctx, *f, nq, min_score, cap, nh, a, sc), n_q, cap, False)
 
     def rank_subject_hits_filtered(self, handle, min_score: float, cap: int, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
         """rank_subject_hits over the eligible cells: a person's score is the best among their eligible covered templates; excl: per query a sequence of SUBJECT ids
         that are no entries for it.  A person without an eligible covered template is neither counted nor listed."""
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
-        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits_filtered(
-            self.ctx, handle[0], labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
-            _ptr(ent, C.c_int64) if ent is not None else None, nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
+        n_q, keep, f = self._filter(labels, masks, excl, n_q)
+        return self._hit_lists(lambda nq, nh, a, sc, b: self.lib.afis_rank_subject_hits_filtered(self.ctx, handle[0], *f, nq, min_score, cap, nh, a, sc, b), n_q, cap, True)
 
     # ---- rank positions: where a named template or person stands in a query's list ----------------------------------
     def _positions(self, fn, query, names, labels, masks, excl, n_q, subjects: bool, in_score=None):
-        n_q = self.last_n_q if n_q is None else n_q
         q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); a = np.ascontiguousarray(np.asarray(names, np.int64).reshape(-1))
         if len(q) != len(a):
             raise ValueError("one query position per target")
         n = len(q)
-        mk, off, ent = self._filter_args(n_q, masks, excl)
-        flt = (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
-               _ptr(ent, C.c_int64) if ent is not None else None)
+        n_q, keep, flt = self._filter(labels, masks, excl, n_q)
         nb = np.empty(n, np.int64)
         pq, pa, pn = (_ptr(q, C.c_int32), _ptr(a, C.c_int64), _ptr(nb, C.c_int64)) if n else (None, None, None)
         if in_score is not None:
@@ -747,12 +746,9 @@ class Matcher:
         output), over the cells the filter leaves — labels / masks / excl are rank_hits_filtered's: elimination prints and a known mate go into excl.  -> a structured
         array of dtype SCORE_STAT: n valued cells, n_outside, s1 = sum q, s2 = s2_hi x 2^64 + s2_lo = sum q^2 with q = rint(score x 2^20), min, max.  Statistics of
         disjoint shards add up bit for bit (host/sharding.py::merge_score_stats); score_moments gives mean and deviation.  The matrix stays as it is."""
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
+        n_q, keep, f = self._filter(labels, masks, excl, n_q)
         out = np.zeros(n_q if axis == 0 else self.last_n_templates, SCORE_STAT)
-        self._chk(self.lib.afis_score_stats(self.ctx, axis, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
-                                            _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q,
-                                            out.ctypes.data_as(C.c_void_p) if len(out) else None))
+        self._chk(self.lib.afis_score_stats(self.ctx, axis, *f, n_q, out.ctypes.data_as(C.c_void_p) if len(out) else None))
         return out
 
     def normalize_scores(self, offset, scale, axis: int = 0, want_scores: bool = False, n_q: Optional[int] = None):
@@ -787,13 +783,10 @@ class Matcher:
         ascending.  An entry goes to bin b = the number of edges <= its score (by rank key: the two zeros are one value); bin 0 lies below edges[0], the last bin
         reaches edges[-1]; the no-entry word and NaNs with the sign set are counted nowhere.  counts[r, j + 1:].sum() is rank_hits_filtered(edges[j])'s n_hits.  int64;
         histograms of disjoint shards add up (host/sharding.py::merge_score_histograms).  A normalised matrix is accepted: edges in z units.  The matrix stays as it is."""
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
+        n_q, keep, f = self._filter(labels, masks, excl, n_q)
         e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
         out = np.zeros((n_q if axis == 0 else self.last_n_templates, len(e) + 1), np.int64)
-        self._chk(self.lib.afis_score_histogram(self.ctx, axis, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
-                                                _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q,
-                                                len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
+        self._chk(self.lib.afis_score_histogram(self.ctx, axis, *f, n_q, len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
         return out
 
     def entries_at(self, query, rank, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
@@ -801,57 +794,47 @@ class Matcher:
         repeated or not.  -> status [n] (AFIS_POS_LISTED 0, AFIS_POS_NO_ENTRY 1), idx [n] — the GLOBAL index of entry rank[i] of the list rank_hits_filtered(-inf, cap,
         labels, masks, excl) gives its query, for every rank, not only the first 4096; -1 where the row has no more than rank[i] entries — and score [n], the cell's
         own bits (-inf unless listed).  The inverse of rank_positions: rank_positions(query, idx)["n_before"] == rank.  labels / masks / excl are rank_hits_filtered's."""
-        n_q = self.last_n_q if n_q is None else n_q
         q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); r = np.ascontiguousarray(np.asarray(rank, np.int64).reshape(-1))
         if len(q) != len(r):
             raise ValueError("one query position per rank")
         n = len(q)
-        mk, off, ent = self._filter_args(n_q, masks, excl)
+        n_q, keep, f = self._filter(labels, masks, excl, n_q)
         st = np.empty(n, np.int32); ix = np.empty(n, np.int64); sc = np.empty(n, np.float32)
-        self._chk(self.lib.afis_entries_at(self.ctx, labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
-                                           _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None, n_q, n,
-                                           _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
+        self._chk(self.lib.afis_entries_at(self.ctx, *f, n_q, n, _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
                                            _ptr(ix, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None))
         return {"status": st, "idx": ix, "score": sc}
 
     # ---- person distributions: the three calls above over enrolled persons ---------------------------------------------------------
-    def _subject_filter(self, handle, labels, masks, excl, n_q):
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
-        keep = (mk, off, ent)                                               # (the arrays live as long as the tuple the caller holds)
-        return n_q, keep, (handle[0],), (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None,
-                                         _ptr(off, C.c_int64) if off is not None else None, _ptr(ent, C.c_int64) if ent is not None else None)
-
     def subject_score_stats(self, handle, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
         """score_stats over the enrolled persons of a subjects_create handle: a person's cell is the best score among their eligible covered templates (as
         rank_subject_hits_filtered's), per query (axis 0: [n_q], the cohort of persons) or per person over the queries (axis 1: [subjects], ascending id: handle[2]).
         excl: per query a sequence of SUBJECT ids.  A person nothing covers gives the empty statistic.  AFIS_ESTATE on a normalised matrix, as score_stats."""
-        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        n_q, keep, flt = self._filter(labels, masks, excl, n_q)
         out = np.zeros(n_q if axis == 0 else len(handle[2]), SCORE_STAT)
-        self._chk(self.lib.afis_subject_score_stats(self.ctx, *h, axis, *flt, n_q, out.ctypes.data_as(C.c_void_p) if len(out) else None))
+        self._chk(self.lib.afis_subject_score_stats(self.ctx, handle[0], axis, *flt, n_q, out.ctypes.data_as(C.c_void_p) if len(out) else None))
         return out
 
     def subject_score_histogram(self, handle, edges, axis: int = 0, labels=None, masks=None, excl=None, n_q: Optional[int] = None) -> np.ndarray:
         """score_histogram over the enrolled persons of a subjects_create handle, per query (axis 0: [n_q][len(edges) + 1]) or per person (axis 1: [subjects][...],
         ascending id: handle[2]).  A person's key is the RAW ordered word of their best cell, as in rank_subject_hits: -0.0 lies below +0.0, for persons and for edges,
         so (-0.0, +0.0) are two edges.  counts[q, j + 1:].sum() is rank_subject_hits_filtered(edges[j])'s n_hits.  excl: per query a sequence of SUBJECT ids."""
-        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        n_q, keep, flt = self._filter(labels, masks, excl, n_q)
         e = np.ascontiguousarray(np.asarray(edges, np.float32).reshape(-1))
         out = np.zeros((n_q if axis == 0 else len(handle[2]), len(e) + 1), np.int64)
-        self._chk(self.lib.afis_subject_score_histogram(self.ctx, *h, axis, *flt, n_q, len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
+        self._chk(self.lib.afis_subject_score_histogram(self.ctx, handle[0], axis, *flt, n_q, len(e), _ptr(e, C.c_float) if len(e) else None, _ptr(out, C.c_int64) if out.size else None))
         return out
 
     def subject_entries_at(self, handle, query, rank, labels=None, masks=None, excl=None, n_q: Optional[int] = None):
         """entries_at over the enrolled persons of a subjects_create handle: -> status [n], subject [n] — the id of entry rank[i] of the list
         rank_subject_hits_filtered(-inf, cap, labels, masks, excl) gives query[i], for every rank; -1 where the row has no more than rank[i] persons —, score [n] and
         best_idx [n], the person's best score and the GLOBAL index of the template that holds it.  The inverse of rank_subject_positions."""
-        n_q, keep, h, flt = self._subject_filter(handle, labels, masks, excl, n_q)
+        n_q, keep, flt = self._filter(labels, masks, excl, n_q)
         q = np.ascontiguousarray(np.asarray(query, np.int32).reshape(-1)); r = np.ascontiguousarray(np.asarray(rank, np.int64).reshape(-1))
         if len(q) != len(r):
             raise ValueError("one query position per rank")
         n = len(q)
         st = np.empty(n, np.int32); sid = np.empty(n, np.int64); sc = np.empty(n, np.float32); bi = np.empty(n, np.int64)
-        self._chk(self.lib.afis_subject_entries_at(self.ctx, *h, *flt, n_q, n, _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
+        self._chk(self.lib.afis_subject_entries_at(self.ctx, handle[0], *flt, n_q, n, _ptr(q, C.c_int32) if n else None, _ptr(r, C.c_int64) if n else None, _ptr(st, C.c_int32) if n else None,
                                                    _ptr(sid, C.c_int64) if n else None, _ptr(sc, C.c_float) if n else None, _ptr(bi, C.c_int64) if n else None))
         return {"status": st, "subject": sid, "score": sc, "best_idx": bi}
 
@@ -873,13 +856,10 @@ class Matcher:
 
     # ---- link groups: the connected components rows and columns make above a decision score ----------------------------------
     def _link(self, fn, min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q):
-        n_q = self.last_n_q if n_q is None else n_q
-        mk, off, ent = self._filter_args(n_q, masks, excl)
+        n_q, keep, flt = self._filter(labels, masks, excl, n_q)
         rn = None if row_node is None else np.ascontiguousarray(np.asarray(row_node, np.int64).reshape(-1))
         if rn is not None and len(rn) != n_q:
             raise ValueError("one row_node per query")
-        flt = (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
-               _ptr(ent, C.c_int64) if ent is not None else None)
 
         def call(cg, cm):
             cnt = np.zeros(4, np.int64)
@@ -1157,27 +1137,19 @@ class Matcher:
         return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_subject_hits(self.ctx, handle[0], co, nq, mode, nc, min_score, cap, cid, nh, a, sc),
                                 case_of, cap, True)
 
-    @staticmethod
-    def _filter_ptrs(labels, mk, off, ent):
-        """_filter_args' arrays and a labels_create handle as the four leading filter arguments of the C calls."""
-        return (labels[0] if labels is not None else None, _ptr(mk, C.c_uint64) if mk is not None else None, _ptr(off, C.c_int64) if off is not None else None,
-                _ptr(ent, C.c_int64) if ent is not None else None)
-
     def rank_case_hits_filtered(self, case_of: Sequence[int], mode: int, min_score: float, cap: int, labels=None, masks=None, excl=None):
         """rank_case_hits, every column folded over the members that are ELIGIBLE for it.  labels / masks / excl are rank_hits_filtered's, per QUERY position (a case-wide
         elimination list is that list repeated for each member).  A column no member of the case is eligible for is no entry: neither counted nor listed, whatever
         min_score is; one whose eligible members all hold -1 is CASE_SUM's -1, listed when min_score <= -1."""
         co = np.asarray(case_of, np.int64).reshape(-1)
-        mk, off, ent = self._filter_args(len(co), masks, excl)
-        f = self._filter_ptrs(labels, mk, off, ent)
+        _, keep, f = self._filter(labels, masks, excl, len(co))
         return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_hits_filtered(self.ctx, *f, co, nq, mode, nc, min_score, cap, cid, nh, a, sc), co, cap, False)
 
     def rank_case_subject_hits_filtered(self, handle, case_of: Sequence[int], mode: int, min_score: float, cap: int, labels=None, masks=None, excl=None):
         """rank_case_subject_hits over the eligible members: a member's value is the person's best score among their covered templates that are eligible for that
         member; excl: per query a sequence of SUBJECT ids.  A person no member is eligible for is neither counted nor listed."""
         co = np.asarray(case_of, np.int64).reshape(-1)
-        mk, off, ent = self._filter_args(len(co), masks, excl)
-        f = self._filter_ptrs(labels, mk, off, ent)
+        _, keep, f = self._filter(labels, masks, excl, len(co))
         return self._case_lists(lambda co, nq, nc, cid, nh, a, sc: self.lib.afis_rank_case_subject_hits_filtered(self.ctx, handle[0], *f, co, nq, mode, nc, min_score, cap, cid, nh, a, sc),
                                 co, cap, True)
 
@@ -1201,8 +1173,7 @@ class Matcher:
         labels / masks / excl are rank_hits_filtered's, per QUERY position of the last search (n_q defaults as there); a template no query is eligible for has
         n_hits 0 and all padding."""
         n = self.last_n_templates if n_templates is None else n_templates
-        mk, off, ent = self._filter_args(self.last_n_q if n_q is None else n_q, masks, excl)
-        f = self._filter_ptrs(labels, mk, off, ent)
+        _, keep, f = self._filter(labels, masks, excl, n_q)
         return self._latent_lists(lambda nt, nh, li, sc: self.lib.afis_rank_latent_hits_filtered(self.ctx, *f, nt, min_score, cap, latent_base, nh, li, sc), n, cap)
 
     def rank_latents(self, k: int, latent_base: int = 0, n_templates: Optional[int] = None):

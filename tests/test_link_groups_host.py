@@ -59,11 +59,13 @@ def test_the_kernels_and_the_host_unit_are_product_objects():
     for unit in ("afis_link.cpp", "link_groups_check.cpp"):
         assert '#include "link_groups.h"' in open(os.path.join(CSRC, unit)).read(), unit   # one text for the kernels, the host unit and the check program
     hdr = open(os.path.join(CSRC, "link_groups.h")).read()
-    assert re.findall(r'#include\s+"([^"]+)"', hdr) == ["score_order.h"]    # the standard library and score_order.h only
+    assert re.findall(r'#include\s+"([^"]+)"', hdr) == ["column_names.h", "score_order.h"]   # the standard library, score_order.h and the column names' view only ...
+    assert not re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, "column_names.h")).read())   # ... which is the standard library alone
     dev = open(os.path.join(CSRC, "afis_device.h")).read()
     assert re.search(r"kLinkChunkScalar\s*=\s*256,\s*kLinkChunkVec\s*=\s*1024", dev) and re.search(r"kFilterRows\s*=\s*8", dev)   # what tests/test_gpu_link_groups.py sizes its cases by
     link = open(os.path.join(CSRC, "afis_link.cpp")).read()
     assert "FilterPass" in link and "check_filtered(" in link and "link_arrange(" in link   # the filtered calls' checks and filter pass, not a second definition
+    assert "MatrixCall mc{ctx, who, subj, kTemplateCells, {ctx, labels, masks, subj ? no_cells : pairs, subj != nullptr}}" in link and "queue_cells(" not in link   # ... the FilterPass the matrix calls' driver holds and queues
 
 
 def test_the_options_are_documented():

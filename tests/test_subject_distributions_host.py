@@ -86,8 +86,13 @@ def test_the_kernels_and_the_host_units_are_product_objects():
         assert '#include "score_hist.h"' in open(os.path.join(CSRC, unit)).read(), unit
     dist = open(os.path.join(CSRC, "afis_distribution.cpp")).read(); norm = open(os.path.join(CSRC, "afis_normalize.cpp")).read()
     # no second definition of eligibility or of a person's best: the pre-passes are the filtered subject hit lists', queued in one place
-    assert dist.count("queue_subject_best(") == 1 and dist.count("queue_drop_subjects(") == 1 and "queue_subject_best(" not in norm and "queue_subject_keys(" in norm
-    assert "FilterPass fp{ctx, labels, masks, pairs, subj != nullptr}" in dist and "FilterPass fp{ctx, labels, masks, pairs, subj != nullptr}" in norm
+    # ... by the matrix calls' driver (MatrixCall, afis_hits.cpp), which every person distribution call asks for the person cells and hands the filter as the hit lists do
+    assert dist.count("queue_subject_best(") == 1 and dist.count("queue_drop_subjects(") == 1 and "queue_subject_best(" not in norm and "queue_subject_keys(" not in norm
+    hits = open(os.path.join(CSRC, "afis_hits.cpp")).read()
+    drv = hits[hits.index("int MatrixCall::begin("):]
+    assert "if (cells == kPersonKeys) return queue_subject_keys(ctx, subj, fp);" in drv[:drv.index("\n}\n")] and hits.count("queue_subject_keys(") == 1
+    call = "MatrixCall mc{ctx, who, subj, subj ? kPersonKeys : kTemplateCells, {ctx, labels, masks, pairs, subj != nullptr}}"
+    assert dist.count(call) == 2 and norm.count(call) == 1 and "FilterPass fp{" not in dist + norm
 
 
 def test_the_options_and_the_recipes_are_documented():
