@@ -397,6 +397,7 @@ int afis_count_before(afis_ctx* ctx, afis_labels* labels /*or NULL*/, const uint
  *                         every ranking call reads them and takes min_score in z units; scores_out, where given, receives the normalised matrix in the search's
  *                         column order.  The matrix is then marked normalised: both calls refuse it with AFIS_ESTATE, and the next search clears the mark.  n_q must
  *                         be the last search's.  Normalising along both axes of one matrix is not offered
+ *                         (by this call alone: the kept matrices below keep the raw matrix, recall it for the other axis and fuse the two halves)
  * The three helpers are host arithmetic on statistics — no context, no device:
  * afis_score_stat_add     acc += other, field by field with carry, min of mins and max of maxes; AFIS_EINVAL, acc unchanged, where n would pass 2^27
  * afis_score_stat_remove  takes one valued cell's contribution out of acc exactly, so that trimming a cohort by its best k cells is integer arithmetic over the top-k a
@@ -1415,6 +1416,72 @@ int afis_search_prints_cascade(afis_ctx* ctx, const int64_t* idx /*[n_q], GLOBAL
                                int64_t* n_kept /*[n_q] or NULL*/, int64_t* kept_idx /*[n_q][keep] or NULL*/,
                                float* kept_parts /*[n_q][keep][2] or NULL*/);
 
+/* Kept matrices: the last search's matrix as an object — kept, read, recalled and fused on the device.
+ * Why      every ranking and analysis call reads THE LAST search's matrix, the next search overwrites it and the normalisation rewrites it.  The raw lists after a
+ *          z-normalisation, a normalisation along the other axis, the mean of two normalisations (S-norm), a symmetric print score (a -> b fused with b -> a) and
+ *          the fusion of two searches of the same latents over the same columns each cost a second full search, or [n_q][columns] floats over the bus and back.
+ * What     a handle holds a device copy of a matrix with its RECORD: n_q, columns, the subset it was scored over (or the whole shard), the gallery epoch and the
+ *          normalised mark.  Kept matrices are plain allocations, as subsets are: option "matrix_device_bytes" (read-only) is what the live ones hold.
+ *   STALE        a handle whose gallery epoch has passed (afis_gallery_commit after afis_gallery_reopen, afis_gallery_remove, afis_gallery_commit_at) or whose
+ *                subset has been freed (afis_subset_free marks the context's kept matrices of that subset).  Reading, recalling and fusing a stale handle is
+ *                AFIS_ESTATE, with a message that names the edit; the info call still answers, with stale = 1; freeing always works
+ *   THE CELL RULE  (csrc/matrix_fuse.h, one definition for host and device) for the operands k = 0 .. n - 1 in argument order, c_k the cell word — the one across
+ *                the diagonal where the operand is read transposed —, v_k its float, w_k its weight (1.0 where weights is NULL):
+ *                  there_k   c_k is not the no-entry word 0xffffffff
+ *                  part_k    raw matrices: there_k and the sign bit of v_k + 0.0f clear — the case lists' rule: the -1 of an empty template, every negative value
+ *                            and a NaN with the sign set stay out.  Normalised matrices: there_k — a negative z-score is a value, and every outside cell became
+ *                            no entry when the matrix was normalised
+ *                  no operand is there                                        -> no entry
+ *                  AFIS_FUSE_REQUIRE_ALL and some operand is not there        -> no entry
+ *                  otherwise no operand takes part (raw matrices only), or with AFIS_FUSE_REQUIRE_ALL some operand that is there does not take part -> -1.0f
+ *                  AFIS_FUSE_SUM   double acc = +0.0; for every k that takes part, in order: acc = acc + w_k * (double)v_k — the product and the sum each rounded
+ *                            in fp64, no fused multiply-add; the result is (float)acc.  A sum that is no number is the one word 0x7fc00000: which NaN an
+ *                            operation produces (the sign of inf - inf and of 0 x inf, what survives of a payload) differs between processors, so the rule names
+ *                            the word
+ *                  AFIS_FUSE_MAX / AFIS_FUSE_MIN   the v_k of greatest / least rank key (the ordered word of v_k + 0.0f) among those that take part; the first
+ *                            operand that holds it keeps its bits
+ * afis_matrix_keep    copies the last search's matrix, whatever left it, and its record into a new handle, on the context's stream.  The checks are the ranking
+ *                     calls' (a committed gallery, a matrix still there and of the shard as it stands: AFIS_ESTATE otherwise); the matrix is neither written nor
+ *                     invalidated, as by afis_score_stats.  An empty shard or n_q == 0 gives a valid handle of zero cells and queues nothing.  Option
+ *                     "matrix_keep_us" (read-only): the device time of the copy
+ * afis_matrix_free    releases a handle; NULL and a handle that is not live are ignored.  afis_destroy releases the handles that are left
+ * afis_matrix_info    fills *out for any live handle, stale or not
+ * afis_matrix_read    rows row0 .. row0 + n_rows - 1 of a kept matrix into out [n_rows][columns], the columns in the order of the search's scores output (for a
+ *                     subset the caller's column order).  AFIS_EINVAL for rows outside the matrix or a null out
+ * afis_matrix_recall  copies the kept matrix back as the last search's matrix and restores its record, the normalised mark included: after afis_normalize_scores and
+ *                     a recall of the raw matrix afis_score_stats works again, and the matrix may be normalised along the other axis.  It needs no last search.
+ *                     The handle stays usable
+ * afis_matrix_fuse    applies the cell rule to 1 <= n <= AFIS_FUSE_OPERANDS_MAX operands.  All of one n_q and one columns, all over the same subset or all over the
+ *                     whole shard, all raw or all normalised — AFIS_EINVAL otherwise.  transposed[k] != 0 reads operand k transposed: only where n_q == columns, and
+ *                     the CALLER vouches that row i and column i name the same print (a print search of a set over the same set, in one order; a subset must
+ *                     have been listed in ascending order).  weights belong to AFIS_FUSE_SUM — NULL for the other modes — and each must be finite.  Every argument
+ *                     error is reported before anything is queued, with the last matrix unchanged and rankable.  The same handle may appear more than once:
+ *                     (A, A) with transposed = (0, 1) under AFIS_FUSE_MIN is the symmetric score min(a -> b, b -> a).  After AFIS_OK the result IS the last
+ *                     search's matrix, with the operands' record: every ranking call reads it (a fused normalised matrix takes min_score in z units), and
+ *                     scores_out, where given, receives it in the search's column order.  Option "matrix_fuse_us" (read-only): the device time of the launches
+ * How      csrc/afis_matrix.cpp, csrc/matrix_fuse.hip.  k_matrix_fuse: a thread owns one column of a row — four adjacent ones as one 16-byte word where columns
+ *          % 4 == 0 —, the operands' pointers and weights travel in the kernel's argument segment (scalar loads), the loads of four operands are in flight
+ *          together; no atomic, no LDS, every output word written once.  The result is built in the spare of the two score buffers and swapped in, as
+ *          afis_search_eligible's and afis_normalize_scores' are.  A transposed operand goes through k_transpose_scores into scratch first, once per distinct handle.
+ * Shards: every untransposed call is per rank, without an exchange: a rank's columns are its shard's, keep / recall / fuse the same operands on every rank and merge
+ *          the ranking calls' lists as before.  S-norm needs the merged statistics first.
+ * These calls do not give: fusing matrices of different column sets (a subset's columns into a whole-shard matrix); a transposed operand across shards (row i's mate
+ *          column lies on another rank) or over a subset listed out of order; the match CLI. */
+typedef struct afis_matrix afis_matrix;
+#define AFIS_FUSE_SUM 0
+#define AFIS_FUSE_MAX 1
+#define AFIS_FUSE_MIN 2
+#define AFIS_FUSE_REQUIRE_ALL 4        /* or-ed into mode */
+#define AFIS_FUSE_OPERANDS_MAX 16
+typedef struct { int32_t n_q; int32_t normalized; int64_t columns; int32_t over_subset; int32_t stale; } afis_matrix_desc;
+int  afis_matrix_keep  (afis_ctx* ctx, afis_matrix** out);
+void afis_matrix_free  (afis_ctx* ctx, afis_matrix* m);
+int  afis_matrix_info  (afis_ctx* ctx, const afis_matrix* m, afis_matrix_desc* out);
+int  afis_matrix_read  (afis_ctx* ctx, const afis_matrix* m, int row0, int n_rows, float* out /*[n_rows][columns]*/);
+int  afis_matrix_recall(afis_ctx* ctx, const afis_matrix* m);
+int  afis_matrix_fuse  (afis_ctx* ctx, const afis_matrix* const* ms /*[n]*/, const double* weights /*[n] or NULL*/,
+                        const uint8_t* transposed /*[n] or NULL*/, int n, int mode, float* scores_out /*[n_q][columns] or NULL*/);
+
 /* afis_get_timing2 copies min(struct_size, sizeof(afis_timing)) bytes: pass sizeof(afis_timing) of the header the caller was compiled
  * against, so that a library with a longer struct never writes past the caller's.  afis_get_timing (kept for callers of the round-2
  * header) fills only the fields up to `pairs` (48 bytes, the struct of that header); the fields after it need afis_get_timing2. */
@@ -1481,6 +1548,9 @@ int afis_set_option(afis_ctx* ctx, const char* name, int64_t value);
  * first; then the counters' memset, k_link_init, for persons in mutual mode k_link_first_cols and k_link_row_cols, k_link_scan, k_link_flatten and k_link_compact), from
  * HIP events around them; 0 when that call queued nothing.
  * "link_d2h_bytes" (read-only): the bytes that call returned from the device: 32 of counters, then 8 per node in a group of two or more; 0 when that call queued nothing.
+ * "matrix_device_bytes" (read-only): the device bytes held by the context's live kept matrices (0 when there is none).  "matrix_keep_us" (read-only): the device time
+ * of the last afis_matrix_keep's copy, from HIP events around it; 0 when that call queued nothing.  "matrix_fuse_us" (read-only): the device time of the last
+ * afis_matrix_fuse's launches (k_transpose_scores once per distinct transposed operand, then k_matrix_fuse), from HIP events around them; 0 when that call queued nothing.
  * "corr_pairs_per_launch" (settable, 1 .. 1 048 576; default AFIS_CORR_PAIRS_PER_LAUNCH): the pairs of one chunk of afis_correspondences_pairs at most — about 5.8 KB of
  * device memory and 2.9 KB of pinned host memory each.  "correspondences_us" (read-only): the device time of the last afis_correspondences_pairs' or afis_correspondences'
  * launches (per chunk and launch group k_minu_cands<true> and k_graph_minutiae in its pair form), from HIP events around every chunk's, summed; 0 when that call queued nothing.

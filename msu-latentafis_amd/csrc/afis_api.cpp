@@ -111,6 +111,9 @@ void afis_destroy(afis_ctx* c)
     c->subject_sets.clear();
     for (afis_labels* lb : c->label_sets) release_labels(lb);                // label handles that are still live
     c->label_sets.clear();
+    for (afis_matrix* mx : c->matrices) release_matrix(mx);                  // kept matrices that are still live
+    c->matrices.clear();
+    c->fuse_t.release();
     free_gallery_dev(c);
     c->out_perm.release(); c->subj_best.release(); c->subj_out.release(); c->hits_out.release(); c->scores_t.release(); c->case_fused.release(); c->case_tab.release(); c->filt_scores.release(); c->filt_tab.release(); c->pos_tab.release(); c->pos_out.release(); c->stat_tab.release(); c->stat_out.release(); c->hist_tab.release(); c->sel_tab.release(); c->sel_out.release(); c->subj_keys.release(); c->link_tab.release(); c->link_out.release(); c->pair_buf.release(); c->pair_tex_slab.release(); c->elig_scores.release(); c->wt_tab.release(); c->casc_buf.release(); c->casc_slab.release();
     c->codewords.release(); c->table.release(); c->lut.release(); c->rm_val.release(); c->rm_arg.release(); c->rm_cv.release(); c->rm_n.release();
@@ -199,7 +202,10 @@ int afis_get_option(const afis_ctx* ctx, const char* name, int64_t* value)
     else if (n == "subject_entries_at_us") *value = ctx->subject_entries_at_us;        // read-only: device time of the last afis_subject_entries_at's launches
     else if (n == "link_groups_us") *value = ctx->link_groups_us;                      // read-only: device time of the last afis_link_groups' / afis_link_subject_groups' launches
     else if (n == "link_d2h_bytes") *value = ctx->link_d2h_bytes;                      // read-only: bytes that call returned from the device (the counts, then 8 per linked node)
-    else if (n == "rank_positions_us") *value = ctx->rank_positions_us;                // read-only: device time of the last afis_rank_positions' / afis_rank_subject_positions' / afis_count_before's launches
+    else if (n == "matrix_device_bytes") *value = (int64_t)matrix_device_bytes(ctx);    // read-only: device bytes held by the live kept matrices (afis_matrix_keep)
+    else if (n == "matrix_keep_us") *value = ctx->matrix_keep_us;                      // read-only: device time of the last afis_matrix_keep's copy
+    else if (n == "matrix_fuse_us") *value = ctx->matrix_fuse_us;                      // read-only: device time of the last afis_matrix_fuse's launches
+    else if (n == "rank_positions_us") *value = ctx->rank_positions_us;               // read-only: device time of the last afis_rank_positions' / afis_rank_subject_positions' / afis_count_before's launches
     else if (n == "filter_us") *value = ctx->filter_us;                                // read-only: ... of which everything before k_rank_hits (the filter pass; for subjects the maxima; the drops)
     else if (n == "eligible_classes") *value = ctx->eligible_classes;                  // read-only: classes (distinct mask triples) of the last afis_search_eligible
     else if (n == "eligible_expand_us") *value = ctx->eligible_expand_us;              // read-only: device time of that call's k_expand_rows launches, summed over the classes

@@ -1,5 +1,5 @@
 // afis_ctx.h — the host side's internal state and helpers, shared by its translation units: afis_api.cpp (context, options, timing), afis_gallery.cpp (staging,
-// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, the driver and checks every hit-list call goes through, and the driver of every other call that reads the last search's matrix in place), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_evidence.cpp (the evidence calls of a pair list: the texture scorer's correspondences, the exact moments of every scorer's survivors and the fit they give; what they ask of the pair driver), afis_print_pairs.cpp (pair scoring, correspondence export and the evidence calls for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
+// container, commit), afis_search.cpp (query groups, the launch sequence of a search, the minutiae stage every driver of the search family sizes and queues, the query handle's rule, all-templates mode), afis_corr.cpp (correspondence export of a pair list: what it asks of the pair driver), afis_pairs.cpp (the driver every pair-list call goes through, the texture stage of a pair table, and pair scoring: the fused scores and parts of a pair list), afis_subset.cpp (subset search), afis_subjects.cpp (subject rank lists), afis_hits.cpp (hit lists, the driver and checks every hit-list call goes through, and the driver of every other call that reads the last search's matrix in place), afis_cases.cpp (case lists), afis_filter.cpp (labels, filtered hit lists), afis_positions.cpp (rank positions: where a named template or person stands), afis_normalize.cpp (cohort statistics of the last search's matrix, its z-normalisation, and the host arithmetic on statistics), afis_distribution.cpp (score distributions of that matrix: per-row histograms and the entry at any rank, of templates and of enrolled persons — whose statistics are afis_normalize.cpp's too), afis_link.cpp (link groups: the connected components rows and columns of that matrix make above a decision score), afis_eligible.cpp (eligible search: the classes of a batch over temporary sub-shards), afis_weighted.cpp (weighted search: any set of a latent's templates, folded on the device), afis_prints.cpp (print search: resident prints as queries, built on the device), afis_evidence.cpp (the evidence calls of a pair list: the texture scorer's correspondences, the exact moments of every scorer's survivors and the fit they give; what they ask of the pair driver), afis_print_pairs.cpp (pair scoring, correspondence export and the evidence calls for resident print pairs: temporary print handles in batches, the pair drivers over them), afis_reverse.cpp (reverse search: reserved query handles, column hit lists), afis_cascade.cpp (cascade search: the minutiae scorers for every cell, the texture scorer for the kept ones; and the driver every cascade call goes through), afis_cascade_eligible.cpp (the cascade over a live subset's columns, and per latent over the templates it is eligible for: that driver over sub-shards), afis_print_cascade.cpp (print cascade: resident prints as that driver's queries, and the kernels that differ), afis_matrix.cpp (kept matrices: the last search's matrix kept, read, recalled and fused on the device) and afis_taps.cpp (parity taps and the direct ADC kernels' host side, test library only).
 // The order of scores — the ordered word, the two keys made of it, the composites — is score_order.h's (through afis_device.h), shared with the kernels.
 // Not part of the ABI: include/afis_matcher.h is.
 #pragma once
@@ -139,6 +139,14 @@ struct afis_labels {
 // touched it or what it refers to: afis_rank_subjects ranks it.  Set by a search that succeeded, cleared by drain_abandoned at the top of every entry point that queues work.
 struct LastSearch { bool valid = false; int n_q = 0; int64_t G = 0; const afis_subset* sub = nullptr; uint64_t gallery_epoch = 0; bool normalized = false; };   // (gallery_epoch: the shard the matrix was scored against; normalized: afis_normalize_scores has replaced the scores by z-scores — that call and afis_score_stats refuse the matrix, every search starts a record without the flag)
 
+// A kept matrix (afis_matrix_keep): a device copy of the last search's matrix as it stood, with its record.  rec.valid is unused; rec.sub is cleared — and sub_freed
+// set — when the subset it names is freed (afis_subset_free).
+struct afis_matrix {
+    DevBuf d;                            // [rec.n_q][rec.G] floats in the order of the shard searched; nothing where there is no cell
+    LastSearch rec;
+    bool over_subset = false, sub_freed = false;
+};
+
 struct afis_ctx : Shard {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -191,6 +199,9 @@ struct afis_ctx : Shard {
     DevBuf link_tab, link_out;           // afis_link_groups / afis_link_subject_groups: the call's words (afis_link.cpp has the layout: counters, parent | label | size [n_nodes] int32, the subject form's first_col, the uploaded tables) and the (node, label) pairs of the linked nodes
     int64_t link_groups_us = 0;          // option link_groups_us (read-only): device time of the last such call's launches (the filter pass, the counters' memset, k_link_init, the subject form's two column kernels in mutual mode, k_link_scan, k_link_flatten, k_link_compact)
     int64_t link_d2h_bytes = 0;          // option link_d2h_bytes (read-only): bytes that call returned from the device: 32 of counters, then 8 per linked node
+    std::vector<afis_matrix*> matrices;  // live kept matrices (afis_matrix_keep .. afis_matrix_free; afis_destroy releases what is left); option matrix_device_bytes (read-only) is what they hold
+    DevBuf fuse_t;                       // afis_matrix_fuse: its transposed operands, one [n][n] matrix per distinct handle read transposed, each on a 256-byte boundary (the result is built in elig_scores and swapped in as afis_search_eligible's is)
+    int64_t matrix_keep_us = 0, matrix_fuse_us = 0;   // options of those names (read-only): device time of the last afis_matrix_keep's copy / the last afis_matrix_fuse's launches (k_transpose_scores per distinct transposed operand, k_matrix_fuse), HIP events around them
     int corr_pairs_per_launch = kCorrPairsPerLaunch;   // option corr_pairs_per_launch: pairs per chunk of that call at most
     int64_t correspondences_us = 0;      // option correspondences_us (read-only): device time of the last afis_correspondences_pairs' / afis_correspondences' launches (HIP events around every chunk's, summed)
     DevBuf pair_buf, pair_tex_slab;      // every pair-list call (PairCall below has the layout), grown on demand: one chunk's candidate lists, survivors, counts, parts and tables — about 5.8 KB per pair of option corr_pairs_per_launch for afis_correspondences_pairs; with afis_score_pairs' dense row maxima and scores kScorePairBytes + 8 lt_pad per pair of option score_pairs_per_launch —, and the texture list kernel's slab for a chunk's launches of afis_score_pairs
@@ -599,6 +610,10 @@ ColumnNames column_names(const afis_ctx* ctx, const afis_subjects* s) __attribut
 // afis_normalize.cpp
 // order[t]: the caller's column of position t of the last search's matrix — a subset listed out of order stands in ascending global index order on the device; empty: the identity
 std::vector<int32_t> column_order(const LastSearch& ls) __attribute__((visibility("hidden")));
+// afis_matrix.cpp
+void release_matrix(afis_matrix* m);                   // its device buffer and the handle itself
+size_t matrix_device_bytes(const afis_ctx* ctx);       // option matrix_device_bytes: what the live kept matrices hold on the device
+void matrices_lose_subset(afis_ctx* ctx, const afis_subset* s);   // afis_subset_free: the context's kept matrices that were scored over s are stale from here on
 // afis_cascade.cpp
 // One cascade call, whatever its queries are: the minutiae stage for every cell, the selection of the `keep` best columns per query, the texture scorer for the kept
 // cells.  The driver owns the launch sequence, the layout of casc_buf and of the pinned buffer, the times and the ends of the entry points; afis_search_cascade and

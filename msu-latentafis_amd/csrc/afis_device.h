@@ -383,6 +383,10 @@ hipError_t launch_case_fuse_subjects(const unsigned long long* best, int S, cons
 // member gets 0xffffffff (no entry), one whose folded members all hold -1 is kCaseSum's -1.0f
 hipError_t launch_case_fuse_eligible(const float* filtered, int G, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
 hipError_t launch_case_fuse_subjects_eligible(const unsigned long long* best, int S, const int32_t* case_off, const int32_t* member, int n_cases, int mode, float* fused, hipStream_t stream);
+// afis_matrix_fuse (matrix_fuse.hip; the cell rule: matrix_fuse.h): out [n_q][columns] = the fold of the n <= 16 matrices src[k] of that shape, in argument order, with
+// weights [n] (NULL: 1.0 each; kFuseSum only) under mode (kFuseSum / kFuseMax / kFuseMin, kFuseRequireAll or-ed in); normalized: the operands hold z-scores.  src and
+// weights are HOST arrays: they travel in the kernel's argument segment.  Every word of out is written once; out is none of the operands
+hipError_t launch_matrix_fuse(const float* const* src, const double* weights, int n, int mode, int normalized, int n_q, int columns, float* out, hipStream_t stream);
 // afis_rank_hits_filtered / afis_rank_subject_hits_filtered (hit_filter.hip): filtered [n_q][G] = scores [n_q][G] with every cell whose column's label fails the row's
 // masks [n_q][3] (any_of, all_of, none_of) replaced by the word 0xffffffff, which launch_rank_hits never counts and launch_subject_best turns into a composite that is
 // never counted; labels [templates of the resident shard], the label of position p is labels[p], or labels[d_global[p] - index_base] for a subset's matrix.  A thread

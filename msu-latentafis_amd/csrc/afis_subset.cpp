@@ -144,6 +144,7 @@ void afis_subset_free(afis_ctx* ctx, afis_subset* s)
         (void)hipSetDevice(ctx->device);
         (void)quiesce(ctx, "afis_subset_free");                             // a search that timed out may still read the sub-shard: bounded wait, as every gallery edit (past its deadline hipFree itself waits for the device)
         ctx->subsets.erase(std::remove(ctx->subsets.begin(), ctx->subsets.end(), s), ctx->subsets.end());
+        matrices_lose_subset(ctx, s);                                       // kept matrices of this subset (afis_matrix_keep) are stale from here on
     }
     release_subset(s);
 }

@@ -70,6 +70,12 @@ assert SCORE_STAT.itemsize == 48
 CORR_MOMENTS = np.dtype([(f, "<i8") for f in ("n", "slx", "sly", "srx", "sry", "dot", "cross", "ll", "rr")])
 assert CORR_MOMENTS.itemsize == 72
 TEX_CORR_MAX = 200
+FUSE_SUM, FUSE_MAX, FUSE_MIN, FUSE_REQUIRE_ALL, FUSE_OPERANDS_MAX = 0, 1, 2, 4, 16      # AFIS_FUSE_*: afis_matrix_fuse's modes, its flag and its operand count
+
+
+class MatrixDesc(C.Structure):
+    """afis_matrix_desc"""
+    _fields_ = [("n_q", C.c_int32), ("normalized", C.c_int32), ("columns", C.c_int64), ("over_subset", C.c_int32), ("stale", C.c_int32)]
 
 EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis_destroy", "afis_last_error", "afis_gallery_add", "afis_gallery_add_dat", "afis_gallery_add_dat_batch", "afis_gallery_reserve",
            "afis_gallery_add_packed", "afis_gallery_commit", "afis_gallery_size", "afis_gallery_reopen", "afis_gallery_remove", "afis_gallery_commit_at", "afis_gallery_export", "afis_gallery_save", "afis_gallery_load",
@@ -80,6 +86,7 @@ EXPORTS = ["afis_create", "afis_create_from_codebook", "afis_device_info", "afis
            "afis_labels_create", "afis_labels_free", "afis_rank_hits_filtered", "afis_rank_subject_hits_filtered",
            "afis_rank_case_hits_filtered", "afis_rank_case_subject_hits_filtered", "afis_rank_latent_hits_filtered", "afis_search_eligible", "afis_search_weighted", "afis_search_prints",
            "afis_rank_positions", "afis_rank_subject_positions", "afis_count_before", "afis_score_stats", "afis_normalize_scores", "afis_score_stat_add", "afis_score_stat_remove", "afis_score_stat_moments", "afis_score_histogram", "afis_entries_at", "afis_subject_score_stats", "afis_subject_score_histogram", "afis_subject_entries_at", "afis_link_groups", "afis_link_subject_groups",
+           "afis_matrix_keep", "afis_matrix_free", "afis_matrix_info", "afis_matrix_read", "afis_matrix_recall", "afis_matrix_fuse",
            "afis_correspondences_pairs", "afis_score_pairs", "afis_score_print_pairs", "afis_correspondences_print_pairs",
            "afis_texture_correspondences_pairs", "afis_texture_correspondences_print_pairs", "afis_pair_alignments", "afis_print_pair_alignments", "afis_corr_moments_add", "afis_alignment_fit", "afis_search_cascade", "afis_search_prints_cascade", "afis_search_cascade_subset", "afis_search_cascade_eligible",
            "afis_search_resident", "afis_queries_free", "afis_correspondences", "afis_match_all_templates", "afis_pq_encode", "afis_encode_rolled_dat", "afis_pq_train", "afis_pq_train_init_points", "afis_codebook_write", "afis_get_timing", "afis_get_timing2", "afis_set_option", "afis_get_option"]
@@ -199,6 +206,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         u64p = C.POINTER(C.c_uint64)
         lib.afis_link_groups.argtypes = [vp, vp, u64p, i64p, i64p, C.c_int, i64p, C.c_float, C.c_int, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, i64p, i64p]
         lib.afis_link_subject_groups.argtypes = [vp, vp, vp, u64p, i64p, i64p, C.c_int, i64p, C.c_float, C.c_int, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, i64p, i64p]
+    if hasattr(lib, "afis_matrix_keep"):                                # kept matrices; absent from older builds compared by tools/lib_ab.py
+        lib.afis_matrix_keep.argtypes = [vp, C.POINTER(vp)]
+        lib.afis_matrix_free.argtypes = [vp, vp]; lib.afis_matrix_free.restype = None
+        lib.afis_matrix_info.argtypes = [vp, vp, C.POINTER(MatrixDesc)]
+        lib.afis_matrix_read.argtypes = [vp, vp, C.c_int, C.c_int, fp]
+        lib.afis_matrix_recall.argtypes = [vp, vp]
+        lib.afis_matrix_fuse.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int, C.c_int, fp]
     lib.afis_correspondences.argtypes = [vp, vp, i64p, C.c_int, i32p, C.POINTER(C.c_int16)]
     if hasattr(lib, "afis_correspondences_pairs"):                      # the pair-list export; absent from older builds compared by tools/lib_ab.py
         lib.afis_correspondences_pairs.argtypes = [vp, vp, C.c_int64, i32p, i64p, i32p, C.POINTER(C.c_int16), fp]
@@ -894,6 +908,58 @@ class Matcher:
         first column by ascending global index."""
         return self._link(lambda f, nq, rn, ms, md, cg, cm, *out: self.lib.afis_link_subject_groups(self.ctx, handle[0], *f, nq, rn, ms, md, cg, cm, *out),
                           min_score, mode, row_node, labels, masks, excl, cap_groups, cap_members, n_q)
+
+    # ---- kept matrices: the last search's matrix kept, read, recalled and fused on the device ------------------------------
+    def matrix_keep(self):
+        """A device copy of the LAST search's matrix with its record (n_q, columns, subset, gallery epoch, normalised mark) -> a handle for the calls below.  The
+        matrix stays as it is.  Free it with matrix_free; close() releases what is left."""
+        h = C.c_void_p()
+        self._chk(self.lib.afis_matrix_keep(self.ctx, C.byref(h)))
+        return h
+
+    def matrix_free(self, handle):
+        self.lib.afis_matrix_free(self.ctx, handle)
+
+    def matrix_info(self, handle) -> dict:
+        """-> {"n_q", "normalized", "columns", "over_subset", "stale"}; answers for a stale handle too."""
+        d = MatrixDesc()
+        self._chk(self.lib.afis_matrix_info(self.ctx, handle, C.byref(d)))
+        return {"n_q": d.n_q, "normalized": bool(d.normalized), "columns": d.columns, "over_subset": bool(d.over_subset), "stale": bool(d.stale)}
+
+    def matrix_read(self, handle, row0: int = 0, n_rows: Optional[int] = None) -> np.ndarray:
+        """Rows row0 .. row0 + n_rows - 1 (default: all from row0 on) of a kept matrix -> [n_rows][columns] float32, the columns in the order of the search's scores."""
+        info = self.matrix_info(handle)
+        n_rows = info["n_q"] - row0 if n_rows is None else n_rows
+        out = np.empty((max(n_rows, 0), info["columns"]), np.float32)
+        self._chk(self.lib.afis_matrix_read(self.ctx, handle, row0, n_rows, _ptr(out, C.c_float) if out.size else None))
+        return out
+
+    def matrix_recall(self, handle):
+        """The kept matrix becomes the last search's matrix again, record and normalised mark included; the handle stays usable."""
+        self._chk(self.lib.afis_matrix_recall(self.ctx, handle))
+        info = self.matrix_info(handle)
+        self.last_n_q = info["n_q"]; self.last_n_templates = info["columns"]
+
+    def matrix_fuse(self, handles, mode: int = FUSE_SUM, weights=None, transposed=None, want_scores: bool = False):
+        """The kept matrices `handles` (1 .. 16, all of one shape, column set and kind) folded cell by cell in argument order — FUSE_SUM (fp64, with weights),
+        FUSE_MAX, FUSE_MIN, FUSE_REQUIRE_ALL or-ed in — into the last search's matrix, which every ranking call then reads.  transposed[k] true reads operand k
+        transposed (square matrices whose row i and column i are the same print).  -> the fused matrix [n_q][columns] if want_scores, else None."""
+        hs = list(handles)
+        n = len(hs)
+        arr = (C.c_void_p * max(n, 1))(*[h if isinstance(h, C.c_void_p) else C.c_void_p(h) for h in hs])
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+        t = None if transposed is None else np.ascontiguousarray(np.asarray(transposed).reshape(-1) != 0).astype(np.uint8)
+        if (w is not None and len(w) != n) or (t is not None and len(t) != n):
+            raise ValueError("one weight and one transposed flag per operand")
+        out = None
+        if want_scores and 1 <= n <= FUSE_OPERANDS_MAX:
+            info = self.matrix_info(hs[0])
+            out = np.empty((info["n_q"], info["columns"]), np.float32)
+        self._chk(self.lib.afis_matrix_fuse(self.ctx, arr, _ptr(w, C.c_double) if w is not None and n else None, _ptr(t, C.c_uint8) if t is not None and n else None, n, mode,
+                                            _ptr(out, C.c_float) if out is not None and out.size else None))
+        info = self.matrix_info(hs[0])
+        self.last_n_q = info["n_q"]; self.last_n_templates = info["columns"]
+        return out
 
     # ---- eligible search: only the pairs a latent is eligible for are scored -----------------------------------------
     def search_eligible(self, latents: Sequence[FPTemplate], labels, masks, want_scores: bool = True):
